@@ -6,8 +6,14 @@ One "step" = one full ``MarigoldDepthPipeline.__call__`` on one synthetic 768x76
 members, on-device ensembling, D2H of the final [768,768] fp32 map (color_map=None, like
 script/depth/infer.py).  The image is already resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (headline fields only).  ``--full`` adds what the
+line's other fields need: the calibration before the warm-up, one-at-a-time latency, the per-kernel roofline, the
+ensembling / gather timing and the CPU baseline.  ``--dump-outputs DIR`` writes the last timed map's output arrays as
+DIR/<name>.npy (float32); every map draws its noise from its own generator seeded with 2024, so the same arguments
+give the same inputs on every run.
 
 N > 1: one process per GPU; the E members of every map are sharded over the ranks, collected with
 ONE gather (RCCL over xGMI) and aggregated on rank 0 ("strong" scaling: the work per map is fixed).
@@ -50,13 +56,58 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"],
                     help="16-bit operand type of the engine (fp32 accumulation): bf16 = the headline build; fp16 = libmarigold_hip_f16.so, "
                          "the reference's --fp16 arithmetic")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: calibration, latency, per-kernel roofline, ensembling / gather "
+                         "timing, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the per-kernel profile and the ensembling timing")
     ap.add_argument("--graph", action="store_true", help="replay the denoising loop as a hipGraph")
-    ap.add_argument("--dump-ops", default="", help="write the per-op timing table to this file")
+    ap.add_argument("--dump-ops", default="", help="with --full: write the per-op timing table to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the output arrays of the last timed map to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-baseline-only", default="", help=argparse.SUPPRESS)  # internal: child mode
     ap.add_argument("--cpu-baseline-timeout", type=int, default=200)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops needs --full (the per-op table comes from the per-kernel profile)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+OUTPUT_SEED = 2024          # every map's noise generator (map_images: one generator per map, so lanes cannot reorder the draws)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(out, kind):
+    """name -> array: what a caller of the pipeline receives for one map (the PIL renderings are derived from these)."""
+    if kind == "iid":
+        arrays = {}
+        for e in out.entries:
+            arrays[e.name] = e.array
+            arrays[f"{e.name}_uncertainty"] = e.uncertainty
+    elif kind == "normals":
+        arrays = {"normals": out.normals_np, "uncertainty": out.uncertainty}
+    else:
+        arrays = {"depth": out.depth_np, "uncertainty": out.uncertainty}
+    return {k: v for k, v in arrays.items() if v is not None}
+
+
+def dump_outputs(arrays, path):
+    """Writes each array as <path>/<name>.npy in float32; above DUMP_LIMIT_BYTES in all, each array becomes a fixed
+    seeded sample of its elements (flattened, in index order) with the indices alongside as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // (3 * total))   # 4 bytes per kept value + 8 per float64 index
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    return sorted(arrays)
 
 
 def log(*a):
@@ -377,8 +428,8 @@ def main():
     if rank == 0:
         log(f"[bench] synthetic weights + pipeline ready in {time.perf_counter() - t0:.1f}s "
             f"(host cores {os.cpu_count()})")
-    calib = calibration(dev) if rank == 0 else None
-    if rank == 0:
+    calib = calibration(dev) if rank == 0 and args.full else None
+    if calib is not None:
         log(f"[bench] calibration: {calib}")
     img = syn.synthetic_image(args.res, args.res, seed=0).to(dev)   # resident in HBM before timing
     torch.manual_seed(2024)
@@ -398,18 +449,25 @@ def main():
     # (with several ranks every rank runs the same lanes; the gathers are issued in map order on all of them - pipeline._Turnstile)
     in_flight = args.in_flight if args.in_flight > 0 else pipe.maps_in_flight_for(args.ensemble)
 
+    def generators(k):
+        return [torch.Generator(device=dev).manual_seed(OUTPUT_SEED) for _ in range(k)]
+
     def run_maps(k):
-        last = None
-        for last in pipe.map_images([img] * k, in_flight=in_flight, **kw):
-            pass
-        return last
+        """k maps through map_images -> (the last map's output, the number of maps it returned)"""
+        last, n = None, 0
+        for last in pipe.map_images([img] * k, in_flight=in_flight, generators=generators(k), **kw):
+            n += 1
+        if n != k:
+            raise RuntimeError(f"map_images returned {n} maps for {k} images")
+        return last, n
 
     out = None
     for i in range(args.warmup):
         t1 = time.perf_counter()
         if i == 0 and in_flight > 1:
-            out = pipe(img, **kw)   # the first map alone: programs built, kernels loaded and their attributes set by ONE thread
-        out = run_maps(in_flight)   # one map per lane: every replica's programs built
+            # the first map alone: programs built, kernels loaded and their attributes set by ONE thread
+            out = pipe(img, generator=generators(1)[0], **kw)
+        out, _ = run_maps(in_flight)   # one map per lane: every replica's programs built
         torch.cuda.synchronize()
         if rank == 0:
             log(f"[bench] warmup {i}: {time.perf_counter() - t1:.3f}s ({in_flight} map(s))")
@@ -419,14 +477,16 @@ def main():
             for prog in pipe.unet._programs.values():
                 prog.seq.capture()
         torch.cuda.synchronize()
-        out = pipe(img, **kw)
+        out = pipe(img, generator=generators(1)[0], **kw)
     barrier()
     t1 = time.perf_counter()
-    out = run_maps(args.steps)
+    out, timed_maps = run_maps(args.steps)
     barrier()
     dt = time.perf_counter() - t1
+    if rank == 0:
+        log(f"[bench] timed {timed_maps} maps in {dt:.3f}s")
     latency_ms = None
-    if in_flight > 1:   # the same maps one at a time: what a single request waits (not the headline)
+    if args.full and in_flight > 1:   # the same maps one at a time: what a single request waits (not the headline)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         for _ in range(2):
@@ -443,10 +503,13 @@ def main():
         assert res is not None and res.shape[-2:] == (args.res, args.res)
         import numpy as np
         assert np.isfinite(res).all()
+        if args.dump_outputs:
+            names = dump_outputs(output_arrays(out, args.kind), args.dump_outputs)
+            log(f"[bench] outputs of the last timed map written to {args.dump_outputs}: {', '.join(names)}")
 
     # ---- per-kernel-class roofline from HIP-event timings of every launch (rank 0) --------------
     kernels, roof, stages, flops_per_map = {}, None, {}, 0
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         try:
             progs = [("denoise", p.seq) for p in pipe.unet._programs.values()] + \
                     [(f"vae.{k[0]}", v[0]) for k, v in pipe.vae._programs.items()]
@@ -515,7 +578,7 @@ def main():
 
     # ---- the parts of a map that are not native programs: test-time ensembling (host BFGS driving two fused kernels
     # per cost evaluation) and, with several ranks, the single gather of the members -------------------------------
-    if not args.no_profile and args.ensemble > 1:
+    if args.full and not args.no_profile and args.ensemble > 1:
         try:
             import marigold_amd.dist as mdist
             from marigold_amd import ensemble as ens
@@ -550,7 +613,7 @@ def main():
             log(f"[bench] ensemble / gather timing skipped: {type(e).__name__}: {e}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the oracle runs in a child process under a hard timeout: it is a reported baseline and must
         # never be able to stall the benchmark (or share threads / memory with the timed process)
         import subprocess
@@ -585,6 +648,7 @@ def main():
             "value": round(value, 4), "unit": f"{args.kind} maps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "full": bool(args.full),   # False: the fields below that need extra measurements (--full) are None / empty
             "config": {"workload": (f"marigold-{args.kind}-v1-1 architecture (SD-v2 UNet 865.9M + AutoencoderKL), "
                                     f"{args.res}x{args.res}, ensemble_size={args.ensemble}, {args.denoise} "
                                     + ("DDIM steps (trailing, zero-SNR, v-prediction)" if args.scheduler == "ddim" else "LCM steps")
@@ -600,10 +664,12 @@ def main():
                             "gathers_per_map": 1} if dist_on else None),
             "cpu_baseline": cpu,
             "calibration": calib,
-            # whole-map figures only where rank 0 ran the whole map (its programs cover its own members only)
-            "algorithmic_tflop_per_map": round(flops_per_map / 1e12, 2) if world == 1 else None,
-            "pipeline_tflops": round(flops_per_map * value / 1e12, 1) if world == 1 else None,
-            "pipeline_mfma_frac": round(flops_per_map * value / 1e12 / opstats.MFMA_PEAK_TFLOPS, 4) if world == 1 else None,
+            # whole-map figures only where rank 0 ran the whole map (its programs cover its own members only) and the per-kernel
+            # profile counted its FLOPs (--full without --no-profile)
+            "algorithmic_tflop_per_map": round(flops_per_map / 1e12, 2) if world == 1 and flops_per_map else None,
+            "pipeline_tflops": round(flops_per_map * value / 1e12, 1) if world == 1 and flops_per_map else None,
+            "pipeline_mfma_frac": (round(flops_per_map * value / 1e12 / opstats.MFMA_PEAK_TFLOPS, 4)
+                                   if world == 1 and flops_per_map else None),
             # the same against SURVEY.md section 8(d)'s reference-faithful count (273.92 TFLOP per map at the headline configuration):
             # comparable across rounds however much work the engine folds away (sub-pixel up-sampling, collapsed cross-attention)
             "pipeline_mfma_frac_survey": (round(SURVEY_TFLOP_PER_MAP * value / opstats.MFMA_PEAK_TFLOPS, 4)

@@ -13,6 +13,8 @@ TEST INFRASTRUCTURE - see oracle/__init__.py.  Run in the BUILD container only (
    ``schedulers.py``, ``pipeline.py``) on the tiny seeded configuration of
    ``marigold_amd.arch`` - minted here because the reference holds no golden vectors for
    this boundary ("parity unpinned").
+3. ``ensemble_ref_optimiser.npz`` (``python -m oracle.make_golden optimiser``) - the reference's depth alignment
+   optimiser on the d_e* cases of ``ensemble_ref.npz``: start, settings, cost evaluations, final parameters.
 """
 import importlib.util
 import os
@@ -135,6 +137,51 @@ def make_ensemble_golden():
     print("ensemble_ref.npz:", sorted(out))
 
 
+def minimize_settings(args, kwargs):
+    """The arguments of a ``scipy.optimize.minimize`` call after the objective and the start, as one JSON string."""
+    import json
+    return json.dumps({"args": list(args), "kwargs": kwargs}, sort_keys=True)
+
+
+def make_ensemble_optimiser_golden(n_evals=40):
+    """tests/golden/ensemble_ref_optimiser.npz: what the reference's depth alignment optimiser does on the d_e* cases of
+    ensemble_ref.npz - its start p0, the first ``n_evals`` (param, cost) evaluations of its cost function, its final
+    parameters and their cost.  BFGS on finite differences of an fp32 cost follows the cost's rounding noise, so the
+    ensembled map itself is only reproducible on a host that rounds every sum the same way; these records let the
+    restatement be checked piece by piece on any host."""
+    import scipy.optimize
+    ref = _import_reference_ensemble()
+    out = {}
+    minimize = scipy.optimize.minimize
+    for name, E, H, W, seed in [("d_e4", 4, 48, 64, 11), ("d_e10", 10, 32, 40, 12), ("d_e3", 3, 24, 24, 13)]:
+        x = synth_depth_members(E, H, W, seed)
+        rec = {}
+
+        def recording(fun, x0, *a, **k):
+            evals = []
+
+            def f(p):
+                c = fun(p)
+                evals.append((np.array(p, dtype=np.float64), float(c)))
+                return c
+            res = minimize(f, x0, *a, **k)
+            rec.update(p0=np.array(x0, dtype=np.float64), param=np.array(res.x, dtype=np.float64),
+                       cost=float(fun(res.x)), evals=evals, settings=minimize_settings(a, k))
+            return res
+        scipy.optimize.minimize = recording
+        try:
+            d, u = ref.ensemble_depth(x.clone(), True, True, output_uncertainty=True)
+        finally:
+            scipy.optimize.minimize = minimize
+        out[f"{name}_p0"], out[f"{name}_param"], out[f"{name}_cost"] = rec["p0"], rec["param"], np.array(rec["cost"])
+        out[f"{name}_eval_params"] = np.stack([p for p, _ in rec["evals"][:n_evals]])
+        out[f"{name}_eval_costs"] = np.array([c for _, c in rec["evals"][:n_evals]])
+        out[f"{name}_minimize_settings"] = np.array(rec["settings"])
+        out[f"{name}_out"], out[f"{name}_unc"] = d.numpy(), u.numpy()
+    np.savez_compressed(os.path.join(GOLD, "ensemble_ref_optimiser.npz"), **out)
+    print("ensemble_ref_optimiser.npz:", sorted(out))
+
+
 def make_ensemble_768_golden():
     """The metric configuration of test-time ensembling: E = 10 members at 768 x 768 through the REFERENCE's own
     ensemble_depth (about two minutes of CPU: ~4 600 cost evaluations).  The members come from the seeded
@@ -237,6 +284,9 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     if len(sys.argv) > 1 and sys.argv[1] == "ensemble768":
         make_ensemble_768_golden()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "optimiser":
+        make_ensemble_optimiser_golden()
         sys.exit(0)
     make_scheduler_golden()
     make_ensemble_golden()

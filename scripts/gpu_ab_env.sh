@@ -3,14 +3,15 @@
 # Interleaved twice; prints ms per map and the per-class kernel times of each run.  MARIGOLD_TUNING=1 is set for both sides.
 export PYTHONUNBUFFERED=1 MARIGOLD_TUNING=1
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+OUT=$(realpath -m "${OUT:-bench_logs}")   # where the logs land (any directory; bench_logs/ by default)
+mkdir -p $OUT
 NAME=$1; A=$2; B=$3; shift 3
-LOG=gpurun_out/ab_$NAME.log
+LOG=$OUT/ab_$NAME.log
 : > $LOG
 for round in 1 2; do
   for side in A B; do
     if [ $side == A ]; then E="$A"; else E="$B"; fi
-    env $E timeout 400 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --dump-ops gpurun_out/ops_${NAME}_$side.tsv "$@" 2>gpurun_out/ab_${NAME}_err_$side.log | python -c "
+    env $E timeout 400 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --dump-ops $OUT/ops_${NAME}_$side.tsv "$@" 2>$OUT/ab_${NAME}_err_$side.log | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
@@ -18,4 +19,4 @@ for l in sys.stdin:
 " >> $LOG
   done
 done
-cat $LOG; tail -3 gpurun_out/ab_${NAME}_err_B.log
+cat $LOG; tail -3 $OUT/ab_${NAME}_err_B.log

@@ -1,11 +1,13 @@
 #!/bin/bash
 # Kernel trace of one map -> the idle gaps between consecutive kernels on the stream (start[i+1] - end[i]).
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$PWD; mkdir -p gpurun_out; rm -rf gpurun_out/prof
-(cd /tmp && export TMPDIR=/tmp && MARIGOLD_TUNING=1 MARIGOLD_GN_COOP=0 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/prof -o tr -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $R/gpurun_out/rocprof_bench.log 2>&1)
+cd "$(dirname "$0")/.."; R=$PWD
+export OUT=$(realpath -m "${OUT:-bench_logs}")   # where the logs land (any directory; bench_logs/ by default)
+mkdir -p $OUT; rm -rf $OUT/prof
+(cd /tmp && export TMPDIR=/tmp && MARIGOLD_TUNING=1 MARIGOLD_GN_COOP=0 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -o tr -- python $R/bench.py --steps 1 --warmup 1 > $OUT/rocprof_bench.log 2>&1)
 echo "rocprof rc=$?"
 python - <<'PY'
-import csv, glob, collections
-f = glob.glob('gpurun_out/prof/**/*kernel_trace.csv', recursive=True)[0]
+import csv, glob, collections, os
+f = glob.glob(os.environ['OUT'] + '/prof/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 # the last ~2800 kernels = the timed map (bench ran warmup + 1 step); take kernels after the calibration
@@ -26,4 +28,4 @@ for i in range(len(tail) - 1):
 for k, v in sorted(byk.items(), key=lambda kv: -sum(kv[1]))[:25]:
     print(f'{k:60s} n={len(v):4d} mean gap before {sum(v)/len(v)/1000:6.2f} us')
 PY
-rm -rf gpurun_out/prof
+rm -rf $OUT/prof

@@ -3,12 +3,13 @@
 # (per-GPU shards of the member-parallel path are small ensembles: how many lanes they want).
 export PYTHONUNBUFFERED=1
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
-LOG=gpurun_out/inflight_sweep.log
+OUT=$(realpath -m "${OUT:-bench_logs}")   # where the logs land (any directory; bench_logs/ by default)
+mkdir -p $OUT
+LOG=$OUT/inflight_sweep.log
 : > $LOG
 for e in $1; do
   for n in $2; do
-    timeout 300 python bench.py --ensemble $e --in-flight $n --steps 12 --warmup 2 --no-cpu-baseline --no-profile 2>gpurun_out/inflight_sweep_err.log | python -c "
+    timeout 300 python bench.py --full --ensemble $e --in-flight $n --steps 12 --warmup 2 --no-cpu-baseline --no-profile 2>$OUT/inflight_sweep_err.log | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
@@ -16,4 +17,4 @@ for l in sys.stdin:
 " >> $LOG
   done
 done
-cat $LOG; tail -3 gpurun_out/inflight_sweep_err.log
+cat $LOG; tail -3 $OUT/inflight_sweep_err.log

@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 ENS=${ENS:-1,2,3,5}
 bench() { # name
   for e in ${ENS//,/ }; do
-    MARIGOLD_TUNING=1 timeout 300 python bench.py --ensemble $e --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
+    MARIGOLD_TUNING=1 timeout 300 python bench.py --full --ensemble $e --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -648,7 +648,7 @@ def test_bench_nccl_path_single_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny",
-           "--res", "128", "--ensemble", "3", "--denoise", "2", "--no-cpu-baseline"]
+           "--res", "128", "--ensemble", "3", "--denoise", "2", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, MARIGOLD_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -657,6 +657,40 @@ def test_bench_nccl_path_single_rank(tmp_path):
     assert line["collective"] == {"backend": "nccl", "world_size": 1, "forced_single_rank": True, "gathers_per_map": 1}
     assert "gather" in line["stages"] and line["stages"]["gather"]["ms"] > 0
     print(f"[parity] bench.py under torchrun, nccl world 1: {line['ms_per_step']} ms/step, gather {line['stages']['gather']}")
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain bench.py run (no --full) prints the headline fields only, times exactly --steps maps (the count of maps
+    map_images returned in the timed region, which bench.py logs), and --dump-outputs
+    writes the last timed map's arrays: two runs with the same arguments (here with different step counts - every map
+    is the same seeded computation) give the same arrays, bit for bit (tiny architecture, two maps in flight)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for steps in (2, 3):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--tiny",
+               "--res", "128", "--ensemble", "3", "--denoise", "2", "--in-flight", "2", "--dump-outputs", str(tmp_path / f"s{steps}")]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        # the maps map_images returned inside the timed region, counted by bench.py
+        timed = [int(ln.split()[2]) for ln in r.stderr.splitlines() if ln.startswith("[bench] timed ")]
+        lines.append((line, timed))
+    for steps, (line, timed) in zip((2, 3), lines):
+        assert timed == [steps], timed
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        assert line["unit"] == "depth maps/s" and line["dtype"] == "bf16" and line["full"] is False
+        assert line["calibration"] is None and line["cpu_baseline"] is None and line["roofline"] is None
+        assert line["kernels"] == {} and line["stages"] == {} and line["latency_ms_per_map"] is None
+        assert line["algorithmic_tflop_per_map"] is None and line["pipeline_tflops"] is None and line["pipeline_mfma_frac"] is None
+    # ensemble_depth's default (output_uncertainty=False, like the reference) leaves the uncertainty out: the depth map only
+    files = sorted(os.listdir(tmp_path / "s2"))
+    assert files == ["depth.npy"] and sorted(os.listdir(tmp_path / "s3")) == files
+    a, b = np.load(tmp_path / "s2" / "depth.npy"), np.load(tmp_path / "s3" / "depth.npy")
+    assert a.dtype == np.float32 and a.shape == (128, 128) and np.isfinite(a).all()
+    np.testing.assert_array_equal(a, b)
 
 
 def test_model_image_runs_the_pipeline_from_c(tiny, tmp_path):

@@ -1338,3 +1338,30 @@ def test_conv3x3_groupnorm_byproduct_slots():
     assert slots(variant=8, N=128, H=50, W=37) == 3 * 3        # ragged
     assert slots(variant=6, N=320, C0=320) == 0 and slots(variant=10) == 0 and slots(variant=11, N=320, C0=320) == 0
     assert slots(variant=9, N=128) == 0                         # the 256-channel tile needs N % 256 == 0
+
+
+def test_bench_dump_outputs_writes_float32_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (host side): the arrays a pipeline caller receives, one float32 .npy each; above the size limit
+    every array becomes the same seeded sample of its elements, with the sampled indices alongside."""
+    import bench
+    from marigold_amd.pipeline import MarigoldDepthOutput
+    rng = np.random.default_rng(3)
+    depth, unc = rng.random((48, 64)), rng.random((48, 64)).astype(np.float32)
+    arrays = bench.output_arrays(MarigoldDepthOutput(depth_np=depth, depth_colored=None, uncertainty=unc), "depth")
+    assert sorted(arrays) == ["depth", "uncertainty"]
+    assert sorted(bench.output_arrays(MarigoldDepthOutput(depth, None, None), "depth")) == ["depth"]
+    assert bench.dump_outputs(arrays, str(tmp_path / "all")) == ["depth", "uncertainty"]
+    got = np.load(tmp_path / "all" / "depth.npy")
+    assert got.dtype == np.float32 and got.shape == depth.shape and np.array_equal(got, depth.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "all" / "uncertainty.npy"), unc)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 12 * 1024)
+    for run in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / run))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["depth.npy", "depth_index.npy", "uncertainty.npy", "uncertainty_index.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 12 * 1024 + 4 * 128   # + the .npy headers
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "depth_index.npy").astype(np.int64)
+    assert len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "depth.npy"), depth.astype(np.float32).reshape(-1)[idx])
