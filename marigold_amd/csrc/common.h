@@ -49,14 +49,18 @@ __device__ __forceinline__ float bf2f(bf16_t v) {
   else return __uint_as_float(((uint32_t)v) << 16);
 }
 // two fp32 -> packed operands (round to nearest even) in one instruction: v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32; the fp16 form
-// saturates at +-65504 first (a bf16 value of 1e5 is a number, an fp16 inf poisons every sum it enters)
+// saturates at +-65504 (a bf16 value of 1e5 is a number, an fp16 inf poisons every sum it enters) and keeps NaN: the pair is
+// converted first (|x| >= 65520 rounds to inf) and then clamped with IEEE maximum / minimum (v_pk_maximum3_f16 / v_pk_minimum3_f16),
+// which propagate NaN - a clamp by v_med3_f32 / v_max_f32 turns a NaN into -65504.  Two VALU ops per pair as before, but the dependent
+// packed pair needs an s_nop between them and the constants take moves: the fp16 objects grow by about 1 %.
 __device__ __forceinline__ uint32_t cvt_pk_bf16_f32(float lo, float hi) {
-  if constexpr (MG_F16) {
-    lo = __builtin_amdgcn_fmed3f(lo, -MG_OP16_MAX, MG_OP16_MAX);
-    hi = __builtin_amdgcn_fmed3f(hi, -MG_OP16_MAX, MG_OP16_MAX);
-  }
   mg_f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, mg_bf16x2_t));
+  mg_bf16x2_t h = __builtin_convertvector(v, mg_bf16x2_t);
+  if constexpr (MG_F16) {
+    const mg_bf16x2_t m = {(mg_op16_t)MG_OP16_MAX, (mg_op16_t)MG_OP16_MAX};
+    h = __builtin_elementwise_minimum(__builtin_elementwise_maximum(h, -m), m);
+  }
+  return __builtin_bit_cast(uint32_t, h);
 }
 __device__ __forceinline__ bf16_t f2bf(float f) {  // round-to-nearest-even, NaN preserved
   if constexpr (MG_F16) return (bf16_t)(cvt_pk_bf16_f32(f, 0.f) & 0xffffu);

@@ -145,7 +145,7 @@ def test_c2_depth_768_t10_vs_oracle(full, gold768):
     rl = full["vae"].encode_rgb_latent(rgb.cuda())
     e_enc = _rel(rl, gold768["rgb_latent"])
     print(f"[parity] C2 encode_rgb 768x768: latent rmse/rms {e_enc:.3e}")
-    assert e_enc < 2e-2
+    assert e_enc < 1.9e-2   # 1.5x the 1.30e-2 measured on the MI355X (per-op table: profiles/shadow_vae_encode_768.tsv)
     pipe.scheduler.set_timesteps(10)
     full["unet"].set_context(full["ctx"])
     prog = full["unet"].denoise_program(1, 96, 96, pipe.scheduler, 10, rgb_broadcast=True)

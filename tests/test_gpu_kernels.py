@@ -550,6 +550,49 @@ def test_flash_attn64_benchmark_shape(dev):
     _close("flash_attn64/5 heads x 9216 tokens", out, ref)
 
 
+def test_flash_attn64_benchmark_shape_hand_placed_key_split(dev):
+    """What the product runs at its main attention launch: the permuted V^T at 10 members x 5 heads x 9 216 tokens, where the
+    launcher picks the hand-placed kernel (variant 27 on its own; 26 forced beside it).  1 800 blocks of 256 queries leave
+    1 800 mod CUs over: with the engine's workspace and the automatic rule they go out as key-split pieces - which the plan
+    (mg_flash4w_plan_test) must confirm - with split = 1 always, with split = 2 never.  Every launch against CPU SDPA in fp32."""
+    import ctypes
+    from marigold_amd import _lib as L, ops
+    from marigold_amd.util.host import usable_cores
+    torch.set_num_threads(min(32, usable_cores()))
+    B, heads, T = 10, 5, 9216
+    C = heads * 64
+    g = torch.Generator().manual_seed(12)
+    qkv = _bf(torch.randn(B, T, 3 * C, generator=g) * 1.2)
+    q, k, v = qkv.split(C, dim=-1)
+    qh, kh, vh = (t.reshape(B, T, heads, 64).transpose(1, 2) for t in (q, k, v))
+    ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, T, C)
+    qkd = qkv.to(dev, OP16)
+    vtp = ops.permute_vt_keys(v.permute(0, 2, 1).contiguous().to(dev, OP16))
+    lib = L.load(F16)
+    cu, lds, hbm = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    arch = ctypes.create_string_buffer(64)
+    L.check(lib.mg_device_info(ctypes.byref(cu), ctypes.byref(lds), ctypes.byref(hbm), arch, 64), "mg_device_info", lib)
+    for split, ws_bytes in ((0, ops.FLASH_WS_BYTES_AUTO), (1, ops.FLASH_WS_BYTES), (2, 0)):
+        plan = (ctypes.c_int * 3)()
+        assert lib.mg_flash4w_plan_test(B, heads, T, cu.value, ws_bytes, split, plan, None) == 0
+        nb = B * heads * (T // 256)
+        assert plan[0] + plan[1] == nb
+        if split == 2:
+            assert plan[1] == 0
+        else:
+            assert plan[1] == nb % cu.value > 0 and plan[2] > plan[1], (cu.value, list(plan))   # the left-over blocks go out in pieces
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        for variant in (0, 26, 27):
+            out = torch.full((B, T, C), float("nan"), device=dev, dtype=OP16)
+            _run(ops.flash_attn64(qkd, qkd[:, :, C:], vtp, out, B=B, heads=heads, Ntok=T, ldq=3 * C, ldo=C, ldvt=T, sq=T * 3 * C,
+                                  sk=T * 3 * C, svt=C * T, so=T * C, scale=0.125, variant=variant, vt_perm=True, ws=ws,
+                                  ws_bytes=ws_bytes, split=split))
+            _close(f"flash_attn64/B{B}h{heads}T{T}/v{variant}p/split{split} ({plan[1]} of {nb} blocks in {plan[2]} key pieces)",
+                   out, ref)
+            if ws is not None:
+                assert int(ws[:4096].view(torch.int32).abs().sum()) == 0, "tickets not back at zero"
+
+
 def test_igemm_linear_geglu_f32_trans_batched(dev):
     from marigold_amd import _lib as L, ops, weights as Wm
     g = torch.Generator().manual_seed(5)
@@ -1911,3 +1954,146 @@ def test_colorize_lut_matches_reference_chain(dev, cmap):
     ref = (iu.colorize_depth_maps(d.numpy(), 0, 1, cmap=cmap).squeeze() * 255).astype(np.uint8)   # [3,H,W]
     got = iu.colorize_depth_device(d.to(dev), 0.0, 1.0, cmap=cmap).cpu().numpy()                  # [H,W,3]
     assert got.shape == (37, 53, 3) and np.array_equal(np.moveaxis(got, -1, 0), ref)
+
+
+# --------------------------------------------------------------------------- NaN in, NaN out
+# A NaN in an input must reach exactly the outputs that depend on it, in both operand builds: no store, clamp or padding
+# path may turn it into a finite value (the fp16 build's saturation at +-65504 once did: v_med3_f32 returns min3 on a NaN),
+# and none may spread it to outputs that do not read it (a zero pad multiplied in instead of selected would).  The mask of
+# NaN outputs must equal the fp32 torch reference's; the rest is held to the usual bound.
+def _nan_parity(name, got, ref, tol=1.5e-2):
+    got = got.detach().float().cpu()
+    ref = ref.detach().float().cpu()
+    want, have = torch.isnan(ref), torch.isnan(got)
+    assert want.any(), f"{name}: the reference has no NaN output"
+    assert torch.equal(have, want), (f"{name}: {int((want & ~have).sum())} of {int(want.sum())} outputs that depend on the NaN input "
+                                     f"are not NaN, {int((have & ~want).sum())} that do not are")
+    _close(f"{name}/non-NaN", torch.where(want, 0.0, got), torch.where(want, 0.0, ref), tol)
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,variant", [(2, 16, 24, 128, 320, 0), (2, 16, 24, 128, 192, 36), (2, 16, 24, 128, 320, 62),
+                                                    (1, 14, 14, 128, 256, 73), (1, 12, 12, 1280, 128, 0)])
+def test_nan_propagates_igemm_conv(dev, B, H, W, Cin, Cout, variant):
+    """MG_OP_IGEMM conv3x3 (tile variants incl. the hand-placed 192 x 320 loop; the last case runs the automatic split-K with its
+    fp32 partials and reduce launch): NaN at an interior pixel of the first image and at an image-border pixel of the last (the same
+    image when B = 1)."""
+    from marigold_amd import ops, weights as Wm
+    g = torch.Generator().manual_seed(100 + variant + Cin)
+    x = _bf(torch.randn(B, Cin, H, W, generator=g))
+    x[0, 5, H // 2, W // 3] = float("nan")
+    x[B - 1, Cin - 1, 0, W - 1] = float("nan")
+    w = _bf(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin))
+    bias = torch.randn(Cout, generator=g) * 0.1
+    ref = F.conv2d(x, w, bias, padding=1)
+    out = torch.full((B, H, W, Cout), float("nan"), device=dev, dtype=OP16)
+    wd, bd = Wm.pack_conv3x3(w).to(dev, OP16), bias.to(dev)
+    _run(ops.igemm(_nhwc(x).to(dev, OP16), wd, out, B=B, H=H, W=W, Cin=Cin, Ho=H, Wo=W, N=Cout, taps=9, stride=1, pad=1, bias=bd,
+                   variant=variant))
+    _nan_parity(f"nan/igemm conv B{B} {H}x{W} {Cin}->{Cout} v{variant}", out.float().permute(0, 3, 1, 2), ref)
+
+
+# (the four-wave tile 11: bf16 only - its in-stream GroupNorm fix-up unpacks bf16, the fp16 build runs fused norms on 12 waves)
+@pytest.mark.parametrize("variant", [0, 6] + ([] if F16 else [11]))
+def test_nan_propagates_conv3x3_fused_norm(dev, variant):
+    """MG_OP_CONV3X3 with the GroupNorm scale / shift + SiLU fused into its operand staging: a NaN input pixel becomes a NaN
+    normalised pixel and NaN outputs over its 3 x 3 neighbourhood, nothing else (the zero padding stays zero)."""
+    from marigold_amd import ops, weights as Wm
+    B, H, W, C, N = 2, 24, 32, 320, 320
+    g = torch.Generator().manual_seed(200 + variant)
+    x = _bf(torch.randn(B, C, H, W, generator=g))
+    x[1, 17, 0, 0] = float("nan")
+    x[0, 300, 13, 20] = float("nan")
+    w = _bf(torch.randn(N, C, 3, 3, generator=g) / math.sqrt(9 * C))
+    bias = torch.randn(N, generator=g) * 0.1
+    ss = torch.stack([1.0 + 0.3 * torch.randn(B, C, generator=g), 0.3 * torch.randn(B, C, generator=g)], dim=1)
+    ref = _ref_fused_conv(x, w, bias, ss, True, None, None)
+    out = torch.full((B, H, W, N), float("nan"), device=dev, dtype=OP16)
+    wd, bd, ssd = Wm.pack_conv3x3(w).to(dev, OP16), bias.to(dev), ss.to(dev).contiguous()
+    _run(ops.conv3x3(_nhwc(x).to(dev, OP16), wd, out, B=B, H=H, W=W, C0=C, N=N, ss=ssd, silu=True, bias=bd, variant=variant))
+    _nan_parity(f"nan/conv3x3 fused norm v{variant}", out.float().permute(0, 3, 1, 2), ref)
+
+
+def test_nan_propagates_groupnorm(dev):
+    """gn_apply alone (scale / shift of the clean tensor: exactly the NaN element) and the gn_stats -> gn_finalize -> gn_apply chain
+    (the NaN's (image, group) throughout)."""
+    from marigold_amd import ops
+    B, H, W, C, eps = 2, 12, 20, 320, 1e-5
+    HW, cpg = H * W, C // 32
+    g = torch.Generator().manual_seed(7)
+    x = _bf(torch.randn(B, C, H, W, generator=g) * 1.5 + 0.3)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.2 * torch.randn(C, generator=g)
+    xg = x.reshape(B, 32, -1)
+    sc = (xg.var(-1, unbiased=False) + eps).rsqrt().repeat_interleave(cpg, 1) * gamma
+    sh = beta - xg.mean(-1).repeat_interleave(cpg, 1) * sc
+    xn = x.clone()
+    xn[1, 37, 3, 4] = float("nan")
+    xd = _nhwc(xn).to(dev, OP16)
+    ss = torch.stack([sc, sh], 1).to(dev).contiguous()
+    out = torch.full_like(xd, float("nan"))
+    _run(ops.gn_apply(xd, ss, out, B=B, HW=HW, C=C, silu=True))
+    _nan_parity("nan/gn_apply", out.float().permute(0, 3, 1, 2), F.silu(xn * sc[:, :, None, None] + sh[:, :, None, None]))
+    chunks = 8
+    part = torch.empty(B, chunks, C, 2, device=dev)
+    ss2 = torch.empty(B, 2, C, device=dev)
+    out = torch.full_like(xd, float("nan"))
+    for op in (ops.gn_stats(xd, part, B=B, HW=HW, C=C, chunks=chunks, groups=32),
+               ops.gn_finalize(part, gamma.to(dev), beta.to(dev), ss2, B=B, C=C, groups=32, slots=chunks, HW=HW, eps=eps),
+               ops.gn_apply(xd, ss2, out, B=B, HW=HW, C=C, silu=True)):
+        _run(op)
+    _nan_parity("nan/gn_stats+finalize+apply", out.float().permute(0, 3, 1, 2), F.silu(F.group_norm(xn, 32, gamma, beta, eps)))
+
+
+def test_nan_propagates_rowgemm(dev):
+    """MG_OP_ROWGEMM: a NaN in one row of x gives a NaN output row - bias form and GEGLU with the folded LayerNorm (whose
+    statistics of that row are NaN as well)."""
+    from marigold_amd import _lib as L, ops, weights as Wm
+    B, T, C = 2, 1056, 320
+    M = B * T
+    g = torch.Generator().manual_seed(9)
+    x = _bf(torch.randn(M, C, generator=g))
+    x[777, 11] = float("nan")
+    x[M - 1, 0] = float("nan")
+    xd = x.to(dev, OP16)
+    w, b = torch.randn(C, C, generator=g) / math.sqrt(C), 0.1 * torch.randn(C, generator=g)
+    out = torch.full((M, C), float("nan"), device=dev, dtype=OP16)
+    pk = Wm.pack_rowgemm(w, b).to(dev)
+    _run(ops.rowgemm(xd, pk, out, M=M, K=C, N=C))
+    _nan_parity("nan/rowgemm bias", out, x @ _bf(w).t() + b)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.2 * torch.randn(C, generator=g)
+    stx = torch.stack([x.mean(-1), 1.0 / torch.sqrt(x.var(-1, unbiased=False) + 1e-5)], dim=-1).to(dev).contiguous()
+    wg, bg = torch.randn(8 * C, C, generator=g) / math.sqrt(C), 0.1 * torch.randn(8 * C, generator=g)
+    wp, lg, lc = Wm.fold_layernorm(wg[Wm.rowgemm_geglu_order(8 * C)], bg[Wm.rowgemm_geglu_order(8 * C)], gamma, beta)
+    pk = Wm.pack_rowgemm(wp.float(), lc, lg).to(dev)
+    hid = torch.full((M, 4 * C), float("nan"), device=dev, dtype=OP16)
+    _run(ops.rowgemm(xd, pk, hid, M=M, K=C, N=8 * C, form=L.RG_GEGLU, ln_in=stx))
+    u, gt = (F.layer_norm(x, (C,), gamma, beta, 1e-5) @ wg.t() + bg).chunk(2, dim=-1)
+    _nan_parity("nan/rowgemm geglu", hid, u * F.gelu(gt), tol=2e-2)
+
+
+def test_nan_propagates_flash_attn64(dev):
+    """MG_OP_FLASH_ATTN64: a NaN in one query gives that query's output row of that head NaN, a NaN in one value that channel of
+    every query of its (image, head) - through the key tile that holds it and the key-split combine -, nothing else: the compiled kernel
+    on both key orders and the hand-placed variants 26 / 27, with key-split pieces and without."""
+    from marigold_amd import ops
+    B, heads, T = 2, 2, 1024
+    C = heads * 64
+    g = torch.Generator().manual_seed(13)
+    qkv = _bf(torch.randn(B, T, 3 * C, generator=g))
+    qkv[1, 300, 64 + 5] = float("nan")     # query 300 of image 1, head 1
+    qkv[0, 0, 0] = float("nan")            # query 0 of image 0, head 0
+    qkv[1, 700, 2 * C + 3] = float("nan")  # value of key 700 of image 1, head 0, channel 3: that channel of every query of the head
+    q, k, v = qkv.split(C, dim=-1)
+    qh, kh, vh = (t.reshape(B, T, heads, 64).transpose(1, 2) for t in (q, k, v))
+    ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, T, C)
+    qkd = qkv.to(dev, OP16)
+    vt = v.permute(0, 2, 1).contiguous().to(dev, OP16)
+    vtp = ops.permute_vt_keys(vt)
+    ws = torch.zeros(ops.FLASH_WS_BYTES, dtype=torch.uint8, device=dev)
+    for variant, perm, split in [(0, False, 2), (21, False, 2), (0, True, 2), (25, True, 2), (26, True, 2), (27, True, 2), (26, True, 1),
+                                 (27, True, 1)]:
+        out = torch.full((B, T, C), float("nan"), device=dev, dtype=OP16)
+        _run(ops.flash_attn64(qkd, qkd[:, :, C:], vtp if perm else vt, out, B=B, heads=heads, Ntok=T, ldq=3 * C, ldo=C, ldvt=T,
+                              sq=T * 3 * C, sk=T * 3 * C, svt=C * T, so=T * C, scale=0.125, variant=variant, vt_perm=perm,
+                              ws=ws if split == 1 else None, ws_bytes=ops.FLASH_WS_BYTES if split == 1 else 0, split=split))
+        _nan_parity(f"nan/flash_attn64 v{variant}{'p' if perm else ''} split{split}", out, ref)
+    assert int(ws[:4096].view(torch.int32).abs().sum()) == 0, "tickets not back at zero"
