@@ -171,8 +171,10 @@ enum mg_op_kind {
    * boundary (conv_in of the UNet incl. the torch.cat of marigold_depth_pipeline.py:456-458, of the
    * VAE encoder and decoder): fp32 NCHW (two sources) -> bf16 [B*H*W][Kp], k = tap*(C0+C1) + c,
    * columns >= 9*(C0+C1) zero.  The convolution itself is then an MG_OP_IGEMM with K = Kp.
-   *  p[0] src0 f32 [B|1][C0][H][W]  p[1] src1 f32 [B][C1][H][W] | NULL  p[2] out bf16 [B*H*W][Kp];
-   *  i: B,H,W,C0,C1,Kp, src0_broadcast */
+   *  p[0] src0 f32 [B|1|B/i[7]][C0][H][W]  p[1] src1 f32 [B][C1][H][W] | NULL  p[2] out bf16 [B*H*W][Kp];
+   *  i: B,H,W,C0,C1,Kp, src0_broadcast, i[7] members per src0 row: 0 = src0_broadcast decides (row 0 for every b,
+   *  or row b); m > 0 = row b reads src0 row b / m (several images in one program, m ensemble members each;
+   *  requires src0_broadcast = 0 and B % m == 0) */
   MG_OP_IM2COL_SMALL = 16,
   /* Patch-resident conv3x3 (stride 1, pad 1) with the ResNet block's GroupNorm + SiLU fused into the operand staging
    * (diffusers ResnetBlock2D: norm1 -> silu -> conv1, norm2 -> silu -> conv2), the UNet's skip concat folded into the

@@ -54,6 +54,9 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
     p.add_argument("--maps_in_flight", type=int, default=0,
                    help="Images on the GPU at a time (independent maps on concurrent HIP streams; results do not depend on it); "
                         "0 = the engine's default (2).")
+    p.add_argument("--images_per_program", type=int, default=1,
+                   help="Consecutive images of one processed size that share one denoising program (their members batched); "
+                        "1 = one image per program.")
     return p
 
 
@@ -173,8 +176,12 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         g.manual_seed(args.seed)
         return g
 
+    if args.images_per_program < 1:
+        raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
     if hasattr(pipeline, "map_images"):
         # the engine's multi-image form: up to --maps_in_flight images on the GPU at a time, outputs in input order
+        if args.images_per_program > 1:
+            kw["images_per_program"] = args.images_per_program
         outs = pipeline.map_images((Image.open(f) for f in files), in_flight=args.maps_in_flight or None,
                                    generators=(generator_of(f) for f in files), **kw)
         for rgb_path, out in zip(files, outs):

@@ -101,16 +101,18 @@ __global__ __launch_bounds__(256) void latent_1x1_kernel(const float* __restrict
 }
 
 // one thread per output pixel: gather the 3x3 x CIN fp32 neighbourhood, round to bf16, write the
-// Kp-wide row with 16-byte stores (reads are coalesced along W, writes are whole rows)
+// Kp-wide row with 16-byte stores (reads are coalesced along W, writes are whole rows).
+// Row b of the output reads row b / div0 of src0 (div0 = 0: row 0 for every b, the shared image latent)
 template <int CIN, int KP>
 __global__ __launch_bounds__(256) void im2col_small_kernel(const float* __restrict__ src0,
                                                            const float* __restrict__ src1,
                                                            bf16_t* __restrict__ out, int B, int H, int W,
-                                                           int C0, int bcast0) {
+                                                           int C0, int div0) {
   const long long hw = (long long)H * W;
   const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= (long long)B * hw) return;
   const int b = (int)(pix / hw);
+  const int b0 = div0 ? b / div0 : 0;
   const int rem = (int)(pix % hw);
   const int y = rem / W, x = rem % W;
   float v[KP];
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void im2col_small_kernel(const float* __restri
 #pragma unroll
     for (int c = 0; c < CIN; ++c) {
       if (ok) {
-        v[t * CIN + c] = c < C0 ? src0[((long long)(bcast0 ? 0 : b) * C0 + c) * hw + (long long)iy * W + ix]
+        v[t * CIN + c] = c < C0 ? src0[((long long)b0 * C0 + c) * hw + (long long)iy * W + ix]
                                 : src1[((long long)b * (CIN - C0) + (c - C0)) * hw + (long long)iy * W + ix];
       }
     }
@@ -227,12 +229,18 @@ int mg_launch_misc(const mg_op* op, hipStream_t s) {
       const int B = op->i[0], H = op->i[1], W = op->i[2], C0 = op->i[3], C1 = op->i[4], Kp = op->i[5];
       const int cin = C0 + C1;
       MG_REQUIRE(C1 == 0 || op->p[1], "im2col_small: src1 missing");
+      // src0 rows: i[7] = members per src0 row (b reads row b / i[7]); 0 = the legacy form, i[6] = 1 broadcasts row 0
+      const int bcast0 = op->i[6], per0 = op->i[7];
+      MG_REQUIRE(per0 >= 0, "im2col_small: members per src0 row %d < 0", per0);
+      MG_REQUIRE(per0 == 0 || bcast0 == 0, "im2col_small: src0 broadcast and members per src0 row %d both set", per0);
+      MG_REQUIRE(per0 == 0 || B % per0 == 0, "im2col_small: B %d not a multiple of the members per src0 row %d", B, per0);
+      const int div0 = per0 ? per0 : (bcast0 ? 0 : 1);
       const long long npix = (long long)B * H * W;
       const dim3 grid((unsigned)((npix + 255) / 256));
 #define I2C_CASE(N, K)                                                                             \
   if (cin == N && Kp == K) {                                                                       \
     MG_LAUNCH((im2col_small_kernel<N, K>), grid, dim3(256), 0, s, (const float*)op->p[0],         \
-              (const float*)op->p[1], (bf16_t*)op->p[2], B, H, W, C0, op->i[6]);                   \
+              (const float*)op->p[1], (bf16_t*)op->p[2], B, H, W, C0, div0);                       \
     break;                                                                                         \
   }
       I2C_CASE(3, 64) I2C_CASE(4, 64) I2C_CASE(8, 128) I2C_CASE(12, 128) I2C_CASE(16, 192)

@@ -565,12 +565,14 @@ class Builder:
                          residual=None if residual is None else residual.t), name)
         return out
 
-    def conv_from_nchw(self, src0, src1, name, B, H, W, C0, C1, cout, bcast0=False):
+    def conv_from_nchw(self, src0, src1, name, B, H, W, C0, C1, cout, bcast0=False, members0=0):
         """conv3x3 (pad 1) from <= 8 fp32 NCHW channels (two sources = the folded torch.cat of
-        marigold_depth_pipeline.py:456-458) to bf16 NHWC on the MFMA path: im2col + GEMM."""
+        marigold_depth_pipeline.py:456-458) to bf16 NHWC on the MFMA path: im2col + GEMM.  ``members0`` = m > 0: row b
+        takes src0 row b // m (several images' latents, m members each)."""
         w, kp = self.ws.conv_in_mfma(name)
         col = self.raw(B * H * W * kp * 2)
-        self.add(O.im2col_small(src0, src1, col, B=B, H=H, W=W, C0=C0, C1=C1, Kp=kp, bcast0=bcast0), f"{name}.im2col")
+        self.add(O.im2col_small(src0, src1, col, B=B, H=H, W=W, C0=C0, C1=C1, Kp=kp, bcast0=bcast0,
+                                members_per_src0=members0), f"{name}.im2col")
         out = self.new(B, H, W, cout)
         self.add(O.linear(col, w, out.t, M=B * H * W, K=kp, N=cout, bias=self.ws.bias(name),
                           k_alg=9 * (C0 + C1)), name)
@@ -905,9 +907,10 @@ def emit_time_embeddings(bld, cfg, timesteps):
     return table
 
 
-def emit_unet_forward(bld, cfg, ctx, rgb_latent, x_latent, eps_out, temb_table, step, B, h, w, sched=None):
+def emit_unet_forward(bld, cfg, ctx, rgb_latent, x_latent, eps_out, temb_table, step, B, h, w, sched=None, rgb_members=None):
     """One UNet forward: eps_out[B,4,h,w] = unet(cat(rgb_latent, x_latent), t_step, ctx).
-    rgb_latent is [1,4,h,w] (shared by all members) or [B,4,h,w].  With ``sched`` = (cx, cm, cn, noise) the model
+    rgb_latent is [1,4,h,w] (shared by all members) or [B,4,h,w]; with ``rgb_members`` = m it is [B / m,4,h,w] and
+    member b takes image b // m.  With ``sched`` = (cx, cm, cn, noise) the model
     output is not stored: the scheduler update x_latent <- cx x_latent + cm out + cn noise is conv_out's tail."""
     ws = bld.ws
     boc = list(cfg.block_out_channels)
@@ -921,7 +924,7 @@ def emit_unet_forward(bld, cfg, ctx, rgb_latent, x_latent, eps_out, temb_table, 
     cin = ws.sd["conv_in.weight"].shape[1]
     c_rgb = rgb_latent.shape[1]   # 4 image-latent channels + 4 per predicted modality (IID: 8 / 12)
     x = bld.conv_from_nchw(rgb_latent, x_latent, "conv_in", B, h, w, c_rgb, cin - c_rgb, c0,
-                           bcast0=rgb_latent.shape[0] == 1)
+                           bcast0=not rgb_members and rgb_latent.shape[0] == 1, members0=rgb_members or 0)
     skips = [x]
     force_size = any(d % (2 ** (n - 1)) != 0 for d in (h, w))
     for i in range(n):

@@ -61,6 +61,9 @@ def infer_parser(kind):
     p.add_argument("--maps_in_flight", type=int, default=0,
                    help="Images on the GPU at a time (independent maps on concurrent HIP streams; results do not depend on it); "
                         "0 = the engine's default (2).")
+    p.add_argument("--images_per_program", type=int, default=1,
+                   help="Consecutive images of one processed size that share one denoising program (their members batched); "
+                        "1 = one image per program.")
     return p
 
 
@@ -116,6 +119,8 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
     logging.info(f"Inference settings: checkpoint = `{args.checkpoint}`, with denoise_steps = {args.denoise_steps}, "
                  f"ensemble_size = {args.ensemble_size}, processing resolution = {args.processing_res}, "
                  f"seed = {args.seed}; dataset config = `{args.dataset_config}`.")
+    if args.images_per_program < 1:
+        raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
     seed = int(time.time()) if args.seed is None else args.seed
     seed_all(seed)
     if not _confirm_existing(args.output_dir, args.yes):
@@ -158,6 +163,8 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
                 samples.append(sample)
                 yield Image.fromarray(np.moveaxis(_pipeline_input(kind, sample), 0, -1))
         if hasattr(pipeline, "map_images"):   # the engine: up to --maps_in_flight images on the GPU at a time
+            if args.images_per_program > 1:
+                kw["images_per_program"] = args.images_per_program
             outs = pipeline.map_images(images(), in_flight=args.maps_in_flight or None, generators=(generator_of() for _ in range(n)), **kw)
         else:                                 # an object with the reference pipeline's call surface only
             outs = (pipeline(im, generator=generator_of(), **kw) for im in images())

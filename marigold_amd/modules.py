@@ -133,21 +133,30 @@ class UNet2DConditionModelHIP(_EngineModule):
                     del self.ws.cache[k]
 
     def denoise_program(self, B, h, w, scheduler, n_steps, rgb_broadcast=True, with_scheduler=True,
-                        timesteps=None):
+                        timesteps=None, rgb_members=None):
+        """``rgb_members`` = m: the B members are B / m images with m members each - ``rgb_latent`` is [B / m,4,h,w] and
+        member b is conditioned on image b // m (``rgb_broadcast`` is then ignored); None = one image (``rgb_broadcast``) or
+        one per member."""
         self._require_device()
         if self._ctx is None:
             raise RuntimeError("UNet context not set (set_context)")
+        if rgb_members is not None and (int(rgb_members) < 1 or B % int(rgb_members)):
+            raise ValueError(f"denoise_program: B = {B} is not a multiple of rgb_members = {rgb_members}")
         if timesteps is None:
             scheduler.set_timesteps(n_steps)
             timesteps = [int(t) for t in scheduler.timesteps]
         key = (B, h, w, tuple(timesteps), rgb_broadcast, with_scheduler,
                scheduler.signature() if with_scheduler else None)
+        if rgb_members is not None:
+            rgb_members = int(rgb_members)
+            key = key[:4] + (False,) + key[5:] + (("rgb_members", rgb_members),)
         if key in self._programs:
             return self._programs[key]
         dev = self.device
         seq = self._seq(f"denoise[B={B},{h}x{w},T={len(timesteps)}]")
         bld = E.Builder(seq, self.pool, self.ws, self.config.norm_groups)
-        rgb_latent = torch.zeros(1 if rgb_broadcast else B, 4, h, w, device=dev)
+        n_rgb = B // rgb_members if rgb_members is not None else (1 if rgb_broadcast else B)
+        rgb_latent = torch.zeros(n_rgb, 4, h, w, device=dev)
         x = torch.zeros(B, self.config.out_channels, h, w, device=dev)
         eps = torch.zeros(B, self.config.out_channels, h, w, device=dev)
         seq.hold(rgb_latent, x, eps)
@@ -165,7 +174,8 @@ class UNet2DConditionModelHIP(_EngineModule):
                     nz = seq.hold(torch.zeros(B, self.config.out_channels, h, w, device=dev))
                     noises.append(nz)
                 sched = (cx, cm, cn, nz)
-            E.emit_unet_forward(bld, self.config, self._ctx, rgb_latent, x, eps, table, i, B, h, w, sched=sched)
+            E.emit_unet_forward(bld, self.config, self._ctx, rgb_latent, x, eps, table, i, B, h, w, sched=sched,
+                                rgb_members=rgb_members)
             n_fwd = len(seq) - n0
         seq.keep.extend(bld.persist.values())
         seq.zero_state = {t.data_ptr() for t in bld.persist.values()}   # Builder.zeros_persistent: state the kernels expect zeroed

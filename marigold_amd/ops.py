@@ -164,8 +164,10 @@ def latent_1x1(x, w, b, out, *, B, Ci, Co, HW, scale=1.0):
     return make_op(L.OP_LATENT_1X1, i=[B, Ci, Co, HW], f=[scale], p=[x, w, b, out])
 
 
-def im2col_small(src0, src1, out, *, B, H, W, C0, C1, Kp, bcast0=False):
-    return make_op(L.OP_IM2COL_SMALL, i=[B, H, W, C0, C1, Kp, int(bcast0)], p=[src0, src1, out])
+def im2col_small(src0, src1, out, *, B, H, W, C0, C1, Kp, bcast0=False, members_per_src0=0):
+    """``members_per_src0`` = m > 0: row b reads src0 row b // m (src0 [B / m, C0, H, W]); 0 = ``bcast0`` decides."""
+    i = [B, H, W, C0, C1, Kp, int(bcast0)] + ([int(members_per_src0)] if members_per_src0 else [])
+    return make_op(L.OP_IM2COL_SMALL, i=i, p=[src0, src1, out])
 
 
 def conv3x3_head(x, ss, w, bias, out, *, B, H, W, C, Cout, ldo=0, silu=True):

@@ -9,7 +9,8 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
 * all members of a batch run through one native denoising program (no per-step Python);
 * optional member parallelism over the GPUs of a node (``enable_member_parallel``): members are
   sharded over ranks and collected with ONE gather (RCCL over xGMI) before aggregation;
-* ``init_latents`` (extension) lets callers supply the initial noise for parity runs.
+* ``init_latents`` (extension) lets callers supply the initial noise for parity runs;
+* ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program.
 """
 import logging
 from dataclasses import dataclass
@@ -25,8 +26,8 @@ from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .schedulers import DDIMScheduler, LCMScheduler
 from .util.batchsize import find_batch_size
-from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method, pil_to_tensor,
-                              resize, resize_max_res)
+from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method, max_res_size,
+                              pil_to_tensor, resize, resize_max_res)
 
 
 @dataclass
@@ -194,7 +195,8 @@ class _MarigoldPipelineBase:
             lanes.append((self.replicate(), torch.cuda.Stream(device=self.device)))
         return lanes[:n]
 
-    def map_images(self, images, in_flight: Optional[int] = None, generators=None, **call_kwargs):
+    def map_images(self, images, in_flight: Optional[int] = None, generators=None, images_per_program: int = 1,
+                   **call_kwargs):
         """``(pipe(image, **call_kwargs) for image in images)`` with up to ``in_flight`` maps on the GPU at a time (default
         ``maps_in_flight_for(ensemble_size)``; 1 = one after the other on the caller's stream).  A generator: outputs come in input order
         as they complete, and ``images`` (any iterable) is consumed as lanes become free.  ``generators``: one
@@ -202,57 +204,111 @@ class _MarigoldPipelineBase:
         completion order, so ``generator=`` is refused; every map is then bit-identical to what ``pipe(image, generator=g)``
         returns on its own.  Member-parallel pipelines (several ranks): every rank must call this with the same images and
         ``in_flight``; the lanes then issue their gathers strictly in map order, one at a time (``_Turnstile``), so the collective
-        sequence is the same on every rank whichever lane finishes first."""
-        n = self.maps_in_flight_for(call_kwargs.get("ensemble_size", 1)) if in_flight is None else int(in_flight)
+        sequence is the same on every rank whichever lane finishes first.
+
+        ``images_per_program`` = k > 1: up to k consecutive images of the same processed size share one VAE-encode program, one
+        denoising program of k x ensemble_size members and one decode program (a change of size starts a new group); each image's
+        noise is drawn from its own generator exactly as its lone call draws it, and each image gets the output its lone call
+        returns, up to the arithmetic of the larger batch.  ``in_flight`` then counts programs (default
+        ``maps_in_flight_for(k * ensemble_size)``).  Not with ``init_latents``, a shared ``generator`` or several ranks.  With
+        ``batch_size=0`` a program holds at most 64 members at 768 x 768 (``find_batch_size``; more run as several programs of whole
+        images); each lane keeps workspaces for its program's members."""
+        k = int(images_per_program)
+        if k < 1:
+            raise ValueError(f"images_per_program must be >= 1 (got {images_per_program})")
+        if k > 1:
+            if call_kwargs.get("init_latents") is not None:
+                raise ValueError("map_images: init_latents cannot be combined with images_per_program > 1")
+            if call_kwargs.get("generator") is not None:
+                raise ValueError("map_images: pass `generators` (one per image) instead of a shared `generator` when "
+                                 "images_per_program > 1")
+            if self._sharded():
+                raise ValueError("map_images: images_per_program > 1 is not available on a member-parallel pipeline")
+        n = self.maps_in_flight_for(k * call_kwargs.get("ensemble_size", 1)) if in_flight is None else int(in_flight)
         if n < 1:
             raise ValueError(f"in_flight must be >= 1 (got {in_flight})")
         if generators is not None and hasattr(images, "__len__") and hasattr(generators, "__len__") and len(images) != len(generators):
             raise ValueError(f"{len(generators)} generators for {len(images)} images")
         if hasattr(images, "__len__"):
-            n = min(n, max(1, len(images)))
+            n = min(n, max(1, -(-len(images) // k)))
         if self.device.type != "cuda":
             n = 1
         if n > 1 and call_kwargs.get("generator") is not None:
             raise ValueError("map_images: pass `generators` (one per image) instead of a shared `generator` when in_flight > 1")
-        return self._map_images(iter(images), None if generators is None else iter(generators), n, call_kwargs)
+        return self._map_images(iter(images), None if generators is None else iter(generators), n, call_kwargs, k)
 
-    def _map_images(self, images, generators, n, call_kwargs):
+    def _processed_size(self, image, processing_res):
+        """(height, width) ``_preprocess`` gives ``image``, without resampling it."""
+        if isinstance(image, Image.Image):
+            hw = (image.height, image.width)
+        elif isinstance(image, torch.Tensor):
+            hw = tuple(image.shape[-2:])
+        else:
+            raise TypeError(f"Unknown input type: {type(image) = }")
+        if processing_res is None:
+            processing_res = self.default_processing_resolution
+        return max_res_size(hw, processing_res) if processing_res > 0 else hw
+
+    def _map_images(self, images, generators, n, call_kwargs, per_program=1):
         import threading
         lock = threading.Lock()
         count = [0]
+        held = []   # an image whose processed size ended the previous group: it opens the next one
+
+        def pull():
+            """-> (image, generator) | None: the two iterables advance together"""
+            if held:
+                return held.pop()
+            try:
+                image = next(images)
+            except StopIteration:
+                return None
+            g = None
+            if generators is not None:
+                try:
+                    g = next(generators)
+                except StopIteration:
+                    raise ValueError("map_images: fewer generators than images") from None
+            return image, g
 
         def take():
-            """-> (index, image, generator) | None; under the lock: the two iterables advance together"""
+            """-> (index, [(image, generator)]) | None, under the lock: up to ``per_program`` consecutive images of one
+            processed size"""
             with lock:
-                try:
-                    image = next(images)
-                except StopIteration:
+                first = pull()
+                if first is None:
                     return None
-                g = None
-                if generators is not None:
-                    try:
-                        g = next(generators)
-                    except StopIteration:
-                        raise ValueError("map_images: fewer generators than images") from None
+                group = [first]
+                if per_program > 1:
+                    size = self._processed_size(first[0], call_kwargs.get("processing_res"))
+                    while len(group) < per_program and (item := pull()) is not None:
+                        if self._processed_size(item[0], call_kwargs.get("processing_res")) != size:
+                            held.append(item)
+                            break
+                        group.append(item)
                 k = count[0]
                 count[0] += 1
-                return k, image, g
+                return k, group
 
         turnstile = _Turnstile() if (n > 1 and self._sharded()) else None
 
-        def one(pipe, image, g, k=0):
+        def one(pipe, group, k=0):
+            """-> the outputs of the group's images, in order"""
             kw = dict(call_kwargs)
+            if len(group) > 1:
+                return pipe._call_group([im for im, _ in group], None if generators is None else [g for _, g in group], kw)
+            image, g = group[0]
             if generators is not None:
                 kw["generator"] = g
             pipe._gather_turn = None if turnstile is None else (turnstile, k)
             try:
-                return pipe(image, **kw)
+                return [pipe(image, **kw)]
             finally:
                 pipe._gather_turn = None
 
         if n == 1:
             while (item := take()) is not None:
-                yield one(self, item[1], item[2])
+                yield from one(self, item[1])
             return
         lanes = self._lane_pipelines(n)
         caller = torch.cuda.current_stream(self.device)
@@ -270,7 +326,7 @@ class _MarigoldPipelineBase:
                         item = take()
                         if item is None:
                             break
-                        out = one(pipe, item[1], item[2], item[0])
+                        out = one(pipe, item[1], item[0])
                         with cv:
                             done[item[0]] = out
                             cv.notify_all()
@@ -297,8 +353,8 @@ class _MarigoldPipelineBase:
                         raise done["error"]
                     if k not in done:
                         break   # every lane has finished and map k was never started: the input is exhausted
-                    out = done.pop(k)
-                yield out
+                    outs = done.pop(k)
+                yield from outs
                 k += 1
         finally:
             stop.set()
@@ -349,14 +405,15 @@ class _MarigoldPipelineBase:
     def single_infer(self, rgb_in: torch.Tensor, num_inference_steps: int,
                      generator: Union[torch.Generator, None], show_pbar: bool = False,
                      init_latents: Optional[torch.Tensor] = None,
-                     step_noises: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     step_noises: Optional[torch.Tensor] = None, rgb_members: Optional[int] = None) -> torch.Tensor:
         """One batched prediction (reference :396-477).  rgb_in [B,3,h,w] in [-1,1]; identical
-        (expanded) rows are encoded once."""
+        (expanded) rows are encoded once.  ``rgb_members`` = m: rgb_in holds B distinct images and the batch is their
+        B x m members, image-major (one encode program of B images, one denoising program of B m members)."""
         device = self.device
-        B = rgb_in.shape[0]
-        shared = B == 1 or rgb_in.stride(0) == 0
+        B = rgb_in.shape[0] if rgb_members is None else rgb_in.shape[0] * rgb_members
+        shared = rgb_members is None and (B == 1 or rgb_in.stride(0) == 0)
         rgb_in = (rgb_in[:1] if shared else rgb_in).to(device)
-        rgb_latent = self.encode_rgb(rgb_in)                       # [1|B,4,h,w] fp32
+        rgb_latent = self.encode_rgb(rgb_in)                       # [1|B|B/m,4,h,w] fp32
         h, w = rgb_latent.shape[-2:]
         if init_latents is None:
             target_latent = self._randn((B, self._target_latent_channels, h, w), generator)
@@ -366,7 +423,7 @@ class _MarigoldPipelineBase:
             self.encode_empty_text()
         self.unet.set_context(self.empty_text_embed)
         prog = self.unet.denoise_program(B, h, w, self.scheduler, num_inference_steps,
-                                         rgb_broadcast=shared)
+                                         rgb_broadcast=shared, rgb_members=rgb_members)
         prog.rgb_latent.copy_(rgb_latent)
         prog.x.copy_(target_latent)
         for k, nz in enumerate(prog.noises):  # LCM consumes the generator once per non-final step (:466-468)
@@ -430,6 +487,84 @@ class _MarigoldPipelineBase:
                     turn[0].done(turn[1])
         return local
 
+    def _predict_group(self, rgb_norms, ensemble_size, denoising_steps, batch_size, generators):
+        """The E members of each of k images of one processed size -> [k E,C,h,w], image-major.  Image i's initial latents and
+        LCM step noises come from ``generators[i]`` in the order and shapes of its lone call (``_predict_members``: per batch of
+        the lone batch size, the initial latents, then one draw per noised step); the members then run as programs of whole
+        images (k E members, or as many images as ``batch_size`` holds), or - when one image's members exceed ``batch_size`` -
+        image by image in batches of ``batch_size``."""
+        E, k = ensemble_size, len(rgb_norms)
+        res = max(rgb_norms[0].shape[1:])
+        hh, ww = self._latent_hw(rgb_norms[0].shape[-2:])
+        C = self._target_latent_channels
+        self.scheduler.set_timesteps(denoising_steps)
+        n_noise = sum(bool(self.scheduler.needs_noise(i)) for i in range(denoising_steps))
+        lone_bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size=E, input_res=res, dtype=self.dtype)
+        lats, noises = [], [[] for _ in range(n_noise)]
+        for g in generators:
+            for i in range(0, E, lone_bs):
+                m = min(lone_bs, E - i)
+                lats.append(self._randn((m, C, hh, ww), g))
+                for s in range(n_noise):
+                    noises[s].append(self._randn((m, C, hh, ww), g))
+        init = torch.cat(lats, dim=0)
+        noises = [torch.cat(z, dim=0) for z in noises]
+        rgb = torch.cat([r.to(self.device) for r in rgb_norms], dim=0)   # [k,3,h,w]
+        _bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size=k * E, input_res=res, dtype=self.dtype)
+        if _bs >= E:
+            runs = [(j, min(k, j + _bs // E), 0, E) for j in range(0, k, _bs // E)]   # (first image, end image, members)
+        else:
+            runs = [(j, j + 1, i, min(E, i + _bs)) for j in range(k) for i in range(0, E, _bs)]
+        preds = []
+        for j0, j1, m0, m1 in runs:
+            if j1 - j0 == 1:   # one image: the lone call's program
+                rows = slice(j0 * E + m0, j0 * E + m1)
+                preds.append(self.single_infer(rgb[j0:j1].expand(m1 - m0, -1, -1, -1), denoising_steps, None, False,
+                                               init[rows], step_noises=[z[rows] for z in noises]))
+            else:
+                rows = slice(j0 * E, j1 * E)
+                preds.append(self.single_infer(rgb[j0:j1], denoising_steps, None, False, init[rows],
+                                               step_noises=[z[rows] for z in noises], rgb_members=E))
+        return torch.cat(preds, dim=0) if len(preds) > 1 else preds[0]
+
+    _call_args = ("denoising_steps", "ensemble_size", "processing_res", "match_input_res", "resample_method", "batch_size",
+                  "show_progress_bar", "ensemble_kwargs")
+
+    @torch.no_grad()
+    def _call_group(self, images, generators, call_kwargs):
+        """[pipe(image, generator=g, **call_kwargs) for image, g in zip(images, generators)] with the images' members in shared
+        programs (``map_images(images_per_program=k)``): every image preprocessed as ``__call__`` does (one processed size),
+        one ``_predict_group``, then ``__call__``'s tail per image on its own [E, ...] slice."""
+        kw = dict(call_kwargs)
+        unknown = set(kw) - set(self._call_args) - set(self._finish_args)
+        if unknown:
+            raise TypeError(f"{type(self).__name__}() got unexpected keyword arguments {sorted(unknown)}")
+        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
+            kw.get("denoising_steps"), kw.get("ensemble_size", 1), kw.get("processing_res"), kw.get("resample_method", "bilinear"))
+        prepared = [self._preprocess(im, processing_res, resample) for im in images]
+        sizes = {tuple(r.shape[-2:]) for r, _ in prepared}
+        if len(sizes) != 1:
+            raise ValueError(f"images of one program must have one processed size, got {sorted(sizes)}")
+        preds = self._predict_group([r for r, _ in prepared], ensemble_size, denoising_steps, kw.get("batch_size", 0),
+                                    [None] * len(images) if generators is None else list(generators))
+        E = ensemble_size
+        finish = {a: kw[a] for a in self._finish_args if a in kw}
+        return [self._finish(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
+                             kw.get("ensemble_kwargs"), **finish) for j, (_, input_size) in enumerate(prepared)]
+
+    _finish_args = ()
+
+    def _call_settings(self, denoising_steps, ensemble_size, processing_res, resample_method):
+        """``__call__``'s defaults and argument checks -> (denoising_steps, ensemble_size, processing_res, resample mode)."""
+        if denoising_steps is None:
+            denoising_steps = self.default_denoising_steps
+        if processing_res is None:
+            processing_res = self.default_processing_resolution
+        assert processing_res >= 0
+        assert ensemble_size >= 1
+        self._check_inference_step(denoising_steps)
+        return denoising_steps, ensemble_size, processing_res, get_tv_resample_method(resample_method)
+
     def _latent_hw(self, hw):
         h, w = hw
         for _ in range(len(self.vae.config.block_out_channels) - 1):
@@ -483,18 +618,20 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, color_map: str = "Spectral",
                  show_progress_bar: bool = True, ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None) -> MarigoldDepthOutput:
-        if denoising_steps is None:
-            denoising_steps = self.default_denoising_steps
-        if processing_res is None:
-            processing_res = self.default_processing_resolution
-        assert processing_res >= 0
-        assert ensemble_size >= 1
-        self._check_inference_step(denoising_steps)
-        resample = get_tv_resample_method(resample_method)
+        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
+            denoising_steps, ensemble_size, processing_res, resample_method)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
+                            color_map=color_map)
+
+    _finish_args = ("color_map",)
+
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
+                color_map="Spectral") -> MarigoldDepthOutput:
+        """``__call__``'s tail: the members of one image -> its output."""
         if target_preds is None:  # member-parallel non-root rank with a rooted gather
             return MarigoldDepthOutput(depth_np=None, depth_colored=None, uncertainty=None)
         if ensemble_size > 1:
@@ -557,18 +694,17 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None) -> MarigoldNormalsOutput:
-        if denoising_steps is None:
-            denoising_steps = self.default_denoising_steps
-        if processing_res is None:
-            processing_res = self.default_processing_resolution
-        assert processing_res >= 0
-        assert ensemble_size >= 1
-        self._check_inference_step(denoising_steps)
-        resample = get_tv_resample_method(resample_method)
+        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
+            denoising_steps, ensemble_size, processing_res, resample_method)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
+
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
+                ensemble_kwargs) -> MarigoldNormalsOutput:
+        """``__call__``'s tail: the members of one image -> its output."""
         if target_preds is None:
             return MarigoldNormalsOutput(normals_np=None, normals_img=None, uncertainty=None)
         if ensemble_size > 1:
@@ -690,17 +826,16 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None) -> MarigoldIIDOutput:
-        if denoising_steps is None:
-            denoising_steps = self.default_denoising_steps
-        if processing_res is None:
-            processing_res = self.default_processing_resolution
-        assert processing_res >= 0
-        assert ensemble_size >= 1
-        self._check_inference_step(denoising_steps)
-        resample = get_tv_resample_method(resample_method)
+        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
+            denoising_steps, ensemble_size, processing_res, resample_method)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size, generator,
                                              init_latents)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
+
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
+                ensemble_kwargs) -> MarigoldIIDOutput:
+        """``__call__``'s tail: the members of one image -> its output."""
         output = MarigoldIIDOutput(target_names=self.target_names)
         if target_preds is None:   # member-parallel non-root rank with a rooted gather
             return output

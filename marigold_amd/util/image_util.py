@@ -66,11 +66,16 @@ def resize_max_res(img: torch.Tensor, max_edge_resolution: int,
     """Resize so the longer edge equals ``max_edge_resolution`` (may up-scale; no rounding to a
     multiple of 8) - reference :90-120."""
     assert 4 == img.dim(), f"Invalid input shape {img.shape}"
-    original_height, original_width = img.shape[-2:]
+    return resize(img, max_res_size(img.shape[-2:], max_edge_resolution), resample_method, antialias=True)
+
+
+def max_res_size(hw, max_edge_resolution: int):
+    """(height, width) that ``resize_max_res`` resizes an image of size ``hw`` to."""
+    original_height, original_width = hw
     downscale_factor = min(max_edge_resolution / original_width, max_edge_resolution / original_height)
     new_width = int(original_width * downscale_factor)
     new_height = int(original_height * downscale_factor)
-    return resize(img, (new_height, new_width), resample_method, antialias=True)
+    return new_height, new_width
 
 
 def get_tv_resample_method(method_str: str) -> InterpolationMode:
