@@ -161,7 +161,9 @@ enum mg_op_kind {
   MG_OP_LATENT_1X1 = 14,
   /* Pointwise tail of a small-Cout convolution computed by MG_OP_IGEMM into a padded fp32 buffer:
    * out NCHW = post(in[m][0..Cout) * f[0]): MG_POST_DEPTH = mean over channels, clip, (x+1)/2 (marigold_depth_
-   * pipeline.py:515,473-475); MG_POST_NORMALS = clip, L2 normalise (marigold_normals_pipeline.py:438-440); MG_POST_UNIT;
+   * pipeline.py:515,473-475); MG_POST_NORMALS = clip, L2 normalise (marigold_normals_pipeline.py:438-440); MG_POST_UNIT.
+   * The clip to [-1, 1] and the normalise's 1e-6 floor of the norm keep NaN, like torch.clip / clamp(min=eps) (+-inf clip to
+   * +-1): a NaN channel gives a NaN depth (DEPTH), a NaN pixel in all channels (NORMALS), a NaN in that channel (UNIT, NONE);
    * MG_POST_SCHED = the DDIM / LCM update of MG_OP_SCHED_STEP applied to conv_out's result in place of storing it:
    * out <- f[1]*out + f[2]*in + f[3]*noise (out = the latent x_t, NCHW; marigold_depth_pipeline.py:466-468).
    *  p[0] in f32 [B*HW][ldi]  p[1] out f32 NCHW  p[2] noise f32 NCHW | NULL (MG_POST_SCHED) ;

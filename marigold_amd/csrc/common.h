@@ -35,6 +35,23 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #endif
 constexpr float MG_OP16_MAX = MG_F16 ? 65504.0f : 3.3895314e38f;   // largest finite operand value
 
+// Clamps, minima and maxima that KEEP NaN, as torch.clip / clamp(min=) / .min() / .max() do: fminf / fmaxf return the other operand
+// (fmaxf(NaN, -1) = -1; v_med3_f32 returns min3 on a NaN), and everything after the decoder's last convolution must hand a
+// non-finite value on as the reference does, never turn it into a plausible finite one.  Finite operands: the same bits.
+__device__ __forceinline__ float clip_keep_nan(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ float floor_keep_nan(float x, float lo) { return x != x ? x : fmaxf(x, lo); }
+// IEEE 754-2019 minimum / maximum: one instruction each on gfx950 (v_minimum3_f32 / v_maximum3_f32), the price of fminf / fmaxf
+__device__ __forceinline__ float min_keep_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// the running (value, pixel) extremum of the ensembling passes: does candidate (o, op) replace (m, p)?  A NaN beats every number
+// (torch's .min() / .max() / argmin / argmax), equal values - and NaN among themselves - go to the lowest pixel
+__device__ __forceinline__ bool takes_min(float o, long long op, float m, long long p) {
+  return o < m || (o != o && m == m) || ((o == m || (o != o && m != m)) && op < p);
+}
+__device__ __forceinline__ bool takes_max(float o, long long op, float m, long long p) {
+  return o > m || (o != o && m == m) || ((o == m || (o != o && m != m)) && op < p);
+}
+
 typedef __attribute__((ext_vector_type(8))) _Float16 mg_f16x8_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 mg_bf16x8_t;
 __device__ __forceinline__ f32x16 mg_mfma32(bf16x8 a, bf16x8 b, f32x16 c) {   // D = A (32 x 16) B (16 x 32) + C

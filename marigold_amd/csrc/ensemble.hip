@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void depth_stats_kernel(const float* __restric
   float acc[EMAX];
 #pragma unroll
   for (int j = 0; j < EMAX; ++j) acc[j] = 0.f;
-  float mn = 3.0e38f, mx = -3.0e38f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();   // (min / max keep NaN, like the reference's flat.min() / .max())
   double sum = 0.0;
   // fp32 partials over short strides, promoted to fp64 every 64 pixels per thread
   double accd[EMAX];
@@ -51,8 +51,8 @@ __global__ __launch_bounds__(256) void depth_stats_kernel(const float* __restric
   int cnt = 0;
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
     const float di = di_row[p];
-    mn = fminf(mn, di);
-    mx = fmaxf(mx, di);
+    mn = min_keep_nan(mn, di);
+    mx = max_keep_nan(mx, di);
     sum += (double)di;
 #pragma unroll
     for (int j = 0; j < EMAX; ++j)
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256) void depth_stats_kernel(const float* __restric
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o));
-    mx = fmaxf(mx, __shfl_xor(mx, o));
+    mn = min_keep_nan(mn, __shfl_xor(mn, o));
+    mx = max_keep_nan(mx, __shfl_xor(mx, o));
     sum += __shfl_xor(sum, o);
 #pragma unroll
     for (int j = 0; j < EMAX; ++j)
@@ -85,8 +85,8 @@ __global__ __launch_bounds__(256) void depth_stats_kernel(const float* __restric
   double* o = part + ((long long)blockIdx.x * Etot + i) * (Etot + 3);
   for (int k = threadIdx.x; k < E + 3; k += 256) {
     double v;
-    if (k == 0) v = fmin(fmin(red[0][0], red[1][0]), fmin(red[2][0], red[3][0]));
-    else if (k == 1) v = fmax(fmax(red[0][1], red[1][1]), fmax(red[2][1], red[3][1]));
+    if (k == 0) v = (double)min_keep_nan(min_keep_nan((float)red[0][0], (float)red[1][0]), min_keep_nan((float)red[2][0], (float)red[3][0]));   // (floats, held as doubles: exact)
+    else if (k == 1) v = (double)max_keep_nan(max_keep_nan((float)red[0][1], (float)red[1][1]), max_keep_nan((float)red[2][1], (float)red[3][1]));
     else v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
     if (k < 3) { if (j0 == 0) o[k] = v; }       // min / max / sum of row i: once
     else o[3 + j0 + (k - 3)] = v;
@@ -101,11 +101,11 @@ __global__ __launch_bounds__(256) void depth_stats_final_kernel(const double* __
   const int tid = threadIdx.x;
   for (int idx = tid; idx < E * 3; idx += 256) {
     const int i = idx / 3, k = idx % 3;
-    double v = (k == 0) ? 3.0e38 : (k == 1 ? -3.0e38 : 0.0);
+    double v = (k == 0) ? (double)__builtin_inff() : (k == 1 ? -(double)__builtin_inff() : 0.0);
     for (int b = 0; b < nblk; ++b) {
       const double x = part[((long long)b * E + i) * (E + 3) + k];
-      if (k == 0) v = fmin(v, x);
-      else if (k == 1) v = fmax(v, x);
+      if (k == 0) v = (double)min_keep_nan((float)v, (float)x);   // (the members' own floats: exact)
+      else if (k == 1) v = (double)max_keep_nan((float)v, (float)x);
       else v += x;
     }
     if (k == 0) out[i] = v;
@@ -140,12 +140,14 @@ __device__ __forceinline__ float select_rank(const float (&a)[E_], int E, int k)
 
 // The benchmark's ensemble size: k-th smallest of <= 10 values through the 29-comparator sorting network (Knuth, TAOCP 3, n = 10;
 // 58 min / max against ~300 compare / add of the rank count above).  Entries past E are +inf; the VALUE of rank k under
-// (value, index) order is the k-th order statistic, whichever way ties are broken.
+// (value, index) order is the k-th order statistic, whichever way ties are broken.  torch.median propagates NaN and so does the
+// network: its comparators are IEEE minimum / maximum (v_minimum3_f32 / v_maximum3_f32, the price of v_min_f32 / v_max_f32), which
+// return NaN on both wires when either input is one - and every output of a sorting network is reached from every input.
 __device__ __forceinline__ float select_kth10(const float (&v)[10], int E, int k) {
   float a[10];
 #pragma unroll
   for (int e = 0; e < 10; ++e) a[e] = e < E ? v[e] : __builtin_inff();
-#define MG_CE(i, j) { const float lo = fminf(a[i], a[j]), hi = fmaxf(a[i], a[j]); a[i] = lo; a[j] = hi; }
+#define MG_CE(i, j) { const float lo = min_keep_nan(a[i], a[j]), hi = max_keep_nan(a[i], a[j]); a[i] = lo; a[j] = hi; }
   MG_CE(4, 9) MG_CE(3, 8) MG_CE(2, 7) MG_CE(1, 6) MG_CE(0, 5) MG_CE(1, 4) MG_CE(6, 9) MG_CE(0, 3) MG_CE(5, 8) MG_CE(0, 2)
   MG_CE(3, 6) MG_CE(7, 9) MG_CE(0, 1) MG_CE(2, 4) MG_CE(5, 7) MG_CE(8, 9) MG_CE(1, 2) MG_CE(4, 6) MG_CE(7, 8) MG_CE(3, 5)
   MG_CE(2, 5) MG_CE(6, 8) MG_CE(1, 3) MG_CE(4, 7) MG_CE(2, 3) MG_CE(6, 7) MG_CE(3, 4) MG_CE(5, 6) MG_CE(4, 5)
@@ -156,10 +158,21 @@ __device__ __forceinline__ float select_kth10(const float (&v)[10], int E, int k
     if (e == k) r = a[e];
   return r;
 }
+// torch.median propagates NaN: a NaN among the members makes the order statistic NaN.  The rank count would not (its < and == are
+// false on a NaN), so a NaN test stands beside it: one unordered compare per PAIR of values (entries past E are numbers),
+// branch-free, the count itself unchanged.
+template <int E_>
+__device__ __forceinline__ bool any_nan(const float (&a)[E_]) {
+  static_assert(E_ % 2 == 0, "any_nan: pairs");
+  bool r = false;
+#pragma unroll
+  for (int e = 0; e < E_; e += 2) r |= __builtin_isunordered(a[e], a[e + 1]);
+  return r;
+}
 template <int E_>
 __device__ __forceinline__ float select_kth(const float (&a)[E_], int E, int k) {
   if constexpr (E_ == 10) return select_kth10(a, E, k);
-  else return select_rank<E_>(a, E, k);
+  else return any_nan<E_>(a) ? __builtin_nanf("") : select_rank<E_>(a, E, k);
 }
 
 // E_ = compile-time upper bound of E (registers); st = [s[E], t[E]] fp32; reduction 0 median 1 mean
@@ -177,8 +190,11 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
   for (int e = 0; e < E_; ++e) {
     sc[e] = (aligned && e < E) ? st[e] : 1.f;
     sh[e] = (aligned && has_shift && e < E) ? st[E + e] : 0.f;
+    // keep the 2 E_ parameters in vector registers: as scalars they compete with the loops' condition masks, and once they no
+    // longer fit the compiler parks them in VGPR lanes and reads each back (v_readlane + wait states) before every use
+    asm volatile("" : "+v"(sc[e]), "+v"(sh[e]));
   }
-  float mn = 3.0e38f, mx = -3.0e38f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
   const int k = (E - 1) >> 1;  // torch.median: lower middle
   auto pixel = [&](const float (&raw)[E_], long long p, float& pred, float& unc) {
     float a[E_];
@@ -211,6 +227,12 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
     if (pred < mn) { mn = pred; pmn = p; }
     if (pred > mx) { mx = pred; pmx = p; }
   };
+  // a NaN prediction makes min and max NaN (torch's .min() / .max()): both comparisons above are false on it, so the loops only
+  // note that one occurred - an IEEE minimum over the predictions, which a NaN poisons: vector operations on one register, no
+  // condition mask held across the loop (this pass runs ~100 times per map and is short of scalar registers) - and the thread's
+  // extrema become NaN after them.  The members reported beside NaN extrema are those of pixel 0: the regulariser's sub-gradient
+  // means nothing on a NaN cost.
+  float nan_acc = 0.f;
   // four consecutive pixels per thread and pass (16-byte loads, E of them in flight): the optimiser calls this pass ~100 times
   // per map and as one pixel per thread it was 4-5 dependent HBM round trips long (19 us for 23.6 MB; round 3)
   const long long HW4 = (HW & 3) == 0 && (((uintptr_t)d | (uintptr_t)med | (uintptr_t)mad) & 15) == 0 ? HW : 0;
@@ -226,6 +248,7 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
       for (int e = 0; e < E_; ++e) raw[e] = i == 0 ? v[e].x : (i == 1 ? v[e].y : (i == 2 ? v[e].z : v[e].w));
       pixel(raw, p + i, pr[i], un[i]);
     }
+    nan_acc = min_keep_nan(min_keep_nan(nan_acc, pr[0]), min_keep_nan(min_keep_nan(pr[1], pr[2]), pr[3]));
     if (med) *(float4*)(med + p) = make_float4(pr[0], pr[1], pr[2], pr[3]);
     if (mad) *(float4*)(mad + p) = make_float4(un[0], un[1], un[2], un[3]);
   }
@@ -235,23 +258,25 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
     for (int e = 0; e < E_; ++e) raw[e] = e < E ? d[(long long)e * HW + p] : 0.f;
     float pred, unc;
     pixel(raw, p, pred, unc);
+    nan_acc = min_keep_nan(nan_acc, pred);
     if (med) med[p] = pred;
     if (mad) mad[p] = unc;
   }
+  if (nan_acc != nan_acc) { mn = mx = nan_acc; pmn = pmx = 0; }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
     const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
-    if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
+    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
+    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
   }
   if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w) {
-      if (red[w] < red[0] || (red[w] == red[0] && redp[w] < redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (red[4 + w] > red[4] || (red[4 + w] == red[4] && redp[4 + w] < redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
+      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
+      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
     }
     blockmm[2 * blockIdx.x] = red[0];
     blockmm[2 * blockIdx.x + 1] = red[4];
@@ -279,15 +304,18 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
   }
   __syncthreads();
   long long pmn = 0, pmx = 0;
-  float mn = 3.0e38f, mx = -3.0e38f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
   const int k = (E - 1) >> 1;
+  bool saw_nan = false;
   // element of rank k (ties by member index), as select_rank; DEV: of the absolute deviations |a - centre| (formed on the
   // fly: a second [E][256] array would not fit the 160 KB of LDS)
   auto select = [&](bool dev_, float centre) {
     auto val = [&](int e) { const float x = a[e * 256]; return dev_ ? fabsf(__fsub_rn(x, centre)) : x; };
     float res = val(0);
+    bool nan = false;   // torch.median: a NaN member makes the statistic NaN
     for (int e = 0; e < E; ++e) {
       const float ve = val(e);
+      nan |= ve != ve;
       int rank = 0;
       for (int j = 0; j < E; ++j) {
         const float vj = val(j);
@@ -295,7 +323,7 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
       }
       if (rank == k) res = ve;
     }
-    return res;
+    return nan ? __builtin_nanf("") : res;
   };
   for (long long p = (long long)blockIdx.x * 256 + tid; p < HW; p += (long long)gridDim.x * 256) {
     for (int e = 0; e < E; ++e) {
@@ -320,21 +348,23 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
     if (mad) mad[p] = unc;
     if (pred < mn) { mn = pred; pmn = p; }
     if (pred > mx) { mx = pred; pmx = p; }
+    saw_nan |= pred != pred;   // NaN extrema, pixel 0: as depth_median_kernel
   }
+  if (saw_nan) { mn = mx = __builtin_nanf(""); pmn = pmx = 0; }
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
     const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
-    if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
+    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
+    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
   }
   if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) {
-      if (red[w] < red[0] || (red[w] == red[0] && redp[w] < redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (red[4 + w] > red[4] || (red[4 + w] == red[4] && redp[4 + w] < redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
+      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
+      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
     }
     blockmm[2 * blockIdx.x] = red[0];
     blockmm[2 * blockIdx.x + 1] = red[4];
@@ -355,8 +385,9 @@ __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __re
   __shared__ long long redp[8];
   const int tid = threadIdx.x;
   long long pmn = 0, pmx = 0;
-  float mn = 3.0e38f, mx = -3.0e38f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
   const int k = (E - 1) >> 1;
+  bool saw_nan = false;
   auto key_of = [](float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
   auto val_of = [](unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); };
   for (long long p = (long long)blockIdx.x * 256 + tid; p < HW; p += (long long)gridDim.x * 256) {
@@ -367,6 +398,12 @@ __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __re
     auto select = [&](bool dev_, float centre) {
       unsigned prefix = 0;
       int kk = k;
+      bool nan = false;   // torch.median: a NaN member makes the statistic NaN (as a key it would sort past +-inf)
+      for (int e = 0; e < E; ++e) {
+        const float x = aval(e);
+        const float v = dev_ ? fabsf(__fsub_rn(x, centre)) : x;
+        nan |= v != v;
+      }
       for (int bit = 31; bit >= 0; --bit) {
         const unsigned hi_mask = bit == 31 ? 0u : ~((2u << bit) - 1u);   // the bits already decided
         int cnt0 = 0;
@@ -377,7 +414,7 @@ __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __re
         }
         if (kk >= cnt0) { kk -= cnt0; prefix |= 1u << bit; }
       }
-      return val_of(prefix);
+      return nan ? __builtin_nanf("") : val_of(prefix);
     };
     float pred, unc = 0.f;
     if (reduction == 0) {
@@ -397,21 +434,23 @@ __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __re
     if (mad) mad[p] = unc;
     if (pred < mn) { mn = pred; pmn = p; }
     if (pred > mx) { mx = pred; pmx = p; }
+    saw_nan |= pred != pred;   // NaN extrema, pixel 0: as depth_median_kernel
   }
+  if (saw_nan) { mn = mx = __builtin_nanf(""); pmn = pmx = 0; }
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
     const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
-    if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
+    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
+    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
   }
   if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < 4; ++w) {
-      if (red[w] < red[0] || (red[w] == red[0] && redp[w] < redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (red[4 + w] > red[4] || (red[4 + w] == red[4] && redp[4 + w] < redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
+      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
+      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
     }
     blockmm[2 * blockIdx.x] = red[0];
     blockmm[2 * blockIdx.x + 1] = red[4];
@@ -429,24 +468,44 @@ __global__ __launch_bounds__(64) void minmax_final_kernel(const float* __restric
   __shared__ long long px[2];
   // one wave: strided scan of the per-block results, then a lane reduction (ties -> lowest pixel)
   const int lane = threadIdx.x;
-  float mn = 3.0e38f, mx = -3.0e38f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
   long long pmn = 0x7fffffffffffffffll, pmx = 0x7fffffffffffffffll;
+  bool nan = false;
   for (int i = lane; i < nblk; i += 64) {
     const float a = blockmm[2 * i], b = blockmm[2 * i + 1];
     const long long pa = blockpx[2 * i], pb = blockpx[2 * i + 1];
+    nan |= __builtin_isunordered(a, b);
     if (a < mn || (a == mn && pa < pmn)) { mn = a; pmn = pa; }
     if (b > mx || (b == mx && pb < pmx)) { mx = b; pmx = pb; }
   }
+  if (__any(nan)) {   // a block saw a NaN prediction: the scan again in the order that puts a NaN first (wave-uniform, rarely taken)
+    mn = __builtin_inff(); mx = -__builtin_inff();
+    pmn = pmx = 0x7fffffffffffffffll;
+    for (int i = lane; i < nblk; i += 64) {
+      const float a = blockmm[2 * i], b = blockmm[2 * i + 1];
+      const long long pa = blockpx[2 * i], pb = blockpx[2 * i + 1];
+      if (takes_min(a, pa, mn, pmn)) { mn = a; pmn = pa; }
+      if (takes_max(b, pb, mx, pmx)) { mx = b; pmx = pb; }
+    }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-    const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
-    if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
+    for (int o = 32; o > 0; o >>= 1) {
+      const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
+      const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
+      if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
+      if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
+    }
+  } else {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
+      const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
+      if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
+      if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
+    }
   }
   if (lane == 0) {
     out[0] = mn; out[1] = mx;
-    px[0] = pmn; px[1] = pmx;
+    px[0] = pmn < HW ? pmn : 0; px[1] = pmx < HW ? pmx : 0;   // (every block reports a pixel of the map; never read past it)
   }
   __syncthreads();
   for (int e = lane; e < E; e += 64) {
@@ -459,7 +518,7 @@ __global__ __launch_bounds__(256) void depth_norm_kernel(float* __restrict__ med
                                                          const float* __restrict__ mm, long long HW, int shift_inv) {
   const float hi = mm[1];
   const float lo = shift_inv ? mm[0] : 0.f;
-  const float rng = fmaxf(hi - lo, 1e-6f);
+  const float rng = floor_keep_nan(hi - lo, 1e-6f);   // (hi - lo).clamp(min=1e-6): NaN extrema make a NaN map, as in the reference
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
     med[p] = (med[p] - lo) / rng;
     if (unc) unc[p] = unc[p] / rng;
@@ -476,14 +535,14 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
     }
     float mx_ = sx / (float)E, my = sy / (float)E, mz = sz / (float)E;
     const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(mx_, mx_), __fmul_rn(my, my)), __fmul_rn(mz, mz)));
-    const float den = fmaxf(nrm, 1e-6f);
+    const float den = floor_keep_nan(nrm, 1e-6f);
     mx_ = mx_ / den; my = my / den; mz = mz / den;
     float best = -2.f, ua = 0.f;
     int bi = 0;
     for (int e = 0; e < E; ++e) {
       const float* q = n + (long long)e * 3 * HW + p;
       float c = __fadd_rn(__fadd_rn(__fmul_rn(mx_, q[0]), __fmul_rn(my, q[HW])), __fmul_rn(mz, q[2 * HW]));
-      c = fminf(fmaxf(c, -1.f), 1.f);
+      c = clip_keep_nan(c, -1.f, 1.f);   // NaN cosines: no member is closer than member 0 (torch's argmax), the uncertainty is NaN
       if (c > best) { best = c; bi = e; }
       ua += acosf(c);
     }

@@ -162,16 +162,16 @@ __global__ __launch_bounds__(256) void post_nchw_kernel(const float* __restrict_
 #pragma unroll
       for (int co = 0; co < COUT; ++co) m += acc[co];
       m = m / (float)COUT;
-      m = fminf(fmaxf(m, -1.f), 1.f);
+      m = clip_keep_nan(m, -1.f, 1.f);   // torch.clip: a NaN stays a NaN
       out[b * HW + p] = (m + 1.0f) * 0.5f;
     } else if (post == MG_POST_NORMALS) {
       float n2 = 0.f;
 #pragma unroll
       for (int co = 0; co < COUT; ++co) {
-        acc[co] = fminf(fmaxf(acc[co], -1.f), 1.f);
+        acc[co] = clip_keep_nan(acc[co], -1.f, 1.f);
         n2 += acc[co] * acc[co];
       }
-      const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-6f);
+      const float inv = 1.0f / floor_keep_nan(sqrtf(n2), 1e-6f);   // norm.clamp(min=eps) of a NaN norm is NaN
 #pragma unroll
       for (int co = 0; co < COUT; ++co) out[(b * COUT + co) * HW + p] = acc[co] * inv;
     } else if (post == MG_POST_SCHED) {
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void post_nchw_kernel(const float* __restrict_
     } else if (post == MG_POST_UNIT) {   // IID: clip to [-1,1], shift to [0,1] (marigold_iid_pipeline.py:523-526)
 #pragma unroll
       for (int co = 0; co < COUT; ++co)
-        out[(b * COUT + co) * HW + p] = (fminf(fmaxf(acc[co], -1.f), 1.f) + 1.0f) * 0.5f;
+        out[(b * COUT + co) * HW + p] = (clip_keep_nan(acc[co], -1.f, 1.f) + 1.0f) * 0.5f;
     } else {
 #pragma unroll
       for (int co = 0; co < COUT; ++co) out[(b * COUT + co) * HW + p] = acc[co];

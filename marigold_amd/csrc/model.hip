@@ -354,11 +354,11 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
       const float lo = (float)dmin[i], hi = (float)dmax[i];
       if (affine) {
         const float rng = hi - lo;
-        const float sc = 1.0f / (rng > 1e-6f ? rng : 1e-6f);
+        const float sc = 1.0f / (rng < 1e-6f ? 1e-6f : rng);   // clamp(min=1e-6): a NaN range stays NaN, as in ensemble.py::init_param
         x[i] = (double)sc;
         x[E + i] = (double)(-sc * lo);
       } else {
-        x[i] = (double)(1.0f / (hi > 1e-6f ? hi : 1e-6f));
+        x[i] = (double)(1.0f / (hi < 1e-6f ? 1e-6f : hi));
       }
     }
     x0 = x;

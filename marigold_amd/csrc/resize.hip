@@ -106,12 +106,13 @@ __global__ __launch_bounds__(256) void colorize_kernel(const float* __restrict__
   __syncthreads();
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     float x = (depth[i] - lo) * inv_range;
+    const bool bad = x != x;   // matplotlib's "bad" colour, RGBA (0, 0, 0, 0): a NaN depth is a black pixel, not entry 0 of the table
     x = fminf(fmaxf(x, 0.f), 1.f);
     int k = (int)(x * 256.0f);
     k = k > 255 ? 255 : k;
-    out[3 * i + 0] = tab[3 * k + 0];
-    out[3 * i + 1] = tab[3 * k + 1];
-    out[3 * i + 2] = tab[3 * k + 2];
+    out[3 * i + 0] = bad ? (uint8_t)0 : tab[3 * k + 0];
+    out[3 * i + 1] = bad ? (uint8_t)0 : tab[3 * k + 1];
+    out[3 * i + 2] = bad ? (uint8_t)0 : tab[3 * k + 2];
   }
 }
 

@@ -1951,8 +1951,10 @@ def test_colorize_lut_matches_reference_chain(dev, cmap):
     g = torch.Generator().manual_seed(3)
     d = torch.rand(37, 53, generator=g)
     d[0, 0], d[0, 1], d[0, 2] = 1.0, 0.0, 1.5    # ends of the table and a value the clip must catch
+    d[0, 3] = float("nan")                       # matplotlib's "bad" colour: RGB (0, 0, 0), not an entry of the table
     ref = (iu.colorize_depth_maps(d.numpy(), 0, 1, cmap=cmap).squeeze() * 255).astype(np.uint8)   # [3,H,W]
     got = iu.colorize_depth_device(d.to(dev), 0.0, 1.0, cmap=cmap).cpu().numpy()                  # [H,W,3]
+    assert tuple(ref[:, 0, 3]) == (0, 0, 0)
     assert got.shape == (37, 53, 3) and np.array_equal(np.moveaxis(got, -1, 0), ref)
 
 

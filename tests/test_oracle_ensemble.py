@@ -137,3 +137,51 @@ def test_iid(gold, red):
     np.testing.assert_allclose(u.numpy(), gold[f"iid_{red}_unc"], atol=1e-7)
     with pytest.raises(ValueError):
         oens.ensemble_iid(x, reduction="max")
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "+inf"])
+def test_non_finite_input_semantics(bad):
+    """What the reference's ensembling does with ONE non-finite pixel in ONE of five members at 24 x 32 - the semantics the
+    engine follows (tests/test_gpu_output_stage.py takes its masks from these functions at run time).  torch's
+    median, mean, std, clip, .min() and .max() all propagate NaN: nothing turns the fault into a plausible finite value."""
+    import warnings
+    g = torch.Generator().manual_seed(11)
+    E, H, W, e, y, x = 5, 24, 32, 2, 11, 17
+    d = torch.rand(E, 1, H, W, generator=g)
+    d[e, 0, y, x] = bad
+    isnan = bad != bad
+    # per pixel: median and MAD, mean and std
+    for red in ("median", "mean"):
+        pred, unc = oens.depth_reduce(d, red, True)
+        hit = torch.zeros(1, 1, H, W, dtype=torch.bool)
+        hit[0, 0, y, x] = True
+        if isnan or red == "mean":      # NaN: every statistic of that pixel; +inf: the mean is +inf, its std NaN
+            assert torch.equal(~torch.isfinite(pred), hit) and torch.equal(torch.isnan(unc), hit)
+            assert torch.isnan(pred[hit]).all() if isnan else torch.isposinf(pred[hit]).all()
+        else:                            # one +inf of five sorts last: the lower-middle median and the MAD are numbers
+            assert torch.isfinite(pred).all() and torch.isfinite(unc).all()
+        # the regulariser's extrema: .min() / .max() of a map with a NaN are NaN
+        if isnan:
+            assert torch.isnan(pred.min()) and torch.isnan(pred.max())
+        pi, ui = oens.ensemble_iid(d, True, red)
+        assert torch.equal(torch.isnan(pi), torch.isnan(pred)) and torch.equal(torch.isnan(ui), torch.isnan(unc))
+    # the whole depth ensembling: the alignment's cost is NaN at the start (NaN: the member's own min / max; +inf: its scale is
+    # 1 / inf = 0 and 0 * inf = NaN), the optimiser returns at once, and the normalisation by the NaN extrema spreads it
+    for red in ("median", "mean"):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out, unc = oens.ensemble_depth(d.clone(), True, True, output_uncertainty=True, reduction=red, max_iter=5)
+        assert torch.isnan(out).all() and torch.isnan(unc).all()
+    # normals: the mean direction of that pixel is NaN, so is every cosine - argmax takes member 0, the uncertainty is NaN
+    n = torch.nn.functional.normalize(torch.randn(E, 3, H, W, generator=g), dim=1)
+    n[e, 1, y, x] = bad
+    hit = torch.zeros(1, 1, H, W, dtype=torch.bool)
+    hit[0, 0, y, x] = True
+    out, unc = oens.ensemble_normals(n, True, "closest")
+    assert torch.isfinite(out).all() and torch.equal(out[0, :, y, x], n[0, :, y, x]) and torch.equal(torch.isnan(unc), hit)
+    out, unc = oens.ensemble_normals(n, True, "mean")
+    assert torch.equal(torch.isnan(unc), hit) and torch.isfinite(out[~hit.expand(1, 3, H, W)]).all()
+    if isnan:
+        assert torch.isnan(out[0, :, y, x]).all()            # NaN mean / NaN norm: three NaN channels
+    else:
+        assert torch.isnan(out[0, 1, y, x]) and (out[0, [0, 2], y, x] == 0).all()   # inf / inf, finite / inf
