@@ -233,6 +233,30 @@ enum mg_op_kind {
    *  p[0] depth f32 [n]  p[1] LUT uint8 [256][3] (matplotlib's table)  p[2] out uint8 [n][3] (HWC) ; l[0] n ;
    *  f[0] min_depth f[1] max_depth */
   MG_OP_COLORIZE = 25,
+  /* Scoring of one prediction against its ground truth on the device (the validation loop of the reference,
+   * src/trainer/marigold_depth_trainer.py:510-601, with src/util/alignment.py and src/util/metric.py; csrc/evalscore.hip).
+   * Every sum is fp64 and reduced wave -> block -> a per-block partial table -> one block that adds the table in block order:
+   * no floating-point atomics, the same bits on every launch.  Pixels outside the mask never enter a sum.
+   * EVAL_DEPTH_LS: the five sums n, Sx, Sy, Sxx, Sxy of the least-squares fit gt ~ s * pred + t over the valid pixels
+   *   (align_depth_least_square, alignment.py:35-82).
+   *   p[0] pred f32 [H][W]  p[1] gt f32 [H][W]  p[2] mask uint8 [H][W] (non-zero = valid)  p[3] out f64 [5]
+   *   p[4] scratch f64 [512][5] ; i[0] H  i[1] W  i[2] 1 = disparity: y = 1 / gt, valid &= gt > 0 & pred > 0 (script/depth/eval.py:
+   *   185-201)  i[3] width of the sub-sampled fit (alignment_max_res: floor(W * factor), only the width shrinks; 0 = every pixel)
+   *   f[0] fp32(1 / factor): source column = min(floor(dst * f[0]), W - 1)
+   * EVAL_DEPTH_METRICS: a = clip(clip(pred * s + t)) per valid pixel in fp32 (scale and shift from p[3] by the 2 x 2 normal equations in
+   *   fp64, cast to fp32; disparity: a = 1 / max(a, 1e-3); then [min_depth, max_depth], then the 1e-6 floor) and the ten scores of
+   *   script/depth/eval.py:58-69 (metric.py:64-199), finished in fp64.
+   *   p[0] pred  p[1] gt  p[2] mask  p[3] the five sums f64 [5] | NULL (s = 1, t = 0)  p[4] out f64 [13] = abs_relative_difference,
+   *   squared_relative_difference, rmse_linear, rmse_log, log10, delta1_acc, delta2_acc, delta3_acc, i_rmse, silog_rmse, scale, shift, n
+   *   p[5] scratch f64 [512][11] ; i[0] H  i[1] W  i[2] 1 = disparity  i[3] 1 = clip below at f[0]  i[4] 1 = clip above at f[1]
+   * EVAL_NORMALS: per-pixel angle in degrees (compute_cosine_error, metric.py:206-233) and its statistics; the median is exact
+   *   (np.median: mean of the two middle order statistics), by a three-pass radix selection on the angles' bit patterns.
+   *   p[0] pred f32 [3][HW]  p[1] gt f32 [3][HW]  p[2] out f64 [9] = mean, median, percentages below 5 / 7.5 / 11.25 / 22.5 / 30
+   *   degrees, rmse, n (n = 0: NaN)  p[3] error map f32 [HW] | NULL (dropped pixels hold -1)  p[4] workspace (MG_EVAL_WS_BYTES, 8-byte
+   *   aligned; owned by the launch) ; i[0] masked: drop the pixels whose gt vector has zero norm ; l[0] HW */
+  MG_OP_EVAL_DEPTH_LS = 26,
+  MG_OP_EVAL_DEPTH_METRICS = 27,
+  MG_OP_EVAL_NORMALS = 28,
   MG_OP_MEMSET = 30, /* p[0] dst ; i[0] byte value ; l[0] bytes */
   MG_OP_COPY = 31    /* p[0] src p[1] dst ; l[0] bytes (device to device) */
 };
@@ -339,6 +363,22 @@ int mg_sched_step(const float* x, const float* model_out, const float* noise, fl
                   int64_t n, float cx, float cm, float cn, void* stream);
 int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int64_t hw,
                         int reduction, void* stream);
+
+/* One-pass validation (src/trainer/marigold_depth_trainer.py:510-601; script/depth/eval.py:176-240, script/normals/eval.py): score one
+ * prediction against its ground truth on the device, with no host round trip between the fit and the scores.  The caller reads the
+ * results back when it needs them - neither call synchronises.  workspace: MG_EVAL_WS_BYTES of device memory, 8-byte aligned, owned
+ * by the call until the stream has passed it (one workspace per stream).
+ *  mg_eval_depth: pred, gt fp32 [H][W], mask uint8 [H][W]; alignment MG_EVAL_ALIGN_*; align_max_res <= 0 = fit on every pixel;
+ *  min_depth / max_depth: the dataset's clip limits, NaN = none; out13 f64 = the ten scores in script/depth/eval.py's order, scale,
+ *  shift, n (MG_OP_EVAL_DEPTH_LS + MG_OP_EVAL_DEPTH_METRICS).
+ *  mg_eval_normals: pred, gt fp32 [3][HW]; masked = drop pixels whose gt vector has zero norm; out9 f64 and the optional error map
+ *  as MG_OP_EVAL_NORMALS writes them. */
+#define MG_EVAL_WS_BYTES (128 * 1024)
+enum { MG_EVAL_ALIGN_NONE = 0, MG_EVAL_ALIGN_LS = 1, MG_EVAL_ALIGN_LS_DISPARITY = 2 };
+int mg_eval_depth(const float* pred, const float* gt, const uint8_t* mask, int H, int W, int alignment, int align_max_res,
+                  double min_depth, double max_depth, double* out13, void* workspace, void* stream);
+int mg_eval_normals(const float* pred, const float* gt, int64_t HW, int masked, double* out9, float* err_map_or_null,
+                    void* workspace, void* stream);
 
 /* Host arithmetic of ensemble_depth's alignment objective (marigold/util/ensemble.py:129-152, as the closed form of
  * marigold_amd/ensemble.py): pairwise-RMSE cost of the aligned members and its gradient w.r.t. scales s[E] / shifts t[E],

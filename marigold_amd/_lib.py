@@ -25,6 +25,9 @@ OP_CONV3X3_HEAD = 18
 OP_ENS_DEPTH_STATS, OP_ENS_DEPTH_MEDIAN, OP_ENS_DEPTH_NORM, OP_ENS_NORMALS = 20, 21, 22, 23
 OP_RESIZE = 24
 OP_COLORIZE = 25
+OP_EVAL_DEPTH_LS, OP_EVAL_DEPTH_METRICS, OP_EVAL_NORMALS = 26, 27, 28
+EVAL_WS_BYTES = 128 * 1024   # MG_EVAL_WS_BYTES
+EVAL_ALIGN = {None: 0, "least_square": 1, "least_square_disparity": 2}   # MG_EVAL_ALIGN_*
 OP_MEMSET, OP_COPY = 30, 31
 EPI_BF16, EPI_GEGLU, EPI_F32, EPI_SOFTMAX2, EPI_XATTN2 = 0, 1, 2, 3, 4
 POST_NONE, POST_DEPTH, POST_NORMALS, POST_UNIT, POST_SCHED = 0, 1, 2, 3, 4
@@ -38,7 +41,7 @@ EXPORTS = [
     "mg_sched_step", "mg_ensemble_normals", "mg_ens_align_cost_grad", "mg_bfgs_minimize", "mg_ens_align_minimize", "mg_event_create", "mg_event_record",
     "mg_event_elapsed_ms", "mg_event_destroy", "mg_clock_probe", "mg_debug_read_workspace",
     "mg_model_load", "mg_model_destroy", "mg_model_info", "mg_model_device_bytes", "mg_model_validate", "mg_model_vae_encode",
-    "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth",
+    "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals",
 ]
 
 
@@ -115,6 +118,8 @@ def load(f16=False):
     lib.mg_model_vae_decode.argtypes = [ctypes.c_void_p] * 4
     lib.mg_ensemble_depth.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                       ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mg_eval_depth.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3
+    lib.mg_eval_normals.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

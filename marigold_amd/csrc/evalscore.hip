@@ -1,0 +1,445 @@
+// On-device scoring of one prediction against its ground truth: the per-image body of the reference's validation loop
+// (src/trainer/marigold_depth_trainer.py:510-601) and of script/{depth,normals}/eval.py - least-squares alignment
+// (src/util/alignment.py:35-82), the clips of script/depth/eval.py:176-212, the ten depth scores (src/util/metric.py:64-199) and the
+// angular-error statistics of the normals protocol (:206-279).
+//
+// Element arithmetic is fp32 with IEEE division, sqrt and the library's accurate logf / log10f / acosf (this file is built with
+// -ffp-contract=off and no fast-math, so an expression rounds like the numpy / torch element ops it restates); every sum is fp64.
+// Reductions: thread -> wave (xor butterfly) -> block (LDS, fixed order) -> one row of a per-block partial table; a one-block
+// launch then adds the rows in block order.  No floating-point atomics: two launches on the same input give the same bits.
+// The median of the angles is exact: they are non-negative, so their bit patterns order as unsigned integers, and three histogram
+// passes over 11 / 11 / 10 bits (integer atomics in LDS, merged into a global histogram) select the two middle order statistics.
+//
+// The maps are 0.3-0.6 M pixels: every kernel here is a few microseconds of streaming, the cost of a call is its launches.
+#include <math.h>
+#include <string.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int EV_BLOCKS = 512;    // rows of a partial table
+constexpr int EV_THREADS = 256;
+constexpr int LS_N = 5;           // n, Sx, Sy, Sxx, Sxy
+constexpr int DM_N = 11;          // the eleven sums of the depth scores (below)
+constexpr int NM_N = 9;           // Se, See, five counts, n, NaN count
+
+// workspace layout of mg_eval_depth / MG_OP_EVAL_NORMALS (bytes)
+constexpr size_t WS_LS_PART = 0;
+constexpr size_t WS_LS_SUMS = WS_LS_PART + (size_t)EV_BLOCKS * LS_N * 8;
+constexpr size_t WS_DM_PART = WS_LS_SUMS + 64;
+constexpr size_t WS_DEPTH_END = WS_DM_PART + (size_t)EV_BLOCKS * DM_N * 8;
+constexpr size_t WS_NM_PART = 0;
+constexpr size_t WS_NM_STATE = WS_NM_PART + (size_t)EV_BLOCKS * NM_N * 8;
+constexpr size_t WS_NM_HIST0 = WS_NM_STATE + 64;              // [2048]       bits 31..21
+constexpr size_t WS_NM_HIST1 = WS_NM_HIST0 + 2048 * 4;        // [2][2048]    bits 20..10 under each rank's prefix
+constexpr size_t WS_NM_HIST2 = WS_NM_HIST1 + 2 * 2048 * 4;    // [2][1024]    bits 9..0
+constexpr size_t WS_NORMALS_END = WS_NM_HIST2 + 2 * 1024 * 4;
+static_assert(WS_DEPTH_END <= MG_EVAL_WS_BYTES && WS_NORMALS_END <= MG_EVAL_WS_BYTES, "MG_EVAL_WS_BYTES too small");
+
+// the selection's state between the passes: per rank (lower / upper middle) the bits fixed so far and the rank inside them
+struct SelState {
+  unsigned prefix[2];
+  unsigned long long rem[2];
+  unsigned long long n, nan;
+};
+static_assert(sizeof(SelState) <= 64, "SelState");
+
+// v[k] summed over the block -> dst[k] (the block's row of a partial table); every thread of the block calls it
+template <int N>
+__device__ __forceinline__ void block_sum_store(const double (&v)[N], double* __restrict__ dst) {
+  __shared__ double red[EV_THREADS / 64][N];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    double x = v[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);   // (a + b on both sides of a pair: the same bits in every lane)
+    if (lane == 0) red[wave][k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    const int k = threadIdx.x;
+    dst[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// rows [0, nblk) of a partial table added in row order -> out[N]; one block
+__global__ __launch_bounds__(64) void sum_rows_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk, int N) {
+  const int k = threadIdx.x;
+  if (k >= N) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += part[(size_t)b * N + k];
+  out[k] = s;
+}
+
+// ---- depth ----------------------------------------------------------------------------------------------------------
+
+// alignment._nearest_downscale / torch.nn.Upsample(mode="nearest") on a [1, H, W] tensor: the width alone is sub-sampled
+__device__ __forceinline__ int fit_pixel(int idx, int W, int OW, float inv) {
+  if (OW <= 0) return idx;
+  const int row = idx / OW, col = idx - row * OW;
+  const int sc = (int)fminf(floorf((float)col * inv), (float)(W - 1));
+  return row * W + sc;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void depth_ls_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                              const uint8_t* __restrict__ mask, double* __restrict__ part,
+                                                              int H, int W, int OW, float inv, int disparity) {
+  double acc[LS_N];
+#pragma unroll
+  for (int k = 0; k < LS_N; ++k) acc[k] = 0.0;
+  const int total = H * (OW > 0 ? OW : W);
+  for (int idx = blockIdx.x * EV_THREADS + threadIdx.x; idx < total; idx += gridDim.x * EV_THREADS) {
+    const int src = fit_pixel(idx, W, OW, inv);
+    if (!mask[src]) continue;
+    const float p = pred[src], g = gt[src];
+    float y = g;
+    if (disparity) {
+      if (!(g > 0.f && p > 0.f)) continue;
+      y = 1.0f / g;
+    }
+    const double x = (double)p, yd = (double)y;
+    acc[0] += 1.0;
+    acc[1] += x;
+    acc[2] += yd;
+    acc[3] += x * x;
+    acc[4] += x * yd;
+  }
+  block_sum_store<LS_N>(acc, part + (size_t)blockIdx.x * LS_N);
+}
+
+// scale, shift of the 2 x 2 normal equations (evaluation/alignment.py), cast to fp32 like the fit of fp32 arrays
+__device__ __forceinline__ void ls_solve(const double* __restrict__ sums, float& s, float& t) {
+  if (!sums) { s = 1.f; t = 0.f; return; }
+  const double n = sums[0], sx = sums[1], sy = sums[2], sxx = sums[3], sxy = sums[4];
+  const double det = n * sxx - sx * sx;
+  const double scale = (n * sxy - sx * sy) / det;
+  const double shift = (sy - scale * sx) / n;
+  s = (float)scale;
+  t = (float)shift;
+}
+
+// sums: 0 |a-g|/g  1 (a-g)^2/g  2 (a-g)^2  3 (ln a - ln g)^2  4 ln a - ln g  5 |log10 a - log10 g|  6..8 max(a/g, g/a) < 1.25^k
+// 9 (1/a - 1/g)^2  10 n
+__global__ __launch_bounds__(EV_THREADS) void depth_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                   const uint8_t* __restrict__ mask, const double* __restrict__ sums,
+                                                                   double* __restrict__ part, int HW, int disparity, int has_lo,
+                                                                   int has_hi, float lo, float hi) {
+  float s, t;
+  ls_solve(sums, s, t);
+  const bool aligned = sums != nullptr;
+  double acc[DM_N];
+#pragma unroll
+  for (int k = 0; k < DM_N; ++k) acc[k] = 0.0;
+  for (int idx = blockIdx.x * EV_THREADS + threadIdx.x; idx < HW; idx += gridDim.x * EV_THREADS) {
+    if (!mask[idx]) continue;
+    const float g = gt[idx];
+    float a = pred[idx];
+    if (aligned) {
+      a = a * s + t;
+      if (disparity) {   // np.clip(disp, 1e-3, None), then disparity2depth: 1 / d where d > 0, else 0
+        a = floor_keep_nan(a, 1e-3f);
+        a = a > 0.f ? 1.0f / a : 0.f;
+      }
+    }
+    if (has_lo) a = floor_keep_nan(a, lo);
+    if (has_hi) a = a != a ? a : fminf(a, hi);
+    a = floor_keep_nan(a, 1e-6f);
+    const float d = a - g, ad = fabsf(d);
+    const float ld = logf(a) - logf(g);
+    const float worst = max_keep_nan(a / g, g / a);
+    const float id = 1.0f / a - 1.0f / g;
+    acc[0] += (double)(ad / g);
+    acc[1] += (double)((ad * ad) / g);
+    acc[2] += (double)(d * d);
+    acc[3] += (double)(ld * ld);
+    acc[4] += (double)ld;
+    acc[5] += (double)fabsf(log10f(a) - log10f(g));
+    acc[6] += worst < 1.25f ? 1.0 : 0.0;
+    acc[7] += worst < 1.5625f ? 1.0 : 0.0;
+    acc[8] += worst < 1.953125f ? 1.0 : 0.0;
+    acc[9] += (double)(id * id);
+    acc[10] += 1.0;
+  }
+  block_sum_store<DM_N>(acc, part + (size_t)blockIdx.x * DM_N);
+}
+
+__global__ __launch_bounds__(64) void depth_metrics_final_kernel(const double* __restrict__ part, const double* __restrict__ sums,
+                                                                 double* __restrict__ out, int nblk) {
+  __shared__ double S[DM_N];
+  if (threadIdx.x < DM_N) {
+    double v = 0.0;
+    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * DM_N + threadIdx.x];
+    S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double n = S[10];
+  float s, t;
+  ls_solve(sums, s, t);
+  const double mlog = S[4] / n;
+  out[0] = S[0] / n;
+  out[1] = S[1] / n;
+  out[2] = sqrt(S[2] / n);
+  out[3] = sqrt(S[3] / n);
+  out[4] = S[5] / n;
+  out[5] = S[6] / n;
+  out[6] = S[7] / n;
+  out[7] = S[8] / n;
+  out[8] = sqrt(S[9] / n);
+  out[9] = sqrt(S[3] / n - mlog * mlog) * 100.0;
+  out[10] = (double)s;
+  out[11] = (double)t;
+  out[12] = n;
+}
+
+// ---- normals --------------------------------------------------------------------------------------------------------
+
+// metrics.compute_cosine_error for pixel i; false = the pixel is dropped (masked and a ground-truth vector of zero norm)
+__device__ __forceinline__ bool normals_angle(const float* __restrict__ pred, const float* __restrict__ gt, long long HW, long long i,
+                                              int masked, float& e) {
+  const float gx = gt[i], gy = gt[HW + i], gz = gt[2 * HW + i];
+  float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
+  if (masked && !(gn > 0.f)) return false;
+  const float px = pred[i], py = pred[HW + i], pz = pred[2 * HW + i];
+  const float pn = max_keep_nan(sqrtf((px * px + py * py) + pz * pz), 1e-8f);
+  gn = max_keep_nan(gn, 1e-8f);
+  float c = ((px / pn) * (gx / gn) + (py / pn) * (gy / gn)) + (pz / pn) * (gz / gn);
+  c = clip_keep_nan(c, -1.0f, 1.0f);
+  e = acosf(c) * 57.29577951308232f;
+  return true;
+}
+
+// the angle of pixel i for the selection passes: from the error map when the caller gave one, else recomputed (the same code, the
+// same bits)
+__device__ __forceinline__ bool angle_of(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ err,
+                                         long long HW, long long i, int masked, float& e) {
+  if (err) {
+    e = err[i];
+    return !(e == -1.0f);
+  }
+  return normals_angle(pred, gt, HW, i, masked, e);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void normals_stats_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                   float* __restrict__ err, double* __restrict__ part,
+                                                                   unsigned* __restrict__ ghist, long long HW, int masked) {
+  __shared__ unsigned hist[2048];
+  for (int b = threadIdx.x; b < 2048; b += EV_THREADS) hist[b] = 0u;
+  __syncthreads();
+  double acc[NM_N];
+#pragma unroll
+  for (int k = 0; k < NM_N; ++k) acc[k] = 0.0;
+  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < HW; i += (long long)gridDim.x * EV_THREADS) {
+    float e;
+    const bool keep = normals_angle(pred, gt, HW, i, masked, e);
+    if (err) err[i] = keep ? e : -1.0f;
+    if (!keep) continue;
+    acc[0] += (double)e;
+    acc[1] += (double)(e * e);
+    acc[2] += e < 5.0f ? 1.0 : 0.0;
+    acc[3] += e < 7.5f ? 1.0 : 0.0;
+    acc[4] += e < 11.25f ? 1.0 : 0.0;
+    acc[5] += e < 22.5f ? 1.0 : 0.0;
+    acc[6] += e < 30.0f ? 1.0 : 0.0;
+    acc[7] += 1.0;
+    acc[8] += e != e ? 1.0 : 0.0;
+    atomicAdd(&hist[__float_as_uint(e) >> 21], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < 2048; b += EV_THREADS)
+    if (hist[b]) atomicAdd(&ghist[b], hist[b]);
+  block_sum_store<NM_N>(acc, part + (size_t)blockIdx.x * NM_N);
+}
+
+// the bin that holds rank st->rem[r] of a histogram, for both ranks (lane 0 of waves 0 and 1); the bin joins the prefix
+__device__ __forceinline__ void select_bin(SelState* __restrict__ st, const unsigned* __restrict__ hist, int bins, int stride, int bits) {
+  const int r = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) != 0 || r >= 2) return;
+  const unsigned* __restrict__ h = hist + (size_t)r * stride;
+  unsigned long long rem = st->rem[r];
+  int b = 0;
+  for (; b < bins - 1; ++b) {
+    const unsigned long long c = h[b];
+    if (rem < c) break;
+    rem -= c;
+  }
+  st->prefix[r] = (st->prefix[r] << bits) | (unsigned)b;
+  st->rem[r] = rem;
+}
+
+// one block: the table's rows in order -> every output but the median; the ranks of the two middle angles; the first selection step
+__global__ __launch_bounds__(128) void normals_reduce_kernel(const double* __restrict__ part, double* __restrict__ out,
+                                                             SelState* __restrict__ st, const unsigned* __restrict__ hist0, int nblk) {
+  __shared__ double S[NM_N];
+  if (threadIdx.x < NM_N) {
+    double v = 0.0;
+    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * NM_N + threadIdx.x];
+    S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double n = S[7];
+    out[0] = S[0] / n;
+    for (int k = 0; k < 5; ++k) out[2 + k] = 100.0 * (S[2 + k] / n);
+    out[7] = sqrt(S[1] / n);
+    out[8] = n;
+    const unsigned long long cnt = (unsigned long long)n;
+    st->n = cnt;
+    st->nan = (unsigned long long)S[8];
+    st->prefix[0] = st->prefix[1] = 0u;
+    st->rem[0] = cnt ? (cnt - 1) / 2 : 0;
+    st->rem[1] = cnt / 2;
+  }
+  __syncthreads();
+  select_bin(st, hist0, 2048, 0, 11);
+}
+
+// passes 2 and 3: the histogram of the next `bits` bits of the angles that carry a rank's prefix; ghist [2][1 << bits]
+__global__ __launch_bounds__(EV_THREADS) void normals_hist_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                  const float* __restrict__ err, const SelState* __restrict__ st,
+                                                                  unsigned* __restrict__ ghist, long long HW, int masked, int shift,
+                                                                  int bits) {
+  __shared__ unsigned hist[2 * 2048];
+  const int bins = 1 << bits;
+  for (int b = threadIdx.x; b < 2 * bins; b += EV_THREADS) hist[b] = 0u;
+  __syncthreads();
+  const unsigned p0 = st->prefix[0], p1 = st->prefix[1];
+  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < HW; i += (long long)gridDim.x * EV_THREADS) {
+    float e;
+    if (!angle_of(pred, gt, err, HW, i, masked, e)) continue;
+    const unsigned u = __float_as_uint(e);
+    const unsigned hi = u >> (shift + bits), bin = (u >> shift) & (unsigned)(bins - 1);
+    if (hi == p0) atomicAdd(&hist[bin], 1u);
+    if (hi == p1) atomicAdd(&hist[bins + bin], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < 2 * bins; b += EV_THREADS)
+    if (hist[b]) atomicAdd(&ghist[b], hist[b]);
+}
+
+__global__ __launch_bounds__(128) void normals_select_kernel(SelState* __restrict__ st, const unsigned* __restrict__ hist, int bins,
+                                                             int bits, double* __restrict__ out_median) {
+  select_bin(st, hist, bins, bins, bits);
+  if (!out_median) return;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  // np.median: the mean of the two middle order statistics, in the array's own fp32 (odd n: both ranks are the same element)
+  const float lo = __uint_as_float(st->prefix[0]), hi = __uint_as_float(st->prefix[1]);
+  const float med = (lo + hi) / 2.0f;
+  *out_median = (st->n == 0 || st->nan != 0) ? (double)__builtin_nanf("") : (double)med;
+}
+
+int grid_for(long long n) { return (int)max(1ll, min((n + EV_THREADS - 1) / EV_THREADS, (long long)EV_BLOCKS)); }
+
+}  // namespace
+
+int mg_launch_evalscore(const mg_op* op, hipStream_t s) {
+  switch (op->kind) {
+    case MG_OP_EVAL_DEPTH_LS: {
+      const int H = op->i[0], W = op->i[1], OW = op->i[3];
+      MG_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31), "eval_depth_ls: bad size %d x %d", H, W);
+      MG_REQUIRE(OW >= 0 && OW <= W, "eval_depth_ls: sub-sampled width %d outside [0, %d]", OW, W);
+      MG_REQUIRE(OW == 0 || op->f[0] >= 1.0f, "eval_depth_ls: inverse factor %g must be >= 1", (double)op->f[0]);
+      MG_REQUIRE(op->p[0] && op->p[1] && op->p[2] && op->p[3] && op->p[4], "eval_depth_ls: null pointer");
+      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4]) % 8 == 0, "eval_depth_ls: out / scratch not 8-byte aligned");
+      const int nblk = grid_for((long long)H * (OW > 0 ? OW : W));
+      MG_LAUNCH(depth_ls_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const float*)op->p[0], (const float*)op->p[1],
+                (const uint8_t*)op->p[2], (double*)op->p[4], H, W, OW, op->f[0], op->i[2] != 0);
+      MG_LAUNCH(sum_rows_kernel, dim3(1), dim3(64), 0, s, (const double*)op->p[4], (double*)op->p[3], nblk, LS_N);
+      break;
+    }
+    case MG_OP_EVAL_DEPTH_METRICS: {
+      const int H = op->i[0], W = op->i[1];
+      MG_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31), "eval_depth_metrics: bad size %d x %d", H, W);
+      MG_REQUIRE(op->p[0] && op->p[1] && op->p[2] && op->p[4] && op->p[5], "eval_depth_metrics: null pointer");
+      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4] | (uintptr_t)op->p[5]) % 8 == 0,
+                 "eval_depth_metrics: sums / out / scratch not 8-byte aligned");
+      const int nblk = grid_for((long long)H * W);
+      MG_LAUNCH(depth_metrics_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const float*)op->p[0], (const float*)op->p[1],
+                (const uint8_t*)op->p[2], (const double*)op->p[3], (double*)op->p[5], H * W, op->i[2] != 0, op->i[3] != 0,
+                op->i[4] != 0, op->f[0], op->f[1]);
+      MG_LAUNCH(depth_metrics_final_kernel, dim3(1), dim3(64), 0, s, (const double*)op->p[5], (const double*)op->p[3],
+                (double*)op->p[4], nblk);
+      break;
+    }
+    case MG_OP_EVAL_NORMALS: {
+      const long long HW = op->l[0];
+      MG_REQUIRE(HW >= 0, "eval_normals: HW %lld < 0", HW);
+      MG_REQUIRE(op->p[2] && op->p[4] && (HW == 0 || (op->p[0] && op->p[1])), "eval_normals: null pointer");
+      MG_REQUIRE(((uintptr_t)op->p[2] | (uintptr_t)op->p[4]) % 8 == 0, "eval_normals: out / workspace not 8-byte aligned");
+      char* const ws = (char*)op->p[4];
+      const float *pred = (const float*)op->p[0], *gt = (const float*)op->p[1];
+      float* const err = (float*)op->p[3];
+      double* const out = (double*)op->p[2];
+      SelState* const st = (SelState*)(ws + WS_NM_STATE);
+      unsigned *h0 = (unsigned*)(ws + WS_NM_HIST0), *h1 = (unsigned*)(ws + WS_NM_HIST1), *h2 = (unsigned*)(ws + WS_NM_HIST2);
+      const int masked = op->i[0] != 0, nblk = grid_for(HW);
+      if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(ws + WS_NM_STATE, 0, WS_NORMALS_END - WS_NM_STATE, s));
+      MG_LAUNCH(normals_stats_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, err, (double*)(ws + WS_NM_PART), h0, HW, masked);
+      MG_LAUNCH(normals_reduce_kernel, dim3(1), dim3(128), 0, s, (const double*)(ws + WS_NM_PART), out, st, (const unsigned*)h0, nblk);
+      MG_LAUNCH(normals_hist_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, (const float*)err, (const SelState*)st, h1, HW,
+                masked, 10, 11);
+      MG_LAUNCH(normals_select_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h1, 2048, 11, (double*)nullptr);
+      MG_LAUNCH(normals_hist_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, (const float*)err, (const SelState*)st, h2, HW,
+                masked, 0, 10);
+      MG_LAUNCH(normals_select_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h2, 1024, 10, out + 1);
+      break;
+    }
+    default: MG_REQUIRE(false, "evalscore: bad op kind %d", op->kind);
+  }
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int mg_eval_depth(const float* pred, const float* gt, const uint8_t* mask, int H, int W, int alignment, int align_max_res,
+                  double min_depth, double max_depth, double* out13, void* workspace, void* stream) {
+  MG_REQUIRE(pred && gt && mask && out13 && workspace, "mg_eval_depth: null pointer");
+  MG_REQUIRE(alignment >= MG_EVAL_ALIGN_NONE && alignment <= MG_EVAL_ALIGN_LS_DISPARITY, "mg_eval_depth: unknown alignment %d", alignment);
+  MG_REQUIRE((uintptr_t)workspace % 8 == 0, "mg_eval_depth: workspace not 8-byte aligned");
+  char* const ws = (char*)workspace;
+  mg_op op;
+  if (alignment != MG_EVAL_ALIGN_NONE) {
+    memset(&op, 0, sizeof(op));
+    op.kind = MG_OP_EVAL_DEPTH_LS;
+    op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask; op.p[3] = ws + WS_LS_SUMS; op.p[4] = ws + WS_LS_PART;
+    op.i[0] = H; op.i[1] = W; op.i[2] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
+    if (align_max_res > 0 && H >= 1 && W >= 1) {   // align_depth_least_square: factor = min(max_res / (H, W)), applied when < 1
+      const double fh = (double)align_max_res / (double)H, fw = (double)align_max_res / (double)W;
+      const double factor = fh < fw ? fh : fw;
+      if (factor < 1.0) {
+        op.i[3] = (int)floor((double)W * factor);
+        op.f[0] = (float)(1.0 / factor);
+        MG_REQUIRE(op.i[3] >= 1, "mg_eval_depth: alignment_max_res %d leaves no column of a %d x %d map", align_max_res, H, W);
+      }
+    }
+    const int rc = mg_launch_evalscore(&op, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_EVAL_DEPTH_METRICS;
+  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask;
+  op.p[3] = alignment != MG_EVAL_ALIGN_NONE ? ws + WS_LS_SUMS : nullptr;
+  op.p[4] = out13; op.p[5] = ws + WS_DM_PART;
+  op.i[0] = H; op.i[1] = W; op.i[2] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
+  op.i[3] = min_depth == min_depth; op.i[4] = max_depth == max_depth;
+  op.f[0] = op.i[3] ? (float)min_depth : 0.f;
+  op.f[1] = op.i[4] ? (float)max_depth : 0.f;
+  return mg_launch_evalscore(&op, (hipStream_t)stream);
+}
+
+int mg_eval_normals(const float* pred, const float* gt, int64_t HW, int masked, double* out9, float* err_map_or_null,
+                    void* workspace, void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_EVAL_NORMALS;
+  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = out9; op.p[3] = err_map_or_null; op.p[4] = workspace;
+  op.i[0] = masked;
+  op.l[0] = HW;
+  return mg_launch_evalscore(&op, (hipStream_t)stream);
+}
+
+}  // extern "C"

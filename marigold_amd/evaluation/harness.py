@@ -9,6 +9,10 @@ Flags, file names and the text formats are the reference's.  What differs is the
 decoded one image ahead on a host thread and predictions are written behind the GPU (the reference's
 DataLoader(batch_size=1, num_workers=0) serialises decode -> predict -> save), and the scores are numpy
 (see metrics.py).  Inference only runs on an MI355X - there is no CPU path.
+
+One-pass validation (depth, normals): ``infer_main --evaluate`` scores every image on the GPU as it leaves the engine
+(device.py; the reference's validation loop, src/trainer/marigold_depth_trainer.py:510-601) and writes the files of
+``eval_main`` under ``--eval_output_dir``; ``eval_main --on_device`` runs the same scorer on read-back files.
 """
 import argparse
 import logging
@@ -60,11 +64,24 @@ def infer_parser(kind):
     p.add_argument("--yes", action="store_true", help="Do not ask before writing into an existing output dir.")
     p.add_argument("--maps_in_flight", type=int, default=0,
                    help="Images on the GPU at a time (independent maps on concurrent HIP streams; results do not depend on it); "
-                        "0 = the engine's default (2).")
+                        "0 = the engine's default (3 while a program holds up to 8 members on this GPU, else 2).")
     p.add_argument("--images_per_program", type=int, default=1,
                    help="Consecutive images of one processed size that share one denoising program (their members batched); "
                         "1 = one image per program.")
+    p.add_argument("--evaluate", action="store_true",
+                   help="Score every prediction on the GPU as it is produced and write per_sample_metrics.csv and "
+                        "eval_metrics[-<alignment>].txt like eval.py (depth and normals).")
+    p.add_argument("--eval_output_dir", type=str, default=None, help="Where --evaluate writes; default <output_dir>/eval.")
+    p.add_argument("--no_save_predictions", action="store_true", help="With --evaluate: do not write the .npy predictions.")
+    if kind == "depth":
+        _alignment_arguments(p)
     return p
+
+
+def _alignment_arguments(p):
+    p.add_argument("--alignment", choices=[None, "least_square", "least_square_disparity"], default=None,
+                   help="Method to estimate scale and shift between predictions and ground truth.")
+    p.add_argument("--alignment_max_res", type=int, default=None, help="Max operating resolution used for LS alignment")
 
 
 def _confirm_existing(directory, assume_yes):
@@ -121,13 +138,19 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
                  f"seed = {args.seed}; dataset config = `{args.dataset_config}`.")
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
+    if args.evaluate and kind == "iid":
+        raise ValueError("--evaluate scores depth and normals only: the IID metrics (SSIM, quantile mapping) run on the host, "
+                         "use script/iid/eval.py on the written predictions")
+    if args.no_save_predictions and not args.evaluate:
+        raise ValueError("--no_save_predictions without --evaluate would compute predictions and keep none of them")
     seed = int(time.time()) if args.seed is None else args.seed
     seed_all(seed)
     if not _confirm_existing(args.output_dir, args.yes):
         return 0
     os.makedirs(args.output_dir, exist_ok=True)
     logging.info(f"output dir = {args.output_dir}")
-    dataset = get_dataset(load_dataset_config(args.dataset_config), args.base_data_dir, DatasetMode.RGB_ONLY)
+    dataset = get_dataset(load_dataset_config(args.dataset_config), args.base_data_dir,
+                          DatasetMode.EVAL if args.evaluate else DatasetMode.RGB_ONLY)   # (EVAL samples carry rgb_int + the ground truth)
     if dataset.spec.kind != kind:
         raise AssertionError(f"'{dataset.name}' is a {dataset.spec.kind} dataset, not {kind}")
     if pipeline is None:
@@ -169,10 +192,23 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
         else:                                 # an object with the reference pipeline's call surface only
             outs = (pipeline(im, generator=generator_of(), **kw) for im in images())
         writes = []
-        for i, out in enumerate(outs):
-            for rel, arr in _prediction_files(kind, dataset, pipeline, samples[i]["rgb_relative_path"], out):
-                writes.append(writer.submit(_save_npy, os.path.join(args.output_dir, rel), arr))
-            samples[i] = None
+
+        def results():   # saves each output behind the GPU; with --evaluate yields its scores
+            for i, out in enumerate(outs):
+                files = _prediction_files(kind, dataset, pipeline, samples[i]["rgb_relative_path"], out)
+                if not args.no_save_predictions:
+                    for rel, arr in files:
+                        writes.append(writer.submit(_save_npy, os.path.join(args.output_dir, rel), arr))
+                if args.evaluate:
+                    yield _score_on_device(kind, args, dataset, samples[i], files[0][1], names)
+                samples[i] = None
+        if args.evaluate:
+            names = list(M.DEPTH_METRICS if kind == "depth" else M.NORMALS_METRICS)
+            _write_eval_files(kind, args.eval_output_dir or os.path.join(args.output_dir, "eval"), dataset, args.output_dir,
+                              names, results(), getattr(args, "alignment", None))
+        else:
+            for _ in results():
+                pass
         for w in writes:
             w.result()
     dt = time.perf_counter() - t0
@@ -191,9 +227,7 @@ def eval_parser(kind):
     p.add_argument("--base_data_dir", type=str, required=True, help="Base path to the datasets.")
     p.add_argument("--output_dir", type=str, required=True, help="Output directory.")
     if kind == "depth":
-        p.add_argument("--alignment", choices=[None, "least_square", "least_square_disparity"], default=None,
-                       help="Method to estimate scale and shift between predictions and ground truth.")
-        p.add_argument("--alignment_max_res", type=int, default=None, help="Max operating resolution used for LS alignment")
+        _alignment_arguments(p)
     else:
         p.add_argument("--use_mask", action="store_true", help="Evaluate only in the masked region.")
     if kind == "iid":
@@ -204,6 +238,9 @@ def eval_parser(kind):
         p.add_argument("--metrics", nargs="+", default=["psnr", "ssim"], choices=["psnr", "ssim"],
                        help="(LPIPS of the reference needs pretrained network weights; not provided)")
     p.add_argument("--no_cuda", action="store_true", help="(reference flag; scoring runs on the host here)")
+    if kind != "iid":
+        p.add_argument("--on_device", action="store_true",
+                       help="Score on the GPU with the scorer of infer.py --evaluate (evaluation/device.py) instead of numpy.")
     return p
 
 
@@ -220,6 +257,19 @@ def align_and_clip_depth(depth_pred, depth_raw, valid_mask, dataset, alignment=N
     return np.clip(depth_pred, a_min=1e-6, a_max=None)
 
 
+def _score_on_device(kind, args, dataset, data, pred, names):
+    """(label, values) of one prediction from the GPU scorer: the rows ``_score_depth`` / ``_score_normals`` compute in numpy."""
+    from . import device as DV
+    rgb_name = data["rgb_relative_path"]
+    if kind == "depth":
+        label = os.path.join(os.path.dirname(rgb_name), get_pred_name(os.path.basename(rgb_name), dataset.name_mode, suffix=".npy"))
+        res = DV.score_depth(pred, data["depth_raw_linear"].squeeze(), data["valid_mask_raw"].squeeze(), alignment=args.alignment,
+                             alignment_max_res=args.alignment_max_res, min_depth=dataset.min_depth, max_depth=dataset.max_depth)
+    else:
+        label, res = rgb_name, DV.score_normals(pred, data["normals"], masked=True)
+    return label, [res[n] for n in names]
+
+
 def _score_depth(args, dataset, data, names):
     rgb_name = data["rgb_relative_path"]
     pred_name = os.path.join(os.path.dirname(rgb_name),
@@ -228,6 +278,8 @@ def _score_depth(args, dataset, data, names):
     if not os.path.exists(path):
         logging.warning(f"Can't find prediction: {path}")
         return None
+    if args.on_device:
+        return _score_on_device("depth", args, dataset, data, np.load(path).astype(np.float32), names)
     gt, valid = data["depth_raw_linear"].squeeze(), data["valid_mask_raw"].squeeze()
     pred = align_and_clip_depth(np.load(path).astype(np.float32), gt, valid, dataset, args.alignment,
                                 args.alignment_max_res)
@@ -240,6 +292,8 @@ def _score_normals(args, dataset, data, names):
     if not os.path.exists(path):
         logging.warning(f"Can't find prediction: {path}")
         return None
+    if args.on_device:
+        return _score_on_device("normals", args, dataset, data, np.load(path).astype(np.float32), names)
     err = M.compute_cosine_error(np.load(path).astype(np.float32), data["normals"], masked=True)
     return rgb_name, [getattr(M, n)(err) for n in names]
 
@@ -281,28 +335,37 @@ def eval_main(kind, argv=None) -> int:
                 raise ValueError(f"'{t}' specified in targets_to_eval_in_linear_space does not belong to the "
                                  f"predicted targets: target_names={args.target_names}")
         names, score = [f"{m}_{t}" for t in args.target_names for m in args.metrics], _score_iid
+    _write_eval_files(kind, args.output_dir, dataset, args.prediction_dir, names,
+                      (score(args, dataset, data, names) for data in dataset), getattr(args, "alignment", None))
+    return 0
+
+
+def _write_eval_files(kind, output_dir, dataset, prediction_dir, names, scored, alignment=None):
+    """``per_sample_metrics.csv`` and ``eval_metrics[-<alignment>].txt`` (script/depth/eval.py:139-245) from ``scored``, an
+    iterable of ``(label, values)`` rows (None = prediction missing; a None value = an empty cell that is not averaged).
+    The rows are written as they arrive.  Shared by ``eval_main`` and ``infer_main --evaluate``."""
+    os.makedirs(output_dir, exist_ok=True)
     tracker = M.MetricTracker(*names)
-    per_sample = os.path.join(args.output_dir, "per_sample_metrics.csv")
+    per_sample = os.path.join(output_dir, "per_sample_metrics.csv")
     with open(per_sample, "w+") as f:
         f.write("filename," + ",".join(names) + "\n")
-        for data in dataset:
-            scored = score(args, dataset, data, names)
-            if scored is None:
+        for row in scored:
+            if row is None:
                 continue
-            label, values = scored
+            label, values = row
             assert len(values) == len(names)
             for n, v in zip(names, values):
                 if v is not None:
                     tracker.update(n, v)
             f.write(label + "," + ",".join("" if v is None else str(v) for v in values) + "\n")
-    text = (f"Evaluation metrics:\n    of predictions: {args.prediction_dir}\n    on dataset: {dataset.disp_name}\n"
+    text = (f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on dataset: {dataset.disp_name}\n"
             f"    with samples in: {dataset.filename_ls_path}\n")
     if kind == "depth":
         text += f"min_depth = {dataset.min_depth}\nmax_depth = {dataset.max_depth}\n"
     result = tracker.result()
     text += tabulate([list(result.keys()), list(result.values())])
-    name = "eval_metrics" + (f"-{args.alignment}" if kind == "depth" and args.alignment else "") + ".txt"
-    with open(os.path.join(args.output_dir, name), "w+") as f:
+    name = "eval_metrics" + (f"-{alignment}" if kind == "depth" and alignment else "") + ".txt"
+    with open(os.path.join(output_dir, name), "w+") as f:
         f.write(text)
-    logging.info(f"Evaluation metrics saved to {os.path.join(args.output_dir, name)}")
-    return 0
+    logging.info(f"Evaluation metrics saved to {os.path.join(output_dir, name)}")
+    return os.path.join(output_dir, name)

@@ -4,6 +4,8 @@ Predictions are read back from ``.npy`` files and compared with ground truth one
 the work is a handful of masked reductions per image, dominated by file IO, so it stays on the host
 (fp32 element arithmetic like the reference's torch-fp32 tensors, fp64 accumulation for the sums -
 results agree with the reference's to ~1e-6 relative, see tests/test_evaluation.py).
+The same depth and normals scores computed on the GPU, for scoring predictions as the engine produces them, live in
+``device.py`` (csrc/evalscore.hip).
 
 Depth metrics take ``(pred, gt, valid_mask)`` as ``[H,W]`` arrays (src/util/metric.py:64-199);
 normals metrics take the flat per-pixel angular error in degrees (:206-279); the IID helpers follow

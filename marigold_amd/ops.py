@@ -205,6 +205,35 @@ def colorize(depth, lut, out, *, n, lo=0.0, hi=1.0):
     return make_op(L.OP_COLORIZE, f=[lo, hi], p=[depth, lut, out], l=[n])
 
 
+def eval_fit_width(H, W, max_res):
+    """(sub-sampled width, fp32(1 / factor)) of the least-squares fit under ``alignment_max_res`` - evaluation/alignment.py:
+    factor = min(max_res / (H, W)), only the width shrinks; (0, 0.0) = fit on every pixel."""
+    if max_res is None:
+        return 0, 0.0
+    factor = min(max_res / H, max_res / W)
+    if factor >= 1:
+        return 0, 0.0
+    import numpy as np
+    return int(np.floor(W * factor)), float(np.float32(1.0 / factor))
+
+
+def eval_depth_ls(pred, gt, mask, out5, scratch, *, H, W, disparity=False, max_res=None):
+    """The five fp64 sums of the least-squares fit (MG_OP_EVAL_DEPTH_LS); ``scratch``: 512 x 5 doubles."""
+    ow, inv = eval_fit_width(H, W, max_res)
+    return make_op(L.OP_EVAL_DEPTH_LS, i=[H, W, int(disparity), ow], f=[inv], p=[pred, gt, mask, out5, scratch])
+
+
+def eval_depth_metrics(pred, gt, mask, sums5, out13, scratch, *, H, W, disparity=False, min_depth=None, max_depth=None):
+    """Align (``sums5`` from eval_depth_ls, None = as is), clip and score (MG_OP_EVAL_DEPTH_METRICS); ``scratch``: 512 x 11 doubles."""
+    return make_op(L.OP_EVAL_DEPTH_METRICS, i=[H, W, int(disparity), int(min_depth is not None), int(max_depth is not None)],
+                   f=[min_depth or 0.0, max_depth or 0.0], p=[pred, gt, mask, sums5, out13, scratch])
+
+
+def eval_normals(pred, gt, out9, err, ws, *, HW, masked=True):
+    """Angular error and its statistics incl. the exact median (MG_OP_EVAL_NORMALS); ``ws``: L.EVAL_WS_BYTES."""
+    return make_op(L.OP_EVAL_NORMALS, i=[int(masked)], p=[pred, gt, out9, err, ws], l=[HW])
+
+
 def memset(dst, nbytes, value=0):
     return make_op(L.OP_MEMSET, i=[value], p=[dst], l=[nbytes])
 
