@@ -258,7 +258,29 @@ enum mg_op_kind {
   MG_OP_EVAL_DEPTH_METRICS = 27,
   MG_OP_EVAL_NORMALS = 28,
   MG_OP_MEMSET = 30, /* p[0] dst ; i[0] byte value ; l[0] bytes */
-  MG_OP_COPY = 31    /* p[0] src p[1] dst ; l[0] bytes (device to device) */
+  MG_OP_COPY = 31,   /* p[0] src p[1] dst ; l[0] bytes (device to device) */
+  /* Scoring of one intrinsic-image target (albedo, shading, ...) against its ground truth on the device: compute_iid_metric of the
+   * reference (src/util/metric.py:263-338) with the PSNR / SSIM of torchmetrics it is called with (script/iid/eval.py); same
+   * file, same reduction scheme and the same guarantees as the EVAL ops above.  The three ops share their fields:
+   *   p[0] pred f32 [3][H][W]  p[1] gt f32 [3][H][W]  p[2] mask uint8 [3][H][W] (non-zero = valid) | NULL (every element valid)
+   *   p[3] out f64 [8] = psnr, ssim, alignment scale, quantile, brightness scale, valid elements, two reserved slots (at present
+   *   PREP leaves the two order statistics of its quantile there for the tests: not part of the interface)  p[4] workspace (MG_EVAL_WS_BYTES, 8-byte aligned; PREP leaves the mapping in it for the two
+   *   score ops of the same target) ; i[0] H  i[1] W  i[2] MG_IID_GAMMA_*: x <- x^gamma in fp32 on every load of both images
+   *   i[3] 1 = an up-to-scale target: the score ops map both images on load with what PREP found (they are never stored).
+   * IIDSCORE_PREP (shading, residual): s = S p g / S p p over the valid elements in fp64 (compute_alignment_scale, :319-334);
+   *   the brightness 0.3 g0 + 0.59 g1 + 0.11 g2 of the ground truth over the pixels of mask channel 0, its 0.9 quantile q with
+   *   linear interpolation at the fp32 position 0.9 (n - 1) like torch.quantile / np.quantile - the two order statistics are
+   *   exact, by the radix selection of EVAL_NORMALS on order-preserving keys; scale = q < 1e-4 ? 0 : 0.8 / q (quantile_map,
+   *   :337-375).  The mapping is pred <- clamp(scale * (fp32(s) * pred), 0, 1), gt <- clamp(scale * gt, 0, 1).  Writes out[2],
+   *   out[3], out[4] and the reserved slots (no pixel: NaN).  i[3] is ignored.
+   * IIDSCORE_PSNR: 10 log10(1 / mean(d^2)) over the valid elements, d taken in fp64 (identical images: +inf); writes out[5], out[0]
+   *   when i[4] != 0 and, for a plain target, out[2] = out[4] = 1 (no valid element: NaN).
+   * IIDSCORE_SSIM: mean SSIM (11 x 11 Gaussian window, sigma 1.5, c1 = 1e-4, c2 = 9e-4, reflect padding by 5 and the padded border
+   *   cropped: 3 (H - 10)(W - 10) values) with the invalid elements of both images set to 0; the five window moments are fp64 sums of
+   *   exact products; needs H, W >= 11; writes out[1] (no valid element: NaN). */
+  MG_OP_IIDSCORE_PREP = 32,
+  MG_OP_IIDSCORE_PSNR = 33,
+  MG_OP_IIDSCORE_SSIM = 34
 };
 
 enum { MG_EPI_BF16 = 0, MG_EPI_GEGLU = 1, MG_EPI_F32 = 2,
@@ -366,7 +388,7 @@ int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int
 
 /* One-pass validation (src/trainer/marigold_depth_trainer.py:510-601; script/depth/eval.py:176-240, script/normals/eval.py): score one
  * prediction against its ground truth on the device, with no host round trip between the fit and the scores.  The caller reads the
- * results back when it needs them - neither call synchronises.  workspace: MG_EVAL_WS_BYTES of device memory, 8-byte aligned, owned
+ * results back when it needs them - none of these calls synchronises.  workspace: MG_EVAL_WS_BYTES of device memory, 8-byte aligned, owned
  * by the call until the stream has passed it (one workspace per stream).
  *  mg_eval_depth: pred, gt fp32 [H][W], mask uint8 [H][W]; alignment MG_EVAL_ALIGN_*; align_max_res <= 0 = fit on every pixel;
  *  min_depth / max_depth: the dataset's clip limits, NaN = none; out13 f64 = the ten scores in script/depth/eval.py's order, scale,
@@ -379,6 +401,16 @@ int mg_eval_depth(const float* pred, const float* gt, const uint8_t* mask, int H
                   double min_depth, double max_depth, double* out13, void* workspace, void* stream);
 int mg_eval_normals(const float* pred, const float* gt, int64_t HW, int masked, double* out9, float* err_map_or_null,
                     void* workspace, void* stream);
+/*  mg_eval_iid: one target of one image, pred, gt fp32 [3][H][W] (H, W >= 11), mask uint8 [3][H][W] or NULL; up_to_scale != 0 for
+ *  shading / residual (MG_OP_IIDSCORE_PREP first); gamma_mode MG_IID_GAMMA_*: the conversions script/iid/eval.py applies before it
+ *  scores (2.2 for a target evaluated in linear space, 1 / 2.2 for Hypersim's albedo; BOTH = 2.2, then 1 / 2.2); metrics_mask
+ *  MG_IID_PSNR | MG_IID_SSIM.  out8 f64 = psnr, ssim, alignment scale, quantile, brightness scale, valid elements, two reserved
+ *  slots (do not read them); a slot nothing was asked to fill holds NaN; no valid element: all NaN and n = 0.  Same workspace
+ *  rule; does not synchronise. */
+enum { MG_IID_GAMMA_NONE = 0, MG_IID_GAMMA_2_2 = 1, MG_IID_GAMMA_INV_2_2 = 2, MG_IID_GAMMA_BOTH = 3 };
+enum { MG_IID_PSNR = 1, MG_IID_SSIM = 2 };
+int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W, int up_to_scale, int gamma_mode,
+                int metrics_mask, double* out8, void* workspace, void* stream);
 
 /* Host arithmetic of ensemble_depth's alignment objective (marigold/util/ensemble.py:129-152, as the closed form of
  * marigold_amd/ensemble.py): pairwise-RMSE cost of the aligned members and its gradient w.r.t. scales s[E] / shifts t[E],

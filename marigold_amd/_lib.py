@@ -29,6 +29,27 @@ OP_EVAL_DEPTH_LS, OP_EVAL_DEPTH_METRICS, OP_EVAL_NORMALS = 26, 27, 28
 EVAL_WS_BYTES = 128 * 1024   # MG_EVAL_WS_BYTES
 EVAL_ALIGN = {None: 0, "least_square": 1, "least_square_disparity": 2}   # MG_EVAL_ALIGN_*
 OP_MEMSET, OP_COPY = 30, 31
+OP_IIDSCORE_PREP, OP_IIDSCORE_PSNR, OP_IIDSCORE_SSIM = 32, 33, 34
+IID_GAMMA = {None: 0, 2.2: 1, 1.0 / 2.2: 2, (2.2, 1.0 / 2.2): 3}   # MG_IID_GAMMA_*
+IID_METRICS = {"psnr": 1, "ssim": 2}   # MG_IID_*
+
+
+def iid_gamma_mode(gamma):
+    """MG_IID_GAMMA_* of ``gamma``: None, 2.2, 1 / 2.2 or the pair (2.2, 1 / 2.2); a number within 1e-3 (relative) of 2.2 or 1 / 2.2
+    names that conversion (0.4545, numpy.float32(2.2)) - the kernels raise to the exact exponents."""
+    if gamma is None:
+        return 0
+    if isinstance(gamma, (list, tuple)):
+        modes = [iid_gamma_mode(g) for g in gamma]
+        if modes in ([1], [2]):
+            return modes[0]
+        if modes == [1, 2]:
+            return 3
+        raise ValueError(f"gamma {gamma!r}: only (2.2, 1 / 2.2), in that order, is a pair the scorer applies")
+    for mode, exponent in ((1, 2.2), (2, 1.0 / 2.2)):
+        if abs(float(gamma) - exponent) <= 1e-3 * exponent:
+            return mode
+    raise ValueError(f"gamma {gamma!r} is not None, 2.2, 1 / 2.2 or (2.2, 1 / 2.2)")
 EPI_BF16, EPI_GEGLU, EPI_F32, EPI_SOFTMAX2, EPI_XATTN2 = 0, 1, 2, 3, 4
 POST_NONE, POST_DEPTH, POST_NORMALS, POST_UNIT, POST_SCHED = 0, 1, 2, 3, 4
 
@@ -41,7 +62,7 @@ EXPORTS = [
     "mg_sched_step", "mg_ensemble_normals", "mg_ens_align_cost_grad", "mg_bfgs_minimize", "mg_ens_align_minimize", "mg_event_create", "mg_event_record",
     "mg_event_elapsed_ms", "mg_event_destroy", "mg_clock_probe", "mg_debug_read_workspace",
     "mg_model_load", "mg_model_destroy", "mg_model_info", "mg_model_device_bytes", "mg_model_validate", "mg_model_vae_encode",
-    "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals",
+    "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals", "mg_eval_iid",
 ]
 
 
@@ -120,6 +141,7 @@ def load(f16=False):
                                       ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_eval_depth.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3
     lib.mg_eval_normals.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4
+    lib.mg_eval_iid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

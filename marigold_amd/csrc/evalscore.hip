@@ -9,6 +9,8 @@
 // launch then adds the rows in block order.  No floating-point atomics: two launches on the same input give the same bits.
 // The median of the angles is exact: they are non-negative, so their bit patterns order as unsigned integers, and three histogram
 // passes over 11 / 11 / 10 bits (integer atomics in LDS, merged into a global histogram) select the two middle order statistics.
+// The same selection finds the brightness quantile of the intrinsic-image scores (compute_iid_metric, src/util/metric.py:263-338;
+// PSNR and a tiled fp64 SSIM) in the last part of this file.
 //
 // The maps are 0.3-0.6 M pixels: every kernel here is a few microseconds of streaming, the cost of a call is its launches.
 #include <math.h>
@@ -296,20 +298,32 @@ __global__ __launch_bounds__(128) void normals_reduce_kernel(const double* __res
   select_bin(st, hist0, 2048, 0, 11);
 }
 
-// passes 2 and 3: the histogram of the next `bits` bits of the angles that carry a rank's prefix; ghist [2][1 << bits]
-__global__ __launch_bounds__(EV_THREADS) void normals_hist_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                                  const float* __restrict__ err, const SelState* __restrict__ st,
-                                                                  unsigned* __restrict__ ghist, long long HW, int masked, int shift,
-                                                                  int bits) {
+// the values a selection runs over, as unsigned keys that order like the values: the angles of the normals protocol (non-negative,
+// so their bit patterns order as they stand); the IID brightness is IidBrightness below
+struct NormalsAngles {
+  const float *pred, *gt, *err;
+  long long HW;
+  int masked;
+  __device__ __forceinline__ bool key(long long i, unsigned& u) const {
+    float e;
+    if (!angle_of(pred, gt, err, HW, i, masked, e)) return false;
+    u = __float_as_uint(e);
+    return true;
+  }
+};
+
+// passes 2 and 3: the histogram of the next `bits` bits of the keys that carry a rank's prefix; ghist [2][1 << bits]
+template <class Src>
+__global__ __launch_bounds__(EV_THREADS) void select_hist_kernel(Src src, const SelState* __restrict__ st, unsigned* __restrict__ ghist,
+                                                                 long long N, int shift, int bits) {
   __shared__ unsigned hist[2 * 2048];
   const int bins = 1 << bits;
   for (int b = threadIdx.x; b < 2 * bins; b += EV_THREADS) hist[b] = 0u;
   __syncthreads();
   const unsigned p0 = st->prefix[0], p1 = st->prefix[1];
-  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < HW; i += (long long)gridDim.x * EV_THREADS) {
-    float e;
-    if (!angle_of(pred, gt, err, HW, i, masked, e)) continue;
-    const unsigned u = __float_as_uint(e);
+  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < N; i += (long long)gridDim.x * EV_THREADS) {
+    unsigned u;
+    if (!src.key(i, u)) continue;
     const unsigned hi = u >> (shift + bits), bin = (u >> shift) & (unsigned)(bins - 1);
     if (hi == p0) atomicAdd(&hist[bin], 1u);
     if (hi == p1) atomicAdd(&hist[bins + bin], 1u);
@@ -319,7 +333,7 @@ __global__ __launch_bounds__(EV_THREADS) void normals_hist_kernel(const float* _
     if (hist[b]) atomicAdd(&ghist[b], hist[b]);
 }
 
-__global__ __launch_bounds__(128) void normals_select_kernel(SelState* __restrict__ st, const unsigned* __restrict__ hist, int bins,
+__global__ __launch_bounds__(128) void select_step_kernel(SelState* __restrict__ st, const unsigned* __restrict__ hist, int bins,
                                                              int bits, double* __restrict__ out_median) {
   select_bin(st, hist, bins, bins, bits);
   if (!out_median) return;
@@ -329,6 +343,297 @@ __global__ __launch_bounds__(128) void normals_select_kernel(SelState* __restric
   const float lo = __uint_as_float(st->prefix[0]), hi = __uint_as_float(st->prefix[1]);
   const float med = (lo + hi) / 2.0f;
   *out_median = (st->n == 0 || st->nan != 0) ? (double)__builtin_nanf("") : (double)med;
+}
+
+// ---- intrinsic image decomposition ----------------------------------------------------------------------------------
+
+constexpr int II_N = 5;           // S p*g, S p*p, valid elements, brightness pixels, NaN brightness values
+constexpr int SS_T = 32;          // the SSIM kernel's output tile is SS_T x SS_T
+constexpr int SS_R = 5;           // radius of the 11-tap window
+constexpr int SS_K = 2 * SS_R + 1;
+constexpr int SS_S = SS_T + 2 * SS_R;   // the staged tile: output tile + halo
+
+// workspace layout of the MG_OP_IIDSCORE_* ops (bytes)
+constexpr size_t WS_II_PART = 0;
+constexpr size_t WS_II_STATE = WS_II_PART + (size_t)EV_BLOCKS * II_N * 8;   // SelState
+constexpr size_t WS_II_MAP = WS_II_STATE + 64;                              // IidMap: survives from PREP to the score ops
+constexpr size_t WS_II_HIST0 = WS_II_MAP + 64;
+constexpr size_t WS_II_HIST1 = WS_II_HIST0 + 2048 * 4;
+constexpr size_t WS_II_HIST2 = WS_II_HIST1 + 2 * 2048 * 4;
+constexpr size_t WS_II_PSNR_PART = WS_II_HIST2 + 2 * 1024 * 4;
+constexpr size_t WS_II_SSIM_PART = WS_II_PSNR_PART + (size_t)EV_BLOCKS * 2 * 8;
+constexpr size_t WS_IID_END = WS_II_SSIM_PART + (size_t)EV_BLOCKS * 2 * 8;
+static_assert(WS_IID_END <= MG_EVAL_WS_BYTES, "MG_EVAL_WS_BYTES too small");
+
+// what PREP leaves for the score kernels: pred <- clamp(q * (s * pred), 0, 1), gt <- clamp(q * gt, 0, 1)
+struct IidMap {
+  float s, q;
+};
+
+// the conversions of script/iid/eval.py:166-174 in fp32: bit 0 = x^2.2 (a target scored in linear space), bit 1 = x^(1/2.2) (Hypersim
+// albedo); both = one after the other, in that order
+__device__ __forceinline__ float iid_gamma(float x, int mode) {
+  if (mode & 1) x = powf(x, 2.2f);
+  if (mode & 2) x = powf(x, (float)(1.0 / 2.2));
+  return x;
+}
+
+// the two images as the scores see them: recomputed from (s, q) on every load, never stored
+struct IidImages {
+  const float *pred, *gt;
+  const uint8_t* mask;   // [3][HW] | NULL
+  const IidMap* map;     // NULL: a plain target
+  int gamma;
+  __device__ __forceinline__ bool valid(long long e) const { return !mask || mask[e]; }
+  __device__ __forceinline__ void load(long long e, float s, float q, float& p, float& g) const {
+    p = iid_gamma(pred[e], gamma);
+    g = iid_gamma(gt[e], gamma);
+    if (map) {
+      p = clip_keep_nan(q * (s * p), 0.f, 1.f);
+      g = clip_keep_nan(q * g, 0.f, 1.f);
+    }
+  }
+};
+
+// brightness of the ground truth over the pixels of mask channel 0 (quantile_map, metric.py:337-375).  Its sign is not known, so
+// the key flips the pattern into an order-preserving one: negative values complemented, the others with the sign bit set.
+struct IidBrightness {
+  const float* gt;
+  const uint8_t* mask;
+  long long HW;
+  int gamma;
+  __device__ __forceinline__ bool value(long long i, float& b) const {
+    if (mask && !mask[i]) return false;
+    const float g0 = iid_gamma(gt[i], gamma), g1 = iid_gamma(gt[HW + i], gamma), g2 = iid_gamma(gt[2 * HW + i], gamma);
+    b = (0.3f * g0 + 0.59f * g1) + 0.11f * g2;
+    return true;
+  }
+  static __device__ __forceinline__ unsigned to_key(float b) {
+    const unsigned u = __float_as_uint(b);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+  }
+  static __device__ __forceinline__ float from_key(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
+  __device__ __forceinline__ bool key(long long i, unsigned& u) const {
+    float b;
+    if (!value(i, b)) return false;
+    u = to_key(b);
+    return true;
+  }
+};
+
+// the sums of compute_alignment_scale (metric.py:319-334) over the valid elements and the first histogram of the brightness
+__global__ __launch_bounds__(EV_THREADS) void iid_prep_kernel(IidImages im, IidBrightness br, double* __restrict__ part,
+                                                              unsigned* __restrict__ ghist, long long HW) {
+  __shared__ unsigned hist[2048];
+  for (int b = threadIdx.x; b < 2048; b += EV_THREADS) hist[b] = 0u;
+  __syncthreads();
+  double acc[II_N];
+#pragma unroll
+  for (int k = 0; k < II_N; ++k) acc[k] = 0.0;
+  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < HW; i += (long long)gridDim.x * EV_THREADS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const long long e = c * HW + i;
+      if (!im.valid(e)) continue;
+      const double p = (double)iid_gamma(im.pred[e], im.gamma), g = (double)iid_gamma(im.gt[e], im.gamma);
+      acc[0] += p * g;
+      acc[1] += p * p;
+      acc[2] += 1.0;
+    }
+    float b;
+    if (!br.value(i, b)) continue;
+    acc[3] += 1.0;
+    acc[4] += b != b ? 1.0 : 0.0;
+    atomicAdd(&hist[IidBrightness::to_key(b) >> 21], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < 2048; b += EV_THREADS)
+    if (hist[b]) atomicAdd(&ghist[b], hist[b]);
+  block_sum_store<II_N>(acc, part + (size_t)blockIdx.x * II_N);
+}
+
+// one block: the alignment scale; the ranks of the two order statistics around 0.9 (n - 1); the first selection step.
+// The position is np.quantile's / torch.quantile's on fp32 input: (n - 1) * 0.9 evaluated in fp32.
+__global__ __launch_bounds__(128) void iid_prep_reduce_kernel(const double* __restrict__ part, double* __restrict__ out,
+                                                              SelState* __restrict__ st, IidMap* __restrict__ map,
+                                                              const unsigned* __restrict__ hist0, int nblk) {
+  __shared__ double S[II_N];
+  if (threadIdx.x < II_N) {
+    double v = 0.0;
+    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * II_N + threadIdx.x];
+    S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double s = S[0] / S[1];
+    out[2] = s;
+    map->s = (float)s;
+    const unsigned long long cnt = (unsigned long long)S[3];
+    st->n = cnt;
+    st->nan = (unsigned long long)S[4];
+    st->prefix[0] = st->prefix[1] = 0u;
+    unsigned long long lo = 0, hi = 0;
+    if (cnt) {
+      const float v = (float)(cnt - 1) * 0.9f;
+      lo = (unsigned long long)floorf(v);
+      hi = lo + 1;
+      if (lo >= cnt - 1) lo = hi = cnt - 1;
+    }
+    st->rem[0] = lo;
+    st->rem[1] = hi;
+  }
+  __syncthreads();
+  select_bin(st, hist0, 2048, 0, 11);
+}
+
+// the last selection step, then numpy's _lerp between the two order statistics in fp32 and the scale of quantile_map
+__global__ __launch_bounds__(128) void iid_quantile_kernel(SelState* __restrict__ st, const unsigned* __restrict__ hist,
+                                                           IidMap* __restrict__ map, double* __restrict__ out) {
+  select_bin(st, hist, 1024, 1024, 10);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const float a = IidBrightness::from_key(st->prefix[0]), b = IidBrightness::from_key(st->prefix[1]);
+  float q = __builtin_nanf(""), lo = q, hi = q;
+  if (st->n != 0 && st->nan == 0) {
+    const float v = (float)(st->n - 1) * 0.9f;
+    const float t = v - floorf(v);   // (both ranks the last element: a == b, whatever t)
+    const float d = b - a;
+    q = t >= 0.5f ? b - d * (1.0f - t) : a + d * t;
+    lo = a;
+    hi = b;
+  }
+  const float scale = (double)q < 1e-4 ? 0.f : (float)(0.8 / (double)q);   // (the host compares and divides q as a Python float)
+  map->q = scale;
+  out[3] = (double)q;
+  out[4] = (double)scale;
+  out[6] = (double)lo;
+  out[7] = (double)hi;
+}
+
+// squared error over the valid elements (metrics.psnr: the difference of the fp32 images is taken in fp64)
+__global__ __launch_bounds__(EV_THREADS) void iid_psnr_kernel(IidImages im, double* __restrict__ part, long long N) {
+  float s = 1.f, q = 1.f;
+  if (im.map) { s = im.map->s; q = im.map->q; }
+  double acc[2] = {0.0, 0.0};
+  for (long long e = (long long)blockIdx.x * EV_THREADS + threadIdx.x; e < N; e += (long long)gridDim.x * EV_THREADS) {
+    if (!im.valid(e)) continue;
+    float p, g;
+    im.load(e, s, q, p, g);
+    const double d = (double)p - (double)g;
+    acc[0] += d * d;
+    acc[1] += 1.0;
+  }
+  block_sum_store<2>(acc, part + (size_t)blockIdx.x * 2);
+}
+
+__global__ __launch_bounds__(64) void iid_psnr_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk,
+                                                            int mapped, int want_psnr) {
+  __shared__ double S[2];
+  if (threadIdx.x < 2) {
+    double v = 0.0;
+    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * 2 + threadIdx.x];
+    S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double n = S[1];
+  if (want_psnr) out[0] = 10.0 * log10(1.0 / (S[0] / n));   // identical images: 1 / 0 = +inf, like the host; n = 0: NaN
+  out[5] = n;
+  if (!mapped) out[2] = out[4] = n > 0.0 ? 1.0 : (double)__builtin_nanf("");
+}
+
+struct SsimWindow {
+  double w[SS_K];
+};
+
+// SSIM (metrics.ssim: 11 x 11 Gaussian window, sigma 1.5, reflect padding, the padded border cropped - so no kept value ever sees
+// a padded pixel and the kept values are those of image rows / columns [5, H - 5) x [5, W - 5)).  One workgroup owns a 32 x 32 tile
+// of kept values of one channel at a time (tiles blockIdx.x, blockIdx.x + gridDim.x, ... in that order, so a block's sum has one
+// order).  Per tile: the 42 x 42 patch (tile + halo of 5) of both images goes to LDS once, masked / mapped / gamma'd in staging;
+// the five moments x, y, xx, yy, xy - exact fp64 products of the fp32 values - are blurred along the rows into an fp64 LDS
+// intermediate [5][42][32] and then along the columns out of it; the per-pixel SSIM is formed in fp64 and summed.
+// fp64 throughout: sigma = E[x^2] - mu^2 cancels against c2 = 9e-4, and the host function is fp64.
+// LDS per workgroup: 2 x 42 x 42 x 4 = 14 112 B patches + 5 x 42 x 32 x 8 = 53 760 B intermediate + 64 B of the block sum = 67 936 B
+// of the CU's 160 KiB (163 840 B): 2 workgroups = 8 waves per CU, 2 per SIMD (130 VGPRs would allow 3: LDS is the limit).  Row pass: a wave reads 32 consecutive floats of two
+// patch rows (ds_read_b32, the halves of the wave on different rows: no conflict); column pass: 32 consecutive doubles of one
+// intermediate row per half wave (ds_read_b64, one 256 B bank row: no conflict).
+__global__ __launch_bounds__(EV_THREADS) void iid_ssim_kernel(IidImages im, SsimWindow win, double* __restrict__ part, int H, int W,
+                                                              int nty, int ntx) {
+  __shared__ float sx[SS_S][SS_S], sy[SS_S][SS_S];
+  __shared__ double rows[5][SS_S][SS_T];
+  float s = 1.f, q = 1.f;
+  if (im.map) { s = im.map->s; q = im.map->q; }
+  const long long HW = (long long)H * W;
+  const int OH = H - 2 * SS_R, OW = W - 2 * SS_R;
+  const double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
+  double acc[2] = {0.0, 0.0};   // the SSIM values; the valid elements staged (> 0: there is something to score)
+  for (int t = blockIdx.x; t < 3 * nty * ntx; t += gridDim.x) {
+    const int c = t / (nty * ntx), ty = (t / ntx) % nty, tx = t % ntx;
+    const int y0 = ty * SS_T, x0 = tx * SS_T;   // the patch's origin in the image = the tile's origin among the kept values
+    for (int idx = threadIdx.x; idx < SS_S * SS_S; idx += EV_THREADS) {
+      const int r = idx / SS_S, cc = idx - r * SS_S;
+      const int iy = y0 + r, ix = x0 + cc;
+      float p = 0.f, g = 0.f;
+      if (iy < H && ix < W) {
+        const long long e = c * HW + (long long)iy * W + ix;
+        if (im.valid(e)) {
+          im.load(e, s, q, p, g);
+          acc[1] += 1.0;
+        }
+      }
+      sx[r][cc] = p;
+      sy[r][cc] = g;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < SS_S * SS_T; idx += EV_THREADS) {
+      const int r = idx / SS_T, cc = idx - r * SS_T;
+      double mx = 0.0, my = 0.0, mxx = 0.0, myy = 0.0, mxy = 0.0;
+#pragma unroll
+      for (int k = 0; k < SS_K; ++k) {
+        const double x = (double)sx[r][cc + k], y = (double)sy[r][cc + k], w = win.w[k];
+        mx = fma(w, x, mx);
+        my = fma(w, y, my);
+        mxx = fma(w, x * x, mxx);
+        myy = fma(w, y * y, myy);
+        mxy = fma(w, x * y, mxy);
+      }
+      rows[0][r][cc] = mx;
+      rows[1][r][cc] = my;
+      rows[2][r][cc] = mxx;
+      rows[3][r][cc] = myy;
+      rows[4][r][cc] = mxy;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < SS_T * SS_T; idx += EV_THREADS) {
+      const int r = idx / SS_T, cc = idx - r * SS_T;
+      if (y0 + r >= OH || x0 + cc >= OW) continue;
+      double m[5];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < SS_K; ++k) v = fma(win.w[k], rows[j][r + k][cc], v);
+        m[j] = v;
+      }
+      const double mx = m[0], my = m[1];
+      const double sxx = m[2] - mx * mx, syy = m[3] - my * my, sxy = m[4] - mx * my;
+      acc[0] += ((2.0 * mx * my + c1) * (2.0 * sxy + c2)) / (((mx * mx + my * my) + c1) * ((sxx + syy) + c2));
+    }
+    __syncthreads();   // the next tile overwrites the patches and the intermediate
+  }
+  block_sum_store<2>(acc, part + (size_t)blockIdx.x * 2);
+}
+
+__global__ __launch_bounds__(64) void iid_ssim_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk,
+                                                            double count) {
+  __shared__ double S[2];
+  if (threadIdx.x < 2) {
+    double v = 0.0;
+    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * 2 + threadIdx.x];
+    S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) out[1] = S[1] > 0.0 ? S[0] / count : (double)__builtin_nanf("");
 }
 
 int grid_for(long long n) { return (int)max(1ll, min((n + EV_THREADS - 1) / EV_THREADS, (long long)EV_BLOCKS)); }
@@ -376,15 +681,66 @@ int mg_launch_evalscore(const mg_op* op, hipStream_t s) {
       SelState* const st = (SelState*)(ws + WS_NM_STATE);
       unsigned *h0 = (unsigned*)(ws + WS_NM_HIST0), *h1 = (unsigned*)(ws + WS_NM_HIST1), *h2 = (unsigned*)(ws + WS_NM_HIST2);
       const int masked = op->i[0] != 0, nblk = grid_for(HW);
+      const NormalsAngles angles{pred, gt, err, HW, masked};
       if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(ws + WS_NM_STATE, 0, WS_NORMALS_END - WS_NM_STATE, s));
       MG_LAUNCH(normals_stats_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, err, (double*)(ws + WS_NM_PART), h0, HW, masked);
       MG_LAUNCH(normals_reduce_kernel, dim3(1), dim3(128), 0, s, (const double*)(ws + WS_NM_PART), out, st, (const unsigned*)h0, nblk);
-      MG_LAUNCH(normals_hist_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, (const float*)err, (const SelState*)st, h1, HW,
-                masked, 10, 11);
-      MG_LAUNCH(normals_select_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h1, 2048, 11, (double*)nullptr);
-      MG_LAUNCH(normals_hist_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, (const float*)err, (const SelState*)st, h2, HW,
-                masked, 0, 10);
-      MG_LAUNCH(normals_select_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h2, 1024, 10, out + 1);
+      MG_LAUNCH(select_hist_kernel<NormalsAngles>, dim3(nblk), dim3(EV_THREADS), 0, s, angles, (const SelState*)st, h1, HW, 10, 11);
+      MG_LAUNCH(select_step_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h1, 2048, 11, (double*)nullptr);
+      MG_LAUNCH(select_hist_kernel<NormalsAngles>, dim3(nblk), dim3(EV_THREADS), 0, s, angles, (const SelState*)st, h2, HW, 0, 10);
+      MG_LAUNCH(select_step_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h2, 1024, 10, out + 1);
+      break;
+    }
+    case MG_OP_IIDSCORE_PREP:
+    case MG_OP_IIDSCORE_PSNR:
+    case MG_OP_IIDSCORE_SSIM: {
+      const char* const name = op->kind == MG_OP_IIDSCORE_PREP ? "iidscore_prep" : op->kind == MG_OP_IIDSCORE_PSNR ? "iidscore_psnr" : "iidscore_ssim";
+      const int H = op->i[0], W = op->i[1], gamma = op->i[2], mapped = op->i[3] != 0;
+      MG_REQUIRE(H >= 1 && W >= 1 && 3ll * H * W < (1ll << 31), "%s: bad size %d x %d", name, H, W);
+      MG_REQUIRE(op->kind != MG_OP_IIDSCORE_SSIM || (H >= SS_K && W >= SS_K),
+                 "%s: H, W >= %d required (an 11 x 11 window, reflect padding by 5 and a non-empty crop), got %d x %d", name, SS_K, H, W);
+      MG_REQUIRE(gamma >= MG_IID_GAMMA_NONE && gamma <= MG_IID_GAMMA_BOTH, "%s: unknown gamma mode %d", name, gamma);
+      MG_REQUIRE(op->p[0] && op->p[1] && op->p[3] && op->p[4], "%s: null pointer", name);
+      MG_REQUIRE(((uintptr_t)op->p[0] | (uintptr_t)op->p[1]) % 4 == 0, "%s: pred / gt not 4-byte aligned", name);
+      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4]) % 8 == 0, "%s: out / workspace not 8-byte aligned", name);
+      char* const ws = (char*)op->p[4];
+      double* const out = (double*)op->p[3];
+      const long long HW = (long long)H * W;
+      IidMap* const map = (IidMap*)(ws + WS_II_MAP);
+      const IidImages im{(const float*)op->p[0], (const float*)op->p[1], (const uint8_t*)op->p[2],
+                         op->kind != MG_OP_IIDSCORE_PREP && mapped ? map : nullptr, gamma};
+      if (op->kind == MG_OP_IIDSCORE_PREP) {
+        const IidBrightness br{im.gt, im.mask, HW, gamma};
+        SelState* const st = (SelState*)(ws + WS_II_STATE);
+        unsigned *h0 = (unsigned*)(ws + WS_II_HIST0), *h1 = (unsigned*)(ws + WS_II_HIST1), *h2 = (unsigned*)(ws + WS_II_HIST2);
+        const int nblk = grid_for(HW);
+        if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(ws + WS_II_STATE, 0, WS_II_PSNR_PART - WS_II_STATE, s));
+        MG_LAUNCH(iid_prep_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, im, br, (double*)(ws + WS_II_PART), h0, HW);
+        MG_LAUNCH(iid_prep_reduce_kernel, dim3(1), dim3(128), 0, s, (const double*)(ws + WS_II_PART), out, st, map, (const unsigned*)h0, nblk);
+        MG_LAUNCH(select_hist_kernel<IidBrightness>, dim3(nblk), dim3(EV_THREADS), 0, s, br, (const SelState*)st, h1, HW, 10, 11);
+        MG_LAUNCH(select_step_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h1, 2048, 11, (double*)nullptr);
+        MG_LAUNCH(select_hist_kernel<IidBrightness>, dim3(nblk), dim3(EV_THREADS), 0, s, br, (const SelState*)st, h2, HW, 0, 10);
+        MG_LAUNCH(iid_quantile_kernel, dim3(1), dim3(128), 0, s, st, (const unsigned*)h2, map, out);
+      } else if (op->kind == MG_OP_IIDSCORE_PSNR) {
+        const int nblk = grid_for(3 * HW);
+        MG_LAUNCH(iid_psnr_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, im, (double*)(ws + WS_II_PSNR_PART), 3 * HW);
+        MG_LAUNCH(iid_psnr_final_kernel, dim3(1), dim3(64), 0, s, (const double*)(ws + WS_II_PSNR_PART), out, nblk, mapped,
+                  op->i[4] != 0);
+      } else {
+        const int OH = H - 2 * SS_R, OW = W - 2 * SS_R;
+        const int nty = (OH + SS_T - 1) / SS_T, ntx = (OW + SS_T - 1) / SS_T;
+        const int nblk = min(3 * nty * ntx, EV_BLOCKS);
+        SsimWindow win;   // metrics.ssim: exp(-(d / sigma)^2 / 2), normalised
+        double sum = 0.0;
+        for (int k = 0; k < SS_K; ++k) {
+          const double d = (double)(k - SS_R) / 1.5;
+          sum += win.w[k] = exp(-(d * d) / 2.0);
+        }
+        for (int k = 0; k < SS_K; ++k) win.w[k] /= sum;
+        MG_LAUNCH(iid_ssim_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, im, win, (double*)(ws + WS_II_SSIM_PART), H, W, nty, ntx);
+        MG_LAUNCH(iid_ssim_final_kernel, dim3(1), dim3(64), 0, s, (const double*)(ws + WS_II_SSIM_PART), out, nblk,
+                  3.0 * (double)OH * (double)OW);
+      }
       break;
     }
     default: MG_REQUIRE(false, "evalscore: bad op kind %d", op->kind);
@@ -440,6 +796,33 @@ int mg_eval_normals(const float* pred, const float* gt, int64_t HW, int masked, 
   op.i[0] = masked;
   op.l[0] = HW;
   return mg_launch_evalscore(&op, (hipStream_t)stream);
+}
+
+int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W, int up_to_scale, int gamma_mode,
+                int metrics_mask, double* out8, void* workspace, void* stream) {
+  MG_REQUIRE(pred && gt && out8 && workspace, "mg_eval_iid: null pointer");
+  MG_REQUIRE(H >= SS_K && W >= SS_K, "mg_eval_iid: H, W >= %d required (an 11 x 11 window, reflect padding by 5 and a non-empty crop), got %d x %d",
+             SS_K, H, W);
+  MG_REQUIRE(metrics_mask >= 0 && metrics_mask <= (MG_IID_PSNR | MG_IID_SSIM), "mg_eval_iid: unknown metrics mask %d", metrics_mask);
+  MG_REQUIRE(((uintptr_t)out8 | (uintptr_t)workspace) % 8 == 0, "mg_eval_iid: out / workspace not 8-byte aligned");
+  if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(out8, 0xff, 8 * sizeof(double), (hipStream_t)stream));   // every slot NaN until an op fills it
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask_or_null; op.p[3] = out8; op.p[4] = workspace;
+  op.i[0] = H; op.i[1] = W; op.i[2] = gamma_mode; op.i[3] = up_to_scale != 0;
+  int rc = 0;
+  if (up_to_scale) {
+    op.kind = MG_OP_IIDSCORE_PREP;
+    if ((rc = mg_launch_evalscore(&op, (hipStream_t)stream))) return rc;
+  }
+  op.kind = MG_OP_IIDSCORE_PSNR;   // always: it counts the valid elements
+  op.i[4] = (metrics_mask & MG_IID_PSNR) != 0;
+  if ((rc = mg_launch_evalscore(&op, (hipStream_t)stream))) return rc;
+  if (metrics_mask & MG_IID_SSIM) {
+    op.kind = MG_OP_IIDSCORE_SSIM;
+    rc = mg_launch_evalscore(&op, (hipStream_t)stream);
+  }
+  return rc;
 }
 
 }  // extern "C"

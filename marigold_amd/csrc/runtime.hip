@@ -70,7 +70,10 @@ static int dispatch(const mg_op* op, hipStream_t s) {
     case MG_OP_COLORIZE: return mg_launch_resize(op, s);
     case MG_OP_EVAL_DEPTH_LS:
     case MG_OP_EVAL_DEPTH_METRICS:
-    case MG_OP_EVAL_NORMALS: return mg_launch_evalscore(op, s);
+    case MG_OP_EVAL_NORMALS:
+    case MG_OP_IIDSCORE_PREP:
+    case MG_OP_IIDSCORE_PSNR:
+    case MG_OP_IIDSCORE_SSIM: return mg_launch_evalscore(op, s);
     default: mg_set_error("mg_launch: unknown op kind %d", op->kind); return 2;
   }
 }

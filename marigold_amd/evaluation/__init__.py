@@ -5,4 +5,4 @@ command-line programs, ``metrics`` / ``alignment`` the scores on the host, ``dev
 from .alignment import align_depth_least_square, depth2disparity, disparity2depth  # noqa: F401
 from .datasets import DatasetMode, PredNameMode, get_dataset, get_pred_name, load_dataset_config  # noqa: F401
 from .metrics import MetricTracker  # noqa: F401
-from .device import score_depth, score_normals  # noqa: F401
+from .device import score_depth, score_iid, score_iid_sample, score_normals  # noqa: F401

@@ -1,6 +1,7 @@
 """The scores of ``metrics.py`` / ``alignment.py`` on the GPU (csrc/evalscore.hip): what the reference's validation loop
 does per image (src/trainer/marigold_depth_trainer.py:510-601) - fit, clip and score in one pass on the accelerator, with
-no prediction file in between.  One library call and one synchronisation (on the 13- or 9-double result) per image.
+no prediction file in between.  One library call and one synchronisation (on the 13- or 9-double result) per image; for
+intrinsic images one call per target and one synchronisation per sample (``score_iid_sample``).
 
 Same definitions as the host functions: fp32 element arithmetic, fp64 sums; the sums are reduced in a fixed order, so a
 score is the same bits on every call.  There is no host fallback: without the library or a GPU these functions raise.
@@ -30,9 +31,13 @@ def _on_device(a, device, dtype):
     return t.to(device=device, dtype=dtype).contiguous()
 
 
-def _setup(device, f16):
+def _require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: the device scorer has no CPU fallback (use evaluation.metrics on the host)")
+
+
+def _setup(device, f16):
+    _require_gpu()
     index = device.index if device.index is not None else torch.cuda.current_device()
     lib = L.init(index, f16)
     stream = torch.cuda.current_stream(device)
@@ -97,3 +102,79 @@ def score_normals(pred, gt, masked=True, return_error_map=False, *, rounded=True
     if return_error_map:
         return res, err[err != -1.0]   # dropped pixels hold -1 (an angle is >= 0 or NaN)
     return res
+
+
+_UP_TO_SCALE = ("shading", "residual")   # metrics.compute_iid_metric
+
+
+def _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, up_to_scale, gamma, metrics, out8, keep):
+    """One mg_eval_iid call on ``out8`` (a row of a device tensor); the uploaded tensors go to ``keep`` until the read-back."""
+    unknown = [m for m in metrics if m not in L.IID_METRICS]
+    if unknown:
+        raise NotImplementedError(f"IID metric '{unknown[0]}' (LPIPS needs pretrained network weights that are not part of this engine)")
+    mode = L.iid_gamma_mode(gamma)
+    p, g = _on_device(pred, device, torch.float32), _on_device(gt, device, torch.float32)
+    if p.ndim < 3 or tuple(p.shape[-3:]) != (3,) + tuple(p.shape[-2:]) or p.numel() != 3 * p.shape[-2] * p.shape[-1] \
+            or p.shape[-3:] != g.shape[-3:] or p.numel() != g.numel():
+        raise ValueError(f"score_iid: shapes {tuple(p.shape)}, {tuple(g.shape)} (want [3,H,W], leading 1s allowed)")
+    h, w = p.shape[-2:]
+    m = None
+    if valid_mask is not None:
+        m = _on_device(valid_mask, device, torch.bool)
+        if m.numel() != p.numel() or m.shape[-3:] != p.shape[-3:]:
+            raise ValueError(f"score_iid: mask shape {tuple(m.shape)} for images {tuple(p.shape)}")
+        m = m.view(torch.uint8)
+    keep += [p, g, m]
+    L.check(lib.mg_eval_iid(p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else None, h, w, int(up_to_scale),
+                            mode, sum(L.IID_METRICS[k] for k in set(metrics)), out8.data_ptr(), ws.data_ptr(), stream),
+            "mg_eval_iid", lib)
+
+
+def _iid_result(values):
+    return dict(psnr=values[0], ssim=values[1], scale=values[2], quantile=values[3], n=int(values[5]))
+
+
+def score_iid(pred, gt, target_name, valid_mask=None, *, metrics=("psnr", "ssim"), gamma=None, device=None, f16=False):
+    """metrics.compute_iid_metric for one target of one image -> ``{"psnr", "ssim", "scale", "quantile", "n"}`` (a metric not in
+    ``metrics``: NaN; ``scale``: the least-squares scale, 1 for a plain target; ``quantile``: the 0.9 brightness quantile, NaN for
+    a plain target; ``n``: valid elements, 0 -> every score NaN).  ``target_name`` "shading" / "residual" are up to scale: aligned
+    and brightness-mapped first.  ``pred`` / ``gt`` [3,H,W] (or [1,3,H,W]), H, W >= 11; ``valid_mask`` bool of the same shape or
+    None; ``gamma``: None, 2.2, 1 / 2.2 or (2.2, 1 / 2.2), a number within 1e-3 of one of them counting as it - ``x ** gamma`` in fp32 on both images first, as script/iid/eval.py does
+    for linear-space targets and Hypersim's albedo.  Numpy arrays are uploaded, CUDA tensors used in place; one read-back."""
+    _require_gpu()
+    device = _device_of(device, pred, gt, valid_mask)
+    with torch.cuda.device(device):
+        lib, ws, stream = _setup(device, f16)
+        out, keep = torch.empty(8, dtype=torch.float64, device=device), []
+        _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, target_name in _UP_TO_SCALE, gamma, metrics, out, keep)
+        values = out.cpu().tolist()   # the one synchronisation
+    return _iid_result(values)
+
+
+def score_iid_sample(preds, data, target_names, *, metrics=("psnr", "ssim"), use_mask=False, linear_targets=(), dataset_name="",
+                     device=None, f16=False):
+    """The value row of harness._score_iid for one sample, scored on the GPU: ``preds`` {target: [3,H,W] prediction} (a target that
+    is absent or None leaves ``None`` cells), ``data`` the dataset sample (``data[target]``, ``data["mask_" + target]``); values
+    metric-major per target; the 2.2 gamma for ``linear_targets`` and the Hypersim three-target albedo rule of
+    script/iid/eval.py:166-174.  Every target is launched before the one read-back."""
+    present = [t for t in target_names if preds.get(t) is not None]
+    rows = {}
+    if present:
+        _require_gpu()
+        device = _device_of(device, *[preds[t] for t in present])
+        with torch.cuda.device(device):
+            lib, ws, stream = _setup(device, f16)
+            out, keep = torch.empty((len(present), 8), dtype=torch.float64, device=device), []
+            for k, t in enumerate(present):
+                gamma = (2.2,) if t in linear_targets else ()
+                if "hypersim" in dataset_name and len(target_names) == 3 and t == "albedo":
+                    gamma += (1.0 / 2.2,)
+                gamma = None if not gamma else gamma[0] if len(gamma) == 1 else gamma
+                _iid_launch(lib, ws, stream, device, preds[t], data[t], data["mask_" + t] if use_mask else None,
+                            t in _UP_TO_SCALE, gamma, metrics, out[k], keep)   # (the calls share the stream's workspace, in stream order)
+            values = out.cpu().tolist()
+        rows = {t: _iid_result(v) for t, v in zip(present, values)}
+    row = []
+    for t in target_names:
+        row += [rows[t][m] for m in metrics] if t in rows else [None] * len(metrics)
+    return row

@@ -234,6 +234,22 @@ def eval_normals(pred, gt, out9, err, ws, *, HW, masked=True):
     return make_op(L.OP_EVAL_NORMALS, i=[int(masked)], p=[pred, gt, out9, err, ws], l=[HW])
 
 
+def iidscore_prep(pred, gt, mask, out8, ws, *, H, W, gamma=None):
+    """Alignment scale, exact 0.9 brightness quantile and its scale for an up-to-scale IID target (MG_OP_IIDSCORE_PREP);
+    ``mask`` uint8 [3,H,W] or None; ``ws``: L.EVAL_WS_BYTES, shared with the score ops of the same target."""
+    return make_op(L.OP_IIDSCORE_PREP, i=[H, W, L.iid_gamma_mode(gamma)], p=[pred, gt, mask, out8, ws])
+
+
+def iidscore_psnr(pred, gt, mask, out8, ws, *, H, W, gamma=None, up_to_scale=False, write_psnr=True):
+    """PSNR over the valid elements and their count (MG_OP_IIDSCORE_PSNR); ``up_to_scale``: map with what iidscore_prep left in ``ws``."""
+    return make_op(L.OP_IIDSCORE_PSNR, i=[H, W, L.iid_gamma_mode(gamma), int(up_to_scale), int(write_psnr)], p=[pred, gt, mask, out8, ws])
+
+
+def iidscore_ssim(pred, gt, mask, out8, ws, *, H, W, gamma=None, up_to_scale=False):
+    """Mean SSIM with the invalid elements zeroed (MG_OP_IIDSCORE_SSIM); H, W >= 11."""
+    return make_op(L.OP_IIDSCORE_SSIM, i=[H, W, L.iid_gamma_mode(gamma), int(up_to_scale)], p=[pred, gt, mask, out8, ws])
+
+
 def memset(dst, nbytes, value=0):
     return make_op(L.OP_MEMSET, i=[value], p=[dst], l=[nbytes])
 
