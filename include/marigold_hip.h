@@ -280,8 +280,18 @@ enum mg_op_kind {
    *   exact products; needs H, W >= 11; writes out[1] (no valid element: NaN). */
   MG_OP_IIDSCORE_PREP = 32,
   MG_OP_IIDSCORE_PSNR = 33,
-  MG_OP_IIDSCORE_SSIM = 34
+  MG_OP_IIDSCORE_SSIM = 34,
+  /* The intrinsic-image output stage (MarigoldIIDOutput.fill_entry, marigold/marigold_iid_pipeline.py:117-136) for all targets of one
+   * image: per target, if linear and up to scale x <- x / max(max over its 3 H W elements, 1e-6) (IEEE division, the maximum keeps
+   * NaN); if linear x <- powf(x, fp32(1 / 2.2)); then (x * 255).astype(uint8) as x86-64 numpy does it: truncation to int32, low 8
+   * bits; NaN and |x * 255| >= 2^31 -> 0.  At most two launches (the maxima, skipped when no target needs one; the map), no atomics:
+   * the same bits on every launch.
+   *  p[0] pred f32 [n][3][H][W]  p[1] out uint8 [n][H][W][3] (HWC)  p[2] workspace f32 [n][MG_IID_VIS_PARTS] (may be NULL when no
+   *  target is both linear and up to scale) ; i[0] n (<= 16)  i[1] H  i[2] W  i[3] bit t: target t is in linear space
+   *  i[4] bit t: target t is up to scale */
+  MG_OP_IID_VIS = 35
 };
+#define MG_IID_VIS_PARTS 128
 
 enum { MG_EPI_BF16 = 0, MG_EPI_GEGLU = 1, MG_EPI_F32 = 2,
        MG_EPI_SOFTMAX2 = 3 /* bf16 out = softmax over column pairs (2h, 2h+1) of f[2] * acc; i[27] = real columns, the rest -> 0:

@@ -30,6 +30,8 @@ EVAL_WS_BYTES = 128 * 1024   # MG_EVAL_WS_BYTES
 EVAL_ALIGN = {None: 0, "least_square": 1, "least_square_disparity": 2}   # MG_EVAL_ALIGN_*
 OP_MEMSET, OP_COPY = 30, 31
 OP_IIDSCORE_PREP, OP_IIDSCORE_PSNR, OP_IIDSCORE_SSIM = 32, 33, 34
+OP_IID_VIS = 35
+IID_VIS_PARTS = 128   # MG_IID_VIS_PARTS
 IID_GAMMA = {None: 0, 2.2: 1, 1.0 / 2.2: 2, (2.2, 1.0 / 2.2): 3}   # MG_IID_GAMMA_*
 IID_METRICS = {"psnr": 1, "ssim": 2}   # MG_IID_*
 

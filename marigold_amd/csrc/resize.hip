@@ -116,7 +116,119 @@ __global__ __launch_bounds__(256) void colorize_kernel(const float* __restrict__
   }
 }
 
+// The output stage of the intrinsic-image pipeline (marigold/marigold_iid_pipeline.py:117-136, MarigoldIIDOutput.fill_entry): per
+// target [3][H][W] in fp32 -> the HWC uint8 image PIL takes,
+//   up to scale:  x <- x / max(max over the target, 1e-6)   (IEEE fp32 division: numpy divides the array by a float32 scalar)
+//   linear:       x <- powf(x, fp32(1 / 2.2))
+//   all:          (x * 255).astype(uint8): truncation to int32, low 8 bits kept; NaN and |x * 255| >= 2^31 give 0 (x86-64 cvttss2si
+//                 returns 0x80000000 for them).
+// The maximum keeps NaN like numpy's (IEEE maximum), so it does not depend on the order: thread -> wave -> block -> one slot of
+// the target's row of a partial table, which every block of the map kernel reduces again.  Two launches for all targets of an image.
+constexpr int IV_THREADS = 256;
+
+__device__ __forceinline__ float iv_block_max(float v, float* __restrict__ red) {   // every thread of the block calls it
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max_keep_nan(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max_keep_nan(max_keep_nan(red[0], red[1]), max_keep_nan(red[2], red[3]));
+}
+
+// grid (parts, n): block (b, t) -> part[t][b] = max over its share of target t's n3 = 3 H W elements; targets outside `need` are skipped
+__global__ __launch_bounds__(IV_THREADS) void iid_vis_max_kernel(const float* __restrict__ src, float* __restrict__ part,
+                                                                 long long n3, unsigned need, int vec) {
+  __shared__ float red[IV_THREADS / 64];
+  const int t = blockIdx.y;
+  if (!((need >> t) & 1u)) return;
+  const float* __restrict__ x = src + (long long)t * n3;
+  const long long first = (long long)blockIdx.x * IV_THREADS + threadIdx.x, step = (long long)gridDim.x * IV_THREADS;
+  float m = -INFINITY;
+  if (vec) {   // n3 % 4 == 0 and a 16-byte aligned base: every target starts on a 16-byte boundary
+    const float4* __restrict__ x4 = (const float4*)x;
+    for (long long i = first; i < n3 / 4; i += step) {
+      const float4 v = x4[i];
+      m = max_keep_nan(max_keep_nan(max_keep_nan(m, v.x), max_keep_nan(v.y, v.z)), v.w);
+    }
+  } else {
+    for (long long i = first; i < n3; i += step) m = max_keep_nan(m, x[i]);
+  }
+  m = iv_block_max(m, red);
+  if (threadIdx.x == 0) part[t * MG_IID_VIS_PARTS + blockIdx.x] = m;
+}
+
+__device__ __forceinline__ unsigned iv_byte(float x, float m, bool scale, bool linear) {
+  if (scale) x = x / m;
+  if (linear) x = powf(x, (float)(1.0 / 2.2));
+  x = x * 255.0f;
+  const int k = fabsf(x) < 2147483648.0f ? (int)x : 0;   // (int) truncates toward zero; NaN fails the comparison
+  return (unsigned)k & 0xffu;
+}
+
+// grid (blocks, n).  vec: a lane owns four neighbouring pixels - three 16-byte loads, one per plane, and 12 contiguous output
+// bytes (a wave writes 768 contiguous bytes); otherwise one pixel per lane.
+__global__ __launch_bounds__(IV_THREADS) void iid_vis_map_kernel(const float* __restrict__ src, const float* __restrict__ part,
+                                                                 uint8_t* __restrict__ out, long long HW, int parts,
+                                                                 unsigned linear_mask, unsigned scale_mask, int vec) {
+  __shared__ float red[IV_THREADS / 64];
+  const int t = blockIdx.y;
+  const bool linear = (linear_mask >> t) & 1u, scale = linear && ((scale_mask >> t) & 1u);
+  float m = 1.0f;
+  if (scale) {   // (uniform over the block)
+    m = iv_block_max((int)threadIdx.x < parts ? part[t * MG_IID_VIS_PARTS + threadIdx.x] : -INFINITY, red);
+    m = 1e-6f > m ? 1e-6f : m;   // Python's max(m, 1e-6): a NaN maximum stays
+  }
+  const float* __restrict__ x = src + (long long)t * 3 * HW;
+  uint8_t* __restrict__ o = out + (long long)t * 3 * HW;
+  const long long first = (long long)blockIdx.x * IV_THREADS + threadIdx.x, step = (long long)gridDim.x * IV_THREADS;
+  if (vec) {   // HW % 4 == 0, src 16-byte and out 4-byte aligned
+    const float4 *__restrict__ r4 = (const float4*)x, *__restrict__ g4 = (const float4*)(x + HW), *__restrict__ b4 = (const float4*)(x + 2 * HW);
+    unsigned* __restrict__ o4 = (unsigned*)o;
+    for (long long q = first; q < HW / 4; q += step) {
+      const float4 r = r4[q], g = g4[q], b = b4[q];
+      const unsigned w0 = iv_byte(r.x, m, scale, linear) | iv_byte(g.x, m, scale, linear) << 8 | iv_byte(b.x, m, scale, linear) << 16 |
+                          iv_byte(r.y, m, scale, linear) << 24;
+      const unsigned w1 = iv_byte(g.y, m, scale, linear) | iv_byte(b.y, m, scale, linear) << 8 | iv_byte(r.z, m, scale, linear) << 16 |
+                          iv_byte(g.z, m, scale, linear) << 24;
+      const unsigned w2 = iv_byte(b.z, m, scale, linear) | iv_byte(r.w, m, scale, linear) << 8 | iv_byte(g.w, m, scale, linear) << 16 |
+                          iv_byte(b.w, m, scale, linear) << 24;
+      o4[3 * q + 0] = w0;
+      o4[3 * q + 1] = w1;
+      o4[3 * q + 2] = w2;
+    }
+  } else {
+    for (long long i = first; i < HW; i += step) {
+      o[3 * i + 0] = (uint8_t)iv_byte(x[i], m, scale, linear);
+      o[3 * i + 1] = (uint8_t)iv_byte(x[HW + i], m, scale, linear);
+      o[3 * i + 2] = (uint8_t)iv_byte(x[2 * HW + i], m, scale, linear);
+    }
+  }
+}
+
+static int launch_iid_vis(const mg_op* op, hipStream_t s) {
+  const int n = op->i[0], H = op->i[1], W = op->i[2];
+  const unsigned linear = (unsigned)op->i[3], up_to_scale = (unsigned)op->i[4];
+  MG_REQUIRE(n >= 1 && n <= 16, "iid_vis: 1 to 16 targets per launch (got %d)", n);
+  MG_REQUIRE(H > 0 && W > 0 && (long long)H * W <= (1ll << 30), "iid_vis: bad size %d x %d", H, W);
+  MG_REQUIRE(!((linear | up_to_scale) >> n), "iid_vis: a flag names a target beyond the %d given", n);
+  MG_REQUIRE(op->p[0] && op->p[1], "iid_vis: null pointer");
+  MG_REQUIRE((uintptr_t)op->p[0] % 4 == 0, "iid_vis: the prediction must be 4-byte aligned");
+  const unsigned need = linear & up_to_scale;   // the maximum is used by the linear, up-to-scale targets only
+  MG_REQUIRE(!need || (op->p[2] && (uintptr_t)op->p[2] % 4 == 0), "iid_vis: null or unaligned workspace (f32 [n][MG_IID_VIS_PARTS])");
+  const long long HW = (long long)H * W;
+  const int vec = HW % 4 == 0 && (uintptr_t)op->p[0] % 16 == 0 && (uintptr_t)op->p[1] % 4 == 0;
+  // a thread of the maximum takes at least 16 elements; the partial rows have MG_IID_VIS_PARTS slots
+  const int parts = (int)min((3 * HW + 16 * IV_THREADS - 1) / (16 * IV_THREADS), (long long)MG_IID_VIS_PARTS);
+  if (need)
+    MG_LAUNCH(iid_vis_max_kernel, dim3(parts, n), dim3(IV_THREADS), 0, s, (const float*)op->p[0], (float*)op->p[2], 3 * HW, need, vec);
+  const long long work = vec ? HW / 4 : HW;
+  MG_LAUNCH(iid_vis_map_kernel, dim3((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)1024), n), dim3(IV_THREADS), 0, s,
+            (const float*)op->p[0], (const float*)op->p[2], (uint8_t*)op->p[1], HW, parts, linear, up_to_scale, vec);
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int mg_launch_resize(const mg_op* op, hipStream_t s) {
+  if (op->kind == MG_OP_IID_VIS) return launch_iid_vis(op, s);
   if (op->kind == MG_OP_COLORIZE) {
     const long long n = op->l[0];
     MG_REQUIRE(n > 0 && op->p[0] && op->p[1] && op->p[2], "colorize: null pointer / empty map");

@@ -13,6 +13,11 @@ DataLoader(batch_size=1, num_workers=0) serialises decode -> predict -> save), a
 One-pass validation (depth, normals): ``infer_main --evaluate`` scores every image on the GPU as it leaves the engine
 (device.py; the reference's validation loop, src/trainer/marigold_depth_trainer.py:510-601) and writes the files of
 ``eval_main`` under ``--eval_output_dir``; ``eval_main --on_device`` runs the same scorer on read-back files.
+
+One-pass validation (iid): ``validate_iid_main`` (script/iid/validate.py) - the reference's IID validation loop
+(src/trainer/marigold_iid_trainer.py, ``validate``): every prediction is scored where the pipeline left it on the GPU
+(``IIDEntry.device_array``, device.score_iid_sample) and the files of ``eval_main("iid")`` are written.  It is a program of its
+own: ``infer_main("iid") --evaluate`` and ``eval_main("iid") --on_device`` keep refusing, as they always have.
 """
 import argparse
 import logging
@@ -46,8 +51,7 @@ def seed_all(seed=0):
 # ---- inference over a dataset ------------------------------------------------------------------------
 
 
-def infer_parser(kind):
-    p = argparse.ArgumentParser(description=f"Marigold : {_TASK[kind]} : Dataset Inference")
+def _model_arguments(p, kind):
     p.add_argument("--checkpoint", type=str, default=_DEFAULT_CKPT[kind], help="Checkpoint path or hub name.")
     p.add_argument("--dataset_config", type=str, required=True, help="Path to the config file of the evaluation dataset.")
     p.add_argument("--base_data_dir", type=str, required=True, help="Base path to the datasets.")
@@ -57,8 +61,9 @@ def infer_parser(kind):
                    help="Resolution the input is resized to before estimation; 0 = native.")
     p.add_argument("--ensemble_size", type=int, required=True, help="Number of predictions to be ensembled.")
     p.add_argument("--half_precision", "--fp16", action="store_true", help="Load the 16-bit weight variant.")
-    p.add_argument("--output_processing_res", action="store_true",
-                   help="Output at the processing resolution instead of resizing back to the input resolution.")
+
+
+def _run_arguments(p):
     p.add_argument("--resample_method", choices=["bilinear", "bicubic", "nearest"], default="bilinear")
     p.add_argument("--seed", type=int, default=None, help="Reproducibility seed; None = time-seeded.")
     p.add_argument("--yes", action="store_true", help="Do not ask before writing into an existing output dir.")
@@ -68,6 +73,14 @@ def infer_parser(kind):
     p.add_argument("--images_per_program", type=int, default=1,
                    help="Consecutive images of one processed size that share one denoising program (their members batched); "
                         "1 = one image per program.")
+
+
+def infer_parser(kind):
+    p = argparse.ArgumentParser(description=f"Marigold : {_TASK[kind]} : Dataset Inference")
+    _model_arguments(p, kind)
+    p.add_argument("--output_processing_res", action="store_true",
+                   help="Output at the processing resolution instead of resizing back to the input resolution.")
+    _run_arguments(p)
     p.add_argument("--evaluate", action="store_true",
                    help="Score every prediction on the GPU as it is produced and write per_sample_metrics.csv and "
                         "eval_metrics[-<alignment>].txt like eval.py (depth and normals).")
@@ -75,6 +88,29 @@ def infer_parser(kind):
     p.add_argument("--no_save_predictions", action="store_true", help="With --evaluate: do not write the .npy predictions.")
     if kind == "depth":
         _alignment_arguments(p)
+    return p
+
+
+def _iid_scoring_arguments(p, target_names=False):
+    p.add_argument("--use_mask", action="store_true", help="Evaluate only in the masked region.")
+    if target_names:
+        p.add_argument("--target_names", nargs="+", default=["albedo", "material"], type=str,
+                       help="A list of predicted targets to evaluate.")
+    p.add_argument("--targets_to_eval_in_linear_space", nargs="*", default=[None], type=str,
+                   help="Targets to evaluate in linear space (as opposed to sRGB by default).")
+    p.add_argument("--metrics", nargs="+", default=["psnr", "ssim"], choices=["psnr", "ssim"],
+                   help="(LPIPS of the reference needs pretrained network weights; not provided)")
+
+
+def validate_iid_parser():
+    """The flags of ``infer_parser("iid")`` that apply to a scored run (the output keeps the input's resolution: the ground
+    truth has it) and the scoring flags of ``eval_parser("iid")``; the targets are the pipeline's."""
+    p = argparse.ArgumentParser(description=f"Marigold : {_TASK['iid']} : One-Pass Validation")
+    _model_arguments(p, "iid")
+    _run_arguments(p)
+    p.add_argument("--eval_output_dir", type=str, default=None, help="Where the metric files go; default <output_dir>/eval.")
+    p.add_argument("--no_save_predictions", action="store_true", help="Do not write the .npy predictions.")
+    _iid_scoring_arguments(p)
     return p
 
 
@@ -122,46 +158,44 @@ def _save_npy(path, arr):
     np.save(path, arr)
 
 
-def infer_main(kind, argv=None, pipeline=None) -> int:
-    """``pipeline`` lets tests inject a ready pipeline object; otherwise the checkpoint is loaded onto the GPU."""
+def _load_pipeline(kind, args, pipeline):
+    """The injected ``pipeline``, or the checkpoint of ``args`` on the GPU."""
     import torch
-    logging.basicConfig(level=logging.INFO)
-    args = infer_parser(kind).parse_args(argv)
-    if args.ensemble_size > 15:
-        logging.warning("Running with large ensemble size will be slow.")
-    match_input_res = not args.output_processing_res
-    if 0 == args.processing_res and match_input_res is False:
-        logging.warning("Processing at native resolution without resizing output might NOT lead to exactly the "
-                        "same resolution, due to the padding and pooling properties of conv layers.")
+    if pipeline is not None:
+        return pipeline
+    if not torch.cuda.is_available():
+        raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
+    import marigold_amd as MA
+    cls = {"depth": MA.MarigoldDepthPipeline, "normals": MA.MarigoldNormalsPipeline,
+           "iid": MA.MarigoldIIDPipeline}[kind]
+    pipeline = cls.from_pretrained(args.checkpoint, variant="fp16" if args.half_precision else None,
+                                   torch_dtype=torch.float16 if args.half_precision else torch.float32)
+    return pipeline.to("cuda")
+
+
+def _open_run(kind, args, mode):
+    """Seed, output folder and dataset of a run over a dataset -> (seed, dataset), or None when the user keeps the folder."""
     logging.info(f"Inference settings: checkpoint = `{args.checkpoint}`, with denoise_steps = {args.denoise_steps}, "
                  f"ensemble_size = {args.ensemble_size}, processing resolution = {args.processing_res}, "
                  f"seed = {args.seed}; dataset config = `{args.dataset_config}`.")
-    if args.images_per_program < 1:
-        raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
-    if args.evaluate and kind == "iid":
-        raise ValueError("--evaluate scores depth and normals only: the IID metrics (SSIM, quantile mapping) run on the host, "
-                         "use script/iid/eval.py on the written predictions")
-    if args.no_save_predictions and not args.evaluate:
-        raise ValueError("--no_save_predictions without --evaluate would compute predictions and keep none of them")
     seed = int(time.time()) if args.seed is None else args.seed
     seed_all(seed)
     if not _confirm_existing(args.output_dir, args.yes):
-        return 0
+        return None
     os.makedirs(args.output_dir, exist_ok=True)
     logging.info(f"output dir = {args.output_dir}")
-    dataset = get_dataset(load_dataset_config(args.dataset_config), args.base_data_dir,
-                          DatasetMode.EVAL if args.evaluate else DatasetMode.RGB_ONLY)   # (EVAL samples carry rgb_int + the ground truth)
+    dataset = get_dataset(load_dataset_config(args.dataset_config), args.base_data_dir, mode)
     if dataset.spec.kind != kind:
         raise AssertionError(f"'{dataset.name}' is a {dataset.spec.kind} dataset, not {kind}")
-    if pipeline is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
-        import marigold_amd as MA
-        cls = {"depth": MA.MarigoldDepthPipeline, "normals": MA.MarigoldNormalsPipeline,
-               "iid": MA.MarigoldIIDPipeline}[kind]
-        pipeline = cls.from_pretrained(args.checkpoint, variant="fp16" if args.half_precision else None,
-                                       torch_dtype=torch.float16 if args.half_precision else torch.float32)
-        pipeline = pipeline.to("cuda")
+    return seed, dataset
+
+
+def _predict_dataset(kind, args, dataset, pipeline, seed, match_input_res, save=True, consume=None, score=None):
+    """The loop ``infer_main`` and ``validate_iid_main`` share: samples decoded one image ahead on a reader thread, up to
+    ``--maps_in_flight`` images on the GPU (``map_images``), predictions saved behind the GPU on writer threads.  ``score(sample,
+    output, files)`` -> one ``(label, values)`` row per image, in input order; ``consume`` takes the iterator of those rows
+    (the metric writer) while the loop runs."""
+    import torch
     device = getattr(pipeline, "device", "cpu")
     n = len(dataset)
     t0 = time.perf_counter()
@@ -193,19 +227,17 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
             outs = (pipeline(im, generator=generator_of(), **kw) for im in images())
         writes = []
 
-        def results():   # saves each output behind the GPU; with --evaluate yields its scores
+        def results():   # saves each output behind the GPU; with a scorer yields its row
             for i, out in enumerate(outs):
                 files = _prediction_files(kind, dataset, pipeline, samples[i]["rgb_relative_path"], out)
-                if not args.no_save_predictions:
+                if save:
                     for rel, arr in files:
                         writes.append(writer.submit(_save_npy, os.path.join(args.output_dir, rel), arr))
-                if args.evaluate:
-                    yield _score_on_device(kind, args, dataset, samples[i], files[0][1], names)
+                if score is not None:
+                    yield score(samples[i], out, files)
                 samples[i] = None
-        if args.evaluate:
-            names = list(M.DEPTH_METRICS if kind == "depth" else M.NORMALS_METRICS)
-            _write_eval_files(kind, args.eval_output_dir or os.path.join(args.output_dir, "eval"), dataset, args.output_dir,
-                              names, results(), getattr(args, "alignment", None))
+        if consume is not None:
+            consume(results())
         else:
             for _ in results():
                 pass
@@ -214,6 +246,78 @@ def infer_main(kind, argv=None, pipeline=None) -> int:
     dt = time.perf_counter() - t0
     logging.info(f"{_TASK[kind]} inference on {dataset.disp_name}: {n} images in {dt:.1f} s "
                  f"({n / max(dt, 1e-9):.2f} img/s)")
+
+
+def infer_main(kind, argv=None, pipeline=None) -> int:
+    """``pipeline`` lets tests inject a ready pipeline object; otherwise the checkpoint is loaded onto the GPU."""
+    logging.basicConfig(level=logging.INFO)
+    args = infer_parser(kind).parse_args(argv)
+    if args.ensemble_size > 15:
+        logging.warning("Running with large ensemble size will be slow.")
+    match_input_res = not args.output_processing_res
+    if 0 == args.processing_res and match_input_res is False:
+        logging.warning("Processing at native resolution without resizing output might NOT lead to exactly the "
+                        "same resolution, due to the padding and pooling properties of conv layers.")
+    if args.images_per_program < 1:
+        raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
+    if args.evaluate and kind == "iid":
+        raise ValueError("--evaluate scores depth and normals only: the IID metrics (SSIM, quantile mapping) run on the host, "
+                         "use script/iid/eval.py on the written predictions")
+    if args.no_save_predictions and not args.evaluate:
+        raise ValueError("--no_save_predictions without --evaluate would compute predictions and keep none of them")
+    run = _open_run(kind, args, DatasetMode.EVAL if args.evaluate else DatasetMode.RGB_ONLY)   # (EVAL samples carry rgb_int + the ground truth)
+    if run is None:
+        return 0
+    seed, dataset = run
+    pipeline = _load_pipeline(kind, args, pipeline)
+    if not args.evaluate:
+        _predict_dataset(kind, args, dataset, pipeline, seed, match_input_res)
+        return 0
+    names = list(M.DEPTH_METRICS if kind == "depth" else M.NORMALS_METRICS)
+    _predict_dataset(kind, args, dataset, pipeline, seed, match_input_res, save=not args.no_save_predictions,
+                     score=lambda sample, out, files: _score_on_device(kind, args, dataset, sample, files[0][1], names),
+                     consume=lambda rows: _write_eval_files(kind, args.eval_output_dir or os.path.join(args.output_dir, "eval"), dataset,
+                                                            args.output_dir, names, rows, getattr(args, "alignment", None)))
+    return 0
+
+
+def _linear_targets(linear, target_names):
+    """``--targets_to_eval_in_linear_space`` checked against the targets (script/iid/eval.py:96-103)."""
+    for t in linear:
+        if t is not None and t not in target_names:
+            raise ValueError(f"'{t}' specified in targets_to_eval_in_linear_space does not belong to the "
+                             f"predicted targets: target_names={target_names}")
+    return linear
+
+
+def validate_iid_main(argv=None, pipeline=None) -> int:
+    """Predict and score an IID dataset in one pass: ``infer_main("iid")``'s run with every output scored on the GPU where the
+    pipeline left it (``IIDEntry.device_array``: no upload of a prediction, one read-back of the scores per sample), and the
+    ``per_sample_metrics.csv`` / ``eval_metrics.txt`` of ``eval_main("iid")`` written under ``--eval_output_dir``.  The targets are
+    ``pipeline.target_names``."""
+    from . import device as DV
+    logging.basicConfig(level=logging.INFO)
+    args = validate_iid_parser().parse_args(argv)
+    if args.ensemble_size > 15:
+        logging.warning("Running with large ensemble size will be slow.")
+    if args.images_per_program < 1:
+        raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
+    pipeline = _load_pipeline("iid", args, pipeline)
+    targets = list(pipeline.target_names)
+    linear = _linear_targets(args.targets_to_eval_in_linear_space, targets)
+    run = _open_run("iid", args, DatasetMode.EVAL)
+    if run is None:
+        return 0
+    seed, dataset = run
+    names = [f"{m}_{t}" for t in targets for m in args.metrics]
+
+    def score(sample, out, files):
+        preds = {t: out[t].device_array if out[t].device_array is not None else out[t].array for t in targets}
+        return sample["rgb_relative_path"], DV.score_iid_sample(preds, sample, targets, metrics=args.metrics, use_mask=args.use_mask,
+                                                                 linear_targets=linear, dataset_name=dataset.name)
+    _predict_dataset("iid", args, dataset, pipeline, seed, True, save=not args.no_save_predictions, score=score,
+                     consume=lambda rows: _write_eval_files("iid", args.eval_output_dir or os.path.join(args.output_dir, "eval"), dataset,
+                                                            args.output_dir, names, rows))
     return 0
 
 
@@ -228,15 +332,10 @@ def eval_parser(kind):
     p.add_argument("--output_dir", type=str, required=True, help="Output directory.")
     if kind == "depth":
         _alignment_arguments(p)
-    else:
+    elif kind == "normals":
         p.add_argument("--use_mask", action="store_true", help="Evaluate only in the masked region.")
-    if kind == "iid":
-        p.add_argument("--target_names", nargs="+", default=["albedo", "material"], type=str,
-                       help="A list of predicted targets to evaluate.")
-        p.add_argument("--targets_to_eval_in_linear_space", nargs="*", default=[None], type=str,
-                       help="Targets to evaluate in linear space (as opposed to sRGB by default).")
-        p.add_argument("--metrics", nargs="+", default=["psnr", "ssim"], choices=["psnr", "ssim"],
-                       help="(LPIPS of the reference needs pretrained network weights; not provided)")
+    else:
+        _iid_scoring_arguments(p, target_names=True)
     p.add_argument("--no_cuda", action="store_true", help="(reference flag; scoring runs on the host here)")
     if kind != "iid":
         p.add_argument("--on_device", action="store_true",
@@ -330,10 +429,7 @@ def eval_main(kind, argv=None) -> int:
     elif kind == "normals":
         names, score = list(M.NORMALS_METRICS), _score_normals
     else:
-        for t in args.targets_to_eval_in_linear_space:
-            if t is not None and t not in args.target_names:
-                raise ValueError(f"'{t}' specified in targets_to_eval_in_linear_space does not belong to the "
-                                 f"predicted targets: target_names={args.target_names}")
+        _linear_targets(args.targets_to_eval_in_linear_space, args.target_names)
         names, score = [f"{m}_{t}" for t in args.target_names for m in args.metrics], _score_iid
     _write_eval_files(kind, args.output_dir, dataset, args.prediction_dir, names,
                       (score(args, dataset, data, names) for data in dataset), getattr(args, "alignment", None))

@@ -205,6 +205,16 @@ def colorize(depth, lut, out, *, n, lo=0.0, hi=1.0):
     return make_op(L.OP_COLORIZE, f=[lo, hi], p=[depth, lut, out], l=[n])
 
 
+def iid_vis(pred, out, ws, *, n, H, W, linear, up_to_scale):
+    """The IID output stage for the ``n`` targets of one image (MG_OP_IID_VIS): fp32 [n,3,H,W] -> uint8 [n,H,W,3]; ``linear`` /
+    ``up_to_scale``: one bool per target; ``ws``: fp32 [n, L.IID_VIS_PARTS], needed when a target is both."""
+    linear, up_to_scale = [bool(v) for v in linear], [bool(v) for v in up_to_scale]
+    if len(linear) != n or len(up_to_scale) != n:
+        raise ValueError(f"iid_vis: {n} targets, {len(linear)} linear and {len(up_to_scale)} up_to_scale flags")
+    linear_bits, scale_bits = (sum(1 << t for t, v in enumerate(flags) if v) for flags in (linear, up_to_scale))
+    return make_op(L.OP_IID_VIS, i=[n, H, W, linear_bits, scale_bits], p=[pred, out, ws])
+
+
 def eval_fit_width(H, W, max_res):
     """(sub-sampled width, fp32(1 / factor)) of the least-squares fit under ``alignment_max_res`` - evaluation/alignment.py:
     factor = min(max_res / (H, W)), only the width shrinks; (0, 0.0) = fit on every pixel."""

@@ -26,8 +26,8 @@ from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .schedulers import DDIMScheduler, LCMScheduler
 from .util.batchsize import find_batch_size
-from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method, max_res_size,
-                              pil_to_tensor, resize, resize_max_res)
+from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method,
+                              iid_visualization_device, max_res_size, pil_to_tensor, resize, resize_max_res)
 
 
 @dataclass
@@ -727,11 +727,13 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
 @dataclass
 class IIDEntry:
     """One decomposed component (reference marigold/marigold_iid_pipeline.py:59-77): ``array`` [3,H,W] in
-    [0,1], ``image`` PIL RGB, ``uncertainty`` [3,H,W] | None."""
+    [0,1], ``image`` PIL RGB, ``uncertainty`` [3,H,W] | None.  ``device_array`` (extension): the fp32 CUDA tensor ``array`` was read
+    back from, [3,H,W], when the prediction was finished on the GPU - what the device scorer takes in place of an upload."""
     name: str
     array: Optional[np.ndarray] = None
     image: Optional[Image.Image] = None
     uncertainty: Optional[np.ndarray] = None
+    device_array: Optional[torch.Tensor] = None
 
 
 class MarigoldIIDOutput:
@@ -744,12 +746,15 @@ class MarigoldIIDOutput:
         self._by_name = {e.name: e for e in self.entries}
         self._filled = set()
 
-    def fill_entry(self, name: str, prediction: torch.Tensor, uncertainty: Optional[torch.Tensor] = None,
-                   target_properties: Optional[Dict[str, Any]] = None) -> None:
+    def _check_unfilled(self, name: str) -> None:
         if name not in self._by_name:
             raise KeyError(f"Unknown entry name: {name}")
         if name in self._filled:
             raise RuntimeError(f"Entry {name} already filled")
+
+    def fill_entry(self, name: str, prediction: torch.Tensor, uncertainty: Optional[torch.Tensor] = None,
+                   target_properties: Optional[Dict[str, Any]] = None) -> None:
+        self._check_unfilled(name)
         array = prediction.squeeze().cpu().numpy()
         vis = array
         space = target_properties[name].get("prediction_space", "srgb")
@@ -757,10 +762,18 @@ class MarigoldIIDOutput:
             if target_properties[name].get("up_to_scale", False):
                 vis = vis / max(vis.max(), 1e-6)
             vis = vis ** (1 / 2.2)
+        self._set_entry(name, array, chw2hwc((vis * 255).astype(np.uint8)),
+                        None if uncertainty is None else uncertainty.squeeze().cpu().numpy())
+
+    def _set_entry(self, name: str, array: np.ndarray, image_hwc: np.ndarray, uncertainty: Optional[np.ndarray] = None,
+                   device_array: Optional[torch.Tensor] = None) -> None:
+        """Store one finished component: ``image_hwc`` is the uint8 [H,W,3] picture of ``array``."""
+        self._check_unfilled(name)
         entry = self._by_name[name]
         entry.array = array
-        entry.image = Image.fromarray(chw2hwc((vis * 255).astype(np.uint8)))
-        entry.uncertainty = None if uncertainty is None else uncertainty.squeeze().cpu().numpy()
+        entry.image = Image.fromarray(image_hwc)
+        entry.uncertainty = uncertainty
+        entry.device_array = device_array
         self._filled.add(name)
 
     @property
@@ -815,6 +828,21 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
 
     def fill_outputs(self, output: MarigoldIIDOutput, final_pred: torch.Tensor,
                      pred_uncert: Optional[torch.Tensor] = None):
+        """``final_pred`` [1,3n,H,W] -> the entries of ``output``.  A CUDA prediction is finished on the device: one launch pair for
+        the pictures of all targets (MG_OP_IID_VIS), then one read-back each for the arrays, the uncertainties and the pictures;
+        a host tensor goes through ``fill_entry`` (numpy)."""
+        if final_pred.is_cuda:
+            props, n = self.target_properties, self.n_targets
+            linear = [props[t].get("prediction_space", "srgb") == "linear" for t in self.target_names]
+            up_to_scale = [bool(props[t].get("up_to_scale", False)) for t in self.target_names]
+            dev = final_pred.contiguous().reshape(n, 3, final_pred.shape[-2], final_pred.shape[-1])
+            images = iid_visualization_device(dev, linear, up_to_scale)
+            arrays = dev.cpu().numpy()
+            uncerts = None if pred_uncert is None else pred_uncert.reshape(n, 3, *pred_uncert.shape[-2:]).cpu().numpy()
+            images = images.cpu().numpy()
+            for i, name in enumerate(self.target_names):   # (squeeze: what fill_entry does to its slice)
+                output._set_entry(name, arrays[i].squeeze(), images[i], None if uncerts is None else uncerts[i].squeeze(), dev[i])
+            return
         for i, name in enumerate(self.target_names):
             output.fill_entry(name=name, prediction=final_pred[:, 3 * i:3 * i + 3],
                               uncertainty=None if pred_uncert is None else pred_uncert[:, 3 * i:3 * i + 3],

@@ -139,6 +139,30 @@ def colorize_depth_device(depth: torch.Tensor, min_depth=0.0, max_depth=1.0, cma
     return out
 
 
+def iid_visualization_device(pred: torch.Tensor, linear, up_to_scale) -> torch.Tensor:
+    """Device form of the images ``MarigoldIIDOutput.fill_entry`` builds, for all targets of one image at once: fp32 CUDA
+    ``pred`` [n, 3, H, W] (or [3, H, W]) -> uint8 CUDA [n, H, W, 3].  Per target t: ``linear[t]`` = its prediction space is
+    linear (display gamma 1 / 2.2), ``up_to_scale[t]`` = a linear target is divided by max(its maximum, 1e-6) first; then
+    ``(x * 255).astype(uint8)``.  csrc/resize.hip, MG_OP_IID_VIS: at most two launches on the caller's current stream."""
+    from .. import _lib as L, ops as O
+    if pred.dim() == 3:
+        pred = pred[None]
+    assert pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4 and pred.shape[1] == 3, \
+        f"iid_visualization_device: fp32 CUDA [n, 3, H, W] expected, got {pred.dtype} {tuple(pred.shape)} on {pred.device}"
+    n, _, h, w = pred.shape
+    linear, up_to_scale = [bool(v) for v in linear], [bool(v) for v in up_to_scale]
+    if len(linear) != n or len(up_to_scale) != n:
+        raise ValueError(f"iid_visualization_device: {n} target(s), {len(linear)} linear and {len(up_to_scale)} up_to_scale flag(s)")
+    with torch.cuda.device(pred.device):
+        src = pred.contiguous()
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=src.device)
+        ws = None
+        if any(a and b for a, b in zip(linear, up_to_scale)):
+            ws = torch.empty((n, L.IID_VIS_PARTS), dtype=torch.float32, device=src.device)
+        O.launch(O.iid_vis(src, out, ws, n=n, H=h, W=w, linear=linear, up_to_scale=up_to_scale))
+    return out
+
+
 def chw2hwc(chw):
     assert 3 == len(chw.shape)
     if isinstance(chw, torch.Tensor):
