@@ -3,8 +3,10 @@ mg_igemm_auto_variant + the automatic split-K rule) is not the fastest tile on, 
 split-K count that measured fastest on an MI355X - written by ``tools/sweep_program.py --emit-db`` from timings of the REAL
 launches of the denoising / VAE programs (real buffers and epilogues) at the ensemble sizes one GPU sees (E = 10 on one GPU;
 5 / 3 / 2 / 1 members per GPU when a map's ten members are sharded over 2 / 4 / 8 GPUs), committed with its sweep logs under
-``profiles/``.  A shape absent from the table runs the heuristic; every variant named here is covered by the parity tests
-(tests/test_gpu_kernels.py lists them; the folded launches' tile / split pairs in FOLD_CASES).  The table is gfx950's: the library
+``profiles/``.  A shape absent from the table runs the heuristic.  Every entry is covered as form x tile x split count:
+tests/test_gpu_tuned_launches.py takes its parameter list from this table - every (key without M, tile, split-K count) runs once at
+the entry's own N and K on a reduced M against float64 - and tests/test_tuned_launches_host.py pins the fields the key does not
+carry to the ops of the full-size programs (results: docs/history/tuned_launch_parity.md).  The table is gfx950's: the library
 itself refuses any other device (mg_init), so no second gate is needed here.  The choice is a pure function of the op - deterministic, the same on every rank.
 
 Key = (M, N, K, taps, stride, epilogue, transposed section?, batch_z, residual?, row statistics out?, folded LayerNorm in?,
