@@ -31,44 +31,23 @@ enum mg_op_kind {
   /* conv3x3 / conv1x1 / Linear / batched GEMM as ONE implicit-GEMM bf16 MFMA kernel.
    * Replaces torch conv2d / linear / matmul inside diffusers UNet2DConditionModel and
    * AutoencoderKL (reference call sites marigold_depth_pipeline.py:461-463, 491-492, 512-513).
-   *  p[0] A bf16 [B][H][W][lda>=Cin]   p[1] Wt bf16 [N][ldw>=taps*Cin] (k = (ky*3+kx)*Cin+c)
-   *  p[2] out                          p[3] bias f32[N] | NULL
-   *  p[4] rowvec f32 [B][N] | NULL (time-embedding add)   p[5] residual bf16 [M][ldr] | NULL
-   *  p[6] out2 (transposed section)    p[7] A1 bf16 [B][H][W][lda1] | NULL: second channel source - channels [C0, Cin)
-   *  of every tap come from A1, [0, C0) from A (the UNet's skip concat; i[24] = C0, i[25] = lda1)
-   *  p[8] ln_out f32 [M][N/32 + 1][2] bytes | NULL: the LayerNorm statistics of the tensor this launch produces (bf16
-   *  epilogue, N % 32 == 0, f[1] = eps): every tile writes (sum, sum of squares) of its rows over each 32-column slot into
-   *  [M][N/32][2], and the last column tile of a row block to finish reduces them to (mean, rstd) rows [M][2] stored
-   *  BEHIND the slots (at ln_out + M * (N/32) * 8 bytes) - that address is the ln_in of the consuming layers.  Launches
+   * The slots are named by the MG_IGEMM_* enumerators below, each with its meaning; what spans several of them:
+   *  Second source (P_A1, I_C0, I_LDA1): channels [C0, Cin) of every tap come from A1, [0, C0) from A - the UNet's skip concat,
+   *  never materialised.
+   *  Statistics hand-off (P_LN_OUT, F_LN_EPS, I_TICKETS_LO / _HI): ln_out f32 [M][N/32 + 1][2] holds the LayerNorm statistics
+   *  of the tensor this launch produces (bf16 epilogue, N % 32 == 0): every tile writes (sum, sum of squares) of its rows over each
+   *  32-column slot into [M][N/32][2], and the last column tile of a row block to finish reduces them to (mean, rstd) rows [M][2]
+   *  stored BEHIND the slots (at ln_out + M * (N/32) * 8 bytes) - that address is the ln_in of the consuming layers.  Launches
    *  that write statistics share one ticket array: they must be stream-ordered with respect to each other.
-   *  p[9] ln_in f32 [M][2] (mean, rstd) | NULL, p[10] ln_g f32 [N], p[11] ln_c f32 [N]: LayerNorm FOLDED into this Linear layer
-   *  (diffusers BasicTransformerBlock: norm1 -> attn1.to_q/k/v, norm2 -> attn2.to_q, norm3 -> ff.net.0.proj): A holds the
-   *  raw rows x, Wt = W * gamma, and out = rstd[m] * (acc - mean[m] * ln_g[n]) + ln_c[n] with ln_g[n] = sum_k Wt[n][k],
-   *  ln_c[n] = sum_k beta[k] W[n][k] + bias[n]; (mean, rstd) come from the producer's ln_out.  No separate normalisation
-   *  pass, no normalised tensor in HBM.
-   *  i[0] B  i[1] H  i[2] W  i[3] Cin  i[4] Ho  i[5] Wo
-   *  i[6] N  i[7] taps (1 | 9 | 4 = the sub-pixel form of nearest-2x + conv3x3: batch_z = 4 output parities, see
-   *  MG_OP_CONV3X3)  i[8] stride  i[9] pad  i[10] Hu  i[11] Wu (virtual nearest-
-   *  upsampled input size, 0 = none)  i[12] epilogue (MG_EPI_*)  i[13] ldo  i[14] trans_from
-   *  (columns >= this go to out2 as [img][n-trans_from][ldt] transposed; -1 = none)
-   *  i[15] batch_z  i[16] ldr  i[17] lda  i[18] ldt  i[19] tile variant (0 = auto; 20..53 force a tile,
-   *  60..63 the 256x256 ping-pong schedule - used by the tuning sweep and the parity tests, see
-   *  igemm2.hip::dispatch_tile)  i[20] ldw
-   *  i[21] rowvec broadcast (1 = a single [N] row shared by every image)
-   *  i[22], i[23] un-padded N, K for FLOP accounting (0 = as launched; ignored by the kernel)
-   *  i[26] 1 = the transposed section stores its tokens in accumulator order inside groups of 16 (MG_OP_FLASH_ATTN64 i[7])
-   *  i[29], i[30] low / high 32 bits of the device address of the caller's row-block tickets for the p[8] statistics
-   *  hand-off (65536 zeroed uint32, one buffer per program / stream; 0 = the library's global buffer: single stream only)
-   *  p[12] X0 bf16 [B][H][W][ldx0], p[13] X1 bf16 [B][H][W][ldx1] | NULL, i[32] = Cx, i[33] = Cx0, i[34] ldx0, i[35] ldx1: a 1x1 convolution
-   *  of a SECOND tensor folded in as extra K (diffusers ResnetBlock2D: conv2(h) + conv_shortcut(x) in ONE launch - no shortcut
-   *  launch, no residual round trip): K = taps * Cin + Cx, weight row n = [conv weights (taps * Cin) | shortcut weights (Cx)],
-   *  the extra K tiles read pixel (y, x) of X0 (channels [0, Cx0)) and X1 ([Cx0, Cx): the UNet's skip concat); taps = 9, stride 1,
-   *  pad 1 only; Cx, Cx0 multiples of 64; the bias is the two layers' sum
-   *  i[31] split-K: 0 = automatic (few output tiles x long K: fp32 partials + a fixed-order reduce launch), n >= 1 = exactly n
-   *  K ranges per tile (1 = none) - bf16 epilogue without row statistics / folded LayerNorm / batching only
-   *  p[14] split-K workspace of the caller (64 MiB, 16-byte aligned) | NULL = the library's own, which programs on ONE stream may
-   *  share (stream-ordered reuse); programs that run concurrently on several streams each bring their own
-   *  l[0..3] z-strides (elements) of A, Wt, out, residual      f[0] scale on the accumulator */
+   *  Folded LayerNorm (P_LN_IN, P_LN_G, P_LN_C; diffusers BasicTransformerBlock: norm1 -> attn1.to_q/k/v, norm2 -> attn2.to_q,
+   *  norm3 -> ff.net.0.proj): A holds the raw rows x, Wt = W * gamma, and out = rstd[m] * (acc - mean[m] * ln_g[n]) + ln_c[n] with
+   *  ln_g[n] = sum_k Wt[n][k], ln_c[n] = sum_k beta[k] W[n][k] + bias[n]; (mean, rstd) come from the producer's ln_out.  No
+   *  separate normalisation pass, no normalised tensor in HBM.
+   *  Folded shortcut (P_X0, P_X1, I_CX, I_CX0, I_LDX0, I_LDX1): a 1x1 convolution of a SECOND tensor folded in as extra K
+   *  (diffusers ResnetBlock2D: conv2(h) + conv_shortcut(x) in ONE launch - no shortcut launch, no residual round trip):
+   *  K = taps * Cin + Cx, weight row n = [conv weights (taps * Cin) | shortcut weights (Cx)], the extra K tiles read pixel (y, x)
+   *  of X0 (channels [0, Cx0)) and X1 ([Cx0, Cx): the UNet's skip concat); taps = 9, stride 1, pad 1 only; Cx, Cx0 multiples of
+   *  64; the bias is the two layers' sum. */
   MG_OP_IGEMM = 1,
   /* GroupNorm, 3 launches (stats partials -> per-(b,c) scale/shift -> apply [+SiLU]).
    * Replaces torch group_norm + silu in every ResNet block / Transformer2D input norm.
@@ -97,42 +76,30 @@ enum mg_op_kind {
    * epilogue(x[M][K] W[N][K]^T).  A wave keeps 32 whole rows of x in registers for the launch and the weights stream past
    * it in 64-column stages, pre-packed in MFMA fragment order with a per-stage trailer of per-channel constants
    * (marigold_amd/weights.py::pack_rowgemm; csrc/rowgemm.hip).  M % 32 == 0, N % 64 == 0, N >= 128; K = 640 runs 8 waves
-   * per workgroup (i[10] = 0 | 8), K = 320 4 / 8 / 12.
-   *  p[0] x bf16 [M][ldx]  p[1] packed weights  p[2] out bf16 [M][ldo]  p[3] residual bf16 [M][ldr] | NULL (may alias out)
-   *  p[4] (mean, rstd) f32 [M][2] of the rows of x | NULL: LayerNorm folded (the packed trailer holds its g and c vectors)
-   *  p[5] (mean, rstd) f32 [M][2] of the OUTPUT rows | NULL  p[6] V^T bf16 [B][N - i[9]][ldt] (QKV form)
-   *  p[7] GroupNorm scale/shift f32 [B][2][K] | NULL: x is normalised while it is loaded (bf16(x * scale + shift))
-   *  i: M, K, N, ldx, ldo, ldr, form (0 bias [+ residual] [+ row statistics], 1 GEGLU: stage = 32 value + 32 gate
-   *  channels, out [M][N/2], 2 QKV: columns >= i[9] go to V^T in MG_OP_FLASH_ATTN64's permuted key order), i[7] tokens per
-   *  image (forms with p[6] / p[7]; % 32 == 0), i[8] ldt, i[9] first V column (% 64 == 0), i[10] waves per workgroup
-   *  (0 = 12; 4 / 8 / 12), i[12] column split (0 / 1 = none; n: the N / 64 stages are shared out over n workgroups per row
-   *  block - few rows, many columns; not with p[5]) ; f[0] LayerNorm eps of p[5].
+   * per workgroup (I_WAVES = 0 | 8), K = 320 4 / 8 / 12.
+   * The slots are named by the MG_ROWGEMM_* enumerators below.  The forms (I_FORM):
+   *  0 bias [+ residual] [+ row statistics]; 1 GEGLU: stage = 32 value + 32 gate channels, out [M][N/2]; 2 QKV: columns >=
+   *  I_TRANS_FROM go to V^T (P_VT) in MG_OP_FLASH_ATTN64's permuted key order.
    *  form 3: the collapsed 2-token cross-attention (as MG_EPI_XATTN2) in place on the residual stream: N = 64 score
-   *  columns, i[11] = 2 x heads of them live, f[1] softmax scale; p[1] = weights.pack_rowgemm_xattn (scores stage + VO^T
-   *  fragments + bias), p[4] required, out[M][K] = P VO^T + bias + x, p[5] its row statistics; out may alias x.  K = 640 /
-   *  1280 (the deeper levels): the K-split kernel - 32-row workgroups whose four waves split K and the output channels,
-   *  p[1] = weights.pack_rowgemm_xattn_ksplit.  p[8] (tuning only): per-wave phase cycle stamps | NULL.
-   *  form 1 with p[9] (round 6; K = 320, no column split): the collapsed cross-attention as the PROLOGUE of the GEGLU launch
-   *  (BasicTransformerBlock: x += attn2(norm2(x)); ff(norm3(x))) - p[9] = a weights.pack_rowgemm_xattn image, p[4] = (mean, rstd) of
-   *  the rows AS LOADED (norm2's), i[11] = 2 x heads, f[1] softmax scale; the rows are updated in registers, written once to
-   *  p[10] bf16 [M][ldx] (may alias x: ff.out's residual) and the GEGLU projection's folded LayerNorm (norm3, f[0] eps) takes its
-   *  statistics from the wave's own sums.  Bit-identical to the form-3 launch followed by the plain form-1 launch. */
+   *  columns, I_SM_COLS = 2 x heads of them live, F_SM_SCALE the softmax scale; P_WP = weights.pack_rowgemm_xattn (scores stage +
+   *  VO^T fragments + bias), P_LN_IN required, out[M][K] = P VO^T + bias + x, P_LN_OUT its row statistics; out may alias x.
+   *  K = 640 / 1280 (the deeper levels): the K-split kernel - 32-row workgroups whose four waves split K and the output channels,
+   *  P_WP = weights.pack_rowgemm_xattn_ksplit.
+   *  form 1 with P_XATTN (round 6; K = 320, no column split): the collapsed cross-attention as the PROLOGUE of the GEGLU launch
+   *  (BasicTransformerBlock: x += attn2(norm2(x)); ff(norm3(x))) - P_XATTN = a weights.pack_rowgemm_xattn image, P_LN_IN = (mean,
+   *  rstd) of the rows AS LOADED (norm2's), I_SM_COLS = 2 x heads, F_SM_SCALE the softmax scale; the rows are updated in registers,
+   *  written once to P_XOUT bf16 [M][ldx] (may alias x: ff.out's residual) and the GEGLU projection's folded LayerNorm (norm3,
+   *  F_LN_EPS) takes its statistics from the wave's own sums.  Bit-identical to the form-3 launch followed by the plain form-1
+   *  launch. */
   MG_OP_ROWGEMM = 10,
   /* Self-attention core, head dim 64, bf16 MFMA flash attention with LDS-staged K / V^T
    * tiles (replaces diffusers Attention / SDPA / xformers, run.py:217-220).
-   *  p[0] Q bf16 (row stride ldq)  p[1] K (row stride ldq)  p[2] Vt bf16 [B][heads*64][ldvt]
-   *  p[3] O bf16 (row stride ldo); i: B, heads, Ntok, ldq, ldo, ldvt, variant (0 = current
-   *  kernel, 1 = generation-1 kernel kept for A/B runs), i[7] 1 = Vt's keys are in the order [0-3, 8-11, 4-7, 12-15]
-   *  inside every group of 16 (as written by MG_OP_IGEMM i[26]; Ntok % 16 == 0) ; p[4] tuning only: cycle stamps | NULL ;
-   *  l[0] q batch stride l[1] k batch stride l[2] vt batch stride l[3] o batch stride;
-   *  f[0] softmax scale.
-   *  With i[7] = 1 and Ntok % 256 == 0 (>= 256) the current kernel is the hand-placed one (flash4w.hip; variant 26 forces
+   * The slots are named by the MG_FLASH64_* enumerators below.
+   *  With I_VT_PERM = 1 and Ntok % 256 == 0 (>= 256) the current kernel is the hand-placed one (flash4w.hip; variant 26 forces
    *  its 32x32x16-MFMA stream, 27 the 16x16x32 one with the row sums on the matrix pipe - chosen by itself at >= 4 096 tokens
-   *  from two blocks of 256 queries per CU): softmax against a fixed per-query reference, exact, with an in-kernel running-maximum fallback for rows whose sums
-   *  reach f[1] (0 = 2^100; tests force the fallback with a tiny value).  Optional p[5]: workspace (16-byte aligned, i[8] KB,
-   *  ZEROED once by the caller, then owned by this op's launches on ONE stream - tickets return to zero): the blocks of 256
-   *  queries left over beyond a multiple of the CU count are then split along the keys over the chip (bit-reproducible);
-   *  4 KB + 69 632 bytes x 4 x (blocks % CUs) suffice; i[9]: 0 = split when it pays, 1 = always, 2 = never. */
+   *  from two blocks of 256 queries per CU): softmax against a fixed per-query reference, exact, with an in-kernel running-maximum
+   *  fallback for rows whose sums reach F_REDO_THR.  With the optional workspace P_WS (I_WS_KB, I_SPLIT) the blocks of 256 queries
+   *  left over beyond a multiple of the CU count are split along the keys over the chip (bit-reproducible). */
   MG_OP_FLASH_ATTN64 = 6,
   /* Self-attention core of ONE head of width 512 (the mid-block attention of AutoencoderKL: diffusers Attention in
    * UNetMidBlock2D, marigold_depth_pipeline.py:491-492, 512-513), flash form: the scores stay in registers.
@@ -181,19 +148,11 @@ enum mg_op_kind {
   /* Patch-resident conv3x3 (stride 1, pad 1) with the ResNet block's GroupNorm + SiLU fused into the operand staging
    * (diffusers ResnetBlock2D: norm1 -> silu -> conv1, norm2 -> silu -> conv2), the UNet's skip concat folded into the
    * channel loop (torch.cat([hidden, skip]) in the up blocks) and Upsample2D's nearest-2x + conv in sub-pixel form.
-   *  p[0] A0 bf16 [B][H][W][lda0 >= C0]  p[1] Wt bf16 [N][ldw >= 9*Cin], k = (ky*3+kx)*Cin + c, Cin = C0 + C1
-   *       (sub-pixel mode: [4][N][4*Cin], parity z = 2a+b, k = (ty*2+tx)*Cin + c - weights.py::pack_conv3x3_subpix)
-   *  p[2] out bf16 [B][H][W][ldo] (sub-pixel: [B][2H][2W][ldo])  p[3] bias f32 [N] | NULL
-   *  p[4] rowvec f32 [B][N] | NULL  p[5] residual bf16 (out's shape, row stride ldr) | NULL
-   *  p[6] A1 bf16 [B][H][W][lda1 >= C1] | NULL (second channel source)
-   *  p[7] scale_shift f32 [B][2][Cin] | NULL: input = silu?(x * scale + shift) for in-image pixels (MG_OP_GN_FINALIZE's
-   *       output; zero padding stays zero)
-   *  i[0] B  i[1] H  i[2] W  i[3] C0  i[4] C1  i[5] N  i[6] sub-pixel 2x mode  i[7] silu  i[8] lda0  i[9] lda1
-   *  i[10] ldo  i[11] ldr  i[12] ldw  i[13] rowvec broadcast  i[14] tile variant (0 = auto)
-   *  l[0] parity stride of Wt in elements (sub-pixel mode)
-   *  p[8] (optional) f32 [B][i[16]][N / i[15]][2]: (sum, sum of squares) of every group of i[15] (4 | 8 | 16 | 32) output
-   *  channels over each tile's pixels, of the values as stored - the partial table MG_OP_GN_FINALIZE reduces (slots = i[16] =
-   *  mg_conv3x3_gn_slots(op), HW = H W or 4 H W): the next GroupNorm's statistics without a pass over the tensor. */
+   * The slots are named by the MG_CONV3X3_* enumerators below.  Cin = C0 + C1; weights k = (ky*3+kx)*Cin + c (sub-pixel mode:
+   * [4][N][4*Cin], parity z = 2a+b, k = (ty*2+tx)*Cin + c - weights.py::pack_conv3x3_subpix, L_SW the parity stride).
+   *  Output statistics (P_GN_PART, I_GN_CPG, I_GN_SLOTS): f32 [B][slots][N / cpg][2], (sum, sum of squares) of every group of cpg
+   *  (4 | 8 | 16 | 32) output channels over each tile's pixels, of the values as stored - the partial table MG_OP_GN_FINALIZE
+   *  reduces (slots = mg_conv3x3_gn_slots(op), HW = H W or 4 H W): the next GroupNorm's statistics without a pass over the tensor. */
   MG_OP_CONV3X3 = 17,
   /* The output heads: GroupNorm apply [+ SiLU] + conv3x3 (pad 1) to <= 4 channels in one launch (conv_norm_out -> conv_act ->
    * conv_out of the UNet and of the VAE decoder - the tail of the modules the reference calls at marigold_depth_pipeline.py:461-463
@@ -294,13 +253,13 @@ enum mg_op_kind {
 #define MG_IID_VIS_PARTS 128
 
 enum { MG_EPI_BF16 = 0, MG_EPI_GEGLU = 1, MG_EPI_F32 = 2,
-       MG_EPI_SOFTMAX2 = 3 /* bf16 out = softmax over column pairs (2h, 2h+1) of f[2] * acc; i[27] = real columns, the rest -> 0:
+       MG_EPI_SOFTMAX2 = 3 /* bf16 out = softmax over column pairs (2h, 2h+1) of F_SM_SCALE * acc; I_SM_COLS = real columns, the rest -> 0:
                               the collapsed 2-token cross-attention's probabilities straight from the scores GEMM */,
        MG_EPI_XATTN2 = 4   /* the whole collapsed cross-attention in one launch (diffusers Attention with a 2-token context,
                               BasicTransformerBlock.attn2): N = 64 score columns as in MG_EPI_SOFTMAX2; the probabilities stay in
-                              registers as the operand of a second MFMA stage against p[6] = W2 bf16 [i[28]][64] (the context's
-                              values pushed through to_out), out[M][i[28]] = P W2^T + bias (p[3], of the second stage) + residual
-                              (p[5]); p[8] = f32 [M][2] (mean, rstd) of the OUTPUT rows (one wave owns whole rows: no slots, no
+                              registers as the operand of a second MFMA stage against P_OUT2 = W2 bf16 [I_C2][64] (the context's
+                              values pushed through to_out), out[M][I_C2] = P W2^T + bias (P_BIAS, of the second stage) + residual
+                              (P_RESIDUAL); P_LN_OUT = f32 [M][2] (mean, rstd) of the OUTPUT rows (one wave owns whole rows: no slots, no
                               ticket).  out may alias A and the residual (a row block belongs to one workgroup). */ };
 enum { MG_POST_NONE = 0, MG_POST_DEPTH = 1, MG_POST_NORMALS = 2, MG_POST_UNIT = 3 /* IID: clip, (x+1)/2 */,
        MG_POST_SCHED = 4 /* scheduler update in place of the store, see MG_OP_POST_NCHW */ };
@@ -312,6 +271,169 @@ typedef struct mg_op {
   void* p[16];
   int64_t l[4];
 } mg_op;
+
+/* Field names of the four kinds with many launch forms: MG_<KIND>_<array>_<NAME> is the index of that field in mg_op's i / f / p /
+ * l array.  This is the one table of the wire format (the values are positions: they never change, new fields are appended);
+ * marigold_amd/_lib.py mirrors it (tests/test_host.py compares the two) and marigold_amd/ops.py decodes an op by these names. */
+enum mg_igemm_i {
+  MG_IGEMM_I_B = 0,             /* images */
+  MG_IGEMM_I_H = 1,             /* input height */
+  MG_IGEMM_I_W = 2,             /* input width */
+  MG_IGEMM_I_CIN = 3,           /* input channels (both sources together; % 64 == 0) */
+  MG_IGEMM_I_HO = 4,            /* output height */
+  MG_IGEMM_I_WO = 5,            /* output width: M = B * Ho * Wo rows */
+  MG_IGEMM_I_N = 6,             /* output columns */
+  MG_IGEMM_I_TAPS = 7,          /* 1 | 9 | 4 = the sub-pixel form of nearest-2x + conv3x3: batch_z = 4 output parities, see MG_OP_CONV3X3 */
+  MG_IGEMM_I_STRIDE = 8,
+  MG_IGEMM_I_PAD = 9,
+  MG_IGEMM_I_HU = 10,           /* virtual nearest-up-sampled input height (0 = none) */
+  MG_IGEMM_I_WU = 11,           /* ... and width */
+  MG_IGEMM_I_EPI = 12,          /* epilogue (MG_EPI_*) */
+  MG_IGEMM_I_LDO = 13,          /* row stride of out */
+  MG_IGEMM_I_TRANS_FROM = 14,   /* columns >= this go to out2 as [img][n - trans_from][ldt] transposed; -1 = none */
+  MG_IGEMM_I_BATCH_Z = 15,      /* batched GEMMs (0 = 1), strides in l[] */
+  MG_IGEMM_I_LDR = 16,          /* row stride of the residual (0 = N) */
+  MG_IGEMM_I_LDA = 17,          /* row stride of A (0 = C0, the channels A holds) */
+  MG_IGEMM_I_LDT = 18,          /* row stride of the transposed section */
+  MG_IGEMM_I_VARIANT = 19,      /* tile variant: 0 = automatic; 22-26, 29, 32, 35, 36, 46, 51, 54, 62, 72, 73 force a tile (the tuning
+                                   table, its sweep and the parity tests - igemm2.hip::dispatch_tile) */
+  MG_IGEMM_I_LDW = 20,          /* row stride of Wt (0 = taps * Cin + Cx) */
+  MG_IGEMM_I_ROWVEC_BCAST = 21, /* 1 = rowvec is a single [N] row shared by every image */
+  MG_IGEMM_I_N_ALG = 22,        /* un-padded N for FLOP accounting (0 = as launched; ignored by the kernel) */
+  MG_IGEMM_I_K_ALG = 23,        /* un-padded K for FLOP accounting (0 = as launched; ignored by the kernel) */
+  MG_IGEMM_I_C0 = 24,           /* with A1: the channels A holds (% 64 == 0) */
+  MG_IGEMM_I_LDA1 = 25,         /* row stride of A1 (0 = Cin - C0) */
+  MG_IGEMM_I_TRANS_PERM = 26,   /* 1 = the transposed section stores its tokens in accumulator order inside groups of 16 (MG_FLASH64_I_VT_PERM) */
+  MG_IGEMM_I_SM_COLS = 27,      /* MG_EPI_SOFTMAX2 / _XATTN2: real score columns, the rest -> 0 */
+  MG_IGEMM_I_C2 = 28,           /* MG_EPI_XATTN2: output channels of the second stage */
+  MG_IGEMM_I_TICKETS_LO = 29,   /* low / high 32 bits of the device address of the caller's row-block tickets for the P_LN_OUT */
+  MG_IGEMM_I_TICKETS_HI = 30,   /* hand-off (65536 zeroed uint32, one buffer per program / stream; 0 = the library's global buffer: single stream only) */
+  MG_IGEMM_I_SPLITS = 31,       /* split-K: 0 = automatic (few output tiles x long K: fp32 partials + a fixed-order reduce launch), n >= 1 =
+                                   exactly n K ranges per tile (1 = none) - bf16 epilogue without row statistics / folded LayerNorm / batching only */
+  MG_IGEMM_I_CX = 32,           /* folded shortcut: its input channels (% 64 == 0) */
+  MG_IGEMM_I_CX0 = 33,          /* ... of which X0 holds the first Cx0 (with X1) */
+  MG_IGEMM_I_LDX0 = 34,         /* row stride of X0 (0 = the channels it holds) */
+  MG_IGEMM_I_LDX1 = 35          /* row stride of X1 (0 = Cx - Cx0) */
+};
+enum mg_igemm_f {
+  MG_IGEMM_F_SCALE = 0,         /* scale on the accumulator (0 = 1) */
+  MG_IGEMM_F_LN_EPS = 1,        /* eps of the statistics written to P_LN_OUT */
+  MG_IGEMM_F_SM_SCALE = 2       /* softmax scale of MG_EPI_SOFTMAX2 / _XATTN2 */
+};
+enum mg_igemm_p {
+  MG_IGEMM_P_A = 0,             /* bf16 [B][H][W][lda >= C0] */
+  MG_IGEMM_P_WT = 1,            /* bf16 [N][ldw >= taps * Cin], k = (ky*3+kx)*Cin + c */
+  MG_IGEMM_P_OUT = 2,
+  MG_IGEMM_P_BIAS = 3,          /* f32 [N] | NULL */
+  MG_IGEMM_P_ROWVEC = 4,        /* f32 [B][N] | NULL (time-embedding add) */
+  MG_IGEMM_P_RESIDUAL = 5,      /* bf16 [M][ldr] | NULL */
+  MG_IGEMM_P_OUT2 = 6,          /* the transposed section (MG_EPI_XATTN2: W2 bf16 [c2][64]) */
+  MG_IGEMM_P_A1 = 7,            /* bf16 [B][H][W][lda1] | NULL: second channel source */
+  MG_IGEMM_P_LN_OUT = 8,        /* f32 [M][N/32 + 1][2] | NULL: row statistics of the output (MG_EPI_XATTN2: f32 [M][2]) */
+  MG_IGEMM_P_LN_IN = 9,         /* f32 [M][2] (mean, rstd) | NULL: LayerNorm folded into this layer */
+  MG_IGEMM_P_LN_G = 10,         /* f32 [N] */
+  MG_IGEMM_P_LN_C = 11,         /* f32 [N] */
+  MG_IGEMM_P_X0 = 12,           /* bf16 [B][H][W][ldx0] | NULL: folded shortcut's input */
+  MG_IGEMM_P_X1 = 13,           /* bf16 [B][H][W][ldx1] | NULL: its second source */
+  MG_IGEMM_P_SPLITK_WS = 14     /* split-K workspace of the caller (64 MiB, 16-byte aligned) | NULL = the library's own, which programs on ONE
+                                   stream may share (stream-ordered reuse); programs that run concurrently on several streams each bring their own */
+};
+enum mg_igemm_l { MG_IGEMM_L_SA = 0, MG_IGEMM_L_SW = 1, MG_IGEMM_L_SO = 2, MG_IGEMM_L_SR = 3 };   /* z-strides (elements) of A, Wt, out, residual */
+
+enum mg_conv3x3_i {
+  MG_CONV3X3_I_B = 0,
+  MG_CONV3X3_I_H = 1,
+  MG_CONV3X3_I_W = 2,
+  MG_CONV3X3_I_C0 = 3,            /* channels of A0 (% 64 == 0) */
+  MG_CONV3X3_I_C1 = 4,            /* channels of A1 (0 without) */
+  MG_CONV3X3_I_N = 5,             /* output channels */
+  MG_CONV3X3_I_SUBPIX = 6,        /* sub-pixel 2x mode */
+  MG_CONV3X3_I_SILU = 7,          /* SiLU after the fused scale / shift */
+  MG_CONV3X3_I_LDA0 = 8,          /* row strides, 0 = dense: C0, */
+  MG_CONV3X3_I_LDA1 = 9,          /* C1, */
+  MG_CONV3X3_I_LDO = 10,          /* N, */
+  MG_CONV3X3_I_LDR = 11,          /* N, */
+  MG_CONV3X3_I_LDW = 12,          /* 9 * Cin (sub-pixel: 4 * Cin) */
+  MG_CONV3X3_I_ROWVEC_BCAST = 13, /* 1 = rowvec is a single [N] row shared by every image */
+  MG_CONV3X3_I_VARIANT = 14,      /* tile variant (0 = automatic) */
+  MG_CONV3X3_I_GN_CPG = 15,       /* channels per group of the output statistics (4 | 8 | 16 | 32) */
+  MG_CONV3X3_I_GN_SLOTS = 16      /* slots per image of their table = mg_conv3x3_gn_slots(op) */
+};
+enum mg_conv3x3_p {
+  MG_CONV3X3_P_A0 = 0,            /* bf16 [B][H][W][lda0 >= C0] */
+  MG_CONV3X3_P_WT = 1,            /* bf16 [N][ldw >= 9 * Cin] */
+  MG_CONV3X3_P_OUT = 2,           /* bf16 [B][H][W][ldo] (sub-pixel: [B][2H][2W][ldo]) */
+  MG_CONV3X3_P_BIAS = 3,          /* f32 [N] | NULL */
+  MG_CONV3X3_P_ROWVEC = 4,        /* f32 [B][N] | NULL */
+  MG_CONV3X3_P_RESIDUAL = 5,      /* bf16 (out's shape, row stride ldr) | NULL */
+  MG_CONV3X3_P_A1 = 6,            /* bf16 [B][H][W][lda1 >= C1] | NULL (second channel source) */
+  MG_CONV3X3_P_SS = 7,            /* scale_shift f32 [B][2][Cin] | NULL: input = silu?(x * scale + shift) for in-image pixels
+                                     (MG_OP_GN_FINALIZE's output; zero padding stays zero) */
+  MG_CONV3X3_P_GN_PART = 8        /* (optional) the output's GroupNorm partial sums, see the op */
+};
+enum mg_conv3x3_l { MG_CONV3X3_L_SW = 0 };   /* parity stride of Wt in elements (sub-pixel mode) */
+
+enum mg_rowgemm_i {
+  MG_ROWGEMM_I_M = 0,
+  MG_ROWGEMM_I_K = 1,
+  MG_ROWGEMM_I_N = 2,
+  MG_ROWGEMM_I_LDX = 3,           /* row strides, 0 = dense: K, */
+  MG_ROWGEMM_I_LDO = 4,           /* N (GEGLU: N / 2; form 3: K), */
+  MG_ROWGEMM_I_LDR = 5,           /* N */
+  MG_ROWGEMM_I_FORM = 6,          /* 0 plain, 1 GEGLU, 2 QKV, 3 collapsed cross-attention - see the op */
+  MG_ROWGEMM_I_TOKENS = 7,        /* tokens per image (forms with P_VT / P_GN_SS; % 32 == 0) */
+  MG_ROWGEMM_I_LDT = 8,           /* row stride of V^T */
+  MG_ROWGEMM_I_TRANS_FROM = 9,    /* first V column (% 64 == 0) */
+  MG_ROWGEMM_I_WAVES = 10,        /* waves per workgroup (0 = 12; 4 / 8 / 12; K = 640: 0 | 8) */
+  MG_ROWGEMM_I_SM_COLS = 11,      /* 2 x heads live score columns (form 3, P_XATTN) */
+  MG_ROWGEMM_I_NSPLIT = 12        /* column split (0 / 1 = none; n: the N / 64 stages are shared out over n workgroups per row block - few
+                                     rows, many columns; not with P_LN_OUT) */
+};
+enum mg_rowgemm_f {
+  MG_ROWGEMM_F_LN_EPS = 0,        /* LayerNorm eps of P_LN_OUT */
+  MG_ROWGEMM_F_SM_SCALE = 1       /* softmax scale (form 3, P_XATTN) */
+};
+enum mg_rowgemm_p {
+  MG_ROWGEMM_P_X = 0,             /* bf16 [M][ldx] */
+  MG_ROWGEMM_P_WP = 1,            /* packed weights */
+  MG_ROWGEMM_P_OUT = 2,           /* bf16 [M][ldo] */
+  MG_ROWGEMM_P_RESIDUAL = 3,      /* bf16 [M][ldr] | NULL (may alias out) */
+  MG_ROWGEMM_P_LN_IN = 4,         /* (mean, rstd) f32 [M][2] of the rows of x | NULL: LayerNorm folded (the packed trailer holds its g and c vectors) */
+  MG_ROWGEMM_P_LN_OUT = 5,        /* (mean, rstd) f32 [M][2] of the OUTPUT rows | NULL */
+  MG_ROWGEMM_P_VT = 6,            /* V^T bf16 [B][N - trans_from][ldt] (QKV form) */
+  MG_ROWGEMM_P_GN_SS = 7,         /* GroupNorm scale/shift f32 [B][2][K] | NULL: x is normalised while it is loaded (bf16(x * scale + shift)) */
+  MG_ROWGEMM_P_DBG = 8,           /* (tuning only) per-wave phase cycle stamps | NULL */
+  MG_ROWGEMM_P_XATTN = 9,         /* a weights.pack_rowgemm_xattn image | NULL: the cross-attention prologue of the GEGLU form */
+  MG_ROWGEMM_P_XOUT = 10          /* bf16 [M][ldx]: where the prologue writes the updated rows */
+};
+
+enum mg_flash64_i {
+  MG_FLASH64_I_B = 0,
+  MG_FLASH64_I_HEADS = 1,
+  MG_FLASH64_I_NTOK = 2,
+  MG_FLASH64_I_LDQ = 3,           /* row stride of Q and K */
+  MG_FLASH64_I_LDO = 4,
+  MG_FLASH64_I_LDVT = 5,
+  MG_FLASH64_I_VARIANT = 6,       /* 0 = automatic; 19 / 20 / 21 / 25 force a form of the compiled kernel, 26 / 27 the hand-placed stream */
+  MG_FLASH64_I_VT_PERM = 7,       /* 1 = Vt's keys are in the order [0-3, 8-11, 4-7, 12-15] inside every group of 16 (as written by
+                                     MG_IGEMM_I_TRANS_PERM; Ntok % 16 == 0) */
+  MG_FLASH64_I_WS_KB = 8,         /* size of P_WS in KB */
+  MG_FLASH64_I_SPLIT = 9          /* key split of the left-over blocks: 0 = when it pays, 1 = always, 2 = never */
+};
+enum mg_flash64_f {
+  MG_FLASH64_F_SCALE = 0,         /* softmax scale */
+  MG_FLASH64_F_REDO_THR = 1       /* row-sum bound of the running-maximum fallback (0 = 2^100; tests force the fallback with a tiny value) */
+};
+enum mg_flash64_p {
+  MG_FLASH64_P_Q = 0,             /* bf16 (row stride ldq) */
+  MG_FLASH64_P_K = 1,             /* bf16 (row stride ldq) */
+  MG_FLASH64_P_VT = 2,            /* bf16 [B][heads*64][ldvt] */
+  MG_FLASH64_P_O = 3,             /* bf16 (row stride ldo) */
+  MG_FLASH64_P_DBG = 4,           /* tuning only: cycle stamps | NULL */
+  MG_FLASH64_P_WS = 5             /* workspace | NULL (16-byte aligned, ZEROED once by the caller, then owned by this op's launches on ONE stream -
+                                     tickets return to zero); 4 KB + 69 632 bytes x 4 x (blocks % CUs) suffice */
+};
+enum mg_flash64_l { MG_FLASH64_L_SQ = 0, MG_FLASH64_L_SK = 1, MG_FLASH64_L_SVT = 2, MG_FLASH64_L_SO = 3 };   /* batch strides of Q, K, Vt, O */
 
 typedef struct mg_program mg_program;
 
@@ -383,13 +505,13 @@ int mg_ensemble_depth(const float* preds, int E, int H, int W, int scale_invaria
 /* Named wrappers - what a binding for the reference's seams would call directly. */
 int mg_conv2d_igemm(const mg_op* conv_desc, void* stream);   /* kind must be MG_OP_IGEMM */
 /* Host-only test hook (no device work): how MG_OP_FLASH_ATTN64's hand-placed kernel would share out B x heads sequences of Ntok
- * tokens over a chip of n_cu CUs given a workspace of ws_bytes and the split mode (op i[9]): out[0] whole blocks of 256 queries,
+ * tokens over a chip of n_cu CUs given a workspace of ws_bytes and the split mode (MG_FLASH64_I_SPLIT): out[0] whole blocks of 256 queries,
  * out[1] blocks split along the keys, out[2] workgroups over the split blocks; bounds[0 .. out[2]] (or NULL): the workgroups'
  * piece boundaries in 64-key tiles over the concatenated split blocks. */
 int mg_flash4w_plan_test(int B, int heads, int Ntok, int n_cu, long long ws_bytes, int split, int* out, unsigned* bounds);
 int mg_conv3x3(const mg_op* conv_desc, void* stream);        /* kind must be MG_OP_CONV3X3 (ResnetBlock2D norm+silu+conv) */
-/* Slots per image of the partial table this MG_OP_CONV3X3 can fill with the GroupNorm statistics of its OUTPUT (p[8], see the
- * op), or 0 when the tile variant it runs on does not produce them (then leave p[8] NULL and use MG_OP_GN_STATS). */
+/* Slots per image of the partial table this MG_OP_CONV3X3 can fill with the GroupNorm statistics of its OUTPUT (MG_CONV3X3_P_GN_PART, see the
+ * op), or 0 when the tile variant it runs on does not produce them (then leave it NULL and use MG_OP_GN_STATS). */
 int mg_conv3x3_gn_slots(const mg_op* conv_desc);
 int mg_sched_step(const float* x, const float* model_out, const float* noise, float* out,
                   int64_t n, float cx, float cm, float cn, void* stream);

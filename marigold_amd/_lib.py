@@ -55,6 +55,33 @@ def iid_gamma_mode(gamma):
 EPI_BF16, EPI_GEGLU, EPI_F32, EPI_SOFTMAX2, EPI_XATTN2 = 0, 1, 2, 3, 4
 POST_NONE, POST_DEPTH, POST_NORMALS, POST_UNIT, POST_SCHED = 0, 1, 2, 3, 4
 
+# Field names of the four kinds with many launch forms: kind -> (enumerator prefix, {array: names in slot order}) - the mirror of
+# the MG_<KIND>_<I|F|P|L>_<NAME> enumerators of include/marigold_hip.h (lower case here; the position is the slot).
+# tests/test_host.py compares the two; ops.py builds and decodes these kinds by these names.
+FIELDS = {
+    OP_IGEMM: ("IGEMM", dict(
+        i=("b", "h", "w", "cin", "ho", "wo", "n", "taps", "stride", "pad", "hu", "wu", "epi", "ldo", "trans_from", "batch_z", "ldr",
+           "lda", "ldt", "variant", "ldw", "rowvec_bcast", "n_alg", "k_alg", "c0", "lda1", "trans_perm", "sm_cols", "c2",
+           "tickets_lo", "tickets_hi", "splits", "cx", "cx0", "ldx0", "ldx1"),
+        f=("scale", "ln_eps", "sm_scale"),
+        p=("a", "wt", "out", "bias", "rowvec", "residual", "out2", "a1", "ln_out", "ln_in", "ln_g", "ln_c", "x0", "x1", "splitk_ws"),
+        l=("sa", "sw", "so", "sr"))),
+    OP_CONV3X3: ("CONV3X3", dict(
+        i=("b", "h", "w", "c0", "c1", "n", "subpix", "silu", "lda0", "lda1", "ldo", "ldr", "ldw", "rowvec_bcast", "variant", "gn_cpg",
+           "gn_slots"),
+        p=("a0", "wt", "out", "bias", "rowvec", "residual", "a1", "ss", "gn_part"),
+        l=("sw",))),
+    OP_ROWGEMM: ("ROWGEMM", dict(
+        i=("m", "k", "n", "ldx", "ldo", "ldr", "form", "tokens", "ldt", "trans_from", "waves", "sm_cols", "nsplit"),
+        f=("ln_eps", "sm_scale"),
+        p=("x", "wp", "out", "residual", "ln_in", "ln_out", "vt", "gn_ss", "dbg", "xattn", "xout"))),
+    OP_FLASH_ATTN64: ("FLASH64", dict(
+        i=("b", "heads", "ntok", "ldq", "ldo", "ldvt", "variant", "vt_perm", "ws_kb", "split"),
+        f=("scale", "redo_thr"),
+        p=("q", "k", "vt", "o", "dbg", "ws"),
+        l=("sq", "sk", "svt", "so"))),
+}
+
 OP_NAMES = {v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}
 
 EXPORTS = [

@@ -102,35 +102,35 @@ int mg_launch_attention(const mg_op* op, hipStream_t s) {
   switch (op->kind) {
     case MG_OP_FLASH_ATTN64: {
       FaArgs a;
-      a.Q = (const bf16_t*)op->p[0];
-      a.K = (const bf16_t*)op->p[1];
-      a.Vt = (const bf16_t*)op->p[2];
-      a.O = (bf16_t*)op->p[3];
+      a.Q = (const bf16_t*)op->p[MG_FLASH64_P_Q];
+      a.K = (const bf16_t*)op->p[MG_FLASH64_P_K];
+      a.Vt = (const bf16_t*)op->p[MG_FLASH64_P_VT];
+      a.O = (bf16_t*)op->p[MG_FLASH64_P_O];
       a.zero = g_zero_page;
-      a.B = op->i[0]; a.heads = op->i[1]; a.Ntok = op->i[2];
-      a.ldq = op->i[3]; a.ldo = op->i[4]; a.ldvt = op->i[5];
-      a.sQ = op->l[0]; a.sK = op->l[1]; a.sVt = op->l[2]; a.sO = op->l[3];
-      a.scale_log2 = op->f[0] * 1.4426950408889634f;
-      a.dbg = (unsigned long long*)op->p[4];
-      a.redo_thr = op->f[1] > 0.f ? op->f[1] : (MG_F16 ? 32768.0f : 1.2676506e30f);   // 2^100 (tests force the fallback with a tiny value)
-      a.ws = op->p[5];                                            // variant 26: workspace of the key-split blocks (i[8] KB)
-      a.ws_bytes = (long long)op->i[8] * 1024;
-      a.split = op->i[9];
+      a.B = op->i[MG_FLASH64_I_B]; a.heads = op->i[MG_FLASH64_I_HEADS]; a.Ntok = op->i[MG_FLASH64_I_NTOK];
+      a.ldq = op->i[MG_FLASH64_I_LDQ]; a.ldo = op->i[MG_FLASH64_I_LDO]; a.ldvt = op->i[MG_FLASH64_I_LDVT];
+      a.sQ = op->l[MG_FLASH64_L_SQ]; a.sK = op->l[MG_FLASH64_L_SK]; a.sVt = op->l[MG_FLASH64_L_SVT]; a.sO = op->l[MG_FLASH64_L_SO];
+      a.scale_log2 = op->f[MG_FLASH64_F_SCALE] * 1.4426950408889634f;
+      a.dbg = (unsigned long long*)op->p[MG_FLASH64_P_DBG];
+      a.redo_thr = op->f[MG_FLASH64_F_REDO_THR] > 0.f ? op->f[MG_FLASH64_F_REDO_THR] : (MG_F16 ? 32768.0f : 1.2676506e30f);   // 2^100 (tests force the fallback with a tiny value)
+      a.ws = op->p[MG_FLASH64_P_WS];                                            // variant 26: workspace of the key-split blocks (I_WS_KB)
+      a.ws_bytes = (long long)op->i[MG_FLASH64_I_WS_KB] * 1024;
+      a.split = op->i[MG_FLASH64_I_SPLIT];
       a.n_full = a.n_rem = a.n_rem_wg = 0;
       a.m16 = 0;
-      MG_REQUIRE(!a.ws || ((uintptr_t)a.ws % 16 == 0 && a.ws_bytes > 0), "flash_attn64: workspace must be 16-byte aligned, its size (KB) in i[8]");
+      MG_REQUIRE(!a.ws || ((uintptr_t)a.ws % 16 == 0 && a.ws_bytes > 0), "flash_attn64: workspace must be 16-byte aligned, its size (KB) in I_WS_KB");
       a.nqb = (a.Ntok + FA_QB - 1) / FA_QB;
       MG_REQUIRE(g_zero_page || g_dry_run, "flash_attn64: mg_init() not called");
       MG_REQUIRE(a.Q && a.K && a.Vt && a.O, "flash_attn64: null pointer");
       MG_REQUIRE(a.B > 0 && a.heads > 0 && a.Ntok > 0, "flash_attn64: empty problem");
       MG_REQUIRE(a.ldvt % 64 == 0 && a.ldvt >= a.Ntok, "flash_attn64: ldvt must be a multiple of 64 >= Ntok");
       MG_REQUIRE(a.ldq % 8 == 0 && a.ldo % 4 == 0, "flash_attn64: bad leading dims");
-      // i[6]: 0 = automatic; 19 / 20 / 21 / 25 force a form of the compiled kernel (generation 2.5: 4 / 8 waves with the permuted
+      // I_VARIANT: 0 = automatic; 19 / 20 / 21 / 25 force a form of the compiled kernel (generation 2.5: 4 / 8 waves with the permuted
       // V^T, 4 waves with the natural one, 4 waves + plain v_add_f32 row sums), 26 the hand-placed stream - tests and sweeps
       MG_REQUIRE((a.ldo % 8 == 0) && ((uintptr_t)a.O % 16 == 0) && (a.sO % 8 == 0), "flash_attn64: O needs 16-byte rows (ldo %% 8 == 0, aligned base / batch stride)");
-      const int var = op->i[6];
-      const bool vt_perm = op->i[7] != 0;   // V^T keys permuted inside every group of 16: [0-3, 8-11, 4-7, 12-15]
-      MG_REQUIRE(var == 0 || vt_perm == (var == 19 || var == 20 || var == 25 || var == 26 || var == 27), "flash_attn64: variant %d and the V^T key order (i[7] = %d) do not match", var, op->i[7]);
+      const int var = op->i[MG_FLASH64_I_VARIANT];
+      const bool vt_perm = op->i[MG_FLASH64_I_VT_PERM] != 0;   // V^T keys permuted inside every group of 16: [0-3, 8-11, 4-7, 12-15]
+      MG_REQUIRE(var == 0 || vt_perm == (var == 19 || var == 20 || var == 25 || var == 26 || var == 27), "flash_attn64: variant %d and the V^T key order (I_VT_PERM = %d) do not match", var, op->i[MG_FLASH64_I_VT_PERM]);
       MG_REQUIRE(!vt_perm || a.Ntok % 16 == 0, "flash_attn64: the permuted V^T layout needs Ntok %% 16 == 0");
       const long long g4 = (long long)((a.Ntok + 127) / 128) * a.heads * a.B;
       const long long g8 = (long long)((a.Ntok + 255) / 256) * a.heads * a.B;

@@ -499,23 +499,68 @@ int mg_conv3x3_auto_variant(int N, int subpix, int B, int H, int W, int has_ss, 
   return 4;
 }
 
-// the tile variant MG_OP_CONV3X3 `op` runs on (i[14], or the automatic choice)
-static int mg_conv3x3_variant_of(const mg_op* op) {
-  const int C0 = op->i[3], C1 = op->i[4], N = op->i[5], subpix = op->i[6], silu = op->i[7];
-  const int lda0 = op->i[8] > 0 ? op->i[8] : C0, lda1 = op->i[9] > 0 ? op->i[9] : C1;
-  const bool ss = op->p[7] != nullptr;
+// MG_OP_CONV3X3 decoded once - the kernels' argument block (tile counts left to launch_patch) and what only the host needs;
+// the tile choice, mg_conv3x3_gn_slots and the launcher all read this (marigold_amd/ops.py::conv3x3_view restates the defaults)
+struct Conv3x3Op {
+  ConvPArgs a;
+  int C1;       // channels of the second source
+  int forced;   // MG_CONV3X3_I_VARIANT (0 = the automatic choice)
+};
+
+static Conv3x3Op conv3x3_decode(const mg_op* op) {
+  Conv3x3Op d;
+  ConvPArgs& a = d.a;
+  a.A0 = (const bf16_t*)op->p[MG_CONV3X3_P_A0];
+  a.Wt = (const bf16_t*)op->p[MG_CONV3X3_P_WT];
+  a.out = (bf16_t*)op->p[MG_CONV3X3_P_OUT];
+  a.bias = (const float*)op->p[MG_CONV3X3_P_BIAS];
+  a.rowvec = (const float*)op->p[MG_CONV3X3_P_ROWVEC];
+  a.res = (const bf16_t*)op->p[MG_CONV3X3_P_RESIDUAL];
+  a.A1 = (const bf16_t*)op->p[MG_CONV3X3_P_A1];
+  a.ss = (const float*)op->p[MG_CONV3X3_P_SS];
+  a.gn_part = (float*)op->p[MG_CONV3X3_P_GN_PART];
+  a.gn_cpg = op->i[MG_CONV3X3_I_GN_CPG];
+  a.gn_slots = op->i[MG_CONV3X3_I_GN_SLOTS];
+  a.zero = g_zero_page;
+  a.B = op->i[MG_CONV3X3_I_B]; a.H = op->i[MG_CONV3X3_I_H]; a.W = op->i[MG_CONV3X3_I_W]; a.C0 = op->i[MG_CONV3X3_I_C0];
+  d.C1 = op->i[MG_CONV3X3_I_C1];
+  a.Cin = a.C0 + d.C1;
+  a.N = op->i[MG_CONV3X3_I_N];
+  a.subpix = op->i[MG_CONV3X3_I_SUBPIX];
+  a.silu = op->i[MG_CONV3X3_I_SILU];
+  a.lda0 = op->i[MG_CONV3X3_I_LDA0] > 0 ? op->i[MG_CONV3X3_I_LDA0] : a.C0;
+  a.lda1 = op->i[MG_CONV3X3_I_LDA1] > 0 ? op->i[MG_CONV3X3_I_LDA1] : d.C1;
+  a.ldo = op->i[MG_CONV3X3_I_LDO] > 0 ? op->i[MG_CONV3X3_I_LDO] : a.N;
+  a.ldr = op->i[MG_CONV3X3_I_LDR] > 0 ? op->i[MG_CONV3X3_I_LDR] : a.N;
+  a.T = a.subpix ? 4 : 9;
+  a.tw = a.subpix ? 2 : 3;
+  a.ldw = op->i[MG_CONV3X3_I_LDW] > 0 ? op->i[MG_CONV3X3_I_LDW] : a.T * a.Cin;
+  a.rv_stride = op->i[MG_CONV3X3_I_ROWVEC_BCAST] ? 0 : a.N;
+  d.forced = op->i[MG_CONV3X3_I_VARIANT];
+  a.sW = op->l[MG_CONV3X3_L_SW];
+  a.chunks = a.Cin / 64;
+  a.c0t = a.C0 / 64;
+  a.tiles_x = a.tiles_y = a.tiles_n = 0;
+  return d;
+}
+
+// the tile variant the op runs on (the forced one, or the automatic choice)
+static int conv3x3_variant(const Conv3x3Op& d) {
+  const ConvPArgs& a = d.a;
+  const bool ss = a.ss != nullptr;
   // (the four-wave kernels: SiLU with the fused norm, 31-bit byte offsets into the operands)
-  const int allow4w = (!ss || silu) && (long long)op->i[0] * op->i[1] * op->i[2] * (lda0 > lda1 ? lda0 : lda1) < (1ll << 30) &&
-                      (long long)N * (op->i[12] > 0 ? op->i[12] : (subpix ? 4 : 9) * (C0 + C1)) < (1ll << 30);
-  int variant = op->i[14] ? op->i[14] : mg_conv3x3_auto_variant(N, subpix, op->i[0], op->i[1], op->i[2], ss, C0 + C1, allow4w);
-  if (!op->i[14] && variant == 6 && ss && C0 + C1 > 1024) variant = 3;   // (variant 6 keeps the fused norm's [2][Cin] vectors in 8 KB of LDS)
+  const int allow4w = (!ss || a.silu) && (long long)a.B * a.H * a.W * (a.lda0 > a.lda1 ? a.lda0 : a.lda1) < (1ll << 30) &&
+                      (long long)a.N * a.ldw < (1ll << 30);
+  int variant = d.forced ? d.forced : mg_conv3x3_auto_variant(a.N, a.subpix, a.B, a.H, a.W, ss, a.Cin, allow4w);
+  if (!d.forced && variant == 6 && ss && a.Cin > 1024) variant = 3;   // (variant 6 keeps the fused norm's [2][Cin] vectors in 8 KB of LDS)
   return variant;
 }
 
-// Table slots per image of the output-statistics by-product (p[8]) for this op - 0: its tile variant does not produce them.
+// Table slots per image of the output-statistics by-product (MG_CONV3X3_P_GN_PART) for this op - 0: its tile variant does not produce them.
 int mg_conv3x3_gn_slots_of(const mg_op* op) {
-  const int variant = mg_conv3x3_variant_of(op);
-  const int H = op->i[1], W = op->i[2], N = op->i[5], par = op->i[6] ? 4 : 1;
+  const Conv3x3Op d = conv3x3_decode(op);
+  const int variant = conv3x3_variant(d);
+  const int H = d.a.H, W = d.a.W, N = d.a.N, par = d.a.subpix ? 4 : 1;
   if (variant == 1 && N % 256 == 0) return ((H + 15) / 16) * ((W + 15) / 16) * par;
   if (variant == 8 && N % 128 == 0) return ((H + 23) / 24) * ((W + 15) / 16) * par;
   if (variant == 9 && N % 256 == 0) return ((H + 11) / 12) * ((W + 15) / 16) * par;
@@ -523,38 +568,10 @@ int mg_conv3x3_gn_slots_of(const mg_op* op) {
 }
 
 int mg_launch_conv_patch(const mg_op* op, hipStream_t s) {
-  ConvPArgs a;
-  a.A0 = (const bf16_t*)op->p[0];
-  a.Wt = (const bf16_t*)op->p[1];
-  a.out = (bf16_t*)op->p[2];
-  a.bias = (const float*)op->p[3];
-  a.rowvec = (const float*)op->p[4];
-  a.res = (const bf16_t*)op->p[5];
-  a.A1 = (const bf16_t*)op->p[6];
-  a.ss = (const float*)op->p[7];
-  a.gn_part = (float*)op->p[8];
-  a.gn_cpg = op->i[15];
-  a.gn_slots = op->i[16];
-  a.zero = g_zero_page;
-  a.B = op->i[0]; a.H = op->i[1]; a.W = op->i[2]; a.C0 = op->i[3];
-  const int C1 = op->i[4];
-  a.Cin = a.C0 + C1;
-  a.N = op->i[5];
-  a.subpix = op->i[6];
-  a.silu = op->i[7];
-  a.lda0 = op->i[8] > 0 ? op->i[8] : a.C0;
-  a.lda1 = op->i[9] > 0 ? op->i[9] : C1;
-  a.ldo = op->i[10] > 0 ? op->i[10] : a.N;
-  a.ldr = op->i[11] > 0 ? op->i[11] : a.N;
-  a.T = a.subpix ? 4 : 9;
-  a.tw = a.subpix ? 2 : 3;
-  a.ldw = op->i[12] > 0 ? op->i[12] : a.T * a.Cin;
-  a.rv_stride = op->i[13] ? 0 : a.N;
-  const int variant = mg_conv3x3_variant_of(op);
-  a.sW = op->l[0];
-  a.chunks = a.Cin / 64;
-  a.c0t = a.C0 / 64;
-  a.tiles_x = a.tiles_y = a.tiles_n = 0;
+  const Conv3x3Op d = conv3x3_decode(op);
+  const ConvPArgs& a = d.a;
+  const int C1 = d.C1;
+  const int variant = conv3x3_variant(d);
   MG_REQUIRE(g_zero_page || g_dry_run, "conv3x3: mg_init() not called");
   MG_REQUIRE(a.A0 && a.Wt && a.out, "conv3x3: null pointer");
   MG_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0, "conv3x3: empty problem");

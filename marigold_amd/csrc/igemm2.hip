@@ -112,7 +112,7 @@ int launch2(const Igemm2Args& a, int batch_z, hipStream_t s) {
   b.ws = nullptr;
   const long long tiles = (long long)b.tiles_m * b.tiles_n;
   // a.splits: -1 = never (forced tile / epilogues the reduce launch cannot finish), 0 = the automatic rule, n >= 1 = exactly n
-  // (op i[31]: the tuning sweeps and the per-batch rules of mg_igemm_auto_split)
+  // (MG_IGEMM_I_SPLITS: the tuning sweeps and the per-batch rules of mg_igemm_auto_split)
   const bool sk_ok = !TRANS && a.splits >= 0 && batch_z == 1 && a.epi == MG_EPI_BF16 && a.n_begin == 0 && a.n_end == a.N && (a.ws || g_splitk_ws);
   if (sk_ok && (a.splits > 1 || (a.splits == 0 && tiles < 160 && b.KT >= 32))) {   // (a wider window, < 256 tiles, measured no gain at E = 10)
     int sp;
@@ -136,7 +136,7 @@ int launch2(const Igemm2Args& a, int batch_z, hipStream_t s) {
     if (sp > 1) {
       b.kps = (b.KT + sp - 1) / sp;
       b.splits = (b.KT + b.kps - 1) / b.kps;
-      b.ws = a.ws ? a.ws : (float*)g_splitk_ws;   // op p[14]: the program's own workspace (programs on concurrent streams)
+      b.ws = a.ws ? a.ws : (float*)g_splitk_ws;   // MG_IGEMM_P_SPLITK_WS: the program's own workspace (programs on concurrent streams)
     }
   }
   const long long grid = tiles * b.splits * batch_z;
@@ -199,31 +199,31 @@ int mg_igemm_auto_variant(long long M, int N, int K, int batch_z, int geglu);
 // returns -1 when the shape is outside the kernel's contract (mg_launch_igemm turns that into an error)
 int mg_launch_igemm2(const mg_op* op, hipStream_t s, int variant) {
   Igemm2Args a;
-  a.A = (const bf16_t*)op->p[0];
-  a.Wt = (const bf16_t*)op->p[1];
-  a.out = op->p[2];
-  a.bias = (const float*)op->p[3];
-  a.rowvec = (const float*)op->p[4];
-  a.res = (const bf16_t*)op->p[5];
-  void* out2 = op->p[6];
+  a.A = (const bf16_t*)op->p[MG_IGEMM_P_A];
+  a.Wt = (const bf16_t*)op->p[MG_IGEMM_P_WT];
+  a.out = op->p[MG_IGEMM_P_OUT];
+  a.bias = (const float*)op->p[MG_IGEMM_P_BIAS];
+  a.rowvec = (const float*)op->p[MG_IGEMM_P_ROWVEC];
+  a.res = (const bf16_t*)op->p[MG_IGEMM_P_RESIDUAL];
+  void* out2 = op->p[MG_IGEMM_P_OUT2];
   a.zero = g_zero_page;
-  const int B = op->i[0];
-  a.H = op->i[1]; a.W = op->i[2]; a.Cin = op->i[3]; a.Ho = op->i[4]; a.Wo = op->i[5];
-  a.N = op->i[6]; a.taps = op->i[7]; a.stride = op->i[8]; a.pad = op->i[9];
-  a.Hu = op->i[10]; a.Wu = op->i[11]; a.epi = op->i[12]; a.ldo = op->i[13];
-  const int trans_from = op->i[14];
-  const int batch_z = op->i[15] > 0 ? op->i[15] : 1;
-  a.ldr = op->i[16] > 0 ? op->i[16] : a.N;
-  a.A1 = (const bf16_t*)op->p[7];
-  a.C0 = a.A1 ? op->i[24] : a.Cin;
-  a.lda1 = a.A1 ? (op->i[25] > 0 ? op->i[25] : a.Cin - a.C0) : 0;
+  const int B = op->i[MG_IGEMM_I_B];
+  a.H = op->i[MG_IGEMM_I_H]; a.W = op->i[MG_IGEMM_I_W]; a.Cin = op->i[MG_IGEMM_I_CIN]; a.Ho = op->i[MG_IGEMM_I_HO]; a.Wo = op->i[MG_IGEMM_I_WO];
+  a.N = op->i[MG_IGEMM_I_N]; a.taps = op->i[MG_IGEMM_I_TAPS]; a.stride = op->i[MG_IGEMM_I_STRIDE]; a.pad = op->i[MG_IGEMM_I_PAD];
+  a.Hu = op->i[MG_IGEMM_I_HU]; a.Wu = op->i[MG_IGEMM_I_WU]; a.epi = op->i[MG_IGEMM_I_EPI]; a.ldo = op->i[MG_IGEMM_I_LDO];
+  const int trans_from = op->i[MG_IGEMM_I_TRANS_FROM];
+  const int batch_z = op->i[MG_IGEMM_I_BATCH_Z] > 0 ? op->i[MG_IGEMM_I_BATCH_Z] : 1;
+  a.ldr = op->i[MG_IGEMM_I_LDR] > 0 ? op->i[MG_IGEMM_I_LDR] : a.N;
+  a.A1 = (const bf16_t*)op->p[MG_IGEMM_P_A1];
+  a.C0 = a.A1 ? op->i[MG_IGEMM_I_C0] : a.Cin;
+  a.lda1 = a.A1 ? (op->i[MG_IGEMM_I_LDA1] > 0 ? op->i[MG_IGEMM_I_LDA1] : a.Cin - a.C0) : 0;
   a.c0t = 0;
-  a.lda = op->i[17] > 0 ? op->i[17] : a.C0;
-  a.ldt = op->i[18];
-  a.ldw = op->i[20] > 0 ? op->i[20] : a.taps * a.Cin + (op->p[12] ? op->i[32] : 0);
-  a.rv_stride = op->i[21] ? 0 : a.N;
-  a.sA = op->l[0]; a.sW = op->l[1]; a.sO = op->l[2]; a.sR = op->l[3];
-  a.scale = op->f[0] == 0.f ? 1.f : op->f[0];
+  a.lda = op->i[MG_IGEMM_I_LDA] > 0 ? op->i[MG_IGEMM_I_LDA] : a.C0;
+  a.ldt = op->i[MG_IGEMM_I_LDT];
+  a.ldw = op->i[MG_IGEMM_I_LDW] > 0 ? op->i[MG_IGEMM_I_LDW] : a.taps * a.Cin + (op->p[MG_IGEMM_P_X0] ? op->i[MG_IGEMM_I_CX] : 0);
+  a.rv_stride = op->i[MG_IGEMM_I_ROWVEC_BCAST] ? 0 : a.N;
+  a.sA = op->l[MG_IGEMM_L_SA]; a.sW = op->l[MG_IGEMM_L_SW]; a.sO = op->l[MG_IGEMM_L_SO]; a.sR = op->l[MG_IGEMM_L_SR];
+  a.scale = op->f[MG_IGEMM_F_SCALE] == 0.f ? 1.f : op->f[MG_IGEMM_F_SCALE];
   a.rows_per_img = a.Ho * a.Wo;
   a.M = B * a.rows_per_img;
   a.cpt = a.Cin / 64;
@@ -231,46 +231,46 @@ int mg_launch_igemm2(const mg_op* op, hipStream_t s, int variant) {
   a.up2 = (a.Hu == 2 * a.H) && (a.Wu == 2 * a.W);
   a.tw = a.taps == 9 ? 3 : (a.taps == 4 ? 2 : 1);
   a.subpix = a.taps == 4;
-  // split-K: i[31] = n >= 1 asks for exactly n K ranges per tile (1 = none); 0 = the automatic rule, which only applies under
-  // the automatic tile choice (a forced tile runs unsplit unless i[31] says otherwise)
-  a.splits = op->i[31] > 0 ? op->i[31] : (variant ? -1 : 0);
-  a.ln_out = (float2*)op->p[8];
-  a.ln_in = (const float2*)op->p[9];
-  a.ln_g = (const float*)op->p[10];
-  a.ln_c = (const float*)op->p[11];
-  a.ln_eps = op->f[1];
-  a.sm_scale = op->f[2];
-  a.sm_cols = op->i[27];
-  a.tperm = op->i[26];
+  // split-K: I_SPLITS = n >= 1 asks for exactly n K ranges per tile (1 = none); 0 = the automatic rule, which only applies under
+  // the automatic tile choice (a forced tile runs unsplit unless I_SPLITS says otherwise)
+  a.splits = op->i[MG_IGEMM_I_SPLITS] > 0 ? op->i[MG_IGEMM_I_SPLITS] : (variant ? -1 : 0);
+  a.ln_out = (float2*)op->p[MG_IGEMM_P_LN_OUT];
+  a.ln_in = (const float2*)op->p[MG_IGEMM_P_LN_IN];
+  a.ln_g = (const float*)op->p[MG_IGEMM_P_LN_G];
+  a.ln_c = (const float*)op->p[MG_IGEMM_P_LN_C];
+  a.ln_eps = op->f[MG_IGEMM_F_LN_EPS];
+  a.sm_scale = op->f[MG_IGEMM_F_SM_SCALE];
+  a.sm_cols = op->i[MG_IGEMM_I_SM_COLS];
+  a.tperm = op->i[MG_IGEMM_I_TRANS_PERM];
   a.w2 = nullptr;
-  a.X0 = (const bf16_t*)op->p[12];
-  a.X1 = (const bf16_t*)op->p[13];
-  a.xcin = a.X0 ? op->i[32] : 0;
-  a.xc0 = a.X1 ? op->i[33] : a.xcin;
-  a.ldx0 = op->i[34] > 0 ? op->i[34] : a.xc0;
-  a.ldx1 = a.X1 ? (op->i[35] > 0 ? op->i[35] : a.xcin - a.xc0) : 0;
+  a.X0 = (const bf16_t*)op->p[MG_IGEMM_P_X0];
+  a.X1 = (const bf16_t*)op->p[MG_IGEMM_P_X1];
+  a.xcin = a.X0 ? op->i[MG_IGEMM_I_CX] : 0;
+  a.xc0 = a.X1 ? op->i[MG_IGEMM_I_CX0] : a.xcin;
+  a.ldx0 = op->i[MG_IGEMM_I_LDX0] > 0 ? op->i[MG_IGEMM_I_LDX0] : a.xc0;
+  a.ldx1 = a.X1 ? (op->i[MG_IGEMM_I_LDX1] > 0 ? op->i[MG_IGEMM_I_LDX1] : a.xcin - a.xc0) : 0;
   a.xcpt = a.xc0t = 0;
   if (a.X0) {
     MG_REQUIRE(a.taps == 9 && a.stride == 1 && a.pad == 1 && a.Hu == 0 && batch_z == 1 && trans_from < 0 && a.epi == MG_EPI_BF16,
-               "igemm: a folded 1x1 convolution (p[12]) rides on a plain 3x3 / stride 1 / pad 1 convolution");
+               "igemm: a folded 1x1 convolution (P_X0) rides on a plain 3x3 / stride 1 / pad 1 convolution");
     MG_REQUIRE(a.xcin > 0 && a.xcin % 64 == 0 && a.xc0 > 0 && a.xc0 % 64 == 0 && a.xc0 <= a.xcin && (a.X1 != nullptr) == (a.xc0 < a.xcin) &&
                a.ldx0 % 8 == 0 && a.ldx1 % 8 == 0 && (uintptr_t)a.X0 % 16 == 0 && (uintptr_t)a.X1 % 16 == 0 && a.ldw >= a.taps * a.Cin + a.xcin,
                "igemm: bad folded source (Cx %d, Cx0 %d: multiples of 64; weight rows hold taps * Cin + Cx columns)", a.xcin, a.xc0);
   }
   {   // tuning only: phase stamps of every workgroup into the (otherwise idle) split-K workspace - tools/igemm_phases.py
     static const int st = mg_tuning_int("MARIGOLD_IGEMM_STAMPS", 0);
-    a.stamps = (st && op->i[31] <= 1 && (variant == 72 || variant == 73)) ? (unsigned long long*)g_splitk_ws : nullptr;
+    a.stamps = (st && op->i[MG_IGEMM_I_SPLITS] <= 1 && (variant == 72 || variant == 73)) ? (unsigned long long*)g_splitk_ws : nullptr;
   }
   a.c2 = 0;
   a.inv_c2 = 0.0;
   if (a.epi == MG_EPI_XATTN2) {
-    a.w2 = (const bf16_t*)op->p[6];
-    a.c2 = op->i[28];
+    a.w2 = (const bf16_t*)op->p[MG_IGEMM_P_OUT2];
+    a.c2 = op->i[MG_IGEMM_I_C2];
     out2 = nullptr;
     MG_REQUIRE(trans_from < 0 && batch_z == 1 && a.taps == 1 && a.N == 64 && a.sm_cols > 0 && a.sm_cols % 2 == 0 && a.sm_cols <= 64 &&
                a.w2 && (uintptr_t)a.w2 % 16 == 0 && a.c2 > 0 && a.c2 % 32 == 0 && a.ldo >= a.c2 && (long long)a.c2 * 4 + 64 <= MG_ZERO_BYTES &&
                (variant == 0 || variant == 54) && (!a.bias || (uintptr_t)a.bias % 16 == 0) && (!a.res || a.ldr >= a.c2),
-               "igemm: the fused cross-attention epilogue takes N = 64 score columns, second-stage weights [c2][64] (c2 %% 32 == 0) in p[6]");
+               "igemm: the fused cross-attention epilogue takes N = 64 score columns, second-stage weights [c2][64] (c2 %% 32 == 0) in P_OUT2");
     variant = 54;
     a.inv_c2 = 1.0 / (double)a.c2;
   }
@@ -293,18 +293,18 @@ int mg_launch_igemm2(const mg_op* op, hipStream_t s, int variant) {
     a.splits = -1;
   }
   a.kps = 0;
-  a.ws = (float*)op->p[14];   // the caller's split-K workspace (MG_SPLITK_WS_BYTES) | NULL = the library's (one stream only)
+  a.ws = (float*)op->p[MG_IGEMM_P_SPLITK_WS];   // the caller's split-K workspace (MG_SPLITK_WS_BYTES) | NULL = the library's (one stream only)
   a.ctr = 0;
   a.fd_rpi = mg_make_fastdiv(a.rows_per_img > 0 ? a.rows_per_img : 1);
   a.fd_wo = mg_make_fastdiv(a.Wo > 0 ? a.Wo : 1);
   a.fd_per_z = a.fd_tiles = a.fd_tiles_n = a.fd_cpt = mg_make_fastdiv(1);
   a.lin = a.taps == 1 && a.stride == 1 && a.pad == 0 && a.Hu == 0 && a.Ho == a.H && a.Wo == a.W;
   a.inv_n = 1.0 / (double)(a.N > 0 ? a.N : 1);
-  // row-block tickets of the ln_out hand-off: the caller's own buffer (i[29] / i[30] = low / high half of its device address;
+  // row-block tickets of the ln_out hand-off: the caller's own buffer (I_TICKETS_LO / _HI = low / high half of its device address;
   // MG_LN_COUNTERS zeroed uint32, one per program / stream - engine.py::Builder) or, absent, the library's global one, which
   // is only safe while every program that writes row statistics runs on ONE stream (the tickets are self-resetting and
   // stream-ordered, but two streams would draw from the same slots)
-  a.ln_ctr = (op->i[29] | op->i[30]) ? (unsigned*)(uintptr_t)((uint64_t)(uint32_t)op->i[29] | ((uint64_t)(uint32_t)op->i[30] << 32))
+  a.ln_ctr = (op->i[MG_IGEMM_I_TICKETS_LO] | op->i[MG_IGEMM_I_TICKETS_HI]) ? (unsigned*)(uintptr_t)((uint64_t)(uint32_t)op->i[MG_IGEMM_I_TICKETS_LO] | ((uint64_t)(uint32_t)op->i[MG_IGEMM_I_TICKETS_HI] << 32))
                                      : g_ln_counters;
   a.tiles_m = a.tiles_n = 0;
   MG_REQUIRE(g_zero_page || g_dry_run, "igemm: mg_init() not called");
@@ -437,8 +437,8 @@ int mg_igemm_auto_variant(long long M, int N, int K, int batch_z, int geglu) {
 }
 
 int mg_launch_igemm(const mg_op* op, hipStream_t s) {
-  const int rc = mg_launch_igemm2(op, s, op->i[19]);
+  const int rc = mg_launch_igemm2(op, s, op->i[MG_IGEMM_I_VARIANT]);
   MG_REQUIRE(rc >= 0, "igemm: unsupported shape (N %d, ldo %d, residual stride %d must be multiples of 8; GEGLU needs N %% 32 == 0; "
-             "out / residual 16-byte aligned; K within the zero region)", op->i[6], op->i[13], op->i[16]);
+             "out / residual 16-byte aligned; K within the zero region)", op->i[MG_IGEMM_I_N], op->i[MG_IGEMM_I_LDO], op->i[MG_IGEMM_I_LDR]);
   return rc;
 }

@@ -98,11 +98,11 @@ int load_program(FILE* f, const ImgProgram& ip, mg_model* m, Prog* out) {
     char* p = m->bufs[r.buf] + r.off;
     if (r.slot < 16) {
       ops[r.op].p[r.slot] = p;
-    } else {   // the (i[29], i[30]) address pair of MG_OP_IGEMM's row-statistics tickets
+    } else {   // the address pair of MG_OP_IGEMM's row-statistics tickets
       MG_REQUIRE(r.slot == 100 && ops[r.op].kind == MG_OP_IGEMM, "mg_model_load: unknown relocation slot %u", r.slot);
       const uint64_t a = (uint64_t)(uintptr_t)p;
-      ops[r.op].i[29] = (int32_t)(uint32_t)(a & 0xffffffffu);
-      ops[r.op].i[30] = (int32_t)(uint32_t)(a >> 32);
+      ops[r.op].i[MG_IGEMM_I_TICKETS_LO] = (int32_t)(uint32_t)(a & 0xffffffffu);
+      ops[r.op].i[MG_IGEMM_I_TICKETS_HI] = (int32_t)(uint32_t)(a >> 32);
     }
   }
   out->prog = mg_program_create(ops.data(), (int)ops.size());

@@ -25,7 +25,7 @@
 // that a lane's accumulator registers 0-7 / 8-15 are channels 8h .. 8h+7 / 16+8h .. 16+8h+7 - 16-byte stores with no
 // lane exchange.  In the V^T section of the QKV projection the operand roles are swapped (x fragment as MFMA A, weights
 // as B - the register images are the same) and the accumulator then holds, per channel, tokens {4h..4h+3, 8+4h..} - the
-// key order MG_OP_FLASH_ATTN64 i[7] consumes, again 16-byte stores.
+// key order MG_OP_FLASH_ATTN64 consumes with MG_FLASH64_I_VT_PERM, again 16-byte stores.
 //
 // Synchronisation: one s_barrier per stage.  A wave waits for its OWN LDS-DMA pieces of stage j with a counted vmcnt
 // before barrier j; vmcnt retires in order on gfx9 and counts stores, so the wait leaves exactly the younger operations in
@@ -861,53 +861,53 @@ int rg_dispatch(const RgArgs& a, int epi, hipStream_t s) {
 
 int mg_launch_rowgemm(const mg_op* op, hipStream_t s) {
   RgArgs a;
-  a.M = op->i[0];
-  const int K = op->i[1];
-  a.N = op->i[2];
-  a.ldx = op->i[3] > 0 ? op->i[3] : K;
-  const int epi = op->i[6];
-  a.ldo = op->i[4] > 0 ? op->i[4] : (epi == RG_GEGLU ? a.N / 2 : a.N);
-  a.ldr = op->i[5] > 0 ? op->i[5] : a.N;
-  a.T = op->i[7];
-  a.ldt = op->i[8];
-  const int trans_from = op->i[9];
-  const int nw = op->i[10] > 0 ? op->i[10] : 12;
-  a.ln_eps = op->f[0];
-  a.x = (const bf16_t*)op->p[0];
-  a.wp = (const char*)op->p[1];
-  a.out = (bf16_t*)op->p[2];
-  a.res = (const bf16_t*)op->p[3];
-  a.ln_in = (const float2*)op->p[4];
-  a.ln_out = (float2*)op->p[5];
-  a.vt = (bf16_t*)op->p[6];
-  a.gn_ss = (const float*)op->p[7];
-  a.dbg = (unsigned long long*)op->p[8];
-  a.xwp = epi == RG_GEGLU ? (const char*)op->p[9] : nullptr;
-  a.xout = (bf16_t*)op->p[10];
-  a.sm_cols = op->i[11];
-  a.sm_scale = op->f[1];
+  a.M = op->i[MG_ROWGEMM_I_M];
+  const int K = op->i[MG_ROWGEMM_I_K];
+  a.N = op->i[MG_ROWGEMM_I_N];
+  a.ldx = op->i[MG_ROWGEMM_I_LDX] > 0 ? op->i[MG_ROWGEMM_I_LDX] : K;
+  const int epi = op->i[MG_ROWGEMM_I_FORM];
+  a.ldo = op->i[MG_ROWGEMM_I_LDO] > 0 ? op->i[MG_ROWGEMM_I_LDO] : (epi == RG_GEGLU ? a.N / 2 : a.N);
+  a.ldr = op->i[MG_ROWGEMM_I_LDR] > 0 ? op->i[MG_ROWGEMM_I_LDR] : a.N;
+  a.T = op->i[MG_ROWGEMM_I_TOKENS];
+  a.ldt = op->i[MG_ROWGEMM_I_LDT];
+  const int trans_from = op->i[MG_ROWGEMM_I_TRANS_FROM];
+  const int nw = op->i[MG_ROWGEMM_I_WAVES] > 0 ? op->i[MG_ROWGEMM_I_WAVES] : 12;
+  a.ln_eps = op->f[MG_ROWGEMM_F_LN_EPS];
+  a.x = (const bf16_t*)op->p[MG_ROWGEMM_P_X];
+  a.wp = (const char*)op->p[MG_ROWGEMM_P_WP];
+  a.out = (bf16_t*)op->p[MG_ROWGEMM_P_OUT];
+  a.res = (const bf16_t*)op->p[MG_ROWGEMM_P_RESIDUAL];
+  a.ln_in = (const float2*)op->p[MG_ROWGEMM_P_LN_IN];
+  a.ln_out = (float2*)op->p[MG_ROWGEMM_P_LN_OUT];
+  a.vt = (bf16_t*)op->p[MG_ROWGEMM_P_VT];
+  a.gn_ss = (const float*)op->p[MG_ROWGEMM_P_GN_SS];
+  a.dbg = (unsigned long long*)op->p[MG_ROWGEMM_P_DBG];
+  a.xwp = epi == RG_GEGLU ? (const char*)op->p[MG_ROWGEMM_P_XATTN] : nullptr;
+  a.xout = (bf16_t*)op->p[MG_ROWGEMM_P_XOUT];
+  a.sm_cols = op->i[MG_ROWGEMM_I_SM_COLS];
+  a.sm_scale = op->f[MG_ROWGEMM_F_SM_SCALE];
   a.inv_k = 1.0 / (double)K;
   a.inv_n = 1.0 / (double)(a.N > 0 ? a.N : 1);
   a.trans_stage = epi == RG_QKV ? trans_from / 64 : (1 << 30);
   a.prio = 1;
   {
-    const int nsplit = op->i[12] > 1 ? op->i[12] : 1, nst = a.N >> 6;
+    const int nsplit = op->i[MG_ROWGEMM_I_NSPLIT] > 1 ? op->i[MG_ROWGEMM_I_NSPLIT] : 1, nst = a.N >> 6;
     a.spl = (nst + nsplit - 1) / nsplit;
     if (a.spl < 2 && nst >= 2) a.spl = 2;   // (the weight ring is primed two stages deep)
     MG_REQUIRE(nsplit == 1 || !a.ln_out, "rowgemm: row statistics need whole rows in one workgroup (no column split)");
   }
   MG_REQUIRE(epi >= RG_BF16 && epi <= RG_XATTN, "rowgemm: unknown form %d", epi);
   if (a.xwp) {
-    MG_REQUIRE(K == 320 && a.xout && a.ln_in && (op->i[12] <= 1) && a.sm_cols > 0 && a.sm_cols % 2 == 0 && a.sm_cols <= 64 &&
+    MG_REQUIRE(K == 320 && a.xout && a.ln_in && (op->i[MG_ROWGEMM_I_NSPLIT] <= 1) && a.sm_cols > 0 && a.sm_cols % 2 == 0 && a.sm_cols <= 64 &&
                (uintptr_t)a.xwp % 16 == 0 && (uintptr_t)a.xout % 16 == 0,
-               "rowgemm: the cross-attention prologue (p[9]) rides on the unsplit K = 320 GEGLU form; p[10] = the updated rows, p[4] = the (mean, rstd) "
-               "table of the rows as loaded, i[11] = 2 x heads score columns");
+               "rowgemm: the cross-attention prologue (P_XATTN) rides on the unsplit K = 320 GEGLU form; P_XOUT = the updated rows, P_LN_IN = the (mean, rstd) "
+               "table of the rows as loaded, I_SM_COLS = 2 x heads score columns");
   }
   if (epi == RG_XATTN && (K == 640 || K == 1280)) {
     RgXkArgs x;
     x.x = a.x; x.wp = a.wp; x.out = a.out; x.ln_in = a.ln_in; x.ln_out = a.ln_out;
-    x.M = a.M; x.ldx = a.ldx; x.ldo = op->i[4] > 0 ? op->i[4] : K; x.sm_cols = op->i[11];
-    x.sm_scale = op->f[1]; x.ln_eps = a.ln_eps; x.inv_n = 1.0 / (double)K;
+    x.M = a.M; x.ldx = a.ldx; x.ldo = op->i[MG_ROWGEMM_I_LDO] > 0 ? op->i[MG_ROWGEMM_I_LDO] : K; x.sm_cols = op->i[MG_ROWGEMM_I_SM_COLS];
+    x.sm_scale = op->f[MG_ROWGEMM_F_SM_SCALE]; x.ln_eps = a.ln_eps; x.inv_n = 1.0 / (double)K;
     MG_REQUIRE(x.x && x.wp && x.out && x.ln_in, "rowgemm: the cross-attention form needs x, packed weights, out and the (mean, rstd) table of x");
     MG_REQUIRE(a.N == 64 && x.M >= 32 && x.M % 32 == 0 && x.ldx >= K && x.ldx % 8 == 0 && x.ldo >= K && x.ldo % 8 == 0, "rowgemm: rows / leading dimensions");
     MG_REQUIRE(x.sm_cols > 0 && x.sm_cols % 2 == 0 && x.sm_cols <= 64, "rowgemm: score columns (2 per head, <= 64)");
@@ -918,8 +918,8 @@ int mg_launch_rowgemm(const mg_op* op, hipStream_t s) {
   if (epi == RG_XATTN) {
     RgXArgs x;
     x.x = a.x; x.wp = a.wp; x.out = a.out; x.ln_in = a.ln_in; x.ln_out = a.ln_out;
-    x.M = a.M; x.ldx = a.ldx; x.ldo = op->i[4] > 0 ? op->i[4] : K; x.sm_cols = op->i[11];
-    x.sm_scale = op->f[1]; x.ln_eps = a.ln_eps; x.inv_n = 1.0 / (double)K;
+    x.M = a.M; x.ldx = a.ldx; x.ldo = op->i[MG_ROWGEMM_I_LDO] > 0 ? op->i[MG_ROWGEMM_I_LDO] : K; x.sm_cols = op->i[MG_ROWGEMM_I_SM_COLS];
+    x.sm_scale = op->f[MG_ROWGEMM_F_SM_SCALE]; x.ln_eps = a.ln_eps; x.inv_n = 1.0 / (double)K;
     MG_REQUIRE(x.x && x.wp && x.out && x.ln_in, "rowgemm: the cross-attention form needs x, packed weights, out and the (mean, rstd) table of x");
     MG_REQUIRE(K == 320 && a.N == 64, "rowgemm: the cross-attention form is instantiated for K = c2 = 320 and 64 score columns (got K %d, N %d)", K, a.N);
     MG_REQUIRE(x.M >= 32 && x.M % 32 == 0 && x.ldx >= K && x.ldx % 8 == 0 && x.ldo >= K && x.ldo % 8 == 0, "rowgemm: rows / leading dimensions");
@@ -944,9 +944,9 @@ int mg_launch_rowgemm(const mg_op* op, hipStream_t s) {
   if (epi == RG_QKV)
     MG_REQUIRE(a.vt && trans_from > 0 && trans_from % 64 == 0 && trans_from < a.N && a.T > 0 && a.T % 32 == 0 && a.M % a.T == 0 &&
                a.ldt >= a.T && a.ldt % 8 == 0 && (uintptr_t)a.vt % 16 == 0,
-               "rowgemm: the QKV form needs V^T (p[8]), trans_from %% 64 == 0, tokens per image %% 32 == 0, ldt >= tokens");
+               "rowgemm: the QKV form needs V^T (P_VT), trans_from %% 64 == 0, tokens per image %% 32 == 0, ldt >= tokens");
   if (K == 640) {   // 160 registers of rows per wave: two waves per SIMD
-    const int nw6 = op->i[10] > 0 ? op->i[10] : 8;
+    const int nw6 = op->i[MG_ROWGEMM_I_WAVES] > 0 ? op->i[MG_ROWGEMM_I_WAVES] : 8;
     if (nw6 == 8) return rg_dispatch<640, 8>(a, epi, s);
     MG_REQUIRE(false, "rowgemm: K = 640 runs 8 waves per workgroup (got %d)", nw6);
   }

@@ -303,10 +303,9 @@ class Builder:
         return self.persist[key]
 
     def add(self, op, label):
-        if op.kind == L.OP_IGEMM and not op.p[14]:
-            # the program's own split-K workspace (MG_OP_IGEMM p[14]): programs on concurrent streams - two maps in flight -
-            # must not share the library's
-            op.p[14] = self.zeros_persistent("splitk_ws", O.SPLITK_WS_BYTES).data_ptr()
+        if op.kind == L.OP_IGEMM and not O.Raw(op).splitk_ws:
+            # the program's own split-K workspace: programs on concurrent streams - two maps in flight - must not share the library's
+            O.Raw(op).splitk_ws = self.zeros_persistent("splitk_ws", O.SPLITK_WS_BYTES)
         self.seq.add(tuning.apply(op), label)   # (MG_OP_IGEMM: the measured tile / split-K choice where the table has one)
         if op.kind in TWICE_KINDS:
             assert op.kind in (L.OP_GN_STATS, L.OP_GN_FINALIZE, L.OP_GN_APPLY, L.OP_GN_SLAB, L.OP_FLASH_ATTN64, L.OP_FLASH_ATTN512)

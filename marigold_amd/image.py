@@ -27,7 +27,7 @@ from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 MAGIC = b"MGIMG1\0\0"
 VERSION = 1
 KIND_SCRATCH, KIND_ZERO, KIND_DATA = 0, 1, 2
-SLOT_LN_COUNTERS = 100   # relocation slot of the (i[29], i[30]) address pair of MG_OP_IGEMM; slots 0..15 = p[k]
+SLOT_LN_COUNTERS = 100   # relocation slot of MG_OP_IGEMM's ticket address pair (ops.igemm_tickets); slots 0..15 = p[k]
 _PRED = {"depth": (L.POST_DEPTH, 1), "normals": (L.POST_NORMALS, 3), "iid": (L.POST_UNIT, 3)}
 
 
@@ -134,8 +134,8 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
                     hit = bufs.find(op.p[s_])
                     if hit is not None:
                         used.add(hit[0])
-            if op.kind == L.OP_IGEMM and (op.i[29] or op.i[30]):
-                hit = bufs.find((op.i[29] & 0xffffffff) | ((op.i[30] & 0xffffffff) << 32))
+            if op.kind == L.OP_IGEMM and O.igemm_tickets(op):
+                hit = bufs.find(O.igemm_tickets(op))
                 if hit is not None:
                     used.add(hit[0])
         for t in io.values():
@@ -161,13 +161,12 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
                             raise RuntimeError(f"model image: op {k} ({seq.labels[k]}) of {name} points outside every known buffer (p[{s}])")
                         relocs.append((k, s, hit[0], hit[1]))
                         c.p[s] = None
-                if c.kind == L.OP_IGEMM and (c.i[29] or c.i[30]):
-                    ptr = (c.i[29] & 0xffffffff) | ((c.i[30] & 0xffffffff) << 32)
-                    hit = bufs.find(ptr)
+                if c.kind == L.OP_IGEMM and O.igemm_tickets(c):
+                    hit = bufs.find(O.igemm_tickets(c))
                     if hit is None:
                         raise RuntimeError(f"model image: the row-statistics tickets of op {k} of {name} are not in a known buffer")
                     relocs.append((k, SLOT_LN_COUNTERS, hit[0], hit[1]))
-                    c.i[29] = c.i[30] = 0
+                    O.set_igemm_tickets(c, None)
                 raw += bytes(c)
             slots = []
             for nm, t in io.items():

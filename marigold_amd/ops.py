@@ -2,7 +2,10 @@
 host-side container that turns a list of them into a native program (``mg_program_*``).
 
 torch is used only as the owner of device memory and the source of the HIP stream handle.
-Field layout of every op is documented in include/marigold_hip.h.
+Field layout of every op is documented in include/marigold_hip.h.  The four kinds with many launch forms (MG_OP_IGEMM,
+MG_OP_CONV3X3, MG_OP_ROWGEMM, MG_OP_FLASH_ATTN64) are built and read by field NAME (the header's enumerators, mirrored in
+_lib.FIELDS): ``Raw`` is an op's fields as stored, ``igemm_view`` / ``conv3x3_view`` / ``rowgemm_view`` / ``flash_attn64_view`` the op
+decoded the way its launcher decodes it.  The launchers' defaulting rules are restated in those views and nowhere else in Python.
 """
 import ctypes
 
@@ -34,6 +37,131 @@ def make_op(kind, i=(), f=(), p=(), l=()):
     return op
 
 
+# --------------------------------------------------------------------------- named fields
+
+_TO_SLOT = dict(i=int, f=float, p=_ptr, l=int)
+_WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in L.FIELDS.items()}
+assert all(len(w) == sum(len(names) for names in L.FIELDS[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
+
+
+class Raw:
+    """The fields of an op of one of the ``L.FIELDS`` kinds by name, as stored: ``Raw(op).ldw`` reads and writes the op's MG_IGEMM_I_LDW slot."""
+
+    def __init__(self, op):
+        object.__setattr__(self, "op", op)
+        object.__setattr__(self, "_where", _WHERE[op.kind])
+
+    def __getattr__(self, name):
+        if name not in self._where:
+            raise AttributeError(f"{L.OP_NAMES[self.op.kind]} has no field {name!r}")
+        arr, k = self._where[name]
+        return getattr(self.op, arr)[k] or 0   # (a NULL pointer reads as 0, not None)
+
+    def __setattr__(self, name, value):
+        arr, k = self._where[name]
+        getattr(self.op, arr)[k] = _TO_SLOT[arr](value)
+
+
+def build_op(kind, **fields):
+    """An op of one of the ``L.FIELDS`` kinds from its fields by name; what is not named stays zero / NULL."""
+    op = MgOp()
+    op.kind = kind
+    raw = Raw(op)
+    for name, value in fields.items():
+        setattr(raw, name, value)
+    return op
+
+
+class View:
+    """An op decoded once.  ``raw``: its fields as stored (writable).  The attributes set by the ``*_view`` function: what the
+    launcher works with after its defaulting rules; every other field name reads through to ``raw``."""
+
+    def __init__(self, op):
+        self.op, self.raw = op, Raw(op)
+
+    def __getattr__(self, name):
+        return getattr(self.raw, name)
+
+
+def igemm_view(op):
+    """MG_OP_IGEMM as csrc/igemm2.hip::mg_launch_igemm2 decodes it.  ``M`` rows; ``K`` = taps * Cin, ``Kx`` = K + the folded
+    shortcut's ``cx`` channels (``cx0`` of them in X0); ``c0`` = the channels A holds; row strides with their defaults (``ldo`` has
+    none in the launcher: ``igemm()`` fills it in); ``n_out`` = columns stored (GEGLU: N / 2); ``fits_31bit``: the operands are
+    within the hand-placed tiles' (72 / 73) 31-bit byte offsets."""
+    v = View(op)
+    r = v.raw
+    v.has_residual, v.has_ln_out, v.has_ln_in, v.has_a1, v.has_rowvec, v.has_fold, v.has_x1 = (
+        bool(x) for x in (r.residual, r.ln_out, r.ln_in, r.a1, r.rowvec, r.x0, r.x1))
+    v.has_trans = r.trans_from >= 0
+    v.M = r.b * r.ho * r.wo
+    v.batch_z = max(1, r.batch_z)
+    v.cx = r.cx if v.has_fold else 0
+    v.cx0 = r.cx0 if v.has_x1 else v.cx
+    v.K = r.taps * r.cin
+    v.Kx = v.K + v.cx
+    v.c0 = r.c0 if v.has_a1 else r.cin
+    v.lda = r.lda if r.lda > 0 else v.c0
+    v.lda1 = (r.lda1 if r.lda1 > 0 else r.cin - v.c0) if v.has_a1 else 0
+    v.ldw = r.ldw if r.ldw > 0 else v.Kx
+    v.ldr = r.ldr if r.ldr > 0 else r.n
+    v.ldx0 = r.ldx0 if r.ldx0 > 0 else v.cx0
+    v.ldx1 = (r.ldx1 if r.ldx1 > 0 else v.cx - v.cx0) if v.has_x1 else 0
+    v.n_out = r.n // 2 if r.epi == L.EPI_GEGLU else r.n
+    v.fits_31bit = r.b * r.h * r.w * max(v.lda, v.lda1, v.ldx0, v.ldx1) < (1 << 30) and r.n * v.ldw < (1 << 30)
+    return v
+
+
+def conv3x3_view(op):
+    """MG_OP_CONV3X3 as csrc/conv_patch.hip::conv3x3_decode decodes it: ``cin`` = C0 + C1, ``taps`` (4 in sub-pixel mode: ``par`` = 4
+    output parities; else 9), dense row strides where the op leaves them 0."""
+    v = View(op)
+    r = v.raw
+    v.has_residual, v.has_a1, v.has_ss, v.has_rowvec, v.has_gn_part = (bool(x) for x in (r.residual, r.a1, r.ss, r.rowvec, r.gn_part))
+    v.cin = r.c0 + r.c1
+    v.taps, v.par = (4, 4) if r.subpix else (9, 1)
+    v.lda0 = r.lda0 if r.lda0 > 0 else r.c0
+    v.lda1 = r.lda1 if r.lda1 > 0 else r.c1
+    v.ldo = r.ldo if r.ldo > 0 else r.n
+    v.ldr = r.ldr if r.ldr > 0 else r.n
+    v.ldw = r.ldw if r.ldw > 0 else v.taps * v.cin
+    return v
+
+
+def rowgemm_view(op):
+    """MG_OP_ROWGEMM as csrc/rowgemm.hip::mg_launch_rowgemm decodes it: ``n_out`` = columns stored (GEGLU: N / 2; the
+    cross-attention form writes K), dense row strides where the op leaves them 0, ``has_xattn``: the cross-attention prologue."""
+    v = View(op)
+    r = v.raw
+    v.has_residual, v.has_ln_in, v.has_ln_out, v.has_gn_ss = (bool(x) for x in (r.residual, r.ln_in, r.ln_out, r.gn_ss))
+    v.has_xattn = r.form == L.RG_GEGLU and bool(r.xattn)
+    v.n_out = {L.RG_GEGLU: r.n // 2, L.RG_XATTN: r.k}.get(r.form, r.n)
+    v.ldx = r.ldx if r.ldx > 0 else r.k
+    v.ldo = r.ldo if r.ldo > 0 else v.n_out
+    v.ldr = r.ldr if r.ldr > 0 else r.n
+    v.waves = r.waves if r.waves > 0 else (8 if r.k == 640 else 12)
+    return v
+
+
+def flash_attn64_view(op):
+    """MG_OP_FLASH_ATTN64: no defaulting rules - every field as stored; ``ws_bytes`` of the workspace."""
+    v = View(op)
+    v.ws_bytes = v.raw.ws_kb * 1024
+    return v
+
+
+def igemm_tickets(op):
+    """Device address of the caller's row-block tickets of an MG_OP_IGEMM (its ``tickets_lo`` / ``tickets_hi`` halves); 0 = the library's."""
+    r = Raw(op)
+    return (r.tickets_lo & 0xffffffff) | ((r.tickets_hi & 0xffffffff) << 32)
+
+
+def set_igemm_tickets(op, addr):
+    """Store the ticket buffer's address (tensor / int; None or 0 clears it) as two int32 halves."""
+    addr = _ptr(addr) or 0
+    r = Raw(op)
+    r.tickets_lo, r.tickets_hi = (h - (1 << 32) if h >= 1 << 31 else h for h in (addr & 0xffffffff, (addr >> 32) & 0xffffffff))
+
+
 def current_stream_handle():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -48,17 +176,19 @@ def igemm(a, w, out, *, B, H, W, Cin, Ho, Wo, N, taps=1, stride=1, pad=0, up=Non
     """``fold`` = (x0, x1 | None, Cx0, Cx[, ldx0, ldx1]): a 1x1 convolution of a second tensor (the ResNet block's conv_shortcut)
     as extra K of this 3x3 convolution; ``w`` rows are then [conv weights | shortcut weights]."""
     hu, wu = up if up else (0, 0)
-    cp = _ptr(ln_counters) or 0   # the program's own row-block tickets (two int32 halves of the device address)
-    c_lo, c_hi = cp & 0xffffffff, (cp >> 32) & 0xffffffff
-    c_lo, c_hi = (c_lo - (1 << 32) if c_lo >= 1 << 31 else c_lo), (c_hi - (1 << 32) if c_hi >= 1 << 31 else c_hi)
     if ldo is None:
         ldo = N // 2 if epi == L.EPI_GEGLU else N
-    return make_op(L.OP_IGEMM,
-                   i=[B, H, W, Cin, Ho, Wo, N, taps, stride, pad, hu, wu, epi, ldo, trans_from,
-                      batch_z, ldr, lda, ldt, variant, ldw, int(rowvec_bcast), n_alg, k_alg, C0, lda1,
-                      int(trans_perm), sm_cols, c2, c_lo, c_hi, splits] + ([fold[3], fold[2], fold[4] if len(fold) > 4 else 0, fold[5] if len(fold) > 5 else 0] if fold else []),
-                   f=[scale, ln_eps, sm_scale], p=[a, w, out, bias, rowvec, residual, out2, a1, ln_out, ln_in, ln_g, ln_c] + ([fold[0], fold[1]] if fold else []),
-                   l=list(zstrides))
+    op = build_op(L.OP_IGEMM, b=B, h=H, w=W, cin=Cin, ho=Ho, wo=Wo, n=N, taps=taps, stride=stride, pad=pad, hu=hu, wu=wu, epi=epi, ldo=ldo,
+                  trans_from=trans_from, batch_z=batch_z, ldr=ldr, lda=lda, ldt=ldt, variant=variant, ldw=ldw, rowvec_bcast=rowvec_bcast,
+                  n_alg=n_alg, k_alg=k_alg, c0=C0, lda1=lda1, trans_perm=trans_perm, sm_cols=sm_cols, c2=c2, splits=splits,
+                  scale=scale, ln_eps=ln_eps, sm_scale=sm_scale, a=a, wt=w, out=out, bias=bias, rowvec=rowvec, residual=residual,
+                  out2=out2, a1=a1, ln_out=ln_out, ln_in=ln_in, ln_g=ln_g, ln_c=ln_c, **dict(zip(("sa", "sw", "so", "sr"), zstrides)))
+    set_igemm_tickets(op, ln_counters)   # the program's own row-block tickets
+    if fold:
+        r = Raw(op)
+        r.x0, r.x1, r.cx0, r.cx = fold[:4]
+        r.ldx0, r.ldx1 = (tuple(fold[4:6]) + (0, 0))[:2]
+    return op
 
 
 def conv3x3(a0, w, out, *, B, H, W, C0, N, a1=None, C1=0, subpix=False, ss=None, silu=False, bias=None, rowvec=None,
@@ -67,9 +197,9 @@ def conv3x3(a0, w, out, *, B, H, W, C0, N, a1=None, C1=0, subpix=False, ss=None,
     """Patch-resident conv3x3 / pad 1 (MG_OP_CONV3X3): fused GroupNorm scale/shift (+SiLU) on the input, second
     channel source, sub-pixel 2x up-sampling; ``gn_part``: the output's GroupNorm partial sums as a by-product
     (``conv3x3_gn_slots`` tells whether / how many slots per image)."""
-    return make_op(L.OP_CONV3X3,
-                   i=[B, H, W, C0, C1, N, int(subpix), int(silu), lda0, lda1, ldo, ldr, ldw, int(rowvec_bcast), variant, gn_cpg, gn_slots],
-                   p=[a0, w, out, bias, rowvec, residual, a1, ss, gn_part], l=[wz])
+    return build_op(L.OP_CONV3X3, b=B, h=H, w=W, c0=C0, c1=C1, n=N, subpix=subpix, silu=silu, lda0=lda0, lda1=lda1, ldo=ldo, ldr=ldr,
+                    ldw=ldw, rowvec_bcast=rowvec_bcast, variant=variant, gn_cpg=gn_cpg, gn_slots=gn_slots, a0=a0, wt=w, out=out, bias=bias,
+                    rowvec=rowvec, residual=residual, a1=a1, ss=ss, gn_part=gn_part, sw=wz)
 
 
 def conv3x3_gn_slots(op, f16=False):
@@ -84,8 +214,9 @@ def rowgemm(x, wp, out, *, M, K, N, form=L.RG_BF16, ldx=0, ldo=0, ldr=0, residua
     """Row-resident GEMM (MG_OP_ROWGEMM): ``wp`` from weights.pack_rowgemm (form RG_XATTN: pack_rowgemm_xattn).  ``xattn`` (GEGLU
     form, K = 320, no column split): a pack_rowgemm_xattn image - the collapsed cross-attention runs on the rows in registers before
     the projection (``ln_in`` = the statistics of the rows as loaded, ``xout`` = where the updated rows go, ``sm_cols`` / ``sm_scale``)."""
-    return make_op(L.OP_ROWGEMM, i=[M, K, N, ldx, ldo, ldr, form, tokens, ldt, trans_from, waves, sm_cols, nsplit], f=[ln_eps, sm_scale],
-                   p=[x, wp, out, residual, ln_in, ln_out, vt, gn_ss, dbg, xattn, xout if xattn is not None else None])
+    return build_op(L.OP_ROWGEMM, m=M, k=K, n=N, ldx=ldx, ldo=ldo, ldr=ldr, form=form, tokens=tokens, ldt=ldt, trans_from=trans_from,
+                    waves=waves, sm_cols=sm_cols, nsplit=nsplit, ln_eps=ln_eps, sm_scale=sm_scale, x=x, wp=wp, out=out, residual=residual,
+                    ln_in=ln_in, ln_out=ln_out, vt=vt, gn_ss=gn_ss, dbg=dbg, xattn=xattn, xout=xout if xattn is not None else None)
 
 
 def linear(x, w, out, *, M, K, N, **kw):
@@ -114,7 +245,7 @@ def gn_slab(x0, out, ss, *, B, HW, C, groups, gamma, beta, eps, silu=False, x1=N
     return make_op(L.OP_GN_SLAB, i=[B, HW, C, C0, groups, int(silu)], f=[eps], p=[x0, x1, out, gamma, beta, ss])
 
 
-SPLITK_WS_BYTES = 64 << 20   # MG_SPLITK_WS_BYTES (csrc/common.h): what MG_OP_IGEMM p[14] must hold
+SPLITK_WS_BYTES = 64 << 20   # MG_SPLITK_WS_BYTES (csrc/common.h): what MG_OP_IGEMM's splitk_ws must hold
 FLASH_WS_BYTES = 4096 + 255 * 4 * 4 * (16384 + 1024)   # tickets + four partial results for up to 255 split blocks of queries (tests: split = 1)
 # What the engine allocates per program: the automatic rule (split = 0) only splits a left-over of at most CUs / 8 blocks (32 on
 # MI355X; 40 leaves room for a larger part) - 11 MB instead of 71 MB zeroed per Builder.  A smaller workspace than a launch could
@@ -130,8 +261,9 @@ def flash_attn64(q, k, vt, o, *, B, heads, Ntok, ldq, ldo, ldvt, sq, sk, svt, so
     queries with the running-maximum loop.  ``ws`` (optional, ZEROED once, then owned by the launches of one stream): workspace of
     the hand-placed kernel's key-split blocks - the blocks of 256 queries beyond the last multiple of the CU count are split
     along the keys over the chip (``FLASH_WS_BYTES`` covers every case); ``split``: 0 = when it pays, 1 = always (tests), 2 = never."""
-    return make_op(L.OP_FLASH_ATTN64, i=[B, heads, Ntok, ldq, ldo, ldvt, variant, int(vt_perm), ws_bytes // 1024, split], f=[scale, redo_thr],
-                   p=[q, k, vt, o, dbg, ws], l=[sq, sk, svt, so])
+    return build_op(L.OP_FLASH_ATTN64, b=B, heads=heads, ntok=Ntok, ldq=ldq, ldo=ldo, ldvt=ldvt, variant=variant, vt_perm=vt_perm,
+                    ws_kb=ws_bytes // 1024, split=split, scale=scale, redo_thr=redo_thr, q=q, k=k, vt=vt, o=o, dbg=dbg, ws=ws,
+                    sq=sq, sk=sk, svt=svt, so=so)
 
 
 def flash_attn512(q, k, vt, o, *, B, Ntok, ldq, ldo, ldvt, sq, sk, svt, so, scale):

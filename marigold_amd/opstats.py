@@ -3,7 +3,7 @@ every input + one write of every output, weights counted once per launch) and th
 it runs on.  bench.py turns per-op HIP-event timings into per-class achieved TFLOP/s / GB/s
 against the gfx950 rooflines; DESIGN.md quotes the same formulas.
 """
-from . import _lib as L
+from . import _lib as L, ops as O
 
 MFMA_PEAK_TFLOPS = 2500.0   # bf16 dense, /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0       # HBM3E spec (6.29 TB/s measured streaming)
@@ -25,48 +25,47 @@ def op_cost(op):
     cls = CLASS.get(k, "other")
     flops = byts = 0
     if k == L.OP_IGEMM:
-        B, H, W, Cin, Ho, Wo, N, taps = (i[j] for j in range(8))
-        epi, bz = i[12], max(1, i[15])
-        M, K = B * Ho * Wo, taps * Cin
-        flops = 2 * M * (i[22] or N) * (i[23] or K) * bz   # i[22] / i[23]: un-padded N / K of the boundary convs
-        cx = i[32] if op.p[12] else 0                      # a folded 1x1 convolution: extra K, its input and weights read once
-        flops += 2 * M * N * cx
-        n_out = N // 2 if epi == L.EPI_GEGLU else N
-        osz = 4 if epi == L.EPI_F32 else 2   # bf16 for the plain, GEGLU and pair-softmax epilogues
+        v = O.igemm_view(op)
+        B, H, W, Cin, N, taps, M, K, bz, cx, n_out = v.b, v.h, v.w, v.cin, v.n, v.taps, v.M, v.K, v.batch_z, v.cx, v.n_out
+        flops = 2 * M * (v.n_alg or N) * (v.k_alg or K) * bz   # n_alg / k_alg: un-padded N / K of the boundary convs
+        flops += 2 * M * N * cx                                # a folded 1x1 convolution: extra K, its input and weights read once
+        osz = 4 if v.epi == L.EPI_F32 else 2   # bf16 for the plain, GEGLU and pair-softmax epilogues
         if taps == 4:   # sub-pixel up-sampling conv: the 4 parities share one input, each writes its own output pixels
             byts = B * H * W * Cin * 2 + bz * (N * K * 2 + M * n_out * osz)
         else:
             byts = bz * (B * H * W * Cin * 2 + N * K * 2 + M * n_out * osz)
-        if epi == L.EPI_XATTN2:   # second stage: P [M][N] x W2 [c2][N] -> out [M][c2] (+ residual)
-            c2 = i[28]
+        if v.epi == L.EPI_XATTN2:   # second stage: P [M][N] x W2 [c2][N] -> out [M][c2] (+ residual)
+            c2 = v.c2
             flops += 2 * M * c2 * N
-            byts = B * H * W * Cin * 2 + N * K * 2 + c2 * N * 2 + M * c2 * 2 + (M * c2 * 2 if op.p[5] else 0)
-        elif op.p[5]:
+            byts = B * H * W * Cin * 2 + N * K * 2 + c2 * N * 2 + M * c2 * 2 + (M * c2 * 2 if v.has_residual else 0)
+        elif v.has_residual:
             byts += bz * M * n_out * 2   # fused residual read
         byts += (M + N) * cx * 2
     elif k == L.OP_ROWGEMM:
-        M, K, N, form = i[0], i[1], i[2], i[6]
+        v = O.rowgemm_view(op)
+        M, K, N, form = v.m, v.k, v.n, v.form
         flops = 2 * M * N * K
-        byts = M * K * 2 + N * K * 2 + M * (N // 2 if form == L.RG_GEGLU else N) * 2 + (M * N * 2 if op.p[3] else 0)
+        byts = M * K * 2 + N * K * 2 + M * (N // 2 if form == L.RG_GEGLU else N) * 2 + (M * N * 2 if v.has_residual else 0)
         if form == L.RG_XATTN:   # + P [M][64] x VO^T [K][64]; x read once, out [M][K] written once
             flops += 2 * M * K * N
             byts = 2 * M * K * 2 + 2 * N * K * 2
-        if form == L.RG_GEGLU and op.p[9]:   # the cross-attention prologue: scores + blend GEMMs, the updated rows written once
+        if v.has_xattn:   # the cross-attention prologue: scores + blend GEMMs, the updated rows written once
             flops += 2 * 2 * M * K * 64
             byts += M * K * 2 + 2 * 64 * K * 2
     elif k == L.OP_CONV3X3:
-        B, H, W, C0, C1, N, subpix = (i[j] for j in range(7))
-        Cin, par, T = C0 + C1, (4 if subpix else 1), (4 if subpix else 9)
+        v = O.conv3x3_view(op)
+        B, H, W, N, Cin, par, T = v.b, v.h, v.w, v.n, v.cin, v.par, v.taps
         flops = 2 * B * H * W * N * T * Cin * par
         byts = B * H * W * Cin * 2 + par * (N * T * Cin * 2 + B * H * W * N * 2)
-        if op.p[5]:
+        if v.has_residual:
             byts += B * H * W * N * 2
     elif k == L.OP_CONV3X3_HEAD:
         B, H, W, C, co = (i[j] for j in range(5))
         flops = 2 * B * H * W * co * 9 * C
         byts = B * H * W * (C * 2 + co * 4)
     elif k == L.OP_FLASH_ATTN64:
-        B, heads, T = i[0], i[1], i[2]
+        v = O.flash_attn64_view(op)
+        B, heads, T = v.b, v.heads, v.ntok
         flops = 4 * B * heads * T * T * 64
         byts = 4 * B * heads * T * 64 * 2
     elif k == L.OP_FLASH_ATTN512:

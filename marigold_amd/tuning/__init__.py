@@ -15,7 +15,7 @@ second source?, time-embedding row?): what the tile's time depends on; B / H / W
 import json
 import os
 
-from .. import _lib as L
+from .. import _lib as L, ops as O
 
 _DB = None
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gfx950.json")
@@ -23,35 +23,20 @@ ENABLED = not (os.environ.get("MARIGOLD_TUNING") == "1" and os.environ.get("MARI
 
 
 def key_of(op):
-    i = op.i
-    M, K = i[0] * i[4] * i[5], i[7] * i[3]
-    key = (f"{M},{i[6]},{K},{i[7]},{i[8]},{i[12]},{int(i[14] >= 0)},{max(1, i[15])},"
-           f"{int(bool(op.p[5]))},{int(bool(op.p[8]))},{int(bool(op.p[9]))},{int(bool(op.p[7]))},{int(bool(op.p[4]))}")
-    key += f",x{i[32]}" if op.p[12] else ""   # (a folded 1x1 convolution: its channel count)
+    v = O.igemm_view(op)
+    key = (f"{v.M},{v.n},{v.K},{v.taps},{v.stride},{v.epi},{int(v.has_trans)},{v.batch_z},"
+           f"{int(v.has_residual)},{int(v.has_ln_out)},{int(v.has_ln_in)},{int(v.has_a1)},{int(v.has_rowvec)}")
+    key += f",x{v.cx}" if v.has_fold else ""   # (a folded 1x1 convolution: its channel count)
     # (round 6) what else decides whether a tile is legal or fast - appended only where it differs from the plain form the table
     # was swept on, so that existing entries keep their keys and an odd launch can never collide with them: a virtual up-sampled
     # input, a padding other than the tap window's own, operand row strides wider than the channel count
-    if i[10] or i[11]:
-        key += f",u{i[10]}x{i[11]}"
-    if i[9] != (1 if i[7] in (9, 4) else 0):
-        key += f",p{i[9]}"
-    c0 = i[24] if op.p[7] else i[3]
-    if (i[17] and i[17] != c0) or (op.p[7] and i[25] and i[25] != i[3] - c0) or (i[20] and i[20] != K + (i[32] if op.p[12] else 0)):
-        key += f",ld{i[17]}.{i[25]}.{i[20]}"
+    if v.hu or v.wu:
+        key += f",u{v.hu}x{v.wu}"
+    if v.pad != (1 if v.taps in (9, 4) else 0):
+        key += f",p{v.pad}"
+    if v.lda != v.c0 or v.lda1 != v.cin - v.c0 or v.ldw != v.Kx:
+        key += f",ld{v.raw.lda}.{v.raw.lda1}.{v.raw.ldw}"
     return key
-
-
-def _fits_31bit(op):
-    """The hand-placed tiles (72 / 73) address their operands with 31-bit byte offsets (csrc/igemm2.hip::dispatch_tile); the
-    library's own choice falls back to 62 / 46 beyond that - a table entry must not take that fallback away."""
-    i = op.i
-    c0 = i[24] if op.p[7] else i[3]
-    lda = i[17] or c0
-    lda1 = (i[25] or i[3] - c0) if op.p[7] else 0
-    ldx0 = (i[34] or (i[33] if op.p[13] else i[32])) if op.p[12] else 0
-    ldx1 = (i[35] or i[32] - i[33]) if op.p[13] else 0
-    ldw = i[20] or i[7] * i[3] + (i[32] if op.p[12] else 0)
-    return i[0] * i[1] * i[2] * max(lda, lda1, ldx0, ldx1) < (1 << 30) and i[6] * ldw < (1 << 30)
 
 
 def load():
@@ -66,11 +51,16 @@ def load():
 
 
 def apply(op):
-    """Set the measured (tile variant, split-K count) on an MG_OP_IGEMM op that leaves both to the library (i[19] == 0 and
-    i[31] == 0).  Returns the op."""
-    if not ENABLED or op.kind != L.OP_IGEMM or op.i[19] != 0 or op.i[31] != 0:
+    """Set the measured (tile variant, split-K count) on an MG_OP_IGEMM op that leaves both to the library (``variant`` == 0 and
+    ``splits`` == 0).  Returns the op.  The hand-placed tiles (72 / 73) address their operands with 31-bit byte offsets
+    (csrc/igemm2.hip::dispatch_tile); the library's own choice falls back to 62 / 46 beyond that - a table entry must not take
+    that fallback away."""
+    if not ENABLED or op.kind != L.OP_IGEMM:
+        return op
+    v = O.igemm_view(op)
+    if v.variant != 0 or v.splits != 0:
         return op
     hit = load().get(key_of(op))
-    if hit is not None and not (int(hit[0]) in (72, 73) and not _fits_31bit(op)):
-        op.i[19], op.i[31] = int(hit[0]), int(hit[1])
+    if hit is not None and not (int(hit[0]) in (72, 73) and not v.fits_31bit):
+        v.raw.variant, v.raw.splits = int(hit[0]), int(hit[1])
     return op

@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 
 import torch
 
-from marigold_amd import _lib as L
+from marigold_amd import _lib as L, ops as O
 
 MAX_REL_BOUND = 1.5e-2
 # rmse / rms per kind: 2x the worst value measured on the MI355X (VAE encode 768^2, bf16 operands; measured value in brackets)
@@ -155,54 +155,46 @@ def decode(op, resolve, label="", f16=False):
         sp.writes["out"] = R(p[2], o16, (B * H * W, Kp), (Kp, 1))
         sp.rows = row_sample(B * H * W, H * W, Wimg=W, Himg=H)
     elif k == L.OP_IGEMM:
-        for idx, what in ((7, "a second channel source (p[7])"), (8, "row statistics (p[8])"), (9, "folded LayerNorm (p[9])")):
-            if p[idx]:
+        v = O.igemm_view(op)
+        for has, what in ((v.has_a1, "a second channel source"), (v.has_ln_out, "row statistics"), (v.has_ln_in, "folded LayerNorm")):
+            if has:
                 raise Unsupported(label, what)
-        epi = i[12]
+        epi = v.epi
         if epi not in (L.EPI_BF16, L.EPI_F32):
             raise Unsupported(label, f"igemm epilogue {epi}")
-        if i[10] or i[11]:
+        if v.hu or v.wu:
             raise Unsupported(label, "igemm on a virtual up-sampled input")
-        if i[26]:
+        if v.trans_perm:
             raise Unsupported(label, "igemm permuted transposed section")
-        B, H, W, Cin, Ho, Wo, N, taps, stride, pad = i[:10]
+        B, H, W, Cin, Ho, Wo, N, taps, stride, pad = v.b, v.h, v.w, v.cin, v.ho, v.wo, v.n, v.taps, v.stride, v.pad
         if taps not in (1, 9):
             raise Unsupported(label, f"igemm taps {taps}")
-        bz = max(1, i[15])
-        lda = i[17] or Cin
-        Cx, Cx0 = (i[32], i[33]) if p[12] else (0, 0)
-        if p[12] and (taps != 9 or stride != 1 or pad != 1 or bz != 1):
+        bz, Cx, Cx0, tf, M = v.batch_z, v.cx, v.cx0, v.trans_from, v.M
+        if v.has_fold and (taps != 9 or stride != 1 or pad != 1 or bz != 1):
             raise Unsupported(label, "a folded shortcut outside the 3x3 / stride 1 form")
-        ldw = i[20] or taps * Cin + Cx
-        ldo = i[13] or N
-        ldr = i[16] or N
-        tf = i[14]
-        sA, sW, sO, sR = l
-        ncols = tf if tf >= 0 else N
+        ncols = tf if v.has_trans else N
         odt = torch.float32 if epi == L.EPI_F32 else o16
-        sp.reads["A"] = R(p[0], o16, (bz, B * H * W, Cin), (sA, lda, 1))
-        sp.reads["Wt"] = R(p[1], o16, (bz, N, taps * Cin + Cx), (sW, ldw, 1))
-        if p[12]:   # the 1x1 shortcut of a second tensor as extra K: X0 channels [0, Cx0), X1 [Cx0, Cx)
-            sp.reads["X0"] = R(p[12], o16, (B * H * W, Cx0), (i[34] or Cx0, 1))
-            if p[13]:
-                sp.reads["X1"] = R(p[13], o16, (B * H * W, Cx - Cx0), (i[35] or Cx - Cx0, 1))
-            elif Cx != Cx0:
+        sp.reads["A"] = R(v.a, o16, (bz, B * H * W, Cin), (v.sa, v.lda, 1))
+        sp.reads["Wt"] = R(v.wt, o16, (bz, N, v.Kx), (v.sw, v.ldw, 1))
+        if v.has_fold:   # the 1x1 shortcut of a second tensor as extra K: X0 channels [0, Cx0), X1 [Cx0, Cx)
+            sp.reads["X0"] = R(v.x0, o16, (B * H * W, Cx0), (v.ldx0, 1))
+            if v.has_x1:
+                sp.reads["X1"] = R(v.x1, o16, (B * H * W, Cx - Cx0), (v.ldx1, 1))
+            elif Cx != v.raw.cx0:
                 raise Unsupported(label, "a folded shortcut without its second source")
-        if p[3]:
-            sp.reads["bias"] = R(p[3], torch.float32, (N,), (1,))
-        if p[4]:
-            sp.reads["rowvec"] = R(p[4], torch.float32, (B, N), (0 if i[21] else N, 1))
-        M = B * Ho * Wo
-        if p[5]:
-            sp.reads["residual"] = R(p[5], o16, (bz, M, ncols), (sR, ldr, 1))
-        sp.writes["out"] = R(p[2], odt, (bz, M, ncols), (sO, ldo, 1))
-        if tf >= 0:
-            ldt = i[18]
-            sp.writes["out2"] = R(p[6], o16, (B, N - tf, ldt), ((N - tf) * ldt, ldt, 1))
+        if v.bias:
+            sp.reads["bias"] = R(v.bias, torch.float32, (N,), (1,))
+        if v.has_rowvec:
+            sp.reads["rowvec"] = R(v.rowvec, torch.float32, (B, N), (0 if v.rowvec_bcast else N, 1))
+        if v.has_residual:
+            sp.reads["residual"] = R(v.residual, o16, (bz, M, ncols), (v.sr, v.ldr, 1))
+        sp.writes["out"] = R(v.out, odt, (bz, M, ncols), (v.so, v.ldo, 1))
+        if v.has_trans:
+            sp.writes["out2"] = R(v.out2, o16, (B, N - tf, v.ldt), ((N - tf) * v.ldt, v.ldt, 1))
             if bz != 1:
                 raise Unsupported(label, "igemm transposed section with batching")
         sp.rows = row_sample(M, Ho * Wo, Wimg=Wo if taps == 9 else 0, Himg=Ho if taps == 9 else 0)
-        sp.n_check = i[22] or N
+        sp.n_check = v.n_alg or N
     elif k == L.OP_GN_STATS:
         B, HW, C, chunks, Ctot, coff, groups, slot0, slots, C1 = i[:10]
         if not p[4]:
@@ -227,29 +219,25 @@ def decode(op, resolve, label="", f16=False):
         sp.reads["ss"] = R(p[1], torch.float32, (B, 2, C), (2 * C, C, 1))
         sp.writes["out"] = R(p[2], o16, (B, HW, C), (HW * C, C, 1))
     elif k == L.OP_CONV3X3:
-        B, H, W, C0, C1, N, subpix, silu = i[:8]
-        if subpix or C1 or p[6]:
+        v = O.conv3x3_view(op)
+        B, H, W, C0, N = v.b, v.h, v.w, v.c0, v.n
+        if v.subpix or v.c1 or v.has_a1:
             raise Unsupported(label, "conv3x3 sub-pixel / second source")
-        lda0 = i[8] or C0
-        ldo = i[10] or N
-        ldr = i[11] or N
-        ldw = i[12] or 9 * C0
         M = B * H * W
-        sp.reads["A"] = R(p[0], o16, (M, C0), (lda0, 1))
-        sp.reads["Wt"] = R(p[1], o16, (N, 9 * C0), (ldw, 1))
-        if p[3]:
-            sp.reads["bias"] = R(p[3], torch.float32, (N,), (1,))
-        if p[4]:
-            sp.reads["rowvec"] = R(p[4], torch.float32, (B, N), (0 if i[13] else N, 1))
-        if p[5]:
-            sp.reads["residual"] = R(p[5], o16, (M, N), (ldr, 1))
-        if p[7]:
-            sp.reads["ss"] = R(p[7], torch.float32, (B, 2, C0), (2 * C0, C0, 1))
-        sp.writes["out"] = R(p[2], o16, (M, N), (ldo, 1))
-        if p[8]:
-            cpg, slots = i[15], i[16]
-            ng = N // cpg
-            sp.writes["gn_table"] = R(p[8], torch.float32, (B, slots, ng, 2), (slots * ng * 2, ng * 2, 2, 1))
+        sp.reads["A"] = R(v.a0, o16, (M, C0), (v.lda0, 1))
+        sp.reads["Wt"] = R(v.wt, o16, (N, 9 * C0), (v.ldw, 1))
+        if v.bias:
+            sp.reads["bias"] = R(v.bias, torch.float32, (N,), (1,))
+        if v.has_rowvec:
+            sp.reads["rowvec"] = R(v.rowvec, torch.float32, (B, N), (0 if v.rowvec_bcast else N, 1))
+        if v.has_residual:
+            sp.reads["residual"] = R(v.residual, o16, (M, N), (v.ldr, 1))
+        if v.has_ss:
+            sp.reads["ss"] = R(v.ss, torch.float32, (B, 2, C0), (2 * C0, C0, 1))
+        sp.writes["out"] = R(v.out, o16, (M, N), (v.ldo, 1))
+        if v.has_gn_part:
+            ng = N // v.gn_cpg
+            sp.writes["gn_table"] = R(v.gn_part, torch.float32, (B, v.gn_slots, ng, 2), (v.gn_slots * ng * 2, ng * 2, 2, 1))
         sp.rows = row_sample(M, H * W, Wimg=W, Himg=H)
     elif k == L.OP_SOFTMAX_ROWS:
         Rn, ncols, lds, ldp = i[:4]
@@ -312,10 +300,10 @@ def expected(spec, inputs, f16=False):
         ref[:, :9 * C0] = g.to(o16).double()
         return {"out": (ref, rows)}
     if k == L.OP_IGEMM:
-        B, H, W, Cin, Ho, Wo, N, taps, stride, pad = i[:10]
-        tf = i[14]
+        v = O.igemm_view(op)
+        B, H, W, Ho, Wo, N, taps, stride, pad, tf = v.b, v.h, v.w, v.ho, v.wo, v.n, v.taps, v.stride, v.pad, v.trans_from
         rows = spec.rows.to(dev)
-        scale = op.f[0] or 1.0
+        scale = v.scale or 1.0
         res = {}
         bz = inputs["A"].shape[0]
         refs = []
@@ -368,7 +356,8 @@ def expected(spec, inputs, f16=False):
             y = y * torch.sigmoid(y)
         return {"out": (y, None)}
     if k == L.OP_CONV3X3:
-        B, H, W, C0, C1, N, _, silu = i[:8]
+        v = O.conv3x3_view(op)
+        B, H, W, silu = v.b, v.h, v.w, v.silu
         rows = spec.rows.to(dev)
         A = inputs["A"]
         if "ss" in inputs:   # the fused norm: silu?(x * scale + shift), rounded to the operand type as staged; padding stays 0
@@ -400,9 +389,9 @@ def expected(spec, inputs, f16=False):
 
 
 def gn_table_reference(spec, out):
-    """The conv3x3 p[8] table summed over its slots, from the output as stored: [B][groups][2] (sum, sum of squares)."""
-    B, H, W = list(spec.op.i)[:3]
-    N, cpg = spec.op.i[5], spec.op.i[15]
+    """The conv3x3 ``gn_part`` table summed over its slots, from the output as stored: [B][groups][2] (sum, sum of squares)."""
+    v = O.conv3x3_view(spec.op)
+    B, H, W, N, cpg = v.b, v.h, v.w, v.n, v.gn_cpg
     y = out.double().reshape(B, H * W, N // cpg, cpg)
     return torch.stack([y.sum(dim=(1, 3)), (y * y).sum(dim=(1, 3))], -1)
 

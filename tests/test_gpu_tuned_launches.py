@@ -14,6 +14,7 @@ import os
 import pytest
 import torch
 
+from marigold_amd import ops as O
 from tests import op_reference as R
 from tests import tuned_forms as TF
 
@@ -56,7 +57,7 @@ def _max_bound(cls):
 @pytest.mark.parametrize("cls", CLASSES, ids=[c.id for c in CLASSES])
 def test_tuned_launch(dev, table, cls):
     bt = TF.build(cls, None, dev)
-    assert (bt.op.i[19], bt.op.i[31]) == (cls.tile, cls.splits)
+    assert (O.Raw(bt.op).variant, O.Raw(bt.op).splits) == (cls.tile, cls.splits)
     _launch(bt)
     got = {k: v.clone() for k, v in TF.outputs(bt).items()}
     ref, yard = TF.reference(bt), TF.yardstick(bt)

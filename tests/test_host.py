@@ -29,6 +29,88 @@ def test_library_loads_and_exports_header_symbols():
     assert ctypes.sizeof(_lib.MgOp) == 360   # kind + i[40] + f[8] (+4 pad) + p[16] + l[4]
 
 
+def test_op_field_names_match_the_header_and_the_wire_format():
+    """The enumerators of include/marigold_hip.h for the four named kinds equal _lib.FIELDS; every builder argument lands in the raw
+    slot the header documents (the numbers below are the wire format, written out on purpose) and reads back by name; the views
+    restate the launcher's defaulting rules (csrc/igemm2.hip::mg_launch_igemm2)."""
+    from marigold_amd import _lib as L, ops as O
+    hdr = open(os.path.join(ROOT, "include", "marigold_hip.h")).read()
+    parsed = {}
+    for kind, arr, name, val in re.findall(r"\bMG_(IGEMM|CONV3X3|ROWGEMM|FLASH64)_([IFPL])_([A-Z0-9_]+)\s*=\s*(\d+)", hdr):
+        assert name not in parsed.setdefault(kind, {}).setdefault(arr.lower(), {}), (kind, arr, name)
+        parsed[kind][arr.lower()][name] = int(val)
+    mine = {prefix: {arr: {n.upper(): k for k, n in enumerate(names)} for arr, names in tab.items()} for prefix, tab in L.FIELDS.values()}
+    assert parsed == mine
+    assert set(L.FIELDS) == {L.OP_IGEMM, L.OP_CONV3X3, L.OP_ROWGEMM, L.OP_FLASH_ATTN64}
+
+    def check(op, i, f, p, l, names):
+        assert list(op.i) == i + [0] * (40 - len(i)) and list(op.f) == f + [0.0] * (8 - len(f))
+        assert [x or 0 for x in op.p] == p + [0] * (16 - len(p)) and list(op.l) == l + [0] * (4 - len(l))
+        raw = O.Raw(op)
+        for arr, vals in (("i", i), ("f", f), ("p", p), ("l", l)):
+            assert len(names[arr]) == len(vals)
+            for name, val in zip(names[arr], vals):
+                assert getattr(raw, name) == val, (arr, name)
+
+    tickets = 0x123487654321   # (low half >= 2^31: stored as a negative int32)
+    op = O.igemm(101, 102, 103, B=2, H=3, W=4, Cin=5, Ho=6, Wo=7, N=8, taps=9, stride=10, pad=11, up=(12, 13), bias=104, rowvec=105,
+                 residual=106, epi=14, ldo=15, out2=107, trans_from=16, ldt=20, batch_z=17, ldr=18, lda=19, ldw=22, zstrides=(41, 42, 43, 44),
+                 scale=1.5, variant=21, rowvec_bcast=True, n_alg=24, k_alg=25, a1=108, C0=26, lda1=27, ln_out=109, ln_in=110, ln_g=111,
+                 ln_c=112, ln_eps=2.5, sm_scale=3.5, sm_cols=29, c2=30, trans_perm=True, ln_counters=tickets, splits=33,
+                 fold=(113, 114, 35, 34, 36, 37))
+    O.Raw(op).splitk_ws = 115
+    check(op, [2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 1, 24, 25, 26, 27, 1, 29, 30,
+               0x87654321 - (1 << 32), 0x1234, 33, 34, 35, 36, 37],
+          [1.5, 2.5, 3.5], [101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111, 112, 113, 114, 115], [41, 42, 43, 44],
+          dict(i="b h w cin ho wo n taps stride pad hu wu epi ldo trans_from batch_z ldr lda ldt variant ldw rowvec_bcast n_alg k_alg c0 lda1 "
+                 "trans_perm sm_cols c2 tickets_lo tickets_hi splits cx cx0 ldx0 ldx1".split(), f="scale ln_eps sm_scale".split(),
+               p="a wt out bias rowvec residual out2 a1 ln_out ln_in ln_g ln_c x0 x1 splitk_ws".split(), l="sa sw so sr".split()))
+    assert O.igemm_tickets(op) == tickets
+    O.set_igemm_tickets(op, None)
+    assert (op.i[29], op.i[30]) == (0, 0) and O.igemm_tickets(op) == 0
+    op = O.conv3x3(201, 202, 203, B=2, H=3, W=4, C0=5, N=7, a1=207, C1=6, subpix=True, ss=208, silu=True, bias=204, rowvec=205, residual=206,
+                   lda0=8, lda1=9, ldo=10, ldr=11, ldw=12, rowvec_bcast=True, variant=14, wz=45, gn_part=209, gn_cpg=15, gn_slots=16)
+    check(op, [2, 3, 4, 5, 6, 7, 1, 1, 8, 9, 10, 11, 12, 1, 14, 15, 16], [], [201, 202, 203, 204, 205, 206, 207, 208, 209], [45],
+          dict(i="b h w c0 c1 n subpix silu lda0 lda1 ldo ldr ldw rowvec_bcast variant gn_cpg gn_slots".split(), f=[],
+               p="a0 wt out bias rowvec residual a1 ss gn_part".split(), l=["sw"]))
+    v = O.conv3x3_view(op)
+    assert (v.cin, v.taps, v.par, v.lda0, v.lda1, v.ldo, v.ldr, v.ldw) == (11, 4, 4, 8, 9, 10, 11, 12)
+    v = O.conv3x3_view(O.conv3x3(1, 2, 3, B=2, H=3, W=4, C0=64, N=320, a1=4, C1=128))
+    assert (v.cin, v.taps, v.par, v.lda0, v.lda1, v.ldo, v.ldr, v.ldw) == (192, 9, 1, 64, 128, 320, 320, 1728)
+    op = O.rowgemm(301, 302, 303, M=2, K=3, N=4, form=L.RG_GEGLU, ldx=5, ldo=6, ldr=7, residual=304, ln_in=305, ln_out=306, vt=307, gn_ss=308,
+                   tokens=8, ldt=9, trans_from=10, waves=11, ln_eps=1.25, sm_cols=12, sm_scale=2.25, dbg=309, nsplit=13, xattn=310, xout=311)
+    check(op, [2, 3, 4, 5, 6, 7, 1, 8, 9, 10, 11, 12, 13], [1.25, 2.25], [301, 302, 303, 304, 305, 306, 307, 308, 309, 310, 311], [],
+          dict(i="m k n ldx ldo ldr form tokens ldt trans_from waves sm_cols nsplit".split(), f="ln_eps sm_scale".split(),
+               p="x wp out residual ln_in ln_out vt gn_ss dbg xattn xout".split(), l=[]))
+    v = O.rowgemm_view(O.rowgemm(1, 2, 3, M=64, K=320, N=2560, form=L.RG_GEGLU))
+    assert (v.ldx, v.ldo, v.ldr, v.n_out, v.waves, v.has_xattn) == (320, 1280, 2560, 1280, 12, False)
+    v = O.rowgemm_view(O.rowgemm(1, 2, 3, M=64, K=640, N=64, form=L.RG_XATTN))
+    assert (v.ldx, v.ldo, v.n_out, v.waves) == (640, 640, 640, 8)
+    op = O.flash_attn64(401, 402, 403, 404, B=2, heads=3, Ntok=4, ldq=5, ldo=6, ldvt=7, sq=41, sk=42, svt=43, so=44, scale=0.5, variant=8,
+                        vt_perm=True, dbg=405, redo_thr=0.25, ws=406, ws_bytes=9 * 1024, split=10)
+    check(op, [2, 3, 4, 5, 6, 7, 8, 1, 9, 10], [0.5, 0.25], [401, 402, 403, 404, 405, 406], [41, 42, 43, 44],
+          dict(i="b heads ntok ldq ldo ldvt variant vt_perm ws_kb split".split(), f="scale redo_thr".split(), p="q k vt o dbg ws".split(),
+               l="sq sk svt so".split()))
+    assert O.flash_attn64_view(op).ws_bytes == 9216
+
+    # MG_OP_IGEMM's defaults: lda = C0 (the channels A holds), lda1 = Cin - C0, ldw = taps * Cin + Cx, ldx0 = Cx0, ldx1 = Cx - Cx0,
+    # ldr = N; ldo is filled by the builder (N, GEGLU: N / 2) - the launcher takes it as stored
+    def resolved(**kw):
+        v = O.igemm_view(O.igemm(1, 2, 3, B=2, H=8, W=8, Ho=8, Wo=8, N=128, taps=9, stride=1, pad=1, **kw))
+        return v.lda, v.lda1, v.ldw, v.ldx0, v.ldx1, v.ldr, v.ldo
+    assert resolved(Cin=64) == (64, 0, 576, 0, 0, 128, 128)
+    assert resolved(Cin=64, epi=L.EPI_GEGLU) == (64, 0, 576, 0, 0, 128, 64)
+    assert resolved(Cin=192, a1=4, C0=128) == (128, 64, 1728, 0, 0, 128, 128)
+    assert resolved(Cin=64, fold=(5, None, 128, 128)) == (64, 0, 704, 128, 0, 128, 128)
+    assert resolved(Cin=64, fold=(5, 6, 64, 192)) == (64, 0, 768, 64, 128, 128, 128)
+    assert resolved(Cin=128, a1=4, C0=64, lda=72, lda1=80, ldw=2000, ldr=136, ldo=144, fold=(5, 6, 64, 192, 88, 96)) == (72, 80, 2000, 88, 96, 136, 144)
+    assert resolved(Cin=128, a1=4, C0=64, lda=72, lda1=80, ldw=2000, ldr=136, ldo=144, epi=L.EPI_GEGLU) == (72, 80, 2000, 0, 0, 136, 144)
+    v = O.igemm_view(O.igemm(1, 2, 3, B=2, H=8, W=8, Cin=64, Ho=4, Wo=4, N=128, taps=9, stride=2, pad=1, fold=(5, 6, 64, 192), residual=7))
+    assert (v.M, v.K, v.Kx, v.batch_z, v.c0, v.cx, v.cx0, v.n_out) == (32, 576, 768, 1, 64, 192, 64, 128)
+    assert (v.has_residual, v.has_ln_out, v.has_ln_in, v.has_a1, v.has_rowvec, v.has_fold, v.has_x1, v.has_trans) == (True, False, False, False, False, True, True, False)
+    assert v.fits_31bit and not O.igemm_view(O.igemm(1, 2, 3, B=1, H=1 << 12, W=1 << 12, Cin=64, Ho=1, Wo=1, N=8)).fits_31bit
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from marigold_amd import _lib
     monkeypatch.setattr(_lib, "_libs", {})
@@ -385,14 +467,14 @@ def test_full_size_programs_validate_without_gpu():
     # the three up-sampling convolutions (4/9 of their MACs) another 84.9 GF: 2001.5 GF executed per member and forward
     assert abs(per_fwd - 2001.5) < 3, per_fwd
     # the launch forms of round 5, as the engine routes them at full size
-    from marigold_amd import _lib as L
+    from marigold_amd import _lib as L, ops as O
     labelled = list(zip(prog.seq.ops, prog.seq.labels))
     fwd = labelled[prog.n_prologue_ops:prog.n_prologue_ops + prog.n_fwd_ops]
     folded = [op for op, lab in fwd if lab.endswith("conv2+conv_shortcut")]   # conv_shortcut as extra K of conv2 (implicit GEMM levels)
     # (round 6: at ten members the 96 x 96 level's norms are separate passes and its plain convolutions run on the hand-placed GEMM
     # tile - engine.fuse_norm_into_conv - so up_blocks.3's three shortcuts fold as well: 14 folded launches, no shortcut launch left)
-    assert len(folded) == 14 and all(op.kind == L.OP_IGEMM and op.p[12] and op.i[32] % 64 == 0 and op.i[7] == 9 for op in folded)
-    assert sum(bool(op.p[13]) for op in folded) == 12         # the up blocks' [hidden | skip] pairs, never concatenated
+    assert len(folded) == 14 and all(op.kind == L.OP_IGEMM and O.Raw(op).x0 and O.Raw(op).cx % 64 == 0 and O.Raw(op).taps == 9 for op in folded)
+    assert sum(bool(O.Raw(op).x1) for op in folded) == 12         # the up blocks' [hidden | skip] pairs, never concatenated
     assert [lab for _, lab in fwd if lab.endswith(".conv_shortcut")] == []
     assert any(op.kind == L.OP_GN_STATS and op.p[6] and op.i[9] > 0 for op, _ in fwd)      # a skip concat's statistics: one launch
     assert not any(lab.endswith((".stats0", ".stats1")) for _, lab in fwd)
@@ -777,16 +859,16 @@ def test_tuning_table_is_well_formed_and_applied():
               rowvec=a if parts[12] == "1" else None)
     op = O.igemm(a, a, a, **kw)
     assert tuning.key_of(op) == key
-    assert (tuning.apply(op).i[19], op.i[31]) == (variant, splits)
+    assert tuning.apply(op) is op and (O.Raw(op).variant, O.Raw(op).splits) == (variant, splits)
     op2 = O.igemm(a, a, a, variant=23, **kw)
-    assert (tuning.apply(op2).i[19], op2.i[31]) == (23, 0)
+    assert tuning.apply(op2) is op2 and (O.Raw(op2).variant, O.Raw(op2).splits) == (23, 0)
     # a folded launch has its own entries (more K than the plain convolution of the same shape)
     fkey, (fv, fs, *_r) = next((k, v) for k, v in db.items() if k.count(",") == 13 and int(int(k.split(",")[0]) ** 0.5) ** 2 == int(k.split(",")[0]))
     fp = fkey.split(",")
     HW, cx = int(int(fp[0]) ** 0.5), int(fp[13][1:])
     opf = O.igemm(a, a, a, B=1, H=HW, W=HW, Cin=int(fp[2]) // 9, Ho=HW, Wo=HW, N=int(fp[1]), taps=9, stride=1, pad=1, bias=a,
                   residual=a if fp[8] == "1" else None, rowvec=a if fp[12] == "1" else None, fold=(a, None, cx, cx))
-    assert tuning.key_of(opf) == fkey and (tuning.apply(opf).i[19], opf.i[31]) == (fv, fs)
+    assert tuning.key_of(opf) == fkey and tuning.apply(opf) is opf and (O.Raw(opf).variant, O.Raw(opf).splits) == (fv, fs)
 
 
 def test_folded_shortcut_and_stacked_time_projection_weights():

@@ -6,12 +6,12 @@ import re
 import pytest
 import torch
 
-from marigold_amd import _lib as L, tuning
+from marigold_amd import _lib as L, ops as O, tuning
 from tests import tuned_forms as TF
 
-# i[] fields that follow from B, H, W or the stride of the shape (0-2, 4, 5: the shape; 18: ldt = tokens rounded up to 64;
-# 29, 30: the address of the program's tickets - compared as set / not set)
-SHAPE_FIELDS = {0, 1, 2, 4, 5, 18, 29, 30}
+# integer fields that follow from B, H, W or the stride of the shape (ldt = tokens rounded up to 64; the address of the program's
+# tickets - compared as set / not set)
+SHAPE_FIELDS = {"b", "h", "w", "ho", "wo", "ldt", "tickets_lo", "tickets_hi"}
 
 
 def test_every_entry_belongs_to_exactly_one_class():
@@ -39,14 +39,15 @@ def test_rebuilt_op_has_the_entry_key():
     db = tuning.load()
     for c in TF.classes():
         small = TF.build(c, None, None, dummy=True).op
-        assert (small.i[19], small.i[31]) == (c.tile, c.splits)
+        assert (O.Raw(small).variant, O.Raw(small).splits) == (c.tile, c.splits)
         ks = tuning.key_of(small).split(",")
         for key in c.entries:
             op = TF.build(c, int(key.split(",")[0]), None, dummy=True).op
             assert tuning.key_of(op) == key, (c.id, key, tuning.key_of(op))
             assert ks[1:] == key.split(",")[1:], (c.id, key, ",".join(ks))
-            op.i[19] = op.i[31] = 0
-            assert (tuning.apply(op).i[19], op.i[31]) == (db[key][0], db[key][1])
+            r = O.Raw(op)
+            r.variant = r.splits = 0
+            assert tuning.apply(op) is op and (r.variant, r.splits) == (db[key][0], db[key][1])
 
 
 def test_reduced_launches_pass_their_kernels_contracts():
@@ -94,7 +95,7 @@ def test_classes_agree_with_the_production_programs():
     reached, reached_folded, wrong = set(), set(), []
     for op, lab, fold in _production_ops():
         key = tuning.key_of(op)
-        if key not in db or (op.i[19], op.i[31]) != (db[key][0], db[key][1]):
+        if key not in db or (O.Raw(op).variant, O.Raw(op).splits) != (db[key][0], db[key][1]):
             continue
         reached.add(key)
         if fold:
@@ -103,8 +104,10 @@ def test_classes_agree_with_the_production_programs():
         if c.id not in rebuilt:
             rebuilt[c.id] = TF.build(c, None, None, dummy=True).op
         mine = rebuilt[c.id]
-        di = [(k, op.i[k], mine.i[k]) for k in range(len(op.i)) if k not in SHAPE_FIELDS and op.i[k] != mine.i[k]]
-        di += [(k, "set", "not set") for k in (29, 30) if bool(op.i[k]) != bool(mine.i[k])]
+        rp, rm, names = O.Raw(op), O.Raw(mine), L.FIELDS[L.OP_IGEMM][1]["i"]
+        di = [(n, getattr(rp, n), getattr(rm, n)) for n in names if n not in SHAPE_FIELDS and getattr(rp, n) != getattr(rm, n)]
+        di += [(k, op.i[k], mine.i[k]) for k in range(len(names), len(op.i)) if op.i[k] != mine.i[k]]   # (the unnamed tail stays zero)
+        di += [("tickets", "set", "not set")] if bool(O.igemm_tickets(op)) != bool(O.igemm_tickets(mine)) else []
         dp = [(k, bool(op.p[k]), bool(mine.p[k])) for k in range(len(op.p)) if bool(op.p[k]) != bool(mine.p[k])]
         df = [(k, op.f[k], mine.f[k]) for k in range(3) if op.f[k] != mine.f[k]]
         if di or dp or df:

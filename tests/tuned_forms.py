@@ -234,7 +234,7 @@ def build(cls, M_small=None, device=None, dummy=False):
     if Cx:
         kw.update(fold=(t["x0"], t["x1"], lay["Cx0"], Cx))
     op = O.igemm(t["a"], t["w"], t["out"], **kw)
-    op.p[14] = t["ws"].data_ptr()      # Builder.add: the program's own split-K workspace
+    O.Raw(op).splitk_ws = t["ws"]      # Builder.add: the program's own split-K workspace
     return Built(cls, op, geom, lay, t, perm)
 
 

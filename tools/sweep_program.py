@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Program-driven tile sweep (run on the MI355X; tuning, not the product path): builds the real denoising / VAE-decode programs
 for the given ensemble sizes, takes every DISTINCT MG_OP_IGEMM launch of one UNet forward (real buffers, epilogues, folded
-LayerNorm, second sources ...), and times it under each candidate tile variant x split-K count (op i[19], i[31]).  Prints one
+LayerNorm, second sources ...), and times it under each candidate tile variant x split-K count (the op's ``variant`` and ``splits`` fields).  Prints one
 line per layer with the automatic choice's time and the best candidates, writes gpurun_out/sweep_program_E<e>.tsv.  The rules of
 mg_igemm_auto_variant / mg_igemm_auto_split are set from these tables (profiles/r5_sweep_program_*.tsv).
 
@@ -25,9 +25,9 @@ def clone(op, variant=None, splits=None):
     c = L.MgOp()
     ctypes.memmove(ctypes.addressof(c), ctypes.addressof(op), ctypes.sizeof(L.MgOp))
     if variant is not None:
-        c.i[19] = variant
+        O.Raw(c).variant = variant
     if splits is not None:
-        c.i[31] = splits
+        O.Raw(c).splits = splits
     return c
 
 
@@ -47,7 +47,9 @@ def time_op(op, iters, stream):
 
 
 def key_of(op):
-    return (op.kind,) + tuple(op.i[j] for j in range(36) if j not in (19, 31)) + tuple(bool(op.p[j]) for j in range(16))
+    """What makes two MG_OP_IGEMM launches the same layer: every integer field but the tile / split-K choice, and which pointers are set."""
+    r, names = O.Raw(op), L.FIELDS[L.OP_IGEMM][1]
+    return (op.kind,) + tuple(getattr(r, n) for n in names["i"] if n not in ("variant", "splits")) + tuple(bool(getattr(r, n)) for n in names["p"])
 
 
 def main():
@@ -92,10 +94,9 @@ def main():
                 seen[k][1] += 1
                 continue
             seen[k] = [label, 1]
-            B, H, W, Cin, Ho, Wo, N, taps = (op.i[j] for j in range(8))
-            Mrows, K = B * Ho * Wo, taps * Cin + (op.i[32] if op.p[12] else 0)
-            epi = op.i[12]
-            can_split = epi == L.EPI_BF16 and op.i[14] < 0 and op.i[15] <= 1 and not op.p[8] and not op.p[9]
+            v = O.igemm_view(op)
+            Mrows, N, K, taps, epi = v.M, v.n, v.Kx, v.taps, v.epi
+            can_split = epi == L.EPI_BF16 and not v.has_trans and v.batch_z == 1 and not v.has_ln_out and not v.has_ln_in
             op = clone(op, 0, 0)   # the heuristic's choice is the baseline (whatever table the engine applied)
             cands = [(v, sp) for v in [0] + variants for sp in ([0] + splits if can_split else [0])]
             samples = {c: [] for c in cands}
@@ -117,8 +118,8 @@ def main():
                 if bt < (1.0 - args.min_gain) * t_auto and (t_auto - bt) >= 1.0:
                     db[tuning.key_of(op)] = [bv, max(1, bs), round(t_auto, 1), round(bt, 1), f"E={E} {label}"]
             best = sorted(res.items(), key=lambda kv: kv[1])[:4]
-            flops = 2.0 * Mrows * N * K * max(1, op.i[15])
-            rows.append((label, Mrows, N, K, taps, epi, int(bool(op.p[5])), int(bool(op.p[8])), int(bool(op.p[9])), t_auto, best, res))
+            flops = 2.0 * Mrows * N * K * v.batch_z
+            rows.append((label, Mrows, N, K, taps, epi, int(v.has_residual), int(v.has_ln_out), int(v.has_ln_in), t_auto, best, res))
             print(f"E={E} {label[-52:]:52s} M={Mrows:6d} N={N:5d} K={K:6d} epi={epi} auto {t_auto:7.1f}us ({flops / t_auto / 1e6:6.0f} TF) | " +
                   "  ".join(f"v{v}/s{sp}:{t:6.1f}" for (v, sp), t in best), flush=True)
         with open(os.path.join(ROOT, "gpurun_out", f"sweep_program_E{E}.tsv"), "w") as f:
