@@ -248,7 +248,21 @@ enum mg_op_kind {
    *  p[0] pred f32 [n][3][H][W]  p[1] out uint8 [n][H][W][3] (HWC)  p[2] workspace f32 [n][MG_IID_VIS_PARTS] (may be NULL when no
    *  target is both linear and up to scale) ; i[0] n (<= 16)  i[1] H  i[2] W  i[3] bit t: target t is in linear space
    *  i[4] bit t: target t is up to scale */
-  MG_OP_IID_VIS = 35
+  MG_OP_IID_VIS = 35,
+  /* The two remaining ends of the device I/O boundary (csrc/resize.hip); they take free numbers below the last kind.  Their slots are
+   * named by the MG_RGB_PREP_* / MG_NORMALS_VIS_* enumerators below.
+   * RGB_PREP: the input stage of every pipeline (marigold/marigold_depth_pipeline.py:229-255: pil_to_tensor, resize_max_res,
+   *   `rgb / 255.0 * 2.0 - 1.0`, the cast to the pipeline's dtype) on the uint8 picture as uploaded: [Hin][Win][3] (PIL's layout, I_HWC)
+   *   or [3][Hin][Win] -> [3][Hout][Wout] in fp32 or the build's 16-bit operand type (I_OUT16).  Same size: one launch.  Sizes
+   *   differ: MG_OP_RESIZE's launches on the three planes with the uint8 rounding (bicubic: the clamp first) and the normalisation in
+   *   the last one's store - no uint8 intermediate.  The normalisation is torch's, rounding for rounding, in fp32: x / 255 (IEEE
+   *   division: the host kernel) or x * fp32(1 / 255) (I_RECIPROCAL: what torch's device kernel makes of a division by a scalar), then
+   *   * 2, then - 1.
+   * NORMALS_VIS: the normals picture (marigold/marigold_normals_pipeline.py:297-301), the counterpart of MG_OP_COLORIZE: fp32
+   *   [3][H][W] -> uint8 [H][W][3], out = uint8((clip(x, -1, 1) + 1) * 127.5) - the clip keeps NaN like numpy.clip, the sum and the
+   *   product are two fp32 roundings, the cast truncates; NaN -> 0 (MG_OP_IID_VIS's convention). */
+  MG_OP_RGB_PREP = 5,
+  MG_OP_NORMALS_VIS = 8
 };
 #define MG_IID_VIS_PARTS 128
 
@@ -272,7 +286,7 @@ typedef struct mg_op {
   int64_t l[4];
 } mg_op;
 
-/* Field names of the four kinds with many launch forms: MG_<KIND>_<array>_<NAME> is the index of that field in mg_op's i / f / p /
+/* Field names of the four kinds with many launch forms and of the I/O stages (MG_OP_RGB_PREP, MG_OP_NORMALS_VIS): MG_<KIND>_<array>_<NAME> is the index of that field in mg_op's i / f / p /
  * l array.  This is the one table of the wire format (the values are positions: they never change, new fields are appended);
  * marigold_amd/_lib.py mirrors it (tests/test_host.py compares the two) and marigold_amd/ops.py decodes an op by these names. */
 enum mg_igemm_i {
@@ -435,6 +449,30 @@ enum mg_flash64_p {
 };
 enum mg_flash64_l { MG_FLASH64_L_SQ = 0, MG_FLASH64_L_SK = 1, MG_FLASH64_L_SVT = 2, MG_FLASH64_L_SO = 3 };   /* batch strides of Q, K, Vt, O */
 
+enum mg_rgb_prep_i {
+  MG_RGB_PREP_I_HIN = 0,          /* source height */
+  MG_RGB_PREP_I_WIN = 1,          /* source width */
+  MG_RGB_PREP_I_HOUT = 2,         /* destination height */
+  MG_RGB_PREP_I_WOUT = 3,         /* destination width */
+  MG_RGB_PREP_I_MODE = 4,         /* when the sizes differ: 0 bilinear, 1 bicubic, 2 nearest-exact (MG_OP_RESIZE's modes) */
+  MG_RGB_PREP_I_HWC = 5,          /* 1 = the source is [Hin][Win][3] (3-byte pixels), 0 = [3][Hin][Win] planes */
+  MG_RGB_PREP_I_OUT16 = 6,        /* 1 = the destination holds the build's 16-bit operand type (bf16 / fp16), 0 = fp32 */
+  MG_RGB_PREP_I_RECIPROCAL = 7    /* 1 = x * fp32(1 / 255) in place of the IEEE division x / 255 */
+};
+enum mg_rgb_prep_p {
+  MG_RGB_PREP_P_SRC = 0,          /* uint8, any alignment (four pixels per lane when Win % 4 == 0 and it is 4-byte aligned) */
+  MG_RGB_PREP_P_DST = 1,          /* [3][Hout][Wout] */
+  MG_RGB_PREP_P_TMP = 2           /* f32 [3][Hin][Wout] | NULL: needed by bilinear / bicubic when both sizes change */
+};
+enum mg_normals_vis_i {
+  MG_NORMALS_VIS_I_H = 0,
+  MG_NORMALS_VIS_I_W = 1
+};
+enum mg_normals_vis_p {
+  MG_NORMALS_VIS_P_PRED = 0,      /* f32 [3][H][W], 4-byte aligned (four pixels per lane when H W % 4 == 0 and it is 16-byte aligned) */
+  MG_NORMALS_VIS_P_OUT = 1        /* uint8 [H][W][3] */
+};
+
 typedef struct mg_program mg_program;
 
 /* Library / device */
@@ -543,6 +581,15 @@ enum { MG_IID_GAMMA_NONE = 0, MG_IID_GAMMA_2_2 = 1, MG_IID_GAMMA_INV_2_2 = 2, MG
 enum { MG_IID_PSNR = 1, MG_IID_SSIM = 2 };
 int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W, int up_to_scale, int gamma_mode,
                 int metrics_mask, double* out8, void* workspace, void* stream);
+
+/* The device I/O boundary on raw pointers (csrc/resize.hip): MG_OP_RGB_PREP and MG_OP_NORMALS_VIS as calls; neither synchronises.
+ *  mg_rgb_prepare: src uint8 [Hin][Win][3] (hwc != 0) or [3][Hin][Win] -> dst [3][Hout][Wout], fp32 or (out16 != 0) the build's 16-bit
+ *  operand type; mode 0 bilinear / 1 bicubic / 2 nearest-exact when the sizes differ; reciprocal: see MG_RGB_PREP_I_RECIPROCAL;
+ *  tmp: fp32 [3][Hin][Wout], needed by modes 0 and 1 when both sizes change.
+ *  mg_normals_visualize: pred fp32 [3][H][W] -> out uint8 [H][W][3]. */
+int mg_rgb_prepare(const uint8_t* src, int hwc, int Hin, int Win, void* dst, int out16, int Hout, int Wout, int mode, int reciprocal,
+                   float* tmp_or_null, void* stream);
+int mg_normals_visualize(const float* pred, int H, int W, uint8_t* out_hwc, void* stream);
 
 /* Host arithmetic of ensemble_depth's alignment objective (marigold/util/ensemble.py:129-152, as the closed form of
  * marigold_amd/ensemble.py): pairwise-RMSE cost of the aligned members and its gradient w.r.t. scales s[E] / shifts t[E],

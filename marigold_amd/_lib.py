@@ -31,6 +31,7 @@ EVAL_ALIGN = {None: 0, "least_square": 1, "least_square_disparity": 2}   # MG_EV
 OP_MEMSET, OP_COPY = 30, 31
 OP_IIDSCORE_PREP, OP_IIDSCORE_PSNR, OP_IIDSCORE_SSIM = 32, 33, 34
 OP_IID_VIS = 35
+OP_RGB_PREP, OP_NORMALS_VIS = 5, 8   # the I/O stages: free numbers below the last kind
 IID_VIS_PARTS = 128   # MG_IID_VIS_PARTS
 IID_GAMMA = {None: 0, 2.2: 1, 1.0 / 2.2: 2, (2.2, 1.0 / 2.2): 3}   # MG_IID_GAMMA_*
 IID_METRICS = {"psnr": 1, "ssim": 2}   # MG_IID_*
@@ -82,6 +83,17 @@ FIELDS = {
         l=("sq", "sk", "svt", "so"))),
 }
 
+# The same table for the two I/O stages (MG_RGB_PREP_* / MG_NORMALS_VIS_* in the header; tests/test_io_stages_host.py compares them).
+# Kept beside FIELDS, which stays the set of the four many-form kinds.
+IO_FIELDS = {
+    OP_RGB_PREP: ("RGB_PREP", dict(
+        i=("hin", "win", "hout", "wout", "mode", "hwc", "out16", "reciprocal"),
+        p=("src", "dst", "tmp"))),
+    OP_NORMALS_VIS: ("NORMALS_VIS", dict(
+        i=("h", "w"),
+        p=("pred", "out"))),
+}
+
 OP_NAMES = {v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}
 
 EXPORTS = [
@@ -92,6 +104,7 @@ EXPORTS = [
     "mg_event_elapsed_ms", "mg_event_destroy", "mg_clock_probe", "mg_debug_read_workspace",
     "mg_model_load", "mg_model_destroy", "mg_model_info", "mg_model_device_bytes", "mg_model_validate", "mg_model_vae_encode",
     "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals", "mg_eval_iid",
+    "mg_rgb_prepare", "mg_normals_visualize",
 ]
 
 
@@ -171,6 +184,8 @@ def load(f16=False):
     lib.mg_eval_depth.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3
     lib.mg_eval_normals.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4
     lib.mg_eval_iid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
+    lib.mg_rgb_prepare.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
+    lib.mg_normals_visualize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

@@ -9,6 +9,8 @@
 // horizontal pass first (into an fp32 temporary), then vertical; uint8 inputs are computed in float,
 // rounded half-to-even (clamped to [0, 255] for bicubic) and cast back.  nearest-exact:
 // src = floor((i + 0.5) * scale).
+#include <string.h>
+
 #include "common.h"
 
 namespace {
@@ -22,19 +24,58 @@ __device__ __forceinline__ float aa_filter(float x, int bicubic) {
   return 0.0f;
 }
 
-__device__ __forceinline__ float ld(const uint8_t* p, long long i) { return (float)p[i]; }
-__device__ __forceinline__ float ld(const float* p, long long i) { return p[i]; }
-__device__ __forceinline__ void st(float* p, long long i, float v, int) { p[i] = v; }
-__device__ __forceinline__ void st(uint8_t* p, long long i, float v, int bicubic) {
+// The byte a resampled uint8 image holds, as a float: round half to even like torch.round(), bicubic clamped to [0, 255] first.
+__device__ __forceinline__ float u8_round(float v, int bicubic) {
   if (bicubic) v = fminf(fmaxf(v, 0.0f), 255.0f);
-  p[i] = (uint8_t)rintf(v);  // round half to even, like torch.round()
+  return (float)(uint8_t)rintf(v);
 }
+
+// torch's `x / 255.0 * 2.0 - 1.0` on a byte value, in fp32 with torch's roundings (the file is built without FMA contraction, and the
+// intrinsics keep the compiler from re-associating): the host kernel divides (IEEE), the device kernel of a tensor divided by a
+// scalar multiplies by fp32(1 / 255) - 111 of the 256 byte values end up one ulp apart, so the caller says which chain it replaces.
+__device__ __forceinline__ float rgb_norm(float x, int reciprocal) {
+  const float q = reciprocal ? __fmul_rn(x, 1.0f / 255.0f) : __fdiv_rn(x, 255.0f);
+  return __fsub_rn(__fmul_rn(q, 2.0f), 1.0f);
+}
+
+// Where a pass reads and writes; `i` is always the index into [planes][rows][cols].
+template <typename T>
+struct plane_src {   // planes as MG_OP_RESIZE has them
+  const T* __restrict__ p;
+  __device__ __forceinline__ float ld(long long i) const { return (float)p[i]; }
+};
+struct hwc_src {     // the same three planes read from 3-byte pixels (PIL's layout); hw = rows * cols of the source
+  const uint8_t* __restrict__ p;
+  long long hw;
+  __device__ __forceinline__ float ld(long long i) const {
+    const int c = (i >= hw) + (i >= 2 * hw);
+    return (float)p[(i - c * hw) * 3 + c];
+  }
+};
+template <typename T>
+struct plane_dst {
+  T* __restrict__ p;
+  __device__ __forceinline__ void st(long long i, float v, int bicubic) const {
+    if constexpr (std::is_same_v<T, uint8_t>) p[i] = (uint8_t)u8_round(v, bicubic);
+    else p[i] = v;
+  }
+};
+template <typename T>
+struct norm_dst {    // MG_OP_RGB_PREP's last pass: the uint8 result normalised in the store; T = float | bf16_t (the operand type)
+  T* __restrict__ p;
+  int reciprocal;
+  __device__ __forceinline__ void st(long long i, float v, int bicubic) const {
+    const float y = rgb_norm(u8_round(v, bicubic), reciprocal);
+    if constexpr (std::is_same_v<T, float>) p[i] = y;
+    else p[i] = f2bf(y);
+  }
+};
 
 // One output element per thread.  The resampled axis has `in_len` -> `out_len` elements with element
 // stride `s_axis`; the other in-plane axis has `other` elements with stride `s_other`; planes are
 // contiguous (`plane_in` / `plane_out` elements).  Output is [planes][out rows][out cols] row-major.
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void resize_aa_pass_kernel(const TI* __restrict__ src, TO* __restrict__ dst,
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void resize_aa_pass_kernel(const SRC src, const DST dst,
                                                              long long total, int in_len, int out_len, int other,
                                                              int horizontal, int bicubic, float scale) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -65,14 +106,14 @@ __global__ __launch_bounds__(256) void resize_aa_pass_kernel(const TI* __restric
     w = total_w != 0.0f ? w / total_w : 0.0f;
     const long long sidx = horizontal ? base + (long long)o * in_len + (j + xmin)
                                       : base + (long long)(j + xmin) * other + o;
-    const float v = ld(src, sidx) * w;
+    const float v = src.ld(sidx) * w;
     t = j == 0 ? v : t + v;
   }
-  st(dst, idx, t, bicubic);
+  dst.st(idx, t, bicubic);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void resize_nearest_exact_kernel(const T* __restrict__ src, T* __restrict__ dst,
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void resize_nearest_exact_kernel(const SRC src, const DST dst,
                                                                    long long total, int Hin, int Win, int Hout,
                                                                    int Wout, float sy, float sx) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -82,15 +123,38 @@ __global__ __launch_bounds__(256) void resize_nearest_exact_kernel(const T* __re
   int iy = (int)floorf(((float)y + 0.5f) * sy), ix = (int)floorf(((float)x + 0.5f) * sx);
   iy = iy < Hin - 1 ? iy : Hin - 1;
   ix = ix < Win - 1 ? ix : Win - 1;
-  dst[idx] = src[(plane * Hin + iy) * Win + ix];
+  dst.st(idx, src.ld((plane * Hin + iy) * Win + ix), 0);   // (a byte or an fp32 value passes through ld / st unchanged)
 }
 
-template <typename TI, typename TO>
-void launch_pass(const void* src, void* dst, long long total, int in_len, int out_len, int other, int horizontal,
+template <typename SRC, typename DST>
+void launch_pass(const SRC src, const DST dst, long long total, int in_len, int out_len, int other, int horizontal,
                  int bicubic, hipStream_t s) {
   const float scale = (float)in_len / (float)out_len;
-  MG_LAUNCH((resize_aa_pass_kernel<TI, TO>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const TI*)src,
-            (TO*)dst, total, in_len, out_len, other, horizontal, bicubic, scale);
+  MG_LAUNCH((resize_aa_pass_kernel<SRC, DST>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, total, in_len,
+            out_len, other, horizontal, bicubic, scale);
+}
+
+// The resample of `planes` [Hin][Win] planes to [Hout][Wout] (sizes differ): nearest-exact in one launch, bilinear / bicubic
+// horizontal first (rows = Hin, into the fp32 temporary), then vertical on the result - torch's order; one pass when one axis changes.
+template <typename SRC, typename DST>
+void launch_resample(const SRC src, const DST dst, float* tmp, long long planes, int Hin, int Win, int Hout, int Wout, int mode,
+                     hipStream_t s) {
+  if (mode == 2) {
+    const long long total = planes * Hout * Wout;
+    const float sy = (float)Hin / (float)Hout, sx = (float)Win / (float)Wout;
+    MG_LAUNCH((resize_nearest_exact_kernel<SRC, DST>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, total, Hin, Win,
+              Hout, Wout, sy, sx);
+    return;
+  }
+  const int bicubic = mode == 1;
+  if (Win != Wout && Hin != Hout) {
+    launch_pass(src, plane_dst<float>{tmp}, planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
+    launch_pass(plane_src<float>{tmp}, dst, planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
+  } else if (Win != Wout) {
+    launch_pass(src, dst, planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
+  } else {
+    launch_pass(src, dst, planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
+  }
 }
 
 }  // namespace
@@ -227,8 +291,140 @@ static int launch_iid_vis(const mg_op* op, hipStream_t s) {
   return 0;
 }
 
+// The input stage of every pipeline (marigold/marigold_depth_pipeline.py:229-255: pil_to_tensor, resize_max_res, `rgb / 255.0 * 2.0 -
+// 1.0`, the cast to the pipeline's dtype) on the uint8 picture as PIL holds it (HWC) or as a [3][H][W] tensor.  Same size: the
+// kernel below; sizes differ: the resampling passes above with the normalisation in the last pass's store (launch_rgb_prep).
+struct u32x3 { unsigned x, y, z; };   // 12 bytes, 4-byte aligned: four HWC pixels
+
+template <typename T>
+__device__ __forceinline__ void rgb_prep_store4(T* __restrict__ p, long long q, float a, float b, float c, float d) {
+  if constexpr (std::is_same_v<T, float>) ((float4*)p)[q] = make_float4(a, b, c, d);
+  else ((uint2*)p)[q] = make_uint2(pack2bf(a, b), pack2bf(c, d));
+}
+
+// vec: a lane owns four neighbouring pixels - HWC: one 12-byte load, CHW: one 4-byte load per plane - and writes one vector per
+// plane (16 bytes of fp32, 8 bytes of the operand type); otherwise one pixel per lane.
+template <typename T>
+__global__ __launch_bounds__(IV_THREADS) void rgb_prep_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, long long HW, int hwc,
+                                                              int reciprocal, int vec) {
+  const long long first = (long long)blockIdx.x * IV_THREADS + threadIdx.x, step = (long long)gridDim.x * IV_THREADS;
+  if (vec) {   // W % 4 == 0 (so HW % 4 == 0: every plane starts on a vector boundary), src 4-byte and dst vector aligned
+    for (long long q = first; q < HW / 4; q += step) {
+      unsigned r, g, b;   // byte k of each: channel value of pixel 4 q + k
+      if (hwc) {
+        const u32x3 w = ((const u32x3*)src)[q];   // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+        r = (w.x & 0xffu) | (w.x >> 24) << 8 | ((w.y >> 16) & 0xffu) << 16 | ((w.z >> 8) & 0xffu) << 24;
+        g = ((w.x >> 8) & 0xffu) | (w.y & 0xffu) << 8 | (w.y >> 24) << 16 | ((w.z >> 16) & 0xffu) << 24;
+        b = ((w.x >> 16) & 0xffu) | ((w.y >> 8) & 0xffu) << 8 | (w.z & 0xffu) << 16 | (w.z >> 24) << 24;
+      } else {
+        const unsigned* __restrict__ s4 = (const unsigned*)src;
+        r = s4[q]; g = s4[HW / 4 + q]; b = s4[HW / 2 + q];
+      }
+      const unsigned ch[3] = {r, g, b};
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        rgb_prep_store4(dst + c * HW, q, rgb_norm((float)(ch[c] & 0xffu), reciprocal), rgb_norm((float)((ch[c] >> 8) & 0xffu), reciprocal),
+                        rgb_norm((float)((ch[c] >> 16) & 0xffu), reciprocal), rgb_norm((float)(ch[c] >> 24), reciprocal));
+    }
+  } else {
+    for (long long i = first; i < HW; i += step) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float y = rgb_norm((float)(hwc ? src[3 * i + c] : src[c * HW + i]), reciprocal);
+        if constexpr (std::is_same_v<T, float>) dst[c * HW + i] = y;
+        else dst[c * HW + i] = f2bf(y);
+      }
+    }
+  }
+}
+
+static int launch_rgb_prep(const mg_op* op, hipStream_t s) {
+  const int Hin = op->i[MG_RGB_PREP_I_HIN], Win = op->i[MG_RGB_PREP_I_WIN], Hout = op->i[MG_RGB_PREP_I_HOUT], Wout = op->i[MG_RGB_PREP_I_WOUT];
+  const int mode = op->i[MG_RGB_PREP_I_MODE], hwc = op->i[MG_RGB_PREP_I_HWC] != 0, out16 = op->i[MG_RGB_PREP_I_OUT16] != 0;
+  const int reciprocal = op->i[MG_RGB_PREP_I_RECIPROCAL] != 0;
+  const uint8_t* src = (const uint8_t*)op->p[MG_RGB_PREP_P_SRC];
+  void* dst = op->p[MG_RGB_PREP_P_DST];
+  float* tmp = (float*)op->p[MG_RGB_PREP_P_TMP];
+  MG_REQUIRE(Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && (long long)Hin * Win <= (1ll << 30) && (long long)Hout * Wout <= (1ll << 30),
+             "rgb_prep: bad size %d x %d -> %d x %d", Hin, Win, Hout, Wout);
+  MG_REQUIRE(mode >= 0 && mode <= 2, "rgb_prep: mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
+  MG_REQUIRE(src && dst, "rgb_prep: null pointer");
+  MG_REQUIRE((uintptr_t)dst % (out16 ? 2 : 4) == 0, "rgb_prep: the destination must be aligned to its element");
+  if (Hin == Hout && Win == Wout) {
+    const long long HW = (long long)Hin * Win;
+    const int vec = Win % 4 == 0 && (uintptr_t)src % 4 == 0 && (uintptr_t)dst % (out16 ? 8 : 16) == 0;
+    const long long work = vec ? HW / 4 : HW;
+    const dim3 grid((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)2048));
+    if (out16) MG_LAUNCH(rgb_prep_kernel<bf16_t>, grid, dim3(IV_THREADS), 0, s, src, (bf16_t*)dst, HW, hwc, reciprocal, vec);
+    else MG_LAUNCH(rgb_prep_kernel<float>, grid, dim3(IV_THREADS), 0, s, src, (float*)dst, HW, hwc, reciprocal, vec);
+  } else {
+    MG_REQUIRE(mode == 2 || Hin == Hout || Win == Wout || (tmp && (uintptr_t)tmp % 4 == 0),
+               "rgb_prep: fp32 temporary [3][Hin][Wout] missing or unaligned");
+    const hwc_src sh{src, (long long)Hin * Win};
+    const plane_src<uint8_t> sp{src};
+    const norm_dst<bf16_t> d16{(bf16_t*)dst, reciprocal};
+    const norm_dst<float> d32{(float*)dst, reciprocal};
+    if (hwc && out16) launch_resample(sh, d16, tmp, 3, Hin, Win, Hout, Wout, mode, s);
+    else if (hwc) launch_resample(sh, d32, tmp, 3, Hin, Win, Hout, Wout, mode, s);
+    else if (out16) launch_resample(sp, d16, tmp, 3, Hin, Win, Hout, Wout, mode, s);
+    else launch_resample(sp, d32, tmp, 3, Hin, Win, Hout, Wout, mode, s);
+  }
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// The normals picture (marigold/marigold_normals_pipeline.py:297-301): clip(-1, 1) as numpy.clip does (NaN stays), (x + 1) * 127.5 in
+// fp32 with two roundings, astype(uint8) = truncation to int32 and its low 8 bits; NaN gives 0 (MG_OP_IID_VIS's convention for
+// x86-64).  After the clip the product lies in [0, 255], so nothing else is out of range.
+__device__ __forceinline__ unsigned nv_byte(float x) {
+  x = clip_keep_nan(x, -1.0f, 1.0f);
+  x = __fmul_rn(__fadd_rn(x, 1.0f), 127.5f);
+  return (unsigned)(x == x ? (int)x : 0) & 0xffu;
+}
+
+// vec: a lane owns four neighbouring pixels - three 16-byte loads, one per plane, and 12 contiguous output bytes; otherwise one pixel.
+__global__ __launch_bounds__(IV_THREADS) void normals_vis_kernel(const float* __restrict__ x, uint8_t* __restrict__ o, long long HW, int vec) {
+  const long long first = (long long)blockIdx.x * IV_THREADS + threadIdx.x, step = (long long)gridDim.x * IV_THREADS;
+  if (vec) {   // HW % 4 == 0, x 16-byte and o 4-byte aligned
+    const float4 *__restrict__ r4 = (const float4*)x, *__restrict__ g4 = (const float4*)(x + HW), *__restrict__ b4 = (const float4*)(x + 2 * HW);
+    u32x3* __restrict__ o12 = (u32x3*)o;
+    for (long long q = first; q < HW / 4; q += step) {
+      const float4 r = r4[q], g = g4[q], b = b4[q];
+      u32x3 w;
+      w.x = nv_byte(r.x) | nv_byte(g.x) << 8 | nv_byte(b.x) << 16 | nv_byte(r.y) << 24;
+      w.y = nv_byte(g.y) | nv_byte(b.y) << 8 | nv_byte(r.z) << 16 | nv_byte(g.z) << 24;
+      w.z = nv_byte(b.z) | nv_byte(r.w) << 8 | nv_byte(g.w) << 16 | nv_byte(b.w) << 24;
+      o12[q] = w;
+    }
+  } else {
+    for (long long i = first; i < HW; i += step) {
+      o[3 * i + 0] = (uint8_t)nv_byte(x[i]);
+      o[3 * i + 1] = (uint8_t)nv_byte(x[HW + i]);
+      o[3 * i + 2] = (uint8_t)nv_byte(x[2 * HW + i]);
+    }
+  }
+}
+
+static int launch_normals_vis(const mg_op* op, hipStream_t s) {
+  const int H = op->i[MG_NORMALS_VIS_I_H], W = op->i[MG_NORMALS_VIS_I_W];
+  const float* pred = (const float*)op->p[MG_NORMALS_VIS_P_PRED];
+  uint8_t* out = (uint8_t*)op->p[MG_NORMALS_VIS_P_OUT];
+  MG_REQUIRE(H > 0 && W > 0 && (long long)H * W <= (1ll << 30), "normals_vis: bad size %d x %d", H, W);
+  MG_REQUIRE(pred && out, "normals_vis: null pointer");
+  MG_REQUIRE((uintptr_t)pred % 4 == 0, "normals_vis: the prediction must be 4-byte aligned");
+  const long long HW = (long long)H * W;
+  const int vec = HW % 4 == 0 && (uintptr_t)pred % 16 == 0 && (uintptr_t)out % 4 == 0;
+  const long long work = vec ? HW / 4 : HW;
+  MG_LAUNCH(normals_vis_kernel, dim3((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)2048)), dim3(IV_THREADS), 0, s, pred, out,
+            HW, vec);
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int mg_launch_resize(const mg_op* op, hipStream_t s) {
   if (op->kind == MG_OP_IID_VIS) return launch_iid_vis(op, s);
+  if (op->kind == MG_OP_RGB_PREP) return launch_rgb_prep(op, s);
+  if (op->kind == MG_OP_NORMALS_VIS) return launch_normals_vis(op, s);
   if (op->kind == MG_OP_COLORIZE) {
     const long long n = op->l[0];
     MG_REQUIRE(n > 0 && op->p[0] && op->p[1] && op->p[2], "colorize: null pointer / empty map");
@@ -244,34 +440,37 @@ int mg_launch_resize(const mg_op* op, hipStream_t s) {
   MG_REQUIRE(planes > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, "resize: empty image");
   MG_REQUIRE(mode >= 0 && mode <= 2, "resize: mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
   MG_REQUIRE(op->p[0] && op->p[1], "resize: null pointer");
-  if (mode == 2) {
-    const long long total = planes * Hout * Wout;
-    const float sy = (float)Hin / (float)Hout, sx = (float)Win / (float)Wout;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (u8) MG_LAUNCH(resize_nearest_exact_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)op->p[0],
-                      (uint8_t*)op->p[1], total, Hin, Win, Hout, Wout, sy, sx);
-    else MG_LAUNCH(resize_nearest_exact_kernel<float>, grid, dim3(256), 0, s, (const float*)op->p[0],
-                   (float*)op->p[1], total, Hin, Win, Hout, Wout, sy, sx);
-  } else {
-    const int bicubic = mode == 1;
-    const bool do_h = Win != Wout, do_v = Hin != Hout;
-    MG_REQUIRE(!(do_h && do_v) || op->p[2], "resize: fp32 temporary [planes][Hin][Wout] missing");
-    // horizontal first (rows = Hin), then vertical on the result - torch's order
-    if (do_h && do_v) {
-      if (u8) launch_pass<uint8_t, float>(op->p[0], op->p[2], planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
-      else launch_pass<float, float>(op->p[0], op->p[2], planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
-      if (u8) launch_pass<float, uint8_t>(op->p[2], op->p[1], planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
-      else launch_pass<float, float>(op->p[2], op->p[1], planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
-    } else if (do_h) {
-      if (u8) launch_pass<uint8_t, uint8_t>(op->p[0], op->p[1], planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
-      else launch_pass<float, float>(op->p[0], op->p[1], planes * Hin * Wout, Win, Wout, Hin, 1, bicubic, s);
-    } else if (do_v) {
-      if (u8) launch_pass<uint8_t, uint8_t>(op->p[0], op->p[1], planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
-      else launch_pass<float, float>(op->p[0], op->p[1], planes * Hout * Wout, Hin, Hout, Wout, 0, bicubic, s);
-    } else {
-      MG_REQUIRE(false, "resize: sizes are equal (the caller returns the input unchanged)");
-    }
-  }
+  MG_REQUIRE(mode == 2 || Win != Wout || Hin != Hout, "resize: sizes are equal (the caller returns the input unchanged)");
+  MG_REQUIRE(mode == 2 || !(Win != Wout && Hin != Hout) || op->p[2], "resize: fp32 temporary [planes][Hin][Wout] missing");
+  if (u8) launch_resample(plane_src<uint8_t>{(const uint8_t*)op->p[0]}, plane_dst<uint8_t>{(uint8_t*)op->p[1]}, (float*)op->p[2], planes,
+                          Hin, Win, Hout, Wout, mode, s);
+  else launch_resample(plane_src<float>{(const float*)op->p[0]}, plane_dst<float>{(float*)op->p[1]}, (float*)op->p[2], planes, Hin, Win,
+                       Hout, Wout, mode, s);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+extern "C" {
+
+int mg_rgb_prepare(const uint8_t* src, int hwc, int Hin, int Win, void* dst, int out16, int Hout, int Wout, int mode, int reciprocal,
+                   float* tmp_or_null, void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_RGB_PREP;
+  op.p[MG_RGB_PREP_P_SRC] = (void*)src; op.p[MG_RGB_PREP_P_DST] = dst; op.p[MG_RGB_PREP_P_TMP] = tmp_or_null;
+  op.i[MG_RGB_PREP_I_HIN] = Hin; op.i[MG_RGB_PREP_I_WIN] = Win; op.i[MG_RGB_PREP_I_HOUT] = Hout; op.i[MG_RGB_PREP_I_WOUT] = Wout;
+  op.i[MG_RGB_PREP_I_MODE] = mode; op.i[MG_RGB_PREP_I_HWC] = hwc != 0; op.i[MG_RGB_PREP_I_OUT16] = out16 != 0;
+  op.i[MG_RGB_PREP_I_RECIPROCAL] = reciprocal != 0;
+  return launch_rgb_prep(&op, (hipStream_t)stream);
+}
+
+int mg_normals_visualize(const float* pred, int H, int W, uint8_t* out_hwc, void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_NORMALS_VIS;
+  op.p[MG_NORMALS_VIS_P_PRED] = (void*)pred; op.p[MG_NORMALS_VIS_P_OUT] = out_hwc;
+  op.i[MG_NORMALS_VIS_I_H] = H; op.i[MG_NORMALS_VIS_I_W] = W;
+  return launch_normals_vis(&op, (hipStream_t)stream);
+}
+
+}  // extern "C"

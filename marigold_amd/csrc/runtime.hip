@@ -68,7 +68,9 @@ static int dispatch(const mg_op* op, hipStream_t s) {
     case MG_OP_ENS_NORMALS: return mg_launch_ensemble(op, s);
     case MG_OP_RESIZE:
     case MG_OP_COLORIZE:
-    case MG_OP_IID_VIS: return mg_launch_resize(op, s);
+    case MG_OP_IID_VIS:
+    case MG_OP_RGB_PREP:
+    case MG_OP_NORMALS_VIS: return mg_launch_resize(op, s);
     case MG_OP_EVAL_DEPTH_LS:
     case MG_OP_EVAL_DEPTH_METRICS:
     case MG_OP_EVAL_NORMALS:

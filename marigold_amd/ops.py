@@ -40,12 +40,13 @@ def make_op(kind, i=(), f=(), p=(), l=()):
 # --------------------------------------------------------------------------- named fields
 
 _TO_SLOT = dict(i=int, f=float, p=_ptr, l=int)
-_WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in L.FIELDS.items()}
-assert all(len(w) == sum(len(names) for names in L.FIELDS[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
+_TABLES = {**L.FIELDS, **L.IO_FIELDS}
+_WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in _TABLES.items()}
+assert all(len(w) == sum(len(names) for names in _TABLES[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
 
 
 class Raw:
-    """The fields of an op of one of the ``L.FIELDS`` kinds by name, as stored: ``Raw(op).ldw`` reads and writes the op's MG_IGEMM_I_LDW slot."""
+    """The fields of an op of one of the ``L.FIELDS`` / ``L.IO_FIELDS`` kinds by name, as stored: ``Raw(op).ldw`` reads and writes the op's MG_IGEMM_I_LDW slot."""
 
     def __init__(self, op):
         object.__setattr__(self, "op", op)
@@ -63,7 +64,7 @@ class Raw:
 
 
 def build_op(kind, **fields):
-    """An op of one of the ``L.FIELDS`` kinds from its fields by name; what is not named stays zero / NULL."""
+    """An op of one of the ``L.FIELDS`` / ``L.IO_FIELDS`` kinds from its fields by name; what is not named stays zero / NULL."""
     op = MgOp()
     op.kind = kind
     raw = Raw(op)
@@ -345,6 +346,23 @@ def iid_vis(pred, out, ws, *, n, H, W, linear, up_to_scale):
         raise ValueError(f"iid_vis: {n} targets, {len(linear)} linear and {len(up_to_scale)} up_to_scale flags")
     linear_bits, scale_bits = (sum(1 << t for t, v in enumerate(flags) if v) for flags in (linear, up_to_scale))
     return make_op(L.OP_IID_VIS, i=[n, H, W, linear_bits, scale_bits], p=[pred, out, ws])
+
+
+RESIZE_MODES = {"bilinear": 0, "bicubic": 1, "nearest-exact": 2}   # MG_OP_RESIZE's and MG_OP_RGB_PREP's `mode`
+
+
+def rgb_prep(src, dst, tmp=None, *, Hin, Win, Hout=None, Wout=None, mode=0, hwc=True, out16=False, reciprocal=False):
+    """The pipelines' input stage (MG_OP_RGB_PREP): uint8 ``src`` [Hin,Win,3] (``hwc``) or [3,Hin,Win] -> ``dst`` [3,Hout,Wout] =
+    ``src / 255.0 * 2.0 - 1.0`` in fp32 or (``out16``) the library's 16-bit operand type, resampled first when the sizes differ
+    (``mode``: a key of RESIZE_MODES or its number; ``tmp``: fp32 [3,Hin,Wout] when bilinear / bicubic change both sizes).
+    ``reciprocal``: multiply by fp32(1 / 255) as torch's device kernel does, in place of the host kernel's IEEE division."""
+    return build_op(L.OP_RGB_PREP, hin=Hin, win=Win, hout=Hin if Hout is None else Hout, wout=Win if Wout is None else Wout,
+                    mode=RESIZE_MODES.get(mode, mode), hwc=bool(hwc), out16=bool(out16), reciprocal=bool(reciprocal), src=src, dst=dst, tmp=tmp)
+
+
+def normals_vis(pred, out, *, H, W):
+    """The normals picture (MG_OP_NORMALS_VIS): fp32 ``pred`` [3,H,W] -> uint8 ``out`` [H,W,3]."""
+    return build_op(L.OP_NORMALS_VIS, h=H, w=W, pred=pred, out=out)
 
 
 def eval_fit_width(H, W, max_res):

@@ -14,7 +14,7 @@ CLASS = {
     L.OP_SOFTMAX_ROWS: "softmax",
     L.OP_SCHED_STEP: "scheduler_step", L.OP_LINEAR_SMALL_M: "time_embedding",
     L.OP_LATENT_1X1: "boundary_conv", L.OP_POST_NCHW: "boundary_conv", L.OP_CONV3X3_HEAD: "boundary_conv", L.OP_IM2COL_SMALL: "boundary_conv", L.OP_ENS_DEPTH_STATS: "ensemble", L.OP_ENS_DEPTH_MEDIAN: "ensemble",
-    L.OP_ENS_DEPTH_NORM: "ensemble", L.OP_ENS_NORMALS: "ensemble", L.OP_RESIZE: "resize", L.OP_COLORIZE: "resize", L.OP_IID_VIS: "resize", L.OP_MEMSET: "memops", L.OP_COPY: "memops",
+    L.OP_ENS_DEPTH_NORM: "ensemble", L.OP_ENS_NORMALS: "ensemble", L.OP_RESIZE: "resize", L.OP_COLORIZE: "resize", L.OP_IID_VIS: "resize", L.OP_RGB_PREP: "resize", L.OP_NORMALS_VIS: "resize", L.OP_MEMSET: "memops", L.OP_COPY: "memops",
 }
 BOUND = {"igemm_mfma": "mfma", "rowgemm_mfma": "mfma", "conv3x3_patch": "mfma", "flash_attn64": "mfma", "flash_attn512": "mfma"}   # everything else is HBM-bound streaming
 
@@ -102,6 +102,13 @@ def op_cost(op):
     elif k == L.OP_IID_VIS:   # the fp32 planes read once (twice by the targets that take a maximum first), one byte written per element
         n3 = 3 * i[1] * i[2]
         byts = n3 * (5 * i[0] + 4 * bin(i[3] & i[4]).count("1"))
+    elif k == L.OP_RGB_PREP:   # one byte read per source element, one fp32 / 16-bit value written; two passes: the fp32 temporary once each way
+        v = O.Raw(op)
+        byts = 3 * (v.hin * v.win + v.hout * v.wout * (2 if v.out16 else 4))
+        if v.mode != 2 and v.hin != v.hout and v.win != v.wout:
+            byts += 2 * 3 * v.hin * v.wout * 4
+    elif k == L.OP_NORMALS_VIS:
+        byts = 3 * i[0] * i[1] * 5
     elif k in (L.OP_MEMSET, L.OP_COPY):
         byts = l[0]
     return cls, flops, byts

@@ -27,7 +27,8 @@ from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .schedulers import DDIMScheduler, LCMScheduler
 from .util.batchsize import find_batch_size
 from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method,
-                              iid_visualization_device, max_res_size, pil_to_tensor, resize, resize_max_res)
+                              iid_visualization_device, max_res_size, normals_visualization_device, pil_to_tensor,
+                              prepare_rgb_device, resize, resize_max_res)
 
 
 @dataclass
@@ -571,7 +572,38 @@ class _MarigoldPipelineBase:
             h, w = (h - 2) // 2 + 1, (w - 2) // 2 + 1
         return h, w
 
+    # The uint8 ends of a CUDA pipeline run on the device (csrc/resize.hip): MG_OP_RGB_PREP in ``_preprocess``, MG_OP_NORMALS_VIS in the
+    # normals pipeline's ``_finish``.  False: the host code of both (what host pipelines and float inputs run anyway) - the same bits.
+    device_io_stages = True
+
+    def _preprocess_device(self, input_image, processing_res, resample_method):
+        """``_preprocess`` of a PIL image or a uint8 [1,3,H,W] tensor on the device -> (rgb_norm on the device, input_size), or None
+        where the host code must run to give the same bits.  The picture goes up once as uint8 - PIL's HWC bytes as they are, no
+        host transpose - and one MG_OP_RGB_PREP makes what the VAE encoder reads.  The range assert of the host code is vacuous
+        here: the bytes 0 ... 255 map into [-1, 1] exactly (0 -> -1, 255 -> 1, monotonic in between), so it is not repeated."""
+        if isinstance(input_image, Image.Image):
+            u8 = torch.from_numpy(np.array(input_image.convert("RGB")))   # [H,W,3]; (np.array: torch wants a writable buffer)
+            hwc, hw = True, tuple(u8.shape[:2])
+            input_size = torch.Size((1, 3) + hw)
+        elif isinstance(input_image, torch.Tensor) and input_image.dtype == torch.uint8 and input_image.dim() == 4 and \
+                tuple(input_image.shape[:2]) == (1, 3):
+            u8, hwc, hw, input_size = input_image, False, tuple(input_image.shape[-2:]), input_image.shape
+        else:
+            return None
+        # where the host code computes: on the device (torch's device kernels: x * fp32(1 / 255)) if the tensor is there or goes
+        # there to be resampled, else on the host (IEEE division) - the stage rounds the same way
+        resample = processing_res > 0 and max(hw) != processing_res   # (else resize_max_res's factor is exactly 1: the same size)
+        on_device = u8.is_cuda or resample
+        size = max_res_size(hw, processing_res) if resample else hw
+        if u8.is_cuda and u8.device != self.device:
+            u8 = u8.to(self.device)
+        return prepare_rgb_device(u8, size, resample_method, self.io_dtype, hwc, device=self.device, reciprocal=on_device), input_size
+
     def _preprocess(self, input_image, processing_res, resample_method):
+        if getattr(self, "device_io_stages", False) and getattr(self.device, "type", None) == "cuda":
+            staged = self._preprocess_device(input_image, processing_res, resample_method)
+            if staged is not None:
+                return staged
         if isinstance(input_image, Image.Image):
             input_image = input_image.convert("RGB")
             rgb = pil_to_tensor(input_image).unsqueeze(0)
@@ -713,12 +745,19 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
             final_pred, pred_uncert = target_preds, None
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
+        img_dev = None
+        if final_pred.is_cuda and self.device_io_stages and final_pred.squeeze().dim() == 3:
+            # the picture on the device (the clip to [-1, 1] is part of the kernel); the host gets the map and a uint8 HWC image
+            img_dev = normals_visualization_device(final_pred.squeeze().float())
         final_pred = final_pred.squeeze().cpu().numpy()
         if pred_uncert is not None:
             pred_uncert = pred_uncert.squeeze().cpu().numpy()
         final_pred = final_pred.clip(-1, 1)
-        normals_img = ((final_pred + 1) * 127.5).astype(np.uint8)
-        normals_img = Image.fromarray(chw2hwc(normals_img))
+        if img_dev is not None:
+            normals_img = Image.fromarray(img_dev.cpu().numpy())
+        else:
+            normals_img = ((final_pred + 1) * 127.5).astype(np.uint8)
+            normals_img = Image.fromarray(chw2hwc(normals_img))
         return MarigoldNormalsOutput(normals_np=final_pred, normals_img=normals_img, uncertainty=pred_uncert)
 
 

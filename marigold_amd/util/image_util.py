@@ -20,7 +20,7 @@ class InterpolationMode(enum.Enum):
     NEAREST_EXACT = "nearest-exact"
 
 
-_HIP_MODES = {"bilinear": 0, "bicubic": 1, "nearest-exact": 2}
+_HIP_MODES = {"bilinear": 0, "bicubic": 1, "nearest-exact": 2}   # (= ops.RESIZE_MODES)
 
 
 def _resize_hip(img, h, w, mode):
@@ -160,6 +160,59 @@ def iid_visualization_device(pred: torch.Tensor, linear, up_to_scale) -> torch.T
         if any(a and b for a, b in zip(linear, up_to_scale)):
             ws = torch.empty((n, L.IID_VIS_PARTS), dtype=torch.float32, device=src.device)
         O.launch(O.iid_vis(src, out, ws, n=n, H=h, W=w, linear=linear, up_to_scale=up_to_scale))
+    return out
+
+
+def prepare_rgb_device(image_u8: torch.Tensor, size=None, interpolation=InterpolationMode.BILINEAR, io_dtype=torch.float32, hwc=True,
+                       device=None, reciprocal=None) -> torch.Tensor:
+    """Device form of the pipelines' input stage: the uint8 picture ``image_u8`` - [H, W, 3] as PIL holds it (``hwc``) or [(1,) 3, H, W]
+    - is uploaded as it is (a CUDA tensor stays where it is; ``device`` names the GPU of a host tensor) and one MG_OP_RGB_PREP
+    (csrc/resize.hip) produces ``(resize(x, size, interpolation) / 255.0 * 2.0 - 1.0).to(io_dtype)`` as [1, 3, h, w]: one launch
+    for the same size (``size`` None or the picture's own), else the resampling launches with the uint8 rounding and the
+    normalisation in the last one's store.  ``io_dtype``: fp32, or bf16 / fp16 through the library of that operand type.
+    ``reciprocal``: round like torch's DEVICE kernel, which multiplies by fp32(1 / 255) where the host kernel divides (111 of the
+    256 byte values come out one ulp apart) - by default what a pipeline's ``_preprocess`` ran before this stage existed: the
+    device chain after a device resample, the host chain otherwise."""
+    from .. import _lib as L, ops as O
+    assert image_u8.dtype == torch.uint8, f"prepare_rgb_device: uint8 expected, got {image_u8.dtype}"
+    if io_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"prepare_rgb_device: io_dtype {io_dtype} is not fp32, bf16 or fp16")
+    x = image_u8
+    if hwc:
+        assert x.dim() == 3 and x.shape[-1] == 3, f"prepare_rgb_device: [H, W, 3] expected, got {tuple(x.shape)}"
+        Hin, Win = x.shape[:2]
+    else:
+        assert x.dim() in (3, 4) and x.shape[-3] == 3 and x.numel() == 3 * x.shape[-2] * x.shape[-1], \
+            f"prepare_rgb_device: [(1,) 3, H, W] expected, got {tuple(x.shape)}"
+        Hin, Win = x.shape[-2:]
+    h, w = (Hin, Win) if size is None else (int(size[0]), int(size[1]))
+    if reciprocal is None:
+        reciprocal = (h, w) != (Hin, Win)
+    if not x.is_cuda:
+        x = x.to(device if device is not None else "cuda")
+    assert x.is_cuda, "prepare_rgb_device: a CUDA device is required"
+    mode = interpolation.value
+    with torch.cuda.device(x.device):
+        src = x.contiguous()
+        dst = torch.empty((1, 3, h, w), dtype=io_dtype, device=src.device)
+        tmp = None
+        if mode != "nearest-exact" and Hin != h and Win != w:
+            tmp = torch.empty(3 * Hin * w, dtype=torch.float32, device=src.device)
+        O.launch(O.rgb_prep(src, dst, tmp, Hin=Hin, Win=Win, Hout=h, Wout=w, mode=mode, hwc=hwc, out16=io_dtype != torch.float32,
+                            reciprocal=reciprocal), lib=L.load(io_dtype == torch.float16))
+    return dst
+
+
+def normals_visualization_device(pred: torch.Tensor) -> torch.Tensor:
+    """Device form of the normals picture ``chw2hwc(((pred.clip(-1, 1) + 1) * 127.5).astype(uint8))``: fp32 CUDA ``pred`` [3, H, W] ->
+    uint8 CUDA [H, W, 3] (csrc/resize.hip, MG_OP_NORMALS_VIS: one launch on the caller's current stream; NaN gives 0)."""
+    from .. import ops as O
+    assert pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and pred.shape[0] == 3, \
+        f"normals_visualization_device: fp32 CUDA [3, H, W] expected, got {pred.dtype} {tuple(pred.shape)} on {pred.device}"
+    with torch.cuda.device(pred.device):
+        src = pred.contiguous()
+        out = torch.empty(tuple(src.shape[1:]) + (3,), dtype=torch.uint8, device=src.device)
+        O.launch(O.normals_vis(src, out, H=src.shape[1], W=src.shape[2]))
     return out
 
 
