@@ -262,7 +262,16 @@ enum mg_op_kind {
    *   [3][H][W] -> uint8 [H][W][3], out = uint8((clip(x, -1, 1) + 1) * 127.5) - the clip keeps NaN like numpy.clip, the sum and the
    *   product are two fp32 roundings, the cast truncates; NaN -> 0 (MG_OP_IID_VIS's convention). */
   MG_OP_RGB_PREP = 5,
-  MG_OP_NORMALS_VIS = 8
+  MG_OP_NORMALS_VIS = 8,
+  /* Gaussian noise without a host generator (csrc/randn.hip): what torch.randn(generator=...) is to the reference's initial latents
+   * and LCM step noises (marigold/marigold_depth_pipeline.py:430-435, :466-468), for hosts that have no torch.  Stateless:
+   * Philox4x32-10 (Salmon et al., SC'11; Random123's constants) with key = (seed lo, seed hi) and counter = (block lo, block hi,
+   * stream lo, stream hi); element L_OFFSET + i of the stream is word (L_OFFSET + i) % 4 of block (L_OFFSET + i) / 4 and depends on
+   * nothing else - not on the grid, on L_N or on where a draw was split.  Words (0, 1) and (2, 3) of a block are two Box-Muller pairs
+   * (a, b): u = ((a >> 9) + 1) 2^-23 in (0, 1], v = (b >> 8) 2^-24, r = sqrtf(-2 logf(u)), outputs r cospi(2 v) and r sinpi(2 v);
+   * |z| <= sqrt(46 ln 2) = 5.647.  The 16-bit store rounds the fp32 value to nearest even.  A free number below the last kind; the
+   * slots are named by the MG_RANDN_* enumerators below. */
+  MG_OP_RANDN = 29
 };
 #define MG_IID_VIS_PARTS 128
 
@@ -473,6 +482,20 @@ enum mg_normals_vis_p {
   MG_NORMALS_VIS_P_OUT = 1        /* uint8 [H][W][3] */
 };
 
+enum mg_randn_i {
+  MG_RANDN_I_MODE = 0,            /* 0 = normals, 1 = the raw uint32 words (dst uint32 [n]; tests and debugging) */
+  MG_RANDN_I_OUT16 = 1            /* 1 = the destination holds the build's 16-bit operand type (bf16 / fp16), 0 = fp32; mode 0 only */
+};
+enum mg_randn_p {
+  MG_RANDN_P_DST = 0              /* [n], aligned to its element (a lane stores a block of four at once when that address is 16- / 8-byte aligned) */
+};
+enum mg_randn_l {
+  MG_RANDN_L_N = 0,               /* elements to draw (>= 1) */
+  MG_RANDN_L_OFFSET = 1,          /* index of the first one in its stream (>= 0; offset + n <= 2^62) */
+  MG_RANDN_L_SEED = 2,            /* the 64-bit seed (the bits of a uint64) */
+  MG_RANDN_L_STREAM = 3           /* the 64-bit stream id: independent sequences of one seed */
+};
+
 typedef struct mg_program mg_program;
 
 /* Library / device */
@@ -527,6 +550,29 @@ int mg_model_validate(mg_model* m);
 int mg_model_vae_encode(mg_model* m, const float* rgb, float* latent, void* stream);
 int mg_model_denoise(mg_model* m, const float* rgb_latent, float* x, const float* step_noise, void* stream);
 int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* stream);
+
+/* The whole prediction of one picture as ONE call, from the uint8 bytes and a seed to the ensembled map - __call__ of the reference's
+ * pipelines (marigold/marigold_depth_pipeline.py:154-338, marigold_normals_pipeline.py:139-308) up to match_input_res, for a host
+ * that has neither torch nor a noise file.  All pointers are device pointers.  The chain: mg_rgb_prepare to the model's H x W (rgb
+ * uint8 [Hin][Win][3] with hwc != 0, else [3][Hin][Win]; mode and reciprocal as in mg_rgb_prepare) -> encode -> MG_OP_RANDN of
+ * stream 0 as the initial latents [B,C,h,w] -> denoise (an LCM image: step noise k = stream k + 1, cfg[8] of them) -> decode ->
+ * ensemble: depth by mg_ensemble_depth, normals by MG_OP_ENS_NORMALS, a single member (B == 1) is copied.  pred_out fp32 [channels]
+ * [cfg[11]][cfg[12]] (the decoded size); unc_out fp32 [cfg[11]][cfg[12]] | NULL, written when B > 1 (the pipelines return none for
+ * one member); info4 | NULL as in mg_ensemble_depth (zeros where no alignment ran).  opts NULL = the reference's defaults
+ * (ensemble.py:39-49, :199-203), which MG_PREDICT_OPTS_DEFAULT spells out.  An intrinsic-image model is refused.  The resampling
+ * temporary is the model's: allocated at the first call that needs it, counted by mg_model_device_bytes, freed by mg_model_destroy.
+ * Synchronises the stream where mg_ensemble_depth does (depth, B > 1) and nowhere else.  The Python pipelines give the same map, bit
+ * for bit, from the same bytes with generator=marigold_amd.NativeNoise(seed) and match_input_res=False. */
+typedef struct mg_predict_opts {
+  int scale_invariant, shift_invariant;   /* depth: the alignment (the pipeline's constructor arguments) */
+  int reduction;                          /* depth: 0 median / 1 mean */
+  int max_iter, max_res;                  /* depth: BFGS iterations; the alignment runs on members down-sampled to max_res (<= 0: never) */
+  int normals_reduction;                  /* normals: 0 closest / 1 mean */
+  double regularizer_strength, tol;       /* depth */
+} mg_predict_opts;
+#define MG_PREDICT_OPTS_DEFAULT {1, 1, 0, 50, 1024, 0, 0.02, 1e-6}
+int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                     const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null, void* stream);
 
 /* ensemble_depth(depth[E,1,H,W], scale_invariant, shift_invariant, output_uncertainty, reduction, regularizer_strength, max_iter,
  * tol, max_res) of marigold/util/ensemble.py:39-196 as ONE call on device pointers: member statistics, init_param, the native
@@ -590,6 +636,19 @@ int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null,
 int mg_rgb_prepare(const uint8_t* src, int hwc, int Hin, int Win, void* dst, int out16, int Hout, int Wout, int mode, int reciprocal,
                    float* tmp_or_null, void* stream);
 int mg_normals_visualize(const float* pred, int H, int W, uint8_t* out_hwc, void* stream);
+
+/* MG_OP_RANDN as a call: elements [offset, offset + n) of stream stream_id of seed -> dst (fp32, or with out16 != 0 the build's 16-bit
+ * operand type).  Does not synchronise. */
+int mg_randn(uint64_t seed, uint64_t stream_id, int64_t offset, int64_t n, void* dst, int out16, void* stream);
+/* The ops that finish a picture, as calls (a C host need not fill in an mg_op): MG_OP_RESIZE (u8 != 0: uint8 planes, else fp32; tmp:
+ * fp32 [planes][Hin][Wout] when modes 0 / 1 change both sizes), MG_OP_COLORIZE (lut256x3: the colour map's 256 x 3 uint8 table, e.g.
+ * matplotlib's Spectral sampled at k / 255) and MG_OP_IID_VIS (bit t of linear_bits / up_to_scale_bits: target t; workspace fp32
+ * [n_targets][MG_IID_VIS_PARTS] when a target is both).  None of them synchronises. */
+int mg_resize(const void* src, void* dst, float* tmp_or_null, int planes, int Hin, int Win, int Hout, int Wout, int mode, int u8,
+              void* stream);
+int mg_colorize(const float* depth, const uint8_t* lut256x3, uint8_t* out_hwc, int64_t n, float min_depth, float max_depth, void* stream);
+int mg_iid_visualize(const float* pred, uint8_t* out_hwc, float* workspace_or_null, int n_targets, int H, int W, int linear_bits,
+                     int up_to_scale_bits, void* stream);
 
 /* Host arithmetic of ensemble_depth's alignment objective (marigold/util/ensemble.py:129-152, as the closed form of
  * marigold_amd/ensemble.py): pairwise-RMSE cost of the aligned members and its gradient w.r.t. scales s[E] / shifts t[E],

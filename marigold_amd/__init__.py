@@ -2,6 +2,7 @@
 reference's pipeline API (exports mirror /root/reference/marigold/__init__.py:31-41)."""
 from .pipeline import (IIDEntry, MarigoldDepthOutput, MarigoldDepthPipeline,  # noqa: F401
                        MarigoldIIDOutput, MarigoldIIDPipeline, MarigoldNormalsOutput, MarigoldNormalsPipeline)
+from .noise import NativeNoise, native_randn  # noqa: F401
 
 MarigoldPipeline = MarigoldDepthPipeline  # for backward compatibility
 

@@ -32,6 +32,7 @@ OP_MEMSET, OP_COPY = 30, 31
 OP_IIDSCORE_PREP, OP_IIDSCORE_PSNR, OP_IIDSCORE_SSIM = 32, 33, 34
 OP_IID_VIS = 35
 OP_RGB_PREP, OP_NORMALS_VIS = 5, 8   # the I/O stages: free numbers below the last kind
+OP_RANDN = 29   # the native noise generator: likewise
 IID_VIS_PARTS = 128   # MG_IID_VIS_PARTS
 IID_GAMMA = {None: 0, 2.2: 1, 1.0 / 2.2: 2, (2.2, 1.0 / 2.2): 3}   # MG_IID_GAMMA_*
 IID_METRICS = {"psnr": 1, "ssim": 2}   # MG_IID_*
@@ -94,6 +95,14 @@ IO_FIELDS = {
         p=("pred", "out"))),
 }
 
+# ... and for the noise generator (MG_RANDN_* in the header; tests/test_native_noise_host.py compares them).
+NOISE_FIELDS = {
+    OP_RANDN: ("RANDN", dict(
+        i=("mode", "out16"),
+        p=("dst",),
+        l=("n", "offset", "seed", "stream"))),
+}
+
 OP_NAMES = {v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}
 
 EXPORTS = [
@@ -105,7 +114,18 @@ EXPORTS = [
     "mg_model_load", "mg_model_destroy", "mg_model_info", "mg_model_device_bytes", "mg_model_validate", "mg_model_vae_encode",
     "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals", "mg_eval_iid",
     "mg_rgb_prepare", "mg_normals_visualize",
+    "mg_randn", "mg_resize", "mg_colorize", "mg_iid_visualize", "mg_model_predict",
 ]
+
+
+class MgPredictOpts(ctypes.Structure):
+    """mg_predict_opts; the defaults are MG_PREDICT_OPTS_DEFAULT (the reference's)."""
+    _fields_ = [("scale_invariant", ctypes.c_int), ("shift_invariant", ctypes.c_int), ("reduction", ctypes.c_int), ("max_iter", ctypes.c_int),
+                ("max_res", ctypes.c_int), ("normals_reduction", ctypes.c_int), ("regularizer_strength", ctypes.c_double), ("tol", ctypes.c_double)]
+
+    def __init__(self, scale_invariant=1, shift_invariant=1, reduction=0, max_iter=50, max_res=1024, normals_reduction=0,
+                 regularizer_strength=0.02, tol=1e-6):
+        super().__init__(scale_invariant, shift_invariant, reduction, max_iter, max_res, normals_reduction, regularizer_strength, tol)
 
 
 class MgOp(ctypes.Structure):
@@ -186,6 +206,11 @@ def load(f16=False):
     lib.mg_eval_iid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
     lib.mg_rgb_prepare.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
     lib.mg_normals_visualize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mg_randn.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.mg_resize.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 7 + [ctypes.c_void_p]
+    lib.mg_colorize.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+    lib.mg_iid_visualize.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    lib.mg_model_predict.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgPredictOpts)] + [ctypes.c_void_p] * 4
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

@@ -246,3 +246,4 @@ int mg_launch_head_conv(const mg_op* op, hipStream_t s);
 int mg_launch_ensemble(const mg_op* op, hipStream_t s);
 int mg_launch_resize(const mg_op* op, hipStream_t s);
 int mg_launch_evalscore(const mg_op* op, hipStream_t s);
+int mg_launch_randn(const mg_op* op, hipStream_t s);

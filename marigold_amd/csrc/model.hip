@@ -75,6 +75,8 @@ struct mg_model {
   std::vector<char*> bufs;
   std::vector<uint64_t> buf_bytes;   // the buffer table's sizes: every relocation / slot is checked against them
   Prog enc, den, dec;
+  void* predict_tmp = nullptr;       // mg_model_predict's resampling temporary (fp32 [3][Hin][W]), grown on demand
+  uint64_t predict_tmp_bytes = 0;
 };
 
 namespace {
@@ -220,6 +222,7 @@ void mg_model_destroy(mg_model* m) {
   for (Prog* p : {&m->enc, &m->den, &m->dec})
     if (p->prog) mg_program_destroy(p->prog);
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
+  if (m->predict_tmp) (void)hipFree(m->predict_tmp);
   delete m;
 }
 
@@ -229,7 +232,7 @@ int mg_model_info(const mg_model* m, int* cfg16) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)m->arena_bytes : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes) : 0; }
 
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
@@ -398,4 +401,72 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
   MG_CHECK_HIP(hipStreamSynchronize(s));   // the temporaries above are freed on return
   if (info4) { info4[0] = fval; info4[1] = nfev; info4[2] = nit; info4[3] = status; }
   return 0;
+}
+
+// ---- the whole prediction as one call: bytes + seed -> ensembled map (__call__ of the reference's pipelines up to match_input_res:
+// marigold/marigold_depth_pipeline.py:229-312, marigold_normals_pipeline.py:215-290).  The stages hand their results on inside the
+// model's own program slots; the members are ensembled straight out of the decode program's output slot.
+extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
+                                void* stream) {
+  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
+  const uint32_t* cfg = m->hdr.cfg;
+  const int B = (int)cfg[0], H = (int)cfg[1], W = (int)cfg[2], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8];
+  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
+  MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
+  MG_REQUIRE(Hin > 0 && Win > 0, "mg_model_predict: bad input size %d x %d", Hin, Win);
+  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
+  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
+  const hipStream_t s = (hipStream_t)stream;
+  const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
+  const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
+  const uint64_t HWo = (uint64_t)Ho * Wo;
+  MG_REQUIRE(e_in->nbytes == (uint64_t)3 * H * W * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes && xs->nbytes % 4 == 0 &&
+             d_out->nbytes == (uint64_t)B * C * HWo * 4, "mg_model_predict: the image's slots do not chain");
+  // 1. the picture -> [1,3,H,W] in [-1, 1], in the encoder's input slot
+  float* tmp = nullptr;
+  if (mode != 2 && Hin != H && Win != W) {
+    const uint64_t need = (uint64_t)3 * Hin * W * 4;
+    if (m->predict_tmp_bytes < need) {
+      if (m->predict_tmp) MG_CHECK_HIP(hipFree(m->predict_tmp));   // (hipFree waits for the work that still uses it)
+      m->predict_tmp = nullptr;
+      m->predict_tmp_bytes = 0;
+      MG_CHECK_HIP(hipMalloc(&m->predict_tmp, need));
+      m->predict_tmp_bytes = need;
+    }
+    tmp = (float*)m->predict_tmp;
+  }
+  if (int rc = mg_rgb_prepare(rgb, hwc, Hin, Win, e_in->ptr, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
+  // 2. encode
+  if (int rc = mg_program_run(m->enc.prog, stream)) return rc;
+  if (int rc = copy_dd(rl->ptr, e_out->ptr, rl->nbytes, s)) return rc;
+  // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
+  if (int rc = mg_randn(seed, 0, 0, (int64_t)(xs->nbytes / 4), xs->ptr, 0, stream)) return rc;
+  for (int k = 0; k < n_noise; ++k) {
+    char nm[24];
+    snprintf(nm, sizeof(nm), "noise%d", k);
+    const Slot* ns = m->den.slot(nm);
+    MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "mg_model_predict: the image lacks slot %s", nm);
+    if (int rc = mg_randn(seed, (uint64_t)k + 1, 0, (int64_t)(ns->nbytes / 4), ns->ptr, 0, stream)) return rc;
+  }
+  // 4. denoise, 5. decode
+  if (int rc = mg_program_run(m->den.prog, stream)) return rc;
+  if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
+  if (int rc = mg_program_run(m->dec.prog, stream)) return rc;
+  // 6. ensemble (one member: the pipelines return it as it is, without an uncertainty)
+  const float* preds = (const float*)d_out->ptr;
+  if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
+  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)C * HWo * 4, s);
+  if (post == MG_POST_DEPTH)
+    return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
+                             o.max_res, pred_out, unc_out_or_null, info4_or_null, stream);
+  MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
+  mg_op en;
+  memset(&en, 0, sizeof(en));
+  en.kind = MG_OP_ENS_NORMALS;
+  en.p[0] = (void*)preds; en.p[1] = pred_out; en.p[2] = unc_out_or_null;
+  en.i[0] = B; en.i[1] = o.normals_reduction;
+  en.l[0] = (int64_t)HWo;
+  return mg_launch(&en, stream);
 }

@@ -77,6 +77,7 @@ static int dispatch(const mg_op* op, hipStream_t s) {
     case MG_OP_IIDSCORE_PREP:
     case MG_OP_IIDSCORE_PSNR:
     case MG_OP_IIDSCORE_SSIM: return mg_launch_evalscore(op, s);
+    case MG_OP_RANDN: return mg_launch_randn(op, s);
     default: mg_set_error("mg_launch: unknown op kind %d", op->kind); return 2;
   }
 }
@@ -257,6 +258,36 @@ int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int
   op.i[0] = E; op.i[1] = reduction;
   op.l[0] = hw;
   return mg_launch_ensemble(&op, (hipStream_t)stream);
+}
+
+int mg_resize(const void* src, void* dst, float* tmp_or_null, int planes, int Hin, int Win, int Hout, int Wout, int mode, int u8,
+              void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_RESIZE;
+  op.p[0] = (void*)src; op.p[1] = dst; op.p[2] = tmp_or_null;
+  op.i[0] = planes; op.i[1] = Hin; op.i[2] = Win; op.i[3] = Hout; op.i[4] = Wout; op.i[5] = mode; op.i[6] = u8 != 0;
+  return mg_launch_resize(&op, (hipStream_t)stream);
+}
+
+int mg_colorize(const float* depth, const uint8_t* lut256x3, uint8_t* out_hwc, int64_t n, float min_depth, float max_depth, void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_COLORIZE;
+  op.p[0] = (void*)depth; op.p[1] = (void*)lut256x3; op.p[2] = out_hwc;
+  op.l[0] = n;
+  op.f[0] = min_depth; op.f[1] = max_depth;
+  return mg_launch_resize(&op, (hipStream_t)stream);
+}
+
+int mg_iid_visualize(const float* pred, uint8_t* out_hwc, float* workspace_or_null, int n_targets, int H, int W, int linear_bits,
+                     int up_to_scale_bits, void* stream) {
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_IID_VIS;
+  op.p[0] = (void*)pred; op.p[1] = out_hwc; op.p[2] = workspace_or_null;
+  op.i[0] = n_targets; op.i[1] = H; op.i[2] = W; op.i[3] = linear_bits; op.i[4] = up_to_scale_bits;
+  return mg_launch_resize(&op, (hipStream_t)stream);
 }
 
 // ---- shader clock under matrix-core load (mg_clock_probe; bench.py's calibration block) ----

@@ -40,7 +40,7 @@ def make_op(kind, i=(), f=(), p=(), l=()):
 # --------------------------------------------------------------------------- named fields
 
 _TO_SLOT = dict(i=int, f=float, p=_ptr, l=int)
-_TABLES = {**L.FIELDS, **L.IO_FIELDS}
+_TABLES = {**L.FIELDS, **L.IO_FIELDS, **L.NOISE_FIELDS}
 _WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in _TABLES.items()}
 assert all(len(w) == sum(len(names) for names in _TABLES[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
 
@@ -363,6 +363,16 @@ def rgb_prep(src, dst, tmp=None, *, Hin, Win, Hout=None, Wout=None, mode=0, hwc=
 def normals_vis(pred, out, *, H, W):
     """The normals picture (MG_OP_NORMALS_VIS): fp32 ``pred`` [3,H,W] -> uint8 ``out`` [H,W,3]."""
     return build_op(L.OP_NORMALS_VIS, h=H, w=W, pred=pred, out=out)
+
+
+def randn(dst, *, n, seed, stream=0, offset=0, words=False, out16=False):
+    """Native Gaussian noise (MG_OP_RANDN): elements [offset, offset + n) of stream ``stream`` of the 64-bit ``seed`` -> ``dst``, fp32 or
+    (``out16``) the library's 16-bit operand type; ``words``: the raw Philox4x32-10 words instead (``dst`` uint32 / int32)."""
+    seed, stream = int(seed), int(stream)
+    if not (0 <= seed < 1 << 64 and 0 <= stream < 1 << 64):
+        raise ValueError(f"randn: seed {seed} / stream {stream} outside 64 bits")
+    as_i64 = lambda v: v - (1 << 64) if v >= 1 << 63 else v   # the bits of a uint64 in the op's int64 slot
+    return build_op(L.OP_RANDN, mode=int(bool(words)), out16=bool(out16), dst=dst, n=n, offset=offset, seed=as_i64(seed), stream=as_i64(stream))
 
 
 def eval_fit_width(H, W, max_res):

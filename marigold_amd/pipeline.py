@@ -10,6 +10,7 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
 * optional member parallelism over the GPUs of a node (``enable_member_parallel``): members are
   sharded over ranks and collected with ONE gather (RCCL over xGMI) before aggregation;
 * ``init_latents`` (extension) lets callers supply the initial noise for parity runs;
+* ``generator=NativeNoise(seed)`` (extension) draws the noise with the library's own generator (noise.py), as a C host does;
 * ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program.
 """
 import logging
@@ -24,6 +25,7 @@ from . import _lib as L
 from . import dist as mdist
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
+from .noise import NativeNoise
 from .schedulers import DDIMScheduler, LCMScheduler
 from .util.batchsize import find_batch_size
 from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_maps, get_tv_resample_method,
@@ -124,6 +126,8 @@ class _MarigoldPipelineBase:
     noise_dtype = torch.float32
 
     def _randn(self, shape, generator):
+        if isinstance(generator, NativeNoise):   # the library's generator: the next stream of its seed, fp32 rounded to io_dtype in the store
+            return generator.randn(shape, dtype=self.io_dtype, device=self.device)
         return torch.randn(tuple(shape), device=self.device, dtype=self.noise_dtype, generator=generator).to(self.io_dtype)
 
     def to(self, device):
@@ -201,7 +205,7 @@ class _MarigoldPipelineBase:
         """``(pipe(image, **call_kwargs) for image in images)`` with up to ``in_flight`` maps on the GPU at a time (default
         ``maps_in_flight_for(ensemble_size)``; 1 = one after the other on the caller's stream).  A generator: outputs come in input order
         as they complete, and ``images`` (any iterable) is consumed as lanes become free.  ``generators``: one
-        ``torch.Generator`` (or None) per image - with several maps in flight a single shared generator would be consumed in
+        ``torch.Generator`` (or ``NativeNoise``, or None) per image - with several maps in flight a single shared generator would be consumed in
         completion order, so ``generator=`` is refused; every map is then bit-identical to what ``pipe(image, generator=g)``
         returns on its own.  Member-parallel pipelines (several ranks): every rank must call this with the same images and
         ``in_flight``; the lanes then issue their gathers strictly in map order, one at a time (``_Turnstile``), so the collective
