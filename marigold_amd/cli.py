@@ -53,7 +53,7 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
     p.add_argument("--apple_silicon", action="store_true", help="(reference flag; not available on this engine)")
     p.add_argument("--maps_in_flight", type=int, default=0,
                    help="Images on the GPU at a time (independent maps on concurrent HIP streams; results do not depend on it); "
-                        "0 = the engine's default (3 while a program holds up to 8 members on this GPU, else 2).")
+                        "0 = the engine's default (maps_in_flight_for: 3 lanes while a program holds 8 members or fewer on this GPU, else 2).")
     p.add_argument("--images_per_program", type=int, default=1,
                    help="Consecutive images of one processed size that share one denoising program (their members batched); "
                         "1 = one image per program.")

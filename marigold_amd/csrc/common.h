@@ -224,6 +224,17 @@ int mg_tuning_int(const char* name, int dflt);
       return 1;                                                                    \
     }                                                                              \
   } while (0)
+// Once per kernel, before its launch: raise `kern`'s hipFuncAttributeMaxDynamicSharedMemorySize to `bytes` (runtime.hip, over
+// kernel_once.h).  Safe when several host threads make the first launch of the same or different kernels at once; the attribute is
+// set at most once per size, a larger request raises it; a failure is reported (mg_set_error, -> 1) and tried again by the next
+// launch; under g_dry_run nothing is set or recorded.  `no_static_lds`: refuse (-> 2), in the same once-only step, a kernel whose
+// static LDS is not empty - its dynamic LDS must start at address 0.
+int mg_kernel_max_lds(const void* kern, int bytes, bool no_static_lds = false);
+#define MG_KERNEL_MAX_LDS(...)                                   \
+  do {                                                           \
+    if (const int _rc = mg_kernel_max_lds(__VA_ARGS__)) return _rc; \
+  } while (0)
+int mg_cu_count();   // compute units of the device mg_init bound; 256 (MI355X) before mg_init
 #define MG_REQUIRE(cond, ...)      \
   do {                             \
     if (!(cond)) {                 \

@@ -437,12 +437,10 @@ int launch_patch(const ConvPArgs& a0, hipStream_t s) {
   MG_REQUIRE(grid > 0 && grid < (1ll << 31), "conv3x3: bad grid %lld", grid);
   void (*kern)(const ConvPArgs) = a.ss ? conv_patch_kernel<TH, TW, BN, WGM, WGN, NSTB, true>
                                        : conv_patch_kernel<TH, TW, BN, WGM, WGN, NSTB, false>;
-  int ki = a.ss ? 1 : 0;
   if constexpr ((WGM * WGN == 12 && BN != 320) || (TH == 16 && BN == 256 && NSTB == 2)) {   // the output's GroupNorm statistics as a
     // by-product: the VAE's 12-wave tiles and the 16 x 16 x 256 tile its 256-channel sub-pixel up-sampling runs on
     if (a.gn_part) {
       kern = a.ss ? conv_patch_kernel<TH, TW, BN, WGM, WGN, NSTB, true, true> : conv_patch_kernel<TH, TW, BN, WGM, WGN, NSTB, false, true>;
-      ki += 2;
       MG_REQUIRE((a.gn_cpg == 4 || a.gn_cpg == 8 || a.gn_cpg == 16 || a.gn_cpg == 32) && a.N % a.gn_cpg == 0 && a.N % BN == 0 &&
                  a.gn_slots == a.tiles_x * a.tiles_y * (a.subpix ? 4 : 1),
                  "conv3x3: output statistics need 4 / 8 / 16 / 32 channels per group, N %% %d == 0 and %d table slots (got %d)", BN,
@@ -451,11 +449,7 @@ int launch_patch(const ConvPArgs& a0, hipStream_t s) {
   } else {
     MG_REQUIRE(!a.gn_part, "conv3x3: this tile variant does not produce output statistics (mg_conv3x3_gn_slots() tells)");
   }
-  static bool attr_set[4] = {false, false, false, false};
-  if (!attr_set[ki] && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set[ki] = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)kern, LDS);
   MG_LAUNCH(kern, dim3((unsigned)grid), dim3(NT), LDS, s, a);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;

@@ -119,11 +119,7 @@ int launch4w(const ConvPArgs& a0, void (*plain)(const ConvPArgs), void (*fixed)(
   const long long grid = (long long)a.tiles_x * a.tiles_y * a.tiles_n * a.B * (a.subpix ? 4 : 1);
   MG_REQUIRE(grid > 0 && grid < (1ll << 31), "conv3x3: bad grid %lld", grid);
   void (*kern)(const ConvPArgs) = a.ss ? fixed : plain;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[a.ss ? 1 : 0] && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set[a.ss ? 1 : 0] = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)kern, 160 * 1024);
   MG_LAUNCH(kern, dim3((unsigned)grid), dim3(256), LDS, s, a);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;

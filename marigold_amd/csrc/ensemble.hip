@@ -592,12 +592,7 @@ int mg_launch_ensemble(const mg_op* op, hipStream_t s) {
                   op->l[0], op->i[1], op->i[2], op->p[1] != nullptr);
       } else if (E > EMAX) {
         const size_t lds = ((size_t)E * 256 + 2 * E) * sizeof(float);
-        static bool attr = false;
-        if (!attr && !g_dry_run) {
-          MG_CHECK_HIP(hipFuncSetAttribute((const void*)depth_median_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(((size_t)EMAX_LDS * 256 + 2 * EMAX_LDS) * sizeof(float))));
-          attr = true;
-        }
+        MG_KERNEL_MAX_LDS((const void*)depth_median_lds_kernel, (int)(((size_t)EMAX_LDS * 256 + 2 * EMAX_LDS) * sizeof(float)));
         MG_LAUNCH(depth_median_lds_kernel, dim3(nblk), dim3(256), lds, s, (const float*)op->p[0], (const float*)op->p[1],
                   (float*)op->p[2], (float*)op->p[3], (float*)op->p[5], (long long*)((char*)op->p[5] + 8 * ENS_BLOCKS), E,
                   op->l[0], op->i[1], op->i[2], op->p[1] != nullptr);

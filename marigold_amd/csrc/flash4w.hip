@@ -543,20 +543,7 @@ int mg_launch_flash4w(const FaArgs& a_in, hipStream_t s) {
   MG_REQUIRE(mg_flash4w_ok(a, true), "flash_attn64 (hand-placed form): Ntok %d must be a multiple of 256, "
              "16-byte aligned operands", a.Ntok);
   const int LDS = F4_LDS;
-  static bool attr_set = false;
-  static int n_cu = 256;
-  if (!attr_set && !g_dry_run) {
-    for (const void* fn : {(const void*)flash_attn64_4w_kernel<false>, (const void*)flash_attn64_4w_kernel<true>}) {
-      hipFuncAttributes fa;
-      MG_CHECK_HIP(hipFuncGetAttributes(&fa, fn));
-      MG_REQUIRE(fa.sharedSizeBytes == 0, "flash_attn64 (hand-placed form): the ring must start at LDS address 0 (static LDS %d bytes)", (int)fa.sharedSizeBytes);
-      MG_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    }
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    attr_set = true;
-  }
+  const int n_cu = mg_cu_count();
   MG_REQUIRE((long long)(a.Ntok / 256) * a.heads * a.B < (1ll << 30), "flash_attn64: too many query blocks");
   mg_flash4w_plan(&a, n_cu);
   const long long grid = (long long)a.n_full + a.n_rem_wg;
@@ -564,7 +551,8 @@ int mg_launch_flash4w(const FaArgs& a_in, hipStream_t s) {
   // power-limited regime it was built for: E = 10: 851 vs 911 us; a tie at 2 304 tokens and for two members, 2 % slower for one
   // (profiles/r6_flash_mfma16.log).  m16 < 0: this rule; MARIGOLD_FLASH4W_M16 = 0 / 1 (tuning gate) forces a form.
   if (a.m16 < 0) a.m16 = (a.Ntok >= 4096 && (long long)(a.Ntok / 256) * a.heads * a.B >= 2ll * n_cu) ? 1 : 0;
-  if (a.m16) MG_LAUNCH(flash_attn64_4w_kernel<true>, dim3((unsigned)grid), dim3(256), LDS, s, a);   // the stream on 16x16x32 MFMAs (variant 27)
-  else MG_LAUNCH(flash_attn64_4w_kernel<false>, dim3((unsigned)grid), dim3(256), LDS, s, a);
+  const auto kern = !a.m16 ? flash_attn64_4w_kernel<false> : flash_attn64_4w_kernel<true>;   // <true>: the stream on 16x16x32 MFMAs (variant 27)
+  MG_KERNEL_MAX_LDS((const void*)kern, LDS, true);   // the hand-placed ring must start at LDS address 0
+  MG_LAUNCH(kern, dim3((unsigned)grid), dim3(256), LDS, s, a);
   return 0;
 }

@@ -243,11 +243,7 @@ int mg_launch_flash512(const mg_op* op, hipStream_t s) {
              "flash_attn512: 16-byte alignment");
   MG_REQUIRE(FA5_D * 2 <= MG_ZERO_BYTES, "flash_attn512: zero page too small");
   const int LDS = 2 * FA5_STAGE;
-  static bool attr_set = false;
-  if (!attr_set && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)flash_attn512_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)flash_attn512_kernel, LDS);
   const long long grid = (long long)((a.Ntok + FA5_QB - 1) / FA5_QB) * a.B;
   MG_LAUNCH(flash_attn512_kernel, dim3((unsigned)grid), dim3(256), LDS, s, a);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());

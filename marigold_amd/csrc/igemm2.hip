@@ -87,16 +87,11 @@ int launch2(const Igemm2Args& a, int batch_z, hipStream_t s) {
   constexpr int NT = WGM * WGN * 64;
   constexpr int LDS = NSTAGE * (BM + BN) * BK * 2 + BM * 8;   // ring + (mean, rstd) of the tile's rows (folded LayerNorm)
   static_assert(LDS <= 160 * 1024, "LDS ring exceeds 160 KiB");
-  static bool attr_set[2] = {false, false};   // [1]: the instrumented instantiation (tuning only)
-  const int ai = a.stamps ? 1 : 0;
   void (*kern)(const Igemm2Args);
-  if constexpr (BIG >= 0) kern = (void (*)(const Igemm2Args))mg_igemm2_big_kernel(a.stamps ? BIG + 2 : BIG);
+  if constexpr (BIG >= 0) kern = (void (*)(const Igemm2Args))mg_igemm2_big_kernel(a.stamps ? BIG + 2 : BIG);   // + 2: the instrumented instantiation (tuning only)
   else if constexpr (PPOPT >= 0) kern = igemm2_pingpong_kernel<TRANS, PPOPT>;
   else kern = igemm2_kernel<BM, BN, WGM, WGN, NSTAGE, TRANS, SPLIT, PF, ABL, BK>;
-  if (!attr_set[ai] && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set[ai] = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)kern, LDS);
   Igemm2Args b = a;
   b.cpt = a.Cin / BK;
   b.c0t = a.A1 ? a.C0 / BK : b.cpt;

@@ -660,12 +660,8 @@ void rowgemm_xattn_kernel(const RgXArgs a) {
 template <int K, int NW>
 int rg_launch_xattn(const RgXArgs& a, hipStream_t s) {
   constexpr int LDS = (2 * (K / 16) + 1 + (K / 64) * 8 + 2) * 1024;
-  static bool attr_set = false;
   auto kern = rowgemm_xattn_kernel<K, NW>;
-  if (!attr_set && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)kern, LDS);
   const int rows = NW * 32;
   MG_LAUNCH(kern, dim3((a.M + rows - 1) / rows), dim3(NW * 64), LDS, s, a);
   return 0;
@@ -819,12 +815,8 @@ int rg_launch(const RgArgs& a, hipStream_t s) {
   // XA: the cross-attention images (scores stage + VO^T fragments + bias) sit behind ring slot 0
   constexpr int LDS = XA ? (RING / 3 + (2 * (K / 16) + 1 + (K / 64) * 8 + 2) * 1024 > RING ? RING / 3 + (2 * (K / 16) + 1 + (K / 64) * 8 + 2) * 1024 : RING) : RING;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
   auto kern = rowgemm_kernel<K, NW, EPI, LN, GN, RES, LNO, XA>;
-  if (!attr_set && !g_dry_run) {
-    MG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr_set = true;
-  }
+  MG_KERNEL_MAX_LDS((const void*)kern, LDS);
   const int rows = NW * 32;
   MG_LAUNCH(kern, dim3((a.M + rows - 1) / rows, ((a.N >> 6) + a.spl - 1) / a.spl), dim3(NW * 64), LDS, s, a);
   return 0;

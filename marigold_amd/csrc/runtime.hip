@@ -7,10 +7,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <mutex>
 #include <vector>
 
 #include "common.h"
+#include "kernel_once.h"
 
 void* g_zero_page = nullptr;
 void* g_splitk_ws = nullptr;
@@ -19,6 +21,23 @@ thread_local bool g_dry_run = false;
 static thread_local char g_err[512] = "";
 static std::mutex g_init_mutex;
 static int g_device = -1;
+static std::atomic<int> g_cu_count{256};
+static mg_kernel_once g_kernel_once;
+
+int mg_cu_count() { return g_cu_count.load(std::memory_order_relaxed); }
+
+// The one place the library sets a kernel attribute (contract: common.h).
+int mg_kernel_max_lds(const void* kern, int bytes, bool no_static_lds) {
+  return g_kernel_once.raise(kern, bytes, g_dry_run, [no_static_lds](const void* k, int b) {
+    if (no_static_lds) {
+      hipFuncAttributes fa;
+      MG_CHECK_HIP(hipFuncGetAttributes(&fa, k));
+      MG_REQUIRE(fa.sharedSizeBytes == 0, "this kernel's dynamic LDS must start at LDS address 0 (static LDS %d bytes)", (int)fa.sharedSizeBytes);
+    }
+    MG_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, b));
+    return 0;
+  });
+}
 
 // The ONE place the library reads the environment.  Tuning switches (tile / kernel choices for A/B runs and sweeps) are honoured
 // only under MARIGOLD_TUNING=1; without it every launcher runs its compiled-in default, whatever else the environment holds.
@@ -104,6 +123,7 @@ int mg_init(int device) {
   if (g_zero_page && g_device == device) return 0;
   MG_REQUIRE(g_device < 0 || g_device == device,
              "mg_init: one process drives one GPU (already bound to device %d)", g_device);
+  if (prop.multiProcessorCount > 0) g_cu_count = prop.multiProcessorCount;
   MG_CHECK_HIP(hipMalloc(&g_zero_page, MG_ZERO_BYTES));
   MG_CHECK_HIP(hipMemset(g_zero_page, 0, MG_ZERO_BYTES));
   MG_CHECK_HIP(hipMalloc(&g_splitk_ws, MG_SPLITK_WS_BYTES));

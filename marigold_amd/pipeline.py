@@ -13,8 +13,12 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
 * ``generator=NativeNoise(seed)`` (extension) draws the noise with the library's own generator (noise.py), as a C host does;
 * ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program.
 """
+import contextlib
+import copy
+import functools
 import logging
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
@@ -24,6 +28,7 @@ from PIL import Image
 from . import _lib as L
 from . import dist as mdist
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
+from .lanes import Turnstile as _Turnstile, run_lanes
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .noise import NativeNoise
 from .schedulers import DDIMScheduler, LCMScheduler
@@ -51,31 +56,13 @@ class MarigoldNormalsOutput:
     uncertainty: Union[None, np.ndarray]
 
 
-class _Turnstile:
-    """Calls pass in index order, one at a time: ``wait(k)`` returns once 0 ... k - 1 are ``done``."""
-
-    def __init__(self):
-        import threading
-        self._cv = threading.Condition()
-        self._next = 0
-        self._error = None
-
-    def wait(self, k):
-        with self._cv:
-            self._cv.wait_for(lambda: self._next == k or self._error is not None)
-            if self._error is not None:
-                raise RuntimeError("map_images: another lane failed before its gather") from self._error
-
-    def done(self, k):
-        with self._cv:
-            if self._next == k:
-                self._next = k + 1
-            self._cv.notify_all()
-
-    def abort(self, error):
-        with self._cv:
-            self._error = error
-            self._cv.notify_all()
+@contextlib.contextmanager
+def _on_stream(device, stream, caller):
+    """``with`` this in a lane's thread: its work goes to the lane's HIP stream, behind what the caller has queued on its own."""
+    torch.cuda.set_device(device)
+    stream.wait_stream(caller)   # inputs the caller produced on its stream
+    with torch.cuda.stream(stream):
+        yield
 
 
 class _MarigoldPipelineBase:
@@ -84,6 +71,7 @@ class _MarigoldPipelineBase:
     _ckpt_hint = "prs-eth/marigold-depth-v1-1"
     _target_latent_channels = 4    # latent channels the UNet predicts (4 per modality)
     _pred_channels = 1             # channels of one decoded prediction
+    _gather_turn = None            # (turnstile, map index): set only on the per-call view a lane of map_images runs on
 
     def __init__(self, unet: UNet2DConditionModelHIP, vae: AutoencoderKLHIP,
                  scheduler: Union[DDIMScheduler, LCMScheduler], text_encoder=None, tokenizer=None,
@@ -102,6 +90,9 @@ class _MarigoldPipelineBase:
         self.empty_text_embed = empty_text_embed
         self._member_group = None
         self._member_parallel = False
+        self._member_root = None
+        self._member_force = False
+        self._lanes = []   # map_images' lanes: (unet and vae engine, stream)
 
     # ---- diffusers.DiffusionPipeline surface the callers use ---------------------------------
     @property
@@ -133,7 +124,7 @@ class _MarigoldPipelineBase:
     def to(self, device):
         self.unet.to(device)
         self.vae.to(device)
-        self._lanes = None   # engine replicas of map_images belong to the device they were made on
+        self._lanes = []   # engine replicas of map_images belong to the device they were made on
         return self
 
     @classmethod
@@ -157,7 +148,7 @@ class _MarigoldPipelineBase:
         self._member_force = bool(force_collective) and mdist.is_on(group)
 
     def _sharded(self):
-        return self._member_parallel and (mdist.world_size(self._member_group) > 1 or getattr(self, "_member_force", False))
+        return self._member_parallel and (mdist.world_size(self._member_group) > 1 or self._member_force)
 
     # ---- maps in flight ----------------------------------------------------------------------
     # The reference's scripts call the pipeline image by image (script/depth/run.py:231-262, script/depth/infer.py): every map waits
@@ -182,29 +173,38 @@ class _MarigoldPipelineBase:
         local = -(-max(1, int(ensemble_size)) // max(1, world))
         return self.small_ensemble_maps_in_flight if local <= self.small_ensemble_members else self.default_maps_in_flight
 
+    def _view(self, unet, vae):
+        """A shallow copy of this pipeline as it is now, over the given engines and with a scheduler object of its own."""
+        v = copy.copy(self)
+        v.unet, v.vae, v.scheduler, v._lanes = unet, vae, copy.deepcopy(self.scheduler), []
+        return v
+
     def replicate(self):
         """Another pipeline over the same device-resident weights: engine replicas (own workspaces, programs, launch-private
-        state) and its own scheduler object - what ``map_images`` runs a second map on."""
-        import copy
-        r = copy.copy(self)
-        r.unet, r.vae = self.unet.replica(), self.vae.replica()
-        r.scheduler = copy.deepcopy(self.scheduler)
-        r._lanes = None
-        return r
+        state) and its own scheduler object - what a caller's second thread runs a map on."""
+        return self._view(self.unet.replica(), self.vae.replica())
 
-    def _lane_pipelines(self, n):
-        lanes = getattr(self, "_lanes", None)
-        if lanes is None:
-            lanes = self._lanes = [(self, torch.cuda.Stream(device=self.device))]
-        while len(lanes) < n:
-            lanes.append((self.replicate(), torch.cuda.Stream(device=self.device)))
-        return lanes[:n]
+    def _lane_resources(self, n):
+        """The first n lanes, (engines, stream) each: lane 0 over the pipeline's own unet / vae engines, the others over
+        replicas.  All that ``map_images`` keeps between calls: the pipelines its lanes run on are views made per call."""
+        while len(self._lanes) < n:
+            unet, vae = (self.unet.replica(), self.vae.replica()) if self._lanes else (self.unet, self.vae)
+            self._lanes.append((SimpleNamespace(unet=unet, vae=vae), self._lane_stream()))
+        return self._lanes[:n]
+
+    def _lane_stream(self):
+        return torch.cuda.Stream(device=self.device)
+
+    def _lane_contexts(self, streams):
+        """-> (a context per lane, for its thread; what the caller calls once they are all left)"""
+        caller = torch.cuda.current_stream(self.device)
+        return [_on_stream(self.device, s, caller) for s in streams], lambda: [caller.wait_stream(s) for s in streams]
 
     def map_images(self, images, in_flight: Optional[int] = None, generators=None, images_per_program: int = 1,
                    **call_kwargs):
         """``(pipe(image, **call_kwargs) for image in images)`` with up to ``in_flight`` maps on the GPU at a time (default
         ``maps_in_flight_for(ensemble_size)``; 1 = one after the other on the caller's stream).  A generator: outputs come in input order
-        as they complete, and ``images`` (any iterable) is consumed as lanes become free.  ``generators``: one
+        as they complete, and ``images`` (any iterable) is consumed as lanes become free, at most one group per lane ahead of the caller.  ``generators``: one
         ``torch.Generator`` (or ``NativeNoise``, or None) per image - with several maps in flight a single shared generator would be consumed in
         completion order, so ``generator=`` is refused; every map is then bit-identical to what ``pipe(image, generator=g)``
         returns on its own.  Member-parallel pipelines (several ranks): every rank must call this with the same images and
@@ -255,118 +255,51 @@ class _MarigoldPipelineBase:
         return max_res_size(hw, processing_res) if processing_res > 0 else hw
 
     def _map_images(self, images, generators, n, call_kwargs, per_program=1):
-        import threading
-        lock = threading.Lock()
-        count = [0]
-        held = []   # an image whose processed size ended the previous group: it opens the next one
+        def groups():
+            """[(image, generator)]: up to ``per_program`` consecutive images of one processed size; the two iterables advance together"""
+            group, size = [], None
+            for image in images:
+                g = None if generators is None else next(generators, StopIteration)
+                if g is StopIteration:
+                    raise ValueError("map_images: fewer generators than images")
+                image_size = self._processed_size(image, call_kwargs.get("processing_res")) if per_program > 1 else None
+                if group and image_size != size:   # this image opens the next group
+                    yield group
+                    group = []
+                group.append((image, g))
+                size = image_size
+                if len(group) == per_program:
+                    yield group
+                    group = []
+            if group:
+                yield group
 
-        def pull():
-            """-> (image, generator) | None: the two iterables advance together"""
-            if held:
-                return held.pop()
-            try:
-                image = next(images)
-            except StopIteration:
-                return None
-            g = None
-            if generators is not None:
-                try:
-                    g = next(generators)
-                except StopIteration:
-                    raise ValueError("map_images: fewer generators than images") from None
-            return image, g
+        take = functools.partial(next, enumerate(groups()), None)   # -> (index, group) | None; one lane at a time (run_lanes)
+        views, contexts, leave, turnstile = [self], [contextlib.nullcontext()], lambda: None, None   # one lane: inline, on this very object
+        if n > 1:
+            if self.empty_text_embed is None:
+                self.encode_empty_text()   # what a lone call would write back to the pipeline
+            lanes = self._lane_resources(n)
+            views = [self._view(e.unet, e.vae) for e, _ in lanes]   # lane 0 too: no lane works on the caller's object
+            contexts, leave = self._lane_contexts([stream for _, stream in lanes])
+            turnstile = _Turnstile() if self._sharded() else None
 
-        def take():
-            """-> (index, [(image, generator)]) | None, under the lock: up to ``per_program`` consecutive images of one
-            processed size"""
-            with lock:
-                first = pull()
-                if first is None:
-                    return None
-                group = [first]
-                if per_program > 1:
-                    size = self._processed_size(first[0], call_kwargs.get("processing_res"))
-                    while len(group) < per_program and (item := pull()) is not None:
-                        if self._processed_size(item[0], call_kwargs.get("processing_res")) != size:
-                            held.append(item)
-                            break
-                        group.append(item)
-                k = count[0]
-                count[0] += 1
-                return k, group
-
-        turnstile = _Turnstile() if (n > 1 and self._sharded()) else None
-
-        def one(pipe, group, k=0):
+        def run(lane, group, k):
             """-> the outputs of the group's images, in order"""
-            kw = dict(call_kwargs)
+            pipe, kw = views[lane], dict(call_kwargs)
             if len(group) > 1:
                 return pipe._call_group([im for im, _ in group], None if generators is None else [g for _, g in group], kw)
             image, g = group[0]
             if generators is not None:
                 kw["generator"] = g
-            pipe._gather_turn = None if turnstile is None else (turnstile, k)
-            try:
-                return [pipe(image, **kw)]
-            finally:
-                pipe._gather_turn = None
+            if turnstile is not None:
+                pipe._gather_turn = (turnstile, k)   # on this call's view of the lane
+            return [pipe(image, **kw)]
 
-        if n == 1:
-            while (item := take()) is not None:
-                yield from one(self, item[1])
-            return
-        lanes = self._lane_pipelines(n)
-        caller = torch.cuda.current_stream(self.device)
-        done = {}
-        cv = threading.Condition()
-        stop = threading.Event()
-        live = [len(lanes)]
-
-        def work(pipe, stream):
-            try:
-                torch.cuda.set_device(self.device)
-                stream.wait_stream(caller)   # inputs the caller produced on its stream
-                with torch.cuda.stream(stream):
-                    while not stop.is_set():
-                        item = take()
-                        if item is None:
-                            break
-                        out = one(pipe, item[1], item[0])
-                        with cv:
-                            done[item[0]] = out
-                            cv.notify_all()
-            except BaseException as e:  # noqa: BLE001 - handed to the caller's thread
-                if turnstile is not None:
-                    turnstile.abort(e)   # lanes waiting for their turn must not wait for a gather that will never be issued
-                with cv:
-                    done.setdefault("error", e)
-                    cv.notify_all()
-            finally:
-                with cv:
-                    live[0] -= 1
-                    cv.notify_all()
-
-        threads = [threading.Thread(target=work, args=lane, daemon=True) for lane in lanes]
-        for t in threads:
-            t.start()
         try:
-            k = 0
-            while True:
-                with cv:
-                    cv.wait_for(lambda: k in done or "error" in done or live[0] == 0)
-                    if "error" in done:
-                        raise done["error"]
-                    if k not in done:
-                        break   # every lane has finished and map k was never started: the input is exhausted
-                    outs = done.pop(k)
-                yield from outs
-                k += 1
+            yield from run_lanes(contexts, take, run, turnstile)
         finally:
-            stop.set()
-            for t in threads:
-                t.join()
-            for _, stream in lanes:
-                caller.wait_stream(stream)
+            leave()
 
     # ---- reference methods -------------------------------------------------------------------
     def _check_inference_step(self, n_step: int) -> None:
@@ -481,15 +414,13 @@ class _MarigoldPipelineBase:
             hh, ww = (f * d for d in self._latent_hw(rgb_norm.shape[-2:]))
             # maps in flight: the gather is a collective on ONE process group - every rank issues the gathers of maps 0, 1, 2 ...
             # in that order, one at a time, whichever lane (thread, stream) predicted them (map_images hands each call its turn)
-            turn = getattr(self, "_gather_turn", None)
+            turn = self._gather_turn
             if turn is not None:
                 turn[0].wait(turn[1])
-            try:
-                return mdist.gather_members(local, E, (C, hh, ww), self.device, self._member_group,
-                                            getattr(self, "_member_root", None), force=getattr(self, "_member_force", False))
-            finally:
-                if turn is not None:
-                    turn[0].done(turn[1])
+            local = mdist.gather_members(local, E, (C, hh, ww), self.device, self._member_group, self._member_root,
+                                         force=self._member_force)
+            if turn is not None:
+                turn[0].done(turn[1])   # only a gather that succeeded hands the turn on; a failed one aborts the turnstile (run_lanes)
         return local
 
     def _predict_group(self, rgb_norms, ensemble_size, denoising_steps, batch_size, generators):

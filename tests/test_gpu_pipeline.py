@@ -244,6 +244,7 @@ def test_map_images_maps_in_flight_bit_identical(tiny):
         got = [getattr(o, key) for o in pipe.map_images(imgs[:4], in_flight=2, generators=gens()[:4], **kw)]
         assert all(np.array_equal(a, b) for a, b in zip(alone, got))
         assert len(pipe._lanes) == 3 and pipe._lanes[1][0].unet.ws is pipe.unet.ws and pipe._lanes[1][0].unet.pool is not pipe.unet.pool
+        assert pipe._lanes[0][0].unet is pipe.unet and pipe._lanes[0][0].vae is pipe.vae   # lane 0: the pipeline's own engines
     with pytest.raises(ValueError):
         list(pipe.map_images(imgs, in_flight=2, generator=gens()[0], **kw))
     with pytest.raises(ValueError):
@@ -255,6 +256,77 @@ def test_map_images_maps_in_flight_bit_identical(tiny):
     bad = [imgs[0], "not an image", imgs[1]]
     with pytest.raises(TypeError):
         list(pipe.map_images(bad, in_flight=2, **kw))
+
+
+@pytest.mark.parametrize("kind,key", [("depth", "depth_np"), ("normals", "normals_np")])
+def test_map_images_sees_settings_changed_between_calls(tiny, kind, key):
+    """The lanes of a ``map_images`` call run on the pipeline as it is at that call: a scheduler and a default step count set after
+    lanes exist reach every lane - each map is bit-identical to the lone call made after the change."""
+    from marigold_amd import schedulers as S
+    from marigold_amd import synthetic as syn
+    imgs = [syn.synthetic_image(64, 128, seed=k) for k in range(5)]
+
+    def gens():
+        return [torch.Generator(device="cuda:0").manual_seed(1000 + k) for k in range(len(imgs))]
+    pipe = _engine_pipe(tiny, kind, S.DDIMScheduler())
+    kw = dict(ensemble_size=3, processing_res=0, show_progress_bar=False)
+    if kind == "depth":
+        kw["color_map"] = None
+    assert len(list(pipe.map_images(imgs[:3], in_flight=3, generators=gens()[:3], denoising_steps=2, **kw))) == 3
+    pipe.scheduler = S.LCMScheduler()
+    pipe.default_denoising_steps = 1
+    if kind == "normals":
+        # the normals pipeline refuses the LCM scheduler, as the reference's does (marigold_normals_pipeline.py): the lanes refuse it
+        # like the lone call - they ran DDIM a moment ago - and the bit-identity is then checked with another DDIM schedule
+        with pytest.raises(RuntimeError, match="does not support the LCMScheduler"):
+            pipe(imgs[0], generator=gens()[0], **kw)
+        with pytest.raises(RuntimeError, match="does not support the LCMScheduler"):
+            list(pipe.map_images(imgs, in_flight=3, generators=gens(), **kw))
+        pipe.scheduler = S.DDIMScheduler(timestep_spacing="leading")
+    got = [getattr(o, key) for o in pipe.map_images(imgs, in_flight=3, generators=gens(), **kw)]
+    alone = [getattr(pipe(im, generator=g, **kw), key) for im, g in zip(imgs, gens())]
+    assert len(got) == len(imgs)
+    for k, (a, b) in enumerate(zip(alone, got)):
+        assert np.array_equal(a, b), f"{kind}: map {k} differs from the lone call after the change of settings"
+
+
+def _first_launches_worker(q):
+    """A fresh process whose first GPU work is five maps on three lanes - no serial warm-up: the lanes' threads make the first
+    launch of most kernels at the same time."""
+    import marigold_amd as M
+    from marigold_amd import synthetic as syn
+    from marigold_amd.arch import TINY_UNET, TINY_VAE
+    pipe = M.build_synthetic_pipeline("depth", TINY_UNET, TINY_VAE, default_processing_resolution=0).to("cuda:0")
+    imgs = [syn.synthetic_image(64, 128, seed=k) for k in range(5)]
+    kw = dict(denoising_steps=2, ensemble_size=3, processing_res=0, color_map=None, show_progress_bar=False)
+
+    def gens():
+        return [torch.Generator(device="cuda:0").manual_seed(1000 + k) for k in range(5)]
+    got = [o.depth_np for o in pipe.map_images(imgs, in_flight=3, generators=gens(), **kw)]
+    alone = [pipe(im, generator=g, **kw).depth_np for im, g in zip(imgs, gens())]
+    assert len(got) == 5
+    for k, (a, b) in enumerate(zip(alone, got)):
+        assert np.array_equal(a, b), f"map {k} of the first, concurrent launches differs from its lone call"
+    q.put("ok")
+
+
+def test_first_launches_from_three_lanes():
+    """The native library's once-per-kernel setup (mg_kernel_max_lds) with three lane threads making their first launches at once,
+    in a process that has done no GPU work before: every map bit-identical to its lone call.  Runs once - it does not hunt a race."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_first_launches_worker, args=(q,))
+    p.start()
+    try:
+        p.join(timeout=240)
+        assert not p.is_alive(), "the child is still running"
+        assert p.exitcode == 0
+        assert q.get(timeout=10) == "ok"
+    finally:
+        if p.is_alive():
+            p.terminate()
+            p.join(timeout=30)
 
 
 def test_pipeline_image_size_not_a_multiple_of_8(tiny):
@@ -519,6 +591,10 @@ def _mp_worker(rank, world, port, q, hw=(64, 128)):
     from marigold_amd import synthetic as syn
     from marigold_amd.arch import TINY_UNET, TINY_VAE
     pipe = M.build_synthetic_pipeline("depth", TINY_UNET, TINY_VAE, default_processing_resolution=0).to("cuda:0")
+    # lanes exist before the pipeline becomes member-parallel: their views are made per call, so they all take their turns below
+    warm = [syn.synthetic_image(hw[0], hw[1], seed=k) for k in range(3)]
+    assert len(list(pipe.map_images(warm, in_flight=3, generators=[torch.Generator(device="cuda:0").manual_seed(k) for k in range(3)],
+                                    denoising_steps=2, ensemble_size=3, processing_res=0, color_map=None, show_progress_bar=False))) == 3
     pipe.enable_member_parallel(root=0)
     img = syn.synthetic_image(hw[0], hw[1], seed=0)
     g = torch.Generator(device="cuda:0").manual_seed(5)
@@ -560,10 +636,16 @@ def test_member_parallel_two_ranks_share_one_gpu(hw):
     procs = [ctx.Process(target=_mp_worker, args=(r, 2, port, q, hw)) for r in range(2)]
     for p in procs:
         p.start()
-    got, many = q.get(timeout=240)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        got, many = q.get(timeout=240)
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:   # a lost turn fails the test within the timeouts above and leaves no process holding the GPU
+            if p.is_alive():
+                p.terminate()
+                p.join(timeout=30)
     pipe = M.build_synthetic_pipeline("depth", TINY_UNET, TINY_VAE, default_processing_resolution=0).to("cuda:0")
     for k, m_ in enumerate(many):   # five maps, two in flight per rank, each equal to the single-process map of its image / seed
         r_ = pipe(syn.synthetic_image(hw[0], hw[1], seed=k), denoising_steps=2, ensemble_size=3, processing_res=0, color_map=None,

@@ -17,8 +17,12 @@ class _StandIn(MarigoldDepthPipeline):
     def __init__(self, processing_res=0):
         self.unet = SimpleNamespace(device=torch.device("cpu"))
         self.default_processing_resolution = processing_res
+        self.empty_text_embed = None
         self._member_group = None
         self._member_parallel = False
+        self._member_root = None
+        self._member_force = False
+        self._lanes = []
         self.calls = []
 
     def __call__(self, image, generator=None, **kw):
