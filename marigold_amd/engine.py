@@ -9,7 +9,6 @@ the pipeline boundary).  Buffers come from a size-keyed pool that is recycled al
 program order, so the working set of a forward stays small and cache-friendly.
 """
 import math
-import os
 import threading
 from collections import defaultdict
 
@@ -17,48 +16,12 @@ import torch
 
 from . import _lib as L
 from . import ops as O
+from . import routes as R
 from . import tuning
 from . import weights as Wm
 from .arch import UNetConfig, VAEConfig, unet_up_resnet_channels
 
 LATENT_SCALE = 0.18215  # marigold_depth_pipeline.py:118
-
-
-def _tune(name, default):
-    """Tuning switch ``name`` (an environment variable): honoured ONLY under MARIGOLD_TUNING=1 (same-box A/B runs, sweeps);
-    without it the engine builds the product configuration whatever else the environment holds.  The library's switches sit
-    behind the same gate (csrc/runtime.hip::mg_tuning_int)."""
-    if os.environ.get("MARIGOLD_TUNING") != "1":
-        return default
-    v = os.environ.get(name)
-    if v is None:
-        return default
-    return v if isinstance(default, str) else type(default)(int(v))
-
-
-USE_PATCH = _tune("MARIGOLD_PATCH_CONV", True)          # patch-resident conv3x3 kernel where eligible
-FUSE_GN = _tune("MARIGOLD_FUSE_GN", "auto")             # auto | all | none: GroupNorm apply inside the conv
-GN_BYPRODUCT = _tune("MARIGOLD_GN_BYPRODUCT", True)     # GroupNorm partial sums from the producing convolution's epilogue
-VAE_FLASH_SMALL_MIN_BLOCKS = _tune("MARIGOLD_VAE_FLASH_MIN_BLOCKS", 100)   # flash512 for launches of at least this many 128-query blocks
-IGEMM73_CONV = _tune("MARIGOLD_IGEMM73_CONV", True)     # plain N = 320 k convolutions on the hand-placed 192 x 320 GEMM tile
-IGEMM73_CONV_MIN_TILES = _tune("MARIGOLD_IGEMM73_CONV_MIN_TILES", 120)
-IGEMM72_VAE = _tune("MARIGOLD_IGEMM72_VAE", True)       # plain 512-channel convolutions on the hand-placed implicit-GEMM tile
-GN_STATS_ONE_LAUNCH = _tune("MARIGOLD_GN_STATS_ONE_LAUNCH", True)   # the two sources of a skip concat in one statistics launch
-HEAD_CONV = _tune("MARIGOLD_HEAD_CONV", True)   # conv_norm_out + SiLU + conv_out (<= 4 channels) as one MG_OP_CONV3X3_HEAD launch
-HEAD_CONV_MIN_PIXELS = _tune("MARIGOLD_HEAD_CONV_MIN_PIXELS", 1 << 18)
-FOLD_SHORTCUT = _tune("MARIGOLD_FOLD_SHORTCUT", True)   # conv_shortcut as extra K of conv2 where conv2 runs on the implicit GEMM
-GN_SLAB = _tune("MARIGOLD_GN_SLAB", True)               # GroupNorm as one launch per norm (MG_OP_GN_SLAB) where it applies
-GN_SLAB_MIN_WG = _tune("MARIGOLD_GN_SLAB_MIN_WG", 64)   # ... from this many (image, channel window) workgroups,
-GN_SLAB_SMALL_KB = _tune("MARIGOLD_GN_SLAB_SMALL_KB", 48)   # or fewer when a workgroup's share of the tensor is at most this (small ensembles)
-ROWGEMM = _tune("MARIGOLD_ROWGEMM", True)               # row-resident GEMM (MG_OP_ROWGEMM) for the K = 320 token-local layers
-XATTN_KSPLIT = _tune("MARIGOLD_XATTN_KSPLIT", True)     # deep-level collapsed cross-attention as the K-split kernel
-ROWGEMM_WIDE = _tune("MARIGOLD_ROWGEMM_WIDE", True)     # ... and its K = 640 form for the 640-channel level's QKV / GEGLU
-XATTN_IN_GEGLU = _tune("MARIGOLD_XATTN_IN_GEGLU", True)   # the collapsed cross-attention as the prologue of the row-resident GEGLU launch
-ROWGEMM_MIN_M = _tune("MARIGOLD_ROWGEMM_MIN_M", 9216)   # below: the tile GEMM (one 96 x 96 member is 72 128-row workgroups)
-# Measurement probe (never the product path): every launch of these op kinds is issued TWICE (idempotent kinds only: GroupNorm
-# 2,3,4,9 / flash attention 6,11 write outputs they do not read) - the map's extra time is what that class costs with the
-# other lanes running beside it, i.e. the most a faster kernel of that class could return (tools: scripts/gpu_ab_env.sh)
-TWICE_KINDS = tuple(int(k) for k in _tune("MARIGOLD_TWICE_KINDS", "").split(",") if k)
 
 
 class Act:
@@ -284,9 +247,7 @@ class Builder:
         for x in xs:
             if x is None:
                 continue
-            if isinstance(x, Act) and x.gn is not None:
-                self.pool.put(x.gn[0])
-                x.gn = None
+            self.drop_gn(x)
             self.pool.put(x.t if isinstance(x, Act) else x)
 
     def drop_gn(self, x):
@@ -307,75 +268,11 @@ class Builder:
             # the program's own split-K workspace: programs on concurrent streams - two maps in flight - must not share the library's
             O.Raw(op).splitk_ws = self.zeros_persistent("splitk_ws", O.SPLITK_WS_BYTES)
         self.seq.add(tuning.apply(op), label)   # (MG_OP_IGEMM: the measured tile / split-K choice where the table has one)
-        if op.kind in TWICE_KINDS:
+        if op.kind in R.TWICE_KINDS:
             assert op.kind in (L.OP_GN_STATS, L.OP_GN_FINALIZE, L.OP_GN_APPLY, L.OP_GN_SLAB, L.OP_FLASH_ATTN64, L.OP_FLASH_ATTN512)
             self.seq.add(op, label + ".again")
 
     # ---- primitive layers ----------------------------------------------------------------
-    @staticmethod
-    def rowgemm_ok(x):
-        """Token-local Linear layers of this activation on MG_OP_ROWGEMM?  K = 320 is what the kernel is built for (a wave
-        keeps 32 rows x 320 channels in 80 registers); whole 32-row tiles inside an image (the V^T section and the folded
-        GroupNorm are per image), enough 384-row workgroups for the chip, and the permuted V^T the QKV form writes."""
-        return ROWGEMM and x.C == 320 and x.HW % 32 == 0 and x.M >= ROWGEMM_MIN_M
-
-    @staticmethod
-    def rowgemm_wide_ok(x):
-        """The 640-channel level: MG_OP_ROWGEMM's K = 640 form (8 waves x 32 rows x 640 channels in 160 registers each) pays
-        only where the columns can be split over two workgroups per 256-row block - the QKV projection (97 -> 80 us) and GEGLU
-        (216 -> 194 us); the whole-row-statistics layers stay on the tile GEMM (90 workgroups: 64 vs 49 us),
-        profiles/r3_rowgemm_k640.log."""
-        return ROWGEMM and ROWGEMM_WIDE and x.C == 640 and x.HW % 32 == 0 and x.M >= 60 * 256
-
-    @staticmethod
-    def rowgemm_cfg(M, N, whole_rows=False, xattn=False, K=320):
-        if K == 640:
-            nb = -(-M // 256)
-            return dict(waves=8, nsplit=max(1, min(N // 128, 256 // nb)))
-        return Builder._rowgemm_cfg320(M, N, whole_rows, xattn)
-
-    @staticmethod
-    def _rowgemm_cfg320(M, N, whole_rows=False, xattn=False):
-        """-> dict(waves=, nsplit=) of an MG_OP_ROWGEMM launch: 12 waves (384 rows) per workgroup when that still gives the
-        chip >= 160 workgroups, else 8, else 4 with the N / 64 column stages shared out over several workgroups per row
-        block (not for the forms that take whole-row statistics) - measured per ensemble size,
-        profiles/r3_rowgemm_small_batch.log."""
-        if M >= 160 * 384:
-            return dict(waves=12)
-        if M >= 120 * 256 or xattn:
-            return dict(waves=8)
-        if whole_rows:
-            return dict(waves=4)
-        nwg = -(-M // 128)
-        return dict(waves=4, nsplit=max(1, min(N // 128, round(300 / nwg))))
-
-    def gn_slab_ok(self, srcs, apply):
-        """One-launch GroupNorm (MG_OP_GN_SLAB: a workgroup owns whole groups of an image over all rows)?  UNet-sized
-        maps with enough (image, channel window) pairs to fill the chip; the normalising form keeps the rows in registers
-        (<= 48 rows per thread).  Large tensors (UNet level 0, the VAE) stay on the chunked statistics / apply passes."""
-        B, HW = srcs[0].B, srcs[0].HW
-        C = sum(x.C for x in srcs)
-        if not GN_SLAB or len(srcs) > 2 or C % self.groups or any(x.C % 4 for x in srcs):
-            return False
-        cpg = C // self.groups
-        cw = cpg * (4 // math.gcd(cpg, 4))
-        nwg = B * (C // cw)
-        # (round 5) few workgroups are fine while each one's share is small: a single member's 24 x 24 / 12 x 12 maps (368 KB -
-        # 1.5 MB) took a statistics launch (13-16 us: tickets, last-block finalize) + an apply launch (8-9 us) for lack of 64 of them
-        if not (16 <= cw <= 128) or HW > 16384 or (nwg < GN_SLAB_MIN_WG and B * HW * C * 2 > nwg * GN_SLAB_SMALL_KB * 1024):
-            return False
-        # measured per layer (profiles/r3_groupnorm_slab_vs_chunked.log): a slab pass beats statistics + apply only while
-        # the tensor is small enough that the chunked passes are launch/latency-bound (<= 16 MiB: UNet levels 2-3), or
-        # when it replaces the TWO statistics launches of a skip concat at levels 1-3; on the big level-0 / VAE tensors
-        # its B * C / cw workgroups are too few and the chunked passes win by 1.3-1.8x
-        if not ((len(srcs) == 2 and HW <= 2304) or B * HW * C * 2 <= (16 << 20)):
-            return False
-        if apply:
-            nt = 1024 if HW * cw * 2 >= 48 * 1024 else 256
-            if -(-HW // (nt // (cw // 4))) > 48:
-                return False
-        return True
-
     def gn_slab(self, srcs, name, eps, silu, apply):
         """-> (scale/shift buffer, normalised Act | None) in ONE launch."""
         x = srcs[0]
@@ -387,10 +284,10 @@ class Builder:
                            x1=srcs[1].t if len(srcs) > 1 else None, C0=x.C), f"{name}.slab" + ("+apply" if apply else ""))
         return ss, out
 
-    def gn_scale_shift(self, srcs, name, eps):
+    def gn_scale_shift(self, srcs, name, eps, stats):
         """GroupNorm statistics over the channel concat of ``srcs`` (never materialised: one statistics launch per
-        source into a shared partial table) -> fp32 [B][2][C] (scale, shift) buffer."""
-        if self.gn_slab_ok(srcs, False):
+        source into a shared partial table) -> fp32 [B][2][C] (scale, shift) buffer.  ``stats``: routes.NormRoute.stats."""
+        if stats == R.STATS_SLAB:
             return self.gn_slab(srcs, name, eps, False, False)[0]
         B, HW = srcs[0].B, srcs[0].HW
         C = sum(x.C for x in srcs)
@@ -400,25 +297,20 @@ class Builder:
             self.add(O.gn_finalize(part, self.ws.vec(f"{name}.weight"), self.ws.vec(f"{name}.bias"), ss, B=B, C=C,
                                    groups=self.groups, slots=slots, HW=HW, eps=eps), f"{name}.finalize")
             return ss
-        # ~288 (chunk, image) blocks - about one per CU - of >= 32 rows: with eight row loads in flight per thread and the
-        # chunk's tail fetched as one batch (round 3) a block streams its rows in 2-4 round trips, and the cost that is left
-        # grows with the NUMBER of blocks (tickets, the last block's table reduction): 59 MB at E = 10 takes 16.3 us with 24-32
-        # chunks per image against 23.5 with the 76 of round 2 (28.7 before the tail fix), profiles/r3_gn_stats_chunks.log
-        chunks = max(1, min(HW // 32, 64, max(8, 288 // B)))
+        chunks = R.gn_stats_chunks(B, HW)
         slots = chunks * len(srcs)
         part = self.raw(B * slots * self.groups * 2 * 4)
         ss = self.raw(B * 2 * C * 4)
         counters = self.zeros_persistent("gn_counters", 4 * max(B, 1024))   # stream-ordered reuse; left zero by every use
         # the image's last-arriving statistics block turns the partial table into scale / shift (no finalize launch); the two
         # sources of a skip concat share one launch
-        assert len(srcs) <= 2
         coff = 0
-        for k, grp in enumerate([srcs] if GN_STATS_ONE_LAUNCH else [[x] for x in srcs]):
+        for k, grp in enumerate([srcs] if R.GN_STATS_ONE_LAUNCH else [[x] for x in srcs]):
             x1 = grp[1] if len(grp) > 1 else None
             self.add(O.gn_stats(grp[0].t, part, B=B, HW=HW, C=grp[0].C, chunks=chunks, groups=self.groups, Ctot=C, coff=coff,
                                 slot0=k * chunks, slots=slots, gamma=self.ws.vec(f"{name}.weight"), beta=self.ws.vec(f"{name}.bias"),
                                 ss=ss, counters=counters, eps=eps, x1=x1.t if x1 else None, C1=x1.C if x1 else 0),
-                     f"{name}.stats" + (f"{k}" if len(srcs) > 1 and not GN_STATS_ONE_LAUNCH else ""))
+                     f"{name}.stats" + (f"{k}" if len(srcs) > 1 and not R.GN_STATS_ONE_LAUNCH else ""))
             coff += grp[0].C
         self.free(part)
         return ss
@@ -432,56 +324,20 @@ class Builder:
                             x1=srcs[1].t if len(srcs) > 1 else None, C0=x.C), f"{name}.apply")
         return out
 
+    def norm(self, srcs, name, eps, silu, route):
+        """GroupNorm of the concat of ``srcs`` as ``route`` (a routes.NormRoute) says -> (scale / shift buffer, normalised Act |
+        None where the consuming launch applies them)."""
+        if route.apply == R.APPLY_SLAB:
+            return self.gn_slab(srcs, name, eps, silu, True)
+        ss = self.gn_scale_shift(srcs, name, eps, route.stats)
+        return ss, (None if route.apply == R.APPLY_CONSUMER else self.gn_apply(srcs, ss, name, silu))
+
     def group_norm(self, x, name, eps, silu):
-        if self.gn_slab_ok([x], True):
-            ss, out = self.gn_slab([x], name, eps, silu, True)
-            self.free(ss)
-            return out
-        ss = self.gn_scale_shift([x], name, eps)
-        out = self.gn_apply([x], ss, name, silu)
+        ss, out = self.norm([x], name, eps, silu, R.norm_route(x.B, x.HW, (x.C,), self.groups))
         self.free(ss)
         return out
 
     # ---- patch-resident conv3x3 (MG_OP_CONV3X3) ------------------------------------------------------
-    @staticmethod
-    def patch_eligible(H, W, B=None, N=None, subpix=False):
-        """16-pixel-wide tiles: maps that waste little of them (the 24x24 / 12x12 levels stay on the implicit GEMM,
-        whose split-K also fills the chip there) and - when the batch and width are given - enough workgroups for the
-        256 CUs (a single member at 96x96 has 36-72 spatial tiles: the implicit GEMM's smaller tiles fill the chip)."""
-        if not ((H >= 32 and W >= 32) or (H % 16 == 0 and W % 16 == 0)):
-            return False
-        if B is None:
-            return True
-        if N % 256 == 0:
-            th, bn = 16, 256
-        elif N == 320 or (subpix and N % 320 == 0):
-            th, bn = 8, 320
-        else:
-            th, bn = 16, 128
-        grid = B * -(-H // th) * -(-W // 16) * -(-N // bn) * (4 if subpix else 1)
-        return grid >= 240
-
-    def fuse_norm_into_conv(self, B, H, W, Cin, N):
-        """Apply the GroupNorm affine + SiLU inside the convolution's operand staging?  The fix-up runs once per
-        workgroup and channel tile, i.e. (output-channel tiles) x 1.27 (halo) times per element, on VALU that the
-        MFMAs do not hide: it pays when one workgroup covers all output channels (N <= 320) or when the separate
-        pass would be HBM-bound on a tensor that no cache holds (profiles/r2_sweep3_patch_conv.log)."""
-        mode = FUSE_GN
-        if mode not in ("auto", "auto5"):
-            return mode == "all"
-        tiles_n = 1 if N in (128, 256, 320) else -(-N // (256 if N % 256 == 0 else 128))
-        if mode == "auto5":   # the rule of rounds 2-5 (A/B)
-            return tiles_n == 1 or B * H * W * Cin * 2 >= (192 << 20)
-        # Round 6, measured layer by layer with the norm fused everywhere / nowhere (profiles/r6_ab_fuse_gn_per_layer.log): the
-        # fix-up is VALU beside the MFMAs, the separate pass is HBM traffic - and with two maps in flight (section 6b) an HBM-bound
-        # pass runs under the other map's matrix work.  Fused wins on the VAE's 128 / 256-channel levels (tensors of 0.75-1.5 GB:
-        # +0.45 ... +0.97 ms per block unfused, and with two lanes the 256-channel level alone +1.4 ms per map); it LOSES where the plain convolution gets a hand-placed four-wave kernel that the
-        # fused one does not - the UNet's 320-channel level from six members (-0.1 ... -0.66 ms per block) - and on the VAE's
-        # 512-channel 192 x 192 level (two output-channel tiles repeat the fix-up: -0.17 ... -0.24 ms per block).
-        if N == 320:
-            return B * -(-H // 12) * -(-W // 16) < 280   # (six members: -1.1 ms with two lanes, -3 ms alone; five: a tie)
-        return tiles_n == 1
-
     def conv3x3p(self, srcs, name, cout, *, ss=None, silu=False, rowvec=None, residual=None, out=None, subpix=False):
         x = srcs[0]
         skip = srcs[1] if len(srcs) > 1 else None
@@ -494,30 +350,25 @@ class Builder:
                   silu=silu, bias=self.ws.bias(name), rowvec=rowvec, rowvec_bcast=rowvec is not None,
                   residual=None if residual is None else residual.t, wz=cout * 4 * Cin if subpix else 0)
         op = O.conv3x3(x.t, w, out.t, **kw)
-        # (round 4) the GroupNorm statistics of the output as a by-product of the 12-wave tiles' epilogue - the tensors of the
-        # VAE's 768^2 / 384^2 levels are re-read at HBM speed otherwise (4.6 ms of statistics passes per decode at E = 10)
-        cpg = cout // self.groups
         self.drop_gn(out)   # this launch rewrites `out`: a table left by an earlier producer describes other values
-        if GN_BYPRODUCT and cout % self.groups == 0 and cpg in (4, 8, 16, 32) and out.HW * cout * 2 >= (8 << 20):
+        if R.gn_byproduct_ok(out.HW, cout, self.groups):   # the GroupNorm statistics of the output from this launch's epilogue
             slots = O.conv3x3_gn_slots(op, getattr(self.seq, "f16", False))
             if slots > 0:
                 part = self.raw(x.B * slots * self.groups * 2 * 4)
-                op = O.conv3x3(x.t, w, out.t, gn_part=part, gn_cpg=cpg, gn_slots=slots, **kw)
+                op = O.conv3x3(x.t, w, out.t, gn_part=part, gn_cpg=cout // self.groups, gn_slots=slots, **kw)
                 out.gn = (part, slots)
         self.add(op, name)
         return out
 
-    def conv_on_gemm(self, B, H, W, Cin, cout):
-        """Does a plain stride-1 3x3 convolution of this shape run on MG_OP_IGEMM (True) or on the patch-resident kernel?
-        (the rule of ``conv3x3`` below)"""
-        M = B * H * W
-        big = (IGEMM72_VAE and cout % 256 == 0 and Cin >= 512 and -(-M // 256) * (cout // 256) >= 720) or \
-              (IGEMM73_CONV and cout % 320 == 0 and cout % 256 != 0 and Cin >= 320 and -(-M // 192) * (cout // 320) >= IGEMM73_CONV_MIN_TILES)
-        return big or not (USE_PATCH and self.patch_eligible(H, W, B, cout, False))
-
-    def conv3x3(self, x, name, cout, *, stride=1, pad=1, up=None, rowvec=None, residual=None, out=None, fold=None):
-        """``fold`` = (shortcut layer name, x0, x1 | None): that 1x1 convolution of x0 (+ x1) rides as extra K (implicit GEMM only:
-        the caller asks ``conv_on_gemm`` first)."""
+    def conv3x3(self, x, name, cout, *, stride=1, pad=1, up=None, rowvec=None, residual=None, out=None, fold=None, route=None):
+        """3x3 convolution of ``x`` as ``route`` (routes.conv_route; asked here for a convolution outside a ResNet block) says.
+        ``fold`` = (shortcut layer name, x0, x1 | None): that 1x1 convolution of x0 (+ x1) rides as extra K (routes.CONV_IGEMM only)."""
+        if route is None:
+            route = R.conv_route(x.B, x.H, x.W, x.C, cout, stride, pad, up, rowvec is not None or residual is not None)
+        if route == R.CONV_PATCH:
+            return self.conv3x3p([x], name, cout, rowvec=rowvec, residual=residual, out=out)
+        if route == R.CONV_PATCH_SUBPIX:
+            return self.conv3x3p([x], name, cout, out=out, subpix=True)
         H, W = (up if up else (x.H, x.W))
         if stride == 1:
             Ho, Wo = H, W
@@ -528,40 +379,20 @@ class Builder:
         if out is None:
             out = self.new(x.B, Ho, Wo, cout)
         self.drop_gn(out)
-        # (round 4) plain 512-channel VAE convolutions with >= 720 tiles of 256 x 256: the hand-placed implicit-GEMM tile
-        # (variant 72, picked by the library) runs them at 1 284 TFLOP/s against 1 202 / 1 050 for the patch kernels
-        if fold is not None:
+        kw = dict(B=x.B, H=x.H, W=x.W, Cin=x.C, N=cout)
+        if route == R.CONV_IGEMM_SUBPIX:
+            self.add(O.igemm(x.t, self.ws.conv3x3_subpix(name), out.t, Ho=x.H, Wo=x.W, taps=4, stride=1, pad=1, bias=self.ws.bias(name),
+                             batch_z=4, zstrides=(0, cout * 4 * x.C, 0, 0), **kw), name)
+        elif fold is not None:
             sc, x0, x1 = fold
-            assert stride == 1 and pad == 1 and up is None and residual is None and self.conv_on_gemm(x.B, x.H, x.W, x.C, cout)
             wf, bf = self.ws.conv3x3_fold(name, sc)
             cx = x0.C + (x1.C if x1 is not None else 0)
-            self.add(O.igemm(x.t, wf, out.t, B=x.B, H=x.H, W=x.W, Cin=x.C, Ho=Ho, Wo=Wo, N=cout, taps=9, stride=1, pad=1, bias=bf,
+            self.add(O.igemm(x.t, wf, out.t, Ho=Ho, Wo=Wo, taps=9, stride=1, pad=1, bias=bf, rowvec=rowvec, rowvec_bcast=rowvec is not None,
+                             fold=(x0.t, None if x1 is None else x1.t, x0.C, cx), **kw), f"{name}+{sc.rsplit('.', 1)[-1]}")
+        else:
+            self.add(O.igemm(x.t, self.ws.conv3x3(name), out.t, Ho=Ho, Wo=Wo, taps=9, stride=stride, pad=pad, up=up, bias=self.ws.bias(name),
                              rowvec=rowvec, rowvec_bcast=rowvec is not None,
-                             fold=(x0.t, None if x1 is None else x1.t, x0.C, cx)), f"{name}+{sc.rsplit('.', 1)[-1]}")
-            return out
-        big_gemm = (IGEMM72_VAE and up is None and stride == 1 and pad == 1 and cout % 256 == 0 and x.C >= 512 and
-                    -(-x.M // 256) * (cout // 256) >= 720)
-        # ... and the plain N = 320 k convolutions with a chip's worth of 192 x 320 tiles (the 640-channel level at 48 x 48) on
-        # variant 73: 640 -> 640 1 193 vs 1 147-1 182 for the four-wave patch kernel, 1280 -> 640 1 303 vs 1 267-1 277
-        # (round 5: from 120 tiles - six members at 48 x 48; with eight the four-wave patch kernel ran these at 760-790 TFLOP/s
-        # where the GEMM tile does 1 170-1 300: the >= 200 of round 4 had been set at E = 10 only)
-        big_gemm = big_gemm or (IGEMM73_CONV and up is None and stride == 1 and pad == 1 and cout % 320 == 0 and cout % 256 != 0 and
-                                x.C >= 320 and -(-x.M // 192) * (cout // 320) >= IGEMM73_CONV_MIN_TILES)
-        if USE_PATCH and not big_gemm and stride == 1 and pad == 1 and self.patch_eligible(x.H, x.W, x.B, cout, up is not None):
-            if up is None:
-                return self.conv3x3p([x], name, cout, rowvec=rowvec, residual=residual, out=out)
-            if up == (2 * x.H, 2 * x.W) and rowvec is None and residual is None:
-                return self.conv3x3p([x], name, cout, out=out, subpix=True)
-        if up and up == (2 * x.H, 2 * x.W) and stride == 1 and pad == 1 and rowvec is None and residual is None:
-            # exact 2x nearest up-sampling: four 2x2 convolutions on the low-resolution input (4/9 of the MACs)
-            self.add(O.igemm(x.t, self.ws.conv3x3_subpix(name), out.t, B=x.B, H=x.H, W=x.W, Cin=x.C, Ho=x.H, Wo=x.W,
-                             N=cout, taps=4, stride=1, pad=1, bias=self.ws.bias(name), batch_z=4,
-                             zstrides=(0, cout * 4 * x.C, 0, 0)), name)
-            return out
-        self.add(O.igemm(x.t, self.ws.conv3x3(name), out.t, B=x.B, H=x.H, W=x.W, Cin=x.C, Ho=Ho, Wo=Wo,
-                         N=cout, taps=9, stride=stride, pad=pad, up=up, bias=self.ws.bias(name),
-                         rowvec=rowvec, rowvec_bcast=rowvec is not None,
-                         residual=None if residual is None else residual.t), name)
+                             residual=None if residual is None else residual.t, **kw), name)
         return out
 
     def conv_from_nchw(self, src0, src1, name, B, H, W, C0, C1, cout, bcast0=False, members0=0):
@@ -578,17 +409,10 @@ class Builder:
         self.free(col)
         return out
 
-    def head_conv_ok(self, x, cout):
-        """norm + SiLU + conv3x3 to <= 4 channels as one MG_OP_CONV3X3_HEAD launch?  The VAE decoder's head (768^2 maps: 0.80 ms
-        against 0.58 + 1.22 ms for the normalising pass + the implicit GEMM at ten members); NOT the UNet's - its 96^2 maps are
-        360 workgroups of ten LDS-bound passes (79-102 us at ten members, 64-101 at one) where the pass + GEMM pair takes 54 / 33 us
-        (profiles/r5_ops_hipevents*.tsv of the two final sessions)."""
-        return HEAD_CONV and cout <= 4 and x.C % 32 == 0 and x.B * x.H * x.W >= HEAD_CONV_MIN_PIXELS
-
     def norm_conv_to_nchw(self, x, norm, eps, key, w4, bias, out, cout, **kw):
         """conv_norm_out -> SiLU -> conv_out -> the pointwise tail (diffusers' output heads of the UNet and the VAE decoder)."""
-        if self.head_conv_ok(x, cout):
-            ss = self.gn_scale_shift([x], norm, eps)
+        if R.head_conv_ok(x.B, x.H, x.W, x.C, cout):
+            ss, _ = self.norm([x], norm, eps, True, R.norm_route(x.B, x.HW, (x.C,), self.groups, consumer=True))
             self.conv_to_nchw(x, key, w4, bias, out, cout, head_ss=ss, **kw)
             self.free(ss)
         else:
@@ -640,51 +464,38 @@ class Builder:
     # ---- composite blocks ----------------------------------------------------------------
     def resnet(self, x, name, cout, eps, temb_row=None, skip=None):
         """diffusers ResnetBlock2D on the channel concat of ``x`` and ``skip`` (the UNet's up blocks; the concat is
-        never materialised on the patch path).  norm -> SiLU is applied inside the convolution's operand staging where
-        ``fuse_norm_into_conv`` says it pays, else by one pass that also performs the concat."""
+        never materialised on the patch path), emitted as routes.resnet_route says: norm -> SiLU inside the convolution's
+        operand staging, or by one pass that also performs the concat."""
         srcs = [x] + ([skip] if skip is not None else [])
-        Cin = sum(y.C for y in srcs)
-        patch = USE_PATCH and self.patch_eligible(x.H, x.W, x.B, cout)
+        sc = f"{name}.conv_shortcut"
+        r = R.resnet_route(x.B, x.H, x.W, tuple(y.C for y in srcs), cout, self.ws.has(sc), self.groups)
 
-        def norm_conv(inputs, norm, conv, rowvec=None, residual=None, out=None, fold=None):
-            cin = sum(y.C for y in inputs)
-            fused = patch and self.fuse_norm_into_conv(x.B, x.H, x.W, cin, cout)
-            assert fold is None or not fused
-            if not fused and self.gn_slab_ok(inputs, True):   # statistics + normalisation (+ the concat) in one launch
-                ss, h = self.gn_slab(inputs, norm, eps, True, True)
-                y = self.conv3x3(h, conv, cout, rowvec=rowvec, residual=residual, out=out, fold=fold)
-                self.free(h, ss)
-                return y
-            ss = self.gn_scale_shift(inputs, norm, eps)
-            if fused:
+        def norm_conv(inputs, norm, nr, conv, cr, rowvec=None, residual=None, out=None, fold=None):
+            ss, h = self.norm(inputs, norm, eps, True, nr)
+            if h is None:
                 y = self.conv3x3p(inputs, conv, cout, ss=ss, silu=True, rowvec=rowvec, residual=residual, out=out)
             else:
-                h = self.gn_apply(inputs, ss, norm, True)
-                y = self.conv3x3(h, conv, cout, rowvec=rowvec, residual=residual, out=out, fold=fold)
+                y = self.conv3x3(h, conv, cout, rowvec=rowvec, residual=residual, out=out, fold=fold, route=cr)
                 self.free(h)
             self.free(ss)
             return y
 
-        h1 = norm_conv(srcs, f"{name}.norm1", f"{name}.conv1", rowvec=temb_row)
-        sc = f"{name}.conv_shortcut"
-        # (round 5) where conv2 runs on the implicit GEMM (the 48 x 48 ... 12 x 12 levels) its conv_shortcut - a 1x1 convolution of the
-        # block's INPUT - rides as extra K of conv2: one launch instead of two, no residual tensor written and read back
-        if (FOLD_SHORTCUT and self.ws.has(sc) and all(y.C % 64 == 0 for y in srcs) and cout % 64 == 0 and
-                not (patch and self.fuse_norm_into_conv(x.B, x.H, x.W, cout, cout)) and self.conv_on_gemm(x.B, x.H, x.W, cout, cout)):
-            out = norm_conv([h1], f"{name}.norm2", f"{name}.conv2", fold=(sc, x, skip))
-        elif self.ws.has(f"{name}.conv_shortcut"):
-            res = self.dense(x, self.ws.mat(f"{name}.conv_shortcut"), self.ws.bias(f"{name}.conv_shortcut"),
-                             cout, label=f"{name}.conv_shortcut", skip=skip)
-            out = norm_conv([h1], f"{name}.norm2", f"{name}.conv2", residual=res, out=res)  # in-place residual add
+        h1 = norm_conv(srcs, f"{name}.norm1", r.norm1, f"{name}.conv1", r.conv1, rowvec=temb_row)
+        if r.shortcut == R.SHORTCUT_FOLDED:
+            out = norm_conv([h1], f"{name}.norm2", r.norm2, f"{name}.conv2", r.conv2, fold=(sc, x, skip))
+        elif r.shortcut == R.SHORTCUT_LAUNCH:
+            res = self.dense(x, self.ws.mat(sc), self.ws.bias(sc), cout, label=sc, skip=skip)
+            out = norm_conv([h1], f"{name}.norm2", r.norm2, f"{name}.conv2", r.conv2, residual=res, out=res)  # in-place residual add
         else:
-            assert skip is None and Cin == cout
-            out = norm_conv([h1], f"{name}.norm2", f"{name}.conv2", residual=x)
+            assert skip is None and x.C == cout, f"{name}: the checkpoint has no conv_shortcut for {x.C} -> {cout} channels"
+            out = norm_conv([h1], f"{name}.norm2", r.norm2, f"{name}.conv2", r.conv2, residual=x)
         self.free(h1)
         return out
 
-    def self_attention(self, h, st, prefix, norm, heads, st_out):
+    def self_attention(self, h, st, prefix, norm, heads, st_out, r):
         """h += to_out(attn(LN(h))) with the LayerNorm folded into the fused QKV projection (``st`` = row statistics of
-        h from its producer); the to_out epilogue writes the statistics of the new h into ``st_out``.  Head dim 64."""
+        h from its producer); the to_out epilogue writes the statistics of the new h into ``st_out``.  Head dim 64.
+        ``r``: the block's routes.TransformerRoute."""
         C, B, T, M = h.C, h.B, h.HW, h.M
         ldvt = (T + 63) // 64 * 64
         qk = self.raw(M * 2 * C * 2)
@@ -692,11 +503,10 @@ class Builder:
         # V^T with its keys in the QK^T accumulator order inside groups of 16: the QKV epilogue skips its lane regroup and
         # the attention kernel (generation 3) its v_permlane32_swap - a format private to this producer / consumer pair
         perm = T % 16 == 0
-        rg = perm and self.rowgemm_ok(h)
-        if rg or (perm and self.rowgemm_wide_ok(h)):
+        if r.qkv is not None:
             self.add(O.rowgemm(h.t, self.ws.rg_qkv_ln(prefix, norm), qk, M=M, K=C, N=3 * C, form=L.RG_QKV, ldo=2 * C,
                                ln_in=self.ln_mean_rstd(st, M, C), vt=vt, tokens=T, ldt=ldvt, trans_from=2 * C,
-                               **self.rowgemm_cfg(M, 3 * C, K=C)), f"{prefix}.qkv")
+                               **r.qkv), f"{prefix}.qkv")
         else:
             wqkv, g, c = self.ws.qkv_ln(prefix, norm)
             self.add(O.igemm(h.t, wqkv, qk, B=B, H=T, W=1, Cin=C, Ho=T, Wo=1, N=3 * C, ldo=2 * C, out2=vt,
@@ -707,36 +517,30 @@ class Builder:
                                 ldo=C, ldvt=ldvt, sq=T * 2 * C, sk=T * 2 * C, svt=C * ldvt, so=T * C,
                                 scale=1.0 / math.sqrt(C // heads), vt_perm=perm, ws=ws, ws_bytes=O.FLASH_WS_BYTES_AUTO), f"{prefix}.flash")
         self.free(qk)
-        if rg:
+        if r.whole_rows is not None:
             self.add(O.rowgemm(o.t, self.ws.rg_mat(f"{prefix}.to_out.0"), h.t, M=M, K=C, N=C, residual=h.t,
-                               ln_out=self.ln_mean_rstd(st_out, M, C), **self.rowgemm_cfg(M, C, whole_rows=True)), f"{prefix}.to_out")
+                               ln_out=self.ln_mean_rstd(st_out, M, C), **r.whole_rows), f"{prefix}.to_out")
         else:
             self.dense(o, self.ws.mat(f"{prefix}.to_out.0"), self.ws.bias(f"{prefix}.to_out.0"), C,
                        residual=h, out=h, label=f"{prefix}.to_out", ln_out=st_out)
         self.free(o)
 
-    def cross_attention2(self, h, st, prefix, norm, heads, ctx, st_out):
+    def cross_attention2(self, h, st, prefix, norm, heads, ctx, st_out, r):
         """h += attn2(LN(h), ctx) with the 2-token context collapsed into two thin GEMMs and the LayerNorm folded into
-        the first one (``st``: row statistics of h, ``st_out``: of the new h for the next folded LayerNorm)."""
+        the first one (``st``: row statistics of h, ``st_out``: of the new h for the next folded LayerNorm), in the form
+        ``r.xattn`` names (never routes.XATTN_IN_GEGLU_LAUNCH: that one is part of the GEGLU launch)."""
         C, M = h.C, h.M
-        if XATTN_KSPLIT and ROWGEMM and 2 * heads <= 64 and C in (640, 1280) and M % 32 == 0:
-            # the deep levels: 32-row workgroups whose four waves split K (scores) and the output channels (blend)
+        if r.xattn_cfg is not None:
+            # a single row-resident launch (the K-split kernel at the deep levels): the residual stream is read once and written once
             self.add(O.rowgemm(h.t, self.ws.rg_cross_ln(prefix, ctx, heads, norm), h.t, M=M, K=C, N=64, form=L.RG_XATTN,
                                ln_in=self.ln_mean_rstd(st, M, C), ln_out=self.ln_mean_rstd(st_out, M, C),
-                               sm_cols=2 * heads, sm_scale=1.0 / math.sqrt(C // heads)), f"{prefix}.scores+softmax2+blend")
-            return
-        if 2 * heads <= 64 and self.rowgemm_ok(h):
-            # the same single launch in the row-resident form: the residual stream is read once (registers) and written once
-            self.add(O.rowgemm(h.t, self.ws.rg_cross_ln(prefix, ctx, heads, norm), h.t, M=M, K=C, N=64, form=L.RG_XATTN,
-                               ln_in=self.ln_mean_rstd(st, M, C), ln_out=self.ln_mean_rstd(st_out, M, C),
-                               sm_cols=2 * heads, sm_scale=1.0 / math.sqrt(C // heads), **self.rowgemm_cfg(M, C, xattn=True)),
-                     f"{prefix}.scores+softmax2+blend")
+                               sm_cols=2 * heads, sm_scale=1.0 / math.sqrt(C // heads), **r.xattn_cfg), f"{prefix}.scores+softmax2+blend")
             return
         # ONE launch on the tile GEMM: scores GEMM with the LayerNorm folded in, the 2-key softmax on its accumulators, the
         # probabilities as the register operand of the blend GEMM (x the context's values pushed through to_out), + bias +
         # residual, in place on the residual stream, (mean, rstd) of the new rows for the next folded LayerNorm
         wqk, g, c, vot, npad = self.ws.cross_ln(prefix, ctx, heads, norm)
-        if npad == 64 and C % 32 == 0:
+        if r.xattn == R.XATTN_TILE:
             self.add(O.linear(h.t, wqk, h.t, M=M, K=C, N=npad, epi=L.EPI_XATTN2, ln_in=self.ln_mean_rstd(st, M, C),
                               ln_g=g, ln_c=c, sm_scale=1.0 / math.sqrt(C // heads), sm_cols=2 * heads, out2=vot, c2=C, ldo=C,
                               bias=self.ws.bias(f"{prefix}.to_out.0"), residual=h.t, ldr=C,
@@ -756,38 +560,31 @@ class Builder:
         that consumes one takes the raw residual stream and corrects in its epilogue (MG_OP_IGEMM ln_in), with the row
         statistics written by the epilogue of the GEMM that produced the stream (ln_out)."""
         C = x.C
+        r = R.transformer_route(x.B, x.HW, C, heads, self.groups)
+        k320 = r.rows == R.ROWS_K320
         st = [self.ln_table(x.M, C) for _ in range(3)]
-        rg = self.rowgemm_ok(x)
-        if rg:
-            # the GroupNorm never runs as a pass: statistics only, its scale / shift applied while proj_in loads its rows
-            if self.gn_slab_ok([x], False):
-                ss, _ = self.gn_slab([x], f"{name}.norm", 1e-6, False, False)
-            else:
-                ss = self.gn_scale_shift([x], f"{name}.norm", 1e-6)
+        ss, g = self.norm([x], f"{name}.norm", 1e-6, False, r.norm)
+        if k320:   # the GroupNorm's scale / shift are applied while proj_in loads its rows
             h = self.new(x.B, x.H, x.W, C)
             self.add(O.rowgemm(x.t, self.ws.rg_mat(f"{name}.proj_in"), h.t, M=x.M, K=C, N=C, gn_ss=ss, tokens=x.HW,
-                               ln_out=self.ln_mean_rstd(st[0], x.M, C), **self.rowgemm_cfg(x.M, C, whole_rows=True)), f"{name}.proj_in")
+                               ln_out=self.ln_mean_rstd(st[0], x.M, C), **r.whole_rows), f"{name}.proj_in")
             self.free(ss)
         else:
-            g = self.group_norm(x, f"{name}.norm", 1e-6, False)
+            self.free(ss)
             h = self.dense(g, self.ws.mat(f"{name}.proj_in"), self.ws.bias(f"{name}.proj_in"), C,
                            label=f"{name}.proj_in", ln_out=st[0])
             self.free(g)
         b = f"{name}.transformer_blocks.0"
-        self.self_attention(h, st[0], f"{b}.attn1", f"{b}.norm1", heads, st[1])
-        # (round 6) at the 320-channel level the collapsed cross-attention is the PROLOGUE of the GEGLU launch: that launch holds the
-        # rows in registers anyway - it updates them (and stores them once, for ff.out's residual), takes the next LayerNorm's
-        # statistics from its own sums and goes on; no cross-attention launch, one read of the residual stream less
-        gcfg = self.rowgemm_cfg(h.M, 8 * C, K=C) if (rg or self.rowgemm_wide_ok(h)) else None
-        fuse_x = rg and XATTN_IN_GEGLU and 2 * heads <= 64 and gcfg.get("nsplit", 1) <= 1
+        self.self_attention(h, st[0], f"{b}.attn1", f"{b}.norm1", heads, st[1], r)
+        fuse_x = r.xattn == R.XATTN_IN_GEGLU_LAUNCH
         if not fuse_x:
-            self.cross_attention2(h, st[1], f"{b}.attn2", f"{b}.norm2", heads, ctx, st[2])
-        if gcfg is not None:
+            self.cross_attention2(h, st[1], f"{b}.attn2", f"{b}.norm2", heads, ctx, st[2], r)
+        if r.geglu is not None:
             ff = self.new(h.B, h.H, h.W, 4 * C)
             xkw = dict(xattn=self.ws.rg_cross_ln(f"{b}.attn2", ctx, heads, f"{b}.norm2"), xout=h.t, sm_cols=2 * heads,
                        sm_scale=1.0 / math.sqrt(C // heads)) if fuse_x else {}
             self.add(O.rowgemm(h.t, self.ws.rg_geglu_ln(f"{b}.ff.net.0.proj", f"{b}.norm3"), ff.t, M=h.M, K=C, N=8 * C,
-                               form=L.RG_GEGLU, ln_in=self.ln_mean_rstd(st[1] if fuse_x else st[2], h.M, C), **gcfg, **xkw),
+                               form=L.RG_GEGLU, ln_in=self.ln_mean_rstd(st[1] if fuse_x else st[2], h.M, C), **r.geglu, **xkw),
                      f"{b}.attn2+ff.geglu" if fuse_x else f"{b}.ff.geglu")
         else:
             wg, gg, cg = self.ws.geglu_ln(f"{b}.ff.net.0.proj", f"{b}.norm3")
@@ -802,9 +599,9 @@ class Builder:
                    label=f"{b}.ff.out")
         self.free(ff)
         # NB: the GEMM input must never alias its output (other column tiles still read it)
-        if rg:
+        if k320:
             self.add(O.rowgemm(h.t, self.ws.rg_mat(f"{name}.proj_out"), x.t, M=h.M, K=C, N=C, residual=x.t,
-                               **self.rowgemm_cfg(h.M, C)), f"{name}.proj_out")
+                               **r.proj_out), f"{name}.proj_out")
             out = x
         else:
             out = self.dense(h, self.ws.mat(f"{name}.proj_out"), self.ws.bias(f"{name}.proj_out"), C,
@@ -826,12 +623,7 @@ class Builder:
                          out2=vt, trans_from=2 * C, ldt=ldp), f"{name}.qkv")
         self.free(g)
         o = self.new(x.B, x.H, x.W, C)
-        if C == 512 and B * ((T + 127) // 128) >= VAE_FLASH_SMALL_MIN_BLOCKS:
-            # round 4: flash form - the T x T scores (340 MB of fp32 per image at 96 x 96 latent pixels) never leave the
-            # registers.  One workgroup per 128 queries and CU: a launch that does not fill the chip (a single image: 72
-            # workgroups - the encoder always, the decoder of a one-member shard) takes 0.93 ms against 0.50 ms for the
-            # three-stage form below (profiles/r4_flash512.log; two-wave workgroups of 64 queries: 1.12 ms), so launches of
-            # fewer than 100 query blocks take the three-stage form (round 5: -0.5 ms per map at every ensemble size)
+        if R.vae_attention_flash(B, T, C):   # the T x T scores never leave the registers
             self.add(O.flash_attn512(qk, qk.data_ptr() + C * 2, vt, o.t, B=B, Ntok=T, ldq=2 * C, ldo=C, ldvt=ldp,
                                      sq=T * 2 * C, sk=T * 2 * C, svt=C * ldp, so=T * C, scale=1.0 / math.sqrt(C)), f"{name}.flash")
             self.free(qk)

@@ -472,7 +472,7 @@ def test_full_size_programs_validate_without_gpu():
     fwd = labelled[prog.n_prologue_ops:prog.n_prologue_ops + prog.n_fwd_ops]
     folded = [op for op, lab in fwd if lab.endswith("conv2+conv_shortcut")]   # conv_shortcut as extra K of conv2 (implicit GEMM levels)
     # (round 6: at ten members the 96 x 96 level's norms are separate passes and its plain convolutions run on the hand-placed GEMM
-    # tile - engine.fuse_norm_into_conv - so up_blocks.3's three shortcuts fold as well: 14 folded launches, no shortcut launch left)
+    # tile - routes.fuse_norm_into_conv - so up_blocks.3's three shortcuts fold as well: 14 folded launches, no shortcut launch left)
     assert len(folded) == 14 and all(op.kind == L.OP_IGEMM and O.Raw(op).x0 and O.Raw(op).cx % 64 == 0 and O.Raw(op).taps == 9 for op in folded)
     assert sum(bool(O.Raw(op).x1) for op in folded) == 12         # the up blocks' [hidden | skip] pairs, never concatenated
     assert [lab for _, lab in fwd if lab.endswith(".conv_shortcut")] == []
@@ -1247,21 +1247,21 @@ def test_rowgemm_cross_attention_packing():
 
 
 def test_rowgemm_launch_shape_per_row_count():
-    """engine.Builder.rowgemm_cfg: 12 waves while 384-row workgroups still fill the chip, then 8, then 4 with the column stages
+    """routes.rowgemm_cfg: 12 waves while 384-row workgroups still fill the chip, then 8, then 4 with the column stages
     shared out (never for the whole-row-statistics forms); the K = 640 form always 8 waves with the columns split so that
     workgroups <= CUs."""
-    from marigold_amd.engine import Builder
+    from marigold_amd.routes import rowgemm_cfg
     T = 9216
-    assert Builder.rowgemm_cfg(10 * T, 960) == dict(waves=12)
-    assert Builder.rowgemm_cfg(7 * T, 960) == dict(waves=12)
-    assert Builder.rowgemm_cfg(5 * T, 960) == dict(waves=8)
-    c1 = Builder.rowgemm_cfg(1 * T, 960)
+    assert rowgemm_cfg(10 * T, 960) == dict(waves=12)
+    assert rowgemm_cfg(7 * T, 960) == dict(waves=12)
+    assert rowgemm_cfg(5 * T, 960) == dict(waves=8)
+    c1 = rowgemm_cfg(1 * T, 960)
     assert c1["waves"] == 4 and c1["nsplit"] == 4          # 72 row blocks x 4 = 288 workgroups
-    assert Builder.rowgemm_cfg(1 * T, 320, whole_rows=True) == dict(waves=4)
-    assert Builder.rowgemm_cfg(2 * T, 320, xattn=True) == dict(waves=8)
-    w = Builder.rowgemm_cfg(10 * 2304, 1920, K=640)
+    assert rowgemm_cfg(1 * T, 320, whole_rows=True) == dict(waves=4)
+    assert rowgemm_cfg(2 * T, 320, xattn=True) == dict(waves=8)
+    w = rowgemm_cfg(10 * 2304, 1920, K=640)
     assert w == dict(waves=8, nsplit=2)                    # 90 blocks x 2
-    w = Builder.rowgemm_cfg(5 * 2304, 5120, K=640)
+    w = rowgemm_cfg(5 * 2304, 5120, K=640)
     assert w["waves"] == 8 and 45 * w["nsplit"] <= 256 and w["nsplit"] >= 4
 
 

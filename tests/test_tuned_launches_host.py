@@ -62,7 +62,7 @@ def test_reduced_launches_pass_their_kernels_contracts():
 def _production_ops():
     """[(op, label)] of the IGEMM launches of the UNet and VAE programs at 768^2, for every ensemble size the table names, with
     conv_shortcut folded into conv2 (the product) and as its own launch (what the table's stand-alone shortcut entries were swept on)."""
-    from marigold_amd import engine as E
+    from marigold_amd import routes as R
     from marigold_amd.arch import UNetConfig, VAEConfig, unet_param_shapes, vae_param_shapes
     from marigold_amd.modules import AutoencoderKLHIP, UNet2DConditionModelHIP
     from marigold_amd.schedulers import DDIMScheduler
@@ -71,10 +71,10 @@ def _production_ops():
     usd = {k: torch.zeros(s) for k, s in unet_param_shapes(ucfg).items()}
     vsd = {k: torch.zeros(s) for k, s in vae_param_shapes(vcfg).items()}
     found = []
-    fold0 = E.FOLD_SHORTCUT
+    fold0 = R.FOLD_SHORTCUT
     try:
         for fold in (True, False):
-            E.FOLD_SHORTCUT = fold
+            R.FOLD_SHORTCUT = fold
             unet = UNet2DConditionModelHIP(usd, ucfg).dry()
             unet.set_context(torch.zeros(1, 2, 1024))
             vae = AutoencoderKLHIP(vsd, vcfg).dry()
@@ -84,7 +84,7 @@ def _production_ops():
             for seq in seqs:
                 found += [(op, lab, fold) for op, lab in zip(seq.ops, seq.labels) if op.kind == L.OP_IGEMM]
     finally:
-        E.FOLD_SHORTCUT = fold0
+        R.FOLD_SHORTCUT = fold0
     return found
 
 
