@@ -271,7 +271,18 @@ enum mg_op_kind {
    * (a, b): u = ((a >> 9) + 1) 2^-23 in (0, 1], v = (b >> 8) 2^-24, r = sqrtf(-2 logf(u)), outputs r cospi(2 v) and r sinpi(2 v);
    * |z| <= sqrt(46 ln 2) = 5.647.  The 16-bit store rounds the fp32 value to nearest even.  A free number below the last kind; the
    * slots are named by the MG_RANDN_* enumerators below. */
-  MG_OP_RANDN = 29
+  MG_OP_RANDN = 29,
+  /* Test-time ensembling of the intrinsic-image members (ensemble_iid, marigold/util/ensemble.py:252-270; csrc/ensemble.hip): a
+   * reduction over the E members of every element on its own - P_PREDS fp32 [E][n] -> P_PRED [n] and, when P_UNC is not NULL,
+   * P_UNC [n].  I_REDUCTION 0: the median, the lower middle value for an even E as torch.median gives it, with the median of the
+   * absolute deviations from it (same rule) as the uncertainty; 1: the mean (the members added in order, divided by E) with the
+   * unbiased standard deviation.  A NaN member makes both results of its element NaN.  No alignment, no extrema: the op has no
+   * min / max table, no scratch and no atomics, leaves nothing to zero between launches and gives the same bits on every launch -
+   * those of MG_OP_ENS_DEPTH_MEDIAN without alignment, whose selection and summation order it keeps.  Any E >= 1: up to 32 members
+   * are selected in registers, larger ensembles straight from memory.  A lane owns four neighbouring elements (one 16-byte load
+   * per member, one 16-byte store per output) when n % 4 == 0, E <= 32 and the three pointers are 16-byte aligned, else one element.  The
+   * free number below the first ensembling kind; the slots are named by the MG_ENS_IID_* enumerators below. */
+  MG_OP_ENS_IID = 19
 };
 #define MG_IID_VIS_PARTS 128
 
@@ -496,6 +507,19 @@ enum mg_randn_l {
   MG_RANDN_L_STREAM = 3           /* the 64-bit stream id: independent sequences of one seed */
 };
 
+enum mg_ens_iid_i {
+  MG_ENS_IID_I_E = 0,             /* members (>= 1) */
+  MG_ENS_IID_I_REDUCTION = 1      /* 0 = median (+ median absolute deviation), 1 = mean (+ unbiased standard deviation) */
+};
+enum mg_ens_iid_p {
+  MG_ENS_IID_P_PREDS = 0,         /* f32 [E][n], 4-byte aligned */
+  MG_ENS_IID_P_PRED = 1,          /* f32 [n] */
+  MG_ENS_IID_P_UNC = 2            /* f32 [n] | NULL: no uncertainty is computed */
+};
+enum mg_ens_iid_l {
+  MG_ENS_IID_L_N = 0              /* elements per member (>= 1) */
+};
+
 typedef struct mg_program mg_program;
 
 /* Library / device */
@@ -559,7 +583,8 @@ int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* str
  * ensemble: depth by mg_ensemble_depth, normals by MG_OP_ENS_NORMALS, a single member (B == 1) is copied.  pred_out fp32 [channels]
  * [cfg[11]][cfg[12]] (the decoded size); unc_out fp32 [cfg[11]][cfg[12]] | NULL, written when B > 1 (the pipelines return none for
  * one member); info4 | NULL as in mg_ensemble_depth (zeros where no alignment ran).  opts NULL = the reference's defaults
- * (ensemble.py:39-49, :199-203), which MG_PREDICT_OPTS_DEFAULT spells out.  An intrinsic-image model is refused.  The resampling
+ * (ensemble.py:39-49, :199-203), which MG_PREDICT_OPTS_DEFAULT spells out.  An intrinsic-image model is refused (its entry point is
+ * mg_model_predict_iid, below).  The resampling
  * temporary is the model's: allocated at the first call that needs it, counted by mg_model_device_bytes, freed by mg_model_destroy.
  * Synchronises the stream where mg_ensemble_depth does (depth, B > 1) and nowhere else.  The Python pipelines give the same map, bit
  * for bit, from the same bytes with generator=marigold_amd.NativeNoise(seed) and match_input_res=False. */
@@ -573,6 +598,36 @@ typedef struct mg_predict_opts {
 #define MG_PREDICT_OPTS_DEFAULT {1, 1, 0, 50, 1024, 0, 0.02, 1e-6}
 int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                      const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null, void* stream);
+
+/* The same for an intrinsic-image model (appearance, lighting): __call__ of the reference's MarigoldIIDPipeline with fill_outputs
+ * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[10] = n_targets
+ * >= 1, 3 n_targets prediction channels, a DDIM image: the pipeline refuses the LCM scheduler and so does this call); a depth or
+ * normals model is refused.  The chain up to the decoder is that of mg_model_predict, argument for argument; the denoised latent
+ * [B, 4 n_targets, h, w] is the decoder's batch [B n_targets, 4, h, w] as it lies.  Then: B > 1 - one MG_OP_ENS_IID over the members,
+ * straight out of the decoder's output (opts.reduction; unc_out, when given, receives the uncertainty); B == 1 - a copy, unc_out is
+ * not written (the pipeline returns none).  With opts.out_h, out_w set and different from the decoded size cfg[11] x cfg[12] the
+ * ensembled prediction is resampled to them (the pipeline's match_input_res: MG_OP_RESIZE in mode opts.out_mode; the uncertainty
+ * is not resampled, reference :378-385).  With pictures_out the targets' pictures are made of what was stored to pred_out
+ * (MG_OP_IID_VIS; bit t of linear_bits / up_to_scale_bits describes target t).
+ *  pred_out fp32 [3 n_targets][out_h][out_w] (the decoded size when out_h = out_w = 0)
+ *  unc_out  fp32 [3 n_targets][cfg[11]][cfg[12]] | NULL
+ *  pictures_out uint8 [n_targets][out_h][out_w][3] | NULL
+ * opts NULL = MG_IID_OPTS_DEFAULT: the median, every target in sRGB space, no resampling.  The temporaries (input resampling,
+ * the prediction before its resampling with that pass's intermediate, the picture stage's workspace) are the model's: allocated at the
+ * first call that needs them, grown when a later call needs more, counted by mg_model_device_bytes, freed by mg_model_destroy.
+ * Synchronises nowhere.  The Python pipeline gives the same arrays, uncertainties and pictures, bit for bit, from the same bytes with
+ * generator=marigold_amd.NativeNoise(seed) (tests/test_gpu_iid_c_host.py; examples/host_iid.cpp). */
+typedef struct mg_iid_opts {
+  int reduction;          /* 0 median / 1 mean */
+  int linear_bits;        /* bit t: target t is predicted in linear space      (target_properties[name].prediction_space == "linear") */
+  int up_to_scale_bits;   /* bit t: target t is linear and up to scale         (...["up_to_scale"])                                    */
+  int out_h, out_w;       /* match_input_res: size of pred_out and pictures; 0, 0 = the model's output size */
+  int out_mode;           /* resample mode of that resize, the numbering of MG_OP_RESIZE */
+} mg_iid_opts;
+#define MG_IID_OPTS_DEFAULT {0, 0, 0, 0, 0, 0}
+int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                         const mg_iid_opts* opts_or_null, float* pred_out, float* unc_out_or_null, uint8_t* pictures_out_or_null,
+                         void* stream);
 
 /* ensemble_depth(depth[E,1,H,W], scale_invariant, shift_invariant, output_uncertainty, reduction, regularizer_strength, max_iter,
  * tol, max_res) of marigold/util/ensemble.py:39-196 as ONE call on device pointers: member statistics, init_param, the native
@@ -601,6 +656,8 @@ int mg_sched_step(const float* x, const float* model_out, const float* noise, fl
                   int64_t n, float cx, float cm, float cn, void* stream);
 int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int64_t hw,
                         int reduction, void* stream);
+/* MG_OP_ENS_IID as a call: preds fp32 [E][n] -> pred_out [n] (+ unc_out [n]); reduction 0 median / 1 mean.  Does not synchronise. */
+int mg_ensemble_iid(const float* preds, int E, int64_t n, int reduction, float* pred_out, float* unc_out_or_null, void* stream);
 
 /* One-pass validation (src/trainer/marigold_depth_trainer.py:510-601; script/depth/eval.py:176-240, script/normals/eval.py): score one
  * prediction against its ground truth on the device, with no host round trip between the fit and the scores.  The caller reads the

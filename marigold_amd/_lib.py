@@ -33,6 +33,7 @@ OP_IIDSCORE_PREP, OP_IIDSCORE_PSNR, OP_IIDSCORE_SSIM = 32, 33, 34
 OP_IID_VIS = 35
 OP_RGB_PREP, OP_NORMALS_VIS = 5, 8   # the I/O stages: free numbers below the last kind
 OP_RANDN = 29   # the native noise generator: likewise
+OP_ENS_IID = 19   # the intrinsic-image ensemble: the free number below the first ensembling kind
 IID_VIS_PARTS = 128   # MG_IID_VIS_PARTS
 IID_GAMMA = {None: 0, 2.2: 1, 1.0 / 2.2: 2, (2.2, 1.0 / 2.2): 3}   # MG_IID_GAMMA_*
 IID_METRICS = {"psnr": 1, "ssim": 2}   # MG_IID_*
@@ -103,6 +104,14 @@ NOISE_FIELDS = {
         l=("n", "offset", "seed", "stream"))),
 }
 
+# ... and for the intrinsic-image ensemble (MG_ENS_IID_* in the header; tests/test_iid_c_host.py compares them).
+ENS_FIELDS = {
+    OP_ENS_IID: ("ENS_IID", dict(
+        i=("e", "reduction"),
+        p=("preds", "pred", "unc"),
+        l=("n",))),
+}
+
 OP_NAMES = {v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}
 
 EXPORTS = [
@@ -115,6 +124,7 @@ EXPORTS = [
     "mg_model_denoise", "mg_model_vae_decode", "mg_ensemble_depth", "mg_eval_depth", "mg_eval_normals", "mg_eval_iid",
     "mg_rgb_prepare", "mg_normals_visualize",
     "mg_randn", "mg_resize", "mg_colorize", "mg_iid_visualize", "mg_model_predict",
+    "mg_ensemble_iid", "mg_model_predict_iid",
 ]
 
 
@@ -126,6 +136,12 @@ class MgPredictOpts(ctypes.Structure):
     def __init__(self, scale_invariant=1, shift_invariant=1, reduction=0, max_iter=50, max_res=1024, normals_reduction=0,
                  regularizer_strength=0.02, tol=1e-6):
         super().__init__(scale_invariant, shift_invariant, reduction, max_iter, max_res, normals_reduction, regularizer_strength, tol)
+
+
+class MgIidOpts(ctypes.Structure):
+    """mg_iid_opts; the defaults are MG_IID_OPTS_DEFAULT (the median, every target in sRGB space, the model's output size)."""
+    _fields_ = [("reduction", ctypes.c_int), ("linear_bits", ctypes.c_int), ("up_to_scale_bits", ctypes.c_int), ("out_h", ctypes.c_int),
+                ("out_w", ctypes.c_int), ("out_mode", ctypes.c_int)]
 
 
 class MgOp(ctypes.Structure):
@@ -211,6 +227,8 @@ def load(f16=False):
     lib.mg_colorize.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
     lib.mg_iid_visualize.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
     lib.mg_model_predict.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgPredictOpts)] + [ctypes.c_void_p] * 4
+    lib.mg_ensemble_iid.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mg_model_predict_iid.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgIidOpts)] + [ctypes.c_void_p] * 4
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

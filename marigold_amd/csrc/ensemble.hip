@@ -556,6 +556,150 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
   }
 }
 
+// ---- MG_OP_ENS_IID: ensemble_iid (marigold/util/ensemble.py:252-270) - the reduction over the members of every element on its own.
+// It is depth_median_kernel's `pixel` without the alignment and without the extrema: no min / max table, no scratch, nothing shared
+// between lanes.  The arithmetic is restated operation for operation - the same selection functions on the same padded arrays, the
+// members added in the same order, the same separately rounded operations (this file is built without FMA contraction) - and not
+// shared with that kernel, whose register allocation (it runs ~100 times per depth map) stays what it was measured with.
+template <int E_>
+__device__ __forceinline__ void iid_reduce(const float (&a)[E_], int E, int reduction, bool want_unc, float& pred, float& unc) {
+  const int k = (E - 1) >> 1;   // torch.median: lower middle
+  unc = 0.f;
+  if (reduction == 0) {
+    pred = select_kth<E_>(a, E, k);
+    if (want_unc) {
+      float dv[E_];
+#pragma unroll
+      for (int e = 0; e < E_; ++e) dv[e] = fabsf(__fsub_rn(a[e], pred));
+      unc = select_kth<E_>(dv, E, k);
+    }
+  } else {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E_; ++e)
+      if (e < E) s += a[e];
+    pred = s / (float)E;
+    if (want_unc) {
+      float q = 0.f;
+#pragma unroll
+      for (int e = 0; e < E_; ++e)
+        if (e < E) { const float dd = a[e] - pred; q += dd * dd; }
+      unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));   // torch.std: unbiased
+    }
+  }
+}
+
+// E <= E_ <= EMAX members in registers (the bound of depth_median_kernel's register-resident selection).  vec: a lane owns four
+// neighbouring elements - one 16-byte load per member, one 16-byte store per output (n % 4 == 0 and all pointers 16-byte aligned:
+// the launcher decides); else one element.
+template <int E_>
+__global__ __launch_bounds__(256) void iid_kernel(const float* __restrict__ d, float* __restrict__ pred, float* __restrict__ unc, int E,
+                                                  long long n, int reduction, int vec) {
+  if (vec) {
+    for (long long p = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; p < n; p += (long long)gridDim.x * 1024) {
+      float4 v[E_];
+#pragma unroll
+      for (int e = 0; e < E_; ++e) v[e] = e < E ? *(const float4*)(d + (long long)e * n + p) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float pr[4], un[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float a[E_];
+#pragma unroll
+        for (int e = 0; e < E_; ++e) a[e] = i == 0 ? v[e].x : (i == 1 ? v[e].y : (i == 2 ? v[e].z : v[e].w));
+        iid_reduce<E_>(a, E, reduction, unc != nullptr, pr[i], un[i]);
+      }
+      *(float4*)(pred + p) = make_float4(pr[0], pr[1], pr[2], pr[3]);
+      if (unc) *(float4*)(unc + p) = make_float4(un[0], un[1], un[2], un[3]);
+    }
+  } else {
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
+      float a[E_];
+#pragma unroll
+      for (int e = 0; e < E_; ++e) a[e] = e < E ? d[(long long)e * n + p] : 0.f;
+      float pr, un;
+      iid_reduce<E_>(a, E, reduction, unc != nullptr, pr, un);
+      pred[p] = pr;
+      if (unc) unc[p] = un;
+    }
+  }
+}
+
+// More than EMAX members: one element per lane, the members read from memory (cache-resident after the first pass) wherever the
+// register-resident kernel reads its array.  The order statistic as the kernels the depth op runs at these sizes find it: up to
+// EMAX_LDS members by counting ranks with ties broken by the member index (depth_median_lds_kernel), beyond by the bitwise selection
+// of depth_median_big_kernel - the same values, and the same sign where the statistic falls among zeros of both signs.
+__global__ __launch_bounds__(256) void iid_mem_kernel(const float* __restrict__ d, float* __restrict__ pred, float* __restrict__ unc, int E,
+                                                      long long n, int reduction) {
+  const int k = (E - 1) >> 1;
+  const bool by_rank = E <= EMAX_LDS;
+  auto key_of = [](float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
+  auto val_of = [](unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); };
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
+    auto val = [&](int e, bool dev_, float centre) {
+      const float x = d[(long long)e * n + p];
+      return dev_ ? fabsf(__fsub_rn(x, centre)) : x;
+    };
+    auto select = [&](bool dev_, float centre) {
+      bool nan = false;   // torch.median: a NaN member makes the statistic NaN
+      float res = val(0, dev_, centre);
+      if (by_rank) {
+        for (int e = 0; e < E; ++e) {
+          const float ve = val(e, dev_, centre);
+          nan |= ve != ve;
+          int rank = 0;
+          for (int j = 0; j < E; ++j) {
+            const float vj = val(j, dev_, centre);
+            rank += (vj < ve) || (vj == ve && j < e);
+          }
+          if (rank == k) res = ve;
+        }
+      } else {
+        for (int e = 0; e < E; ++e) {
+          const float v = val(e, dev_, centre);
+          nan |= v != v;
+        }
+        unsigned prefix = 0;
+        int kk = k;
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned hi_mask = bit == 31 ? 0u : ~((2u << bit) - 1u);   // the bits already decided
+          int cnt0 = 0;
+          for (int e = 0; e < E; ++e) {
+            const unsigned key = key_of(val(e, dev_, centre));
+            cnt0 += ((key & hi_mask) == prefix && !((key >> bit) & 1u)) ? 1 : 0;
+          }
+          if (kk >= cnt0) { kk -= cnt0; prefix |= 1u << bit; }
+        }
+        res = val_of(prefix);
+      }
+      return nan ? __builtin_nanf("") : res;
+    };
+    float pr, un = 0.f;
+    if (reduction == 0) {
+      pr = select(false, 0.f);
+      if (unc) un = select(true, pr);
+    } else {
+      float s = 0.f;
+      for (int e = 0; e < E; ++e) s += val(e, false, 0.f);
+      pr = s / (float)E;
+      if (unc) {
+        float q = 0.f;
+        for (int e = 0; e < E; ++e) { const float dd = val(e, false, 0.f) - pr; q += dd * dd; }
+        un = sqrtf(q / (float)(E - 1));
+      }
+    }
+    pred[p] = pr;
+    if (unc) unc[p] = un;
+  }
+}
+
+template <int E_>
+void launch_iid(const float* d, float* pred, float* unc, int E, long long n, int reduction, hipStream_t s) {
+  const int vec = (n & 3) == 0 && (((uintptr_t)d | (uintptr_t)pred | (uintptr_t)unc) & 15) == 0;
+  const long long per = vec ? 1024 : 256;
+  const int nblk = (int)min((n + per - 1) / per, (long long)2048);
+  MG_LAUNCH(iid_kernel<E_>, dim3(nblk), dim3(256), 0, s, d, pred, unc, E, n, reduction, vec);
+}
+
 template <int E_>
 void launch_median(const mg_op* op, int nblk, hipStream_t s) {
   MG_LAUNCH(depth_median_kernel<E_>, dim3(nblk), dim3(256), 0, s, (const float*)op->p[0],
@@ -622,6 +766,27 @@ int mg_launch_ensemble(const mg_op* op, hipStream_t s) {
       const int nblk = (int)min((HW + 255) / 256, (long long)2048);
       MG_LAUNCH(normals_kernel, dim3(nblk), dim3(256), 0, s, (const float*)op->p[0],
                          (float*)op->p[1], (float*)op->p[2], E, HW, op->i[1]);
+      break;
+    }
+    case MG_OP_ENS_IID: {
+      const int E = op->i[MG_ENS_IID_I_E], reduction = op->i[MG_ENS_IID_I_REDUCTION];
+      const long long n = op->l[MG_ENS_IID_L_N];
+      const float* d = (const float*)op->p[MG_ENS_IID_P_PREDS];
+      float *pred = (float*)op->p[MG_ENS_IID_P_PRED], *unc = (float*)op->p[MG_ENS_IID_P_UNC];
+      MG_REQUIRE(E >= 1, "ens_iid: E %d must be >= 1", E);
+      MG_REQUIRE(n >= 1 && n <= (1ll << 40), "ens_iid: bad element count %lld", n);
+      MG_REQUIRE(reduction == 0 || reduction == 1, "ens_iid: Unrecognized reduction method: %d.", reduction);
+      MG_REQUIRE(d && pred, "ens_iid: null pointer");
+      MG_REQUIRE((((uintptr_t)d | (uintptr_t)pred | (uintptr_t)unc) & 3) == 0, "ens_iid: the members and the outputs must be 4-byte aligned");
+      // the register bounds are those MG_OP_ENS_DEPTH_MEDIAN instantiates: at E <= 10 the selection is the sorting network there too
+      if (E > EMAX) {
+        const int nblk = (int)min((n + 255) / 256, (long long)2048);
+        MG_LAUNCH(iid_mem_kernel, dim3(nblk), dim3(256), 0, s, d, pred, unc, E, n, reduction);
+      } else if (E <= 4) launch_iid<4>(d, pred, unc, E, n, reduction, s);
+      else if (E <= 8) launch_iid<8>(d, pred, unc, E, n, reduction, s);
+      else if (E <= 10) launch_iid<10>(d, pred, unc, E, n, reduction, s);
+      else if (E <= 16) launch_iid<16>(d, pred, unc, E, n, reduction, s);
+      else launch_iid<EMAX>(d, pred, unc, E, n, reduction, s);
       break;
     }
     default: MG_REQUIRE(false, "ensemble: bad op kind %d", op->kind);

@@ -75,8 +75,10 @@ struct mg_model {
   std::vector<char*> bufs;
   std::vector<uint64_t> buf_bytes;   // the buffer table's sizes: every relocation / slot is checked against them
   Prog enc, den, dec;
-  void* predict_tmp = nullptr;       // mg_model_predict's resampling temporary (fp32 [3][Hin][W]), grown on demand
+  void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W]), grown on demand
   uint64_t predict_tmp_bytes = 0;
+  void* iid_tmp = nullptr;           // mg_model_predict_iid's output temporaries (see iid_tmp_layout), grown on demand
+  uint64_t iid_tmp_bytes = 0;
 };
 
 namespace {
@@ -223,6 +225,7 @@ void mg_model_destroy(mg_model* m) {
     if (p->prog) mg_program_destroy(p->prog);
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
+  if (m->iid_tmp) (void)hipFree(m->iid_tmp);
   delete m;
 }
 
@@ -232,7 +235,7 @@ int mg_model_info(const mg_model* m, int* cfg16) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->iid_tmp_bytes) : 0; }
 
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
@@ -404,37 +407,41 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
 }
 
 // ---- the whole prediction as one call: bytes + seed -> ensembled map (__call__ of the reference's pipelines up to match_input_res:
-// marigold/marigold_depth_pipeline.py:229-312, marigold_normals_pipeline.py:215-290).  The stages hand their results on inside the
-// model's own program slots; the members are ensembled straight out of the decode program's output slot.
-extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
-                                void* stream) {
-  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
+// marigold/marigold_depth_pipeline.py:229-312, marigold_normals_pipeline.py:215-290; with fill_outputs for the intrinsic-image
+// pipeline, marigold_iid_pipeline.py:239-411).  The stages hand their results on inside the model's own program slots; the members
+// are ensembled straight out of the decode program's output slot.
+namespace {
+
+// A temporary of the model: at least `need` bytes behind *p, allocated at the first call that needs it, replaced when a later call
+// needs more (mg_model_device_bytes counts *bytes, mg_model_destroy frees).
+int grow_tmp(void** p, uint64_t* bytes, uint64_t need) {
+  if (*bytes >= need) return 0;
+  if (*p) MG_CHECK_HIP(hipFree(*p));   // (hipFree waits for the work that still uses it)
+  *p = nullptr;
+  *bytes = 0;
+  MG_CHECK_HIP(hipMalloc(p, need));
+  *bytes = need;
+  return 0;
+}
+
+// Stages 1 to 5 of a one-call prediction, the same for every kind of model: the picture into the encoder, encode, the noise
+// (MG_OP_RANDN: stream 0 = the initial latents, stream k + 1 = the LCM scheduler's step noise k), denoise, decode.  `who` names the
+// entry point in the messages.  On return the B members lie in the decode program's output slot, *preds.
+int predict_members(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                    void* stream, const float** preds) {
   const uint32_t* cfg = m->hdr.cfg;
-  const int B = (int)cfg[0], H = (int)cfg[1], W = (int)cfg[2], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8];
-  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
-  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
-  MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
-  MG_REQUIRE(Hin > 0 && Win > 0, "mg_model_predict: bad input size %d x %d", Hin, Win);
-  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
-  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
+  const int B = (int)cfg[0], H = (int)cfg[1], W = (int)cfg[2], C = (int)cfg[6], n_noise = (int)cfg[8];
+  MG_REQUIRE(Hin > 0 && Win > 0, "%s: bad input size %d x %d", who, Hin, Win);
   const hipStream_t s = (hipStream_t)stream;
   const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
   const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
-  const uint64_t HWo = (uint64_t)Ho * Wo;
+  const uint64_t HWo = (uint64_t)cfg[11] * cfg[12];
   MG_REQUIRE(e_in->nbytes == (uint64_t)3 * H * W * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes && xs->nbytes % 4 == 0 &&
-             d_out->nbytes == (uint64_t)B * C * HWo * 4, "mg_model_predict: the image's slots do not chain");
+             d_out->nbytes == (uint64_t)B * C * HWo * 4, "%s: the image's slots do not chain", who);
   // 1. the picture -> [1,3,H,W] in [-1, 1], in the encoder's input slot
   float* tmp = nullptr;
   if (mode != 2 && Hin != H && Win != W) {
-    const uint64_t need = (uint64_t)3 * Hin * W * 4;
-    if (m->predict_tmp_bytes < need) {
-      if (m->predict_tmp) MG_CHECK_HIP(hipFree(m->predict_tmp));   // (hipFree waits for the work that still uses it)
-      m->predict_tmp = nullptr;
-      m->predict_tmp_bytes = 0;
-      MG_CHECK_HIP(hipMalloc(&m->predict_tmp, need));
-      m->predict_tmp_bytes = need;
-    }
+    if (int rc = grow_tmp(&m->predict_tmp, &m->predict_tmp_bytes, (uint64_t)3 * Hin * W * 4)) return rc;
     tmp = (float*)m->predict_tmp;
   }
   if (int rc = mg_rgb_prepare(rgb, hwc, Hin, Win, e_in->ptr, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
@@ -447,15 +454,35 @@ extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hi
     char nm[24];
     snprintf(nm, sizeof(nm), "noise%d", k);
     const Slot* ns = m->den.slot(nm);
-    MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "mg_model_predict: the image lacks slot %s", nm);
+    MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "%s: the image lacks slot %s", who, nm);
     if (int rc = mg_randn(seed, (uint64_t)k + 1, 0, (int64_t)(ns->nbytes / 4), ns->ptr, 0, stream)) return rc;
   }
-  // 4. denoise, 5. decode
+  // 4. denoise, 5. decode (an intrinsic-image model: the latent [B, 4 n, h, w] is the decoder's batch [B n, 4, h, w], the same bytes)
   if (int rc = mg_program_run(m->den.prog, stream)) return rc;
   if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
   if (int rc = mg_program_run(m->dec.prog, stream)) return rc;
+  *preds = (const float*)d_out->ptr;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
+                                void* stream) {
+  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
+  const uint32_t* cfg = m->hdr.cfg;
+  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7];
+  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
+  MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
+  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
+  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
+  const hipStream_t s = (hipStream_t)stream;
+  const uint64_t HWo = (uint64_t)Ho * Wo;
+  const float* preds = nullptr;
+  if (int rc = predict_members(m, "mg_model_predict", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
   // 6. ensemble (one member: the pipelines return it as it is, without an uncertainty)
-  const float* preds = (const float*)d_out->ptr;
   if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
   if (B == 1) return copy_dd(pred_out, preds, (uint64_t)C * HWo * 4, s);
   if (post == MG_POST_DEPTH)
@@ -469,4 +496,70 @@ extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hi
   en.i[0] = B; en.i[1] = o.normals_reduction;
   en.l[0] = (int64_t)HWo;
   return mg_launch(&en, stream);
+}
+
+namespace {
+// mg_model_predict_iid's temporaries, carved out of the model's iid_tmp in this order (each part rounded up to 256 bytes):
+// the ensembled prediction at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
+// [planes][Ho][out_w] (modes 0 / 1 when both sizes change), the picture stage's workspace [n][MG_IID_VIS_PARTS] (a target that is
+// linear and up to scale).
+struct IidTmp {
+  uint64_t ens = 0, rtmp = 0, ws = 0;
+  uint64_t total() const { return ens + rtmp + ws; }
+};
+IidTmp iid_tmp_layout(int B, int n, int Ho, int Wo, int oh, int ow, int out_mode, bool pictures, int linear_bits, int up_to_scale_bits) {
+  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
+  IidTmp t;
+  const bool resize = oh != Ho || ow != Wo;
+  if (resize && B > 1) t.ens = r256((uint64_t)3 * n * Ho * Wo * 4);
+  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)3 * n * Ho * ow * 4);
+  if (pictures && (linear_bits & up_to_scale_bits)) t.ws = r256((uint64_t)n * MG_IID_VIS_PARTS * 4);
+  return t;
+}
+}  // namespace
+
+extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                    const mg_iid_opts* opts_or_null, float* pred_out, float* unc_out_or_null, uint8_t* pictures_out_or_null,
+                                    void* stream) {
+  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict_iid: bad arguments (or a host-only model)");
+  const uint32_t* cfg = m->hdr.cfg;
+  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8], n = (int)cfg[10];
+  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  MG_REQUIRE(post == MG_POST_UNIT && n >= 1 && C == 3 * n,
+             "mg_model_predict_iid: an intrinsic-image model is required (a depth or a normals image goes through mg_model_predict)");
+  // MarigoldIIDPipeline._check_inference_step (marigold_iid_pipeline.py:443-447) raises on the LCM scheduler: so does its C form
+  MG_REQUIRE(n_noise == 0, "mg_model_predict_iid: This pipeline implementation does not support the LCMScheduler (the image draws noise in %d steps)", n_noise);
+  static const mg_iid_opts defaults = MG_IID_OPTS_DEFAULT;
+  const mg_iid_opts& o = opts_or_null ? *opts_or_null : defaults;
+  MG_REQUIRE(o.reduction == 0 || o.reduction == 1, "mg_model_predict_iid: Unrecognized reduction method: %d.", o.reduction);
+  MG_REQUIRE((o.out_h == 0 && o.out_w == 0) || (o.out_h > 0 && o.out_w > 0), "mg_model_predict_iid: bad output size %d x %d", o.out_h, o.out_w);
+  MG_REQUIRE(o.out_mode >= 0 && o.out_mode <= 2, "mg_model_predict_iid: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
+  MG_REQUIRE(n <= 16 && !((unsigned)(o.linear_bits | o.up_to_scale_bits) >> n), "mg_model_predict_iid: a flag names a target beyond the %d of the model (at most 16)", n);
+  const int oh = o.out_h ? o.out_h : Ho, ow = o.out_w ? o.out_w : Wo;
+  const bool resize = oh != Ho || ow != Wo;
+  const hipStream_t s = (hipStream_t)stream;
+  const IidTmp t = iid_tmp_layout(B, n, Ho, Wo, oh, ow, o.out_mode, pictures_out_or_null != nullptr, o.linear_bits, o.up_to_scale_bits);
+  if (int rc = grow_tmp(&m->iid_tmp, &m->iid_tmp_bytes, t.total())) return rc;
+  float* const ens = (float*)m->iid_tmp;
+  float* const rtmp = t.rtmp ? (float*)((char*)m->iid_tmp + t.ens) : nullptr;
+  float* const ws = t.ws ? (float*)((char*)m->iid_tmp + t.ens + t.rtmp) : nullptr;
+  const float* preds = nullptr;
+  if (int rc = predict_members(m, "mg_model_predict_iid", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
+  // 6. ensemble (ensemble_iid, :369-375; one member: the pipeline returns it as it is, without an uncertainty)
+  const int64_t n_el = (int64_t)C * Ho * Wo;
+  const float* final_pred = preds;   // at the decoded size
+  if (B > 1) {
+    float* dst = resize ? ens : pred_out;
+    if (int rc = mg_ensemble_iid(preds, B, n_el, o.reduction, dst, unc_out_or_null, stream)) return rc;
+    final_pred = dst;
+  }
+  // 7. match_input_res (:378-385): the prediction only
+  if (resize) {
+    if (int rc = mg_resize(final_pred, pred_out, rtmp, C, Ho, Wo, oh, ow, o.out_mode, 0, stream)) return rc;
+  } else if (B == 1) {
+    if (int rc = copy_dd(pred_out, preds, (uint64_t)n_el * 4, s)) return rc;
+  }
+  // 8. the pictures of what was stored (fill_outputs -> MarigoldIIDOutput.fill_entry, :117-136, :393-411)
+  if (pictures_out_or_null) return mg_iid_visualize(pred_out, pictures_out_or_null, ws, n, oh, ow, o.linear_bits, o.up_to_scale_bits, stream);
+  return 0;
 }

@@ -84,7 +84,8 @@ static int dispatch(const mg_op* op, hipStream_t s) {
     case MG_OP_ENS_DEPTH_STATS:
     case MG_OP_ENS_DEPTH_MEDIAN:
     case MG_OP_ENS_DEPTH_NORM:
-    case MG_OP_ENS_NORMALS: return mg_launch_ensemble(op, s);
+    case MG_OP_ENS_NORMALS:
+    case MG_OP_ENS_IID: return mg_launch_ensemble(op, s);
     case MG_OP_RESIZE:
     case MG_OP_COLORIZE:
     case MG_OP_IID_VIS:
@@ -277,6 +278,17 @@ int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int
   op.p[0] = (void*)normals; op.p[1] = out; op.p[2] = unc;
   op.i[0] = E; op.i[1] = reduction;
   op.l[0] = hw;
+  return mg_launch_ensemble(&op, (hipStream_t)stream);
+}
+
+int mg_ensemble_iid(const float* preds, int E, int64_t n, int reduction, float* pred_out, float* unc_out_or_null, void* stream) {
+  MG_REQUIRE(preds && pred_out, "mg_ensemble_iid: null pointer");
+  mg_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = MG_OP_ENS_IID;
+  op.p[MG_ENS_IID_P_PREDS] = (void*)preds; op.p[MG_ENS_IID_P_PRED] = pred_out; op.p[MG_ENS_IID_P_UNC] = unc_out_or_null;
+  op.i[MG_ENS_IID_I_E] = E; op.i[MG_ENS_IID_I_REDUCTION] = reduction;
+  op.l[MG_ENS_IID_L_N] = n;
   return mg_launch_ensemble(&op, (hipStream_t)stream);
 }
 

@@ -261,6 +261,27 @@ class ModelImage:
                                               O.current_stream_handle()), "mg_model_vae_decode")
         return out
 
+    def predict_iid(self, u8, seed, *, opts=None, pictures=False, mode=0, reciprocal=None):
+        """``mg_model_predict_iid`` on the uint8 CUDA picture ``u8`` [Hin, Win, 3]: -> (pred fp32 [3 n, out_h, out_w], unc fp32
+        [3 n, Hout, Wout] | None for a single member, pictures uint8 [n, out_h, out_w, 3] | None unless ``pictures``).  ``opts``: an
+        ``_lib.MgIidOpts`` (None = the defaults); ``mode`` / ``reciprocal``: the input resampling as in ``mg_rgb_prepare`` (by default
+        the reciprocal normalisation when the picture is resampled, as the pipelines' input stage)."""
+        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_iid: a uint8 CUDA [H, W, 3] picture"
+        u8 = u8.contiguous()
+        Hin, Win = u8.shape[:2]
+        if reciprocal is None:
+            reciprocal = (Hin, Win) != (self.H, self.W)
+        oh, ow = ((opts.out_h or self.Hout), (opts.out_w or self.Wout)) if opts is not None else (self.Hout, self.Wout)
+        n = self.pred_channels // 3
+        pred = torch.empty(self.pred_channels, oh, ow, device=u8.device, dtype=torch.float32)
+        unc = torch.empty(self.pred_channels, self.Hout, self.Wout, device=u8.device, dtype=torch.float32) if self.B > 1 else None
+        pics = torch.empty(n, oh, ow, 3, device=u8.device, dtype=torch.uint8) if pictures else None
+        L.check(self._lib.mg_model_predict_iid(self.handle, u8.data_ptr(), 1, Hin, Win, int(mode), int(bool(reciprocal)), int(seed) & ((1 << 64) - 1),
+                                               None if opts is None else ctypes.byref(opts), pred.data_ptr(),
+                                               None if unc is None else unc.data_ptr(), None if pics is None else pics.data_ptr(),
+                                               O.current_stream_handle()), "mg_model_predict_iid", self._lib)
+        return pred, unc, pics
+
     def close(self):
         if self.handle:
             self._lib.mg_model_destroy(self.handle)

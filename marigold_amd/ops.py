@@ -40,7 +40,7 @@ def make_op(kind, i=(), f=(), p=(), l=()):
 # --------------------------------------------------------------------------- named fields
 
 _TO_SLOT = dict(i=int, f=float, p=_ptr, l=int)
-_TABLES = {**L.FIELDS, **L.IO_FIELDS, **L.NOISE_FIELDS}
+_TABLES = {**L.FIELDS, **L.IO_FIELDS, **L.NOISE_FIELDS, **L.ENS_FIELDS}
 _WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in _TABLES.items()}
 assert all(len(w) == sum(len(names) for names in _TABLES[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
 
@@ -328,6 +328,12 @@ def ens_depth_norm(med, unc, minmax, *, HW, shift_invariant=True):
 
 def ens_normals(n, out, unc, *, E, HW, reduction=0):
     return make_op(L.OP_ENS_NORMALS, i=[E, reduction], p=[n, out, unc], l=[HW])
+
+
+def ens_iid(preds, pred, unc, *, E, n, reduction=0):
+    """The intrinsic-image ensemble (MG_OP_ENS_IID): fp32 ``preds`` [E, n] -> ``pred`` [n] and, unless ``unc`` is None, ``unc`` [n]:
+    per element the median (+ median absolute deviation; ``reduction`` 0) or the mean (+ unbiased std; 1) over the members."""
+    return build_op(L.OP_ENS_IID, e=E, reduction=reduction, preds=preds, pred=pred, unc=unc, n=n)
 
 
 def resize(src, dst, tmp, *, planes, Hin, Win, Hout, Wout, mode, u8):

@@ -14,7 +14,7 @@ CLASS = {
     L.OP_SOFTMAX_ROWS: "softmax",
     L.OP_SCHED_STEP: "scheduler_step", L.OP_LINEAR_SMALL_M: "time_embedding",
     L.OP_LATENT_1X1: "boundary_conv", L.OP_POST_NCHW: "boundary_conv", L.OP_CONV3X3_HEAD: "boundary_conv", L.OP_IM2COL_SMALL: "boundary_conv", L.OP_ENS_DEPTH_STATS: "ensemble", L.OP_ENS_DEPTH_MEDIAN: "ensemble",
-    L.OP_ENS_DEPTH_NORM: "ensemble", L.OP_ENS_NORMALS: "ensemble", L.OP_RESIZE: "resize", L.OP_COLORIZE: "resize", L.OP_IID_VIS: "resize", L.OP_RGB_PREP: "resize", L.OP_NORMALS_VIS: "resize", L.OP_RANDN: "noise", L.OP_MEMSET: "memops", L.OP_COPY: "memops",
+    L.OP_ENS_DEPTH_NORM: "ensemble", L.OP_ENS_NORMALS: "ensemble", L.OP_ENS_IID: "ensemble", L.OP_RESIZE: "resize", L.OP_COLORIZE: "resize", L.OP_IID_VIS: "resize", L.OP_RGB_PREP: "resize", L.OP_NORMALS_VIS: "resize", L.OP_RANDN: "noise", L.OP_MEMSET: "memops", L.OP_COPY: "memops",
 }
 BOUND = {"igemm_mfma": "mfma", "rowgemm_mfma": "mfma", "conv3x3_patch": "mfma", "flash_attn64": "mfma", "flash_attn512": "mfma"}   # everything else is HBM-bound streaming
 
@@ -99,6 +99,8 @@ def op_cost(op):
         byts = 2 * l[0] * 4
     elif k == L.OP_ENS_NORMALS:
         byts = (i[0] + 1) * 3 * l[0] * 4
+    elif k == L.OP_ENS_IID:   # every member read once, the prediction (and the uncertainty) written once
+        byts = (i[0] + (2 if op.p[2] else 1)) * l[0] * 4
     elif k == L.OP_IID_VIS:   # the fp32 planes read once (twice by the targets that take a maximum first), one byte written per element
         n3 = 3 * i[1] * i[2]
         byts = n3 * (5 * i[0] + 4 * bin(i[3] & i[4]).count("1"))
