@@ -51,25 +51,19 @@ enum mg_op_kind {
   MG_OP_IGEMM = 1,
   /* GroupNorm, 3 launches (stats partials -> per-(b,c) scale/shift -> apply [+SiLU]).
    * Replaces torch group_norm + silu in every ResNet block / Transformer2D input norm.
-   *  STATS:    p[0] x bf16 [B][HW][C]  p[1] partials f32 [B][slots][groups][2] ; i: B,HW,C,chunks, Ctot (0 = C), coff,
-   *            groups, slot0, slots (0 = chunks) - x holds channels [coff, coff+C) of a Ctot-channel norm (the UNet's skip
-   *            concat torch.cat([hidden, skip]) is normalised source by source, never materialised); block (chunk, b)
-   *            writes slot slot0 + chunk.  With p[4] != NULL the image's last-arriving block also does FINALIZE's job
-   *            (no finalize launch): p[2] gamma p[3] beta p[4] scale_shift [B][2][Ctot] p[5] uint32 [B] arrival counters
-   *            (zero before the first use; left zero) ; f[0] eps.  p[6] x1 bf16 [B][HW][C1] | NULL, i[9] = C1: a second
-   *            source (channels [coff+C, +C1)) in the same launch - blocks [chunks, 2 chunks) write slots slot0 + chunks + ...
-   *  FINALIZE: p[0] partials p[1] gamma f32 p[2] beta f32 p[3] scale_shift f32 [B][2][C];
-   *            i: B,C,groups,slots,HW ; f[0] eps
-   *  APPLY:    p[0] x  p[1] scale_shift  p[2] out bf16 [B][HW][C]  p[3] x1 | NULL ; i: B,HW,C,silu, C0 - with x1 the
-   *            output channels [0,C0) come from x ([B][HW][C0]) and [C0,C) from x1 ([B][HW][C-C0]) */
+   * The slots are named by the MG_GN_STATS_* / MG_GN_FINALIZE_* / MG_GN_APPLY_* enumerators below.
+   *  STATS:    P_X holds channels [I_COFF, I_COFF + I_C) of an I_CTOT-channel norm (the UNet's skip concat torch.cat([hidden, skip])
+   *            is normalised source by source, never materialised); block (chunk, b) writes slot I_SLOT0 + chunk of P_PARTIALS.
+   *            With P_SS != NULL the image's last-arriving block also does FINALIZE's job (no finalize launch): P_GAMMA, P_BETA,
+   *            P_COUNTERS and F_EPS are then required.  P_X1 with I_C1: a second source (channels [coff + C, + C1)) in the same
+   *            launch - blocks [chunks, 2 chunks) write slots slot0 + chunks + ...
+   *  APPLY:    with P_X1 the output channels [0, I_C0) come from P_X ([B][HW][C0]) and [C0, C) from P_X1 ([B][HW][C - C0]) */
   MG_OP_GN_STATS = 2,
   MG_OP_GN_FINALIZE = 3,
   MG_OP_GN_APPLY = 4,
   /* GroupNorm as ONE launch (statistics + scale/shift [+ normalised output]): a workgroup owns whole groups of one image
    * (channel window lcm(C / groups, 4) <= 128) over all H x W rows - no partial table, no tickets, one read of the tensor.
-   *  p[0] x0 bf16 [B][HW][C0]  p[1] x1 bf16 [B][HW][C - C0] | NULL (second channel source: the UNet's skip concat)
-   *  p[2] out bf16 [B][HW][C] | NULL (statistics only)  p[3] gamma f32 [C]  p[4] beta f32 [C]  p[5] scale_shift f32 [B][2][C]
-   *  i: B, HW, C, C0 (with x1), groups, silu ; f[0] eps.  The normalised form keeps the rows in registers: H x W x window
+   * The slots are named by the MG_GN_SLAB_* enumerators below.  The normalised form keeps the rows in registers: H x W x window
    *  <= 48 rows per thread of a 1024-thread workgroup (the UNet's 96^2 ... 12^2 levels at any width). */
   MG_OP_GN_SLAB = 9,
   /* Row-resident GEMM for the token-local Linear layers at K = 320 / 640 (the two widest transformer levels): out[M][N] =
@@ -103,47 +97,36 @@ enum mg_op_kind {
   MG_OP_FLASH_ATTN64 = 6,
   /* Self-attention core of ONE head of width 512 (the mid-block attention of AutoencoderKL: diffusers Attention in
    * UNetMidBlock2D, marigold_depth_pipeline.py:491-492, 512-513), flash form: the scores stay in registers.
-   *  p[0] Q bf16 (row stride ldq)  p[1] K (row stride ldq)  p[2] Vt bf16 [B][512][ldvt] (natural key order, ldvt >= Ntok rounded
-   *  up to 32, pad columns zero)  p[3] O bf16 (row stride ldo); i: B, Ntok, ldq, ldo, ldvt ;
-   *  l[0] q batch stride l[1] k batch stride l[2] vt batch stride l[3] o batch stride ; f[0] softmax scale */
+   * The slots are named by the MG_FLASH_ATTN512_* enumerators below. */
   MG_OP_FLASH_ATTN512 = 11,
   /* Row softmax fp32 -> bf16 (single-head attention of a width other than 512, materialised scores; the collapsed 2-token
    * cross-attention of marigold_depth_pipeline.py:381-394, 438-442 needs no softmax op: scores = LN(x) Wqk^T with
    * Wqk[(h,j)] = Wq_h^T k_{j,h}, p = softmax over the key pair, out = p VO + bias + x with VO[(h,j)] = Wo[:,h] v_{j,h} run as
-   * MG_EPI_XATTN2 / MG_OP_ROWGEMM form 3).
-   *  p[0] S f32 [R][lds] p[1] P bf16 [R][ldp] ; i: R, ncols, lds, ldp (pad cols zeroed) */
+   * MG_EPI_XATTN2 / MG_OP_ROWGEMM form 3).  The slots are named by the MG_SOFTMAX_ROWS_* enumerators below. */
   MG_OP_SOFTMAX_ROWS = 7,
   /* Scheduler update (DDIM / LCM, diffusers *.step at marigold_depth_pipeline.py:466-468):
-   * out = f[0]*x + f[1]*model_out + f[2]*noise.  p[0] x f32 p[1] model_out f32
-   * p[2] noise f32 | NULL  p[3] out f32 ; l[0] n elements */
+   * out = F_CX * x + F_CM * model_out + F_CN * noise.  The slots are named by the MG_SCHED_STEP_* enumerators below. */
   MG_OP_SCHED_STEP = 12,
   /* Small-M dense layer in fp32 (time-embedding MLP and per-ResNet projections):
-   * out[m][n] = act_out(sum_k act_in(in[m][k]) * W[n][k] + b[n]).
-   *  p[0] in f32 [M][K] p[1] W f32 [N][K] p[2] b f32|NULL p[3] out f32 [M][ldo];
-   *  i: M,N,K,act_in,act_out(0 none,1 silu),ldo */
+   * out[m][n] = act_out(sum_k act_in(x[m][k]) * W[n][k] + bias[n]).  The slots are named by the MG_LINEAR_SMALL_M_* enumerators below. */
   MG_OP_LINEAR_SMALL_M = 13,
   /* 1x1 conv on fp32 NCHW latents with input scale (post_quant_conv after /0.18215,
-   * marigold_depth_pipeline.py:510-512).  p[0] in f32 [B][Ci][HW] p[1] W f32 [Co][Ci]
-   * p[2] b f32 p[3] out f32 [B][Co][HW] ; i: B,Ci,Co,HW ; f[0] input scale */
+   * marigold_depth_pipeline.py:510-512).  The slots are named by the MG_LATENT_1X1_* enumerators below. */
   MG_OP_LATENT_1X1 = 14,
   /* Pointwise tail of a small-Cout convolution computed by MG_OP_IGEMM into a padded fp32 buffer:
-   * out NCHW = post(in[m][0..Cout) * f[0]): MG_POST_DEPTH = mean over channels, clip, (x+1)/2 (marigold_depth_
+   * out NCHW = post(in[m][0..Cout) * F_SCALE): MG_POST_DEPTH = mean over channels, clip, (x+1)/2 (marigold_depth_
    * pipeline.py:515,473-475); MG_POST_NORMALS = clip, L2 normalise (marigold_normals_pipeline.py:438-440); MG_POST_UNIT.
    * The clip to [-1, 1] and the normalise's 1e-6 floor of the norm keep NaN, like torch.clip / clamp(min=eps) (+-inf clip to
    * +-1): a NaN channel gives a NaN depth (DEPTH), a NaN pixel in all channels (NORMALS), a NaN in that channel (UNIT, NONE);
    * MG_POST_SCHED = the DDIM / LCM update of MG_OP_SCHED_STEP applied to conv_out's result in place of storing it:
-   * out <- f[1]*out + f[2]*in + f[3]*noise (out = the latent x_t, NCHW; marigold_depth_pipeline.py:466-468).
-   *  p[0] in f32 [B*HW][ldi]  p[1] out f32 NCHW  p[2] noise f32 NCHW | NULL (MG_POST_SCHED) ;
-   *  i: B, HW, Cout, ldi, post ; f[0] scale, f[1..3] cx, cm, cn */
+   * out <- F_CX * out + F_CM * in + F_CN * noise (out = the latent x_t, NCHW; marigold_depth_pipeline.py:466-468).
+   * The slots are named by the MG_POST_NCHW_* enumerators below. */
   MG_OP_POST_NCHW = 15,
   /* im2col of a 3x3 / pad 1 neighbourhood for the <= 8-channel convolutions at the latent / image
    * boundary (conv_in of the UNet incl. the torch.cat of marigold_depth_pipeline.py:456-458, of the
    * VAE encoder and decoder): fp32 NCHW (two sources) -> bf16 [B*H*W][Kp], k = tap*(C0+C1) + c,
    * columns >= 9*(C0+C1) zero.  The convolution itself is then an MG_OP_IGEMM with K = Kp.
-   *  p[0] src0 f32 [B|1|B/i[7]][C0][H][W]  p[1] src1 f32 [B][C1][H][W] | NULL  p[2] out bf16 [B*H*W][Kp];
-   *  i: B,H,W,C0,C1,Kp, src0_broadcast, i[7] members per src0 row: 0 = src0_broadcast decides (row 0 for every b,
-   *  or row b); m > 0 = row b reads src0 row b / m (several images in one program, m ensemble members each;
-   *  requires src0_broadcast = 0 and B % m == 0) */
+   * The slots are named by the MG_IM2COL_SMALL_* enumerators below. */
   MG_OP_IM2COL_SMALL = 16,
   /* Patch-resident conv3x3 (stride 1, pad 1) with the ResNet block's GroupNorm + SiLU fused into the operand staging
    * (diffusers ResnetBlock2D: norm1 -> silu -> conv1, norm2 -> silu -> conv2), the UNet's skip concat folded into the
@@ -158,39 +141,28 @@ enum mg_op_kind {
    * conv_out of the UNet and of the VAE decoder - the tail of the modules the reference calls at marigold_depth_pipeline.py:461-463
    * and :498-516; csrc/head_conv.hip: the raw input patch of a pixel tile is normalised on its
    * way into LDS, the taps are packed bf16 dot products - no MFMA work at <= 4 output channels, one HBM read of the input).
-   *  p[0] x bf16 [B][H][W][C]  p[1] scale_shift f32 [B][2][C] | NULL  p[2] Wt bf16 [>= Cout][9 C], k = (ky*3+kx)*C + c
-   *  p[3] bias f32 | NULL  p[4] out f32 [B H W][ldo] (columns [0, Cout): what MG_OP_POST_NCHW reads)
-   *  i[0] B  i[1] H  i[2] W  i[3] C (% 32 == 0)  i[4] Cout (1..4)  i[5] ldo (0 = Cout)  i[6] silu */
+   * The slots are named by the MG_CONV3X3_HEAD_* enumerators below. */
   MG_OP_CONV3X3_HEAD = 18,
   /* Test-time ensembling (marigold/util/ensemble.py).
    * DEPTH_STATS : one pass over [E][HW]: per-member min,max,mean and the centred E x E
    *               second-moment matrix (closed form of the pairwise-RMSE cost, :138-145).
-   *   p[0] d f32 [E][HW] p[1] blocks f64 scratch p[2] out f64 [3E + E*E] ; i: E ; l[0] HW
    * DEPTH_MEDIAN: aligned = s*d+t; lower-middle median over E (+MAD); block min/max.
-   *   p[0] d f32 [E][HW] p[1] st f32 [s[E], t[E]] | NULL (no alignment) p[2] med f32 [HW]|NULL
-   *   p[3] mad f32 [HW]|NULL  p[4] out f32 [2+2E] = min, max of the prediction and the raw member
-   *   values d[.][argmin px], d[.][argmax px] (exact sub-gradient of the regulariser on the
-   *   host)  p[5] scratch (>= 12288 B) ; i: E, reduction(0 median,1 mean), has_shift ; l[0] HW
    * (DEPTH_STATS scratch: >= nblk*E*(E+3) doubles, nblk = min(ceil(HW / 256), E > 256 ? 32 : 128) - 128*E*(E+3) always suffices.  Any E >= 1: <= 32 members are selected in registers, <= 128 in LDS,
    * larger ensembles by a bitwise selection over the members in memory - the reference has no limit, ensemble.py:39-49)
-   * DEPTH_NORM  : out = (med - lo)/range ; unc /= range.  p[0] med p[1] mad|NULL p[2] minmax
-   *   ; i[0] shift_invariant ; l[0] HW
-   * NORMALS     : p[0] n f32 [E][3][HW] p[1] out f32 [3][HW] p[2] unc f32 [HW]|NULL ;
-   *   i: E, reduction(0 closest,1 mean) ; l[0] HW */
+   * DEPTH_NORM  : out = (med - lo)/range ; unc /= range, in place.
+   * NORMALS     : the member closest to the mean direction, or the normalised mean.
+   * The slots are named by the MG_ENS_DEPTH_STATS_* / MG_ENS_DEPTH_MEDIAN_* / MG_ENS_DEPTH_NORM_* / MG_ENS_NORMALS_* enumerators below. */
   MG_OP_ENS_DEPTH_STATS = 20,
   MG_OP_ENS_DEPTH_MEDIAN = 21,
   MG_OP_ENS_DEPTH_NORM = 22,
   MG_OP_ENS_NORMALS = 23,
   /* Image resampling either side of the path (marigold/util/image_util.py:90-120, marigold_depth_
    * pipeline.py:306-312, ensemble.py:158-161): torchvision resize(..., antialias=True) semantics.
-   *  p[0] src  p[1] dst  p[2] f32 temporary [planes][Hin][Wout] (needed when both sizes change) ;
-   *  i: planes (= B*C), Hin, Win, Hout, Wout, mode (0 bilinear, 1 bicubic, 2 nearest-exact),
-   *  dtype (1: uint8 in/out - computed in float, rounded half-to-even; 0: fp32) */
+   * The slots are named by the MG_RESIZE_* enumerators below. */
   MG_OP_RESIZE = 24,
   /* Colour-mapped depth image (marigold/util/image_util.py:38-76 colorize_depth_maps followed by the pipeline's
-   * (x * 255).astype(uint8), marigold_depth_pipeline.py:318-327): out[px] = LUT[min(int(clip((d-f[0])/(f[1]-f[0]),0,1)*256),255)].
-   *  p[0] depth f32 [n]  p[1] LUT uint8 [256][3] (matplotlib's table)  p[2] out uint8 [n][3] (HWC) ; l[0] n ;
-   *  f[0] min_depth f[1] max_depth */
+   * (x * 255).astype(uint8), marigold_depth_pipeline.py:318-327): out[px] = LUT[min(int(clip((d - F_MIN_DEPTH) / (F_MAX_DEPTH -
+   * F_MIN_DEPTH), 0, 1) * 256), 255)].  The slots are named by the MG_COLORIZE_* enumerators below. */
   MG_OP_COLORIZE = 25,
   /* Scoring of one prediction against its ground truth on the device (the validation loop of the reference,
    * src/trainer/marigold_depth_trainer.py:510-601, with src/util/alignment.py and src/util/metric.py; csrc/evalscore.hip).
@@ -198,42 +170,32 @@ enum mg_op_kind {
    * no floating-point atomics, the same bits on every launch.  Pixels outside the mask never enter a sum.
    * EVAL_DEPTH_LS: the five sums n, Sx, Sy, Sxx, Sxy of the least-squares fit gt ~ s * pred + t over the valid pixels
    *   (align_depth_least_square, alignment.py:35-82).
-   *   p[0] pred f32 [H][W]  p[1] gt f32 [H][W]  p[2] mask uint8 [H][W] (non-zero = valid)  p[3] out f64 [5]
-   *   p[4] scratch f64 [512][5] ; i[0] H  i[1] W  i[2] 1 = disparity: y = 1 / gt, valid &= gt > 0 & pred > 0 (script/depth/eval.py:
-   *   185-201)  i[3] width of the sub-sampled fit (alignment_max_res: floor(W * factor), only the width shrinks; 0 = every pixel)
-   *   f[0] fp32(1 / factor): source column = min(floor(dst * f[0]), W - 1)
-   * EVAL_DEPTH_METRICS: a = clip(clip(pred * s + t)) per valid pixel in fp32 (scale and shift from p[3] by the 2 x 2 normal equations in
+   * EVAL_DEPTH_METRICS: a = clip(clip(pred * s + t)) per valid pixel in fp32 (scale and shift from P_SUMS by the 2 x 2 normal equations in
    *   fp64, cast to fp32; disparity: a = 1 / max(a, 1e-3); then [min_depth, max_depth], then the 1e-6 floor) and the ten scores of
    *   script/depth/eval.py:58-69 (metric.py:64-199), finished in fp64.
-   *   p[0] pred  p[1] gt  p[2] mask  p[3] the five sums f64 [5] | NULL (s = 1, t = 0)  p[4] out f64 [13] = abs_relative_difference,
-   *   squared_relative_difference, rmse_linear, rmse_log, log10, delta1_acc, delta2_acc, delta3_acc, i_rmse, silog_rmse, scale, shift, n
-   *   p[5] scratch f64 [512][11] ; i[0] H  i[1] W  i[2] 1 = disparity  i[3] 1 = clip below at f[0]  i[4] 1 = clip above at f[1]
    * EVAL_NORMALS: per-pixel angle in degrees (compute_cosine_error, metric.py:206-233) and its statistics; the median is exact
    *   (np.median: mean of the two middle order statistics), by a three-pass radix selection on the angles' bit patterns.
-   *   p[0] pred f32 [3][HW]  p[1] gt f32 [3][HW]  p[2] out f64 [9] = mean, median, percentages below 5 / 7.5 / 11.25 / 22.5 / 30
-   *   degrees, rmse, n (n = 0: NaN)  p[3] error map f32 [HW] | NULL (dropped pixels hold -1)  p[4] workspace (MG_EVAL_WS_BYTES, 8-byte
-   *   aligned; owned by the launch) ; i[0] masked: drop the pixels whose gt vector has zero norm ; l[0] HW */
+   * The slots are named by the MG_EVAL_DEPTH_LS_* / MG_EVAL_DEPTH_METRICS_* / MG_EVAL_NORMALS_* enumerators below. */
   MG_OP_EVAL_DEPTH_LS = 26,
   MG_OP_EVAL_DEPTH_METRICS = 27,
   MG_OP_EVAL_NORMALS = 28,
-  MG_OP_MEMSET = 30, /* p[0] dst ; i[0] byte value ; l[0] bytes */
-  MG_OP_COPY = 31,   /* p[0] src p[1] dst ; l[0] bytes (device to device) */
+  MG_OP_MEMSET = 30, /* hipMemsetAsync; the slots are named by the MG_MEMSET_* enumerators below */
+  MG_OP_COPY = 31,   /* hipMemcpyAsync, device to device; the slots are named by the MG_COPY_* enumerators below */
   /* Scoring of one intrinsic-image target (albedo, shading, ...) against its ground truth on the device: compute_iid_metric of the
    * reference (src/util/metric.py:263-338) with the PSNR / SSIM of torchmetrics it is called with (script/iid/eval.py); same
-   * file, same reduction scheme and the same guarantees as the EVAL ops above.  The three ops share their fields:
-   *   p[0] pred f32 [3][H][W]  p[1] gt f32 [3][H][W]  p[2] mask uint8 [3][H][W] (non-zero = valid) | NULL (every element valid)
-   *   p[3] out f64 [8] = psnr, ssim, alignment scale, quantile, brightness scale, valid elements, two reserved slots (at present
-   *   PREP leaves the two order statistics of its quantile there for the tests: not part of the interface)  p[4] workspace (MG_EVAL_WS_BYTES, 8-byte aligned; PREP leaves the mapping in it for the two
-   *   score ops of the same target) ; i[0] H  i[1] W  i[2] MG_IID_GAMMA_*: x <- x^gamma in fp32 on every load of both images
-   *   i[3] 1 = an up-to-scale target: the score ops map both images on load with what PREP found (they are never stored).
+   * file, same reduction scheme and the same guarantees as the EVAL ops above.  The three ops share their fields, slot for slot (one op
+   * can be launched as each kind in turn, as mg_eval_iid does): the MG_IIDSCORE_PREP_* / MG_IIDSCORE_PSNR_* / MG_IIDSCORE_SSIM_*
+   * enumerators below.  P_OUT f64 [8] = psnr, ssim, alignment scale, quantile, brightness scale, valid elements, two reserved slots (at
+   * present PREP leaves the two order statistics of its quantile there for the tests: not part of the interface); PREP leaves the
+   * mapping in P_WS for the two score ops of the same target, which map both images on load with it (they are never stored).
    * IIDSCORE_PREP (shading, residual): s = S p g / S p p over the valid elements in fp64 (compute_alignment_scale, :319-334);
    *   the brightness 0.3 g0 + 0.59 g1 + 0.11 g2 of the ground truth over the pixels of mask channel 0, its 0.9 quantile q with
    *   linear interpolation at the fp32 position 0.9 (n - 1) like torch.quantile / np.quantile - the two order statistics are
    *   exact, by the radix selection of EVAL_NORMALS on order-preserving keys; scale = q < 1e-4 ? 0 : 0.8 / q (quantile_map,
    *   :337-375).  The mapping is pred <- clamp(scale * (fp32(s) * pred), 0, 1), gt <- clamp(scale * gt, 0, 1).  Writes out[2],
-   *   out[3], out[4] and the reserved slots (no pixel: NaN).  i[3] is ignored.
+   *   out[3], out[4] and the reserved slots (no pixel: NaN).  Slot 3 of i (the score ops' I_UP_TO_SCALE) is ignored.
    * IIDSCORE_PSNR: 10 log10(1 / mean(d^2)) over the valid elements, d taken in fp64 (identical images: +inf); writes out[5], out[0]
-   *   when i[4] != 0 and, for a plain target, out[2] = out[4] = 1 (no valid element: NaN).
+   *   when I_WRITE_PSNR != 0 and, for a plain target, out[2] = out[4] = 1 (no valid element: NaN).
    * IIDSCORE_SSIM: mean SSIM (11 x 11 Gaussian window, sigma 1.5, c1 = 1e-4, c2 = 9e-4, reflect padding by 5 and the padded border
    *   cropped: 3 (H - 10)(W - 10) values) with the invalid elements of both images set to 0; the five window moments are fp64 sums of
    *   exact products; needs H, W >= 11; writes out[1] (no valid element: NaN). */
@@ -244,10 +206,7 @@ enum mg_op_kind {
    * image: per target, if linear and up to scale x <- x / max(max over its 3 H W elements, 1e-6) (IEEE division, the maximum keeps
    * NaN); if linear x <- powf(x, fp32(1 / 2.2)); then (x * 255).astype(uint8) as x86-64 numpy does it: truncation to int32, low 8
    * bits; NaN and |x * 255| >= 2^31 -> 0.  At most two launches (the maxima, skipped when no target needs one; the map), no atomics:
-   * the same bits on every launch.
-   *  p[0] pred f32 [n][3][H][W]  p[1] out uint8 [n][H][W][3] (HWC)  p[2] workspace f32 [n][MG_IID_VIS_PARTS] (may be NULL when no
-   *  target is both linear and up to scale) ; i[0] n (<= 16)  i[1] H  i[2] W  i[3] bit t: target t is in linear space
-   *  i[4] bit t: target t is up to scale */
+   * the same bits on every launch.  The slots are named by the MG_IID_VIS_* enumerators below. */
   MG_OP_IID_VIS = 35,
   /* The two remaining ends of the device I/O boundary (csrc/resize.hip); they take free numbers below the last kind.  Their slots are
    * named by the MG_RGB_PREP_* / MG_NORMALS_VIS_* enumerators below.
@@ -306,8 +265,8 @@ typedef struct mg_op {
   int64_t l[4];
 } mg_op;
 
-/* Field names of the four kinds with many launch forms and of the I/O stages (MG_OP_RGB_PREP, MG_OP_NORMALS_VIS): MG_<KIND>_<array>_<NAME> is the index of that field in mg_op's i / f / p /
- * l array.  This is the one table of the wire format (the values are positions: they never change, new fields are appended);
+/* Field names of every kind: MG_<KIND>_<array>_<NAME> is the index of that field in mg_op's i / f / p / l array (<KIND> is the kind's name
+ * without MG_OP_; MG_OP_FLASH_ATTN64's is FLASH64).  This is the one table of the wire format (the values are positions: they never change, new fields are appended);
  * marigold_amd/_lib.py mirrors it (tests/test_host.py compares the two) and marigold_amd/ops.py decodes an op by these names. */
 enum mg_igemm_i {
   MG_IGEMM_I_B = 0,             /* images */
@@ -518,6 +477,349 @@ enum mg_ens_iid_p {
 };
 enum mg_ens_iid_l {
   MG_ENS_IID_L_N = 0              /* elements per member (>= 1) */
+};
+
+enum mg_gn_stats_i {
+  MG_GN_STATS_I_B = 0,
+  MG_GN_STATS_I_HW = 1,
+  MG_GN_STATS_I_C = 2,            /* channels of x */
+  MG_GN_STATS_I_CHUNKS = 3,       /* blocks per image and source */
+  MG_GN_STATS_I_CTOT = 4,         /* channels of the whole norm (0 = C) */
+  MG_GN_STATS_I_COFF = 5,         /* first channel of the norm that x holds */
+  MG_GN_STATS_I_GROUPS = 6,
+  MG_GN_STATS_I_SLOT0 = 7,        /* first slot this launch writes */
+  MG_GN_STATS_I_SLOTS = 8,        /* slots per image of the table (0 = chunks) */
+  MG_GN_STATS_I_C1 = 9            /* channels of x1 */
+};
+enum mg_gn_stats_f { MG_GN_STATS_F_EPS = 0 };
+enum mg_gn_stats_p {
+  MG_GN_STATS_P_X = 0,            /* bf16 [B][HW][C] */
+  MG_GN_STATS_P_PARTIALS = 1,     /* f32 [B][slots][groups][2], 8-byte aligned */
+  MG_GN_STATS_P_GAMMA = 2,        /* f32 [Ctot] (fused finalize) */
+  MG_GN_STATS_P_BETA = 3,         /* f32 [Ctot] (fused finalize) */
+  MG_GN_STATS_P_SS = 4,           /* scale_shift f32 [B][2][Ctot] | NULL = no fused finalize */
+  MG_GN_STATS_P_COUNTERS = 5,     /* uint32 [B] arrival counters (zero before the first use; left zero) */
+  MG_GN_STATS_P_X1 = 6            /* bf16 [B][HW][C1] | NULL: second source */
+};
+enum mg_gn_finalize_i {
+  MG_GN_FINALIZE_I_B = 0,
+  MG_GN_FINALIZE_I_C = 1,
+  MG_GN_FINALIZE_I_GROUPS = 2,
+  MG_GN_FINALIZE_I_SLOTS = 3,
+  MG_GN_FINALIZE_I_HW = 4
+};
+enum mg_gn_finalize_f { MG_GN_FINALIZE_F_EPS = 0 };
+enum mg_gn_finalize_p {
+  MG_GN_FINALIZE_P_PARTIALS = 0,  /* f32 [B][slots][groups][2] */
+  MG_GN_FINALIZE_P_GAMMA = 1,     /* f32 [C] */
+  MG_GN_FINALIZE_P_BETA = 2,      /* f32 [C] */
+  MG_GN_FINALIZE_P_SS = 3         /* scale_shift f32 [B][2][C] */
+};
+enum mg_gn_apply_i {
+  MG_GN_APPLY_I_B = 0,
+  MG_GN_APPLY_I_HW = 1,
+  MG_GN_APPLY_I_C = 2,
+  MG_GN_APPLY_I_SILU = 3,
+  MG_GN_APPLY_I_C0 = 4            /* with x1: the channels x holds */
+};
+enum mg_gn_apply_p {
+  MG_GN_APPLY_P_X = 0,            /* bf16 [B][HW][C] (with x1: [B][HW][C0]) */
+  MG_GN_APPLY_P_SS = 1,           /* scale_shift f32 [B][2][C] */
+  MG_GN_APPLY_P_OUT = 2,          /* bf16 [B][HW][C] */
+  MG_GN_APPLY_P_X1 = 3            /* bf16 [B][HW][C - C0] | NULL */
+};
+enum mg_gn_slab_i {
+  MG_GN_SLAB_I_B = 0,
+  MG_GN_SLAB_I_HW = 1,
+  MG_GN_SLAB_I_C = 2,
+  MG_GN_SLAB_I_C0 = 3,            /* with x1: the channels x0 holds */
+  MG_GN_SLAB_I_GROUPS = 4,
+  MG_GN_SLAB_I_SILU = 5
+};
+enum mg_gn_slab_f { MG_GN_SLAB_F_EPS = 0 };
+enum mg_gn_slab_p {
+  MG_GN_SLAB_P_X0 = 0,            /* bf16 [B][HW][C0] */
+  MG_GN_SLAB_P_X1 = 1,            /* bf16 [B][HW][C - C0] | NULL (second channel source: the UNet's skip concat) */
+  MG_GN_SLAB_P_OUT = 2,           /* bf16 [B][HW][C] | NULL (statistics only) */
+  MG_GN_SLAB_P_GAMMA = 3,         /* f32 [C] */
+  MG_GN_SLAB_P_BETA = 4,          /* f32 [C] */
+  MG_GN_SLAB_P_SS = 5             /* scale_shift f32 [B][2][C] */
+};
+
+enum mg_flash_attn512_i {
+  MG_FLASH_ATTN512_I_B = 0,
+  MG_FLASH_ATTN512_I_NTOK = 1,
+  MG_FLASH_ATTN512_I_LDQ = 2,     /* row stride of Q and K */
+  MG_FLASH_ATTN512_I_LDO = 3,
+  MG_FLASH_ATTN512_I_LDVT = 4     /* >= Ntok rounded up to 32 */
+};
+enum mg_flash_attn512_f { MG_FLASH_ATTN512_F_SCALE = 0 };   /* softmax scale */
+enum mg_flash_attn512_p {
+  MG_FLASH_ATTN512_P_Q = 0,       /* bf16 (row stride ldq) */
+  MG_FLASH_ATTN512_P_K = 1,       /* bf16 (row stride ldq) */
+  MG_FLASH_ATTN512_P_VT = 2,      /* bf16 [B][512][ldvt] (natural key order, pad columns zero) */
+  MG_FLASH_ATTN512_P_O = 3        /* bf16 (row stride ldo) */
+};
+enum mg_flash_attn512_l { MG_FLASH_ATTN512_L_SQ = 0, MG_FLASH_ATTN512_L_SK = 1, MG_FLASH_ATTN512_L_SVT = 2, MG_FLASH_ATTN512_L_SO = 3 };   /* batch strides of Q, K, Vt, O */
+
+enum mg_softmax_rows_i {
+  MG_SOFTMAX_ROWS_I_R = 0,        /* rows */
+  MG_SOFTMAX_ROWS_I_NCOLS = 1,
+  MG_SOFTMAX_ROWS_I_LDS = 2,      /* row stride of the scores */
+  MG_SOFTMAX_ROWS_I_LDP = 3       /* row stride of the probabilities (pad columns zeroed) */
+};
+enum mg_softmax_rows_p {
+  MG_SOFTMAX_ROWS_P_SCORES = 0,   /* f32 [R][lds] */
+  MG_SOFTMAX_ROWS_P_PROBS = 1     /* bf16 [R][ldp] */
+};
+
+enum mg_sched_step_f { MG_SCHED_STEP_F_CX = 0, MG_SCHED_STEP_F_CM = 1, MG_SCHED_STEP_F_CN = 2 };   /* coefficients of x, model_out, noise */
+enum mg_sched_step_p {
+  MG_SCHED_STEP_P_X = 0,          /* f32 [n] */
+  MG_SCHED_STEP_P_MODEL_OUT = 1,  /* f32 [n] */
+  MG_SCHED_STEP_P_NOISE = 2,      /* f32 [n] | NULL */
+  MG_SCHED_STEP_P_OUT = 3         /* f32 [n] */
+};
+enum mg_sched_step_l { MG_SCHED_STEP_L_N = 0 };   /* elements */
+
+enum mg_linear_small_m_i {
+  MG_LINEAR_SMALL_M_I_M = 0,
+  MG_LINEAR_SMALL_M_I_N = 1,
+  MG_LINEAR_SMALL_M_I_K = 2,
+  MG_LINEAR_SMALL_M_I_ACT_IN = 3,   /* 0 none, 1 silu */
+  MG_LINEAR_SMALL_M_I_ACT_OUT = 4,  /* 0 none, 1 silu */
+  MG_LINEAR_SMALL_M_I_LDO = 5       /* row stride of out (0 = N) */
+};
+enum mg_linear_small_m_p {
+  MG_LINEAR_SMALL_M_P_X = 0,      /* f32 [M][K] */
+  MG_LINEAR_SMALL_M_P_W = 1,      /* f32 [N][K] */
+  MG_LINEAR_SMALL_M_P_BIAS = 2,   /* f32 [N] | NULL */
+  MG_LINEAR_SMALL_M_P_OUT = 3     /* f32 [M][ldo] */
+};
+
+enum mg_latent_1x1_i { MG_LATENT_1X1_I_B = 0, MG_LATENT_1X1_I_CI = 1, MG_LATENT_1X1_I_CO = 2, MG_LATENT_1X1_I_HW = 3 };
+enum mg_latent_1x1_f { MG_LATENT_1X1_F_SCALE = 0 };   /* input scale (0 = 1) */
+enum mg_latent_1x1_p {
+  MG_LATENT_1X1_P_X = 0,          /* f32 [B][Ci][HW] */
+  MG_LATENT_1X1_P_W = 1,          /* f32 [Co][Ci] */
+  MG_LATENT_1X1_P_BIAS = 2,       /* f32 [Co] */
+  MG_LATENT_1X1_P_OUT = 3         /* f32 [B][Co][HW] */
+};
+
+enum mg_post_nchw_i {
+  MG_POST_NCHW_I_B = 0,
+  MG_POST_NCHW_I_HW = 1,
+  MG_POST_NCHW_I_COUT = 2,        /* 1 | 3 | 4 | 8 | 12 */
+  MG_POST_NCHW_I_LDI = 3,         /* row stride of the input */
+  MG_POST_NCHW_I_POST = 4         /* MG_POST_* */
+};
+enum mg_post_nchw_f {
+  MG_POST_NCHW_F_SCALE = 0,       /* scale on the input (0 = 1) */
+  MG_POST_NCHW_F_CX = 1,          /* MG_POST_SCHED: coefficient of out (the latent x_t), */
+  MG_POST_NCHW_F_CM = 2,          /* of the input (the model's output), */
+  MG_POST_NCHW_F_CN = 3           /* of the noise */
+};
+enum mg_post_nchw_p {
+  MG_POST_NCHW_P_X = 0,           /* f32 [B*HW][ldi] */
+  MG_POST_NCHW_P_OUT = 1,         /* f32 NCHW */
+  MG_POST_NCHW_P_NOISE = 2        /* f32 NCHW | NULL (MG_POST_SCHED) */
+};
+
+enum mg_im2col_small_i {
+  MG_IM2COL_SMALL_I_B = 0,
+  MG_IM2COL_SMALL_I_H = 1,
+  MG_IM2COL_SMALL_I_W = 2,
+  MG_IM2COL_SMALL_I_C0 = 3,
+  MG_IM2COL_SMALL_I_C1 = 4,
+  MG_IM2COL_SMALL_I_KP = 5,               /* columns of out (>= 9 (C0 + C1)) */
+  MG_IM2COL_SMALL_I_SRC0_BROADCAST = 6,   /* 1 = src0 row 0 for every b, 0 = row b */
+  MG_IM2COL_SMALL_I_MEMBERS_PER_SRC0 = 7  /* 0 = src0_broadcast decides; m > 0 = row b reads src0 row b / m (several images in one program,
+                                             m ensemble members each; requires src0_broadcast = 0 and B % m == 0) */
+};
+enum mg_im2col_small_p {
+  MG_IM2COL_SMALL_P_SRC0 = 0,     /* f32 [B | 1 | B / members_per_src0][C0][H][W] */
+  MG_IM2COL_SMALL_P_SRC1 = 1,     /* f32 [B][C1][H][W] | NULL */
+  MG_IM2COL_SMALL_P_OUT = 2       /* bf16 [B*H*W][Kp] */
+};
+
+enum mg_conv3x3_head_i {
+  MG_CONV3X3_HEAD_I_B = 0,
+  MG_CONV3X3_HEAD_I_H = 1,
+  MG_CONV3X3_HEAD_I_W = 2,
+  MG_CONV3X3_HEAD_I_C = 3,        /* % 32 == 0 */
+  MG_CONV3X3_HEAD_I_COUT = 4,     /* 1..4 */
+  MG_CONV3X3_HEAD_I_LDO = 5,      /* row stride of out (0 = Cout) */
+  MG_CONV3X3_HEAD_I_SILU = 6
+};
+enum mg_conv3x3_head_p {
+  MG_CONV3X3_HEAD_P_X = 0,        /* bf16 [B][H][W][C] */
+  MG_CONV3X3_HEAD_P_SS = 1,       /* scale_shift f32 [B][2][C] | NULL */
+  MG_CONV3X3_HEAD_P_WT = 2,       /* bf16 [>= Cout][9 C], k = (ky*3+kx)*C + c */
+  MG_CONV3X3_HEAD_P_BIAS = 3,     /* f32 | NULL */
+  MG_CONV3X3_HEAD_P_OUT = 4       /* f32 [B H W][ldo] (columns [0, Cout): what MG_OP_POST_NCHW reads) */
+};
+
+enum mg_ens_depth_stats_i { MG_ENS_DEPTH_STATS_I_E = 0 };
+enum mg_ens_depth_stats_p {
+  MG_ENS_DEPTH_STATS_P_D = 0,         /* f32 [E][HW] */
+  MG_ENS_DEPTH_STATS_P_SCRATCH = 1,   /* f64 per-block partials (size: see the op) */
+  MG_ENS_DEPTH_STATS_P_OUT = 2        /* f64 [3E + E*E] */
+};
+enum mg_ens_depth_stats_l { MG_ENS_DEPTH_STATS_L_HW = 0 };
+enum mg_ens_depth_median_i {
+  MG_ENS_DEPTH_MEDIAN_I_E = 0,
+  MG_ENS_DEPTH_MEDIAN_I_REDUCTION = 1,  /* 0 median, 1 mean */
+  MG_ENS_DEPTH_MEDIAN_I_HAS_SHIFT = 2
+};
+enum mg_ens_depth_median_p {
+  MG_ENS_DEPTH_MEDIAN_P_D = 0,        /* f32 [E][HW] */
+  MG_ENS_DEPTH_MEDIAN_P_ST = 1,       /* f32 [s[E], t[E]] | NULL (no alignment) */
+  MG_ENS_DEPTH_MEDIAN_P_MED = 2,      /* f32 [HW] | NULL */
+  MG_ENS_DEPTH_MEDIAN_P_MAD = 3,      /* f32 [HW] | NULL */
+  MG_ENS_DEPTH_MEDIAN_P_MINMAX = 4,   /* f32 [2 + 2E] = min, max of the prediction and the raw member values d[.][argmin px], d[.][argmax px]
+                                         (exact sub-gradient of the regulariser on the host) */
+  MG_ENS_DEPTH_MEDIAN_P_SCRATCH = 5   /* >= 12288 B */
+};
+enum mg_ens_depth_median_l { MG_ENS_DEPTH_MEDIAN_L_HW = 0 };
+enum mg_ens_depth_norm_i { MG_ENS_DEPTH_NORM_I_SHIFT_INVARIANT = 0 };
+enum mg_ens_depth_norm_p {
+  MG_ENS_DEPTH_NORM_P_MED = 0,        /* f32 [HW] */
+  MG_ENS_DEPTH_NORM_P_MAD = 1,        /* f32 [HW] | NULL */
+  MG_ENS_DEPTH_NORM_P_MINMAX = 2      /* MG_ENS_DEPTH_MEDIAN_P_MINMAX */
+};
+enum mg_ens_depth_norm_l { MG_ENS_DEPTH_NORM_L_HW = 0 };
+enum mg_ens_normals_i {
+  MG_ENS_NORMALS_I_E = 0,
+  MG_ENS_NORMALS_I_REDUCTION = 1      /* 0 closest, 1 mean */
+};
+enum mg_ens_normals_p {
+  MG_ENS_NORMALS_P_NORMALS = 0,       /* f32 [E][3][HW] */
+  MG_ENS_NORMALS_P_OUT = 1,           /* f32 [3][HW] */
+  MG_ENS_NORMALS_P_UNC = 2            /* f32 [HW] | NULL */
+};
+enum mg_ens_normals_l { MG_ENS_NORMALS_L_HW = 0 };
+
+enum mg_resize_i {
+  MG_RESIZE_I_PLANES = 0,         /* = B * C */
+  MG_RESIZE_I_HIN = 1,
+  MG_RESIZE_I_WIN = 2,
+  MG_RESIZE_I_HOUT = 3,
+  MG_RESIZE_I_WOUT = 4,
+  MG_RESIZE_I_MODE = 5,           /* 0 bilinear, 1 bicubic, 2 nearest-exact */
+  MG_RESIZE_I_U8 = 6              /* 1: uint8 in / out - computed in float, rounded half-to-even; 0: fp32 */
+};
+enum mg_resize_p {
+  MG_RESIZE_P_SRC = 0,
+  MG_RESIZE_P_DST = 1,
+  MG_RESIZE_P_TMP = 2             /* f32 [planes][Hin][Wout] | NULL (needed when both sizes change) */
+};
+
+enum mg_colorize_f { MG_COLORIZE_F_MIN_DEPTH = 0, MG_COLORIZE_F_MAX_DEPTH = 1 };
+enum mg_colorize_p {
+  MG_COLORIZE_P_DEPTH = 0,        /* f32 [n] */
+  MG_COLORIZE_P_LUT = 1,          /* uint8 [256][3] (matplotlib's table) */
+  MG_COLORIZE_P_OUT = 2           /* uint8 [n][3] (HWC) */
+};
+enum mg_colorize_l { MG_COLORIZE_L_N = 0 };
+
+enum mg_eval_depth_ls_i {
+  MG_EVAL_DEPTH_LS_I_H = 0,
+  MG_EVAL_DEPTH_LS_I_W = 1,
+  MG_EVAL_DEPTH_LS_I_DISPARITY = 2,   /* 1 = y = 1 / gt, valid &= gt > 0 & pred > 0 (script/depth/eval.py:185-201) */
+  MG_EVAL_DEPTH_LS_I_FIT_W = 3        /* width of the sub-sampled fit (alignment_max_res: floor(W * factor), only the width shrinks; 0 = every pixel) */
+};
+enum mg_eval_depth_ls_f { MG_EVAL_DEPTH_LS_F_INV_FACTOR = 0 };   /* fp32(1 / factor): source column = min(floor(dst * inv_factor), W - 1) */
+enum mg_eval_depth_ls_p {
+  MG_EVAL_DEPTH_LS_P_PRED = 0,        /* f32 [H][W] */
+  MG_EVAL_DEPTH_LS_P_GT = 1,          /* f32 [H][W] */
+  MG_EVAL_DEPTH_LS_P_MASK = 2,        /* uint8 [H][W] (non-zero = valid) */
+  MG_EVAL_DEPTH_LS_P_OUT = 3,         /* f64 [5] */
+  MG_EVAL_DEPTH_LS_P_SCRATCH = 4      /* f64 [512][5] */
+};
+enum mg_eval_depth_metrics_i {
+  MG_EVAL_DEPTH_METRICS_I_H = 0,
+  MG_EVAL_DEPTH_METRICS_I_W = 1,
+  MG_EVAL_DEPTH_METRICS_I_DISPARITY = 2,
+  MG_EVAL_DEPTH_METRICS_I_CLIP_MIN = 3,   /* 1 = clip below at F_MIN_DEPTH */
+  MG_EVAL_DEPTH_METRICS_I_CLIP_MAX = 4    /* 1 = clip above at F_MAX_DEPTH */
+};
+enum mg_eval_depth_metrics_f { MG_EVAL_DEPTH_METRICS_F_MIN_DEPTH = 0, MG_EVAL_DEPTH_METRICS_F_MAX_DEPTH = 1 };
+enum mg_eval_depth_metrics_p {
+  MG_EVAL_DEPTH_METRICS_P_PRED = 0,
+  MG_EVAL_DEPTH_METRICS_P_GT = 1,
+  MG_EVAL_DEPTH_METRICS_P_MASK = 2,
+  MG_EVAL_DEPTH_METRICS_P_SUMS = 3,       /* the five sums f64 [5] | NULL (s = 1, t = 0) */
+  MG_EVAL_DEPTH_METRICS_P_OUT = 4,        /* f64 [13] = abs_relative_difference, squared_relative_difference, rmse_linear, rmse_log, log10,
+                                             delta1_acc, delta2_acc, delta3_acc, i_rmse, silog_rmse, scale, shift, n */
+  MG_EVAL_DEPTH_METRICS_P_SCRATCH = 5     /* f64 [512][11] */
+};
+enum mg_eval_normals_i { MG_EVAL_NORMALS_I_MASKED = 0 };   /* drop the pixels whose gt vector has zero norm */
+enum mg_eval_normals_p {
+  MG_EVAL_NORMALS_P_PRED = 0,         /* f32 [3][HW] */
+  MG_EVAL_NORMALS_P_GT = 1,           /* f32 [3][HW] */
+  MG_EVAL_NORMALS_P_OUT = 2,          /* f64 [9] = mean, median, percentages below 5 / 7.5 / 11.25 / 22.5 / 30 degrees, rmse, n (n = 0: NaN) */
+  MG_EVAL_NORMALS_P_ERR = 3,          /* error map f32 [HW] | NULL (dropped pixels hold -1) */
+  MG_EVAL_NORMALS_P_WS = 4            /* workspace (MG_EVAL_WS_BYTES, 8-byte aligned; owned by the launch) */
+};
+enum mg_eval_normals_l { MG_EVAL_NORMALS_L_HW = 0 };
+
+enum mg_memset_i { MG_MEMSET_I_VALUE = 0 };   /* byte value */
+enum mg_memset_p { MG_MEMSET_P_DST = 0 };
+enum mg_memset_l { MG_MEMSET_L_BYTES = 0 };
+enum mg_copy_p { MG_COPY_P_SRC = 0, MG_COPY_P_DST = 1 };
+enum mg_copy_l { MG_COPY_L_BYTES = 0 };
+
+enum mg_iidscore_prep_i {
+  MG_IIDSCORE_PREP_I_H = 0,
+  MG_IIDSCORE_PREP_I_W = 1,
+  MG_IIDSCORE_PREP_I_GAMMA = 2        /* MG_IID_GAMMA_*: x <- x^gamma in fp32 on every load of both images */
+};
+enum mg_iidscore_prep_p {
+  MG_IIDSCORE_PREP_P_PRED = 0,        /* f32 [3][H][W] */
+  MG_IIDSCORE_PREP_P_GT = 1,          /* f32 [3][H][W] */
+  MG_IIDSCORE_PREP_P_MASK = 2,        /* uint8 [3][H][W] (non-zero = valid) | NULL (every element valid) */
+  MG_IIDSCORE_PREP_P_OUT = 3,         /* f64 [8], see the op */
+  MG_IIDSCORE_PREP_P_WS = 4           /* workspace (MG_EVAL_WS_BYTES, 8-byte aligned) */
+};
+enum mg_iidscore_psnr_i {
+  MG_IIDSCORE_PSNR_I_H = 0,
+  MG_IIDSCORE_PSNR_I_W = 1,
+  MG_IIDSCORE_PSNR_I_GAMMA = 2,
+  MG_IIDSCORE_PSNR_I_UP_TO_SCALE = 3, /* 1 = an up-to-scale target: map both images on load with what PREP found */
+  MG_IIDSCORE_PSNR_I_WRITE_PSNR = 4   /* 1 = write out[0] (0: only count the valid elements) */
+};
+enum mg_iidscore_psnr_p {
+  MG_IIDSCORE_PSNR_P_PRED = 0,
+  MG_IIDSCORE_PSNR_P_GT = 1,
+  MG_IIDSCORE_PSNR_P_MASK = 2,
+  MG_IIDSCORE_PSNR_P_OUT = 3,
+  MG_IIDSCORE_PSNR_P_WS = 4
+};
+enum mg_iidscore_ssim_i {
+  MG_IIDSCORE_SSIM_I_H = 0,
+  MG_IIDSCORE_SSIM_I_W = 1,
+  MG_IIDSCORE_SSIM_I_GAMMA = 2,
+  MG_IIDSCORE_SSIM_I_UP_TO_SCALE = 3
+};
+enum mg_iidscore_ssim_p {
+  MG_IIDSCORE_SSIM_P_PRED = 0,
+  MG_IIDSCORE_SSIM_P_GT = 1,
+  MG_IIDSCORE_SSIM_P_MASK = 2,
+  MG_IIDSCORE_SSIM_P_OUT = 3,
+  MG_IIDSCORE_SSIM_P_WS = 4
+};
+
+enum mg_iid_vis_i {
+  MG_IID_VIS_I_N = 0,                 /* targets (<= 16) */
+  MG_IID_VIS_I_H = 1,
+  MG_IID_VIS_I_W = 2,
+  MG_IID_VIS_I_LINEAR_BITS = 3,       /* bit t: target t is in linear space */
+  MG_IID_VIS_I_UP_TO_SCALE_BITS = 4   /* bit t: target t is up to scale */
+};
+enum mg_iid_vis_p {
+  MG_IID_VIS_P_PRED = 0,              /* f32 [n][3][H][W] */
+  MG_IID_VIS_P_OUT = 1,               /* uint8 [n][H][W][3] (HWC) */
+  MG_IID_VIS_P_WS = 2                 /* f32 [n][MG_IID_VIS_PARTS] (may be NULL when no target is both linear and up to scale) */
 };
 
 typedef struct mg_program mg_program;

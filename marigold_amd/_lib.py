@@ -58,9 +58,9 @@ def iid_gamma_mode(gamma):
 EPI_BF16, EPI_GEGLU, EPI_F32, EPI_SOFTMAX2, EPI_XATTN2 = 0, 1, 2, 3, 4
 POST_NONE, POST_DEPTH, POST_NORMALS, POST_UNIT, POST_SCHED = 0, 1, 2, 3, 4
 
-# Field names of the four kinds with many launch forms: kind -> (enumerator prefix, {array: names in slot order}) - the mirror of
-# the MG_<KIND>_<I|F|P|L>_<NAME> enumerators of include/marigold_hip.h (lower case here; the position is the slot).
-# tests/test_host.py compares the two; ops.py builds and decodes these kinds by these names.
+# Field names of every kind: kind -> (enumerator prefix, {array: names in slot order}) - the mirror of the
+# MG_<KIND>_<I|F|P|L>_<NAME> enumerators of include/marigold_hip.h (lower case here; the position is the slot).
+# tests/test_host.py compares the two; ops.py builds and reads every kind by these names.
 FIELDS = {
     OP_IGEMM: ("IGEMM", dict(
         i=("b", "h", "w", "cin", "ho", "wo", "n", "taps", "stride", "pad", "hu", "wu", "epi", "ldo", "trans_from", "batch_z", "ldr",
@@ -83,33 +83,118 @@ FIELDS = {
         f=("scale", "redo_thr"),
         p=("q", "k", "vt", "o", "dbg", "ws"),
         l=("sq", "sk", "svt", "so"))),
-}
-
-# The same table for the two I/O stages (MG_RGB_PREP_* / MG_NORMALS_VIS_* in the header; tests/test_io_stages_host.py compares them).
-# Kept beside FIELDS, which stays the set of the four many-form kinds.
-IO_FIELDS = {
     OP_RGB_PREP: ("RGB_PREP", dict(
         i=("hin", "win", "hout", "wout", "mode", "hwc", "out16", "reciprocal"),
         p=("src", "dst", "tmp"))),
     OP_NORMALS_VIS: ("NORMALS_VIS", dict(
         i=("h", "w"),
         p=("pred", "out"))),
-}
-
-# ... and for the noise generator (MG_RANDN_* in the header; tests/test_native_noise_host.py compares them).
-NOISE_FIELDS = {
     OP_RANDN: ("RANDN", dict(
         i=("mode", "out16"),
         p=("dst",),
         l=("n", "offset", "seed", "stream"))),
-}
-
-# ... and for the intrinsic-image ensemble (MG_ENS_IID_* in the header; tests/test_iid_c_host.py compares them).
-ENS_FIELDS = {
     OP_ENS_IID: ("ENS_IID", dict(
         i=("e", "reduction"),
         p=("preds", "pred", "unc"),
         l=("n",))),
+    OP_GN_STATS: ("GN_STATS", dict(
+        i=("b", "hw", "c", "chunks", "ctot", "coff", "groups", "slot0", "slots", "c1"),
+        f=("eps",),
+        p=("x", "partials", "gamma", "beta", "ss", "counters", "x1"))),
+    OP_GN_FINALIZE: ("GN_FINALIZE", dict(
+        i=("b", "c", "groups", "slots", "hw"),
+        f=("eps",),
+        p=("partials", "gamma", "beta", "ss"))),
+    OP_GN_APPLY: ("GN_APPLY", dict(
+        i=("b", "hw", "c", "silu", "c0"),
+        p=("x", "ss", "out", "x1"))),
+    OP_GN_SLAB: ("GN_SLAB", dict(
+        i=("b", "hw", "c", "c0", "groups", "silu"),
+        f=("eps",),
+        p=("x0", "x1", "out", "gamma", "beta", "ss"))),
+    OP_FLASH_ATTN512: ("FLASH_ATTN512", dict(
+        i=("b", "ntok", "ldq", "ldo", "ldvt"),
+        f=("scale",),
+        p=("q", "k", "vt", "o"),
+        l=("sq", "sk", "svt", "so"))),
+    OP_SOFTMAX_ROWS: ("SOFTMAX_ROWS", dict(
+        i=("r", "ncols", "lds", "ldp"),
+        p=("scores", "probs"))),
+    OP_SCHED_STEP: ("SCHED_STEP", dict(
+        f=("cx", "cm", "cn"),
+        p=("x", "model_out", "noise", "out"),
+        l=("n",))),
+    OP_LINEAR_SMALL_M: ("LINEAR_SMALL_M", dict(
+        i=("m", "n", "k", "act_in", "act_out", "ldo"),
+        p=("x", "w", "bias", "out"))),
+    OP_LATENT_1X1: ("LATENT_1X1", dict(
+        i=("b", "ci", "co", "hw"),
+        f=("scale",),
+        p=("x", "w", "bias", "out"))),
+    OP_POST_NCHW: ("POST_NCHW", dict(
+        i=("b", "hw", "cout", "ldi", "post"),
+        f=("scale", "cx", "cm", "cn"),
+        p=("x", "out", "noise"))),
+    OP_IM2COL_SMALL: ("IM2COL_SMALL", dict(
+        i=("b", "h", "w", "c0", "c1", "kp", "src0_broadcast", "members_per_src0"),
+        p=("src0", "src1", "out"))),
+    OP_CONV3X3_HEAD: ("CONV3X3_HEAD", dict(
+        i=("b", "h", "w", "c", "cout", "ldo", "silu"),
+        p=("x", "ss", "wt", "bias", "out"))),
+    OP_ENS_DEPTH_STATS: ("ENS_DEPTH_STATS", dict(
+        i=("e",),
+        p=("d", "scratch", "out"),
+        l=("hw",))),
+    OP_ENS_DEPTH_MEDIAN: ("ENS_DEPTH_MEDIAN", dict(
+        i=("e", "reduction", "has_shift"),
+        p=("d", "st", "med", "mad", "minmax", "scratch"),
+        l=("hw",))),
+    OP_ENS_DEPTH_NORM: ("ENS_DEPTH_NORM", dict(
+        i=("shift_invariant",),
+        p=("med", "mad", "minmax"),
+        l=("hw",))),
+    OP_ENS_NORMALS: ("ENS_NORMALS", dict(
+        i=("e", "reduction"),
+        p=("normals", "out", "unc"),
+        l=("hw",))),
+    OP_RESIZE: ("RESIZE", dict(
+        i=("planes", "hin", "win", "hout", "wout", "mode", "u8"),
+        p=("src", "dst", "tmp"))),
+    OP_COLORIZE: ("COLORIZE", dict(
+        f=("min_depth", "max_depth"),
+        p=("depth", "lut", "out"),
+        l=("n",))),
+    OP_EVAL_DEPTH_LS: ("EVAL_DEPTH_LS", dict(
+        i=("h", "w", "disparity", "fit_w"),
+        f=("inv_factor",),
+        p=("pred", "gt", "mask", "out", "scratch"))),
+    OP_EVAL_DEPTH_METRICS: ("EVAL_DEPTH_METRICS", dict(
+        i=("h", "w", "disparity", "clip_min", "clip_max"),
+        f=("min_depth", "max_depth"),
+        p=("pred", "gt", "mask", "sums", "out", "scratch"))),
+    OP_EVAL_NORMALS: ("EVAL_NORMALS", dict(
+        i=("masked",),
+        p=("pred", "gt", "out", "err", "ws"),
+        l=("hw",))),
+    OP_MEMSET: ("MEMSET", dict(
+        i=("value",),
+        p=("dst",),
+        l=("bytes",))),
+    OP_COPY: ("COPY", dict(
+        p=("src", "dst"),
+        l=("bytes",))),
+    OP_IIDSCORE_PREP: ("IIDSCORE_PREP", dict(
+        i=("h", "w", "gamma"),
+        p=("pred", "gt", "mask", "out", "ws"))),
+    OP_IIDSCORE_PSNR: ("IIDSCORE_PSNR", dict(
+        i=("h", "w", "gamma", "up_to_scale", "write_psnr"),
+        p=("pred", "gt", "mask", "out", "ws"))),
+    OP_IIDSCORE_SSIM: ("IIDSCORE_SSIM", dict(
+        i=("h", "w", "gamma", "up_to_scale"),
+        p=("pred", "gt", "mask", "out", "ws"))),
+    OP_IID_VIS: ("IID_VIS", dict(
+        i=("n", "h", "w", "linear_bits", "up_to_scale_bits"),
+        p=("pred", "out", "ws"))),
 }
 
 OP_NAMES = {v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}

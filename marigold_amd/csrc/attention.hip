@@ -164,10 +164,11 @@ int mg_launch_attention(const mg_op* op, hipStream_t s) {
       break;
     }
     case MG_OP_SOFTMAX_ROWS: {
-      const int R = op->i[0], ncols = op->i[1], lds_ = op->i[2], ldp = op->i[3];
+      const int R = op->i[MG_SOFTMAX_ROWS_I_R], ncols = op->i[MG_SOFTMAX_ROWS_I_NCOLS];
+      const int lds_ = op->i[MG_SOFTMAX_ROWS_I_LDS], ldp = op->i[MG_SOFTMAX_ROWS_I_LDP];
       MG_REQUIRE(R > 0 && ncols > 0 && lds_ % 4 == 0 && ldp % 4 == 0 && ldp >= ncols, "softmax_rows: bad dims");
-      MG_LAUNCH(softmax_rows_kernel, dim3(R), dim3(256), 0, s, (const float*)op->p[0],
-                         (bf16_t*)op->p[1], ncols, (long long)lds_, (long long)ldp);
+      MG_LAUNCH(softmax_rows_kernel, dim3(R), dim3(256), 0, s, (const float*)op->p[MG_SOFTMAX_ROWS_P_SCORES],
+                         (bf16_t*)op->p[MG_SOFTMAX_ROWS_P_PROBS], ncols, (long long)lds_, (long long)ldp);
       break;
     }
     default: MG_REQUIRE(false, "attention: bad op kind %d", op->kind);

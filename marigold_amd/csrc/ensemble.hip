@@ -700,12 +700,28 @@ void launch_iid(const float* d, float* pred, float* unc, int E, long long n, int
   MG_LAUNCH(iid_kernel<E_>, dim3(nblk), dim3(256), 0, s, d, pred, unc, E, n, reduction, vec);
 }
 
+// MG_OP_ENS_DEPTH_MEDIAN decoded once: the argument list its three selection kernels share.  The scratch holds the per-block
+// (min, max) table and, behind it, the pixels they were found at.
+struct MedianOp {
+  const float *d, *st;
+  float *med, *mad, *minmax, *blockmm;
+  long long* blockpx;
+  int E;
+  long long HW;
+  int reduction, has_shift;
+  explicit MedianOp(const mg_op* op)
+      : d((const float*)op->p[MG_ENS_DEPTH_MEDIAN_P_D]), st((const float*)op->p[MG_ENS_DEPTH_MEDIAN_P_ST]),
+        med((float*)op->p[MG_ENS_DEPTH_MEDIAN_P_MED]), mad((float*)op->p[MG_ENS_DEPTH_MEDIAN_P_MAD]),
+        minmax((float*)op->p[MG_ENS_DEPTH_MEDIAN_P_MINMAX]), blockmm((float*)op->p[MG_ENS_DEPTH_MEDIAN_P_SCRATCH]),
+        blockpx((long long*)((char*)op->p[MG_ENS_DEPTH_MEDIAN_P_SCRATCH] + 8 * ENS_BLOCKS)), E(op->i[MG_ENS_DEPTH_MEDIAN_I_E]),
+        HW(op->l[MG_ENS_DEPTH_MEDIAN_L_HW]), reduction(op->i[MG_ENS_DEPTH_MEDIAN_I_REDUCTION]),
+        has_shift(op->i[MG_ENS_DEPTH_MEDIAN_I_HAS_SHIFT]) {}
+};
+#define MEDIAN_KERNEL_ARGS(m) m.d, m.st, m.med, m.mad, m.blockmm, m.blockpx, m.E, m.HW, m.reduction, m.has_shift, m.st != nullptr
+
 template <int E_>
-void launch_median(const mg_op* op, int nblk, hipStream_t s) {
-  MG_LAUNCH(depth_median_kernel<E_>, dim3(nblk), dim3(256), 0, s, (const float*)op->p[0],
-                     (const float*)op->p[1], (float*)op->p[2], (float*)op->p[3], (float*)op->p[5],
-                     (long long*)((char*)op->p[5] + 8 * ENS_BLOCKS), op->i[0], op->l[0], op->i[1], op->i[2],
-                     op->p[1] != nullptr);
+void launch_median(const MedianOp& m, int nblk, hipStream_t s) {
+  MG_LAUNCH(depth_median_kernel<E_>, dim3(nblk), dim3(256), 0, s, MEDIAN_KERNEL_ARGS(m));
 }
 
 }  // namespace
@@ -713,59 +729,54 @@ void launch_median(const mg_op* op, int nblk, hipStream_t s) {
 int mg_launch_ensemble(const mg_op* op, hipStream_t s) {
   switch (op->kind) {
     case MG_OP_ENS_DEPTH_STATS: {
-      const int E = op->i[0];
-      const long long HW = op->l[0];
+      const int E = op->i[MG_ENS_DEPTH_STATS_I_E];
+      const long long HW = op->l[MG_ENS_DEPTH_STATS_L_HW];
       MG_REQUIRE(E >= 1 && E <= 65535, "ens_depth_stats: E %d out of range [1,65535]", E);
       // (the partial table is nblk x E x (E + 3) doubles: fewer pixel blocks for the ensembles beyond the kernels' usual range)
       const int nblk = (int)min((HW + 255) / 256, (long long)(E > 256 ? 32 : 128));
-      MG_LAUNCH(depth_stats_kernel, dim3(nblk, E, (E + EMAX - 1) / EMAX), dim3(256), 0, s, (const float*)op->p[0],
-                         (double*)op->p[1], E, HW);
-      MG_LAUNCH(depth_stats_final_kernel, dim3(1), dim3(256), 0, s, (const double*)op->p[1],
-                         (double*)op->p[2], E, nblk, HW);
+      MG_LAUNCH(depth_stats_kernel, dim3(nblk, E, (E + EMAX - 1) / EMAX), dim3(256), 0, s, (const float*)op->p[MG_ENS_DEPTH_STATS_P_D],
+                         (double*)op->p[MG_ENS_DEPTH_STATS_P_SCRATCH], E, HW);
+      MG_LAUNCH(depth_stats_final_kernel, dim3(1), dim3(256), 0, s, (const double*)op->p[MG_ENS_DEPTH_STATS_P_SCRATCH],
+                         (double*)op->p[MG_ENS_DEPTH_STATS_P_OUT], E, nblk, HW);
       break;
     }
     case MG_OP_ENS_DEPTH_MEDIAN: {
-      const int E = op->i[0];
-      const long long HW = op->l[0];
+      const MedianOp m(op);
+      const int E = m.E;
       MG_REQUIRE(E >= 1, "ens_depth_median: E %d must be >= 1", E);
-      MG_REQUIRE(op->p[4] && op->p[5], "ens_depth_median: minmax / scratch missing");
-      const int nblk = (int)min((HW + 255) / 256, (long long)ENS_BLOCKS);
+      MG_REQUIRE(m.minmax && m.blockmm, "ens_depth_median: minmax / scratch missing");
+      const int nblk = (int)min((m.HW + 255) / 256, (long long)ENS_BLOCKS);
       if (E > EMAX_LDS) {
-        MG_LAUNCH(depth_median_big_kernel, dim3(nblk), dim3(256), 0, s, (const float*)op->p[0], (const float*)op->p[1],
-                  (float*)op->p[2], (float*)op->p[3], (float*)op->p[5], (long long*)((char*)op->p[5] + 8 * ENS_BLOCKS), E,
-                  op->l[0], op->i[1], op->i[2], op->p[1] != nullptr);
+        MG_LAUNCH(depth_median_big_kernel, dim3(nblk), dim3(256), 0, s, MEDIAN_KERNEL_ARGS(m));
       } else if (E > EMAX) {
         const size_t lds = ((size_t)E * 256 + 2 * E) * sizeof(float);
         MG_KERNEL_MAX_LDS((const void*)depth_median_lds_kernel, (int)(((size_t)EMAX_LDS * 256 + 2 * EMAX_LDS) * sizeof(float)));
-        MG_LAUNCH(depth_median_lds_kernel, dim3(nblk), dim3(256), lds, s, (const float*)op->p[0], (const float*)op->p[1],
-                  (float*)op->p[2], (float*)op->p[3], (float*)op->p[5], (long long*)((char*)op->p[5] + 8 * ENS_BLOCKS), E,
-                  op->l[0], op->i[1], op->i[2], op->p[1] != nullptr);
-      } else if (E <= 4) launch_median<4>(op, nblk, s);
-      else if (E <= 8) launch_median<8>(op, nblk, s);
-      else if (E <= 10) launch_median<10>(op, nblk, s);
-      else if (E <= 16) launch_median<16>(op, nblk, s);
-      else launch_median<EMAX>(op, nblk, s);
+        MG_LAUNCH(depth_median_lds_kernel, dim3(nblk), dim3(256), lds, s, MEDIAN_KERNEL_ARGS(m));
+      } else if (E <= 4) launch_median<4>(m, nblk, s);
+      else if (E <= 8) launch_median<8>(m, nblk, s);
+      else if (E <= 10) launch_median<10>(m, nblk, s);
+      else if (E <= 16) launch_median<16>(m, nblk, s);
+      else launch_median<EMAX>(m, nblk, s);
       // (round 3: finishing the reduction in the median kernel's last-arriving block instead - fence + ticket per block - measured
       // SLOWER than this 5 us launch: 40-41 vs 34-36 us per pass, profiles/r3_ab_native_bfgs_alignment.log)
-      MG_LAUNCH(minmax_final_kernel, dim3(1), dim3(64), 0, s, (const float*)op->p[5],
-                         (const long long*)((char*)op->p[5] + 8 * ENS_BLOCKS), (const float*)op->p[0],
-                         (float*)op->p[4], nblk, E, HW);
+      MG_LAUNCH(minmax_final_kernel, dim3(1), dim3(64), 0, s, (const float*)m.blockmm, (const long long*)m.blockpx, m.d, m.minmax, nblk, E,
+                m.HW);
       break;
     }
     case MG_OP_ENS_DEPTH_NORM: {
-      const long long HW = op->l[0];
+      const long long HW = op->l[MG_ENS_DEPTH_NORM_L_HW];
       const int nblk = (int)min((HW + 255) / 256, (long long)2048);
-      MG_LAUNCH(depth_norm_kernel, dim3(nblk), dim3(256), 0, s, (float*)op->p[0], (float*)op->p[1],
-                         (const float*)op->p[2], HW, op->i[0]);
+      MG_LAUNCH(depth_norm_kernel, dim3(nblk), dim3(256), 0, s, (float*)op->p[MG_ENS_DEPTH_NORM_P_MED], (float*)op->p[MG_ENS_DEPTH_NORM_P_MAD],
+                         (const float*)op->p[MG_ENS_DEPTH_NORM_P_MINMAX], HW, op->i[MG_ENS_DEPTH_NORM_I_SHIFT_INVARIANT]);
       break;
     }
     case MG_OP_ENS_NORMALS: {
-      const int E = op->i[0];
-      const long long HW = op->l[0];
+      const int E = op->i[MG_ENS_NORMALS_I_E];
+      const long long HW = op->l[MG_ENS_NORMALS_L_HW];
       MG_REQUIRE(E >= 1, "ens_normals: E must be >= 1");
       const int nblk = (int)min((HW + 255) / 256, (long long)2048);
-      MG_LAUNCH(normals_kernel, dim3(nblk), dim3(256), 0, s, (const float*)op->p[0],
-                         (float*)op->p[1], (float*)op->p[2], E, HW, op->i[1]);
+      MG_LAUNCH(normals_kernel, dim3(nblk), dim3(256), 0, s, (const float*)op->p[MG_ENS_NORMALS_P_NORMALS],
+                         (float*)op->p[MG_ENS_NORMALS_P_OUT], (float*)op->p[MG_ENS_NORMALS_P_UNC], E, HW, op->i[MG_ENS_NORMALS_I_REDUCTION]);
       break;
     }
     case MG_OP_ENS_IID: {

@@ -640,47 +640,62 @@ int grid_for(long long n) { return (int)max(1ll, min((n + EV_THREADS - 1) / EV_T
 
 }  // namespace
 
+// MG_OP_IIDSCORE_PREP / _PSNR / _SSIM share their slots: the launcher and mg_eval_iid read and write all three by PSNR's names
+#define IID_SAME_SLOT(ARR_NAME) \
+  static_assert((int)MG_IIDSCORE_PREP_##ARR_NAME == (int)MG_IIDSCORE_PSNR_##ARR_NAME && (int)MG_IIDSCORE_SSIM_##ARR_NAME == (int)MG_IIDSCORE_PSNR_##ARR_NAME, #ARR_NAME)
+IID_SAME_SLOT(I_H); IID_SAME_SLOT(I_W); IID_SAME_SLOT(I_GAMMA); IID_SAME_SLOT(P_PRED); IID_SAME_SLOT(P_GT); IID_SAME_SLOT(P_MASK);
+IID_SAME_SLOT(P_OUT); IID_SAME_SLOT(P_WS);
+static_assert((int)MG_IIDSCORE_SSIM_I_UP_TO_SCALE == (int)MG_IIDSCORE_PSNR_I_UP_TO_SCALE, "I_UP_TO_SCALE");
+#undef IID_SAME_SLOT
+
 int mg_launch_evalscore(const mg_op* op, hipStream_t s) {
   switch (op->kind) {
     case MG_OP_EVAL_DEPTH_LS: {
-      const int H = op->i[0], W = op->i[1], OW = op->i[3];
+      const int H = op->i[MG_EVAL_DEPTH_LS_I_H], W = op->i[MG_EVAL_DEPTH_LS_I_W], OW = op->i[MG_EVAL_DEPTH_LS_I_FIT_W];
+      const float inv_factor = op->f[MG_EVAL_DEPTH_LS_F_INV_FACTOR];
+      const float *pred = (const float*)op->p[MG_EVAL_DEPTH_LS_P_PRED], *gt = (const float*)op->p[MG_EVAL_DEPTH_LS_P_GT];
+      const uint8_t* mask = (const uint8_t*)op->p[MG_EVAL_DEPTH_LS_P_MASK];
+      double *out = (double*)op->p[MG_EVAL_DEPTH_LS_P_OUT], *scratch = (double*)op->p[MG_EVAL_DEPTH_LS_P_SCRATCH];
       MG_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31), "eval_depth_ls: bad size %d x %d", H, W);
       MG_REQUIRE(OW >= 0 && OW <= W, "eval_depth_ls: sub-sampled width %d outside [0, %d]", OW, W);
-      MG_REQUIRE(OW == 0 || op->f[0] >= 1.0f, "eval_depth_ls: inverse factor %g must be >= 1", (double)op->f[0]);
-      MG_REQUIRE(op->p[0] && op->p[1] && op->p[2] && op->p[3] && op->p[4], "eval_depth_ls: null pointer");
-      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4]) % 8 == 0, "eval_depth_ls: out / scratch not 8-byte aligned");
+      MG_REQUIRE(OW == 0 || inv_factor >= 1.0f, "eval_depth_ls: inverse factor %g must be >= 1", (double)inv_factor);
+      MG_REQUIRE(pred && gt && mask && out && scratch, "eval_depth_ls: null pointer");
+      MG_REQUIRE(((uintptr_t)out | (uintptr_t)scratch) % 8 == 0, "eval_depth_ls: out / scratch not 8-byte aligned");
       const int nblk = grid_for((long long)H * (OW > 0 ? OW : W));
-      MG_LAUNCH(depth_ls_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const float*)op->p[0], (const float*)op->p[1],
-                (const uint8_t*)op->p[2], (double*)op->p[4], H, W, OW, op->f[0], op->i[2] != 0);
-      MG_LAUNCH(sum_rows_kernel, dim3(1), dim3(64), 0, s, (const double*)op->p[4], (double*)op->p[3], nblk, LS_N);
+      MG_LAUNCH(depth_ls_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, mask, scratch, H, W, OW, inv_factor,
+                op->i[MG_EVAL_DEPTH_LS_I_DISPARITY] != 0);
+      MG_LAUNCH(sum_rows_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, out, nblk, LS_N);
       break;
     }
     case MG_OP_EVAL_DEPTH_METRICS: {
-      const int H = op->i[0], W = op->i[1];
+      const int H = op->i[MG_EVAL_DEPTH_METRICS_I_H], W = op->i[MG_EVAL_DEPTH_METRICS_I_W];
+      const float *pred = (const float*)op->p[MG_EVAL_DEPTH_METRICS_P_PRED], *gt = (const float*)op->p[MG_EVAL_DEPTH_METRICS_P_GT];
+      const uint8_t* mask = (const uint8_t*)op->p[MG_EVAL_DEPTH_METRICS_P_MASK];
+      const double* sums = (const double*)op->p[MG_EVAL_DEPTH_METRICS_P_SUMS];
+      double *out = (double*)op->p[MG_EVAL_DEPTH_METRICS_P_OUT], *scratch = (double*)op->p[MG_EVAL_DEPTH_METRICS_P_SCRATCH];
       MG_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31), "eval_depth_metrics: bad size %d x %d", H, W);
-      MG_REQUIRE(op->p[0] && op->p[1] && op->p[2] && op->p[4] && op->p[5], "eval_depth_metrics: null pointer");
-      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4] | (uintptr_t)op->p[5]) % 8 == 0,
+      MG_REQUIRE(pred && gt && mask && out && scratch, "eval_depth_metrics: null pointer");
+      MG_REQUIRE(((uintptr_t)sums | (uintptr_t)out | (uintptr_t)scratch) % 8 == 0,
                  "eval_depth_metrics: sums / out / scratch not 8-byte aligned");
       const int nblk = grid_for((long long)H * W);
-      MG_LAUNCH(depth_metrics_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const float*)op->p[0], (const float*)op->p[1],
-                (const uint8_t*)op->p[2], (const double*)op->p[3], (double*)op->p[5], H * W, op->i[2] != 0, op->i[3] != 0,
-                op->i[4] != 0, op->f[0], op->f[1]);
-      MG_LAUNCH(depth_metrics_final_kernel, dim3(1), dim3(64), 0, s, (const double*)op->p[5], (const double*)op->p[3],
-                (double*)op->p[4], nblk);
+      MG_LAUNCH(depth_metrics_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, mask, sums, scratch, H * W,
+                op->i[MG_EVAL_DEPTH_METRICS_I_DISPARITY] != 0, op->i[MG_EVAL_DEPTH_METRICS_I_CLIP_MIN] != 0,
+                op->i[MG_EVAL_DEPTH_METRICS_I_CLIP_MAX] != 0, op->f[MG_EVAL_DEPTH_METRICS_F_MIN_DEPTH], op->f[MG_EVAL_DEPTH_METRICS_F_MAX_DEPTH]);
+      MG_LAUNCH(depth_metrics_final_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, sums, out, nblk);
       break;
     }
     case MG_OP_EVAL_NORMALS: {
-      const long long HW = op->l[0];
+      const long long HW = op->l[MG_EVAL_NORMALS_L_HW];
       MG_REQUIRE(HW >= 0, "eval_normals: HW %lld < 0", HW);
-      MG_REQUIRE(op->p[2] && op->p[4] && (HW == 0 || (op->p[0] && op->p[1])), "eval_normals: null pointer");
-      MG_REQUIRE(((uintptr_t)op->p[2] | (uintptr_t)op->p[4]) % 8 == 0, "eval_normals: out / workspace not 8-byte aligned");
-      char* const ws = (char*)op->p[4];
-      const float *pred = (const float*)op->p[0], *gt = (const float*)op->p[1];
-      float* const err = (float*)op->p[3];
-      double* const out = (double*)op->p[2];
+      char* const ws = (char*)op->p[MG_EVAL_NORMALS_P_WS];
+      const float *pred = (const float*)op->p[MG_EVAL_NORMALS_P_PRED], *gt = (const float*)op->p[MG_EVAL_NORMALS_P_GT];
+      float* const err = (float*)op->p[MG_EVAL_NORMALS_P_ERR];
+      double* const out = (double*)op->p[MG_EVAL_NORMALS_P_OUT];
+      MG_REQUIRE(out && ws && (HW == 0 || (pred && gt)), "eval_normals: null pointer");
+      MG_REQUIRE(((uintptr_t)out | (uintptr_t)ws) % 8 == 0, "eval_normals: out / workspace not 8-byte aligned");
       SelState* const st = (SelState*)(ws + WS_NM_STATE);
       unsigned *h0 = (unsigned*)(ws + WS_NM_HIST0), *h1 = (unsigned*)(ws + WS_NM_HIST1), *h2 = (unsigned*)(ws + WS_NM_HIST2);
-      const int masked = op->i[0] != 0, nblk = grid_for(HW);
+      const int masked = op->i[MG_EVAL_NORMALS_I_MASKED] != 0, nblk = grid_for(HW);
       const NormalsAngles angles{pred, gt, err, HW, masked};
       if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(ws + WS_NM_STATE, 0, WS_NORMALS_END - WS_NM_STATE, s));
       MG_LAUNCH(normals_stats_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, pred, gt, err, (double*)(ws + WS_NM_PART), h0, HW, masked);
@@ -695,19 +710,22 @@ int mg_launch_evalscore(const mg_op* op, hipStream_t s) {
     case MG_OP_IIDSCORE_PSNR:
     case MG_OP_IIDSCORE_SSIM: {
       const char* const name = op->kind == MG_OP_IIDSCORE_PREP ? "iidscore_prep" : op->kind == MG_OP_IIDSCORE_PSNR ? "iidscore_psnr" : "iidscore_ssim";
-      const int H = op->i[0], W = op->i[1], gamma = op->i[2], mapped = op->i[3] != 0;
+      // (the three kinds share their slots: read by PSNR's names, which hold every field of the other two)
+      const int H = op->i[MG_IIDSCORE_PSNR_I_H], W = op->i[MG_IIDSCORE_PSNR_I_W], gamma = op->i[MG_IIDSCORE_PSNR_I_GAMMA];
+      const int mapped = op->i[MG_IIDSCORE_PSNR_I_UP_TO_SCALE] != 0;
+      const float *pred = (const float*)op->p[MG_IIDSCORE_PSNR_P_PRED], *gt = (const float*)op->p[MG_IIDSCORE_PSNR_P_GT];
+      char* const ws = (char*)op->p[MG_IIDSCORE_PSNR_P_WS];
+      double* const out = (double*)op->p[MG_IIDSCORE_PSNR_P_OUT];
       MG_REQUIRE(H >= 1 && W >= 1 && 3ll * H * W < (1ll << 31), "%s: bad size %d x %d", name, H, W);
       MG_REQUIRE(op->kind != MG_OP_IIDSCORE_SSIM || (H >= SS_K && W >= SS_K),
                  "%s: H, W >= %d required (an 11 x 11 window, reflect padding by 5 and a non-empty crop), got %d x %d", name, SS_K, H, W);
       MG_REQUIRE(gamma >= MG_IID_GAMMA_NONE && gamma <= MG_IID_GAMMA_BOTH, "%s: unknown gamma mode %d", name, gamma);
-      MG_REQUIRE(op->p[0] && op->p[1] && op->p[3] && op->p[4], "%s: null pointer", name);
-      MG_REQUIRE(((uintptr_t)op->p[0] | (uintptr_t)op->p[1]) % 4 == 0, "%s: pred / gt not 4-byte aligned", name);
-      MG_REQUIRE(((uintptr_t)op->p[3] | (uintptr_t)op->p[4]) % 8 == 0, "%s: out / workspace not 8-byte aligned", name);
-      char* const ws = (char*)op->p[4];
-      double* const out = (double*)op->p[3];
+      MG_REQUIRE(pred && gt && out && ws, "%s: null pointer", name);
+      MG_REQUIRE(((uintptr_t)pred | (uintptr_t)gt) % 4 == 0, "%s: pred / gt not 4-byte aligned", name);
+      MG_REQUIRE(((uintptr_t)out | (uintptr_t)ws) % 8 == 0, "%s: out / workspace not 8-byte aligned", name);
       const long long HW = (long long)H * W;
       IidMap* const map = (IidMap*)(ws + WS_II_MAP);
-      const IidImages im{(const float*)op->p[0], (const float*)op->p[1], (const uint8_t*)op->p[2],
+      const IidImages im{pred, gt, (const uint8_t*)op->p[MG_IIDSCORE_PSNR_P_MASK],
                          op->kind != MG_OP_IIDSCORE_PREP && mapped ? map : nullptr, gamma};
       if (op->kind == MG_OP_IIDSCORE_PREP) {
         const IidBrightness br{im.gt, im.mask, HW, gamma};
@@ -725,7 +743,7 @@ int mg_launch_evalscore(const mg_op* op, hipStream_t s) {
         const int nblk = grid_for(3 * HW);
         MG_LAUNCH(iid_psnr_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, im, (double*)(ws + WS_II_PSNR_PART), 3 * HW);
         MG_LAUNCH(iid_psnr_final_kernel, dim3(1), dim3(64), 0, s, (const double*)(ws + WS_II_PSNR_PART), out, nblk, mapped,
-                  op->i[4] != 0);
+                  op->i[MG_IIDSCORE_PSNR_I_WRITE_PSNR] != 0);
       } else {
         const int OH = H - 2 * SS_R, OW = W - 2 * SS_R;
         const int nty = (OH + SS_T - 1) / SS_T, ntx = (OW + SS_T - 1) / SS_T;
@@ -761,15 +779,21 @@ int mg_eval_depth(const float* pred, const float* gt, const uint8_t* mask, int H
   if (alignment != MG_EVAL_ALIGN_NONE) {
     memset(&op, 0, sizeof(op));
     op.kind = MG_OP_EVAL_DEPTH_LS;
-    op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask; op.p[3] = ws + WS_LS_SUMS; op.p[4] = ws + WS_LS_PART;
-    op.i[0] = H; op.i[1] = W; op.i[2] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
+    op.p[MG_EVAL_DEPTH_LS_P_PRED] = (void*)pred;
+    op.p[MG_EVAL_DEPTH_LS_P_GT] = (void*)gt;
+    op.p[MG_EVAL_DEPTH_LS_P_MASK] = (void*)mask;
+    op.p[MG_EVAL_DEPTH_LS_P_OUT] = ws + WS_LS_SUMS;
+    op.p[MG_EVAL_DEPTH_LS_P_SCRATCH] = ws + WS_LS_PART;
+    op.i[MG_EVAL_DEPTH_LS_I_H] = H;
+    op.i[MG_EVAL_DEPTH_LS_I_W] = W;
+    op.i[MG_EVAL_DEPTH_LS_I_DISPARITY] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
     if (align_max_res > 0 && H >= 1 && W >= 1) {   // align_depth_least_square: factor = min(max_res / (H, W)), applied when < 1
       const double fh = (double)align_max_res / (double)H, fw = (double)align_max_res / (double)W;
       const double factor = fh < fw ? fh : fw;
       if (factor < 1.0) {
-        op.i[3] = (int)floor((double)W * factor);
-        op.f[0] = (float)(1.0 / factor);
-        MG_REQUIRE(op.i[3] >= 1, "mg_eval_depth: alignment_max_res %d leaves no column of a %d x %d map", align_max_res, H, W);
+        op.i[MG_EVAL_DEPTH_LS_I_FIT_W] = (int)floor((double)W * factor);
+        op.f[MG_EVAL_DEPTH_LS_F_INV_FACTOR] = (float)(1.0 / factor);
+        MG_REQUIRE(op.i[MG_EVAL_DEPTH_LS_I_FIT_W] >= 1, "mg_eval_depth: alignment_max_res %d leaves no column of a %d x %d map", align_max_res, H, W);
       }
     }
     const int rc = mg_launch_evalscore(&op, (hipStream_t)stream);
@@ -777,13 +801,20 @@ int mg_eval_depth(const float* pred, const float* gt, const uint8_t* mask, int H
   }
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_EVAL_DEPTH_METRICS;
-  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask;
-  op.p[3] = alignment != MG_EVAL_ALIGN_NONE ? ws + WS_LS_SUMS : nullptr;
-  op.p[4] = out13; op.p[5] = ws + WS_DM_PART;
-  op.i[0] = H; op.i[1] = W; op.i[2] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
-  op.i[3] = min_depth == min_depth; op.i[4] = max_depth == max_depth;
-  op.f[0] = op.i[3] ? (float)min_depth : 0.f;
-  op.f[1] = op.i[4] ? (float)max_depth : 0.f;
+  const bool clip_min = min_depth == min_depth, clip_max = max_depth == max_depth;   // (NaN = no limit)
+  op.p[MG_EVAL_DEPTH_METRICS_P_PRED] = (void*)pred;
+  op.p[MG_EVAL_DEPTH_METRICS_P_GT] = (void*)gt;
+  op.p[MG_EVAL_DEPTH_METRICS_P_MASK] = (void*)mask;
+  op.p[MG_EVAL_DEPTH_METRICS_P_SUMS] = alignment != MG_EVAL_ALIGN_NONE ? ws + WS_LS_SUMS : nullptr;
+  op.p[MG_EVAL_DEPTH_METRICS_P_OUT] = out13;
+  op.p[MG_EVAL_DEPTH_METRICS_P_SCRATCH] = ws + WS_DM_PART;
+  op.i[MG_EVAL_DEPTH_METRICS_I_H] = H;
+  op.i[MG_EVAL_DEPTH_METRICS_I_W] = W;
+  op.i[MG_EVAL_DEPTH_METRICS_I_DISPARITY] = alignment == MG_EVAL_ALIGN_LS_DISPARITY;
+  op.i[MG_EVAL_DEPTH_METRICS_I_CLIP_MIN] = clip_min;
+  op.i[MG_EVAL_DEPTH_METRICS_I_CLIP_MAX] = clip_max;
+  op.f[MG_EVAL_DEPTH_METRICS_F_MIN_DEPTH] = clip_min ? (float)min_depth : 0.f;
+  op.f[MG_EVAL_DEPTH_METRICS_F_MAX_DEPTH] = clip_max ? (float)max_depth : 0.f;
   return mg_launch_evalscore(&op, (hipStream_t)stream);
 }
 
@@ -792,9 +823,13 @@ int mg_eval_normals(const float* pred, const float* gt, int64_t HW, int masked, 
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_EVAL_NORMALS;
-  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = out9; op.p[3] = err_map_or_null; op.p[4] = workspace;
-  op.i[0] = masked;
-  op.l[0] = HW;
+  op.p[MG_EVAL_NORMALS_P_PRED] = (void*)pred;
+  op.p[MG_EVAL_NORMALS_P_GT] = (void*)gt;
+  op.p[MG_EVAL_NORMALS_P_OUT] = out9;
+  op.p[MG_EVAL_NORMALS_P_ERR] = err_map_or_null;
+  op.p[MG_EVAL_NORMALS_P_WS] = workspace;
+  op.i[MG_EVAL_NORMALS_I_MASKED] = masked;
+  op.l[MG_EVAL_NORMALS_L_HW] = HW;
   return mg_launch_evalscore(&op, (hipStream_t)stream);
 }
 
@@ -808,15 +843,23 @@ int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null,
   if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(out8, 0xff, 8 * sizeof(double), (hipStream_t)stream));   // every slot NaN until an op fills it
   mg_op op;
   memset(&op, 0, sizeof(op));
-  op.p[0] = (void*)pred; op.p[1] = (void*)gt; op.p[2] = (void*)mask_or_null; op.p[3] = out8; op.p[4] = workspace;
-  op.i[0] = H; op.i[1] = W; op.i[2] = gamma_mode; op.i[3] = up_to_scale != 0;
+  // one op, launched as each kind in turn: the three share their slots (PSNR's names hold every field of the other two)
+  op.p[MG_IIDSCORE_PSNR_P_PRED] = (void*)pred;
+  op.p[MG_IIDSCORE_PSNR_P_GT] = (void*)gt;
+  op.p[MG_IIDSCORE_PSNR_P_MASK] = (void*)mask_or_null;
+  op.p[MG_IIDSCORE_PSNR_P_OUT] = out8;
+  op.p[MG_IIDSCORE_PSNR_P_WS] = workspace;
+  op.i[MG_IIDSCORE_PSNR_I_H] = H;
+  op.i[MG_IIDSCORE_PSNR_I_W] = W;
+  op.i[MG_IIDSCORE_PSNR_I_GAMMA] = gamma_mode;
+  op.i[MG_IIDSCORE_PSNR_I_UP_TO_SCALE] = up_to_scale != 0;
   int rc = 0;
   if (up_to_scale) {
     op.kind = MG_OP_IIDSCORE_PREP;
     if ((rc = mg_launch_evalscore(&op, (hipStream_t)stream))) return rc;
   }
   op.kind = MG_OP_IIDSCORE_PSNR;   // always: it counts the valid elements
-  op.i[4] = (metrics_mask & MG_IID_PSNR) != 0;
+  op.i[MG_IIDSCORE_PSNR_I_WRITE_PSNR] = (metrics_mask & MG_IID_PSNR) != 0;
   if ((rc = mg_launch_evalscore(&op, (hipStream_t)stream))) return rc;
   if (metrics_mask & MG_IID_SSIM) {
     op.kind = MG_OP_IIDSCORE_SSIM;

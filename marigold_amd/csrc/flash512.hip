@@ -226,14 +226,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 int mg_launch_flash512(const mg_op* op, hipStream_t s) {
   Fa5Args a;
-  a.Q = (const bf16_t*)op->p[0];
-  a.K = (const bf16_t*)op->p[1];
-  a.Vt = (const bf16_t*)op->p[2];
-  a.O = (bf16_t*)op->p[3];
+  a.Q = (const bf16_t*)op->p[MG_FLASH_ATTN512_P_Q];
+  a.K = (const bf16_t*)op->p[MG_FLASH_ATTN512_P_K];
+  a.Vt = (const bf16_t*)op->p[MG_FLASH_ATTN512_P_VT];
+  a.O = (bf16_t*)op->p[MG_FLASH_ATTN512_P_O];
   a.zero = g_zero_page;
-  a.B = op->i[0]; a.Ntok = op->i[1]; a.ldq = op->i[2]; a.ldo = op->i[3]; a.ldvt = op->i[4];
-  a.sQ = op->l[0]; a.sK = op->l[1]; a.sVt = op->l[2]; a.sO = op->l[3];
-  a.scale_log2 = op->f[0] * 1.4426950408889634f;
+  a.B = op->i[MG_FLASH_ATTN512_I_B];
+  a.Ntok = op->i[MG_FLASH_ATTN512_I_NTOK];
+  a.ldq = op->i[MG_FLASH_ATTN512_I_LDQ];
+  a.ldo = op->i[MG_FLASH_ATTN512_I_LDO];
+  a.ldvt = op->i[MG_FLASH_ATTN512_I_LDVT];
+  a.sQ = op->l[MG_FLASH_ATTN512_L_SQ];
+  a.sK = op->l[MG_FLASH_ATTN512_L_SK];
+  a.sVt = op->l[MG_FLASH_ATTN512_L_SVT];
+  a.sO = op->l[MG_FLASH_ATTN512_L_SO];
+  a.scale_log2 = op->f[MG_FLASH_ATTN512_F_SCALE] * 1.4426950408889634f;
   MG_REQUIRE(g_zero_page || g_dry_run, "flash_attn512: mg_init() not called");
   MG_REQUIRE(a.Q && a.K && a.Vt && a.O && a.B > 0 && a.Ntok > 0, "flash_attn512: null pointer / empty problem");
   MG_REQUIRE(a.ldq % 8 == 0 && a.ldo % 8 == 0 && a.ldvt % 8 == 0 && a.ldq >= FA5_D && a.ldo >= FA5_D &&

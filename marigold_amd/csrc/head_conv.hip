@@ -170,15 +170,15 @@ int launch_head(const HeadArgs& a0, hipStream_t s) {
 
 int mg_launch_head_conv(const mg_op* op, hipStream_t s) {
   HeadArgs a;
-  a.x = (const bf16_t*)op->p[0];
-  a.ss = (const float*)op->p[1];
-  a.w = (const bf16_t*)op->p[2];
-  a.bias = (const float*)op->p[3];
-  a.out = (float*)op->p[4];
-  a.B = op->i[0]; a.H = op->i[1]; a.W = op->i[2]; a.C = op->i[3];
-  const int cout = op->i[4];
-  a.ldo = op->i[5] > 0 ? op->i[5] : cout;
-  a.silu = op->i[6];
+  a.x = (const bf16_t*)op->p[MG_CONV3X3_HEAD_P_X];
+  a.ss = (const float*)op->p[MG_CONV3X3_HEAD_P_SS];
+  a.w = (const bf16_t*)op->p[MG_CONV3X3_HEAD_P_WT];
+  a.bias = (const float*)op->p[MG_CONV3X3_HEAD_P_BIAS];
+  a.out = (float*)op->p[MG_CONV3X3_HEAD_P_OUT];
+  a.B = op->i[MG_CONV3X3_HEAD_I_B]; a.H = op->i[MG_CONV3X3_HEAD_I_H]; a.W = op->i[MG_CONV3X3_HEAD_I_W]; a.C = op->i[MG_CONV3X3_HEAD_I_C];
+  const int cout = op->i[MG_CONV3X3_HEAD_I_COUT];
+  a.ldo = op->i[MG_CONV3X3_HEAD_I_LDO] > 0 ? op->i[MG_CONV3X3_HEAD_I_LDO] : cout;
+  a.silu = op->i[MG_CONV3X3_HEAD_I_SILU];
   a.tiles_x = a.tiles_y = 0;
   MG_REQUIRE(a.x && a.w && a.out && a.B > 0 && a.H > 0 && a.W > 0, "conv3x3_head: bad arguments");
   // the activation is applied where the norm is (the staging pass): a SiLU without scale / shift is not a form this kernel has

@@ -200,48 +200,53 @@ __global__ __launch_bounds__(256) void post_nchw_kernel(const float* __restrict_
 int mg_launch_misc(const mg_op* op, hipStream_t s) {
   switch (op->kind) {
     case MG_OP_SCHED_STEP: {
-      const long long n = op->l[0];
+      const long long n = op->l[MG_SCHED_STEP_L_N];
       const int grid = (int)min((n + 255) / 256, (long long)4096);
-      MG_LAUNCH(sched_step_kernel, dim3(grid), dim3(256), 0, s, (const float*)op->p[0],
-                         (const float*)op->p[1], (const float*)op->p[2], (float*)op->p[3], n,
-                         op->f[0], op->f[1], op->f[2]);
+      MG_LAUNCH(sched_step_kernel, dim3(grid), dim3(256), 0, s, (const float*)op->p[MG_SCHED_STEP_P_X],
+                (const float*)op->p[MG_SCHED_STEP_P_MODEL_OUT], (const float*)op->p[MG_SCHED_STEP_P_NOISE],
+                (float*)op->p[MG_SCHED_STEP_P_OUT], n, op->f[MG_SCHED_STEP_F_CX], op->f[MG_SCHED_STEP_F_CM], op->f[MG_SCHED_STEP_F_CN]);
       break;
     }
     case MG_OP_LINEAR_SMALL_M: {
-      const int M = op->i[0], N = op->i[1], K = op->i[2];
+      const int M = op->i[MG_LINEAR_SMALL_M_I_M], N = op->i[MG_LINEAR_SMALL_M_I_N], K = op->i[MG_LINEAR_SMALL_M_I_K];
+      const int ldo = op->i[MG_LINEAR_SMALL_M_I_LDO] > 0 ? op->i[MG_LINEAR_SMALL_M_I_LDO] : N;
       MG_REQUIRE(M > 0 && M < 65536 && N > 0 && K > 0, "linear_small_m: bad dims");
       MG_LAUNCH(linear_small_m_kernel, dim3((N + 3) / 4, (M + LSM_ROWS - 1) / LSM_ROWS), dim3(256), 0, s,
-                         (const float*)op->p[0], (const float*)op->p[1], (const float*)op->p[2],
-                         (float*)op->p[3], M, N, K, op->i[3], op->i[4], op->i[5] > 0 ? op->i[5] : N);
+                (const float*)op->p[MG_LINEAR_SMALL_M_P_X], (const float*)op->p[MG_LINEAR_SMALL_M_P_W],
+                (const float*)op->p[MG_LINEAR_SMALL_M_P_BIAS], (float*)op->p[MG_LINEAR_SMALL_M_P_OUT], M, N, K,
+                op->i[MG_LINEAR_SMALL_M_I_ACT_IN], op->i[MG_LINEAR_SMALL_M_I_ACT_OUT], ldo);
       break;
     }
     case MG_OP_LATENT_1X1: {
-      const int B = op->i[0], Ci = op->i[1], Co = op->i[2];
-      const long long HW = op->i[3];
+      const int B = op->i[MG_LATENT_1X1_I_B], Ci = op->i[MG_LATENT_1X1_I_CI], Co = op->i[MG_LATENT_1X1_I_CO];
+      const long long HW = op->i[MG_LATENT_1X1_I_HW];
+      const float scale = op->f[MG_LATENT_1X1_F_SCALE] == 0.f ? 1.f : op->f[MG_LATENT_1X1_F_SCALE];
       const long long total = (long long)B * HW;
       const int grid = (int)min((total + 255) / 256, (long long)4096);
-      MG_LAUNCH(latent_1x1_kernel, dim3(grid), dim3(256), 0, s, (const float*)op->p[0],
-                         (const float*)op->p[1], (const float*)op->p[2], (float*)op->p[3], B, Ci, Co,
-                         HW, op->f[0] == 0.f ? 1.f : op->f[0]);
+      MG_LAUNCH(latent_1x1_kernel, dim3(grid), dim3(256), 0, s, (const float*)op->p[MG_LATENT_1X1_P_X],
+                (const float*)op->p[MG_LATENT_1X1_P_W], (const float*)op->p[MG_LATENT_1X1_P_BIAS], (float*)op->p[MG_LATENT_1X1_P_OUT],
+                B, Ci, Co, HW, scale);
       break;
     }
     case MG_OP_IM2COL_SMALL: {
-      const int B = op->i[0], H = op->i[1], W = op->i[2], C0 = op->i[3], C1 = op->i[4], Kp = op->i[5];
+      const int B = op->i[MG_IM2COL_SMALL_I_B], H = op->i[MG_IM2COL_SMALL_I_H], W = op->i[MG_IM2COL_SMALL_I_W];
+      const int C0 = op->i[MG_IM2COL_SMALL_I_C0], C1 = op->i[MG_IM2COL_SMALL_I_C1], Kp = op->i[MG_IM2COL_SMALL_I_KP];
+      const float *src0 = (const float*)op->p[MG_IM2COL_SMALL_P_SRC0], *src1 = (const float*)op->p[MG_IM2COL_SMALL_P_SRC1];
+      bf16_t* out = (bf16_t*)op->p[MG_IM2COL_SMALL_P_OUT];
       const int cin = C0 + C1;
-      MG_REQUIRE(C1 == 0 || op->p[1], "im2col_small: src1 missing");
-      // src0 rows: i[7] = members per src0 row (b reads row b / i[7]); 0 = the legacy form, i[6] = 1 broadcasts row 0
-      const int bcast0 = op->i[6], per0 = op->i[7];
+      MG_REQUIRE(C1 == 0 || src1, "im2col_small: src1 missing");
+      // src0 rows: per0 members per src0 row (b reads row b / per0); 0 = the legacy form, bcast0 = 1 broadcasts row 0
+      const int bcast0 = op->i[MG_IM2COL_SMALL_I_SRC0_BROADCAST], per0 = op->i[MG_IM2COL_SMALL_I_MEMBERS_PER_SRC0];
       MG_REQUIRE(per0 >= 0, "im2col_small: members per src0 row %d < 0", per0);
       MG_REQUIRE(per0 == 0 || bcast0 == 0, "im2col_small: src0 broadcast and members per src0 row %d both set", per0);
       MG_REQUIRE(per0 == 0 || B % per0 == 0, "im2col_small: B %d not a multiple of the members per src0 row %d", B, per0);
       const int div0 = per0 ? per0 : (bcast0 ? 0 : 1);
       const long long npix = (long long)B * H * W;
       const dim3 grid((unsigned)((npix + 255) / 256));
-#define I2C_CASE(N, K)                                                                             \
-  if (cin == N && Kp == K) {                                                                       \
-    MG_LAUNCH((im2col_small_kernel<N, K>), grid, dim3(256), 0, s, (const float*)op->p[0],         \
-              (const float*)op->p[1], (bf16_t*)op->p[2], B, H, W, C0, div0);                       \
-    break;                                                                                         \
+#define I2C_CASE(N, K)                                                                                       \
+  if (cin == N && Kp == K) {                                                                                 \
+    MG_LAUNCH((im2col_small_kernel<N, K>), grid, dim3(256), 0, s, src0, src1, out, B, H, W, C0, div0);       \
+    break;                                                                                                   \
   }
       I2C_CASE(3, 64) I2C_CASE(4, 64) I2C_CASE(8, 128) I2C_CASE(12, 128) I2C_CASE(16, 192)
 #undef I2C_CASE
@@ -249,27 +254,32 @@ int mg_launch_misc(const mg_op* op, hipStream_t s) {
       break;
     }
     case MG_OP_POST_NCHW: {
-      const long long B = op->i[0], HW = op->i[1];
-      const int Cout = op->i[2], ldi = op->i[3], post = op->i[4];
+      const long long B = op->i[MG_POST_NCHW_I_B], HW = op->i[MG_POST_NCHW_I_HW];
+      const int Cout = op->i[MG_POST_NCHW_I_COUT], ldi = op->i[MG_POST_NCHW_I_LDI], post = op->i[MG_POST_NCHW_I_POST];
+      const float* x = (const float*)op->p[MG_POST_NCHW_P_X];
+      float* out = (float*)op->p[MG_POST_NCHW_P_OUT];
+      const float* noise = (const float*)op->p[MG_POST_NCHW_P_NOISE];
+      const float cx = op->f[MG_POST_NCHW_F_CX], cm = op->f[MG_POST_NCHW_F_CM], cn = op->f[MG_POST_NCHW_F_CN];
       MG_REQUIRE(ldi % 4 == 0 && ldi >= Cout, "post_nchw: ldi %d must be a multiple of 4 >= Cout", ldi);
       const long long npix = B * HW;
       const int grid = (int)min((npix + 255) / 256, (long long)8192);
-      const float sc = op->f[0] == 0.f ? 1.f : op->f[0];
+      const float sc = op->f[MG_POST_NCHW_F_SCALE] == 0.f ? 1.f : op->f[MG_POST_NCHW_F_SCALE];
       switch (Cout) {
-        case 1: MG_LAUNCH(post_nchw_kernel<1>, dim3(grid), dim3(256), 0, s, (const float*)op->p[0], (float*)op->p[1], npix, HW, ldi, post, sc, (const float*)op->p[2], op->f[1], op->f[2], op->f[3]); break;
-        case 3: MG_LAUNCH(post_nchw_kernel<3>, dim3(grid), dim3(256), 0, s, (const float*)op->p[0], (float*)op->p[1], npix, HW, ldi, post, sc, (const float*)op->p[2], op->f[1], op->f[2], op->f[3]); break;
-        case 4: MG_LAUNCH(post_nchw_kernel<4>, dim3(grid), dim3(256), 0, s, (const float*)op->p[0], (float*)op->p[1], npix, HW, ldi, post, sc, (const float*)op->p[2], op->f[1], op->f[2], op->f[3]); break;
-        case 8: MG_LAUNCH(post_nchw_kernel<8>, dim3(grid), dim3(256), 0, s, (const float*)op->p[0], (float*)op->p[1], npix, HW, ldi, post, sc, (const float*)op->p[2], op->f[1], op->f[2], op->f[3]); break;
-        case 12: MG_LAUNCH(post_nchw_kernel<12>, dim3(grid), dim3(256), 0, s, (const float*)op->p[0], (float*)op->p[1], npix, HW, ldi, post, sc, (const float*)op->p[2], op->f[1], op->f[2], op->f[3]); break;
+        case 1: MG_LAUNCH(post_nchw_kernel<1>, dim3(grid), dim3(256), 0, s, x, out, npix, HW, ldi, post, sc, noise, cx, cm, cn); break;
+        case 3: MG_LAUNCH(post_nchw_kernel<3>, dim3(grid), dim3(256), 0, s, x, out, npix, HW, ldi, post, sc, noise, cx, cm, cn); break;
+        case 4: MG_LAUNCH(post_nchw_kernel<4>, dim3(grid), dim3(256), 0, s, x, out, npix, HW, ldi, post, sc, noise, cx, cm, cn); break;
+        case 8: MG_LAUNCH(post_nchw_kernel<8>, dim3(grid), dim3(256), 0, s, x, out, npix, HW, ldi, post, sc, noise, cx, cm, cn); break;
+        case 12: MG_LAUNCH(post_nchw_kernel<12>, dim3(grid), dim3(256), 0, s, x, out, npix, HW, ldi, post, sc, noise, cx, cm, cn); break;
         default: MG_REQUIRE(false, "post_nchw: unsupported Cout %d (1, 3, 4, 8 or 12)", Cout);
       }
       break;
     }
     case MG_OP_MEMSET:
-      if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(op->p[0], op->i[0], (size_t)op->l[0], s));
+      if (!g_dry_run) MG_CHECK_HIP(hipMemsetAsync(op->p[MG_MEMSET_P_DST], op->i[MG_MEMSET_I_VALUE], (size_t)op->l[MG_MEMSET_L_BYTES], s));
       break;
     case MG_OP_COPY:
-      if (!g_dry_run) MG_CHECK_HIP(hipMemcpyAsync(op->p[1], op->p[0], (size_t)op->l[0], hipMemcpyDeviceToDevice, s));
+      if (!g_dry_run)
+        MG_CHECK_HIP(hipMemcpyAsync(op->p[MG_COPY_P_DST], op->p[MG_COPY_P_SRC], (size_t)op->l[MG_COPY_L_BYTES], hipMemcpyDeviceToDevice, s));
       break;
     default: MG_REQUIRE(false, "misc: bad op kind %d", op->kind);
   }

@@ -297,9 +297,16 @@ mg_op make_median_op(const float* d, const float* st, float* med, float* mad, fl
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_ENS_DEPTH_MEDIAN;
-  op.i[0] = E; op.i[1] = reduction; op.i[2] = has_shift;
-  op.p[0] = (void*)d; op.p[1] = (void*)st; op.p[2] = med; op.p[3] = mad; op.p[4] = mm; op.p[5] = scratch;
-  op.l[0] = HW;
+  op.i[MG_ENS_DEPTH_MEDIAN_I_E] = E;
+  op.i[MG_ENS_DEPTH_MEDIAN_I_REDUCTION] = reduction;
+  op.i[MG_ENS_DEPTH_MEDIAN_I_HAS_SHIFT] = has_shift;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_D] = (void*)d;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_ST] = (void*)st;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_MED] = med;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_MAD] = mad;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_MINMAX] = mm;
+  op.p[MG_ENS_DEPTH_MEDIAN_P_SCRATCH] = scratch;
+  op.l[MG_ENS_DEPTH_MEDIAN_L_HW] = HW;
   return op;
 }
 }  // namespace
@@ -330,12 +337,7 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
       Ha = (int)(H * f);
       Wa = (int)(W * f);
       MG_CHECK_HIP(hipMalloc(&small.p, sizeof(float) * (size_t)E * Ha * Wa));
-      mg_op r;
-      memset(&r, 0, sizeof(r));
-      r.kind = MG_OP_RESIZE;
-      r.i[0] = E; r.i[1] = H; r.i[2] = W; r.i[3] = Ha; r.i[4] = Wa; r.i[5] = 2; r.i[6] = 0;
-      r.p[0] = (void*)preds; r.p[1] = small.p;
-      if (int rc = mg_launch(&r, stream)) return rc;
+      if (int rc = mg_resize(preds, small.p, nullptr, E, H, W, Ha, Wa, /* nearest-exact */ 2, /* fp32 */ 0, stream)) return rc;
       d_align = (const float*)small.p;
     }
     const long long HWa = (long long)Ha * Wa;
@@ -345,9 +347,11 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
     mg_op so;
     memset(&so, 0, sizeof(so));
     so.kind = MG_OP_ENS_DEPTH_STATS;
-    so.i[0] = E;
-    so.p[0] = (void*)d_align; so.p[1] = sscratch.p; so.p[2] = stats.p;
-    so.l[0] = HWa;
+    so.i[MG_ENS_DEPTH_STATS_I_E] = E;
+    so.p[MG_ENS_DEPTH_STATS_P_D] = (void*)d_align;
+    so.p[MG_ENS_DEPTH_STATS_P_SCRATCH] = sscratch.p;
+    so.p[MG_ENS_DEPTH_STATS_P_OUT] = stats.p;
+    so.l[MG_ENS_DEPTH_STATS_L_HW] = HWa;
     if (int rc = mg_launch(&so, stream)) return rc;
     std::vector<double> hs(3 * (size_t)E + (size_t)E * E);
     MG_CHECK_HIP(hipMemcpyAsync(hs.data(), stats.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, s));
@@ -397,9 +401,11 @@ extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int sc
   mg_op no;
   memset(&no, 0, sizeof(no));
   no.kind = MG_OP_ENS_DEPTH_NORM;
-  no.i[0] = affine;
-  no.p[0] = depth_out; no.p[1] = unc_out; no.p[2] = mm_dev.p;
-  no.l[0] = HW;
+  no.i[MG_ENS_DEPTH_NORM_I_SHIFT_INVARIANT] = affine;
+  no.p[MG_ENS_DEPTH_NORM_P_MED] = depth_out;
+  no.p[MG_ENS_DEPTH_NORM_P_MAD] = unc_out;
+  no.p[MG_ENS_DEPTH_NORM_P_MINMAX] = mm_dev.p;
+  no.l[MG_ENS_DEPTH_NORM_L_HW] = HW;
   if (int rc = mg_launch(&no, stream)) return rc;
   MG_CHECK_HIP(hipStreamSynchronize(s));   // the temporaries above are freed on return
   if (info4) { info4[0] = fval; info4[1] = nfev; info4[2] = nit; info4[3] = status; }
@@ -489,13 +495,7 @@ extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hi
     return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
                              o.max_res, pred_out, unc_out_or_null, info4_or_null, stream);
   MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
-  mg_op en;
-  memset(&en, 0, sizeof(en));
-  en.kind = MG_OP_ENS_NORMALS;
-  en.p[0] = (void*)preds; en.p[1] = pred_out; en.p[2] = unc_out_or_null;
-  en.i[0] = B; en.i[1] = o.normals_reduction;
-  en.l[0] = (int64_t)HWo;
-  return mg_launch(&en, stream);
+  return mg_ensemble_normals(preds, pred_out, unc_out_or_null, B, (int64_t)HWo, o.normals_reduction, stream);
 }
 
 namespace {

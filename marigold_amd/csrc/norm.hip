@@ -399,69 +399,75 @@ int launch_gn_slab(const GnSlabArgs& a, int B, hipStream_t s) {
 int mg_launch_norm(const mg_op* op, hipStream_t s) {
   switch (op->kind) {
     case MG_OP_GN_STATS: {
-      const int B = op->i[0], HW = op->i[1], C = op->i[2], chunks = op->i[3];
+      const int B = op->i[MG_GN_STATS_I_B], HW = op->i[MG_GN_STATS_I_HW], C = op->i[MG_GN_STATS_I_C], chunks = op->i[MG_GN_STATS_I_CHUNKS];
+      float* partials = (float*)op->p[MG_GN_STATS_P_PARTIALS];
+      const float *gamma = (const float*)op->p[MG_GN_STATS_P_GAMMA], *beta = (const float*)op->p[MG_GN_STATS_P_BETA];
+      unsigned* counters = (unsigned*)op->p[MG_GN_STATS_P_COUNTERS];
       MG_REQUIRE(C % 8 == 0 && C <= 256 * 8 * GN_NV, "gn_stats: unsupported C %d", C);
       MG_REQUIRE(B > 0 && HW > 0 && chunks > 0 && chunks <= HW, "gn_stats: bad dims");
       const int cvv = C / 8, tynn = 256 / (cvv < 256 ? cvv : 256);
-      const int Ctot = op->i[4] > 0 ? op->i[4] : C, coff = op->i[5];
-      const int groups = op->i[6], slot0 = op->i[7], slots = op->i[8] > 0 ? op->i[8] : chunks;
+      const int Ctot = op->i[MG_GN_STATS_I_CTOT] > 0 ? op->i[MG_GN_STATS_I_CTOT] : C, coff = op->i[MG_GN_STATS_I_COFF];
+      const int groups = op->i[MG_GN_STATS_I_GROUPS], slot0 = op->i[MG_GN_STATS_I_SLOT0];
+      const int slots = op->i[MG_GN_STATS_I_SLOTS] > 0 ? op->i[MG_GN_STATS_I_SLOTS] : chunks;
       MG_REQUIRE(coff >= 0 && coff + C <= Ctot && coff % 8 == 0, "gn_stats: channel window [%d,+%d) outside %d", coff, C, Ctot);
       MG_REQUIRE(groups > 0 && Ctot % groups == 0, "gn_stats: %d channels not divisible into %d groups", Ctot, groups);
-      // p[6] / i[9]: a second source (C1 channels right behind the first's) in the same launch - blocks [chunks, 2 chunks)
-      const bf16_t* x1 = (const bf16_t*)op->p[6];
-      const int C1 = x1 ? op->i[9] : 0;
+      // P_X1 / I_C1: a second source (C1 channels right behind the first's) in the same launch - blocks [chunks, 2 chunks)
+      const bf16_t* x1 = (const bf16_t*)op->p[MG_GN_STATS_P_X1];
+      const int C1 = x1 ? op->i[MG_GN_STATS_I_C1] : 0;
       const int nsrc = x1 ? 2 : 1;
       MG_REQUIRE(!x1 || (C1 > 0 && C1 % 8 == 0 && C1 <= 256 * 8 * GN_NV && coff + C + C1 <= Ctot), "gn_stats: second source of %d channels", C1);
       MG_REQUIRE(slot0 >= 0 && slot0 + nsrc * chunks <= slots, "gn_stats: slots [%d,+%d) outside %d", slot0, nsrc * chunks, slots);
-      MG_REQUIRE((uintptr_t)op->p[1] % 8 == 0, "gn_stats: the partial table needs 8-byte alignment");
-      // optional fused finalize: p[2] gamma p[3] beta p[4] scale_shift [B][2][Ctot] p[5] per-image arrival counters
-      float* ssout = (float*)op->p[4];
-      if (ssout) MG_REQUIRE(op->p[2] && op->p[3] && op->p[5], "gn_stats: fused finalize needs gamma, beta and counters");
+      MG_REQUIRE((uintptr_t)partials % 8 == 0, "gn_stats: the partial table needs 8-byte alignment");
+      // optional fused finalize: gamma, beta, scale_shift [B][2][Ctot], per-image arrival counters
+      float* ssout = (float*)op->p[MG_GN_STATS_P_SS];
+      if (ssout) MG_REQUIRE(gamma && beta && counters, "gn_stats: fused finalize needs gamma, beta and counters");
       size_t lds = (size_t)(tynn + 1) * 2 * C * sizeof(float);
       if (x1) {
         const int cv1 = C1 / 8, tyn1 = 256 / (cv1 < 256 ? cv1 : 256);
         lds = max(lds, (size_t)(tyn1 + 1) * 2 * C1 * sizeof(float));
       }
       MG_LAUNCH(gn_stats_kernel, dim3(nsrc * chunks, B), dim3(256), lds, s,
-                         (const bf16_t*)op->p[0], (float*)op->p[1], HW, C, chunks, Ctot, coff, slot0, slots,
-                         (const float*)op->p[2], (const float*)op->p[3], ssout, (unsigned*)op->p[5], groups, op->f[0], x1, C1);
+                         (const bf16_t*)op->p[MG_GN_STATS_P_X], partials, HW, C, chunks, Ctot, coff, slot0, slots, gamma, beta, ssout, counters,
+                         groups, op->f[MG_GN_STATS_F_EPS], x1, C1);
       break;
     }
     case MG_OP_GN_FINALIZE: {
-      const int B = op->i[0], C = op->i[1], groups = op->i[2], slots = op->i[3], HW = op->i[4];
+      const int B = op->i[MG_GN_FINALIZE_I_B], C = op->i[MG_GN_FINALIZE_I_C], groups = op->i[MG_GN_FINALIZE_I_GROUPS];
+      const int slots = op->i[MG_GN_FINALIZE_I_SLOTS], HW = op->i[MG_GN_FINALIZE_I_HW];
       MG_REQUIRE(groups > 0 && C % groups == 0, "gn_finalize: C %d not divisible by groups %d", C, groups);
       MG_LAUNCH(gn_finalize_kernel, dim3(B), dim3(256), 0, s,
-                         (const float*)op->p[0], (const float*)op->p[1], (const float*)op->p[2],
-                         (float*)op->p[3], B, C, groups, slots, HW, op->f[0]);
+                         (const float*)op->p[MG_GN_FINALIZE_P_PARTIALS], (const float*)op->p[MG_GN_FINALIZE_P_GAMMA],
+                         (const float*)op->p[MG_GN_FINALIZE_P_BETA],
+                         (float*)op->p[MG_GN_FINALIZE_P_SS], B, C, groups, slots, HW, op->f[MG_GN_FINALIZE_F_EPS]);
       break;
     }
     case MG_OP_GN_APPLY: {
-      const int B = op->i[0], HW = op->i[1], C = op->i[2];
+      const int B = op->i[MG_GN_APPLY_I_B], HW = op->i[MG_GN_APPLY_I_HW], C = op->i[MG_GN_APPLY_I_C];
       MG_REQUIRE(C % 8 == 0 && B > 0 && HW > 0, "gn_apply: C %d must be a multiple of 8", C);
       // ~2048 workgroups in total, >= 16 rows per thread row-lane
       const int cvv = C / 8, tynn = 256 / (cvv < 256 ? cvv : 256);
       int chunks = (2048 + B - 1) / B;
       chunks = max(1, min(chunks, HW / max(1, 8 * tynn)));
-      const bf16_t* x1 = (const bf16_t*)op->p[3];
-      const int C0 = x1 ? op->i[4] : C;
+      const bf16_t* x1 = (const bf16_t*)op->p[MG_GN_APPLY_P_X1];
+      const int C0 = x1 ? op->i[MG_GN_APPLY_I_C0] : C;
       MG_REQUIRE(C0 > 0 && C0 <= C && C0 % 8 == 0, "gn_apply: first source has %d of %d channels", C0, C);
-      MG_LAUNCH(gn_apply_kernel, dim3(chunks, B), dim3(256), 0, s, (const bf16_t*)op->p[0],
-                (const float*)op->p[1], (bf16_t*)op->p[2], HW, C, op->i[3], chunks, x1, C0);
+      MG_LAUNCH(gn_apply_kernel, dim3(chunks, B), dim3(256), 0, s, (const bf16_t*)op->p[MG_GN_APPLY_P_X],
+                (const float*)op->p[MG_GN_APPLY_P_SS], (bf16_t*)op->p[MG_GN_APPLY_P_OUT], HW, C, op->i[MG_GN_APPLY_I_SILU], chunks, x1, C0);
       break;
     }
     case MG_OP_GN_SLAB: {
       GnSlabArgs a;
-      a.x0 = (const bf16_t*)op->p[0];
-      a.x1 = (const bf16_t*)op->p[1];
-      a.y = (bf16_t*)op->p[2];
-      a.gamma = (const float*)op->p[3];
-      a.beta = (const float*)op->p[4];
-      a.ss = (float*)op->p[5];
-      const int B = op->i[0];
-      a.HW = op->i[1]; a.C = op->i[2]; a.C0 = a.x1 ? op->i[3] : a.C;
-      const int groups = op->i[4];
-      a.silu = op->i[5];
-      a.eps = op->f[0];
+      a.x0 = (const bf16_t*)op->p[MG_GN_SLAB_P_X0];
+      a.x1 = (const bf16_t*)op->p[MG_GN_SLAB_P_X1];
+      a.y = (bf16_t*)op->p[MG_GN_SLAB_P_OUT];
+      a.gamma = (const float*)op->p[MG_GN_SLAB_P_GAMMA];
+      a.beta = (const float*)op->p[MG_GN_SLAB_P_BETA];
+      a.ss = (float*)op->p[MG_GN_SLAB_P_SS];
+      const int B = op->i[MG_GN_SLAB_I_B];
+      a.HW = op->i[MG_GN_SLAB_I_HW]; a.C = op->i[MG_GN_SLAB_I_C]; a.C0 = a.x1 ? op->i[MG_GN_SLAB_I_C0] : a.C;
+      const int groups = op->i[MG_GN_SLAB_I_GROUPS];
+      a.silu = op->i[MG_GN_SLAB_I_SILU];
+      a.eps = op->f[MG_GN_SLAB_F_EPS];
       MG_REQUIRE(a.x0 && a.gamma && a.beta && a.ss && B > 0 && a.HW > 0 && groups > 0 && a.C % groups == 0, "gn_slab: bad arguments");
       a.cpg = a.C / groups;
       a.cw = a.cpg % 4 == 0 ? a.cpg : (a.cpg % 2 == 0 ? 2 * a.cpg : 4 * a.cpg);   // lcm(cpg, 4)

@@ -269,24 +269,26 @@ __global__ __launch_bounds__(IV_THREADS) void iid_vis_map_kernel(const float* __
 }
 
 static int launch_iid_vis(const mg_op* op, hipStream_t s) {
-  const int n = op->i[0], H = op->i[1], W = op->i[2];
-  const unsigned linear = (unsigned)op->i[3], up_to_scale = (unsigned)op->i[4];
+  const int n = op->i[MG_IID_VIS_I_N], H = op->i[MG_IID_VIS_I_H], W = op->i[MG_IID_VIS_I_W];
+  const unsigned linear = (unsigned)op->i[MG_IID_VIS_I_LINEAR_BITS], up_to_scale = (unsigned)op->i[MG_IID_VIS_I_UP_TO_SCALE_BITS];
+  const float* pred = (const float*)op->p[MG_IID_VIS_P_PRED];
+  uint8_t* out = (uint8_t*)op->p[MG_IID_VIS_P_OUT];
+  float* ws = (float*)op->p[MG_IID_VIS_P_WS];
   MG_REQUIRE(n >= 1 && n <= 16, "iid_vis: 1 to 16 targets per launch (got %d)", n);
   MG_REQUIRE(H > 0 && W > 0 && (long long)H * W <= (1ll << 30), "iid_vis: bad size %d x %d", H, W);
   MG_REQUIRE(!((linear | up_to_scale) >> n), "iid_vis: a flag names a target beyond the %d given", n);
-  MG_REQUIRE(op->p[0] && op->p[1], "iid_vis: null pointer");
-  MG_REQUIRE((uintptr_t)op->p[0] % 4 == 0, "iid_vis: the prediction must be 4-byte aligned");
+  MG_REQUIRE(pred && out, "iid_vis: null pointer");
+  MG_REQUIRE((uintptr_t)pred % 4 == 0, "iid_vis: the prediction must be 4-byte aligned");
   const unsigned need = linear & up_to_scale;   // the maximum is used by the linear, up-to-scale targets only
-  MG_REQUIRE(!need || (op->p[2] && (uintptr_t)op->p[2] % 4 == 0), "iid_vis: null or unaligned workspace (f32 [n][MG_IID_VIS_PARTS])");
+  MG_REQUIRE(!need || (ws && (uintptr_t)ws % 4 == 0), "iid_vis: null or unaligned workspace (f32 [n][MG_IID_VIS_PARTS])");
   const long long HW = (long long)H * W;
-  const int vec = HW % 4 == 0 && (uintptr_t)op->p[0] % 16 == 0 && (uintptr_t)op->p[1] % 4 == 0;
+  const int vec = HW % 4 == 0 && (uintptr_t)pred % 16 == 0 && (uintptr_t)out % 4 == 0;
   // a thread of the maximum takes at least 16 elements; the partial rows have MG_IID_VIS_PARTS slots
   const int parts = (int)min((3 * HW + 16 * IV_THREADS - 1) / (16 * IV_THREADS), (long long)MG_IID_VIS_PARTS);
-  if (need)
-    MG_LAUNCH(iid_vis_max_kernel, dim3(parts, n), dim3(IV_THREADS), 0, s, (const float*)op->p[0], (float*)op->p[2], 3 * HW, need, vec);
+  if (need) MG_LAUNCH(iid_vis_max_kernel, dim3(parts, n), dim3(IV_THREADS), 0, s, pred, ws, 3 * HW, need, vec);
   const long long work = vec ? HW / 4 : HW;
   MG_LAUNCH(iid_vis_map_kernel, dim3((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)1024), n), dim3(IV_THREADS), 0, s,
-            (const float*)op->p[0], (const float*)op->p[2], (uint8_t*)op->p[1], HW, parts, linear, up_to_scale, vec);
+            pred, (const float*)ws, out, HW, parts, linear, up_to_scale, vec);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -426,26 +428,30 @@ int mg_launch_resize(const mg_op* op, hipStream_t s) {
   if (op->kind == MG_OP_RGB_PREP) return launch_rgb_prep(op, s);
   if (op->kind == MG_OP_NORMALS_VIS) return launch_normals_vis(op, s);
   if (op->kind == MG_OP_COLORIZE) {
-    const long long n = op->l[0];
-    MG_REQUIRE(n > 0 && op->p[0] && op->p[1] && op->p[2], "colorize: null pointer / empty map");
-    MG_REQUIRE(op->f[1] > op->f[0], "colorize: max_depth must exceed min_depth");
-    MG_LAUNCH(colorize_kernel, dim3((unsigned)min((n + 255) / 256, (long long)4096)), dim3(256), 0, s, (const float*)op->p[0],
-              (const uint8_t*)op->p[1], (uint8_t*)op->p[2], n, op->f[0], 1.0f / (op->f[1] - op->f[0]));
+    const long long n = op->l[MG_COLORIZE_L_N];
+    const float* depth = (const float*)op->p[MG_COLORIZE_P_DEPTH];
+    const uint8_t* lut = (const uint8_t*)op->p[MG_COLORIZE_P_LUT];
+    uint8_t* out = (uint8_t*)op->p[MG_COLORIZE_P_OUT];
+    const float lo = op->f[MG_COLORIZE_F_MIN_DEPTH], hi = op->f[MG_COLORIZE_F_MAX_DEPTH];
+    MG_REQUIRE(n > 0 && depth && lut && out, "colorize: null pointer / empty map");
+    MG_REQUIRE(hi > lo, "colorize: max_depth must exceed min_depth");
+    MG_LAUNCH(colorize_kernel, dim3((unsigned)min((n + 255) / 256, (long long)4096)), dim3(256), 0, s, depth, lut, out, n, lo, 1.0f / (hi - lo));
     if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  const long long planes = op->i[0];
-  const int Hin = op->i[1], Win = op->i[2], Hout = op->i[3], Wout = op->i[4], mode = op->i[5];
-  const int u8 = op->i[6];  // 1: uint8 in and out, 0: fp32
+  const long long planes = op->i[MG_RESIZE_I_PLANES];
+  const int Hin = op->i[MG_RESIZE_I_HIN], Win = op->i[MG_RESIZE_I_WIN], Hout = op->i[MG_RESIZE_I_HOUT], Wout = op->i[MG_RESIZE_I_WOUT];
+  const int mode = op->i[MG_RESIZE_I_MODE];
+  const int u8 = op->i[MG_RESIZE_I_U8];  // 1: uint8 in and out, 0: fp32
+  void *src = op->p[MG_RESIZE_P_SRC], *dst = op->p[MG_RESIZE_P_DST];
+  float* tmp = (float*)op->p[MG_RESIZE_P_TMP];
   MG_REQUIRE(planes > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, "resize: empty image");
   MG_REQUIRE(mode >= 0 && mode <= 2, "resize: mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
-  MG_REQUIRE(op->p[0] && op->p[1], "resize: null pointer");
+  MG_REQUIRE(src && dst, "resize: null pointer");
   MG_REQUIRE(mode == 2 || Win != Wout || Hin != Hout, "resize: sizes are equal (the caller returns the input unchanged)");
-  MG_REQUIRE(mode == 2 || !(Win != Wout && Hin != Hout) || op->p[2], "resize: fp32 temporary [planes][Hin][Wout] missing");
-  if (u8) launch_resample(plane_src<uint8_t>{(const uint8_t*)op->p[0]}, plane_dst<uint8_t>{(uint8_t*)op->p[1]}, (float*)op->p[2], planes,
-                          Hin, Win, Hout, Wout, mode, s);
-  else launch_resample(plane_src<float>{(const float*)op->p[0]}, plane_dst<float>{(float*)op->p[1]}, (float*)op->p[2], planes, Hin, Win,
-                       Hout, Wout, mode, s);
+  MG_REQUIRE(mode == 2 || !(Win != Wout && Hin != Hout) || tmp, "resize: fp32 temporary [planes][Hin][Wout] missing");
+  if (u8) launch_resample(plane_src<uint8_t>{(const uint8_t*)src}, plane_dst<uint8_t>{(uint8_t*)dst}, tmp, planes, Hin, Win, Hout, Wout, mode, s);
+  else launch_resample(plane_src<float>{(const float*)src}, plane_dst<float>{(float*)dst}, tmp, planes, Hin, Win, Hout, Wout, mode, s);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -264,9 +264,14 @@ int mg_sched_step(const float* x, const float* model_out, const float* noise, fl
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_SCHED_STEP;
-  op.p[0] = (void*)x; op.p[1] = (void*)model_out; op.p[2] = (void*)noise; op.p[3] = out;
-  op.l[0] = n;
-  op.f[0] = cx; op.f[1] = cm; op.f[2] = cn;
+  op.p[MG_SCHED_STEP_P_X] = (void*)x;
+  op.p[MG_SCHED_STEP_P_MODEL_OUT] = (void*)model_out;
+  op.p[MG_SCHED_STEP_P_NOISE] = (void*)noise;
+  op.p[MG_SCHED_STEP_P_OUT] = out;
+  op.l[MG_SCHED_STEP_L_N] = n;
+  op.f[MG_SCHED_STEP_F_CX] = cx;
+  op.f[MG_SCHED_STEP_F_CM] = cm;
+  op.f[MG_SCHED_STEP_F_CN] = cn;
   return mg_launch_misc(&op, (hipStream_t)stream);
 }
 
@@ -275,9 +280,12 @@ int mg_ensemble_normals(const float* normals, float* out, float* unc, int E, int
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_ENS_NORMALS;
-  op.p[0] = (void*)normals; op.p[1] = out; op.p[2] = unc;
-  op.i[0] = E; op.i[1] = reduction;
-  op.l[0] = hw;
+  op.p[MG_ENS_NORMALS_P_NORMALS] = (void*)normals;
+  op.p[MG_ENS_NORMALS_P_OUT] = out;
+  op.p[MG_ENS_NORMALS_P_UNC] = unc;
+  op.i[MG_ENS_NORMALS_I_E] = E;
+  op.i[MG_ENS_NORMALS_I_REDUCTION] = reduction;
+  op.l[MG_ENS_NORMALS_L_HW] = hw;
   return mg_launch_ensemble(&op, (hipStream_t)stream);
 }
 
@@ -297,8 +305,16 @@ int mg_resize(const void* src, void* dst, float* tmp_or_null, int planes, int Hi
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_RESIZE;
-  op.p[0] = (void*)src; op.p[1] = dst; op.p[2] = tmp_or_null;
-  op.i[0] = planes; op.i[1] = Hin; op.i[2] = Win; op.i[3] = Hout; op.i[4] = Wout; op.i[5] = mode; op.i[6] = u8 != 0;
+  op.p[MG_RESIZE_P_SRC] = (void*)src;
+  op.p[MG_RESIZE_P_DST] = dst;
+  op.p[MG_RESIZE_P_TMP] = tmp_or_null;
+  op.i[MG_RESIZE_I_PLANES] = planes;
+  op.i[MG_RESIZE_I_HIN] = Hin;
+  op.i[MG_RESIZE_I_WIN] = Win;
+  op.i[MG_RESIZE_I_HOUT] = Hout;
+  op.i[MG_RESIZE_I_WOUT] = Wout;
+  op.i[MG_RESIZE_I_MODE] = mode;
+  op.i[MG_RESIZE_I_U8] = u8 != 0;
   return mg_launch_resize(&op, (hipStream_t)stream);
 }
 
@@ -306,9 +322,12 @@ int mg_colorize(const float* depth, const uint8_t* lut256x3, uint8_t* out_hwc, i
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_COLORIZE;
-  op.p[0] = (void*)depth; op.p[1] = (void*)lut256x3; op.p[2] = out_hwc;
-  op.l[0] = n;
-  op.f[0] = min_depth; op.f[1] = max_depth;
+  op.p[MG_COLORIZE_P_DEPTH] = (void*)depth;
+  op.p[MG_COLORIZE_P_LUT] = (void*)lut256x3;
+  op.p[MG_COLORIZE_P_OUT] = out_hwc;
+  op.l[MG_COLORIZE_L_N] = n;
+  op.f[MG_COLORIZE_F_MIN_DEPTH] = min_depth;
+  op.f[MG_COLORIZE_F_MAX_DEPTH] = max_depth;
   return mg_launch_resize(&op, (hipStream_t)stream);
 }
 
@@ -317,8 +336,14 @@ int mg_iid_visualize(const float* pred, uint8_t* out_hwc, float* workspace_or_nu
   mg_op op;
   memset(&op, 0, sizeof(op));
   op.kind = MG_OP_IID_VIS;
-  op.p[0] = (void*)pred; op.p[1] = out_hwc; op.p[2] = workspace_or_null;
-  op.i[0] = n_targets; op.i[1] = H; op.i[2] = W; op.i[3] = linear_bits; op.i[4] = up_to_scale_bits;
+  op.p[MG_IID_VIS_P_PRED] = (void*)pred;
+  op.p[MG_IID_VIS_P_OUT] = out_hwc;
+  op.p[MG_IID_VIS_P_WS] = workspace_or_null;
+  op.i[MG_IID_VIS_I_N] = n_targets;
+  op.i[MG_IID_VIS_I_H] = H;
+  op.i[MG_IID_VIS_I_W] = W;
+  op.i[MG_IID_VIS_I_LINEAR_BITS] = linear_bits;
+  op.i[MG_IID_VIS_I_UP_TO_SCALE_BITS] = up_to_scale_bits;
   return mg_launch_resize(&op, (hipStream_t)stream);
 }
 

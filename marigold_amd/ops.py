@@ -2,10 +2,11 @@
 host-side container that turns a list of them into a native program (``mg_program_*``).
 
 torch is used only as the owner of device memory and the source of the HIP stream handle.
-Field layout of every op is documented in include/marigold_hip.h.  The four kinds with many launch forms (MG_OP_IGEMM,
-MG_OP_CONV3X3, MG_OP_ROWGEMM, MG_OP_FLASH_ATTN64) are built and read by field NAME (the header's enumerators, mirrored in
-_lib.FIELDS): ``Raw`` is an op's fields as stored, ``igemm_view`` / ``conv3x3_view`` / ``rowgemm_view`` / ``flash_attn64_view`` the op
-decoded the way its launcher decodes it.  The launchers' defaulting rules are restated in those views and nowhere else in Python.
+Field layout of every op is documented in include/marigold_hip.h.  Every kind is built and read by field NAME (the header's
+enumerators, mirrored in _lib.FIELDS): ``build_op`` makes an op from its fields, ``Raw`` is an op's fields as stored.  For the four
+kinds with many launch forms (MG_OP_IGEMM, MG_OP_CONV3X3, MG_OP_ROWGEMM, MG_OP_FLASH_ATTN64) ``igemm_view`` / ``conv3x3_view`` /
+``rowgemm_view`` / ``flash_attn64_view`` are the op decoded the way its launcher decodes it.  The launchers' defaulting rules are
+restated in those views and nowhere else in Python.
 """
 import ctypes
 
@@ -23,30 +24,15 @@ def _ptr(x):
     return int(x)
 
 
-def make_op(kind, i=(), f=(), p=(), l=()):
-    op = MgOp()
-    op.kind = kind
-    for k, v in enumerate(i):
-        op.i[k] = int(v)
-    for k, v in enumerate(f):
-        op.f[k] = float(v)
-    for k, v in enumerate(p):
-        op.p[k] = _ptr(v)
-    for k, v in enumerate(l):
-        op.l[k] = int(v)
-    return op
-
-
 # --------------------------------------------------------------------------- named fields
 
 _TO_SLOT = dict(i=int, f=float, p=_ptr, l=int)
-_TABLES = {**L.FIELDS, **L.IO_FIELDS, **L.NOISE_FIELDS, **L.ENS_FIELDS}
-_WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in _TABLES.items()}
-assert all(len(w) == sum(len(names) for names in _TABLES[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
+_WHERE = {kind: {name: (arr, k) for arr, names in tab.items() for k, name in enumerate(names)} for kind, (_, tab) in L.FIELDS.items()}
+assert all(len(w) == sum(len(names) for names in L.FIELDS[kind][1].values()) for kind, w in _WHERE.items()), "a field name is used twice"
 
 
 class Raw:
-    """The fields of an op of one of the ``L.FIELDS`` / ``L.IO_FIELDS`` kinds by name, as stored: ``Raw(op).ldw`` reads and writes the op's MG_IGEMM_I_LDW slot."""
+    """The fields of an op by name, as stored: ``Raw(op).ldw`` reads and writes an MG_OP_IGEMM's MG_IGEMM_I_LDW slot."""
 
     def __init__(self, op):
         object.__setattr__(self, "op", op)
@@ -64,7 +50,7 @@ class Raw:
 
 
 def build_op(kind, **fields):
-    """An op of one of the ``L.FIELDS`` / ``L.IO_FIELDS`` kinds from its fields by name; what is not named stays zero / NULL."""
+    """An op from its fields by name; what is not named stays zero / NULL."""
     op = MgOp()
     op.kind = kind
     raw = Raw(op)
@@ -229,21 +215,21 @@ def gn_stats(x, partials, *, B, HW, C, chunks, groups, Ctot=0, coff=0, slot0=0, 
              counters=None, eps=0.0, x1=None, C1=0):
     """Partials [B][slots][groups][2]; with ``ss`` the image's last-arriving block also finalizes (MG_OP_GN_STATS).  ``x1``
     ([B][HW][C1]): the concat's second source in the same launch (slots slot0 + chunks ...)."""
-    return make_op(L.OP_GN_STATS, i=[B, HW, C, chunks, Ctot, coff, groups, slot0, slots, C1], f=[eps],
-                   p=[x, partials, gamma, beta, ss, counters, x1])
+    return build_op(L.OP_GN_STATS, b=B, hw=HW, c=C, chunks=chunks, ctot=Ctot, coff=coff, groups=groups, slot0=slot0, slots=slots, c1=C1, eps=eps,
+                    x=x, partials=partials, gamma=gamma, beta=beta, ss=ss, counters=counters, x1=x1)
 
 
 def gn_finalize(partials, gamma, beta, ss, *, B, C, groups, slots, HW, eps):
-    return make_op(L.OP_GN_FINALIZE, i=[B, C, groups, slots, HW], f=[eps], p=[partials, gamma, beta, ss])
+    return build_op(L.OP_GN_FINALIZE, b=B, c=C, groups=groups, slots=slots, hw=HW, eps=eps, partials=partials, gamma=gamma, beta=beta, ss=ss)
 
 
 def gn_apply(x, ss, out, *, B, HW, C, silu, x1=None, C0=0):
-    return make_op(L.OP_GN_APPLY, i=[B, HW, C, int(silu), C0], p=[x, ss, out, x1])
+    return build_op(L.OP_GN_APPLY, b=B, hw=HW, c=C, silu=silu, c0=C0, x=x, ss=ss, out=out, x1=x1)
 
 
 def gn_slab(x0, out, ss, *, B, HW, C, groups, gamma, beta, eps, silu=False, x1=None, C0=0):
     """GroupNorm in one launch (MG_OP_GN_SLAB): scale / shift into ``ss`` and, with ``out``, the normalised tensor."""
-    return make_op(L.OP_GN_SLAB, i=[B, HW, C, C0, groups, int(silu)], f=[eps], p=[x0, x1, out, gamma, beta, ss])
+    return build_op(L.OP_GN_SLAB, b=B, hw=HW, c=C, c0=C0, groups=groups, silu=silu, eps=eps, x0=x0, x1=x1, out=out, gamma=gamma, beta=beta, ss=ss)
 
 
 SPLITK_WS_BYTES = 64 << 20   # MG_SPLITK_WS_BYTES (csrc/common.h): what MG_OP_IGEMM's splitk_ws must hold
@@ -269,7 +255,7 @@ def flash_attn64(q, k, vt, o, *, B, heads, Ntok, ldq, ldo, ldvt, sq, sk, svt, so
 
 def flash_attn512(q, k, vt, o, *, B, Ntok, ldq, ldo, ldvt, sq, sk, svt, so, scale):
     """One head of width 512 (the VAE mid-block attention), flash form: no score matrix in memory (MG_OP_FLASH_ATTN512)."""
-    return make_op(L.OP_FLASH_ATTN512, i=[B, Ntok, ldq, ldo, ldvt], f=[scale], p=[q, k, vt, o], l=[sq, sk, svt, so])
+    return build_op(L.OP_FLASH_ATTN512, b=B, ntok=Ntok, ldq=ldq, ldo=ldo, ldvt=ldvt, scale=scale, q=q, k=k, vt=vt, o=o, sq=sq, sk=sk, svt=svt, so=so)
 
 
 VT_PERM16 = (0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15)
@@ -282,52 +268,52 @@ def permute_vt_keys(vt):
 
 
 def softmax_rows(s, p, *, R, ncols, lds, ldp):
-    return make_op(L.OP_SOFTMAX_ROWS, i=[R, ncols, lds, ldp], p=[s, p])
+    return build_op(L.OP_SOFTMAX_ROWS, r=R, ncols=ncols, lds=lds, ldp=ldp, scores=s, probs=p)
 
 
 def sched_step(x, model_out, noise, out, *, n, cx, cm, cn=0.0):
-    return make_op(L.OP_SCHED_STEP, f=[cx, cm, cn], p=[x, model_out, noise, out], l=[n])
+    return build_op(L.OP_SCHED_STEP, cx=cx, cm=cm, cn=cn, x=x, model_out=model_out, noise=noise, out=out, n=n)
 
 
 def linear_small_m(x, w, b, out, *, M, N, K, act_in=0, act_out=0, ldo=0):
-    return make_op(L.OP_LINEAR_SMALL_M, i=[M, N, K, act_in, act_out, ldo], p=[x, w, b, out])
+    return build_op(L.OP_LINEAR_SMALL_M, m=M, n=N, k=K, act_in=act_in, act_out=act_out, ldo=ldo, x=x, w=w, bias=b, out=out)
 
 
 def latent_1x1(x, w, b, out, *, B, Ci, Co, HW, scale=1.0):
-    return make_op(L.OP_LATENT_1X1, i=[B, Ci, Co, HW], f=[scale], p=[x, w, b, out])
+    return build_op(L.OP_LATENT_1X1, b=B, ci=Ci, co=Co, hw=HW, scale=scale, x=x, w=w, bias=b, out=out)
 
 
 def im2col_small(src0, src1, out, *, B, H, W, C0, C1, Kp, bcast0=False, members_per_src0=0):
     """``members_per_src0`` = m > 0: row b reads src0 row b // m (src0 [B / m, C0, H, W]); 0 = ``bcast0`` decides."""
-    i = [B, H, W, C0, C1, Kp, int(bcast0)] + ([int(members_per_src0)] if members_per_src0 else [])
-    return make_op(L.OP_IM2COL_SMALL, i=i, p=[src0, src1, out])
+    return build_op(L.OP_IM2COL_SMALL, b=B, h=H, w=W, c0=C0, c1=C1, kp=Kp, src0_broadcast=bcast0, members_per_src0=members_per_src0,
+                    src0=src0, src1=src1, out=out)
 
 
 def conv3x3_head(x, ss, w, bias, out, *, B, H, W, C, Cout, ldo=0, silu=True):
     """GroupNorm apply (``ss`` = scale / shift [B][2][C], or None) [+ SiLU] + conv3x3 pad 1 to <= 4 fp32 channels, one launch
     (MG_OP_CONV3X3_HEAD); ``w`` bf16 [>= Cout][9 C] as weights.pack_conv3x3 lays it out."""
-    return make_op(L.OP_CONV3X3_HEAD, i=[B, H, W, C, Cout, ldo, int(silu)], p=[x, ss, w, bias, out])
+    return build_op(L.OP_CONV3X3_HEAD, b=B, h=H, w=W, c=C, cout=Cout, ldo=ldo, silu=silu, x=x, ss=ss, wt=w, bias=bias, out=out)
 
 
 def post_nchw(x, out, *, B, HW, Cout, ldi, post=L.POST_NONE, scale=1.0, noise=None, cx=0.0, cm=0.0, cn=0.0):
-    return make_op(L.OP_POST_NCHW, i=[B, HW, Cout, ldi, post], f=[scale, cx, cm, cn], p=[x, out, noise])
+    return build_op(L.OP_POST_NCHW, b=B, hw=HW, cout=Cout, ldi=ldi, post=post, scale=scale, cx=cx, cm=cm, cn=cn, x=x, out=out, noise=noise)
 
 
 def ens_depth_stats(d, scratch, out, *, E, HW):
-    return make_op(L.OP_ENS_DEPTH_STATS, i=[E], p=[d, scratch, out], l=[HW])
+    return build_op(L.OP_ENS_DEPTH_STATS, e=E, d=d, scratch=scratch, out=out, hw=HW)
 
 
 def ens_depth_median(d, st, med, mad, minmax, scratch, *, E, HW, reduction=0, has_shift=True):
-    return make_op(L.OP_ENS_DEPTH_MEDIAN, i=[E, reduction, int(has_shift)],
-                   p=[d, st, med, mad, minmax, scratch], l=[HW])
+    return build_op(L.OP_ENS_DEPTH_MEDIAN, e=E, reduction=reduction, has_shift=has_shift, d=d, st=st, med=med, mad=mad, minmax=minmax,
+                    scratch=scratch, hw=HW)
 
 
 def ens_depth_norm(med, unc, minmax, *, HW, shift_invariant=True):
-    return make_op(L.OP_ENS_DEPTH_NORM, i=[int(shift_invariant)], p=[med, unc, minmax], l=[HW])
+    return build_op(L.OP_ENS_DEPTH_NORM, shift_invariant=shift_invariant, med=med, mad=unc, minmax=minmax, hw=HW)
 
 
 def ens_normals(n, out, unc, *, E, HW, reduction=0):
-    return make_op(L.OP_ENS_NORMALS, i=[E, reduction], p=[n, out, unc], l=[HW])
+    return build_op(L.OP_ENS_NORMALS, e=E, reduction=reduction, normals=n, out=out, unc=unc, hw=HW)
 
 
 def ens_iid(preds, pred, unc, *, E, n, reduction=0):
@@ -337,11 +323,11 @@ def ens_iid(preds, pred, unc, *, E, n, reduction=0):
 
 
 def resize(src, dst, tmp, *, planes, Hin, Win, Hout, Wout, mode, u8):
-    return make_op(L.OP_RESIZE, i=[planes, Hin, Win, Hout, Wout, mode, int(u8)], p=[src, dst, tmp])
+    return build_op(L.OP_RESIZE, planes=planes, hin=Hin, win=Win, hout=Hout, wout=Wout, mode=mode, u8=u8, src=src, dst=dst, tmp=tmp)
 
 
 def colorize(depth, lut, out, *, n, lo=0.0, hi=1.0):
-    return make_op(L.OP_COLORIZE, f=[lo, hi], p=[depth, lut, out], l=[n])
+    return build_op(L.OP_COLORIZE, min_depth=lo, max_depth=hi, depth=depth, lut=lut, out=out, n=n)
 
 
 def iid_vis(pred, out, ws, *, n, H, W, linear, up_to_scale):
@@ -351,7 +337,7 @@ def iid_vis(pred, out, ws, *, n, H, W, linear, up_to_scale):
     if len(linear) != n or len(up_to_scale) != n:
         raise ValueError(f"iid_vis: {n} targets, {len(linear)} linear and {len(up_to_scale)} up_to_scale flags")
     linear_bits, scale_bits = (sum(1 << t for t, v in enumerate(flags) if v) for flags in (linear, up_to_scale))
-    return make_op(L.OP_IID_VIS, i=[n, H, W, linear_bits, scale_bits], p=[pred, out, ws])
+    return build_op(L.OP_IID_VIS, n=n, h=H, w=W, linear_bits=linear_bits, up_to_scale_bits=scale_bits, pred=pred, out=out, ws=ws)
 
 
 RESIZE_MODES = {"bilinear": 0, "bicubic": 1, "nearest-exact": 2}   # MG_OP_RESIZE's and MG_OP_RGB_PREP's `mode`
@@ -396,42 +382,43 @@ def eval_fit_width(H, W, max_res):
 def eval_depth_ls(pred, gt, mask, out5, scratch, *, H, W, disparity=False, max_res=None):
     """The five fp64 sums of the least-squares fit (MG_OP_EVAL_DEPTH_LS); ``scratch``: 512 x 5 doubles."""
     ow, inv = eval_fit_width(H, W, max_res)
-    return make_op(L.OP_EVAL_DEPTH_LS, i=[H, W, int(disparity), ow], f=[inv], p=[pred, gt, mask, out5, scratch])
+    return build_op(L.OP_EVAL_DEPTH_LS, h=H, w=W, disparity=disparity, fit_w=ow, inv_factor=inv, pred=pred, gt=gt, mask=mask, out=out5, scratch=scratch)
 
 
 def eval_depth_metrics(pred, gt, mask, sums5, out13, scratch, *, H, W, disparity=False, min_depth=None, max_depth=None):
     """Align (``sums5`` from eval_depth_ls, None = as is), clip and score (MG_OP_EVAL_DEPTH_METRICS); ``scratch``: 512 x 11 doubles."""
-    return make_op(L.OP_EVAL_DEPTH_METRICS, i=[H, W, int(disparity), int(min_depth is not None), int(max_depth is not None)],
-                   f=[min_depth or 0.0, max_depth or 0.0], p=[pred, gt, mask, sums5, out13, scratch])
+    return build_op(L.OP_EVAL_DEPTH_METRICS, h=H, w=W, disparity=disparity, clip_min=min_depth is not None, clip_max=max_depth is not None,
+                    min_depth=min_depth or 0.0, max_depth=max_depth or 0.0, pred=pred, gt=gt, mask=mask, sums=sums5, out=out13, scratch=scratch)
 
 
 def eval_normals(pred, gt, out9, err, ws, *, HW, masked=True):
     """Angular error and its statistics incl. the exact median (MG_OP_EVAL_NORMALS); ``ws``: L.EVAL_WS_BYTES."""
-    return make_op(L.OP_EVAL_NORMALS, i=[int(masked)], p=[pred, gt, out9, err, ws], l=[HW])
+    return build_op(L.OP_EVAL_NORMALS, masked=masked, pred=pred, gt=gt, out=out9, err=err, ws=ws, hw=HW)
 
 
 def iidscore_prep(pred, gt, mask, out8, ws, *, H, W, gamma=None):
     """Alignment scale, exact 0.9 brightness quantile and its scale for an up-to-scale IID target (MG_OP_IIDSCORE_PREP);
     ``mask`` uint8 [3,H,W] or None; ``ws``: L.EVAL_WS_BYTES, shared with the score ops of the same target."""
-    return make_op(L.OP_IIDSCORE_PREP, i=[H, W, L.iid_gamma_mode(gamma)], p=[pred, gt, mask, out8, ws])
+    return build_op(L.OP_IIDSCORE_PREP, h=H, w=W, gamma=L.iid_gamma_mode(gamma), pred=pred, gt=gt, mask=mask, out=out8, ws=ws)
 
 
 def iidscore_psnr(pred, gt, mask, out8, ws, *, H, W, gamma=None, up_to_scale=False, write_psnr=True):
     """PSNR over the valid elements and their count (MG_OP_IIDSCORE_PSNR); ``up_to_scale``: map with what iidscore_prep left in ``ws``."""
-    return make_op(L.OP_IIDSCORE_PSNR, i=[H, W, L.iid_gamma_mode(gamma), int(up_to_scale), int(write_psnr)], p=[pred, gt, mask, out8, ws])
+    return build_op(L.OP_IIDSCORE_PSNR, h=H, w=W, gamma=L.iid_gamma_mode(gamma), up_to_scale=up_to_scale, write_psnr=write_psnr,
+                    pred=pred, gt=gt, mask=mask, out=out8, ws=ws)
 
 
 def iidscore_ssim(pred, gt, mask, out8, ws, *, H, W, gamma=None, up_to_scale=False):
     """Mean SSIM with the invalid elements zeroed (MG_OP_IIDSCORE_SSIM); H, W >= 11."""
-    return make_op(L.OP_IIDSCORE_SSIM, i=[H, W, L.iid_gamma_mode(gamma), int(up_to_scale)], p=[pred, gt, mask, out8, ws])
+    return build_op(L.OP_IIDSCORE_SSIM, h=H, w=W, gamma=L.iid_gamma_mode(gamma), up_to_scale=up_to_scale, pred=pred, gt=gt, mask=mask, out=out8, ws=ws)
 
 
 def memset(dst, nbytes, value=0):
-    return make_op(L.OP_MEMSET, i=[value], p=[dst], l=[nbytes])
+    return build_op(L.OP_MEMSET, value=value, dst=dst, bytes=nbytes)
 
 
 def copy(src, dst, nbytes):
-    return make_op(L.OP_COPY, p=[src, dst], l=[nbytes])
+    return build_op(L.OP_COPY, src=src, dst=dst, bytes=nbytes)
 
 
 # --------------------------------------------------------------------------- containers

@@ -21,9 +21,10 @@ BOUND = {"igemm_mfma": "mfma", "rowgemm_mfma": "mfma", "conv3x3_patch": "mfma", 
 
 def op_cost(op):
     """-> (class name, algorithmic FLOPs, algorithmic HBM bytes) of one launch."""
-    k, i, l = op.kind, op.i, op.l
+    k = op.kind
     cls = CLASS.get(k, "other")
     flops = byts = 0
+    r = O.Raw(op) if k in L.FIELDS else None   # the fields as stored, by name
     if k == L.OP_IGEMM:
         v = O.igemm_view(op)
         B, H, W, Cin, N, taps, M, K, bz, cx, n_out = v.b, v.h, v.w, v.cin, v.n, v.taps, v.M, v.K, v.batch_z, v.cx, v.n_out
@@ -60,61 +61,58 @@ def op_cost(op):
         if v.has_residual:
             byts += B * H * W * N * 2
     elif k == L.OP_CONV3X3_HEAD:
-        B, H, W, C, co = (i[j] for j in range(5))
-        flops = 2 * B * H * W * co * 9 * C
-        byts = B * H * W * (C * 2 + co * 4)
+        flops = 2 * r.b * r.h * r.w * r.cout * 9 * r.c
+        byts = r.b * r.h * r.w * (r.c * 2 + r.cout * 4)
     elif k == L.OP_FLASH_ATTN64:
         v = O.flash_attn64_view(op)
         B, heads, T = v.b, v.heads, v.ntok
         flops = 4 * B * heads * T * T * 64
         byts = 4 * B * heads * T * 64 * 2
     elif k == L.OP_FLASH_ATTN512:
-        B, T = i[0], i[1]
-        flops = 4 * B * T * T * 512
-        byts = 4 * B * T * 512 * 2
+        flops = 4 * r.b * r.ntok * r.ntok * 512
+        byts = 4 * r.b * r.ntok * 512 * 2
     elif k == L.OP_GN_STATS:
-        byts = i[0] * i[1] * (i[2] + (i[9] if op.p[6] else 0)) * 2
+        byts = r.b * r.hw * (r.c + (r.c1 if r.x1 else 0)) * 2
     elif k == L.OP_GN_APPLY:
-        byts = 2 * i[0] * i[1] * i[2] * 2
+        byts = 2 * r.b * r.hw * r.c * 2
     elif k == L.OP_GN_SLAB:
-        byts = (2 if op.p[2] else 1) * i[0] * i[1] * i[2] * 2
+        byts = (2 if r.out else 1) * r.b * r.hw * r.c * 2
     elif k == L.OP_SOFTMAX_ROWS:
-        byts = i[0] * i[1] * 4 + i[0] * i[3] * 2
+        byts = r.r * r.ncols * 4 + r.r * r.ldp * 2
     elif k == L.OP_SCHED_STEP:
-        byts = (4 if op.p[2] else 3) * l[0] * 4
+        byts = (4 if r.noise else 3) * r.n * 4
     elif k == L.OP_LINEAR_SMALL_M:
-        flops = 2 * i[0] * i[1] * i[2]
-        byts = i[1] * i[2] * 4
+        flops = 2 * r.m * r.n * r.k
+        byts = r.n * r.k * 4
     elif k == L.OP_LATENT_1X1:
-        byts = i[0] * (i[1] + i[2]) * i[3] * 4
+        byts = r.b * (r.ci + r.co) * r.hw * 4
     elif k == L.OP_IM2COL_SMALL:
-        byts = i[0] * i[1] * i[2] * ((i[3] + i[4]) * 4 + i[5] * 2)
+        byts = r.b * r.h * r.w * ((r.c0 + r.c1) * 4 + r.kp * 2)
     elif k == L.OP_POST_NCHW:
-        byts = i[0] * i[1] * (i[3] + (1 if i[4] == L.POST_DEPTH else i[2])) * 4
-        if i[4] == L.POST_SCHED:   # reads x_t (and the LCM noise) as well
-            byts += i[0] * i[1] * i[2] * 4 * (2 if op.p[2] else 1)
+        byts = r.b * r.hw * (r.ldi + (1 if r.post == L.POST_DEPTH else r.cout)) * 4
+        if r.post == L.POST_SCHED:   # reads x_t (and the LCM noise) as well
+            byts += r.b * r.hw * r.cout * 4 * (2 if r.noise else 1)
     elif k in (L.OP_ENS_DEPTH_STATS, L.OP_ENS_DEPTH_MEDIAN):
-        byts = i[0] * l[0] * 4
+        byts = r.e * r.hw * 4
     elif k == L.OP_ENS_DEPTH_NORM:
-        byts = 2 * l[0] * 4
+        byts = 2 * r.hw * 4
     elif k == L.OP_ENS_NORMALS:
-        byts = (i[0] + 1) * 3 * l[0] * 4
+        byts = (r.e + 1) * 3 * r.hw * 4
     elif k == L.OP_ENS_IID:   # every member read once, the prediction (and the uncertainty) written once
-        byts = (i[0] + (2 if op.p[2] else 1)) * l[0] * 4
+        byts = (r.e + (2 if r.unc else 1)) * r.n * 4
     elif k == L.OP_IID_VIS:   # the fp32 planes read once (twice by the targets that take a maximum first), one byte written per element
-        n3 = 3 * i[1] * i[2]
-        byts = n3 * (5 * i[0] + 4 * bin(i[3] & i[4]).count("1"))
+        n3 = 3 * r.h * r.w
+        byts = n3 * (5 * r.n + 4 * bin(r.linear_bits & r.up_to_scale_bits).count("1"))
     elif k == L.OP_RGB_PREP:   # one byte read per source element, one fp32 / 16-bit value written; two passes: the fp32 temporary once each way
-        v = O.Raw(op)
-        byts = 3 * (v.hin * v.win + v.hout * v.wout * (2 if v.out16 else 4))
-        if v.mode != 2 and v.hin != v.hout and v.win != v.wout:
-            byts += 2 * 3 * v.hin * v.wout * 4
+        byts = 3 * (r.hin * r.win + r.hout * r.wout * (2 if r.out16 else 4))
+        if r.mode != 2 and r.hin != r.hout and r.win != r.wout:
+            byts += 2 * 3 * r.hin * r.wout * 4
     elif k == L.OP_NORMALS_VIS:
-        byts = 3 * i[0] * i[1] * 5
+        byts = 3 * r.h * r.w * 5
     elif k == L.OP_RANDN:   # written once, nothing read
-        byts = l[0] * (2 if i[1] else 4)
+        byts = r.n * (2 if r.out16 else 4)
     elif k in (L.OP_MEMSET, L.OP_COPY):
-        byts = l[0]
+        byts = r.bytes
     return cls, flops, byts
 
 

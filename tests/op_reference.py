@@ -142,17 +142,17 @@ def _op16(f16):
 
 def decode(op, resolve, label="", f16=False):
     """One mg_op -> Spec (regions read / written, sample).  Raises Unsupported for forms without a reference."""
-    k, i, p, l = op.kind, list(op.i), [int(x or 0) for x in op.p], list(op.l)
+    k, r = op.kind, O.Raw(op)
     o16 = _op16(f16)
     name = L.OP_NAMES.get(k, str(k))
     sp = Spec(k, name, label, op)
     R = lambda ptr, dt, shape, strides: Region(ptr, dt, tuple(shape), tuple(strides))
     if k == L.OP_IM2COL_SMALL:
-        B, H, W, C0, C1, Kp, bc = i[:7]
-        if C1 or p[1] or bc:
+        B, H, W, C0, Kp = r.b, r.h, r.w, r.c0, r.kp
+        if r.c1 or r.src1 or r.src0_broadcast:
             raise Unsupported(label, "im2col_small with a second source / broadcast")
-        sp.reads["src0"] = R(p[0], torch.float32, (B, C0, H, W), (C0 * H * W, H * W, W, 1))
-        sp.writes["out"] = R(p[2], o16, (B * H * W, Kp), (Kp, 1))
+        sp.reads["src0"] = R(r.src0, torch.float32, (B, C0, H, W), (C0 * H * W, H * W, W, 1))
+        sp.writes["out"] = R(r.out, o16, (B * H * W, Kp), (Kp, 1))
         sp.rows = row_sample(B * H * W, H * W, Wimg=W, Himg=H)
     elif k == L.OP_IGEMM:
         v = O.igemm_view(op)
@@ -196,28 +196,28 @@ def decode(op, resolve, label="", f16=False):
         sp.rows = row_sample(M, Ho * Wo, Wimg=Wo if taps == 9 else 0, Himg=Ho if taps == 9 else 0)
         sp.n_check = v.n_alg or N
     elif k == L.OP_GN_STATS:
-        B, HW, C, chunks, Ctot, coff, groups, slot0, slots, C1 = i[:10]
-        if not p[4]:
+        B, HW, C = r.b, r.hw, r.c
+        if not r.ss:
             raise Unsupported(label, "gn_stats without the fused finalize")
-        if (Ctot and Ctot != C) or coff or p[6] or C1:
+        if (r.ctot and r.ctot != C) or r.coff or r.x1 or r.c1:
             raise Unsupported(label, "gn_stats of a channel window / second source")
-        sp.reads["x"] = R(p[0], o16, (B, HW, C), (HW * C, C, 1))
-        sp.reads["gamma"] = R(p[2], torch.float32, (C,), (1,))
-        sp.reads["beta"] = R(p[3], torch.float32, (C,), (1,))
-        sp.writes["ss"] = R(p[4], torch.float32, (B, 2, C), (2 * C, C, 1))
+        sp.reads["x"] = R(r.x, o16, (B, HW, C), (HW * C, C, 1))
+        sp.reads["gamma"] = R(r.gamma, torch.float32, (C,), (1,))
+        sp.reads["beta"] = R(r.beta, torch.float32, (C,), (1,))
+        sp.writes["ss"] = R(r.ss, torch.float32, (B, 2, C), (2 * C, C, 1))
     elif k == L.OP_GN_FINALIZE:
-        B, C, groups, slots, HW = i[:5]
-        sp.reads["partials"] = R(p[0], torch.float32, (B, slots, groups, 2), (slots * groups * 2, groups * 2, 2, 1))
-        sp.reads["gamma"] = R(p[1], torch.float32, (C,), (1,))
-        sp.reads["beta"] = R(p[2], torch.float32, (C,), (1,))
-        sp.writes["ss"] = R(p[3], torch.float32, (B, 2, C), (2 * C, C, 1))
+        B, C, groups, slots = r.b, r.c, r.groups, r.slots
+        sp.reads["partials"] = R(r.partials, torch.float32, (B, slots, groups, 2), (slots * groups * 2, groups * 2, 2, 1))
+        sp.reads["gamma"] = R(r.gamma, torch.float32, (C,), (1,))
+        sp.reads["beta"] = R(r.beta, torch.float32, (C,), (1,))
+        sp.writes["ss"] = R(r.ss, torch.float32, (B, 2, C), (2 * C, C, 1))
     elif k == L.OP_GN_APPLY:
-        B, HW, C, silu, C0 = i[:5]
-        if p[3]:
+        B, HW, C = r.b, r.hw, r.c
+        if r.x1:
             raise Unsupported(label, "gn_apply with a second source")
-        sp.reads["x"] = R(p[0], o16, (B, HW, C), (HW * C, C, 1))
-        sp.reads["ss"] = R(p[1], torch.float32, (B, 2, C), (2 * C, C, 1))
-        sp.writes["out"] = R(p[2], o16, (B, HW, C), (HW * C, C, 1))
+        sp.reads["x"] = R(r.x, o16, (B, HW, C), (HW * C, C, 1))
+        sp.reads["ss"] = R(r.ss, torch.float32, (B, 2, C), (2 * C, C, 1))
+        sp.writes["out"] = R(r.out, o16, (B, HW, C), (HW * C, C, 1))
     elif k == L.OP_CONV3X3:
         v = O.conv3x3_view(op)
         B, H, W, C0, N = v.b, v.h, v.w, v.c0, v.n
@@ -240,21 +240,21 @@ def decode(op, resolve, label="", f16=False):
             sp.writes["gn_table"] = R(v.gn_part, torch.float32, (B, v.gn_slots, ng, 2), (v.gn_slots * ng * 2, ng * 2, 2, 1))
         sp.rows = row_sample(M, H * W, Wimg=W, Himg=H)
     elif k == L.OP_SOFTMAX_ROWS:
-        Rn, ncols, lds, ldp = i[:4]
-        sp.reads["S"] = R(p[0], torch.float32, (Rn, ncols), (lds, 1))
-        sp.writes["P"] = R(p[1], o16, (Rn, ldp), (ldp, 1))
+        Rn, ncols, lds, ldp = r.r, r.ncols, r.lds, r.ldp
+        sp.reads["S"] = R(r.scores, torch.float32, (Rn, ncols), (lds, 1))
+        sp.writes["P"] = R(r.probs, o16, (Rn, ldp), (ldp, 1))
         sp.rows = row_sample(Rn, Rn)
     elif k == L.OP_POST_NCHW:
-        B, HW, Cout, ldi, post = i[:5]
-        if post != L.POST_NONE:
-            raise Unsupported(label, f"post_nchw mode {post}")
-        sp.reads["in"] = R(p[0], torch.float32, (B, HW, Cout), (HW * ldi, ldi, 1))
-        sp.writes["out"] = R(p[1], torch.float32, (B, Cout, HW), (Cout * HW, HW, 1))
+        B, HW, Cout, ldi = r.b, r.hw, r.cout, r.ldi
+        if r.post != L.POST_NONE:
+            raise Unsupported(label, f"post_nchw mode {r.post}")
+        sp.reads["in"] = R(r.x, torch.float32, (B, HW, Cout), (HW * ldi, ldi, 1))
+        sp.writes["out"] = R(r.out, torch.float32, (B, Cout, HW), (Cout * HW, HW, 1))
     else:
         raise Unsupported(label, f"op kind {name}")
-    for nm, r in sp.reads.items():   # every pointer the op reads must resolve
-        if resolve(r.ptr) is None:
-            raise KeyError(f"{label}: {nm} pointer {r.ptr:#x} resolves to no held tensor")
+    for nm, reg in sp.reads.items():   # every pointer the op reads must resolve
+        if resolve(reg.ptr) is None:
+            raise KeyError(f"{label}: {nm} pointer {reg.ptr:#x} resolves to no held tensor")
     return sp
 
 
@@ -287,12 +287,11 @@ def _taps_gather(A, rows, B, H, W, Ho, Wo, stride, pad, taps):
 
 def expected(spec, inputs, f16=False):
     """{output: (float64 reference, index)}: index = rows (GEMM-like) or None (whole region)."""
-    op, i, k = spec.op, list(spec.op.i), spec.kind
+    op, k, r = spec.op, spec.kind, O.Raw(spec.op)
     o16 = _op16(f16)
     dev = next(iter(inputs.values())).device
     if k == L.OP_IM2COL_SMALL:
-        B, H, W, C0 = i[:4]
-        Kp = i[5]
+        B, H, W, C0, Kp = r.b, r.h, r.w, r.c0, r.kp
         x = inputs["src0"].double().permute(0, 2, 3, 1).reshape(B * H * W, C0)
         rows = spec.rows.to(dev)
         g = _taps_gather(x, rows, B, H, W, H, W, 1, 1, 9)
@@ -331,15 +330,15 @@ def expected(spec, inputs, f16=False):
             res["out"] = (acc[:, :, :ncheck], rows)
         return res
     if k == L.OP_GN_STATS or k == L.OP_GN_FINALIZE:
-        eps = op.f[0]
+        eps = r.eps
         gamma, beta = inputs["gamma"].double(), inputs["beta"].double()
         if k == L.OP_GN_STATS:
-            B, HW, C, _, _, _, groups = i[:7]
+            B, HW, C, groups = r.b, r.hw, r.c, r.groups
             x = inputs["x"].double().reshape(B, HW, groups, C // groups)
             mean = x.mean(dim=(1, 3))
             var = x.var(dim=(1, 3), unbiased=False)
         else:
-            B, C, groups, slots, HW = i[:5]
+            B, C, groups, HW = r.b, r.c, r.groups, r.hw
             part = inputs["partials"].double().sum(1)     # [B][groups][2] = (sum, sum of squares)
             n = HW * (C // groups)
             mean = part[..., 0] / n
@@ -352,7 +351,7 @@ def expected(spec, inputs, f16=False):
     if k == L.OP_GN_APPLY:
         x, ss = inputs["x"].double(), inputs["ss"].double()
         y = x * ss[:, 0:1, :] + ss[:, 1:2, :]
-        if i[3]:
+        if r.silu:
             y = y * torch.sigmoid(y)
         return {"out": (y, None)}
     if k == L.OP_CONV3X3:
@@ -378,13 +377,13 @@ def expected(spec, inputs, f16=False):
         return {"out": (acc, rows)}
     if k == L.OP_SOFTMAX_ROWS:
         rows = spec.rows.to(dev)
-        ldp = i[3]
+        ldp = r.ldp
         s = inputs["S"][rows].double()
         ref = torch.zeros(len(rows), ldp, dtype=torch.float64, device=dev)
         ref[:, :s.shape[1]] = torch.softmax(s, dim=-1)
         return {"P": (ref, rows)}
     if k == L.OP_POST_NCHW:
-        return {"out": (inputs["in"].double().permute(0, 2, 1) * op.f[0], None)}
+        return {"out": (inputs["in"].double().permute(0, 2, 1) * r.scale, None)}
     raise Unsupported(spec.label, f"op kind {spec.name}")
 
 

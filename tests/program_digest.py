@@ -8,9 +8,9 @@ that served an earlier program would hand out its buffers in another order).  On
 
 A pointer is written as the buffer it points into - the module's pooled buffers, the program's held tensors and the weight
 store's - numbered by order of first appearance in that program, plus its byte offset; ``-`` is null.  The one integer field
-that carries an address, the ticket pair of MG_OP_IGEMM (``tickets_lo`` / ``tickets_hi``; no other name of ``L.FIELDS``,
-``L.IO_FIELDS`` or ``L.NOISE_FIELDS`` holds one), is written the same way.  So the text states every launch, every field and the
-buffer aliasing of a program, and is the same in every process.
+that carries an address, the ticket pair of MG_OP_IGEMM (``tickets_lo`` / ``tickets_hi``; no other integer name of ``L.FIELDS``
+holds one), is written the same way.  So the text states every launch, every field and the buffer aliasing of a program, and is
+the same in every process.
 
     python -m tests.program_digest --write            regenerate tests/golden/program_digest.json (records git's HEAD)
     python -m tests.program_digest --dump DIR         one text file per configuration, to ``diff -r`` two trees

@@ -53,7 +53,7 @@ def test_op_contracts_dry_run():
     seq.add(ops.eval_normals(None, None, a, None, a, HW=0))
     seq.validate()
     bad = ops.eval_depth_ls(a, a, a, a, a, H=120, W=200)
-    bad.i[3] = 201   # sub-sampled width beyond the map's
+    ops.Raw(bad).fit_w = 201   # sub-sampled width beyond the map's
     for op, msg in ((bad, "sub-sampled width"), (ops.eval_depth_ls(a, a, a, a + 4, a, H=8, W=8), "aligned"),
                     (ops.eval_depth_metrics(a, a, None, None, a, a, H=8, W=8), "null"),
                     (ops.eval_normals(a, a, a, None, None, HW=8), "null"),

@@ -59,7 +59,7 @@ def test_op_contracts_dry_run():
     seq.add(ops.iidscore_ssim(a, a, a, a, a, H=768, W=768, up_to_scale=True))
     seq.validate()
     odd_gamma = ops.iidscore_psnr(a, a, a, a, a, H=16, W=16)
-    odd_gamma.i[2] = 4
+    ops.Raw(odd_gamma).gamma = 4
     for op, msg in ((ops.iidscore_ssim(a, a, a, a, a, H=10, W=64), "H, W >= 11 required"),
                     (ops.iidscore_ssim(a, a, a, a, a, H=64, W=10), "H, W >= 11 required"),
                     (ops.iidscore_prep(a, None, a, a, a, H=16, W=16), "null"),

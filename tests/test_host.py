@@ -29,19 +29,49 @@ def test_library_loads_and_exports_header_symbols():
     assert ctypes.sizeof(_lib.MgOp) == 360   # kind + i[40] + f[8] (+4 pad) + p[16] + l[4]
 
 
-def test_op_field_names_match_the_header_and_the_wire_format():
-    """The enumerators of include/marigold_hip.h for the four named kinds equal _lib.FIELDS; every builder argument lands in the raw
-    slot the header documents (the numbers below are the wire format, written out on purpose) and reads back by name; the views
-    restate the launcher's defaulting rules (csrc/igemm2.hip::mg_launch_igemm2)."""
-    from marigold_amd import _lib as L, ops as O
+def test_every_kinds_field_names_and_number_match_the_header():
+    """The enumerators of include/marigold_hip.h equal _lib.FIELDS for every kind, and the header's MG_OP_* numbers equal _lib.OP_*:
+    the one comparison of the two tables.  tests/test_op_wire_host.py pins the bytes of every kind's builder."""
+    import ctypes
+    from marigold_amd import _lib as L
     hdr = open(os.path.join(ROOT, "include", "marigold_hip.h")).read()
+    # the kinds: one number each, the same in the binding
+    kinds = {name: int(n) for name, n in re.findall(r"^\s*MG_OP_(\w+) = (\d+)", hdr, flags=re.M)}
+    assert len(set(kinds.values())) == len(kinds)
+    assert kinds == {k[3:]: v for k, v in vars(L).items() if k.startswith("OP_") and k != "OP_NAMES"}
+    assert L.OP_NAMES == {n: name.lower() for name, n in kinds.items()}
+    assert (kinds["RGB_PREP"], kinds["NORMALS_VIS"], kinds["ENS_IID"]) == (5, 8, 19) and kinds["RANDN"] < 35   # free numbers below the last kind
+    assert kinds["IID_VIS"] == max(kinds.values())
+    assert re.search(r"#define MG_ABI_VERSION 4\b", hdr) and L.ABI_VERSION == 4 and ctypes.sizeof(L.MgOp) == 360
+    # the fields: every kind has a table, its prefix is the kind's name (MG_OP_FLASH_ATTN64: FLASH64)
+    assert set(L.FIELDS) == set(kinds.values())
+    assert {L.OP_NAMES[k].upper(): prefix for k, (prefix, _) in L.FIELDS.items() if L.OP_NAMES[k].upper() != prefix} == {"FLASH_ATTN64": "FLASH64"}
+    prefixes = sorted((prefix for prefix, _ in L.FIELDS.values()), key=len, reverse=True)   # (CONV3X3_HEAD before CONV3X3)
     parsed = {}
-    for kind, arr, name, val in re.findall(r"\bMG_(IGEMM|CONV3X3|ROWGEMM|FLASH64)_([IFPL])_([A-Z0-9_]+)\s*=\s*(\d+)", hdr):
-        assert name not in parsed.setdefault(kind, {}).setdefault(arr.lower(), {}), (kind, arr, name)
+    for kind, arr, name, val in re.findall(r"\bMG_(%s)_([IFPL])_([A-Z0-9_]+)\s*=\s*(\d+)" % "|".join(prefixes), hdr):
+        assert name not in parsed.setdefault(kind, {}).setdefault(arr.lower(), {}), (kind, arr, name)   # no name twice within a kind
+        assert int(val) < dict(i=40, f=8, p=16, l=4)[arr.lower()], (kind, arr, name)                    # inside mg_op's arrays
         parsed[kind][arr.lower()][name] = int(val)
     mine = {prefix: {arr: {n.upper(): k for k, n in enumerate(names)} for arr, names in tab.items()} for prefix, tab in L.FIELDS.values()}
-    assert parsed == mine
-    assert set(L.FIELDS) == {L.OP_IGEMM, L.OP_CONV3X3, L.OP_ROWGEMM, L.OP_FLASH_ATTN64}
+    assert parsed == mine   # every name on both sides, position = slot
+    for prefix, tab in L.FIELDS.values():
+        names = [n for arr in tab.values() for n in arr]
+        assert len(names) == len(set(names)), prefix   # ops.Raw reads a field by its name alone
+    # every enum of field names in the header belongs to a kind of the table (none is left out of the comparison above)
+    assert {(k.upper(), a) for k, a in re.findall(r"^enum mg_(\w+)_([iflp]) \{", hdr, flags=re.M)} == \
+        {(prefix, arr) for prefix, tab in L.FIELDS.values() for arr in tab}
+    # the wire format of the kinds added one at a time, written out on purpose
+    assert L.FIELDS[L.OP_RGB_PREP][1] == dict(i=("hin", "win", "hout", "wout", "mode", "hwc", "out16", "reciprocal"), p=("src", "dst", "tmp"))
+    assert L.FIELDS[L.OP_NORMALS_VIS][1] == dict(i=("h", "w"), p=("pred", "out"))
+    assert L.FIELDS[L.OP_RANDN][1] == dict(i=("mode", "out16"), p=("dst",), l=("n", "offset", "seed", "stream"))
+    assert L.FIELDS[L.OP_ENS_IID][1] == dict(i=("e", "reduction"), p=("preds", "pred", "unc"), l=("n",))
+
+
+def test_op_field_names_match_the_header_and_the_wire_format():
+    """For the four kinds with many launch forms every builder argument lands in the raw slot the header documents (the numbers below
+    are the wire format, written out on purpose) and reads back by name; the views restate the launcher's defaulting rules
+    (csrc/igemm2.hip::mg_launch_igemm2).  The names themselves against the header: the test above."""
+    from marigold_amd import _lib as L, ops as O
 
     def check(op, i, f, p, l, names):
         assert list(op.i) == i + [0] * (40 - len(i)) and list(op.f) == f + [0.0] * (8 - len(f))
@@ -476,7 +506,7 @@ def test_full_size_programs_validate_without_gpu():
     assert len(folded) == 14 and all(op.kind == L.OP_IGEMM and O.Raw(op).x0 and O.Raw(op).cx % 64 == 0 and O.Raw(op).taps == 9 for op in folded)
     assert sum(bool(O.Raw(op).x1) for op in folded) == 12         # the up blocks' [hidden | skip] pairs, never concatenated
     assert [lab for _, lab in fwd if lab.endswith(".conv_shortcut")] == []
-    assert any(op.kind == L.OP_GN_STATS and op.p[6] and op.i[9] > 0 for op, _ in fwd)      # a skip concat's statistics: one launch
+    assert any(op.kind == L.OP_GN_STATS and O.Raw(op).x1 and O.Raw(op).c1 > 0 for op, _ in fwd)      # a skip concat's statistics: one launch
     assert not any(lab.endswith((".stats0", ".stats1")) for _, lab in fwd)
     assert [lab for _, lab in labelled[:prog.n_prologue_ops]].count("resnets.time_emb_proj") == 1
     # the UNet's 96^2 head stays on the pass + GEMM pair, the decoder's 768^2 head is one MG_OP_CONV3X3_HEAD launch
@@ -488,7 +518,9 @@ def test_full_size_programs_validate_without_gpu():
     seq, _, _ = vae._program("decode", 2, 96, 96, 1)
     seq.validate()
     heads = [op for op in seq.ops if op.kind == L.OP_CONV3X3_HEAD]
-    assert len(heads) == 1 and (heads[0].i[1], heads[0].i[2], heads[0].i[3], heads[0].i[4]) == (768, 768, 128, 3) and heads[0].p[1]
+    assert len(heads) == 1
+    head = O.Raw(heads[0])
+    assert (head.h, head.w, head.c, head.cout) == (768, 768, 128, 3) and head.ss
     # 5754.3 GF as published; the three up-sampling convolutions in sub-pixel form execute 869.8 GF less
     assert abs(opstats.program_flops(seq.ops) / 2 / 1e9 - 4884.5) < 5
     # the IID family at full size (appearance: 2 modalities -> 12 in / 8 out latent channels; lighting: 3 -> 16 / 12):

@@ -39,7 +39,8 @@ def test_op_kind_in_header_binding_and_opstats():
     assert re.search(r"#define MG_ABI_VERSION 4\b", header) and L.ABI_VERSION == 4   # additive: no version bump
     a = 0x10000
     op = ops.iid_vis(a, a, a, n=3, H=768, W=768, linear=[True, True, False], up_to_scale=[True, False, True])
-    assert (op.i[0], op.i[1], op.i[2], op.i[3], op.i[4]) == (3, 768, 768, 0b011, 0b101)
+    raw = ops.Raw(op)
+    assert (raw.n, raw.h, raw.w, raw.linear_bits, raw.up_to_scale_bits) == (3, 768, 768, 0b011, 0b101)
     cls, flops, byts = opstats.op_cost(op)
     assert cls == "resize" and flops == 0
     assert byts == 3 * 768 * 768 * (3 * 5 + 4)   # fp32 in, one byte out per element; one target is read twice (its maximum)
@@ -56,7 +57,7 @@ def test_op_contract_dry_run_in_both_libraries():
         seq.add(ops.iid_vis(a, a, None, n=2, H=1, W=1, linear=[False, False], up_to_scale=[True, True]))
         seq.validate()
         stray = ops.iid_vis(a, a, a, n=2, H=8, W=8, linear=[True, False], up_to_scale=[False, False])
-        stray.i[3] = 0b100
+        ops.Raw(stray).linear_bits = 0b100
         for op, msg in ((ops.iid_vis(a, a, None, n=1, H=8, W=8, linear=[True], up_to_scale=[True]), "workspace"),
                         (ops.iid_vis(a, a, a + 2, n=1, H=8, W=8, linear=[True], up_to_scale=[True]), "workspace"),
                         (ops.iid_vis(None, a, a, n=1, H=8, W=8, linear=[False], up_to_scale=[False]), "null"),

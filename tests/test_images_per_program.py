@@ -125,7 +125,7 @@ def test_several_images_programs_validate_at_full_size():
         prog.seq.validate()
         assert tuple(prog.rgb_latent.shape) == (k, 4, 96, 96) and tuple(prog.x.shape) == (k * E, 4, 96, 96)
         i2c = [op for op in prog.seq.ops if op.kind == L.OP_IM2COL_SMALL]
-        assert len(i2c) == 2 and all(op.i[6] == 0 and op.i[7] == E and op.p[0] == prog.rgb_latent.data_ptr() for op in i2c)
+        assert len(i2c) == 2 and all(r.src0_broadcast == 0 and r.members_per_src0 == E and r.src0 == prog.rgb_latent.data_ptr() for r in map(O.Raw, i2c))
     # the legacy programs' keys are untouched; a divisor form is a program of its own
     assert unet.denoise_program(4, 96, 96, DDIMScheduler(), 2, rgb_members=1) is not unet.denoise_program(4, 96, 96, DDIMScheduler(), 2,
                                                                                                         rgb_broadcast=False)

@@ -1,5 +1,5 @@
 """The native noise generator (MG_OP_RANDN) and the one-call C prediction, the parts that need no GPU: the numpy restatement that
-judges the kernel against Random123's known answers; the op's kind and field names in the header, the binding and the builder; its
+judges the kernel against Random123's known answers; the slots the builder fills (the names against the header: tests/test_host.py); its
 contract through both libraries' dry run; the new C entry points in the header, the binding and both libraries; the stream
 bookkeeping of ``NativeNoise``."""
 import ctypes
@@ -52,23 +52,6 @@ def test_restatement_indexing():
 
 
 # ---- the op ------------------------------------------------------------------------------------------------------------------
-
-
-def test_op_kind_and_field_names_match_the_header():
-    header = _header()
-    kinds = {name: int(n) for name, n in re.findall(r"^\s*MG_OP_(\w+) = (\d+)", header, flags=re.M)}
-    others = [n for name, n in kinds.items() if name != "RANDN"]
-    assert kinds["RANDN"] == L.OP_RANDN and L.OP_RANDN < 35 and L.OP_RANDN not in others and len(set(others)) == len(others)
-    assert L.OP_NAMES[L.OP_RANDN] == "randn"
-    parsed = {}
-    for arr, name, val in re.findall(r"\bMG_RANDN_([IFPL])_([A-Z0-9_]+)\s*=\s*(\d+)", header):
-        assert name not in parsed.setdefault(arr.lower(), {}), (arr, name)
-        parsed[arr.lower()][name] = int(val)
-    prefix, tab = L.NOISE_FIELDS[L.OP_RANDN]
-    assert prefix == "RANDN" and parsed == {arr: {n.upper(): k for k, n in enumerate(names)} for arr, names in tab.items()}
-    assert set(L.NOISE_FIELDS) == {L.OP_RANDN} and not set(L.NOISE_FIELDS) & (set(L.FIELDS) | set(L.IO_FIELDS))
-    # the wire format, written out on purpose
-    assert tab == dict(i=("mode", "out16"), p=("dst",), l=("n", "offset", "seed", "stream"))
 
 
 def test_builder_fills_the_documented_slots():
