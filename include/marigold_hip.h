@@ -162,7 +162,13 @@ enum mg_op_kind {
   MG_OP_RESIZE = 24,
   /* Colour-mapped depth image (marigold/util/image_util.py:38-76 colorize_depth_maps followed by the pipeline's
    * (x * 255).astype(uint8), marigold_depth_pipeline.py:318-327): out[px] = LUT[min(int(clip((d - F_MIN_DEPTH) / (F_MAX_DEPTH -
-   * F_MIN_DEPTH), 0, 1) * 256), 255)].  The slots are named by the MG_COLORIZE_* enumerators below. */
+   * F_MIN_DEPTH), 0, 1) * 256), 255)]; a NaN depth is a black pixel.  The slots are named by the MG_COLORIZE_* enumerators below.
+   *  The depth output stage: with P_CLIPPED and / or P_U16 the same launch also stores what the depth pipeline and its command line
+   *  keep of the map (marigold_depth_pipeline.py:314-316, script/depth/run.py): clip(d, 0, 1) as numpy.clip gives it (NaN stays, +-inf ->
+   *  1 / 0, -0.0 stays) and uint16(clip(d, 0, 1) * 65535) - one fp32 product, truncated; NaN -> 0 (MG_OP_IID_VIS's convention).  Both
+   *  are defined for F_MIN_DEPTH = 0, F_MAX_DEPTH = 1 only; P_OUT (and with it P_LUT) is then optional.  P_CLIPPED may be P_DEPTH.  A lane
+   *  owns four neighbouring elements (16-byte load, 16- / 8- / 12-byte stores) when n % 4 == 0 and every pointer given is aligned for
+   *  its access, else one element.  With both NULL the colour bytes are those of the op without them. */
   MG_OP_COLORIZE = 25,
   /* Scoring of one prediction against its ground truth on the device (the validation loop of the reference,
    * src/trainer/marigold_depth_trainer.py:510-601, with src/util/alignment.py and src/util/metric.py; csrc/evalscore.hip).
@@ -219,7 +225,8 @@ enum mg_op_kind {
    *   * 2, then - 1.
    * NORMALS_VIS: the normals picture (marigold/marigold_normals_pipeline.py:297-301), the counterpart of MG_OP_COLORIZE: fp32
    *   [3][H][W] -> uint8 [H][W][3], out = uint8((clip(x, -1, 1) + 1) * 127.5) - the clip keeps NaN like numpy.clip, the sum and the
-   *   product are two fp32 roundings, the cast truncates; NaN -> 0 (MG_OP_IID_VIS's convention). */
+   *   product are two fp32 roundings, the cast truncates; NaN -> 0 (MG_OP_IID_VIS's convention).  (The call mg_normals_finish runs
+   *   the same kernel and can also store the clipped map; the op's fields are the two pointers below and stay so.) */
   MG_OP_RGB_PREP = 5,
   MG_OP_NORMALS_VIS = 8,
   /* Gaussian noise without a host generator (csrc/randn.hip): what torch.randn(generator=...) is to the reference's initial latents
@@ -717,8 +724,10 @@ enum mg_resize_p {
 enum mg_colorize_f { MG_COLORIZE_F_MIN_DEPTH = 0, MG_COLORIZE_F_MAX_DEPTH = 1 };
 enum mg_colorize_p {
   MG_COLORIZE_P_DEPTH = 0,        /* f32 [n] */
-  MG_COLORIZE_P_LUT = 1,          /* uint8 [256][3] (matplotlib's table) */
-  MG_COLORIZE_P_OUT = 2           /* uint8 [n][3] (HWC) */
+  MG_COLORIZE_P_LUT = 1,          /* uint8 [256][3] (matplotlib's table); required with P_OUT */
+  MG_COLORIZE_P_OUT = 2,          /* uint8 [n][3] (HWC) | NULL when P_CLIPPED or P_U16 is given */
+  MG_COLORIZE_P_CLIPPED = 3,      /* f32 [n] | NULL: clip(depth, 0, 1), NaN kept; may alias P_DEPTH (range (0, 1) only) */
+  MG_COLORIZE_P_U16 = 4           /* uint16 [n] | NULL: uint16(clip(depth, 0, 1) * 65535), NaN -> 0 (range (0, 1) only) */
 };
 enum mg_colorize_l { MG_COLORIZE_L_N = 0 };
 
@@ -901,6 +910,37 @@ typedef struct mg_predict_opts {
 int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                      const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null, void* stream);
 
+/* mg_model_predict carried on through match_input_res to what the pipelines return (marigold/marigold_depth_pipeline.py:306-329,
+ * marigold_normals_pipeline.py:282-301) and what script/depth/run.py writes: the map at the size asked for, clipped, the 16-bit depth
+ * and the picture.  Arguments up to opts are mg_model_predict's; the chain up to the ensemble is the same, call for call.  Then:
+ * with out_opts.out_h x out_w set and different from the decoded size cfg[11] x cfg[12] the ensembled prediction - not the
+ * uncertainty - is resampled to them (MG_OP_RESIZE in mode out_opts.out_mode); then one launch of the output stage on what was
+ * stored to pred_out, clipping it in place: depth - MG_OP_COLORIZE with P_CLIPPED = P_DEPTH (clip to [0, 1], the 16-bit values, the
+ * colour picture from out_opts.lut256x3, a DEVICE pointer to the colour map's 256 x 3 uint8 table); normals - mg_normals_finish (clip
+ * to [-1, 1], the picture).
+ *  pred_out    fp32 [channels][out_h][out_w] (the decoded size when out_h = out_w = 0), clipped
+ *  unc_out     fp32 [cfg[11]][cfg[12]] | NULL, written when B > 1
+ *  u16_out     uint16 [out_h][out_w] | NULL = uint16(pred_out * 65535), a depth model only
+ *  picture_out uint8 [out_h][out_w][3] | NULL; a depth model needs out_opts.lut256x3 for it
+ *  info4       as in mg_model_predict
+ * out_opts NULL = MG_OUTPUT_OPTS_DEFAULT: the decoded size, no table.  Refused: a host-only model, an intrinsic-image model (its entry
+ * point is mg_model_predict_iid), a bad out_mode or size, picture_out of a depth model without a table, u16_out or a table with a
+ * normals model.  The temporaries (the ensembled map ahead of a resize, the resize's fp32 intermediate) are the model's: grown on
+ * demand, counted by mg_model_device_bytes, freed by mg_model_destroy.  Synchronises where mg_ensemble_depth does and nowhere else.
+ * The Python pipelines give the same arrays and pictures, bit for bit, with generator=marigold_amd.NativeNoise(seed) and
+ * match_input_res=True (tests/test_gpu_predict_out_c_host.py; examples/host_picture.cpp).  No speed is claimed: the stage is
+ * microseconds beside a map. */
+typedef struct mg_output_opts {
+  int out_h, out_w;          /* match_input_res: size of pred_out, u16_out and picture_out; 0, 0 = the model's output size */
+  int out_mode;              /* resample mode of that resize, the numbering of MG_OP_RESIZE */
+  const uint8_t* lut256x3;   /* depth: the colour map's table on the device (marigold_amd.image.export_color_table writes its bytes) | NULL */
+} mg_output_opts;
+#define MG_OUTPUT_OPTS_DEFAULT {0, 0, 0, 0}
+int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                         const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
+                         float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
+                         void* stream);
+
 /* The same for an intrinsic-image model (appearance, lighting): __call__ of the reference's MarigoldIIDPipeline with fill_outputs
  * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[10] = n_targets
  * >= 1, 3 n_targets prediction channels, a DDIM image: the pipeline refuses the LCM scheduler and so does this call); a depth or
@@ -995,6 +1035,15 @@ int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null,
 int mg_rgb_prepare(const uint8_t* src, int hwc, int Hin, int Win, void* dst, int out16, int Hout, int Wout, int mode, int reciprocal,
                    float* tmp_or_null, void* stream);
 int mg_normals_visualize(const float* pred, int H, int W, uint8_t* out_hwc, void* stream);
+/* The output stages of the depth and the normals pipeline as calls, one launch each; neither synchronises.  At least one output.
+ *  mg_depth_visualize: MG_OP_COLORIZE over the range (0, 1) with its optional outputs - depth fp32 [n] -> clipped fp32 [n] (may be
+ *  `depth` itself), u16 uint16 [n], picture uint8 [n][3] (needs lut256x3, the table on the device).
+ *  mg_normals_finish: MG_OP_NORMALS_VIS's kernel - pred fp32 [3][H][W] -> clipped fp32 [3][H][W] = clip(pred, -1, 1), NaN kept (may be
+ *  `pred` itself), picture uint8 [H][W][3]; four pixels per lane when H W % 4 == 0 and the pointers are 16- / 4-byte aligned, else
+ *  one.  mg_normals_visualize is this call without the clipped map. */
+int mg_depth_visualize(const float* depth, const uint8_t* lut256x3_or_null, int64_t n, float* clipped_out_or_null,
+                       uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, void* stream);
+int mg_normals_finish(const float* pred, int H, int W, float* clipped_out_or_null, uint8_t* picture_out_or_null, void* stream);
 
 /* MG_OP_RANDN as a call: elements [offset, offset + n) of stream stream_id of seed -> dst (fp32, or with out16 != 0 the build's 16-bit
  * operand type).  Does not synchronise. */

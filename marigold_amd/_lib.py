@@ -162,7 +162,7 @@ FIELDS = {
         p=("src", "dst", "tmp"))),
     OP_COLORIZE: ("COLORIZE", dict(
         f=("min_depth", "max_depth"),
-        p=("depth", "lut", "out"),
+        p=("depth", "lut", "out", "clipped", "u16"),
         l=("n",))),
     OP_EVAL_DEPTH_LS: ("EVAL_DEPTH_LS", dict(
         i=("h", "w", "disparity", "fit_w"),
@@ -210,6 +210,7 @@ EXPORTS = [
     "mg_rgb_prepare", "mg_normals_visualize",
     "mg_randn", "mg_resize", "mg_colorize", "mg_iid_visualize", "mg_model_predict",
     "mg_ensemble_iid", "mg_model_predict_iid",
+    "mg_depth_visualize", "mg_normals_finish", "mg_model_predict_out",
 ]
 
 
@@ -227,6 +228,12 @@ class MgIidOpts(ctypes.Structure):
     """mg_iid_opts; the defaults are MG_IID_OPTS_DEFAULT (the median, every target in sRGB space, the model's output size)."""
     _fields_ = [("reduction", ctypes.c_int), ("linear_bits", ctypes.c_int), ("up_to_scale_bits", ctypes.c_int), ("out_h", ctypes.c_int),
                 ("out_w", ctypes.c_int), ("out_mode", ctypes.c_int)]
+
+
+class MgOutputOpts(ctypes.Structure):
+    """mg_output_opts; the defaults are MG_OUTPUT_OPTS_DEFAULT (the model's output size, no colour table).  ``lut256x3``: the DEVICE
+    address of the colour map's 256 x 3 uint8 table."""
+    _fields_ = [("out_h", ctypes.c_int), ("out_w", ctypes.c_int), ("out_mode", ctypes.c_int), ("lut256x3", ctypes.c_void_p)]
 
 
 class MgOp(ctypes.Structure):
@@ -314,6 +321,10 @@ def load(f16=False):
     lib.mg_model_predict.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgPredictOpts)] + [ctypes.c_void_p] * 4
     lib.mg_ensemble_iid.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_model_predict_iid.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgIidOpts)] + [ctypes.c_void_p] * 4
+    lib.mg_depth_visualize.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64] + [ctypes.c_void_p] * 4
+    lib.mg_normals_finish.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
+    lib.mg_model_predict_out.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgPredictOpts),
+                                                                                       ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

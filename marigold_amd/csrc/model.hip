@@ -79,6 +79,8 @@ struct mg_model {
   uint64_t predict_tmp_bytes = 0;
   void* iid_tmp = nullptr;           // mg_model_predict_iid's output temporaries (see iid_tmp_layout), grown on demand
   uint64_t iid_tmp_bytes = 0;
+  void* out_tmp = nullptr;           // mg_model_predict_out's (see out_tmp_layout), grown on demand
+  uint64_t out_tmp_bytes = 0;
 };
 
 namespace {
@@ -226,6 +228,7 @@ void mg_model_destroy(mg_model* m) {
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
   if (m->iid_tmp) (void)hipFree(m->iid_tmp);
+  if (m->out_tmp) (void)hipFree(m->out_tmp);
   delete m;
 }
 
@@ -235,7 +238,7 @@ int mg_model_info(const mg_model* m, int* cfg16) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->iid_tmp_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->iid_tmp_bytes + m->out_tmp_bytes) : 0; }
 
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
@@ -473,6 +476,25 @@ int predict_members(mg_model* m, const char* who, const uint8_t* rgb, int hwc, i
 
 }  // namespace
 
+namespace {
+
+// Stage 6 of a depth / normals prediction: the B members in the decoder's output slot -> the ensembled map in `dst` (one member: the
+// pipelines return it as it is, without an uncertainty - *final_pred is then the slot itself and nothing is stored).
+int ensemble_members(const float* preds, int B, int C, int post, int Ho, int Wo, const mg_predict_opts& o, float* dst, float* unc_out_or_null,
+                     double* info4_or_null, void* stream, const float** final_pred) {
+  if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
+  *final_pred = preds;
+  if (B == 1) return 0;
+  *final_pred = dst;
+  if (post == MG_POST_DEPTH)
+    return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
+                             o.max_res, dst, unc_out_or_null, info4_or_null, stream);
+  MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
+  return mg_ensemble_normals(preds, dst, unc_out_or_null, B, (int64_t)Ho * Wo, o.normals_reduction, stream);
+}
+
+}  // namespace
+
 extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                 const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
                                 void* stream) {
@@ -484,18 +506,76 @@ extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hi
   MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
   static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
   const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
-  const hipStream_t s = (hipStream_t)stream;
-  const uint64_t HWo = (uint64_t)Ho * Wo;
-  const float* preds = nullptr;
+  const float *preds = nullptr, *final_pred = nullptr;
   if (int rc = predict_members(m, "mg_model_predict", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
-  // 6. ensemble (one member: the pipelines return it as it is, without an uncertainty)
-  if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
-  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)C * HWo * 4, s);
-  if (post == MG_POST_DEPTH)
-    return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
-                             o.max_res, pred_out, unc_out_or_null, info4_or_null, stream);
-  MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
-  return mg_ensemble_normals(preds, pred_out, unc_out_or_null, B, (int64_t)HWo, o.normals_reduction, stream);
+  // 6. ensemble
+  if (int rc = ensemble_members(preds, B, C, post, Ho, Wo, o, pred_out, unc_out_or_null, info4_or_null, stream, &final_pred)) return rc;
+  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)C * Ho * Wo * 4, (hipStream_t)stream);
+  return 0;
+}
+
+namespace {
+// mg_model_predict_out's temporaries, carved out of the model's out_tmp in this order (each part rounded up to 256 bytes): the
+// ensembled map at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
+// [C][Ho][out_w] (modes 0 / 1 when both sizes change).
+struct OutTmp {
+  uint64_t ens = 0, rtmp = 0;
+  uint64_t total() const { return ens + rtmp; }
+};
+OutTmp out_tmp_layout(int B, int C, int Ho, int Wo, int oh, int ow, int out_mode) {
+  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
+  OutTmp t;
+  const bool resize = oh != Ho || ow != Wo;
+  if (resize && B > 1) t.ens = r256((uint64_t)C * Ho * Wo * 4);
+  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)C * Ho * ow * 4);
+  return t;
+}
+}  // namespace
+
+extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                    const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
+                                    float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
+                                    void* stream) {
+  MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_out: null argument (the model, the picture and pred_out are required)");
+  MG_REQUIRE(!m->host_only, "mg_model_predict_out: a host-only model cannot predict (load it with device >= 0)");
+  const uint32_t* cfg = m->hdr.cfg;
+  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7];
+  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict_out: an intrinsic-image model goes through mg_model_predict_iid");
+  const bool depth = post == MG_POST_DEPTH && C == 1;
+  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "mg_model_predict_out: a depth or a normals image is required");
+  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
+  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
+  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
+  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
+  MG_REQUIRE((q.out_h == 0 && q.out_w == 0) || (q.out_h > 0 && q.out_w > 0 && (long long)q.out_h * q.out_w <= (1ll << 30)),
+             "mg_model_predict_out: bad output size %d x %d", q.out_h, q.out_w);
+  MG_REQUIRE(q.out_mode >= 0 && q.out_mode <= 2, "mg_model_predict_out: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
+  if (depth) {
+    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "mg_model_predict_out: the picture of a depth model needs out_opts.lut256x3 (the colour table)");
+  } else {
+    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "mg_model_predict_out: u16_out and lut256x3 belong to a depth model, this one predicts normals");
+  }
+  const int oh = q.out_h ? q.out_h : Ho, ow = q.out_w ? q.out_w : Wo;
+  const bool resize = oh != Ho || ow != Wo;
+  const OutTmp t = out_tmp_layout(B, C, Ho, Wo, oh, ow, q.out_mode);
+  if (int rc = grow_tmp(&m->out_tmp, &m->out_tmp_bytes, t.total())) return rc;
+  float* const ens = (float*)m->out_tmp;
+  float* const rtmp = t.rtmp ? (float*)((char*)m->out_tmp + t.ens) : nullptr;
+  const float *preds = nullptr, *final_pred = nullptr;   // final_pred: at the decoded size
+  if (int rc = predict_members(m, "mg_model_predict_out", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
+  // 6. ensemble
+  if (int rc = ensemble_members(preds, B, C, post, Ho, Wo, o, resize ? ens : pred_out, unc_out_or_null, info4_or_null, stream, &final_pred))
+    return rc;
+  // 7. match_input_res (marigold_depth_pipeline.py:306-312, marigold_normals_pipeline.py:282-288): the prediction only
+  if (resize) {
+    if (int rc = mg_resize(final_pred, pred_out, rtmp, C, Ho, Wo, oh, ow, q.out_mode, 0, stream)) return rc;
+  } else if (B == 1) {
+    if (int rc = copy_dd(pred_out, preds, (uint64_t)C * Ho * Wo * 4, (hipStream_t)stream)) return rc;
+  }
+  // 8. the output stage on what was stored, in place: the clip (:314-316 / :294), the 16-bit depth (script/depth/run.py), the picture
+  if (depth) return mg_depth_visualize(pred_out, q.lut256x3, (int64_t)oh * ow, pred_out, u16_out_or_null, picture_out_or_null, stream);
+  return mg_normals_finish(pred_out, oh, ow, pred_out, picture_out_or_null, stream);
 }
 
 namespace {

@@ -163,21 +163,109 @@ void launch_resample(const SRC src, const DST dst, float* tmp, long long planes,
 // marigold_depth_pipeline.py:318-327): matplotlib's listed / segmented colormaps are 256-entry tables indexed by
 // int(x * 256) (x == 1 -> 255); the table arrives as uint8 RGB (built once per colormap on the host from matplotlib
 // itself), the output is the HWC uint8 image PIL takes.
-__global__ __launch_bounds__(256) void colorize_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ lut,
-                                                       uint8_t* __restrict__ out, long long n, float lo, float inv_range) {
+// The same launch is the depth pipeline's whole output stage (:314-316 and script/depth/run.py's 16-bit PNG): `clipped` = np.clip(d, 0, 1)
+// and `u16` = (np.clip(d, 0, 1) * 65535).astype(uint16), both of the depth itself (their range is (0, 1): lo = 0, inv_range = 1).  The
+// clip is written with comparisons so that NaN falls through both (and -0.0 stays, as in numpy's contiguous loop); the 16-bit value
+// is one fp32 product truncated, NaN -> 0.  Every output is optional; `clipped` may be `depth` (a lane reads its elements before
+// it writes them, and no other lane touches them).
+struct u32x3 { unsigned x, y, z; };   // 12 bytes, 4-byte aligned: four HWC pixels
+
+__device__ __forceinline__ float clip_cmp(float x, float lo, float hi) {
+  x = x < lo ? lo : x;
+  x = x > hi ? hi : x;
+  return x;
+}
+
+__device__ __forceinline__ unsigned depth_u16(float c) {   // c = the clipped depth, in [0, 1] or NaN
+  const float y = __fmul_rn(c, 65535.0f);
+  return y == y ? (unsigned)(int)y : 0u;
+}
+
+// The table entry of a depth: 3 k, or -1 for matplotlib's "bad" colour, RGBA (0, 0, 0, 0): a NaN depth is a black pixel, not entry 0
+__device__ __forceinline__ int depth_entry(float d, float lo, float inv_range) {
+  float x = (d - lo) * inv_range;
+  if (x != x) return -1;
+  x = clip_cmp(x, 0.f, 1.f);
+  int k = (int)(x * 256.0f);
+  k = k > 255 ? 255 : k;
+  return 3 * k;
+}
+
+// vec: a lane owns four neighbouring elements - one 16-byte load, a 16-byte store of the clipped values, an 8-byte store of the 16-bit
+// values, a 12-byte store of the colours (n % 4 == 0 and every pointer given aligned for its access); otherwise one element per lane.
+__global__ __launch_bounds__(256) void colorize_kernel(const float* depth, const uint8_t* __restrict__ lut, uint8_t* __restrict__ out,
+                                                       float* clipped, uint16_t* __restrict__ u16, long long n, float lo,
+                                                       float inv_range, int vec) {
   __shared__ uint8_t tab[768];
-  for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
-  __syncthreads();
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    float x = (depth[i] - lo) * inv_range;
-    const bool bad = x != x;   // matplotlib's "bad" colour, RGBA (0, 0, 0, 0): a NaN depth is a black pixel, not entry 0 of the table
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    int k = (int)(x * 256.0f);
-    k = k > 255 ? 255 : k;
-    out[3 * i + 0] = bad ? (uint8_t)0 : tab[3 * k + 0];
-    out[3 * i + 1] = bad ? (uint8_t)0 : tab[3 * k + 1];
-    out[3 * i + 2] = bad ? (uint8_t)0 : tab[3 * k + 2];
+  if (out) {   // (uniform over the grid)
+    for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
+    __syncthreads();
   }
+  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+  if (vec) {
+    for (long long q = first; q < n / 4; q += step) {
+      const float4 d = ((const float4*)depth)[q];
+      const float v[4] = {d.x, d.y, d.z, d.w};
+      if (clipped || u16) {
+        float c[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = clip_cmp(v[j], 0.f, 1.f);
+        if (clipped) ((float4*)clipped)[q] = make_float4(c[0], c[1], c[2], c[3]);
+        if (u16) ((uint2*)u16)[q] = make_uint2(depth_u16(c[0]) | depth_u16(c[1]) << 16, depth_u16(c[2]) | depth_u16(c[3]) << 16);
+      }
+      if (out) {
+        unsigned b[12];   // byte 3 j + c: channel c of pixel 4 q + j
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int e = depth_entry(v[j], lo, inv_range);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) b[3 * j + c] = e < 0 ? 0u : (unsigned)tab[e + c];
+        }
+        u32x3 w;
+        w.x = b[0] | b[1] << 8 | b[2] << 16 | b[3] << 24;
+        w.y = b[4] | b[5] << 8 | b[6] << 16 | b[7] << 24;
+        w.z = b[8] | b[9] << 8 | b[10] << 16 | b[11] << 24;
+        ((u32x3*)out)[q] = w;
+      }
+    }
+  } else {
+    for (long long i = first; i < n; i += step) {
+      const float d = depth[i];
+      if (clipped || u16) {
+        const float c = clip_cmp(d, 0.f, 1.f);
+        if (clipped) clipped[i] = c;
+        if (u16) u16[i] = (uint16_t)depth_u16(c);
+      }
+      if (out) {
+        const int e = depth_entry(d, lo, inv_range);
+        out[3 * i + 0] = e < 0 ? (uint8_t)0 : tab[e + 0];
+        out[3 * i + 1] = e < 0 ? (uint8_t)0 : tab[e + 1];
+        out[3 * i + 2] = e < 0 ? (uint8_t)0 : tab[e + 2];
+      }
+    }
+  }
+}
+
+static int launch_colorize(const mg_op* op, hipStream_t s) {
+  const long long n = op->l[MG_COLORIZE_L_N];
+  const float* depth = (const float*)op->p[MG_COLORIZE_P_DEPTH];
+  const uint8_t* lut = (const uint8_t*)op->p[MG_COLORIZE_P_LUT];
+  uint8_t* out = (uint8_t*)op->p[MG_COLORIZE_P_OUT];
+  float* clipped = (float*)op->p[MG_COLORIZE_P_CLIPPED];
+  uint16_t* u16 = (uint16_t*)op->p[MG_COLORIZE_P_U16];
+  const float lo = op->f[MG_COLORIZE_F_MIN_DEPTH], hi = op->f[MG_COLORIZE_F_MAX_DEPTH];
+  MG_REQUIRE(n > 0 && depth && (out || clipped || u16) && (lut || !out), "colorize: null pointer / empty map");
+  MG_REQUIRE(hi > lo, "colorize: max_depth must exceed min_depth");
+  MG_REQUIRE(!(clipped || u16) || (lo == 0.0f && hi == 1.0f),
+             "colorize: the clipped and the 16-bit output are defined for the range (0, 1) only (got %g, %g)", (double)lo, (double)hi);
+  MG_REQUIRE((uintptr_t)depth % 4 == 0 && (uintptr_t)clipped % 4 == 0 && (uintptr_t)u16 % 2 == 0,
+             "colorize: a pointer is not aligned to its element");
+  const int vec = n % 4 == 0 && (uintptr_t)depth % 16 == 0 && (uintptr_t)clipped % 16 == 0 && (uintptr_t)u16 % 8 == 0 && (uintptr_t)out % 4 == 0;
+  const long long work = vec ? n / 4 : n;
+  MG_LAUNCH(colorize_kernel, dim3((unsigned)min((work + 255) / 256, (long long)4096)), dim3(256), 0, s, depth, lut, out, clipped, u16, n, lo,
+            1.0f / (hi - lo), vec);
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 // The output stage of the intrinsic-image pipeline (marigold/marigold_iid_pipeline.py:117-136, MarigoldIIDOutput.fill_entry): per
@@ -296,8 +384,6 @@ static int launch_iid_vis(const mg_op* op, hipStream_t s) {
 // The input stage of every pipeline (marigold/marigold_depth_pipeline.py:229-255: pil_to_tensor, resize_max_res, `rgb / 255.0 * 2.0 -
 // 1.0`, the cast to the pipeline's dtype) on the uint8 picture as PIL holds it (HWC) or as a [3][H][W] tensor.  Same size: the
 // kernel below; sizes differ: the resampling passes above with the normalisation in the last pass's store (launch_rgb_prep).
-struct u32x3 { unsigned x, y, z; };   // 12 bytes, 4-byte aligned: four HWC pixels
-
 template <typename T>
 __device__ __forceinline__ void rgb_prep_store4(T* __restrict__ p, long long q, float a, float b, float c, float d) {
   if constexpr (std::is_same_v<T, float>) ((float4*)p)[q] = make_float4(a, b, c, d);
@@ -377,68 +463,81 @@ static int launch_rgb_prep(const mg_op* op, hipStream_t s) {
 
 // The normals picture (marigold/marigold_normals_pipeline.py:297-301): clip(-1, 1) as numpy.clip does (NaN stays), (x + 1) * 127.5 in
 // fp32 with two roundings, astype(uint8) = truncation to int32 and its low 8 bits; NaN gives 0 (MG_OP_IID_VIS's convention for
-// x86-64).  After the clip the product lies in [0, 255], so nothing else is out of range.
-__device__ __forceinline__ unsigned nv_byte(float x) {
-  x = clip_keep_nan(x, -1.0f, 1.0f);
-  x = __fmul_rn(__fadd_rn(x, 1.0f), 127.5f);
-  return (unsigned)(x == x ? (int)x : 0) & 0xffu;
+// x86-64).  After the clip the product lies in [0, 255], so nothing else is out of range.  The clipped values themselves are what
+// the pipeline keeps as normals_np (:294): `c`, when given, receives them (it may be `x`: a lane reads its pixels before it
+// writes them); either output may be NULL.
+__device__ __forceinline__ unsigned nv_byte(float c) {   // c = the clipped value
+  const float y = __fmul_rn(__fadd_rn(c, 1.0f), 127.5f);
+  return (unsigned)(y == y ? (int)y : 0) & 0xffu;
 }
 
-// vec: a lane owns four neighbouring pixels - three 16-byte loads, one per plane, and 12 contiguous output bytes; otherwise one pixel.
-__global__ __launch_bounds__(IV_THREADS) void normals_vis_kernel(const float* __restrict__ x, uint8_t* __restrict__ o, long long HW, int vec) {
+__device__ __forceinline__ float4 nv_clip4(float4 v) {
+  return make_float4(clip_keep_nan(v.x, -1.0f, 1.0f), clip_keep_nan(v.y, -1.0f, 1.0f), clip_keep_nan(v.z, -1.0f, 1.0f), clip_keep_nan(v.w, -1.0f, 1.0f));
+}
+
+// vec: a lane owns four neighbouring pixels - three 16-byte loads, one per plane, three 16-byte stores of the clipped values and 12
+// contiguous output bytes; otherwise one pixel.
+__global__ __launch_bounds__(IV_THREADS) void normals_vis_kernel(const float* x, float* c, uint8_t* __restrict__ o, long long HW, int vec) {
   const long long first = (long long)blockIdx.x * IV_THREADS + threadIdx.x, step = (long long)gridDim.x * IV_THREADS;
-  if (vec) {   // HW % 4 == 0, x 16-byte and o 4-byte aligned
-    const float4 *__restrict__ r4 = (const float4*)x, *__restrict__ g4 = (const float4*)(x + HW), *__restrict__ b4 = (const float4*)(x + 2 * HW);
+  if (vec) {   // HW % 4 == 0, x and c 16-byte and o 4-byte aligned
+    const float4 *r4 = (const float4*)x, *g4 = (const float4*)(x + HW), *b4 = (const float4*)(x + 2 * HW);
     u32x3* __restrict__ o12 = (u32x3*)o;
     for (long long q = first; q < HW / 4; q += step) {
-      const float4 r = r4[q], g = g4[q], b = b4[q];
-      u32x3 w;
-      w.x = nv_byte(r.x) | nv_byte(g.x) << 8 | nv_byte(b.x) << 16 | nv_byte(r.y) << 24;
-      w.y = nv_byte(g.y) | nv_byte(b.y) << 8 | nv_byte(r.z) << 16 | nv_byte(g.z) << 24;
-      w.z = nv_byte(b.z) | nv_byte(r.w) << 8 | nv_byte(g.w) << 16 | nv_byte(b.w) << 24;
-      o12[q] = w;
+      const float4 r = nv_clip4(r4[q]), g = nv_clip4(g4[q]), b = nv_clip4(b4[q]);
+      if (c) {
+        ((float4*)c)[q] = r;
+        ((float4*)(c + HW))[q] = g;
+        ((float4*)(c + 2 * HW))[q] = b;
+      }
+      if (o) {
+        u32x3 w;
+        w.x = nv_byte(r.x) | nv_byte(g.x) << 8 | nv_byte(b.x) << 16 | nv_byte(r.y) << 24;
+        w.y = nv_byte(g.y) | nv_byte(b.y) << 8 | nv_byte(r.z) << 16 | nv_byte(g.z) << 24;
+        w.z = nv_byte(b.z) | nv_byte(r.w) << 8 | nv_byte(g.w) << 16 | nv_byte(b.w) << 24;
+        o12[q] = w;
+      }
     }
   } else {
     for (long long i = first; i < HW; i += step) {
-      o[3 * i + 0] = (uint8_t)nv_byte(x[i]);
-      o[3 * i + 1] = (uint8_t)nv_byte(x[HW + i]);
-      o[3 * i + 2] = (uint8_t)nv_byte(x[2 * HW + i]);
+      const float r = clip_keep_nan(x[i], -1.0f, 1.0f), g = clip_keep_nan(x[HW + i], -1.0f, 1.0f), b = clip_keep_nan(x[2 * HW + i], -1.0f, 1.0f);
+      if (c) {
+        c[i] = r;
+        c[HW + i] = g;
+        c[2 * HW + i] = b;
+      }
+      if (o) {
+        o[3 * i + 0] = (uint8_t)nv_byte(r);
+        o[3 * i + 1] = (uint8_t)nv_byte(g);
+        o[3 * i + 2] = (uint8_t)nv_byte(b);
+      }
     }
   }
 }
 
-static int launch_normals_vis(const mg_op* op, hipStream_t s) {
-  const int H = op->i[MG_NORMALS_VIS_I_H], W = op->i[MG_NORMALS_VIS_I_W];
-  const float* pred = (const float*)op->p[MG_NORMALS_VIS_P_PRED];
-  uint8_t* out = (uint8_t*)op->p[MG_NORMALS_VIS_P_OUT];
+static int launch_normals(const float* pred, int H, int W, float* clipped, uint8_t* out, hipStream_t s) {
   MG_REQUIRE(H > 0 && W > 0 && (long long)H * W <= (1ll << 30), "normals_vis: bad size %d x %d", H, W);
-  MG_REQUIRE(pred && out, "normals_vis: null pointer");
-  MG_REQUIRE((uintptr_t)pred % 4 == 0, "normals_vis: the prediction must be 4-byte aligned");
+  MG_REQUIRE(pred && (out || clipped), "normals_vis: null pointer");
+  MG_REQUIRE((uintptr_t)pred % 4 == 0 && (uintptr_t)clipped % 4 == 0, "normals_vis: the prediction must be 4-byte aligned");
   const long long HW = (long long)H * W;
-  const int vec = HW % 4 == 0 && (uintptr_t)pred % 16 == 0 && (uintptr_t)out % 4 == 0;
+  const int vec = HW % 4 == 0 && (uintptr_t)pred % 16 == 0 && (uintptr_t)clipped % 16 == 0 && (uintptr_t)out % 4 == 0;
   const long long work = vec ? HW / 4 : HW;
-  MG_LAUNCH(normals_vis_kernel, dim3((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)2048)), dim3(IV_THREADS), 0, s, pred, out,
-            HW, vec);
+  MG_LAUNCH(normals_vis_kernel, dim3((unsigned)min((work + IV_THREADS - 1) / IV_THREADS, (long long)2048)), dim3(IV_THREADS), 0, s, pred,
+            clipped, out, HW, vec);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+static int launch_normals_vis(const mg_op* op, hipStream_t s) {
+  uint8_t* out = (uint8_t*)op->p[MG_NORMALS_VIS_P_OUT];
+  MG_REQUIRE(out, "normals_vis: null pointer");
+  return launch_normals((const float*)op->p[MG_NORMALS_VIS_P_PRED], op->i[MG_NORMALS_VIS_I_H], op->i[MG_NORMALS_VIS_I_W], nullptr, out, s);
 }
 
 int mg_launch_resize(const mg_op* op, hipStream_t s) {
   if (op->kind == MG_OP_IID_VIS) return launch_iid_vis(op, s);
   if (op->kind == MG_OP_RGB_PREP) return launch_rgb_prep(op, s);
   if (op->kind == MG_OP_NORMALS_VIS) return launch_normals_vis(op, s);
-  if (op->kind == MG_OP_COLORIZE) {
-    const long long n = op->l[MG_COLORIZE_L_N];
-    const float* depth = (const float*)op->p[MG_COLORIZE_P_DEPTH];
-    const uint8_t* lut = (const uint8_t*)op->p[MG_COLORIZE_P_LUT];
-    uint8_t* out = (uint8_t*)op->p[MG_COLORIZE_P_OUT];
-    const float lo = op->f[MG_COLORIZE_F_MIN_DEPTH], hi = op->f[MG_COLORIZE_F_MAX_DEPTH];
-    MG_REQUIRE(n > 0 && depth && lut && out, "colorize: null pointer / empty map");
-    MG_REQUIRE(hi > lo, "colorize: max_depth must exceed min_depth");
-    MG_LAUNCH(colorize_kernel, dim3((unsigned)min((n + 255) / 256, (long long)4096)), dim3(256), 0, s, depth, lut, out, n, lo, 1.0f / (hi - lo));
-    if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
+  if (op->kind == MG_OP_COLORIZE) return launch_colorize(op, s);
   const long long planes = op->i[MG_RESIZE_I_PLANES];
   const int Hin = op->i[MG_RESIZE_I_HIN], Win = op->i[MG_RESIZE_I_WIN], Hout = op->i[MG_RESIZE_I_HOUT], Wout = op->i[MG_RESIZE_I_WOUT];
   const int mode = op->i[MG_RESIZE_I_MODE];
@@ -470,13 +569,25 @@ int mg_rgb_prepare(const uint8_t* src, int hwc, int Hin, int Win, void* dst, int
   return launch_rgb_prep(&op, (hipStream_t)stream);
 }
 
+int mg_normals_finish(const float* pred, int H, int W, float* clipped_out_or_null, uint8_t* picture_out_or_null, void* stream) {
+  return launch_normals(pred, H, W, clipped_out_or_null, picture_out_or_null, (hipStream_t)stream);
+}
+
 int mg_normals_visualize(const float* pred, int H, int W, uint8_t* out_hwc, void* stream) {
+  MG_REQUIRE(out_hwc, "normals_vis: null pointer");
+  return mg_normals_finish(pred, H, W, nullptr, out_hwc, stream);
+}
+
+int mg_depth_visualize(const float* depth, const uint8_t* lut256x3_or_null, int64_t n, float* clipped_out_or_null, uint16_t* u16_out_or_null,
+                       uint8_t* picture_out_or_null, void* stream) {
   mg_op op;
   memset(&op, 0, sizeof(op));
-  op.kind = MG_OP_NORMALS_VIS;
-  op.p[MG_NORMALS_VIS_P_PRED] = (void*)pred; op.p[MG_NORMALS_VIS_P_OUT] = out_hwc;
-  op.i[MG_NORMALS_VIS_I_H] = H; op.i[MG_NORMALS_VIS_I_W] = W;
-  return launch_normals_vis(&op, (hipStream_t)stream);
+  op.kind = MG_OP_COLORIZE;
+  op.p[MG_COLORIZE_P_DEPTH] = (void*)depth; op.p[MG_COLORIZE_P_LUT] = (void*)lut256x3_or_null; op.p[MG_COLORIZE_P_OUT] = picture_out_or_null;
+  op.p[MG_COLORIZE_P_CLIPPED] = clipped_out_or_null; op.p[MG_COLORIZE_P_U16] = u16_out_or_null;
+  op.l[MG_COLORIZE_L_N] = n;
+  op.f[MG_COLORIZE_F_MIN_DEPTH] = 0.0f; op.f[MG_COLORIZE_F_MAX_DEPTH] = 1.0f;
+  return launch_colorize(&op, (hipStream_t)stream);
 }
 
 }  // extern "C"

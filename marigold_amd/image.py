@@ -218,6 +218,18 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
                 pred_channels=cpred * n_mod, step_noises=len(den.noises))
 
 
+def export_color_table(cmap, path):
+    """Write the 768 bytes (256 x RGB, uint8) of the matplotlib colour map ``cmap`` as the depth pipelines index it - the table
+    ``util.image_util.colorize_depth_device`` builds - to ``path``: what a host without matplotlib uploads as
+    ``mg_output_opts.lut256x3`` (examples/host_picture.cpp).  Returns the table (uint8 [256, 3])."""
+    from .util.image_util import colormap_lut_u8
+    table = colormap_lut_u8(cmap)
+    assert table.shape == (256, 3) and table.dtype.itemsize == 1
+    with open(path, "wb") as f:
+        f.write(table.tobytes())
+    return table
+
+
 class ModelImage:
     """ctypes handle on a loaded model image - what a non-Python host does, spelled in Python for the tests and as a second,
     graph-free way to run a fixed-shape deployment: ``encode`` / ``denoise`` / ``decode`` take and return torch CUDA tensors
@@ -281,6 +293,37 @@ class ModelImage:
                                                None if unc is None else unc.data_ptr(), None if pics is None else pics.data_ptr(),
                                                O.current_stream_handle()), "mg_model_predict_iid", self._lib)
         return pred, unc, pics
+
+    def predict_out(self, u8, seed, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False, opts=None, mode=0, reciprocal=None):
+        """``mg_model_predict_out`` on the uint8 CUDA picture ``u8`` [Hin, Win, 3]: the pipelines' output with ``match_input_res`` ->
+        (pred fp32 [C, out_h, out_w] clipped, unc fp32 [Hout, Wout] | None for a single member, u16 uint16 [out_h, out_w] | None unless
+        ``u16``, picture uint8 [out_h, out_w, 3] | None unless ``picture``, info = the four numbers of ``mg_ensemble_depth``).
+        ``out_size``: (out_h, out_w), None = the model's output size; ``out_mode``: a key of ``ops.RESIZE_MODES`` or its number;
+        ``lut``: the colour table, uint8 CUDA [256, 3] (a depth model's picture needs it); ``opts``: an ``_lib.MgPredictOpts``;
+        ``mode`` / ``reciprocal``: the input resampling as in ``predict_iid``."""
+        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_out: a uint8 CUDA [H, W, 3] picture"
+        u8 = u8.contiguous()
+        Hin, Win = u8.shape[:2]
+        if reciprocal is None:
+            reciprocal = (Hin, Win) != (self.H, self.W)
+        oh, ow = (self.Hout, self.Wout) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        if lut is not None:
+            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_out: the colour table is uint8 CUDA [256, 3]"
+            lut = lut.contiguous()
+        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
+                                  None if lut is None else lut.data_ptr())
+        dev = u8.device
+        pred = torch.empty(self.pred_channels, oh, ow, device=dev, dtype=torch.float32)
+        unc = torch.empty(self.Hout, self.Wout, device=dev, dtype=torch.float32) if self.B > 1 else None
+        d16 = torch.empty(oh, ow, device=dev, dtype=torch.uint16) if u16 else None
+        pic = torch.empty(oh, ow, 3, device=dev, dtype=torch.uint8) if picture else None
+        info = (ctypes.c_double * 4)()
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        L.check(self._lib.mg_model_predict_out(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
+                                               int(seed) & ((1 << 64) - 1), None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
+                                               pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle()),
+                "mg_model_predict_out", self._lib)
+        return pred, unc, d16, pic, list(info)
 
     def close(self):
         if self.handle:

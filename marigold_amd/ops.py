@@ -326,8 +326,11 @@ def resize(src, dst, tmp, *, planes, Hin, Win, Hout, Wout, mode, u8):
     return build_op(L.OP_RESIZE, planes=planes, hin=Hin, win=Win, hout=Hout, wout=Wout, mode=mode, u8=u8, src=src, dst=dst, tmp=tmp)
 
 
-def colorize(depth, lut, out, *, n, lo=0.0, hi=1.0):
-    return build_op(L.OP_COLORIZE, min_depth=lo, max_depth=hi, depth=depth, lut=lut, out=out, n=n)
+def colorize(depth, lut, out, *, n, lo=0.0, hi=1.0, clipped=None, u16=None):
+    """The depth picture (MG_OP_COLORIZE): fp32 ``depth`` [n] -> uint8 ``out`` [n, 3] through the 256 x 3 uint8 table ``lut``.
+    ``clipped`` (fp32 [n], may be ``depth``) / ``u16`` (uint16 [n]): the same launch also stores ``clip(depth, 0, 1)`` and
+    ``uint16(clip(depth, 0, 1) * 65535)`` - the range (0, 1) only; ``out`` (and ``lut``) may then be None."""
+    return build_op(L.OP_COLORIZE, min_depth=lo, max_depth=hi, depth=depth, lut=lut, out=out, clipped=clipped, u16=u16, n=n)
 
 
 def iid_vis(pred, out, ws, *, n, H, W, linear, up_to_scale):

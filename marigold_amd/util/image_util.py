@@ -139,6 +139,29 @@ def colorize_depth_device(depth: torch.Tensor, min_depth=0.0, max_depth=1.0, cma
     return out
 
 
+def depth_output_device(depth: torch.Tensor, cmap="Spectral", in_place=False):
+    """The depth pipeline's output stage in one launch (csrc/resize.hip, MG_OP_COLORIZE with its optional outputs): fp32 CUDA map
+    [H, W] -> (clipped fp32 [H, W] = ``clip(depth, 0, 1)`` keeping NaN, u16 uint16 [H, W] = ``(clipped * 65535).astype(uint16)`` - what
+    the command line writes as the 16-bit PNG; NaN gives 0 -, picture uint8 [H, W, 3] | None when ``cmap`` is None).  ``in_place``:
+    the clipped values overwrite ``depth`` (which must be contiguous) and are returned as it."""
+    from .. import ops as O
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2
+    assert not in_place or depth.is_contiguous(), "depth_output_device: in place needs a contiguous map"
+    with torch.cuda.device(depth.device):
+        d = depth.contiguous()
+        lut = pic = None
+        if cmap is not None:
+            key = (cmap, d.device)
+            if key not in _LUT_CACHE:
+                _LUT_CACHE[key] = torch.from_numpy(colormap_lut_u8(cmap)).to(d.device).contiguous()
+            lut = _LUT_CACHE[key]
+            pic = torch.empty(d.shape + (3,), dtype=torch.uint8, device=d.device)
+        clipped = d if in_place else torch.empty_like(d)
+        u16 = torch.empty(d.shape, dtype=torch.uint16, device=d.device)
+        O.launch(O.colorize(d, lut, pic, n=d.numel(), clipped=clipped, u16=u16))
+    return clipped, u16, pic
+
+
 def iid_visualization_device(pred: torch.Tensor, linear, up_to_scale) -> torch.Tensor:
     """Device form of the images ``MarigoldIIDOutput.fill_entry`` builds, for all targets of one image at once: fp32 CUDA
     ``pred`` [n, 3, H, W] (or [3, H, W]) -> uint8 CUDA [n, H, W, 3].  Per target t: ``linear[t]`` = its prediction space is
@@ -214,6 +237,24 @@ def normals_visualization_device(pred: torch.Tensor) -> torch.Tensor:
         out = torch.empty(tuple(src.shape[1:]) + (3,), dtype=torch.uint8, device=src.device)
         O.launch(O.normals_vis(src, out, H=src.shape[1], W=src.shape[2]))
     return out
+
+
+def normals_output_device(pred: torch.Tensor, in_place=False):
+    """The normals pipeline's output stage in one launch (``mg_normals_finish``, MG_OP_NORMALS_VIS's kernel): fp32 CUDA ``pred``
+    [3, H, W] -> (clipped fp32 [3, H, W] = ``clip(pred, -1, 1)`` keeping NaN, picture uint8 [H, W, 3]).  ``in_place``: the clipped
+    values overwrite ``pred`` (contiguous)."""
+    from .. import _lib as L, ops as O
+    assert pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 3 and pred.shape[0] == 3, \
+        f"normals_output_device: fp32 CUDA [3, H, W] expected, got {pred.dtype} {tuple(pred.shape)} on {pred.device}"
+    assert not in_place or pred.is_contiguous(), "normals_output_device: in place needs a contiguous map"
+    with torch.cuda.device(pred.device):
+        src = pred.contiguous()
+        clipped = src if in_place else torch.empty_like(src)
+        out = torch.empty(tuple(src.shape[1:]) + (3,), dtype=torch.uint8, device=src.device)
+        lib = L.load()
+        L.check(lib.mg_normals_finish(src.data_ptr(), src.shape[1], src.shape[2], clipped.data_ptr(), out.data_ptr(), O.current_stream_handle()),
+                "mg_normals_finish", lib)
+    return clipped, out
 
 
 def chw2hwc(chw):
