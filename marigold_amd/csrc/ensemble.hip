@@ -14,9 +14,15 @@
 //     scalars (no host sync).
 // Normals (ensemble_normals :199-249): one fused per-pixel kernel (mean -> normalise -> cosine
 // -> arccos mean / pi -> argmax -> gather).
+// Intrinsic images (ensemble_iid :252-270): IID is DEPTH_MEDIAN's reduction over the members alone, per element.
 // All HBM-bound streaming kernels: E*HW*4 B read per pass, coalesced over pixels.
+// What the kernels share is written once: the reduction over the members of one element (reduce_members for members in registers,
+// reduce_members_mem - rank count, bitwise selection, mean / std - for members in LDS or memory), the block's extrema
+// (store_block_extrema), the wave's (wave_extrema, under either order) and the ladder of register bounds (with_member_bound).
+// tests/golden/ensemble_bits.json holds a digest of every output of every kernel form.
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -175,6 +181,160 @@ __device__ __forceinline__ float select_kth(const float (&a)[E_], int E, int k) 
   else return any_nan<E_>(a) ? __builtin_nanf("") : select_rank<E_>(a, E, k);
 }
 
+// ---- the reduction over the members of one element (a pixel of the depth map, an element of an intrinsic-image target), written
+// once per place the members live in.  reduction 0: the lower-middle median (torch.median) and, where asked for, the median
+// absolute deviation about it; 1: the mean and the unbiased standard deviation (torch.std).  The members are added in index order,
+// every operation is rounded on its own (this file is built without FMA contraction), and a NaN member makes every statistic NaN.
+// Every kernel below that reduces over members calls one of the two functions, so a correction is made here and nowhere else.
+
+// The members in registers: a[0 .. E) of E_ (entries past E are numbers: the callers store 0).
+template <int E_>
+__device__ __forceinline__ void reduce_members(const float (&a)[E_], int E, int reduction, bool want_unc, float& pred, float& unc) {
+  const int k = (E - 1) >> 1;   // torch.median: lower middle
+  unc = 0.f;
+  if (reduction == 0) {
+    pred = select_kth<E_>(a, E, k);
+    if (want_unc) {
+      float dv[E_];
+#pragma unroll
+      for (int e = 0; e < E_; ++e) dv[e] = fabsf(__fsub_rn(a[e], pred));
+      unc = select_kth<E_>(dv, E, k);
+    }
+  } else {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E_; ++e)
+      if (e < E) s += a[e];
+    pred = s / (float)E;
+    if (want_unc) {
+      float q = 0.f;
+#pragma unroll
+      for (int e = 0; e < E_; ++e)
+        if (e < E) { const float dd = a[e] - pred; q += dd * dd; }
+      unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));   // torch.std: unbiased
+    }
+  }
+}
+
+// The members behind an accessor - more of them than a thread keeps in registers: member(e) reads member e of the element from LDS
+// or from memory (cache-resident after the first pass), as often as the selection asks for it.  The deviations |member - centre| of
+// the second selection are formed on the fly (a second array would fit neither place).
+// Element of rank k by counting ranks, ties broken by the member index (as select_rank): O(E^2).  torch.median: a NaN member makes
+// the statistic NaN, and the count would not (its < and == are false on a NaN), so a flag stands beside it.
+template <class Member>
+__device__ __forceinline__ float select_by_rank(const Member& member, int E, int k, bool dev, float centre) {
+  auto val = [&](int e) { const float x = member(e); return dev ? fabsf(__fsub_rn(x, centre)) : x; };
+  float res = val(0);
+  bool nan = false;
+  for (int e = 0; e < E; ++e) {
+    const float ve = val(e);
+    nan |= ve != ve;
+    int rank = 0;
+    for (int j = 0; j < E; ++j) {
+      const float vj = val(j);
+      rank += (vj < ve) || (vj == ve && j < e);
+    }
+    if (rank == k) res = ve;
+  }
+  return nan ? __builtin_nanf("") : res;
+}
+// The same element by a bitwise selection: 32 counting passes over the E values (monotone float -> uint32 key, most significant bit
+// first), O(32 E) instead of O(E^2).  The VALUE of rank k does not depend on how ties are broken, and its sign comes out of the key
+// (where the statistic falls among zeros of both signs: -0 sorts before +0).  A NaN would sort past +-inf as a key: a pass of its
+// own looks for one first.
+template <class Member>
+__device__ __forceinline__ float select_by_bits(const Member& member, int E, int k, bool dev, float centre) {
+  auto val = [&](int e) { const float x = member(e); return dev ? fabsf(__fsub_rn(x, centre)) : x; };
+  auto key_of = [](float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
+  auto val_of = [](unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); };
+  bool nan = false;
+  for (int e = 0; e < E; ++e) {
+    const float v = val(e);
+    nan |= v != v;
+  }
+  unsigned prefix = 0;
+  int kk = k;
+  for (int bit = 31; bit >= 0; --bit) {
+    const unsigned hi_mask = bit == 31 ? 0u : ~((2u << bit) - 1u);   // the bits already decided
+    int cnt0 = 0;
+    for (int e = 0; e < E; ++e) {
+      const unsigned key = key_of(val(e));
+      cnt0 += ((key & hi_mask) == prefix && !((key >> bit) & 1u)) ? 1 : 0;
+    }
+    if (kk >= cnt0) { kk -= cnt0; prefix |= 1u << bit; }
+  }
+  return nan ? __builtin_nanf("") : val_of(prefix);
+}
+// by_rank: which of the two selections (the callers' choice by E; both give the same value)
+template <class Member>
+__device__ __forceinline__ void reduce_members_mem(const Member& member, int E, bool by_rank, int reduction, bool want_unc, float& pred,
+                                                   float& unc) {
+  const int k = (E - 1) >> 1;   // torch.median: lower middle
+  auto select = [&](bool dev, float centre) {
+    return by_rank ? select_by_rank(member, E, k, dev, centre) : select_by_bits(member, E, k, dev, centre);
+  };
+  unc = 0.f;
+  if (reduction == 0) {
+    pred = select(false, 0.f);
+    if (want_unc) unc = select(true, pred);
+  } else {
+    float s = 0.f;
+    for (int e = 0; e < E; ++e) s += member(e);
+    pred = s / (float)E;
+    if (want_unc) {
+      float q = 0.f;
+      for (int e = 0; e < E; ++e) { const float dd = member(e) - pred; q += dd * dd; }
+      unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));   // torch.std: unbiased
+    }
+  }
+}
+
+// ---- the running (value, pixel) extrema of a map: (min, its pixel, max, its pixel), merged under one of two orders
+struct NumberOrder {   // numbers only (no NaN among the candidates): ties go to the lowest pixel
+  static __device__ __forceinline__ bool min(float o, long long op, float m, long long p) { return o < m || (o == m && op < p); }
+  static __device__ __forceinline__ bool max(float o, long long op, float m, long long p) { return o > m || (o == m && op < p); }
+};
+struct NanFirstOrder {   // a NaN beats every number (common.h: takes_min / takes_max)
+  static __device__ __forceinline__ bool min(float o, long long op, float m, long long p) { return takes_min(o, op, m, p); }
+  static __device__ __forceinline__ bool max(float o, long long op, float m, long long p) { return takes_max(o, op, m, p); }
+};
+// the extrema of a wave's 64 lanes, in every lane
+template <class Order>
+__device__ __forceinline__ void wave_extrema(float& mn_io, float& mx_io, long long& pmn_io, long long& pmx_io) {
+  // (on copies: the conditional assignments below are selects on registers, not branches around stores through a reference)
+  float mn = mn_io, mx = mx_io;
+  long long pmn = pmn_io, pmx = pmx_io;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
+    const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
+    if (Order::min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
+    if (Order::max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
+  }
+  mn_io = mn; mx_io = mx; pmn_io = pmn; pmx_io = pmx;
+}
+// The tail of the three median kernels (256 threads; every thread calls it): the block's extrema - wave shuffle, four-wave merge in
+// LDS - into its row of the per-block tables that minmax_final_kernel scans.
+__device__ __forceinline__ void store_block_extrema(float mn, float mx, long long pmn, long long pmx, float* __restrict__ blockmm,
+                                                    long long* __restrict__ blockpx) {
+  __shared__ float red[8];
+  __shared__ long long redp[8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_extrema<NanFirstOrder>(mn, mx, pmn, pmx);
+  if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
+      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
+    }
+    blockmm[2 * blockIdx.x] = red[0];
+    blockmm[2 * blockIdx.x + 1] = red[4];
+    blockpx[2 * blockIdx.x] = redp[0];
+    blockpx[2 * blockIdx.x + 1] = redp[4];
+  }
+}
+
 // E_ = compile-time upper bound of E (registers); st = [s[E], t[E]] fp32; reduction 0 median 1 mean
 template <int E_>
 __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restrict__ d, const float* __restrict__ st,
@@ -182,8 +342,6 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
                                                            float* __restrict__ blockmm, long long* __restrict__ blockpx,
                                                            int E, long long HW,
                                                            int reduction, int has_shift, int aligned) {
-  __shared__ float red[8];
-  __shared__ long long redp[8];
   long long pmn = 0, pmx = 0;
   float sc[E_], sh[E_];
 #pragma unroll
@@ -195,35 +353,12 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
     asm volatile("" : "+v"(sc[e]), "+v"(sh[e]));
   }
   float mn = __builtin_inff(), mx = -__builtin_inff();
-  const int k = (E - 1) >> 1;  // torch.median: lower middle
   auto pixel = [&](const float (&raw)[E_], long long p, float& pred, float& unc) {
     float a[E_];
 #pragma unroll
     for (int e = 0; e < E_; ++e)   // reference: depth * s + t as two separately rounded fp32 ops (ensemble.py:112)
       a[e] = e < E ? (aligned ? __fadd_rn(__fmul_rn(raw[e], sc[e]), sh[e]) : raw[e]) : 0.f;
-    unc = 0.f;
-    if (reduction == 0) {
-      pred = select_kth<E_>(a, E, k);
-      if (mad) {
-        float dv[E_];
-#pragma unroll
-        for (int e = 0; e < E_; ++e) dv[e] = fabsf(__fsub_rn(a[e], pred));
-        unc = select_kth<E_>(dv, E, k);
-      }
-    } else {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < E_; ++e)
-        if (e < E) s += a[e];
-      pred = s / (float)E;
-      if (mad) {
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < E_; ++e)
-          if (e < E) { const float dd = a[e] - pred; q += dd * dd; }
-        unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));  // torch.std: unbiased
-      }
-    }
+    reduce_members<E_>(a, E, reduction, mad != nullptr, pred, unc);
     if (pred < mn) { mn = pred; pmn = p; }
     if (pred > mx) { mx = pred; pmx = p; }
   };
@@ -263,26 +398,7 @@ __global__ __launch_bounds__(256) void depth_median_kernel(const float* __restri
     if (mad) mad[p] = unc;
   }
   if (nan_acc != nan_acc) { mn = mx = nan_acc; pmn = pmx = 0; }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-    const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
-    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
-  }
-  if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
-    }
-    blockmm[2 * blockIdx.x] = red[0];
-    blockmm[2 * blockIdx.x + 1] = red[4];
-    blockpx[2 * blockIdx.x] = redp[0];
-    blockpx[2 * blockIdx.x + 1] = redp[4];
-  }
+  store_block_extrema(mn, mx, pmn, pmx, blockmm, blockpx);
 }
 
 // 33 ... 128 members: the aligned values of a pixel live in LDS ([member][thread]: conflict-free), the lower-middle order
@@ -293,8 +409,6 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
                                                                float* __restrict__ blockmm, long long* __restrict__ blockpx,
                                                                int E, long long HW, int reduction, int has_shift, int aligned) {
   extern __shared__ float lds_a[];   // [E][256] aligned values (128 KB at E = 128), then [2 E] scale / shift
-  __shared__ float red[8];
-  __shared__ long long redp[8];
   const int tid = threadIdx.x;
   float* a = lds_a + tid;
   float* sc = lds_a + (long long)E * 256;
@@ -305,45 +419,15 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
   __syncthreads();
   long long pmn = 0, pmx = 0;
   float mn = __builtin_inff(), mx = -__builtin_inff();
-  const int k = (E - 1) >> 1;
   bool saw_nan = false;
-  // element of rank k (ties by member index), as select_rank; DEV: of the absolute deviations |a - centre| (formed on the
-  // fly: a second [E][256] array would not fit the 160 KB of LDS)
-  auto select = [&](bool dev_, float centre) {
-    auto val = [&](int e) { const float x = a[e * 256]; return dev_ ? fabsf(__fsub_rn(x, centre)) : x; };
-    float res = val(0);
-    bool nan = false;   // torch.median: a NaN member makes the statistic NaN
-    for (int e = 0; e < E; ++e) {
-      const float ve = val(e);
-      nan |= ve != ve;
-      int rank = 0;
-      for (int j = 0; j < E; ++j) {
-        const float vj = val(j);
-        rank += (vj < ve) || (vj == ve && j < e);
-      }
-      if (rank == k) res = ve;
-    }
-    return nan ? __builtin_nanf("") : res;
-  };
+  auto member = [&](int e) { return a[e * 256]; };
   for (long long p = (long long)blockIdx.x * 256 + tid; p < HW; p += (long long)gridDim.x * 256) {
     for (int e = 0; e < E; ++e) {
       const float v = d[(long long)e * HW + p];
       a[e * 256] = aligned ? __fadd_rn(__fmul_rn(v, sc[e]), sc[E + e]) : v;
     }
-    float pred, unc = 0.f;
-    if (reduction == 0) {
-      pred = select(false, 0.f);
-      if (mad) unc = select(true, pred);
-    } else {
-      float s = 0.f;
-      for (int e = 0; e < E; ++e) s += a[e * 256];
-      pred = s / (float)E;
-      if (mad) {
-        float q = 0.f;
-        for (int e = 0; e < E; ++e) { const float dd = a[e * 256] - pred; q += dd * dd; }
-        unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));
-      }
-    }
+    float pred, unc;
+    reduce_members_mem(member, E, true, reduction, mad != nullptr, pred, unc);
     if (med) med[p] = pred;
     if (mad) mad[p] = unc;
     if (pred < mn) { mn = pred; pmn = p; }
@@ -351,85 +435,27 @@ __global__ __launch_bounds__(256) void depth_median_lds_kernel(const float* __re
     saw_nan |= pred != pred;   // NaN extrema, pixel 0: as depth_median_kernel
   }
   if (saw_nan) { mn = mx = __builtin_nanf(""); pmn = pmx = 0; }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-    const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
-    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
-  }
-  if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
-    }
-    blockmm[2 * blockIdx.x] = red[0];
-    blockmm[2 * blockIdx.x + 1] = red[4];
-    blockpx[2 * blockIdx.x] = redp[0];
-    blockpx[2 * blockIdx.x + 1] = redp[4];
-  }
+  store_block_extrema(mn, mx, pmn, pmx, blockmm, blockpx);
 }
 
-// More than 128 members (the reference takes any ensemble size, marigold/util/ensemble.py:39-49): the order statistic of a pixel
-// is found by a bitwise selection over the members' values read straight from memory - 32 counting passes over E values per pixel
-// (monotone float -> uint32 key, most significant bit first), O(32 E) instead of the rank count's O(E^2), no per-pixel storage.
-// Same semantics and outputs as depth_median_kernel: the VALUE of rank (E - 1) / 2 does not depend on how ties are broken.
+// More than 128 members (the reference takes any ensemble size, marigold/util/ensemble.py:39-49): the members' values are read
+// straight from memory and aligned at every read, the order statistic is found by the bitwise selection - no per-pixel storage.
+// Same semantics and outputs as depth_median_kernel.
 __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __restrict__ d, const float* __restrict__ st,
                                                                float* __restrict__ med, float* __restrict__ mad,
                                                                float* __restrict__ blockmm, long long* __restrict__ blockpx,
                                                                int E, long long HW, int reduction, int has_shift, int aligned) {
-  __shared__ float red[8];
-  __shared__ long long redp[8];
   const int tid = threadIdx.x;
   long long pmn = 0, pmx = 0;
   float mn = __builtin_inff(), mx = -__builtin_inff();
-  const int k = (E - 1) >> 1;
   bool saw_nan = false;
-  auto key_of = [](float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
-  auto val_of = [](unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); };
   for (long long p = (long long)blockIdx.x * 256 + tid; p < HW; p += (long long)gridDim.x * 256) {
-    auto aval = [&](int e) {   // reference: depth * s + t as two separately rounded fp32 ops (ensemble.py:112)
+    auto member = [&](int e) {   // reference: depth * s + t as two separately rounded fp32 ops (ensemble.py:112)
       const float v = d[(long long)e * HW + p];
       return aligned ? __fadd_rn(__fmul_rn(v, st[e]), has_shift ? st[E + e] : 0.f) : v;
     };
-    auto select = [&](bool dev_, float centre) {
-      unsigned prefix = 0;
-      int kk = k;
-      bool nan = false;   // torch.median: a NaN member makes the statistic NaN (as a key it would sort past +-inf)
-      for (int e = 0; e < E; ++e) {
-        const float x = aval(e);
-        const float v = dev_ ? fabsf(__fsub_rn(x, centre)) : x;
-        nan |= v != v;
-      }
-      for (int bit = 31; bit >= 0; --bit) {
-        const unsigned hi_mask = bit == 31 ? 0u : ~((2u << bit) - 1u);   // the bits already decided
-        int cnt0 = 0;
-        for (int e = 0; e < E; ++e) {
-          const float x = aval(e);
-          const unsigned key = key_of(dev_ ? fabsf(__fsub_rn(x, centre)) : x);
-          cnt0 += ((key & hi_mask) == prefix && !((key >> bit) & 1u)) ? 1 : 0;
-        }
-        if (kk >= cnt0) { kk -= cnt0; prefix |= 1u << bit; }
-      }
-      return nan ? __builtin_nanf("") : val_of(prefix);
-    };
-    float pred, unc = 0.f;
-    if (reduction == 0) {
-      pred = select(false, 0.f);
-      if (mad) unc = select(true, pred);
-    } else {
-      float s = 0.f;
-      for (int e = 0; e < E; ++e) s += aval(e);
-      pred = s / (float)E;
-      if (mad) {
-        float q = 0.f;
-        for (int e = 0; e < E; ++e) { const float dd = aval(e) - pred; q += dd * dd; }
-        unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));
-      }
-    }
+    float pred, unc;
+    reduce_members_mem(member, E, false, reduction, mad != nullptr, pred, unc);
     if (med) med[p] = pred;
     if (mad) mad[p] = unc;
     if (pred < mn) { mn = pred; pmn = p; }
@@ -437,26 +463,7 @@ __global__ __launch_bounds__(256) void depth_median_big_kernel(const float* __re
     saw_nan |= pred != pred;   // NaN extrema, pixel 0: as depth_median_kernel
   }
   if (saw_nan) { mn = mx = __builtin_nanf(""); pmn = pmx = 0; }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-    const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-    if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
-    if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
-  }
-  if (lane == 0) { red[wave] = mn; red[4 + wave] = mx; redp[wave] = pmn; redp[4 + wave] = pmx; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      if (takes_min(red[w], redp[w], red[0], redp[0])) { red[0] = red[w]; redp[0] = redp[w]; }
-      if (takes_max(red[4 + w], redp[4 + w], red[4], redp[4])) { red[4] = red[4 + w]; redp[4] = redp[4 + w]; }
-    }
-    blockmm[2 * blockIdx.x] = red[0];
-    blockmm[2 * blockIdx.x + 1] = red[4];
-    blockpx[2 * blockIdx.x] = redp[0];
-    blockpx[2 * blockIdx.x + 1] = redp[4];
-  }
+  store_block_extrema(mn, mx, pmn, pmx, blockmm, blockpx);
 }
 
 // out = [min, max, d[0..E)[argmin px], d[0..E)[argmax px]]  (raw member values at the extremal
@@ -468,40 +475,26 @@ __global__ __launch_bounds__(64) void minmax_final_kernel(const float* __restric
   __shared__ long long px[2];
   // one wave: strided scan of the per-block results, then a lane reduction (ties -> lowest pixel)
   const int lane = threadIdx.x;
-  float mn = __builtin_inff(), mx = -__builtin_inff();
-  long long pmn = 0x7fffffffffffffffll, pmx = 0x7fffffffffffffffll;
-  bool nan = false;
-  for (int i = lane; i < nblk; i += 64) {
-    const float a = blockmm[2 * i], b = blockmm[2 * i + 1];
-    const long long pa = blockpx[2 * i], pb = blockpx[2 * i + 1];
-    nan |= __builtin_isunordered(a, b);
-    if (a < mn || (a == mn && pa < pmn)) { mn = a; pmn = pa; }
-    if (b > mx || (b == mx && pb < pmx)) { mx = b; pmx = pb; }
-  }
-  if (__any(nan)) {   // a block saw a NaN prediction: the scan again in the order that puts a NaN first (wave-uniform, rarely taken)
+  float mn, mx;
+  long long pmn, pmx;
+  auto scan = [&](auto order) {   // -> whether a block reported a NaN
     mn = __builtin_inff(); mx = -__builtin_inff();
     pmn = pmx = 0x7fffffffffffffffll;
+    bool nan = false;
     for (int i = lane; i < nblk; i += 64) {
       const float a = blockmm[2 * i], b = blockmm[2 * i + 1];
       const long long pa = blockpx[2 * i], pb = blockpx[2 * i + 1];
-      if (takes_min(a, pa, mn, pmn)) { mn = a; pmn = pa; }
-      if (takes_max(b, pb, mx, pmx)) { mx = b; pmx = pb; }
+      nan |= __builtin_isunordered(a, b);
+      if (order.min(a, pa, mn, pmn)) { mn = a; pmn = pa; }
+      if (order.max(b, pb, mx, pmx)) { mx = b; pmx = pb; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-      const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-      if (takes_min(omn, opmn, mn, pmn)) { mn = omn; pmn = opmn; }
-      if (takes_max(omx, opmx, mx, pmx)) { mx = omx; pmx = opmx; }
-    }
+    return nan;
+  };
+  if (__any(scan(NumberOrder()))) {   // a block saw a NaN prediction: the scan again in the order that puts a NaN first (wave-uniform, rarely taken)
+    scan(NanFirstOrder());
+    wave_extrema<NanFirstOrder>(mn, mx, pmn, pmx);
   } else {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float omn = __shfl_xor(mn, o), omx = __shfl_xor(mx, o);
-      const long long opmn = __shfl_xor(pmn, o), opmx = __shfl_xor(pmx, o);
-      if (omn < mn || (omn == mn && opmn < pmn)) { mn = omn; pmn = opmn; }
-      if (omx > mx || (omx == mx && opmx < pmx)) { mx = omx; pmx = opmx; }
-    }
+    wave_extrema<NumberOrder>(mn, mx, pmn, pmx);
   }
   if (lane == 0) {
     out[0] = mn; out[1] = mx;
@@ -558,36 +551,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
 
 // ---- MG_OP_ENS_IID: ensemble_iid (marigold/util/ensemble.py:252-270) - the reduction over the members of every element on its own.
 // It is depth_median_kernel's `pixel` without the alignment and without the extrema: no min / max table, no scratch, nothing shared
-// between lanes.  The arithmetic is restated operation for operation - the same selection functions on the same padded arrays, the
-// members added in the same order, the same separately rounded operations (this file is built without FMA contraction) - and not
-// shared with that kernel, whose register allocation (it runs ~100 times per depth map) stays what it was measured with.
-template <int E_>
-__device__ __forceinline__ void iid_reduce(const float (&a)[E_], int E, int reduction, bool want_unc, float& pred, float& unc) {
-  const int k = (E - 1) >> 1;   // torch.median: lower middle
-  unc = 0.f;
-  if (reduction == 0) {
-    pred = select_kth<E_>(a, E, k);
-    if (want_unc) {
-      float dv[E_];
-#pragma unroll
-      for (int e = 0; e < E_; ++e) dv[e] = fabsf(__fsub_rn(a[e], pred));
-      unc = select_kth<E_>(dv, E, k);
-    }
-  } else {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < E_; ++e)
-      if (e < E) s += a[e];
-    pred = s / (float)E;
-    if (want_unc) {
-      float q = 0.f;
-#pragma unroll
-      for (int e = 0; e < E_; ++e)
-        if (e < E) { const float dd = a[e] - pred; q += dd * dd; }
-      unc = sqrtf(q / (float)(E > 1 ? E - 1 : 1));   // torch.std: unbiased
-    }
-  }
-}
+// between lanes - and the same reduce_members / reduce_members_mem on the same padded arrays, so the two ops cannot drift apart.
 
 // E <= E_ <= EMAX members in registers (the bound of depth_median_kernel's register-resident selection).  vec: a lane owns four
 // neighbouring elements - one 16-byte load per member, one 16-byte store per output (n % 4 == 0 and all pointers 16-byte aligned:
@@ -606,7 +570,7 @@ __global__ __launch_bounds__(256) void iid_kernel(const float* __restrict__ d, f
         float a[E_];
 #pragma unroll
         for (int e = 0; e < E_; ++e) a[e] = i == 0 ? v[e].x : (i == 1 ? v[e].y : (i == 2 ? v[e].z : v[e].w));
-        iid_reduce<E_>(a, E, reduction, unc != nullptr, pr[i], un[i]);
+        reduce_members<E_>(a, E, reduction, unc != nullptr, pr[i], un[i]);
       }
       *(float4*)(pred + p) = make_float4(pr[0], pr[1], pr[2], pr[3]);
       if (unc) *(float4*)(unc + p) = make_float4(un[0], un[1], un[2], un[3]);
@@ -617,79 +581,36 @@ __global__ __launch_bounds__(256) void iid_kernel(const float* __restrict__ d, f
 #pragma unroll
       for (int e = 0; e < E_; ++e) a[e] = e < E ? d[(long long)e * n + p] : 0.f;
       float pr, un;
-      iid_reduce<E_>(a, E, reduction, unc != nullptr, pr, un);
+      reduce_members<E_>(a, E, reduction, unc != nullptr, pr, un);
       pred[p] = pr;
       if (unc) unc[p] = un;
     }
   }
 }
 
-// More than EMAX members: one element per lane, the members read from memory (cache-resident after the first pass) wherever the
-// register-resident kernel reads its array.  The order statistic as the kernels the depth op runs at these sizes find it: up to
-// EMAX_LDS members by counting ranks with ties broken by the member index (depth_median_lds_kernel), beyond by the bitwise selection
-// of depth_median_big_kernel - the same values, and the same sign where the statistic falls among zeros of both signs.
+// More than EMAX members: one element per lane, the members read from memory wherever the register-resident kernel reads its
+// array.  The order statistic as the kernels the depth op runs at these sizes find it: up to EMAX_LDS members by counting ranks
+// (depth_median_lds_kernel), beyond by the bitwise selection (depth_median_big_kernel).
 __global__ __launch_bounds__(256) void iid_mem_kernel(const float* __restrict__ d, float* __restrict__ pred, float* __restrict__ unc, int E,
                                                       long long n, int reduction) {
-  const int k = (E - 1) >> 1;
-  const bool by_rank = E <= EMAX_LDS;
-  auto key_of = [](float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); };
-  auto val_of = [](unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); };
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
-    auto val = [&](int e, bool dev_, float centre) {
-      const float x = d[(long long)e * n + p];
-      return dev_ ? fabsf(__fsub_rn(x, centre)) : x;
-    };
-    auto select = [&](bool dev_, float centre) {
-      bool nan = false;   // torch.median: a NaN member makes the statistic NaN
-      float res = val(0, dev_, centre);
-      if (by_rank) {
-        for (int e = 0; e < E; ++e) {
-          const float ve = val(e, dev_, centre);
-          nan |= ve != ve;
-          int rank = 0;
-          for (int j = 0; j < E; ++j) {
-            const float vj = val(j, dev_, centre);
-            rank += (vj < ve) || (vj == ve && j < e);
-          }
-          if (rank == k) res = ve;
-        }
-      } else {
-        for (int e = 0; e < E; ++e) {
-          const float v = val(e, dev_, centre);
-          nan |= v != v;
-        }
-        unsigned prefix = 0;
-        int kk = k;
-        for (int bit = 31; bit >= 0; --bit) {
-          const unsigned hi_mask = bit == 31 ? 0u : ~((2u << bit) - 1u);   // the bits already decided
-          int cnt0 = 0;
-          for (int e = 0; e < E; ++e) {
-            const unsigned key = key_of(val(e, dev_, centre));
-            cnt0 += ((key & hi_mask) == prefix && !((key >> bit) & 1u)) ? 1 : 0;
-          }
-          if (kk >= cnt0) { kk -= cnt0; prefix |= 1u << bit; }
-        }
-        res = val_of(prefix);
-      }
-      return nan ? __builtin_nanf("") : res;
-    };
-    float pr, un = 0.f;
-    if (reduction == 0) {
-      pr = select(false, 0.f);
-      if (unc) un = select(true, pr);
-    } else {
-      float s = 0.f;
-      for (int e = 0; e < E; ++e) s += val(e, false, 0.f);
-      pr = s / (float)E;
-      if (unc) {
-        float q = 0.f;
-        for (int e = 0; e < E; ++e) { const float dd = val(e, false, 0.f) - pr; q += dd * dd; }
-        un = sqrtf(q / (float)(E - 1));
-      }
-    }
+    auto member = [&](int e) { return d[(long long)e * n + p]; };
+    float pr, un;
+    reduce_members_mem(member, E, E <= EMAX_LDS, reduction, unc != nullptr, pr, un);
     pred[p] = pr;
     if (unc) unc[p] = un;
   }
+}
+
+// The member bounds the register-resident kernels are instantiated at, for both ops: f(std::integral_constant<int, E_>) with the
+// smallest E_ >= E (E <= EMAX).  At E <= 10 the selection is the sorting network.
+template <class F>
+void with_member_bound(int E, F f) {
+  if (E <= 4) f(std::integral_constant<int, 4>());
+  else if (E <= 8) f(std::integral_constant<int, 8>());
+  else if (E <= 10) f(std::integral_constant<int, 10>());
+  else if (E <= 16) f(std::integral_constant<int, 16>());
+  else f(std::integral_constant<int, EMAX>());
 }
 
 template <int E_>
@@ -752,11 +673,9 @@ int mg_launch_ensemble(const mg_op* op, hipStream_t s) {
         const size_t lds = ((size_t)E * 256 + 2 * E) * sizeof(float);
         MG_KERNEL_MAX_LDS((const void*)depth_median_lds_kernel, (int)(((size_t)EMAX_LDS * 256 + 2 * EMAX_LDS) * sizeof(float)));
         MG_LAUNCH(depth_median_lds_kernel, dim3(nblk), dim3(256), lds, s, MEDIAN_KERNEL_ARGS(m));
-      } else if (E <= 4) launch_median<4>(m, nblk, s);
-      else if (E <= 8) launch_median<8>(m, nblk, s);
-      else if (E <= 10) launch_median<10>(m, nblk, s);
-      else if (E <= 16) launch_median<16>(m, nblk, s);
-      else launch_median<EMAX>(m, nblk, s);
+      } else {
+        with_member_bound(E, [&](auto bound) { launch_median<decltype(bound)::value>(m, nblk, s); });
+      }
       // (round 3: finishing the reduction in the median kernel's last-arriving block instead - fence + ticket per block - measured
       // SLOWER than this 5 us launch: 40-41 vs 34-36 us per pass, profiles/r3_ab_native_bfgs_alignment.log)
       MG_LAUNCH(minmax_final_kernel, dim3(1), dim3(64), 0, s, (const float*)m.blockmm, (const long long*)m.blockpx, m.d, m.minmax, nblk, E,
@@ -789,15 +708,12 @@ int mg_launch_ensemble(const mg_op* op, hipStream_t s) {
       MG_REQUIRE(reduction == 0 || reduction == 1, "ens_iid: Unrecognized reduction method: %d.", reduction);
       MG_REQUIRE(d && pred, "ens_iid: null pointer");
       MG_REQUIRE((((uintptr_t)d | (uintptr_t)pred | (uintptr_t)unc) & 3) == 0, "ens_iid: the members and the outputs must be 4-byte aligned");
-      // the register bounds are those MG_OP_ENS_DEPTH_MEDIAN instantiates: at E <= 10 the selection is the sorting network there too
       if (E > EMAX) {
         const int nblk = (int)min((n + 255) / 256, (long long)2048);
         MG_LAUNCH(iid_mem_kernel, dim3(nblk), dim3(256), 0, s, d, pred, unc, E, n, reduction);
-      } else if (E <= 4) launch_iid<4>(d, pred, unc, E, n, reduction, s);
-      else if (E <= 8) launch_iid<8>(d, pred, unc, E, n, reduction, s);
-      else if (E <= 10) launch_iid<10>(d, pred, unc, E, n, reduction, s);
-      else if (E <= 16) launch_iid<16>(d, pred, unc, E, n, reduction, s);
-      else launch_iid<EMAX>(d, pred, unc, E, n, reduction, s);
+      } else {
+        with_member_bound(E, [&](auto bound) { launch_iid<decltype(bound)::value>(d, pred, unc, E, n, reduction, s); });
+      }
       break;
     }
     default: MG_REQUIRE(false, "ensemble: bad op kind %d", op->kind);

@@ -77,9 +77,7 @@ struct mg_model {
   Prog enc, den, dec;
   void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W]), grown on demand
   uint64_t predict_tmp_bytes = 0;
-  void* iid_tmp = nullptr;           // mg_model_predict_iid's output temporaries (see iid_tmp_layout), grown on demand
-  uint64_t iid_tmp_bytes = 0;
-  void* out_tmp = nullptr;           // mg_model_predict_out's (see out_tmp_layout), grown on demand
+  void* out_tmp = nullptr;           // the one-call predictions' output temporaries (see out_tmp_layout), grown on demand
   uint64_t out_tmp_bytes = 0;
 };
 
@@ -227,7 +225,6 @@ void mg_model_destroy(mg_model* m) {
     if (p->prog) mg_program_destroy(p->prog);
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
-  if (m->iid_tmp) (void)hipFree(m->iid_tmp);
   if (m->out_tmp) (void)hipFree(m->out_tmp);
   delete m;
 }
@@ -238,7 +235,7 @@ int mg_model_info(const mg_model* m, int* cfg16) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->iid_tmp_bytes + m->out_tmp_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes) : 0; }
 
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
@@ -478,19 +475,80 @@ int predict_members(mg_model* m, const char* who, const uint8_t* rgb, int hwc, i
 
 namespace {
 
-// Stage 6 of a depth / normals prediction: the B members in the decoder's output slot -> the ensembled map in `dst` (one member: the
-// pipelines return it as it is, without an uncertainty - *final_pred is then the slot itself and nothing is stored).
-int ensemble_members(const float* preds, int B, int C, int post, int Ho, int Wo, const mg_predict_opts& o, float* dst, float* unc_out_or_null,
-                     double* info4_or_null, void* stream, const float** final_pred) {
+// out_h / out_w / out_mode of an entry point's options (0 x 0: the decoded size; max_pixels 0: no bound) -> the size to store
+int output_size(const char* who, int out_h, int out_w, int out_mode, long long max_pixels, int Ho, int Wo, int* oh, int* ow) {
+  MG_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0 && (!max_pixels || (long long)out_h * out_w <= max_pixels)),
+             "%s: bad output size %d x %d", who, out_h, out_w);
+  MG_REQUIRE(out_mode >= 0 && out_mode <= 2, "%s: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)", who);
+  *oh = out_h ? out_h : Ho;
+  *ow = out_w ? out_w : Wo;
+  return 0;
+}
+
+// The output temporaries of a one-call prediction, carved out of the model's out_tmp in this order (each part rounded up to 256
+// bytes): the ensembled map at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
+// [planes][Ho][out_w] (modes 0 / 1 when both sizes change), the picture stage's workspace (intrinsic images: [n][MG_IID_VIS_PARTS]
+// for a target that is linear and up to scale; depth and normals: none).
+struct OutTmp {
+  uint64_t ens = 0, rtmp = 0, ws = 0;
+  uint64_t total() const { return ens + rtmp + ws; }
+};
+OutTmp out_tmp_layout(int B, int planes, int Ho, int Wo, int oh, int ow, int out_mode, uint64_t ws_bytes) {
+  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
+  OutTmp t;
+  const bool resize = oh != Ho || ow != Wo;
+  if (resize && B > 1) t.ens = r256((uint64_t)planes * Ho * Wo * 4);
+  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)planes * Ho * ow * 4);
+  t.ws = r256(ws_bytes);
+  return t;
+}
+
+// Stages 1 to 7 of a one-call prediction: the members (predict_members), then
+// 6. ensemble(members, dst) -> int: the B members in the decoder's output slot -> the ensembled map (one member: the pipelines
+//    return it as it is, without an uncertainty, and `ensemble` is not called),
+// 7. match_input_res (marigold_depth_pipeline.py:306-312, marigold_normals_pipeline.py:282-288, marigold_iid_pipeline.py:378-385):
+//    the prediction only, [planes][Ho][Wo] -> pred_out [planes][oh][ow].
+// *ws (may be null): the picture workspace of ws_bytes, valid until the model's next prediction.
+template <class Ensemble>
+int predict_resized(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                    int planes, int oh, int ow, int out_mode, uint64_t ws_bytes, float* pred_out, float** ws, void* stream, Ensemble ensemble) {
+  const int B = (int)m->hdr.cfg[0], Ho = (int)m->hdr.cfg[11], Wo = (int)m->hdr.cfg[12];
+  const bool resize = oh != Ho || ow != Wo;
+  const OutTmp t = out_tmp_layout(B, planes, Ho, Wo, oh, ow, out_mode, ws_bytes);
+  if (int rc = grow_tmp(&m->out_tmp, &m->out_tmp_bytes, t.total())) return rc;
+  float* const ens = (float*)m->out_tmp;
+  float* const rtmp = t.rtmp ? (float*)((char*)m->out_tmp + t.ens) : nullptr;
+  if (ws) *ws = t.ws ? (float*)((char*)m->out_tmp + t.ens + t.rtmp) : nullptr;
+  const float* preds = nullptr;
+  if (int rc = predict_members(m, who, rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
+  const float* final_pred = preds;   // at the decoded size
+  if (B > 1) {
+    float* const dst = resize ? ens : pred_out;
+    if (int rc = ensemble(preds, dst)) return rc;
+    final_pred = dst;
+  }
+  if (resize) return mg_resize(final_pred, pred_out, rtmp, planes, Ho, Wo, oh, ow, out_mode, 0, stream);
+  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)planes * Ho * Wo * 4, (hipStream_t)stream);
+  return 0;
+}
+
+// Stages 1 to 7 of a depth / normals prediction
+int predict_depth_or_normals(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                             const mg_predict_opts* opts_or_null, int oh, int ow, int out_mode, float* pred_out, float* unc_out_or_null,
+                             double* info4_or_null, void* stream) {
+  const uint32_t* cfg = m->hdr.cfg;
+  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], Ho = (int)cfg[11], Wo = (int)cfg[12];
+  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
+  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
   if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
-  *final_pred = preds;
-  if (B == 1) return 0;
-  *final_pred = dst;
-  if (post == MG_POST_DEPTH)
-    return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
-                             o.max_res, dst, unc_out_or_null, info4_or_null, stream);
-  MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
-  return mg_ensemble_normals(preds, dst, unc_out_or_null, B, (int64_t)Ho * Wo, o.normals_reduction, stream);
+  return predict_resized(m, who, rgb, hwc, Hin, Win, mode, reciprocal, seed, C, oh, ow, out_mode, 0, pred_out, nullptr, stream,
+                         [&](const float* preds, float* dst) {
+                           if (post == MG_POST_DEPTH)
+                             return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength,
+                                                      o.max_iter, o.tol, o.max_res, dst, unc_out_or_null, info4_or_null, stream);
+                           MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
+                           return mg_ensemble_normals(preds, dst, unc_out_or_null, B, (int64_t)Ho * Wo, o.normals_reduction, stream);
+                         });
 }
 
 }  // namespace
@@ -500,37 +558,13 @@ extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hi
                                 void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
   const uint32_t* cfg = m->hdr.cfg;
-  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7];
-  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
   MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
-  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
-  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
-  const float *preds = nullptr, *final_pred = nullptr;
-  if (int rc = predict_members(m, "mg_model_predict", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
-  // 6. ensemble
-  if (int rc = ensemble_members(preds, B, C, post, Ho, Wo, o, pred_out, unc_out_or_null, info4_or_null, stream, &final_pred)) return rc;
-  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)C * Ho * Wo * 4, (hipStream_t)stream);
-  return 0;
+  // the map at the decoded size: no resize, no temporaries
+  return predict_depth_or_normals(m, "mg_model_predict", rgb, hwc, Hin, Win, mode, reciprocal, seed, opts_or_null, (int)cfg[11], (int)cfg[12], 0,
+                                  pred_out, unc_out_or_null, info4_or_null, stream);
 }
-
-namespace {
-// mg_model_predict_out's temporaries, carved out of the model's out_tmp in this order (each part rounded up to 256 bytes): the
-// ensembled map at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
-// [C][Ho][out_w] (modes 0 / 1 when both sizes change).
-struct OutTmp {
-  uint64_t ens = 0, rtmp = 0;
-  uint64_t total() const { return ens + rtmp; }
-};
-OutTmp out_tmp_layout(int B, int C, int Ho, int Wo, int oh, int ow, int out_mode) {
-  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
-  OutTmp t;
-  const bool resize = oh != Ho || ow != Wo;
-  if (resize && B > 1) t.ens = r256((uint64_t)C * Ho * Wo * 4);
-  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)C * Ho * ow * 4);
-  return t;
-}
-}  // namespace
 
 extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                     const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
@@ -539,64 +573,26 @@ extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, in
   MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_out: null argument (the model, the picture and pred_out are required)");
   MG_REQUIRE(!m->host_only, "mg_model_predict_out: a host-only model cannot predict (load it with device >= 0)");
   const uint32_t* cfg = m->hdr.cfg;
-  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7];
-  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
+  const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict_out: an intrinsic-image model goes through mg_model_predict_iid");
   const bool depth = post == MG_POST_DEPTH && C == 1;
   MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "mg_model_predict_out: a depth or a normals image is required");
-  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
   static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
-  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
   const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
-  MG_REQUIRE((q.out_h == 0 && q.out_w == 0) || (q.out_h > 0 && q.out_w > 0 && (long long)q.out_h * q.out_w <= (1ll << 30)),
-             "mg_model_predict_out: bad output size %d x %d", q.out_h, q.out_w);
-  MG_REQUIRE(q.out_mode >= 0 && q.out_mode <= 2, "mg_model_predict_out: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
+  int oh, ow;
+  if (int rc = output_size("mg_model_predict_out", q.out_h, q.out_w, q.out_mode, 1ll << 30, (int)cfg[11], (int)cfg[12], &oh, &ow)) return rc;
   if (depth) {
     MG_REQUIRE(!picture_out_or_null || q.lut256x3, "mg_model_predict_out: the picture of a depth model needs out_opts.lut256x3 (the colour table)");
   } else {
     MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "mg_model_predict_out: u16_out and lut256x3 belong to a depth model, this one predicts normals");
   }
-  const int oh = q.out_h ? q.out_h : Ho, ow = q.out_w ? q.out_w : Wo;
-  const bool resize = oh != Ho || ow != Wo;
-  const OutTmp t = out_tmp_layout(B, C, Ho, Wo, oh, ow, q.out_mode);
-  if (int rc = grow_tmp(&m->out_tmp, &m->out_tmp_bytes, t.total())) return rc;
-  float* const ens = (float*)m->out_tmp;
-  float* const rtmp = t.rtmp ? (float*)((char*)m->out_tmp + t.ens) : nullptr;
-  const float *preds = nullptr, *final_pred = nullptr;   // final_pred: at the decoded size
-  if (int rc = predict_members(m, "mg_model_predict_out", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
-  // 6. ensemble
-  if (int rc = ensemble_members(preds, B, C, post, Ho, Wo, o, resize ? ens : pred_out, unc_out_or_null, info4_or_null, stream, &final_pred))
+  if (int rc = predict_depth_or_normals(m, "mg_model_predict_out", rgb, hwc, Hin, Win, mode, reciprocal, seed, opts_or_null, oh, ow, q.out_mode,
+                                        pred_out, unc_out_or_null, info4_or_null, stream))
     return rc;
-  // 7. match_input_res (marigold_depth_pipeline.py:306-312, marigold_normals_pipeline.py:282-288): the prediction only
-  if (resize) {
-    if (int rc = mg_resize(final_pred, pred_out, rtmp, C, Ho, Wo, oh, ow, q.out_mode, 0, stream)) return rc;
-  } else if (B == 1) {
-    if (int rc = copy_dd(pred_out, preds, (uint64_t)C * Ho * Wo * 4, (hipStream_t)stream)) return rc;
-  }
   // 8. the output stage on what was stored, in place: the clip (:314-316 / :294), the 16-bit depth (script/depth/run.py), the picture
   if (depth) return mg_depth_visualize(pred_out, q.lut256x3, (int64_t)oh * ow, pred_out, u16_out_or_null, picture_out_or_null, stream);
   return mg_normals_finish(pred_out, oh, ow, pred_out, picture_out_or_null, stream);
 }
-
-namespace {
-// mg_model_predict_iid's temporaries, carved out of the model's iid_tmp in this order (each part rounded up to 256 bytes):
-// the ensembled prediction at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
-// [planes][Ho][out_w] (modes 0 / 1 when both sizes change), the picture stage's workspace [n][MG_IID_VIS_PARTS] (a target that is
-// linear and up to scale).
-struct IidTmp {
-  uint64_t ens = 0, rtmp = 0, ws = 0;
-  uint64_t total() const { return ens + rtmp + ws; }
-};
-IidTmp iid_tmp_layout(int B, int n, int Ho, int Wo, int oh, int ow, int out_mode, bool pictures, int linear_bits, int up_to_scale_bits) {
-  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
-  IidTmp t;
-  const bool resize = oh != Ho || ow != Wo;
-  if (resize && B > 1) t.ens = r256((uint64_t)3 * n * Ho * Wo * 4);
-  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)3 * n * Ho * ow * 4);
-  if (pictures && (linear_bits & up_to_scale_bits)) t.ws = r256((uint64_t)n * MG_IID_VIS_PARTS * 4);
-  return t;
-}
-}  // namespace
 
 extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                     const mg_iid_opts* opts_or_null, float* pred_out, float* unc_out_or_null, uint8_t* pictures_out_or_null,
@@ -612,33 +608,17 @@ extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, in
   static const mg_iid_opts defaults = MG_IID_OPTS_DEFAULT;
   const mg_iid_opts& o = opts_or_null ? *opts_or_null : defaults;
   MG_REQUIRE(o.reduction == 0 || o.reduction == 1, "mg_model_predict_iid: Unrecognized reduction method: %d.", o.reduction);
-  MG_REQUIRE((o.out_h == 0 && o.out_w == 0) || (o.out_h > 0 && o.out_w > 0), "mg_model_predict_iid: bad output size %d x %d", o.out_h, o.out_w);
-  MG_REQUIRE(o.out_mode >= 0 && o.out_mode <= 2, "mg_model_predict_iid: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)");
+  int oh, ow;
+  if (int rc = output_size("mg_model_predict_iid", o.out_h, o.out_w, o.out_mode, 0, Ho, Wo, &oh, &ow)) return rc;
   MG_REQUIRE(n <= 16 && !((unsigned)(o.linear_bits | o.up_to_scale_bits) >> n), "mg_model_predict_iid: a flag names a target beyond the %d of the model (at most 16)", n);
-  const int oh = o.out_h ? o.out_h : Ho, ow = o.out_w ? o.out_w : Wo;
-  const bool resize = oh != Ho || ow != Wo;
-  const hipStream_t s = (hipStream_t)stream;
-  const IidTmp t = iid_tmp_layout(B, n, Ho, Wo, oh, ow, o.out_mode, pictures_out_or_null != nullptr, o.linear_bits, o.up_to_scale_bits);
-  if (int rc = grow_tmp(&m->iid_tmp, &m->iid_tmp_bytes, t.total())) return rc;
-  float* const ens = (float*)m->iid_tmp;
-  float* const rtmp = t.rtmp ? (float*)((char*)m->iid_tmp + t.ens) : nullptr;
-  float* const ws = t.ws ? (float*)((char*)m->iid_tmp + t.ens + t.rtmp) : nullptr;
-  const float* preds = nullptr;
-  if (int rc = predict_members(m, "mg_model_predict_iid", rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
-  // 6. ensemble (ensemble_iid, :369-375; one member: the pipeline returns it as it is, without an uncertainty)
-  const int64_t n_el = (int64_t)C * Ho * Wo;
-  const float* final_pred = preds;   // at the decoded size
-  if (B > 1) {
-    float* dst = resize ? ens : pred_out;
-    if (int rc = mg_ensemble_iid(preds, B, n_el, o.reduction, dst, unc_out_or_null, stream)) return rc;
-    final_pred = dst;
-  }
-  // 7. match_input_res (:378-385): the prediction only
-  if (resize) {
-    if (int rc = mg_resize(final_pred, pred_out, rtmp, C, Ho, Wo, oh, ow, o.out_mode, 0, stream)) return rc;
-  } else if (B == 1) {
-    if (int rc = copy_dd(pred_out, preds, (uint64_t)n_el * 4, s)) return rc;
-  }
+  const uint64_t ws_bytes = pictures_out_or_null && (o.linear_bits & o.up_to_scale_bits) ? (uint64_t)n * MG_IID_VIS_PARTS * 4 : 0;
+  float* ws = nullptr;
+  // 6. the ensemble is ensemble_iid (:369-375)
+  if (int rc = predict_resized(m, "mg_model_predict_iid", rgb, hwc, Hin, Win, mode, reciprocal, seed, C, oh, ow, o.out_mode, ws_bytes, pred_out, &ws,
+                               stream, [&](const float* preds, float* dst) {
+                                 return mg_ensemble_iid(preds, B, (int64_t)C * Ho * Wo, o.reduction, dst, unc_out_or_null, stream);
+                               }))
+    return rc;
   // 8. the pictures of what was stored (fill_outputs -> MarigoldIIDOutput.fill_entry, :117-136, :393-411)
   if (pictures_out_or_null) return mg_iid_visualize(pred_out, pictures_out_or_null, ws, n, oh, ow, o.linear_bits, o.up_to_scale_bits, stream);
   return 0;
