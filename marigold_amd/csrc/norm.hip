@@ -13,9 +13,9 @@ constexpr int GN_NV = 4;  // channel vectors per thread: supports C <= 256*8*GN_
 // grid (chunks, B); block 256.  partials[b][slot][group][2] = (sum, sumsq) of the group's channels THAT THIS SOURCE HOLDS
 // over the chunk's rows, slot = source * chunks + chunk (a norm over the un-materialised concat of two tensors gets one
 // statistics launch per source; a group that straddles the two gets a contribution from each).
-// Threads are laid out txn (channel vectors) x tyn (row lanes); every thread keeps fp32 partials of its rows in
-// registers (4 rows in flight), the row lanes and then the channels of a group are combined through LDS in a FIXED
-// order - bit-reproducible, no floating-point atomics.
+// Threads are laid out txn (channel vectors) x tyn (row lanes); every thread sums its rows in batches of 8 (fp32 inside a batch,
+// fp64 across batches), the row lanes and then the channels of a group are combined through LDS (fp32 storage, fp64 sums) in a
+// FIXED order - bit-reproducible, no floating-point atomics.
 // With ss != nullptr the image's last block to arrive also reduces the table to scale / shift (no finalize launch).
 template <bool SC1>   // SC1: the table was written by other workgroups of this launch with sc1 stores - read it past the L1
 __device__ __forceinline__ void gn_finalize_image(const float* __restrict__ partials, const float* __restrict__ gamma,
@@ -94,27 +94,35 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
   const int rpc = (HW + chunks - 1) / chunks;
   const int r0 = chunk * rpc;
   const int r1 = min(HW, r0 + rpc);
-  float s[GN_NV][8], q[GN_NV][8];
-#pragma unroll
-  for (int v = 0; v < GN_NV; ++v)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[v][j] = q[v][j] = 0.f;
   const bool active = ty < tyn;
   if (active) {
     const bf16_t* xb = x + (long long)b * HW * C;
-    auto acc8 = [&](int v, const uint4& u) {
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a = bflo(w[j]), c = bfhi(w[j]);
-        s[v][2 * j] += a; q[v][2 * j] += a * a;
-        s[v][2 * j + 1] += c; q[v][2 * j + 1] += c * c;
-      }
-    };
 #pragma unroll
     for (int v = 0; v < GN_NV; ++v) {
       const int vc = tx + v * txn;
       if (vc >= cv) break;
+      // fp32 sums over one batch of <= 8 rows, every batch added to fp64 totals.  A chunk's rows are a chain of HW / (chunks tyn)
+      // fp32 additions per thread otherwise, and bf16 data with a mean of 64 sigma sits on a grid of 1/2: its squares are
+      // multiples of 1/4, so past 2^22 every addition of an odd one is a tie, round-to-even drops the 1/4 each time, and the
+      // variance comes out low (chunks = 1 at 96 x 96 x 320: by 10 %; tests/test_gpu_norm_conditioning.py).  A batch of 8 such
+      // squares stays below 2^19 - exact for bf16 operands, at most 8 roundings for fp16.
+      double sd[8], qd[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sd[j] = qd[j] = 0.0;
+      float s8[8], q8[8];
+      auto acc8 = [&](const uint4& u) {
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float a = bflo(w[j]), c = bfhi(w[j]);
+          s8[2 * j] += a; q8[2 * j] += a * a;
+          s8[2 * j + 1] += c; q8[2 * j + 1] += c * c;
+        }
+      };
+      auto flush = [&]() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { sd[j] += (double)s8[j]; qd[j] += (double)q8[j]; }
+      };
       const bf16_t* col = xb + vc * 8;
       int r = r0 + ty;
       for (; r + 7 * tyn < r1; r += 8 * tyn) {  // 8 independent 16-byte loads in flight
@@ -122,7 +130,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
 #pragma unroll
         for (int i = 0; i < 8; ++i) u[i] = *(const uint4*)(col + (long long)(r + i * tyn) * C);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc8(v, u[i]);
+        for (int j = 0; j < 8; ++j) s8[j] = q8[j] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc8(u[i]);
+        flush();
       }
       if (r < r1) {   // the tail as ONE batch (round 3): up to 7 loads in flight from clamped rows, zeroed past the chunk - as a
                       // loop of single loads it was up to 7 serial HBM round trips (of ~2 us) at the end of every workgroup
@@ -133,36 +144,34 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
           u[i] = *(const uint4*)(col + (long long)(ri < r1 ? ri : r1 - 1) * C);
         }
 #pragma unroll
+        for (int j = 0; j < 8; ++j) s8[j] = q8[j] = 0.f;
+#pragma unroll
         for (int i = 0; i < 7; ++i) {
           if (r + i * tyn >= r1) u[i] = make_uint4(0, 0, 0, 0);
-          acc8(v, u[i]);
+          acc8(u[i]);
         }
+        flush();
       }
-    }
+      float* d = lds + ((long long)ty * C + vc * 8) * 2;   // one rounding to fp32 per thread total
 #pragma unroll
-    for (int v = 0; v < GN_NV; ++v) {
-      const int vc = tx + v * txn;
-      if (vc < cv) {
-        float* d = lds + ((long long)ty * C + vc * 8) * 2;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { d[2 * j] = s[v][j]; d[2 * j + 1] = q[v][j]; }
-      }
+      for (int j = 0; j < 8; ++j) { d[2 * j] = (float)sd[j]; d[2 * j + 1] = (float)qd[j]; }
     }
   }
   __syncthreads();
   float* tot = lds + (long long)tyn * 2 * C;
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    float t = 0.f;
-    for (int y = 0; y < tyn; ++y) t += lds[(long long)y * 2 * C + i];
-    tot[i] = t;
+    double t = 0.0;
+    for (int y = 0; y < tyn; ++y) t += (double)lds[(long long)y * 2 * C + i];
+    tot[i] = (float)t;
   }
   __syncthreads();
   const int cpg = Ctot / groups;
   float* out = partials + (((long long)b * slots + slot0 + chunk) * groups) * 2;
   for (int g = threadIdx.x; g < groups; g += 256) {   // this source's share of every group (zero where it has none)
     const int lo = max(g * cpg, coff) - coff, hi = min((g + 1) * cpg, coff + C) - coff;
-    float sg = 0.f, qg = 0.f;
-    for (int c = lo; c < hi; ++c) { sg += tot[2 * c]; qg += tot[2 * c + 1]; }
+    double sgd = 0.0, qgd = 0.0;
+    for (int c = lo; c < hi; ++c) { sgd += (double)tot[2 * c]; qgd += (double)tot[2 * c + 1]; }
+    const float sg = (float)sgd, qg = (float)qgd;   // the table stays fp32: one rounding per (chunk, group)
     if (ss) {   // write-through (sc1) stores: visible at agent scope without a per-block L2 write-back fence
       __hip_atomic_store(&out[2 * g], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&out[2 * g + 1], qg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

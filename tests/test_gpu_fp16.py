@@ -30,6 +30,18 @@ def test_kernel_suite_on_fp16_operands():
     assert " passed" in tail
 
 
+def test_norm_conditioning_on_fp16_operands():
+    """tests/test_gpu_norm_conditioning.py the same way: the whole ladder (|mean| / sigma up to 64) is representable in fp16, whose
+    11-bit mantissas fill the fp32 partial sums that bf16's 8 bits leave nearly exact - nothing there is ``bf16_only``."""
+    env = dict(os.environ, MARIGOLD_TEST_OPERANDS="fp16")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_norm_conditioning.py"), "-m", "gpu", "-q",
+                        "-x", "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    tail = "\n".join(r.stdout.splitlines()[-25:])
+    print(tail)
+    assert r.returncode == 0, tail + r.stderr[-2000:]
+    assert " passed" in tail and " skipped" not in tail
+
+
 def _rel(got, ref):
     got, ref = got.detach().double().cpu(), torch.as_tensor(ref).double()
     return float(((got - ref) ** 2).mean().sqrt() / (ref ** 2).mean().sqrt())
