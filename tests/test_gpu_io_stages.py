@@ -12,6 +12,8 @@ Why bit equality is the bound, and against what.
 * Resampling: the passes are MG_OP_RESIZE's own kernel template, reading the same bytes (from HWC or CHW) and producing the same
   fp32 sums in the same order; the last pass applies the same rounding (and bicubic's clamp) and normalises the byte it would have
   stored.  The same operations in the same order: equality is derived, not measured.
+  That equality alone would be the template against itself, so the ``_resize_hip`` bytes of every case are in turn held against
+  torch on the CPU (``_resampled_reference``, by the rule of tests/resample_accept.py; docs/history/resample_ladder.md).
 * The normals picture: a clip that keeps NaN, two fp32 roundings, a truncation - numpy's element operations restated.  NaN has no
   defined uint8 value; the stage gives 0 (what x86-64 numpy leaves, MG_OP_IID_VIS's convention) and the test asserts that 0 by name.
 * Pipelines: the stage changes where the bits are computed, not the bits, so every array and picture of ``pipe(pil_image)`` equals
@@ -28,6 +30,8 @@ import pytest
 import torch
 from PIL import Image
 
+from tests import resample_accept as RA
+
 pytestmark = pytest.mark.gpu
 
 MODES = ("bilinear", "bicubic", "nearest-exact")
@@ -42,12 +46,12 @@ def libs():
     return {False: L.init(0), True: L.init(0, True)}
 
 
-def _picture(h, w, seed, kind="random"):
-    """uint8 [h, w, 3] on the host."""
+def _picture(h, w, seed, kind="random", coarse=1):
+    """uint8 [h, w, 3] on the host; ``coarse`` multiplies the checker's block size."""
     if kind == "ramp":      # every byte value, three times over at 16 x 16
         return (torch.arange(h * w * 3) % 256).to(torch.uint8).reshape(h, w, 3)
     if kind == "checker":   # saturated black / white blocks of 5 x 7 pixels: bicubic overshoots on both sides of every edge
-        yy, xx = torch.meshgrid(torch.arange(h) // 5, torch.arange(w) // 7, indexing="ij")
+        yy, xx = torch.meshgrid(torch.arange(h) // (5 * coarse), torch.arange(w) // (7 * coarse), indexing="ij")
         return (((yy + xx) % 2) * 255).to(torch.uint8)[:, :, None].expand(h, w, 3).contiguous()
     return torch.randint(0, 256, (h, w, 3), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
 
@@ -126,17 +130,28 @@ def test_rgb_prep_wrapper_same_size(libs):
 
 # ---- 2. MG_OP_RGB_PREP, resampling --------------------------------------------------------------------------------------------
 
-RESAMPLE = [((33, 47), (24, 34)), ((20, 31), (40, 62)), ((37, 64), (37, 32)), ((375, 1242), (231, 768))]
+# ((13, 17), (29, 11)): one axis shrinks and the other grows; ((756, 1008), (144, 192)): a 4032 x 3024 photo's 5.25 x down-size to 768,
+# a quarter of the size - 11 to 22 taps per output, read from 3-byte pixels in the hwc layout
+RESAMPLE = [((33, 47), (24, 34)), ((20, 31), (40, 62)), ((37, 64), (37, 32)), ((375, 1242), (231, 768)), ((13, 17), (29, 11)),
+            ((756, 1008), (144, 192))]
+ANCHOR = {mode: RA.Tally(f"rgb_prep anchor {mode}") for mode in MODES}   # `_resize_hip`'s bytes against torch on the CPU, per mode
 
 
 @functools.lru_cache(maxsize=None)
 def _resampled_reference(src_hw, dst_hw, mode, kind):
-    """(the picture [H,W,3] on the host, today's device chain up to fp32 on the device): computed once per case."""
+    """(the picture [H,W,3] on the host, today's device chain up to fp32 on the device): computed once per case.  The bytes of the
+    chain are themselves held against the host branch of ``resize`` (torch on the CPU) by the rule of tests/resample_accept.py, so
+    that equality with them is equality with torch's resampler and not only with the same kernel template; the share of differing
+    bytes is counted per mode in ``ANCHOR`` and asserted by ``test_resampled_reference_is_torchs``."""
     from marigold_amd.util.image_util import _resize_hip
-    hwc = _picture(src_hw[0], src_hw[1], src_hw[0] + src_hw[1], kind)
+    # (a strong down-size averages 5 x 7 blocks to grey: the blocks grow with it, so that edges stay edges and still saturate)
+    coarse = max(1, min(src_hw[0] // dst_hw[0], src_hw[1] // dst_hw[1]))
+    hwc = _picture(src_hw[0], src_hw[1], src_hw[0] + src_hw[1], kind, coarse)
     chw = hwc.permute(2, 0, 1).contiguous().cuda()
     res = _resize_hip(chw, dst_hw[0], dst_hw[1], mode)
     assert res.dtype == torch.uint8 and tuple(res.shape) == (3,) + dst_hw
+    x = chw.cpu()[None]
+    RA.accept(res.cpu()[None], RA.host_resize(x, dst_hw, mode), x, dst_hw, mode, ANCHOR[mode], (src_hw, dst_hw, mode, kind))
     return hwc, res, res / 255.0 * 2.0 - 1.0
 
 
@@ -157,6 +172,17 @@ def test_rgb_prep_resampled(libs, build, mode, case):
             assert torch.equal(got, want), (layout, kind)
             got = _prep(libs, f16, dtype, src, layout == "hwc", dst_hw, mode, reciprocal=False)   # the same bytes, the host's rounding
             assert torch.equal(got.cpu(), want_host), (layout, kind, "division")
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_resampled_reference_is_torchs(mode):
+    """Every reference of ``test_rgb_prep_resampled`` is, byte for byte up to ties, what torch computes on the CPU (checked where each
+    is made); here: over all of a mode's cases fewer than 2e-3 of the bytes differ."""
+    for src_hw, dst_hw in RESAMPLE:
+        for kind in ("random", "checker") if mode == "bicubic" else ("random",):
+            _resampled_reference(src_hw, dst_hw, mode, kind)
+    assert mode == "nearest-exact" or ANCHOR[mode].outputs >= 3 * sum(h * w for _, (h, w) in RESAMPLE)
+    ANCHOR[mode].close()
 
 
 def test_rgb_prep_wrapper_resampled(libs):
