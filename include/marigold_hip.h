@@ -1026,6 +1026,27 @@ enum { MG_IID_GAMMA_NONE = 0, MG_IID_GAMMA_2_2 = 1, MG_IID_GAMMA_INV_2_2 = 2, MG
 enum { MG_IID_PSNR = 1, MG_IID_SSIM = 2 };
 int mg_eval_iid(const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W, int up_to_scale, int gamma_mode,
                 int metrics_mask, double* out8, void* workspace, void* stream);
+/*  mg_eval_iid_lpips: LPIPS (AlexNet features, fp32 throughout; csrc/lpips.hip, the definition: evaluation/metrics.py:lpips) of the
+ *  same target as mg_eval_iid sees it - gamma, mask (invalid elements of both images -> 0) and, for an up-to-scale target, the (s, q)
+ *  of MG_OP_IIDSCORE_PREP, which the call runs itself into eval_ws (PREP is bit-reproducible: they are mg_eval_iid's).  H, W >= 31.
+ *  net: DEVICE pointers to fp32 weights in the layout the kernels read, layer l = 0..4 (Cin 3, 64, 192, 384, 256; Cout 64, 192, 384,
+ *  256, 256; k 11, 5, 3, 3, 3):
+ *    conv_w[l]  [k * k * Cin][Cout], row (ky * k + kx) * Cin + ci  (torch's [Cout][Cin][k][k] permuted to [k][k][Cin][Cout])
+ *    conv_b[l]  [Cout]
+ *    lin_w[l]   [Cout]  (the 1 x 1 "lin" layer of the tap, no bias)
+ *  out8 f64 = LPIPS, the number of valid elements of either image outside [0, 1] (NaN counts; the caller refuses the score when it
+ *  is not 0), the five per-tap terms, NaN.  eval_ws: MG_EVAL_WS_BYTES, 8-byte aligned; act_ws: mg_lpips_workspace_bytes(H, W) bytes
+ *  (-1 with mg_last_error for a size the call refuses), 16-byte aligned; both owned by the call until the stream has passed it.
+ *  Every argument is checked before the first device call.  No split-K and no floating-point atomics: the same bits on every call.
+ *  Does not synchronise. */
+typedef struct mg_lpips_net {
+  const float* conv_w[5];
+  const float* conv_b[5];
+  const float* lin_w[5];
+} mg_lpips_net;
+long long mg_lpips_workspace_bytes(int H, int W);
+int mg_eval_iid_lpips(const mg_lpips_net* net, const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W,
+                      int up_to_scale, int gamma_mode, double* out8, void* eval_ws, void* act_ws, long long act_ws_bytes, void* stream);
 
 /* The device I/O boundary on raw pointers (csrc/resize.hip): MG_OP_RGB_PREP and MG_OP_NORMALS_VIS as calls; neither synchronises.
  *  mg_rgb_prepare: src uint8 [Hin][Win][3] (hwc != 0) or [3][Hin][Win] -> dst [3][Hout][Wout], fp32 or (out16 != 0) the build's 16-bit

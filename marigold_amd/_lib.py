@@ -211,6 +211,7 @@ EXPORTS = [
     "mg_randn", "mg_resize", "mg_colorize", "mg_iid_visualize", "mg_model_predict",
     "mg_ensemble_iid", "mg_model_predict_iid",
     "mg_depth_visualize", "mg_normals_finish", "mg_model_predict_out",
+    "mg_lpips_workspace_bytes", "mg_eval_iid_lpips",
 ]
 
 
@@ -234,6 +235,11 @@ class MgOutputOpts(ctypes.Structure):
     """mg_output_opts; the defaults are MG_OUTPUT_OPTS_DEFAULT (the model's output size, no colour table).  ``lut256x3``: the DEVICE
     address of the colour map's 256 x 3 uint8 table."""
     _fields_ = [("out_h", ctypes.c_int), ("out_w", ctypes.c_int), ("out_mode", ctypes.c_int), ("lut256x3", ctypes.c_void_p)]
+
+
+class MgLpipsNet(ctypes.Structure):
+    """mg_lpips_net: DEVICE addresses of the fp32 weights of the five layers, packed as the header documents."""
+    _fields_ = [("conv_w", ctypes.c_void_p * 5), ("conv_b", ctypes.c_void_p * 5), ("lin_w", ctypes.c_void_p * 5)]
 
 
 class MgOp(ctypes.Structure):
@@ -312,6 +318,10 @@ def load(f16=False):
     lib.mg_eval_depth.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_double] * 2 + [ctypes.c_void_p] * 3
     lib.mg_eval_normals.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4
     lib.mg_eval_iid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3
+    lib.mg_lpips_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.mg_lpips_workspace_bytes.restype = ctypes.c_longlong
+    lib.mg_eval_iid_lpips.argtypes = [ctypes.POINTER(MgLpipsNet)] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3 + \
+        [ctypes.c_longlong, ctypes.c_void_p]
     lib.mg_rgb_prepare.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
     lib.mg_normals_visualize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_randn.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]

@@ -17,11 +17,10 @@
 #include <string.h>
 
 #include "common.h"
+#include "iid_images.h"   // EV_BLOCKS, EV_THREADS, IidMap, iid_gamma, IidImages and the head of the IID workspace layout
 
 namespace {
 
-constexpr int EV_BLOCKS = 512;    // rows of a partial table
-constexpr int EV_THREADS = 256;
 constexpr int LS_N = 5;           // n, Sx, Sy, Sxx, Sxy
 constexpr int DM_N = 11;          // the eleven sums of the depth scores (below)
 constexpr int NM_N = 9;           // Se, See, five counts, n, NaN count
@@ -347,16 +346,12 @@ __global__ __launch_bounds__(128) void select_step_kernel(SelState* __restrict__
 
 // ---- intrinsic image decomposition ----------------------------------------------------------------------------------
 
-constexpr int II_N = 5;           // S p*g, S p*p, valid elements, brightness pixels, NaN brightness values
 constexpr int SS_T = 32;          // the SSIM kernel's output tile is SS_T x SS_T
 constexpr int SS_R = 5;           // radius of the 11-tap window
 constexpr int SS_K = 2 * SS_R + 1;
 constexpr int SS_S = SS_T + 2 * SS_R;   // the staged tile: output tile + halo
 
-// workspace layout of the MG_OP_IIDSCORE_* ops (bytes)
-constexpr size_t WS_II_PART = 0;
-constexpr size_t WS_II_STATE = WS_II_PART + (size_t)EV_BLOCKS * II_N * 8;   // SelState
-constexpr size_t WS_II_MAP = WS_II_STATE + 64;                              // IidMap: survives from PREP to the score ops
+// workspace layout of the MG_OP_IIDSCORE_* ops (bytes), after the head in iid_images.h
 constexpr size_t WS_II_HIST0 = WS_II_MAP + 64;
 constexpr size_t WS_II_HIST1 = WS_II_HIST0 + 2048 * 4;
 constexpr size_t WS_II_HIST2 = WS_II_HIST1 + 2 * 2048 * 4;
@@ -364,36 +359,6 @@ constexpr size_t WS_II_PSNR_PART = WS_II_HIST2 + 2 * 1024 * 4;
 constexpr size_t WS_II_SSIM_PART = WS_II_PSNR_PART + (size_t)EV_BLOCKS * 2 * 8;
 constexpr size_t WS_IID_END = WS_II_SSIM_PART + (size_t)EV_BLOCKS * 2 * 8;
 static_assert(WS_IID_END <= MG_EVAL_WS_BYTES, "MG_EVAL_WS_BYTES too small");
-
-// what PREP leaves for the score kernels: pred <- clamp(q * (s * pred), 0, 1), gt <- clamp(q * gt, 0, 1)
-struct IidMap {
-  float s, q;
-};
-
-// the conversions of script/iid/eval.py:166-174 in fp32: bit 0 = x^2.2 (a target scored in linear space), bit 1 = x^(1/2.2) (Hypersim
-// albedo); both = one after the other, in that order
-__device__ __forceinline__ float iid_gamma(float x, int mode) {
-  if (mode & 1) x = powf(x, 2.2f);
-  if (mode & 2) x = powf(x, (float)(1.0 / 2.2));
-  return x;
-}
-
-// the two images as the scores see them: recomputed from (s, q) on every load, never stored
-struct IidImages {
-  const float *pred, *gt;
-  const uint8_t* mask;   // [3][HW] | NULL
-  const IidMap* map;     // NULL: a plain target
-  int gamma;
-  __device__ __forceinline__ bool valid(long long e) const { return !mask || mask[e]; }
-  __device__ __forceinline__ void load(long long e, float s, float q, float& p, float& g) const {
-    p = iid_gamma(pred[e], gamma);
-    g = iid_gamma(gt[e], gamma);
-    if (map) {
-      p = clip_keep_nan(q * (s * p), 0.f, 1.f);
-      g = clip_keep_nan(q * g, 0.f, 1.f);
-    }
-  }
-};
 
 // brightness of the ground truth over the pixels of mask channel 0 (quantile_map, metric.py:337-375).  Its sign is not known, so
 // the key flips the pattern into an order-preserving one: negative values complemented, the others with the sign bit set.

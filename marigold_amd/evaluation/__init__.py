@@ -6,3 +6,4 @@ from .alignment import align_depth_least_square, depth2disparity, disparity2dept
 from .datasets import DatasetMode, PredNameMode, get_dataset, get_pred_name, load_dataset_config  # noqa: F401
 from .metrics import MetricTracker  # noqa: F401
 from .device import score_depth, score_iid, score_iid_sample, score_normals  # noqa: F401
+from .lpips_net import LpipsNet  # noqa: F401

@@ -15,6 +15,7 @@ from .. import _lib as L
 from . import metrics as M
 
 _workspaces = {}
+_act_workspaces = {}   # LPIPS activations: one buffer per (device, library, stream), grown on demand
 
 
 def _device_of(device, *arrays):
@@ -107,8 +108,42 @@ def score_normals(pred, gt, masked=True, return_error_map=False, *, rounded=True
 _UP_TO_SCALE = ("shading", "residual")   # metrics.compute_iid_metric
 
 
-def _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, up_to_scale, gamma, metrics, out8, keep):
-    """One mg_eval_iid call on ``out8`` (a row of a device tensor); the uploaded tensors go to ``keep`` until the read-back."""
+def _act_workspace(ws, device, nbytes):
+    """The stream's activation buffer of at least ``nbytes`` (a larger image replaces it; the allocator keeps the old one alive for
+    the launches already queued on the stream).  It only grows and is never freed: one buffer of the largest image scored, per
+    stream that scored one."""
+    key = ws.data_ptr()   # one evaluation workspace per (device, library, stream): the same key
+    act = _act_workspaces.get(key)
+    if act is None or act.numel() < nbytes:
+        act = _act_workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return act
+
+
+def _lpips_launch(lib, ws, stream, device, net, p, g, m, up_to_scale, mode, out8):
+    """One mg_eval_iid_lpips call on ``out8`` for the tensors ``_iid_launch`` uploaded."""
+    h, w = p.shape[-2:]
+    nbytes = lib.mg_lpips_workspace_bytes(h, w)
+    if nbytes < 0:
+        L.check(1, "mg_lpips_workspace_bytes", lib)
+    net.to(device)
+    act = _act_workspace(ws, device, nbytes)
+    L.check(lib.mg_eval_iid_lpips(ctypes.byref(net._struct), p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else None, h, w,
+                                  int(up_to_scale), mode, out8.data_ptr(), ws.data_ptr(), act.data_ptr(), act.numel(), stream),
+            "mg_eval_iid_lpips", lib)
+
+
+def _lpips_value(values):
+    """LPIPS of an out8 row read back; a non-zero out-of-range count is the host function's ValueError."""
+    if values[1] != 0:
+        raise ValueError(f"lpips: {int(values[1])} element(s) outside [0, 1] (NaN counts): the metric is defined on images in [0, 1]")
+    return values[0]
+
+
+def _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, up_to_scale, gamma, metrics, out8, keep, lpips=None, lpips_out8=None):
+    """One mg_eval_iid call on ``out8`` (a row of a device tensor); the uploaded tensors go to ``keep`` until the read-back.  With a
+    network in ``lpips``: ``"lpips"`` may be among ``metrics`` and mg_eval_iid_lpips follows on ``lpips_out8``."""
+    if lpips is not None:
+        metrics = [m for m in metrics if m != "lpips"]
     unknown = [m for m in metrics if m not in L.IID_METRICS]
     if unknown:
         raise NotImplementedError(f"IID metric '{unknown[0]}' (LPIPS needs pretrained network weights that are not part of this engine)")
@@ -128,35 +163,45 @@ def _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, up_to_scale, gamm
     L.check(lib.mg_eval_iid(p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else None, h, w, int(up_to_scale),
                             mode, sum(L.IID_METRICS[k] for k in set(metrics)), out8.data_ptr(), ws.data_ptr(), stream),
             "mg_eval_iid", lib)
+    if lpips is not None:
+        _lpips_launch(lib, ws, stream, device, lpips, p, g, m, up_to_scale, mode, lpips_out8)
 
 
 def _iid_result(values):
     return dict(psnr=values[0], ssim=values[1], scale=values[2], quantile=values[3], n=int(values[5]))
 
 
-def score_iid(pred, gt, target_name, valid_mask=None, *, metrics=("psnr", "ssim"), gamma=None, device=None, f16=False):
+def score_iid(pred, gt, target_name, valid_mask=None, *, metrics=("psnr", "ssim"), gamma=None, device=None, f16=False, lpips=None):
     """metrics.compute_iid_metric for one target of one image -> ``{"psnr", "ssim", "scale", "quantile", "n"}`` (a metric not in
     ``metrics``: NaN; ``scale``: the least-squares scale, 1 for a plain target; ``quantile``: the 0.9 brightness quantile, NaN for
     a plain target; ``n``: valid elements, 0 -> every score NaN).  ``target_name`` "shading" / "residual" are up to scale: aligned
     and brightness-mapped first.  ``pred`` / ``gt`` [3,H,W] (or [1,3,H,W]), H, W >= 11; ``valid_mask`` bool of the same shape or
     None; ``gamma``: None, 2.2, 1 / 2.2 or (2.2, 1 / 2.2), a number within 1e-3 of one of them counting as it - ``x ** gamma`` in fp32 on both images first, as script/iid/eval.py does
-    for linear-space targets and Hypersim's albedo.  Numpy arrays are uploaded, CUDA tensors used in place; one read-back."""
+    for linear-space targets and Hypersim's albedo.  Numpy arrays are uploaded, CUDA tensors used in place; one read-back.
+    ``metrics`` with ``"lpips"`` needs ``lpips``, an ``evaluation.LpipsNet`` (H, W >= 31): the result gains the key ``"lpips"``
+    (``metrics.lpips`` of the same images, fp32 on the device) and the call raises ``ValueError`` when an element of either image,
+    as scored, is outside [0, 1]; without a network it is refused as before."""
     _require_gpu()
     device = _device_of(device, pred, gt, valid_mask)
     with torch.cuda.device(device):
         lib, ws, stream = _setup(device, f16)
-        out, keep = torch.empty(8, dtype=torch.float64, device=device), []
-        _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, target_name in _UP_TO_SCALE, gamma, metrics, out, keep)
+        net = lpips if "lpips" in metrics else None   # (asked for without a network: _iid_launch refuses it)
+        out, keep = torch.empty(8 if net is None else 16, dtype=torch.float64, device=device), []
+        _iid_launch(lib, ws, stream, device, pred, gt, valid_mask, target_name in _UP_TO_SCALE, gamma, metrics, out[:8], keep, net, out[8:])
         values = out.cpu().tolist()   # the one synchronisation
-    return _iid_result(values)
+    res = _iid_result(values)
+    if net is not None:
+        res["lpips"] = _lpips_value(values[8:])
+    return res
 
 
 def score_iid_sample(preds, data, target_names, *, metrics=("psnr", "ssim"), use_mask=False, linear_targets=(), dataset_name="",
-                     device=None, f16=False):
+                     device=None, f16=False, lpips=None):
     """The value row of harness._score_iid for one sample, scored on the GPU: ``preds`` {target: [3,H,W] prediction} (a target that
     is absent or None leaves ``None`` cells), ``data`` the dataset sample (``data[target]``, ``data["mask_" + target]``); values
     metric-major per target; the 2.2 gamma for ``linear_targets`` and the Hypersim three-target albedo rule of
-    script/iid/eval.py:166-174.  Every target is launched before the one read-back."""
+    script/iid/eval.py:166-174.  Every target is launched before the one read-back.  ``lpips``: an ``evaluation.LpipsNet`` - every
+    target's values are followed by its LPIPS (the reference's order: psnr, ssim, lpips)."""
     present = [t for t in target_names if preds.get(t) is not None]
     rows = {}
     if present:
@@ -164,17 +209,21 @@ def score_iid_sample(preds, data, target_names, *, metrics=("psnr", "ssim"), use
         device = _device_of(device, *[preds[t] for t in present])
         with torch.cuda.device(device):
             lib, ws, stream = _setup(device, f16)
-            out, keep = torch.empty((len(present), 8), dtype=torch.float64, device=device), []
+            out, keep = torch.empty((len(present), 8 if lpips is None else 16), dtype=torch.float64, device=device), []
             for k, t in enumerate(present):
                 gamma = (2.2,) if t in linear_targets else ()
                 if "hypersim" in dataset_name and len(target_names) == 3 and t == "albedo":
                     gamma += (1.0 / 2.2,)
                 gamma = None if not gamma else gamma[0] if len(gamma) == 1 else gamma
                 _iid_launch(lib, ws, stream, device, preds[t], data[t], data["mask_" + t] if use_mask else None,
-                            t in _UP_TO_SCALE, gamma, metrics, out[k], keep)   # (the calls share the stream's workspace, in stream order)
+                            t in _UP_TO_SCALE, gamma, metrics, out[k, :8], keep, lpips, out[k, 8:])   # (the calls share the stream's workspace, in stream order)
             values = out.cpu().tolist()
         rows = {t: _iid_result(v) for t, v in zip(present, values)}
+        if lpips is not None:
+            for t, v in zip(present, values):
+                rows[t]["lpips"] = _lpips_value(v[8:])
+    names = list(metrics) if lpips is None else [m for m in metrics if m != "lpips"] + ["lpips"]
     row = []
     for t in target_names:
-        row += [rows[t][m] for m in metrics] if t in rows else [None] * len(metrics)
+        row += [rows[t][m] for m in names] if t in rows else [None] * len(names)
     return row

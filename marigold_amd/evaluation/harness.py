@@ -99,7 +99,10 @@ def _iid_scoring_arguments(p, target_names=False):
     p.add_argument("--targets_to_eval_in_linear_space", nargs="*", default=[None], type=str,
                    help="Targets to evaluate in linear space (as opposed to sRGB by default).")
     p.add_argument("--metrics", nargs="+", default=["psnr", "ssim"], choices=["psnr", "ssim"],
-                   help="(LPIPS of the reference needs pretrained network weights; not provided)")
+                   help="(LPIPS of the reference needs pretrained network weights: give them with --lpips_weights)")
+    p.add_argument("--lpips_weights", nargs=2, default=None, metavar=("BACKBONE", "LIN"), type=str,
+                   help="Score LPIPS too, after each target's --metrics columns: the torchvision AlexNet state dict and the "
+                        "lpips 'lin' layers' state dict (two .pth files; nothing is downloaded).")
 
 
 def validate_iid_parser():
@@ -309,12 +312,16 @@ def validate_iid_main(argv=None, pipeline=None) -> int:
     if run is None:
         return 0
     seed, dataset = run
-    names = [f"{m}_{t}" for t in targets for m in args.metrics]
+    names = _iid_column_names(targets, args)
+    extra = {}
+    if args.lpips_weights:
+        from .lpips_net import LpipsNet
+        extra["lpips"] = LpipsNet.from_files(*args.lpips_weights)
 
     def score(sample, out, files):
         preds = {t: out[t].device_array if out[t].device_array is not None else out[t].array for t in targets}
         return sample["rgb_relative_path"], DV.score_iid_sample(preds, sample, targets, metrics=args.metrics, use_mask=args.use_mask,
-                                                                 linear_targets=linear, dataset_name=dataset.name)
+                                                                 linear_targets=linear, dataset_name=dataset.name, **extra)
     _predict_dataset("iid", args, dataset, pipeline, seed, True, save=not args.no_save_predictions, score=score,
                      consume=lambda rows: _write_eval_files("iid", args.eval_output_dir or os.path.join(args.output_dir, "eval"), dataset,
                                                             args.output_dir, names, rows))
@@ -397,8 +404,16 @@ def _score_normals(args, dataset, data, names):
     return rgb_name, [getattr(M, n)(err) for n in names]
 
 
+def _iid_column_names(targets, args):
+    """Per target: the --metrics columns, then LPIPS when its weights were given (the reference's order: psnr, ssim, lpips)."""
+    metrics = list(args.metrics) + (["lpips"] if getattr(args, "lpips_weights", None) else [])
+    return [f"{m}_{t}" for t in targets for m in metrics]
+
+
 def _score_iid(args, dataset, data, names):
     rgb_name = data["rgb_relative_path"]
+    net = getattr(args, "lpips_net", None)
+    metrics = list(args.metrics) + (["lpips"] if net is not None else [])
     stem = os.path.join(args.prediction_dir, os.path.splitext(rgb_name)[0])
     values = []
     for target in args.target_names:
@@ -407,7 +422,7 @@ def _score_iid(args, dataset, data, names):
             # keep the columns aligned with `names` (metric-major per target): a missing target leaves empty cells
             # and is not counted in the averages (the reference updates its tracker by metric name too)
             logging.warning(f"Can't find prediction: {path}")
-            values += [None] * len(args.metrics)
+            values += [None] * len(metrics)
             continue
         pred, gt = np.load(path)[None].astype(np.float32), data[target][None].astype(np.float32)
         if target in args.targets_to_eval_in_linear_space:
@@ -415,7 +430,8 @@ def _score_iid(args, dataset, data, names):
         if "hypersim" in dataset.name and len(args.target_names) == 3 and target == "albedo":
             pred, gt = pred ** (1.0 / 2.2), gt ** (1.0 / 2.2)
         mask = data["mask_" + target] if args.use_mask else None
-        values += [M.compute_iid_metric(pred.copy(), gt.copy(), target, m, mask) for m in args.metrics]
+        values += [M.compute_iid_metric(pred.copy(), gt.copy(), target, m, mask, **({"lpips_net": net} if m == "lpips" else {}))
+                   for m in metrics]
     return rgb_name, values
 
 
@@ -430,7 +446,10 @@ def eval_main(kind, argv=None) -> int:
         names, score = list(M.NORMALS_METRICS), _score_normals
     else:
         _linear_targets(args.targets_to_eval_in_linear_space, args.target_names)
-        names, score = [f"{m}_{t}" for t in args.target_names for m in args.metrics], _score_iid
+        names, score = _iid_column_names(args.target_names, args), _score_iid
+        if args.lpips_weights:
+            from .lpips_net import LpipsNet
+            args.lpips_net = LpipsNet.from_files(*args.lpips_weights)
     _write_eval_files(kind, args.output_dir, dataset, args.prediction_dir, names,
                       (score(args, dataset, data, names) for data in dataset), getattr(args, "alignment", None))
     return 0

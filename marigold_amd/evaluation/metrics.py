@@ -213,10 +213,82 @@ def ssim(pred, gt, data_range=1.0, sigma=1.5, kernel_size=11, k1=0.01, k2=0.03):
     return float(s[:, r:-r, r:-r].mean())
 
 
-def compute_iid_metric(pred, gt, target_name, metric_name, valid_mask=None):
+# LPIPS: every constant of the definition below, named once (the device path restates them in csrc/lpips.hip)
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)   # scaling layer: (x - shift) / scale per channel
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+LPIPS_CONVS = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))   # Cin, Cout, k, stride, pad
+LPIPS_POOL_BEFORE = (False, True, True, False, False)   # a max-pool in front of the convolution
+LPIPS_POOL = (3, 2)                      # window, stride (floor, no padding)
+LPIPS_NORM_EPS = 1e-8
+LPIPS_MIN_SIZE = 31                      # 31 x 31 gives 7 x 7, 3 x 3 and 1 x 1 maps
+
+
+def _lpips_unit(f):
+    """A position's features as a unit vector: eps INSIDE the root (the lpips package adds 1e-10 after it); all-zero -> 0."""
+    return f / (LPIPS_NORM_EPS + (f * f).sum(dim=1, keepdim=True)).sqrt()
+
+
+def lpips_features(image, net, dtype=None):
+    """The five feature taps (ReLU outputs, torch tensors [1,C,h,w]) of one ``[1,3,H,W]`` image in [0,1]: steps 1-3 of ``lpips``."""
+    import torch
+    import torch.nn.functional as F
+    dtype = torch.float32 if dtype is None else dtype
+    conv_w, conv_b, _ = net.host(dtype)
+    shift = torch.tensor(LPIPS_SHIFT, dtype=dtype).view(1, 3, 1, 1)
+    scale = torch.tensor(LPIPS_SCALE, dtype=dtype).view(1, 3, 1, 1)
+    f = ((2 * torch.as_tensor(image).to(dtype) - 1) - shift) / scale
+    taps = []
+    for l, (_, _, _, stride, pad) in enumerate(LPIPS_CONVS):
+        if LPIPS_POOL_BEFORE[l]:
+            f = F.max_pool2d(f, LPIPS_POOL[0], LPIPS_POOL[1])
+        f = F.relu(F.conv2d(f, conv_w[l], conv_b[l], stride=stride, padding=pad))
+        taps.append(f)
+    return taps
+
+
+def lpips_terms(pred, gt, net, dtype=None):
+    """The five per-tap terms of ``lpips`` (their sum is the score) as Python floats; the range check of ``lpips`` included."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    x = [torch.as_tensor(np.ascontiguousarray(_f32(a))).reshape((1, 3) + tuple(np.shape(a)[-2:])) for a in (pred, gt)]
+    if x[0].shape != x[1].shape or min(x[0].shape[-2:]) < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips: images {tuple(x[0].shape)}, {tuple(x[1].shape)}: two [1,3,H,W] images of one size, H, W >= {LPIPS_MIN_SIZE}")
+    bad = sum(int((~((a >= 0) & (a <= 1))).sum()) for a in x)
+    if bad:
+        raise ValueError(f"lpips: {bad} element(s) outside [0, 1] (NaN counts): the metric is defined on images in [0, 1]")
+    lin_w = net.host(dtype)[2]
+    terms = []
+    for l, (fp, fg) in enumerate(zip(lpips_features(x[0], net, dtype), lpips_features(x[1], net, dtype))):
+        d = (_lpips_unit(fp) - _lpips_unit(fg)) ** 2
+        terms.append(float((lin_w[l] * d).sum(dim=1).to(torch.float64).mean()))
+    return terms
+
+
+def lpips(pred, gt, net, dtype=None):
+    """Learned perceptual image patch similarity on AlexNet features, on torch CPU (``dtype``: torch.float32, the default, or
+    torch.float64 - the reference of the tests).  ``net``: an ``evaluation.LpipsNet``.
+
+    The definition is restated from knowledge of ``torchmetrics.image.LearnedPerceptualImagePatchSimilarity(net_type="alex",
+    normalize=True)``; it is NOT pinned against torchmetrics (tools/pin_lpips_against_torchmetrics.py records the fixture that
+    would pin it).  Inputs: two ``[1,3,H,W]`` fp32 images in [0,1], ``p`` and ``g``, H, W >= 31.
+
+    1. ``x = 2*x - 1``.
+    2. Scaling layer: ``(x - LPIPS_SHIFT) / LPIPS_SCALE`` per channel.
+    3. Five feature taps, each the ReLU output of (LPIPS_CONVS; LPIPS_POOL_BEFORE, LPIPS_POOL): conv1 3 -> 64, 11 x 11, stride 4,
+       pad 2; max-pool 3 / 2 (floor, no pad), conv2 64 -> 192, 5 x 5, pad 2; max-pool 3 / 2, conv3 192 -> 384, 3 x 3, pad 1;
+       conv4 384 -> 256, 3 x 3, pad 1; conv5 256 -> 256, 3 x 3, pad 1.  All with biases; zero padding of the scaled tensor.
+    4. Per tap and position: ``f / sqrt(LPIPS_NORM_EPS + sum_c f_c^2)`` (``_lpips_unit``); an all-zero position gives 0, not NaN.
+    5. Per tap: ``sum_c w_c (fp_c - fg_c)^2`` with the lin weights ``w`` ([1,C,1,1], no bias), then the spatial mean (summed in
+       fp64).  LPIPS is the sum of the five terms.
+    6. An element of either image that is not within [0,1] (a NaN is not) is a ``ValueError``, as with ``normalize=True``."""
+    terms = lpips_terms(pred, gt, net, dtype)
+    return (((terms[0] + terms[1]) + terms[2]) + terms[3]) + terms[4]
+
+
+def compute_iid_metric(pred, gt, target_name, metric_name, valid_mask=None, lpips_net=None):
     """One IID metric of one target (metric.py:285-316): shading / residual are up to scale, so they are
     first scale-aligned to the ground truth and brightness-mapped to [0,1]; PSNR is taken over the valid
-    elements, SSIM with the invalid ones zeroed."""
+    elements, SSIM and LPIPS (``lpips_net``: an ``evaluation.LpipsNet``; without one LPIPS is refused) with the invalid ones zeroed."""
     p, g = _f32(pred), _f32(gt)
     if target_name in ("shading", "residual"):
         p = np.float32(compute_alignment_scale(p, g, valid_mask)) * p
@@ -233,6 +305,8 @@ def compute_iid_metric(pred, gt, target_name, metric_name, valid_mask=None):
         return psnr(p, g)
     if metric_name == "ssim":
         return ssim(p, g)
+    if metric_name == "lpips" and lpips_net is not None:
+        return lpips(p, g, lpips_net)
     raise NotImplementedError(f"IID metric '{metric_name}' (LPIPS needs pretrained network weights that are not "
                               f"part of this engine)")
 
