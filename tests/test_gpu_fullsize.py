@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import scratch_cases as SC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -312,3 +314,39 @@ def test_c2_heavy_tailed_weights_vs_oracle(full, golden_dir):
     m = omet.affine_invariant_depth_errors(gold["ddim10_depth_m0"].astype(np.float32), d[0, 0].float().cpu().numpy())
     print(f"[parity] heavy-tailed C2 depth 768x768 vs fp32 CPU oracle: {m}")
     assert m["rmse"] < DEPTH_RMSE_BOUND and m["delta1"] > DEPTH_D1_BOUND, m
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# No output of a production program depends on what its scratch held before the run (tests/scratch_state.py; the configurations
+# and why they are these shapes: tests/scratch_cases.py).  The cases are here because this file owns the full-size weights: a
+# replica of the fixture's engines shares their device-resident weight store, so a case costs a program build and five forward
+# passes, not another 866 M parameters generated, packed and uploaded.
+
+@pytest.fixture(scope="module")
+def full_f16(full):
+    """The fp16-operand engines over the same state dicts (their own weight store: the operands are packed as fp16)."""
+    from marigold_amd.modules import AutoencoderKLHIP, UNet2DConditionModelHIP
+    unet = UNet2DConditionModelHIP(full["usd"], full["ucfg"], compute_dtype=torch.float16).to("cuda:0")
+    unet.set_context(full["ctx"])
+    return unet, AutoencoderKLHIP(full["vsd"], full["vcfg"], compute_dtype=torch.float16).to("cuda:0")
+
+
+@pytest.mark.parametrize("case", SC.cases(SC.FULL_RECYCLED), ids=SC.case_id)
+def test_scratch_independence(full, case):
+    """Product recycling: finite, bit-identical outputs over four scratch fills, zero state a fixed point, weights and inputs untouched."""
+    full["unet"].set_context(full["ctx"])
+    SC.run_case(full["unet"], full["vae"], case)
+
+
+@pytest.mark.parametrize("case", SC.cases(SC.FULL_F16), ids=SC.case_id)
+def test_scratch_independence_fp16(full_f16, case):
+    rep = SC.run_case(*full_f16, case)
+    assert rep["program"]
+
+
+@pytest.mark.parametrize("case", SC.cases(SC.FULL_FRESH), ids=SC.case_id)
+def test_scratch_independence_without_recycling(full, case):
+    """``Pool.put`` a no-op: no buffer is ever a hand-me-down, so the fill reaches every read that recycling would serve with the
+    finite data of an earlier layer."""
+    full["unet"].set_context(full["ctx"])
+    SC.run_case(full["unet"], full["vae"], case, recycle=False)
