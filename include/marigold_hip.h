@@ -871,11 +871,16 @@ void mg_program_destroy(mg_program* prog);
  *  mg_model_load(path, device): device >= 0 binds the library to that GPU (mg_init) and uploads; device < 0 = host-only: the
  *  image is parsed and relocated against fake addresses so that mg_model_validate can check every op's contract without a GPU.
  *  mg_model_info: cfg16 = B, H, W, latent h, latent w, steps, prediction channels, MG_POST_*, step-noise tensors, sizeof(mg_op),
- *  modalities, decoded H, decoded W.
+ *  modalities, decoded H, decoded W, K.  cfg16[13] = K, the pictures per call the image was exported for
+ *  (export_model_image(images_per_program=K)): 0 in an image of one picture per call - every image written before the field
+ *  existed, and every K = 1 export since - else the written value, K > 1; B = cfg16[0] is then the members of EACH picture.
  *  mg_model_vae_encode: rgb [1,3,H,W] in [-1,1] -> latent [1,4,h,w] (x 0.18215, posterior mean).
  *  mg_model_denoise: rgb_latent [1,4,h,w], x [B,C,h,w] in / out (the initial noise -> the denoised latent), step_noise
  *  [n][B,C,h,w] for the LCM scheduler's n noisy steps (NULL for DDIM).
- *  mg_model_vae_decode: latent [B*modalities,4,h,w] -> pred [B, channels, Hout, Wout] with the pipeline's pointwise tail. */
+ *  mg_model_vae_decode: latent [B*modalities,4,h,w] -> pred [B, channels, Hout, Wout] with the pipeline's pointwise tail.
+ *  On an image of K > 1 pictures per call the three calls copy by slot size as before and carry the batch: rgb [K,3,H,W], rgb_latent
+ *  [K,4,h,w]; x, latent and pred have K B rows, image-major (row i B + j = member j of picture i), step_noise [n][K B,C,h,w].
+ *  mg_model_load checks that the slots of the three programs chain for K pictures of B members before anything can run. */
 typedef struct mg_model mg_model;
 mg_model* mg_model_load(const char* path, int device);
 void mg_model_destroy(mg_model* m);
@@ -940,6 +945,30 @@ int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int 
                          const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
                          float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
                          void* stream);
+
+/* mg_model_predict_out for n pictures in ONE call, on an image exported for K >= n pictures per call (cfg16[13]): the pictures share
+ * one encode, one denoise and one decode program - the programs map_images(images_per_program=K) runs - and every stage before and
+ * after them runs per picture, the very code of mg_model_predict_out (one picture is its n = K = 1 case).
+ *  rgb         a HOST array of n DEVICE pointers, every picture uint8 Hin x Win in the layout `hwc` names
+ *  seeds       a HOST array of n seeds: picture i draws what its lone call draws from seeds[i] (MG_OP_RANDN stream 0 = its B initial
+ *              latents, stream k + 1 = its LCM step noise k), into rows [i B, (i + 1) B) of the denoise program
+ *  pred_out    fp32 [n][channels][out_h][out_w], clipped     unc_out  fp32 [n][cfg[11]][cfg[12]] | NULL, written when B > 1
+ *  u16_out     uint16 [n][out_h][out_w] | NULL               picture_out uint8 [n][out_h][out_w][3] | NULL
+ *  info4       double [n][4] | NULL, per picture as in mg_model_predict
+ * opts and out_opts apply to every picture, with the defaults of mg_model_predict_out.  A call with n < K feeds picture n - 1 and its
+ * seed to the spare rows as well (no row ever reads what an earlier call left there), discards their results and writes nothing
+ * beyond row n - 1 of any output.  Refused before anything is launched, the message starting with "mg_model_predict_many:": n < 1
+ * or n > K, a null rgb or seeds array or a null picture, a host-only model, an intrinsic-image model (exported for one picture per
+ * call only), and every output-option refusal of mg_model_predict_out in the same words.  On an image of K > 1 pictures per call
+ * mg_model_predict, mg_model_predict_out and mg_model_predict_iid refuse and name mg_model_predict_many.  The temporaries (input
+ * resampling for one picture, the ensembled map ahead of a resize, the resize's intermediate) are the model's and serve the pictures
+ * in turn: grown on demand, counted by mg_model_device_bytes.  Synchronises where mg_ensemble_depth does - once per picture for
+ * depth with B > 1 - and nowhere else.  map_images(images_per_program=K, generators=[NativeNoise(seed_i)], match_input_res=True)
+ * gives the same arrays and pictures, bit for bit (tests/test_gpu_predict_many_c_host.py; examples/host_many.cpp). */
+int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                          const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
+                          float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
+                          double* info4_or_null, void* stream);
 
 /* The same for an intrinsic-image model (appearance, lighting): __call__ of the reference's MarigoldIIDPipeline with fill_outputs
  * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[10] = n_targets

@@ -210,7 +210,7 @@ EXPORTS = [
     "mg_rgb_prepare", "mg_normals_visualize",
     "mg_randn", "mg_resize", "mg_colorize", "mg_iid_visualize", "mg_model_predict",
     "mg_ensemble_iid", "mg_model_predict_iid",
-    "mg_depth_visualize", "mg_normals_finish", "mg_model_predict_out",
+    "mg_depth_visualize", "mg_normals_finish", "mg_model_predict_out", "mg_model_predict_many",
     "mg_lpips_workspace_bytes", "mg_eval_iid_lpips",
 ]
 
@@ -335,6 +335,8 @@ def load(f16=False):
     lib.mg_normals_finish.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3
     lib.mg_model_predict_out.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgPredictOpts),
                                                                                        ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
+    lib.mg_model_predict_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 5 + \
+        [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgPredictOpts), ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

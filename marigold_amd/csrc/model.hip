@@ -25,7 +25,8 @@ namespace {
 struct ImgHeader {
   char magic[8];
   uint32_t version, abi, n_buffers, n_programs;
-  uint32_t cfg[16];   // B, H, W, h, w, steps, prediction channels, post, step noises, sizeof(mg_op), modalities, Hout, Wout
+  uint32_t cfg[16];   // B, H, W, h, w, steps, prediction channels, post, step noises, sizeof(mg_op), modalities, Hout, Wout,
+                      // pictures per call (0 = 1: images written before the field; B is then the members of EACH picture)
 };
 struct ImgBuffer {
   uint64_t nbytes, file_off;
@@ -75,7 +76,9 @@ struct mg_model {
   std::vector<char*> bufs;
   std::vector<uint64_t> buf_bytes;   // the buffer table's sizes: every relocation / slot is checked against them
   Prog enc, den, dec;
-  void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W]), grown on demand
+  int K = 1;                         // pictures per call (cfg[13], 0 = 1)
+  void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W], one picture's: the
+                                     // pictures of a call pass through it one after the other), grown on demand
   uint64_t predict_tmp_bytes = 0;
   void* out_tmp = nullptr;           // the one-call predictions' output temporaries (see out_tmp_layout), grown on demand
   uint64_t out_tmp_bytes = 0;
@@ -181,6 +184,14 @@ int load_into(mg_model* m, FILE* f, int device) {
   }
   MG_REQUIRE(m->enc.slot("rgb") && m->enc.slot("latent") && m->den.slot("rgb_latent") && m->den.slot("x") && m->dec.slot("latent") &&
              m->dec.slot("pred"), "mg_model_load: a program lacks its input / output slots");
+  // the three programs hand K pictures of B members on to each other: [K,3,H,W] -> [K,4,h,w]; [K B,...] -> the decoder -> [K B,C,Ho,Wo]
+  m->K = h.cfg[13] ? (int)h.cfg[13] : 1;
+  const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
+  const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
+  const uint64_t K = (uint64_t)m->K;
+  MG_REQUIRE(m->K >= 1 && e_in->nbytes == K * 3 * h.cfg[1] * h.cfg[2] * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
+             xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * h.cfg[0] * h.cfg[6] * h.cfg[11] * h.cfg[12] * 4,
+             "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", m->K, h.cfg[0]);
   return 0;
 }
 
@@ -430,38 +441,43 @@ int grow_tmp(void** p, uint64_t* bytes, uint64_t need) {
   return 0;
 }
 
-// Stages 1 to 5 of a one-call prediction, the same for every kind of model: the picture into the encoder, encode, the noise
-// (MG_OP_RANDN: stream 0 = the initial latents, stream k + 1 = the LCM scheduler's step noise k), denoise, decode.  `who` names the
-// entry point in the messages.  On return the B members lie in the decode program's output slot, *preds.
-int predict_members(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                    void* stream, const float** preds) {
+// Stages 1 to 5 of a one-call prediction, the same for every kind of model, for the n <= K pictures of one call: each picture into its
+// row of the encoder's input, ONE encode, each picture's noise into its B rows (MG_OP_RANDN of its own seed: stream 0 = the initial
+// latents, stream k + 1 = the LCM scheduler's step noise k - what its lone call draws), ONE denoise, ONE decode.  A call with n < K
+// feeds picture n - 1 and its seed to the spare rows too, so that nothing in the programs reads what an earlier call left; the
+// spare results are never read.  `who` names the entry point in the messages.  On return the K B members lie image-major in the
+// decode program's output slot, *preds.  One picture per call is the n = K = 1 case.
+int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                    const uint64_t* seeds, void* stream, const float** preds) {
   const uint32_t* cfg = m->hdr.cfg;
-  const int B = (int)cfg[0], H = (int)cfg[1], W = (int)cfg[2], C = (int)cfg[6], n_noise = (int)cfg[8];
+  const int K = m->K, H = (int)cfg[1], W = (int)cfg[2], n_noise = (int)cfg[8];
   MG_REQUIRE(Hin > 0 && Win > 0, "%s: bad input size %d x %d", who, Hin, Win);
   const hipStream_t s = (hipStream_t)stream;
   const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
   const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
-  const uint64_t HWo = (uint64_t)cfg[11] * cfg[12];
-  MG_REQUIRE(e_in->nbytes == (uint64_t)3 * H * W * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes && xs->nbytes % 4 == 0 &&
-             d_out->nbytes == (uint64_t)B * C * HWo * 4, "%s: the image's slots do not chain", who);
-  // 1. the picture -> [1,3,H,W] in [-1, 1], in the encoder's input slot
+  // (mg_model_load checked that the slots chain)
+  const uint64_t rgb_row = e_in->nbytes / K, x_rows = xs->nbytes / K;   // bytes per picture
+  // 1. picture i -> [1,3,H,W] in [-1, 1], row i of the encoder's input slot
   float* tmp = nullptr;
   if (mode != 2 && Hin != H && Win != W) {
     if (int rc = grow_tmp(&m->predict_tmp, &m->predict_tmp_bytes, (uint64_t)3 * Hin * W * 4)) return rc;
     tmp = (float*)m->predict_tmp;
   }
-  if (int rc = mg_rgb_prepare(rgb, hwc, Hin, Win, e_in->ptr, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
+  for (int i = 0; i < K; ++i)
+    if (int rc = mg_rgb_prepare(rgb[i < n ? i : n - 1], hwc, Hin, Win, e_in->ptr + i * rgb_row, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
   // 2. encode
   if (int rc = mg_program_run(m->enc.prog, stream)) return rc;
   if (int rc = copy_dd(rl->ptr, e_out->ptr, rl->nbytes, s)) return rc;
   // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
-  if (int rc = mg_randn(seed, 0, 0, (int64_t)(xs->nbytes / 4), xs->ptr, 0, stream)) return rc;
+  for (int i = 0; i < K; ++i)
+    if (int rc = mg_randn(seeds[i < n ? i : n - 1], 0, 0, (int64_t)(x_rows / 4), xs->ptr + i * x_rows, 0, stream)) return rc;
   for (int k = 0; k < n_noise; ++k) {
     char nm[24];
     snprintf(nm, sizeof(nm), "noise%d", k);
     const Slot* ns = m->den.slot(nm);
     MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "%s: the image lacks slot %s", who, nm);
-    if (int rc = mg_randn(seed, (uint64_t)k + 1, 0, (int64_t)(ns->nbytes / 4), ns->ptr, 0, stream)) return rc;
+    for (int i = 0; i < K; ++i)
+      if (int rc = mg_randn(seeds[i < n ? i : n - 1], (uint64_t)k + 1, 0, (int64_t)(x_rows / 4), ns->ptr + i * x_rows, 0, stream)) return rc;
   }
   // 4. denoise, 5. decode (an intrinsic-image model: the latent [B, 4 n, h, w] is the decoder's batch [B n, 4, h, w], the same bytes)
   if (int rc = mg_program_run(m->den.prog, stream)) return rc;
@@ -503,15 +519,18 @@ OutTmp out_tmp_layout(int B, int planes, int Ho, int Wo, int oh, int ow, int out
   return t;
 }
 
-// Stages 1 to 7 of a one-call prediction: the members (predict_members), then
-// 6. ensemble(members, dst) -> int: the B members in the decoder's output slot -> the ensembled map (one member: the pipelines
+// Stages 1 to 7 of a one-call prediction of n pictures: the members (predict_members), then for picture i, one after the other,
+// 6. ensemble(i, members, dst) -> int: its B members in the decoder's output slot -> the ensembled map (one member: the pipelines
 //    return it as it is, without an uncertainty, and `ensemble` is not called),
 // 7. match_input_res (marigold_depth_pipeline.py:306-312, marigold_normals_pipeline.py:282-288, marigold_iid_pipeline.py:378-385):
-//    the prediction only, [planes][Ho][Wo] -> pred_out [planes][oh][ow].
-// *ws (may be null): the picture workspace of ws_bytes, valid until the model's next prediction.
-template <class Ensemble>
-int predict_resized(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                    int planes, int oh, int ow, int out_mode, uint64_t ws_bytes, float* pred_out, float** ws, void* stream, Ensemble ensemble) {
+//    the prediction only, [planes][Ho][Wo] -> row i of pred_out [n][planes][oh][ow],
+// 8. finish(i, row i of pred_out) -> int: the entry point's output stage on what was stored.
+// The temporaries serve the pictures in turn (the stream orders them).  *ws (may be null): the picture workspace of ws_bytes, valid
+// until the model's next prediction.
+template <class Ensemble, class Finish>
+int predict_resized(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                    const uint64_t* seeds, int planes, int oh, int ow, int out_mode, uint64_t ws_bytes, float* pred_out, float** ws, void* stream,
+                    Ensemble ensemble, Finish finish) {
   const int B = (int)m->hdr.cfg[0], Ho = (int)m->hdr.cfg[11], Wo = (int)m->hdr.cfg[12];
   const bool resize = oh != Ho || ow != Wo;
   const OutTmp t = out_tmp_layout(B, planes, Ho, Wo, oh, ow, out_mode, ws_bytes);
@@ -519,51 +538,101 @@ int predict_resized(mg_model* m, const char* who, const uint8_t* rgb, int hwc, i
   float* const ens = (float*)m->out_tmp;
   float* const rtmp = t.rtmp ? (float*)((char*)m->out_tmp + t.ens) : nullptr;
   if (ws) *ws = t.ws ? (float*)((char*)m->out_tmp + t.ens + t.rtmp) : nullptr;
-  const float* preds = nullptr;
-  if (int rc = predict_members(m, who, rgb, hwc, Hin, Win, mode, reciprocal, seed, stream, &preds)) return rc;
-  const float* final_pred = preds;   // at the decoded size
-  if (B > 1) {
-    float* const dst = resize ? ens : pred_out;
-    if (int rc = ensemble(preds, dst)) return rc;
-    final_pred = dst;
+  const float* all = nullptr;
+  if (int rc = predict_members(m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, stream, &all)) return rc;
+  for (int i = 0; i < n; ++i) {
+    const float* preds = all + (uint64_t)i * B * planes * Ho * Wo;
+    float* const out = pred_out + (uint64_t)i * planes * oh * ow;
+    const float* final_pred = preds;   // at the decoded size
+    if (B > 1) {
+      float* const dst = resize ? ens : out;
+      if (int rc = ensemble(i, preds, dst)) return rc;
+      final_pred = dst;
+    }
+    if (resize) {
+      if (int rc = mg_resize(final_pred, out, rtmp, planes, Ho, Wo, oh, ow, out_mode, 0, stream)) return rc;
+    } else if (B == 1) {
+      if (int rc = copy_dd(out, preds, (uint64_t)planes * Ho * Wo * 4, (hipStream_t)stream)) return rc;
+    }
+    if (int rc = finish(i, out)) return rc;
   }
-  if (resize) return mg_resize(final_pred, pred_out, rtmp, planes, Ho, Wo, oh, ow, out_mode, 0, stream);
-  if (B == 1) return copy_dd(pred_out, preds, (uint64_t)planes * Ho * Wo * 4, (hipStream_t)stream);
   return 0;
 }
 
-// Stages 1 to 7 of a depth / normals prediction
-int predict_depth_or_normals(mg_model* m, const char* who, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                             const mg_predict_opts* opts_or_null, int oh, int ow, int out_mode, float* pred_out, float* unc_out_or_null,
-                             double* info4_or_null, void* stream) {
+// Stages 1 to 8 of a depth / normals prediction of n pictures; unc_out [n][Ho][Wo], info4 [n][4], the pictures of the output stage
+// (u16_out [n][oh][ow], picture_out [n][oh][ow][3]; `clip`: the output stage runs - mg_model_predict stores the map as it is)
+int predict_depth_or_normals(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                             const uint64_t* seeds, const mg_predict_opts* opts_or_null, int oh, int ow, int out_mode, bool clip,
+                             const uint8_t* lut256x3, float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null,
+                             uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
   const uint32_t* cfg = m->hdr.cfg;
   const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], Ho = (int)cfg[11], Wo = (int)cfg[12];
   static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
   const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
-  if (info4_or_null) info4_or_null[0] = info4_or_null[1] = info4_or_null[2] = info4_or_null[3] = 0.0;
-  return predict_resized(m, who, rgb, hwc, Hin, Win, mode, reciprocal, seed, C, oh, ow, out_mode, 0, pred_out, nullptr, stream,
-                         [&](const float* preds, float* dst) {
-                           if (post == MG_POST_DEPTH)
-                             return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength,
-                                                      o.max_iter, o.tol, o.max_res, dst, unc_out_or_null, info4_or_null, stream);
-                           MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
-                           return mg_ensemble_normals(preds, dst, unc_out_or_null, B, (int64_t)Ho * Wo, o.normals_reduction, stream);
-                         });
+  if (info4_or_null)
+    for (int i = 0; i < 4 * n; ++i) info4_or_null[i] = 0.0;
+  const uint64_t HWo = (uint64_t)Ho * Wo, hw = (uint64_t)oh * ow;
+  return predict_resized(
+      m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, C, oh, ow, out_mode, 0, pred_out, nullptr, stream,
+      [&](int i, const float* preds, float* dst) {
+        float* const unc = unc_out_or_null ? unc_out_or_null + i * HWo : nullptr;
+        if (post == MG_POST_DEPTH)
+          return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
+                                   o.max_res, dst, unc, info4_or_null ? info4_or_null + 4 * i : nullptr, stream);
+        MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
+        return mg_ensemble_normals(preds, dst, unc, B, (int64_t)HWo, o.normals_reduction, stream);
+      },
+      // 8. the output stage on what was stored, in place: the clip (:314-316 / :294), the 16-bit depth (script/depth/run.py), the picture
+      [&](int i, float* out) {
+        if (!clip) return 0;
+        uint8_t* const pic = picture_out_or_null ? picture_out_or_null + i * hw * 3 : nullptr;
+        if (post == MG_POST_DEPTH)
+          return mg_depth_visualize(out, lut256x3, (int64_t)hw, out, u16_out_or_null ? u16_out_or_null + i * hw : nullptr, pic, stream);
+        return mg_normals_finish(out, oh, ow, out, pic, stream);
+      });
+}
+
+// mg_model_predict_out and mg_model_predict_many after their own argument checks: the refusals they share (in `who`'s name), then the
+// prediction.  One picture is n = 1.
+int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                     const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
+                     float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
+  const uint32_t* cfg = m->hdr.cfg;
+  const int C = (int)cfg[6], post = (int)cfg[7];
+  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "%s: an intrinsic-image model goes through mg_model_predict_iid", who);
+  const bool depth = post == MG_POST_DEPTH && C == 1;
+  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
+  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
+  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
+  int oh, ow;
+  if (int rc = output_size(who, q.out_h, q.out_w, q.out_mode, 1ll << 30, (int)cfg[11], (int)cfg[12], &oh, &ow)) return rc;
+  if (depth) {
+    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "%s: the picture of a depth model needs out_opts.lut256x3 (the colour table)", who);
+  } else {
+    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "%s: u16_out and lut256x3 belong to a depth model, this one predicts normals", who);
+  }
+  return predict_depth_or_normals(m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, oh, ow, q.out_mode, true, q.lut256x3,
+                                  pred_out, unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
 }
 
 }  // namespace
+
+// An image of several pictures per call runs through mg_model_predict_many only
+#define MG_REQUIRE_ONE_PICTURE(m, who) \
+  MG_REQUIRE((m)->K == 1, who ": this image runs %d pictures per call: use mg_model_predict_many", (m)->K)
 
 extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                 const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
                                 void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
+  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict");
   const uint32_t* cfg = m->hdr.cfg;
   const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
   MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
   // the map at the decoded size: no resize, no temporaries
-  return predict_depth_or_normals(m, "mg_model_predict", rgb, hwc, Hin, Win, mode, reciprocal, seed, opts_or_null, (int)cfg[11], (int)cfg[12], 0,
-                                  pred_out, unc_out_or_null, info4_or_null, stream);
+  return predict_depth_or_normals(m, "mg_model_predict", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, (int)cfg[11], (int)cfg[12], 0,
+                                  false, nullptr, pred_out, unc_out_or_null, nullptr, nullptr, info4_or_null, stream);
 }
 
 extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
@@ -572,32 +641,29 @@ extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, in
                                     void* stream) {
   MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_out: null argument (the model, the picture and pred_out are required)");
   MG_REQUIRE(!m->host_only, "mg_model_predict_out: a host-only model cannot predict (load it with device >= 0)");
-  const uint32_t* cfg = m->hdr.cfg;
-  const int C = (int)cfg[6], post = (int)cfg[7];
-  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict_out: an intrinsic-image model goes through mg_model_predict_iid");
-  const bool depth = post == MG_POST_DEPTH && C == 1;
-  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "mg_model_predict_out: a depth or a normals image is required");
-  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
-  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
-  int oh, ow;
-  if (int rc = output_size("mg_model_predict_out", q.out_h, q.out_w, q.out_mode, 1ll << 30, (int)cfg[11], (int)cfg[12], &oh, &ow)) return rc;
-  if (depth) {
-    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "mg_model_predict_out: the picture of a depth model needs out_opts.lut256x3 (the colour table)");
-  } else {
-    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "mg_model_predict_out: u16_out and lut256x3 belong to a depth model, this one predicts normals");
-  }
-  if (int rc = predict_depth_or_normals(m, "mg_model_predict_out", rgb, hwc, Hin, Win, mode, reciprocal, seed, opts_or_null, oh, ow, q.out_mode,
-                                        pred_out, unc_out_or_null, info4_or_null, stream))
-    return rc;
-  // 8. the output stage on what was stored, in place: the clip (:314-316 / :294), the 16-bit depth (script/depth/run.py), the picture
-  if (depth) return mg_depth_visualize(pred_out, q.lut256x3, (int64_t)oh * ow, pred_out, u16_out_or_null, picture_out_or_null, stream);
-  return mg_normals_finish(pred_out, oh, ow, pred_out, picture_out_or_null, stream);
+  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_out");
+  return predict_out_many(m, "mg_model_predict_out", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, out_opts_or_null, pred_out,
+                          unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
+}
+
+extern "C" int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
+                                     const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
+                                     float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
+                                     double* info4_or_null, void* stream) {
+  MG_REQUIRE(m, "mg_model_predict_many: null model");
+  MG_REQUIRE(!m->host_only, "mg_model_predict_many: a host-only model cannot predict (load it with device >= 0)");
+  MG_REQUIRE(n >= 1 && n <= m->K, "mg_model_predict_many: %d pictures for an image of %d per call (1 <= n <= %d)", n, m->K, m->K);
+  MG_REQUIRE(rgb && seeds && pred_out, "mg_model_predict_many: null argument (the rgb and seeds arrays and pred_out are required)");
+  for (int i = 0; i < n; ++i) MG_REQUIRE(rgb[i], "mg_model_predict_many: null picture %d of %d", i, n);
+  return predict_out_many(m, "mg_model_predict_many", n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, out_opts_or_null, pred_out,
+                          unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
 }
 
 extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                     const mg_iid_opts* opts_or_null, float* pred_out, float* unc_out_or_null, uint8_t* pictures_out_or_null,
                                     void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict_iid: bad arguments (or a host-only model)");
+  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_iid");
   const uint32_t* cfg = m->hdr.cfg;
   const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8], n = (int)cfg[10];
   const int Ho = (int)cfg[11], Wo = (int)cfg[12];
@@ -614,12 +680,12 @@ extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, in
   const uint64_t ws_bytes = pictures_out_or_null && (o.linear_bits & o.up_to_scale_bits) ? (uint64_t)n * MG_IID_VIS_PARTS * 4 : 0;
   float* ws = nullptr;
   // 6. the ensemble is ensemble_iid (:369-375)
-  if (int rc = predict_resized(m, "mg_model_predict_iid", rgb, hwc, Hin, Win, mode, reciprocal, seed, C, oh, ow, o.out_mode, ws_bytes, pred_out, &ws,
-                               stream, [&](const float* preds, float* dst) {
-                                 return mg_ensemble_iid(preds, B, (int64_t)C * Ho * Wo, o.reduction, dst, unc_out_or_null, stream);
-                               }))
-    return rc;
-  // 8. the pictures of what was stored (fill_outputs -> MarigoldIIDOutput.fill_entry, :117-136, :393-411)
-  if (pictures_out_or_null) return mg_iid_visualize(pred_out, pictures_out_or_null, ws, n, oh, ow, o.linear_bits, o.up_to_scale_bits, stream);
-  return 0;
+  return predict_resized(
+      m, "mg_model_predict_iid", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, C, oh, ow, o.out_mode, ws_bytes, pred_out, &ws, stream,
+      [&](int, const float* preds, float* dst) { return mg_ensemble_iid(preds, B, (int64_t)C * Ho * Wo, o.reduction, dst, unc_out_or_null, stream); },
+      // 8. the pictures of what was stored (fill_outputs -> MarigoldIIDOutput.fill_entry, :117-136, :393-411)
+      [&](int, float* out) {
+        if (!pictures_out_or_null) return 0;
+        return mg_iid_visualize(out, pictures_out_or_null, ws, n, oh, ow, o.linear_bits, o.up_to_scale_bits, stream);
+      });
 }

@@ -83,10 +83,20 @@ def _pad(f, align=64):
     return f.tell()
 
 
-def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_steps=None):
+def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_steps=None, images_per_program=1):
     """Write the model image of ``pipe`` for images of ``height`` x ``width`` (the size fed to the VAE: after the pipeline's
-    ``processing_res`` resize), ``ensemble_size`` members per call and ``denoising_steps`` scheduler steps.  Works with the
-    modules on the GPU (``pipe.to("cuda")``) or, without one, in the host-only mode.  Returns a dict describing the image."""
+    ``processing_res`` resize), ``ensemble_size`` members per picture and ``denoising_steps`` scheduler steps.  Works with the
+    modules on the GPU (``pipe.to("cuda")``) or, without one, in the host-only mode.  Returns a dict describing the image.
+
+    ``images_per_program`` = K > 1: the image runs K pictures per call (``mg_model_predict_many``) through the programs
+    ``map_images(images_per_program=K)`` runs for a full group - one encode of K pictures, one denoising program of K x
+    ``ensemble_size`` members, one decode; the header's ``cfg[13]`` is K.  K = 1 writes the one-picture image, ``cfg[13]`` = 0."""
+    K = int(images_per_program)
+    if K < 1:
+        raise ValueError(f"export_model_image: images_per_program must be >= 1 (got {images_per_program})")
+    if K > 1 and pipe._kind == "iid":
+        raise ValueError("export_model_image: intrinsic-image models are exported for one picture per call (images_per_program=1): "
+                         "mg_model_predict_iid takes one picture")
     unet, vae = pipe.unet, pipe.vae
     assert isinstance(unet, UNet2DConditionModelHIP) and isinstance(vae, AutoencoderKLHIP)
     if unet.ws is None:
@@ -101,11 +111,14 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
         raise ValueError("export_model_image: model images carry bf16 operands (the C host loads libmarigold_hip.so); "
                          "build the pipeline with compute_dtype=torch.bfloat16")
     unet.set_context(pipe.empty_text_embed)
-    enc_seq, enc_in, enc_out = vae._program("encode", 1, height, width)
+    enc_seq, enc_in, enc_out = vae._program("encode", K, height, width)
     h, w = enc_out.shape[-2:]
-    den = unet.denoise_program(B, h, w, pipe.scheduler, T, rgb_broadcast=True)
+    if K == 1:
+        den = unet.denoise_program(B, h, w, pipe.scheduler, T, rgb_broadcast=True)
+    else:   # the programs of a full group (pipeline._predict_group -> single_infer(..., rgb_members=B))
+        den = unet.denoise_program(K * B, h, w, pipe.scheduler, T, rgb_members=B)
     n_mod = getattr(pipe, "n_targets", 1)
-    dec_seq, dec_in, dec_out = vae._program("decode", B * n_mod, h, w, post)
+    dec_seq, dec_in, dec_out = vae._program("decode", K * B * n_mod, h, w, post)
 
     bufs = _Buffers()
     for mod in (unet, vae):
@@ -200,7 +213,8 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
                 f.write(struct.pack(REL, k, s, b, 0, o))
         total = f.tell()
         f.seek(0)
-        cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, dec_out.shape[-2], dec_out.shape[-1]] + [0] * 3
+        cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, dec_out.shape[-2], dec_out.shape[-1],
+               K if K > 1 else 0] + [0] * 2
         f.write(struct.pack(HDR, MAGIC, VERSION, L.ABI_VERSION, n_buf, n_prog, *cfg))
         for (start, end, k, _t), off in zip(bufs.items, buf_off):
             f.write(struct.pack(BUF, end - start, off, k, 0))
@@ -215,7 +229,7 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
     nbytes = {k: sum(it[1] - it[0] for it in bufs.items if it[2] == k) for k in (KIND_SCRATCH, KIND_ZERO, KIND_DATA)}
     return dict(path=path, file_bytes=total, buffers=n_buf, scratch_bytes=nbytes[KIND_SCRATCH], zero_bytes=nbytes[KIND_ZERO],
                 data_bytes=nbytes[KIND_DATA], ops={n: c for (n, c, _s) in ptab}, latent_hw=(int(h), int(w)), B=B, steps=T,
-                pred_channels=cpred * n_mod, step_noises=len(den.noises))
+                pred_channels=cpred * n_mod, step_noises=len(den.noises), images_per_program=K)
 
 
 def export_color_table(cmap, path):
@@ -245,30 +259,33 @@ class ModelImage:
         L.check(lib.mg_model_info(self.handle, cfg), "mg_model_info")
         (self.B, self.H, self.W, self.h, self.w, self.steps, self.pred_channels, self.post, self.n_noise) = list(cfg)[:9]
         self.Hout, self.Wout = cfg[11], cfg[12]
+        self.K = cfg[13] or 1   # pictures per call; B: the members of each
         self.device = device
 
     def validate(self):
         L.check(self._lib.mg_model_validate(self.handle), "mg_model_validate")
 
     def encode(self, rgb):
-        out = torch.empty(1, 4, self.h, self.w, device=rgb.device, dtype=torch.float32)
+        out = torch.empty(self.K, 4, self.h, self.w, device=rgb.device, dtype=torch.float32)
         rgb = rgb.to(torch.float32).contiguous()
-        assert tuple(rgb.shape) == (1, 3, self.H, self.W)
+        assert tuple(rgb.shape) == (self.K, 3, self.H, self.W)
         L.check(self._lib.mg_model_vae_encode(self.handle, rgb.data_ptr(), out.data_ptr(), O.current_stream_handle()), "mg_model_vae_encode")
         return out
 
     def denoise(self, rgb_latent, x, step_noises=None):
+        """``rgb_latent`` [K, 4, h, w]; ``x`` [K B, C, h, w], image-major; ``step_noises``: ``n_noise`` tensors shaped like ``x``."""
         x = x.to(torch.float32).contiguous().clone()
+        assert rgb_latent.shape[0] == self.K and x.shape[0] == self.K * self.B
         nz = None
         if self.n_noise:
             nz = torch.stack(list(step_noises)).to(torch.float32).contiguous()
-            assert nz.shape[0] == self.n_noise
+            assert nz.shape[0] == self.n_noise and nz.shape[1:] == x.shape
         L.check(self._lib.mg_model_denoise(self.handle, rgb_latent.contiguous().data_ptr(), x.data_ptr(),
                                            None if nz is None else nz.data_ptr(), O.current_stream_handle()), "mg_model_denoise")
         return x
 
     def decode(self, latent):
-        out = torch.empty(self.B, self.pred_channels, self.Hout, self.Wout, device=latent.device, dtype=torch.float32)
+        out = torch.empty(self.K * self.B, self.pred_channels, self.Hout, self.Wout, device=latent.device, dtype=torch.float32)
         L.check(self._lib.mg_model_vae_decode(self.handle, latent.to(torch.float32).contiguous().data_ptr(), out.data_ptr(),
                                               O.current_stream_handle()), "mg_model_vae_decode")
         return out
@@ -324,6 +341,43 @@ class ModelImage:
                                                pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle()),
                 "mg_model_predict_out", self._lib)
         return pred, unc, d16, pic, list(info)
+
+    def predict_many(self, u8s, seeds, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False, opts=None, mode=0, reciprocal=None):
+        """``mg_model_predict_many`` on n <= K uint8 CUDA pictures ``u8s`` (each [Hin, Win, 3], one size) with one seed each: what
+        ``predict_out`` returns, stacked image-major -> (pred fp32 [n, C, out_h, out_w] clipped, unc fp32 [n, Hout, Wout] | None for a
+        single member, u16 uint16 [n, out_h, out_w] | None unless ``u16``, picture uint8 [n, out_h, out_w, 3] | None unless
+        ``picture``, info = n lists of the four numbers of ``mg_ensemble_depth``).  The other arguments are ``predict_out``'s and
+        apply to every picture."""
+        u8s, seeds = list(u8s), list(seeds)
+        n = len(u8s)
+        assert n >= 1 and len(seeds) == n, "predict_many: one seed per picture"
+        for u8 in u8s:
+            assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_many: uint8 CUDA [H, W, 3] pictures"
+            assert u8.shape == u8s[0].shape, "predict_many: the pictures of one call have one size"
+        u8s = [u8.contiguous() for u8 in u8s]
+        Hin, Win = u8s[0].shape[:2]
+        if reciprocal is None:
+            reciprocal = (Hin, Win) != (self.H, self.W)
+        oh, ow = (self.Hout, self.Wout) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        if lut is not None:
+            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_many: the colour table is uint8 CUDA [256, 3]"
+            lut = lut.contiguous()
+        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
+                                  None if lut is None else lut.data_ptr())
+        dev = u8s[0].device
+        pred = torch.empty(n, self.pred_channels, oh, ow, device=dev, dtype=torch.float32)
+        unc = torch.empty(n, self.Hout, self.Wout, device=dev, dtype=torch.float32) if self.B > 1 else None
+        d16 = torch.empty(n, oh, ow, device=dev, dtype=torch.uint16) if u16 else None
+        pic = torch.empty(n, oh, ow, 3, device=dev, dtype=torch.uint8) if picture else None
+        info = (ctypes.c_double * (4 * n))()
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        L.check(self._lib.mg_model_predict_many(self.handle, n, (ctypes.c_void_p * n)(*[u8.data_ptr() for u8 in u8s]), 1, Hin, Win,
+                                                int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
+                                                (ctypes.c_uint64 * n)(*[int(s) & ((1 << 64) - 1) for s in seeds]),
+                                                None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
+                                                pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle()),
+                "mg_model_predict_many", self._lib)
+        return pred, unc, d16, pic, [list(info[4 * i:4 * i + 4]) for i in range(n)]
 
     def close(self):
         if self.handle:
