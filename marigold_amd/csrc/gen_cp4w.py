@@ -17,8 +17,8 @@ One K tile = (channel tile c, tap t): 64 input channels of one tap.  Per tile k 
   gap R2       s_waitcnt vmcnt(n) lgkmcnt(0) ; s_barrier  the weights of tile k + 1 (and, by then, every older piece) landed
   gap N0..     ds_read F[0], F[1] of tile k + 1
 
-Counted waits come from queue models of the LDS and VMEM streams (an item's wait = the number of later-issued items of its
-queue), so a schedule edit cannot silently leave a wait short.  Scratch registers of the VALU sequences are the PHYSICAL
+The tile skeleton is gen_k4w.py's (tile), the counted waits come from the queue model of asmstream.py (an item's wait = the
+number of later-issued items of its queue), so a schedule edit cannot silently leave a wait short.  Scratch registers of the VALU sequences are the PHYSICAL
 registers v228-v255 (clobbered): an asm operand cannot name the dwords of a 128-bit tuple.
 
 Operands (bound in conv_patch4w.hip): c<ni><mi> accumulators; a<ks><mi> / b<ks><ni> fragments; pa<mi><ks> pixel-side read
@@ -30,31 +30,26 @@ channels.
 """
 import sys
 
+from asmstream import define
+from gen_k4w import Geo as TileGeo, assert_closed, prologue, tile
+
 STATS = []
 
 
-class Geo:
+class Geo(TileGeo):
+    """the tile of gen_k4w.py with the pixel side read from the resident patch: absolute read addresses (no toggle), weight
+    pieces only in the per-tile DMA"""
+
     def __init__(self, prefix, mi, ni):
-        self.prefix, self.MI, self.NI = prefix, mi, ni
-        self.GS = mi * ni            # MFMAs per k-step
-        self.NM = 4 * self.GS        # MFMAs per K tile
-        self.NW = ni * 2             # weight pieces per wave (BN * 8 / 256 = NI * 2 * 32 * 8 / 256)
+        super().__init__(prefix, mi, ni)
+        self.ND = ni * 2             # weight pieces per wave (BN * 8 / 256 = NI * 2 * 32 * 8 / 256)
 
+    def reads(self, ks):
+        return ([f"ds_read_b128 %[a{ks}{i}], %[pa{i}{ks}]" for i in range(self.MI)] +
+                [f"ds_read_b128 %[b{ks}{i}], %[lb{ks}] offset:{i * 4096}" for i in range(self.NI)])
 
-def mfma(G, g):
-    ks, ni, mi = g // G.GS, (g % G.GS) // G.MI, g % G.MI
-    return f"v_mfma_f32_32x32x16_bf16 %[c{ni}{mi}], %[b{ks}{ni}], %[a{ks}{mi}], %[c{ni}{mi}]"
-
-
-def reads(G, ks):
-    """fragment set F[ks]: (text, queue tag)"""
-    out = [(f"ds_read_b128 %[a{ks}{i}], %[pa{i}{ks}]", f"F{ks}") for i in range(G.MI)]
-    out += [(f"ds_read_b128 %[b{ks}{i}], %[lb{ks}] offset:{i * 4096}", f"F{ks}") for i in range(G.NI)]
-    return out
-
-
-def toggles(ks):
-    return [f"v_xor_b32 %[lb{ks}], %[xb{ks}], %[lb{ks}]"]
+    def toggles(self, ks):
+        return [f"v_xor_b32 %[lb{ks}], %[xb{ks}], %[lb{ks}]"]
 
 
 def addr_ops(G):
@@ -84,7 +79,7 @@ def fix_vec(it, useq):
     ops = []
     first = True
     for j in range(4):     # the two halves of a dword interleaved: a transcendental's result is read two instructions
-        w = U + j          # later (gfx940-family TRANS -> VALU forwarding hazard: one wait state, which nothing inserts here)
+        w = U + j          # later (asmstream.check_hazards)
         xa, xb, ta, tb = X + 2 * j, X + 2 * j + 1, T + 2 * j, T + 2 * j + 1
         seq = [f"v_lshlrev_b32 v{xa}, 16, v{w}",
                f"v_and_b32 v{xb}, 0xffff0000, v{w}",
@@ -114,157 +109,58 @@ def fix_vec(it, useq):
 
 
 def block(G, mode, npatch, fix_its, p):
-    """mode: 'full' | 'nodma' | 'last'.  npatch: patch pieces (operands vp0..) staged in this tile; fix_its: fix-up vectors."""
-    NM = G.NM
-    slots = [[] for _ in range(2 * NM + 1)]      # slot 2g: in front of MFMA g, slot 2g + 1: behind it, slot 2 NM: tail
-    def put(slot, text, kind="op", tag=None):
-        slots[slot].append((text, kind, tag))
-    nF = G.MI + G.NI
-    put(0, None, "wait_lds", "F0")
-    # F[2], F[3] of this tile, two per gap
-    cur = reads(G, 2) + reads(G, 3)
-    g = 0
-    while cur:
-        for _ in range(2):
-            if cur:
-                t, tag = cur.pop(0)
-                put(2 * g + 1, t, "lds", tag)
-        g += 1
-    g_reads_end = g
-    for t in toggles(2):
-        put(2 * g_reads_end + 1, t)
-    for t in toggles(3):
-        put(2 * (g_reads_end + 1) + 1, t)
+    """mode: 'full' | 'nodma' | 'last'.  npatch: patch pieces (operands vp0..) staged in this tile; fix_its: fix-up vectors.
+    The tile of gen_k4w.py (two fragment reads per gap) plus: patch pieces in front of the weight pieces, VALU fillers between
+    the fragment reads and n0, the fix-up's LDS traffic retired at r2."""
+    NM, nF = G.NM, G.NF
     r1, r2, n0 = p["r1"], NM - 2 * nF - 2 + p["r2off"], NM - 2 * nF - 1 + p["r2off"]
-    assert r1 > g_reads_end and n0 + 2 * nF <= NM
-    if mode == "last":
-        put(2 * r1, None, "wait_lds", "ALL")
-        return finish(G, slots, mode, [], [])
-    put(2 * r1, None, "wait_lds", "ALL")
-    put(2 * r1, "s_barrier")
-    # ---- LDS-DMA: patch pieces first, then the weight pieces of tile k + 2 ----
+    assert r1 > nF and n0 + 2 * nF <= NM
+    # ---- LDS-DMA: patch pieces first, then the weight pieces of tile k + 2, one piece every dstep gaps from r1 + 1 ----
+    # (a patch piece is not waited for in its own tile: the wait for the weights of tile k + 1 in the NEXT tile retires it)
     dma = []
     if mode == "full":
         for j in range(npatch):
             dma.append((f"s_add_u32 m0, %[mp], {j * 4096}", f"buffer_load_dwordx4 %[vp{j}], %[sp], 0 offen lds", "P"))
-        for i in range(G.NW):
-            dma.append((f"s_add_u32 m0, %[mw], {i * 4096}", f"buffer_load_dwordx4 %[vb{i}], %[sw], 0 offen lds", "W2"))
-    g = r1 + 1
-    for (a, b, tag) in dma:
-        put(2 * g, a)
-        put(2 * g + 1, b, "vmem", tag)
-        g += p["dstep"]
-    assert g - p["dstep"] < NM, (g, NM)
-    # ---- VALU fillers: next tile's pixel-side addresses, then the fix-up slice ----
-    # pa<mi><2,3> are read by this tile's F[2] / F[3] reads (gaps < g_reads_end): fillers start behind them.  Everything -
-    # the addresses the F[0] / F[1] reads of tile k + 1 use, and every LDS operation of the fix-up (the next stream's entry
-    # wait counts only fragment reads) - sits in front of n0.  A fix-up vector's ds_read is issued LEAD fillers ahead of its
-    # first use (LDS latency under the MFMAs, not in front of them).
-    LEAD = 14
-    fill = [(t, "op", None) for t in addr_ops(G)]
-    for q, it in enumerate(fix_its):
-        rd, ops = fix_vec(it, q)
-        pos = max(0, len(fill) - LEAD)
-        fill.insert(pos, rd)
-        fill += ops
-    s0 = 2 * (g_reads_end + 2)
-    free = [sl for sl in range(s0, 2 * n0) if not any(x[1].startswith("wait") or x[0] == "s_barrier" for x in slots[sl])]
-    per = max(1, -(-len(fill) // max(1, len(free))))
-    assert per <= p["max_per_slot"], f"{G.prefix} {mode} fix {fix_its}: {len(fill)} fillers in {len(free)} slots"
-    # spread evenly over the free slots (Bresenham): a dense front would starve the matrix pipe early and idle late
-    fi = 0
-    for n, sl in enumerate(free):
-        want = (len(fill) * (n + 1)) // len(free)
-        while fi < want:
-            t, kind, tag = fill[fi]
-            fi += 1
-            if kind == "waitfix":
-                put(sl, None, "wait_lds", tag)
-                kind = "op"
-            put(sl, t, kind, tag)
-    STATS.append((G.prefix, mode, npatch, fix_its, len(fill), len(free)))
-    assert fi == len(fill)
-    # ---- tile k + 1 has landed: its first two fragment sets ----
-    put(2 * r2, None, "wait_vm", "W1")
-    put(2 * r2, None, "wait_lds_before_reads", None)
-    put(2 * r2, "s_barrier")
-    nxt = reads(G, 0) + reads(G, 1)
-    g = n0
-    while nxt:
-        t, tag = nxt.pop(0)
-        put(2 * g + 1, t, "lds", tag + "n")
-        g += 1
-    for t in toggles(0) + toggles(1):
-        put(2 * NM, t)
-    return finish(G, slots, mode, ["W1"] * G.NW, [])
+        for i in range(G.ND):
+            dma.append((f"s_add_u32 m0, %[mw], {i * 4096}", f"buffer_load_dwordx4 %[vb{i}], %[sw], 0 offen lds", "T2"))
+    dma = [(r1 + 1 + k * p["dstep"],) + d for k, d in enumerate(dma)]
+    assert not dma or dma[-1][0] < NM, (dma[-1][0], NM)
 
+    def fill(sl, g_reads_end):
+        # ---- VALU fillers: next tile's pixel-side addresses, then the fix-up slice ----
+        # pa<mi><2,3> are read by this tile's F[2] / F[3] reads (gaps < g_reads_end): fillers start behind them.  Everything -
+        # the addresses the F[0] / F[1] reads of tile k + 1 use, and every LDS operation of the fix-up (the next stream's entry
+        # wait counts only fragment reads) - sits in front of n0.  A fix-up vector's ds_read is issued LEAD fillers ahead of its
+        # first use (LDS latency under the MFMAs, not in front of them).
+        LEAD = 14
+        fill = [(t, "op", None) for t in addr_ops(G)]
+        for q, it in enumerate(fix_its):
+            rd, ops = fix_vec(it, q)
+            pos = max(0, len(fill) - LEAD)
+            fill.insert(pos, rd)
+            fill += ops
+        s0 = 2 * (g_reads_end + 2)
+        free = [s for s in range(s0, 2 * n0) if not any(x[1].startswith("wait") or x[0] == "s_barrier" for x in sl.slots[s])]
+        per = max(1, -(-len(fill) // max(1, len(free))))
+        assert per <= p["max_per_slot"], f"{G.prefix} {mode} fix {fix_its}: {len(fill)} fillers in {len(free)} slots"
+        # spread evenly over the free slots (Bresenham): a dense front would starve the matrix pipe early and idle late
+        fi = 0
+        for n, s in enumerate(free):
+            want = (len(fill) * (n + 1)) // len(free)
+            while fi < want:
+                t, kind, tag = fill[fi]
+                fi += 1
+                if kind == "waitfix":
+                    # (r1=14 puts the release barrier's lgkmcnt(0) between a vector's read and this wait: the wait is kept)
+                    sl.put(s, None, "wait_lds", tag, "emit")
+                    kind = "op"
+                sl.put(s, t, kind, tag)
+        STATS.append((G.prefix, mode, npatch, fix_its, len(fill), len(free)))
+        assert fi == len(fill)
 
-def finish(G, slots, mode, vm_queue0, _):
-    """linearise, resolve the counted waits"""
-    NM = G.NM
-    nF = G.MI + G.NI
-    lin = []
-    for g in range(NM):
-        lin += slots[2 * g]
-        lin.append((mfma(G, g), "mfma", None))
-        lin += slots[2 * g + 1]
-    lin += slots[2 * NM]
-    # queues at tile entry: LDS = F[0] then F[1] reads of this tile (issued at the end of the previous stream);
-    # VMEM = the weight pieces of tile k + 1
-    ldsq = ["F0"] * nF + ["F1"] * nF
-    vmq = list(vm_queue0)
-    out = []
-    for (t, kind, tag) in lin:
-        if kind == "lds":
-            ldsq.append(tag)
-            out.append(t)
-        elif kind == "vmem":
-            vmq.append(tag)
-            out.append(t)
-        elif kind == "wait_lds":
-            if tag == "ALL":
-                n = 0
-            else:
-                idx = max(i for i, x in enumerate(ldsq) if x == tag)
-                n = len(ldsq) - 1 - idx
-            assert n <= 15
-            out.append(f"s_waitcnt lgkmcnt({n})")
-        elif kind == "wait_lds_before_reads":
-            # the fix-up's LDS traffic of this tile is retired before the next tile's fragment reads are queued: the next
-            # stream's entry wait counts only those reads
-            out.append("s_waitcnt lgkmcnt(0)")
-        elif kind == "wait_vm":
-            idxs = [i for i, x in enumerate(vmq) if x == tag]
-            n = len(vmq) - 1 - max(idxs) if idxs else len(vmq)
-            out.append(f"s_waitcnt vmcnt({n})")
-        else:
-            out.append(t)
-    if mode == "last":
-        out += ["s_nop 7", "s_nop 7", "s_nop 7"]   # MFMA results -> the epilogue's v_accvgpr_read (see gen_k4w.py)
-    return out
-
-
-def prologue(G):
-    out = [t for (t, _) in reads(G, 0) + reads(G, 1)]
-    return out + toggles(0) + toggles(1)
-
-
-
-def c_literal(ln):
-    """One instruction as a C string literal; the operand-type mnemonics come from common.h (MG_MFMA32_ASM, MG_CVT_PK_ASM: bf16 in the
-    product build, fp16 in the fp16 build) as adjacent literals."""
-    for mnem, macro in (("v_mfma_f32_32x32x16_bf16", "MG_MFMA32_ASM"), ("v_cvt_pk_bf16_f32", "MG_CVT_PK_ASM")):
-        if ln.startswith(mnem + " "):
-            return macro + ' "' + ln[len(mnem):]
-    return '"' + ln
-
-
-def emit(name, lines):
-    out = [f"#define {name} \\"]
-    for ln in lines:
-        out.append(f'  {c_literal(ln)}\\n" \\')
-    out.append('  ""')
-    return "\n".join(out)
+    # at r2 the fix-up's LDS traffic of this tile is retired before the next tile's fragment reads are queued: the next stream's
+    # entry wait counts only those reads
+    return tile(G, mode, 2, r1, r2, n0, dma, fill, drain_lds_at_r2=True)
 
 
 def main():
@@ -281,22 +177,24 @@ def main():
         # ONE statement for the steady state: the stream variants side by side behind a scalar dispatch on %[sel] (0 plain,
         # 1 patch staging, 2.. fix-up slices).  As separate asm statements in a switch hipcc spilled the accumulators and
         # fragment sets around every branch (100+ scratch_store_dwordx4 per tile).
-        variants = [block(G, "full", 0, (), p)] + [block(G, "full", n, (), p) for n in patches] + \
-                   [block(G, "full", 0, its, p) for its in fixsets]
+        # (stream, LDS items, VMEM items it leaves in flight in front of the next tile's: a fix-up slice's last ds_write falls
+        # behind the landed barrier, the patch pieces are waited for a tile later - both retired, in order, by the next stream)
+        variants = [(block(G, "full", 0, (), p), [], [])] + [(block(G, "full", n, (), p), [], ["P"] * n) for n in patches] + \
+                   [(block(G, "full", 0, its, p), [f"fixw{its[-1]}"], []) for its in fixsets]
         loop = []
         for i in range(1, len(variants)):
             loop += [f"s_cmp_eq_u32 %[sel], {i}", f"s_cbranch_scc1 .Lcp4_%=_{i}"]
-        for i, v in enumerate(variants):
+        for i, (v, _, _) in enumerate(variants):
             if i:
                 loop.append(f".Lcp4_%=_{i}:")
-            loop += v
+            loop += v.lines
             if i + 1 < len(variants):
                 loop.append(f"s_branch .Lcp4_%=_end")
         loop.append(".Lcp4_%=_end:")
-        txt += [emit(f"{P}_LOOP", loop), ""]
-        txt += [emit(f"{P}_NODMA", block(G, "nodma", 0, (), p)), ""]
-        txt += [emit(f"{P}_LAST", block(G, "last", 0, (), p)), ""]
-        txt += [emit(f"{P}_PROLOGUE", prologue(G)), ""]
+        nodma, last, pro = block(G, "nodma", 0, (), p), block(G, "last", 0, (), p), prologue(G)
+        assert_closed(G, pro, variants, nodma, last)      # (whichever variant %[sel] picks)
+        for name, lines in (("LOOP", loop), ("NODMA", nodma.lines), ("LAST", last.lines), ("PROLOGUE", pro.lines)):
+            txt += [define(f"{P}_{name}", lines), ""]
     print("\n".join(txt))
     for st in STATS:
         print("stats", st, file=sys.stderr)

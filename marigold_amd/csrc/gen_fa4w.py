@@ -30,10 +30,12 @@ VALU operands.  One iteration t = one tile = 32 MFMAs in eight groups SG0..SG7 o
 Stream = ENTRY, LOOP x cnt {FULL}, NODMA(vmcnt 4), NODMA(vmcnt 0), LAST        (cnt = nkt - 3 >= 1)
 """
 import sys
+from collections import namedtuple
+
+from asmstream import MFMA_RESULT_TAIL, Stream, define, renamed
 
 X = {0: 128, 1: 144}      # score set of a tile's half 0: query block -> first register
 Y = {0: 160, 1: 176}
-MFMA = "v_mfma_f32_32x32x16_bf16"
 
 
 def vt(b, n):
@@ -42,7 +44,7 @@ def vt(b, n):
 
 def vgroup(R, la, lb):
     """exp2, row sums and packing of the eight scores in v[R : R + 7]; P ends up in v[R : R + 3].  A transcendental's result is
-    never read by the next instruction (gfx940-family TRANS -> VALU hazard: one wait state, nothing inserts it here)."""
+    never read by the next instruction (asmstream.check_hazards)."""
     r = [f"v{R + j}" for j in range(8)]
     return [
         f"v_exp_f32 {r[0]}, {r[0]}",
@@ -68,141 +70,6 @@ def vgroup(R, la, lb):
     ]
 
 
-class Stream:
-    def __init__(self, queue):
-        self.out = []
-        self.queue = list(queue)     # LDS reads in flight, oldest first (fragment buffer names)
-
-    def op(self, text):
-        self.out.append(text)
-
-    def read(self, buf, ad, off):
-        self.out.append(f"ds_read_b128 %[{buf}], %[ad{ad}] offset:{off}")   # (ad0..ad3: the 32x32x16 stream; adk0..3 / adv0,1: the 16x16x32 one)
-        assert buf not in self.queue, buf
-        self.queue.append(buf)
-        assert len(self.queue) <= 15
-
-    def need(self, buf):
-        if buf in self.queue:
-            p = self.queue.index(buf)
-            self.out.append(f"s_waitcnt lgkmcnt({len(self.queue) - 1 - p})")
-            self.queue = self.queue[p + 1:]
-
-    def drain(self):
-        if self.queue:
-            self.out.append("s_waitcnt lgkmcnt(0)")
-            self.queue = []
-
-
-KOFF0, KOFF1, VOFF = 0, 4096, 8192     # inside a slot: K of this tile's half 1, K of the next tile's half 0, V^T
-
-
-def entry_reads(st):
-    """The fragments SG0 of an iteration starts from, out of the slot the address registers point at."""
-    st.read("kf0", 0, KOFF0)
-    st.read("kf1", 1, KOFF0)
-    st.read("vf0", 0, VOFF)
-    st.read("vf1", 0, VOFF + 4096)
-
-
-def entry_reads2(st):
-    st.read("kf2", 2, KOFF0)
-    st.read("kf3", 3, KOFF0)
-    st.read("vf2", 1, VOFF)
-    st.read("vf3", 1, VOFF + 4096)
-
-
-def block(kind, queue):
-    """kind: 'full' (LDS-DMA of slot t + 3) | 'nodma4' | 'nodma0' (no DMA; tail waits vmcnt(4) / vmcnt(0)) | 'last'."""
-    st = Stream(queue)
-    last = kind == "last"
-    dma = {}
-    if kind == "full":
-        dma = {1: ("vk0", "srk", "sok", 0), 2: ("vk1", "srk", "sok", 4096), 3: ("vv0", "srv", "sov", 8192), 4: ("vv1", "srv", "sov", 12288)}
-    for i in range(8):
-        half = i >> 2
-        cur = X if half == 0 else Y          # scores being consumed
-        nxt = Y if half == 0 else X          # scores being produced (this tile's half 1 / the next tile's half 0)
-        q = (i >> 1) & 1                     # SG0,1 / SG4,5: query block 0;  SG2,3 / SG6,7: query block 1
-        pair = i & 1                         # k-steps (2 pair, 2 pair + 1) of the QK^T chain; group 2 half + pair of P V
-        qk, pv = [], []
-        if not (last and half == 1):
-            for ks in (2 * pair, 2 * pair + 1):
-                D = vt(nxt[q], 16)
-                C = f"%[ng{q}]" if ks == 0 else D
-                qk.append((f"{MFMA} {D}, %[kf{ks}], %[q{q}{ks}], {C}", f"kf{ks}"))
-        P = vt(cur[q] + 8 * pair, 4)
-        vb = 2 * pair                        # V^T buffers: vf0, vf1 for a half's first group, vf2, vf3 for its second
-        for d in (0, 1):
-            pv.append((f"{MFMA} %[o{q}{d}], %[vf{vb + d}], {P}, %[o{q}{d}]", f"vf{vb + d}"))
-        # QK, PV, QK, PV: the two k-steps of one score accumulator are not back to back, every P V MFMA has an MFMA and five
-        # VALU instructions between the packing of its P and itself
-        mf = [qk[0], pv[0], qk[1], pv[1]] if qk else pv
-        # the VALU stream: P of the group whose P V MFMAs come in the NEXT group of MFMAs
-        j = i + 1
-        if j < 8:
-            jh, jq, jp = j >> 2, (j >> 1) & 1, j & 1
-            va = vgroup((X if jh == 0 else Y)[jq] + 8 * jp, f"%[l{jq}0]", f"%[l{jq}1]")
-        elif not last:
-            va = vgroup(X[0], "%[l00]", "%[l01]")       # (q0, first group) of the next tile
-        else:
-            va = []
-        n = len(mf)
-        per = -(-len(va) // n) if va else 0
-        for k, (text, buf) in enumerate(mf):
-            first = k == 0
-            if first and i in dma:
-                st.op(f"s_add_u32 m0, %[mb], {dma[i][3]}")
-            if last and half == 1 and first:
-                st.op("s_nop 4")      # (no QK^T pair in front of this P V pair: the wait states behind the VALU that packed its P)
-            st.need(buf)
-            st.op(text)
-            if first and i in dma:
-                vo, srd, so, _ = dma[i]
-                st.op(f"buffer_load_dwordx4 %[{vo}], %[{srd}], %[{so}] offen lds")
-                if i == 2:
-                    st.op("s_add_u32 %[sok], %[sok], %[kst]")
-                if i == 4:
-                    st.op("s_add_u32 %[sov], %[sov], 128")
-                    st.op("s_add_u32 %[mb], %[mb], 0x4000")
-                    st.op("s_and_b32 %[mb], %[mb], 0xffff")
-            for text2 in va[k * per:(k + 1) * per]:
-                st.op(text2)
-            qk_done = (not (last and half == 1)) and k == 2       # behind the group's second QK^T MFMA
-            pv_done = k == n - 1
-            # fragment reloads, as soon as the buffer's last MFMA has issued (q1's groups: SG2, SG3 / SG6, SG7)
-            if i == 2 and qk_done and not last:
-                st.read("kf0", 0, KOFF1)
-                st.read("kf1", 1, KOFF1)
-            if i == 3 and qk_done and not last:
-                st.read("kf2", 2, KOFF1)
-                st.read("kf3", 3, KOFF1)
-            if i == 2 and pv_done:
-                st.read("vf0", 2, VOFF)
-                st.read("vf1", 2, VOFF + 4096)
-            if i == 3 and pv_done:
-                st.read("vf2", 3, VOFF)
-                st.read("vf3", 3, VOFF + 4096)
-        if i == 6 and not last:
-            # slot t + 1 has landed for everybody, slot t - 1 is free; the address registers move on
-            st.drain()
-            st.op("s_waitcnt vmcnt(%d)" % {"full": 8, "nodma4": 4, "nodma0": 0}[kind])
-            st.op("s_barrier")
-            for jj in range(4):
-                st.op(f"v_add_u32 %[ad{jj}], 0x4000, %[ad{jj}]")
-                st.op(f"v_and_b32 %[ad{jj}], 0xffff, %[ad{jj}]")
-            entry_reads(st)
-        if i == 7 and not last:
-            entry_reads2(st)
-    if last:
-        st.drain()
-        st.op("s_nop 7")
-        st.op("s_nop 7")
-        st.op("s_nop 7")
-    return st.out, st.queue
-
-
-
 # ---------------------------------------------------------------------------------------------------------------------------
 # The same loop on v_mfma_f32_16x16x32 (round 6, FA4W16_ASM; flash4w.hip, variant 27).  Why: the chip is power-limited under
 # matrix load and this kernel's operands are on the CU (registers / LDS) - the regime in which a wave-tile step on 16x16x32
@@ -224,7 +91,6 @@ def block(kind, queue):
 #   the `pair` = 0 groups carry two more MFMAs: the row sums of their two query blocks (below).
 X16 = {q: 128 + 8 * q for q in range(4)}
 Y16 = {q: 160 + 8 * q for q in range(4)}
-MFMA16 = "v_mfma_f32_16x16x32_bf16"
 
 
 # Row sums on the matrix pipe: one MFMA of P against ones per (query block, half) - every row of the 16 x 16 result is the sum over
@@ -234,7 +100,7 @@ MFMA16 = "v_mfma_f32_16x16x32_bf16"
 # (72 MFMAs per wave-tile): 1 201 / 1 278 TFLOP/s (whole blocks / key-split) against 1 130 / 1 193 at E = 10, 9 216 tokens
 # (profiles/r6_flash_mfma16.log).  The same trade LOST in the 32x32x16 stream (a third 32-cycle MFMA per pair, round 4).
 def vgroup_noadd(R):
-    """exp2 and packing only (the row sums are an MFMA against ones); a transcendental's result is not read by the next instruction"""
+    """exp2 and packing only (the row sums are an MFMA against ones)"""
     r = [f"v{R + j}" for j in range(8)]
     return [f"v_exp_f32 {r[0]}, {r[0]}", f"v_exp_f32 {r[1]}, {r[1]}", f"v_exp_f32 {r[2]}, {r[2]}",
             f"v_cvt_pk_bf16_f32 {r[0]}, {r[0]}, {r[1]}", f"v_exp_f32 {r[3]}, {r[3]}", f"v_exp_f32 {r[4]}, {r[4]}",
@@ -242,187 +108,186 @@ def vgroup_noadd(R):
             f"v_exp_f32 {r[7]}, {r[7]}", f"v_cvt_pk_bf16_f32 {r[2]}, {r[4]}, {r[5]}", f"v_cvt_pk_bf16_f32 {r[3]}, {r[6]}, {r[7]}"]
 
 
-def vg16(R, q):
-    return vgroup_noadd(R)
+KOFF0, KOFF1, VOFF = 0, 4096, 8192     # inside a slot: K of this tile's half 1, K of the next tile's half 0, V^T
+
+# What distinguishes the two forms of the loop.  An iteration is eight groups SG i = (half = i >> 2, qp = (i >> 1) & 1, pair = i & 1)
+# of QK^T MFMAs (two chain steps x the group's query blocks, scores of `nxt`) interleaved with as many P V MFMAs (query blocks x two
+# V^T fragments, probabilities of `cur`); both use the fragments kf / vf [2 pair], [2 pair + 1].
+#   nq        query blocks per group: blocks nq qp ... nq qp + nq - 1
+#   X, Y      the score sets: query block -> first register
+#   qk_dst    (set, q, pair) -> the score registers a QK^T MFMA accumulates into
+#   qk_step   (pair, step) -> the step of the score chain (operand q<q><step>; step 0 takes -reference, %[ng<q>], as C)
+#   pv_src    (set, q, pair) -> the packed probabilities a P V MFMA reads
+#   o_idx     (pair, j) -> the output block of V^T fragment vf[2 pair + j]
+#   kad       address operands ad<..> of the four K fragments
+#   vad       per V^T fragment: (address operand, offset) for an iteration's first half and for its second
+#   bump      the address operands that move on to the next ring slot
+#   valu      (i, last) -> the VALU instructions spread over group i's MFMAs;  pre: those in front of the loop
+#   rowsum_mfma   the row sums ride on the matrix pipe: one more MFMA (P against ones) per query block in the pair-0 groups
+Form = namedtuple("Form", "macro label mfma nq X Y qk_dst qk_step pv_src o_idx kad vad bump valu pre rowsum_mfma")
 
 
-def entry_reads16(st):
-    st.read("kf0", "k0", KOFF0)
-    st.read("kf1", "k1", KOFF0)
-    st.read("vf0", "v0", VOFF)
-    st.read("vf1", "v0", VOFF + 2048)
+def valu32(i, last):
+    """P of the group whose P V MFMAs come in the NEXT group of MFMAs"""
+    j = i + 1
+    if j < 8:
+        jh, jq, jp = j >> 2, (j >> 1) & 1, j & 1
+        return vgroup((X if jh == 0 else Y)[jq] + 8 * jp, f"%[l{jq}0]", f"%[l{jq}1]")
+    return [] if last else vgroup(X[0], "%[l00]", "%[l01]")       # (q0, first group) of the next tile
 
 
-def entry_reads16b(st):
-    st.read("kf2", "k2", KOFF0)
-    st.read("kf3", "k3", KOFF0)
-    st.read("vf2", "v0", VOFF + 4096)
-    st.read("vf3", "v0", VOFF + 6144)
+def valu16(i, last):
+    half, s = i >> 2, i & 3
+    cur, nxt = (X16, Y16) if half == 0 else (Y16, X16)
+    if s < 2:
+        return vgroup_noadd(cur[2 + s])
+    return [] if last and half == 1 else vgroup_noadd(nxt[s - 2])
 
 
-def block16(kind, queue):
-    st = Stream(queue)
+FA32 = Form("FA4W_ASM", ".Lfa4w_loop%=", "v_mfma_f32_32x32x16_bf16", 1, X, Y,
+            qk_dst=lambda S, q, pair: vt(S[q], 16), qk_step=lambda pair, step: 2 * pair + step,
+            pv_src=lambda S, q, pair: vt(S[q] + 8 * pair, 4), o_idx=lambda pair, j: j,
+            kad=("0", "1", "2", "3"),
+            vad=([("0", VOFF), ("0", VOFF + 4096), ("1", VOFF), ("1", VOFF + 4096)],
+                 [("2", VOFF), ("2", VOFF + 4096), ("3", VOFF), ("3", VOFF + 4096)]),
+            bump=("0", "1", "2", "3"), valu=valu32, pre=vgroup(X[0], "%[l00]", "%[l01]"), rowsum_mfma=False)
+FA16 = Form("FA4W16_ASM", ".Lfa4w16_loop%=", "v_mfma_f32_16x16x32_bf16", 2, X16, Y16,
+            qk_dst=lambda S, q, pair: vt(S[q] + 4 * pair, 4), qk_step=lambda pair, step: step,
+            pv_src=lambda S, q, pair: vt(S[q], 4), o_idx=lambda pair, j: 2 * pair + j,
+            kad=("k0", "k1", "k2", "k3"),
+            vad=([("v0", VOFF + 2048 * j) for j in range(4)], [("v1", VOFF + 2048 * j) for j in range(4)]),
+            bump=("k0", "k1", "k2", "k3", "v0", "v1"), valu=valu16, pre=vgroup_noadd(X16[0]) + vgroup_noadd(X16[1]),
+            rowsum_mfma=True)
+
+# Queue tags.  LDS: the fragment buffer a ds_read_b128 fills (kf0-3, vf0-3).  VMEM: S<n> = the four LDS-DMA pieces of ring slot
+# t + n.  The stream is entered with slots 0, 1, 2 in flight: flash4w.hip issues two reference pieces and then, `for (int sl = 0;
+# sl < 3; ++sl)`, four pieces per slot, and its `s_waitcnt vmcnt(12)` + barrier in front of the stream leave exactly those twelve.
+# An iteration is entered with slots t + 1, t + 2 in flight, issues slot t + 3 and waits for t + 1:
+NEXT = {"S2": "S1", "S3": "S2"}
+DMA = {1: ("vk0", "srk", "sok", 0), 2: ("vk1", "srk", "sok", 4096), 3: ("vv0", "srv", "sov", 8192), 4: ("vv1", "srv", "sov", 12288)}
+
+
+def read(st, buf, ad, off):
+    assert buf not in st.ldsq and len(st.ldsq) < 15, (buf, st.ldsq)      # (this generator's own bound: one wait per buffer)
+    st.lds(f"ds_read_b128 %[{buf}], %[ad{ad}] offset:{off}", buf)
+
+
+def entry_reads(st, F, pair):
+    """The fragments SG `pair` of an iteration starts from, out of the slot the address registers point at."""
+    for b in (2 * pair, 2 * pair + 1):
+        read(st, f"kf{b}", F.kad[b], KOFF0)
+    for b in (2 * pair, 2 * pair + 1):
+        read(st, f"vf{b}", *F.vad[0][b])
+
+
+def drain(st):
+    if st.ldsq:
+        st.wait_lds()
+
+
+def block(F, kind, lds, vm):
+    """kind: 'full' (LDS-DMA of slot t + 3) | 'nodma' | 'last'; lds, vm: the entry queues.  -> the resolved stream"""
+    st = Stream(lds, vm)
     last = kind == "last"
-    dma = {}
-    if kind == "full":
-        dma = {1: ("vk0", "srk", "sok", 0), 2: ("vk1", "srk", "sok", 4096), 3: ("vv0", "srv", "sov", 8192), 4: ("vv1", "srv", "sov", 12288)}
+    dma = DMA if kind == "full" else {}
     for i in range(8):
-        half, s = i >> 2, i & 3
-        qp, pair = s >> 1, s & 1
-        cur = X16 if half == 0 else Y16
-        nxt = Y16 if half == 0 else X16
-        qs = (2 * qp, 2 * qp + 1)
+        half, qp, pair = i >> 2, (i >> 1) & 1, i & 1
+        cur, nxt = (F.X, F.Y) if half == 0 else (F.Y, F.X)     # scores being consumed / produced (this tile's half 1, the next tile's half 0)
+        qs = range(F.nq * qp, F.nq * qp + F.nq)
+        tail_half = last and half == 1                         # no next tile: no QK^T MFMAs
         qk, pv = [], []
-        if not (last and half == 1):
-            for ds in (0, 1):
+        if not tail_half:
+            for step in (0, 1):
                 for q in qs:
-                    D = vt(nxt[q] + 4 * pair, 4)
-                    C = f"%[ng{q}]" if ds == 0 else D
-                    qk.append((f"{MFMA16} {D}, %[kf{2 * pair + ds}], %[q{q}{ds}], {C}", f"kf{2 * pair + ds}"))
+                    ks, D = F.qk_step(pair, step), F.qk_dst(nxt, q, pair)
+                    C = f"%[ng{q}]" if ks == 0 else D
+                    qk.append((f"{F.mfma} {D}, %[kf{2 * pair + step}], %[q{q}{ks}], {C}", f"kf{2 * pair + step}"))
         for q in qs:
             for j in (0, 1):
-                db = 2 * pair + j
-                pv.append((f"{MFMA16} %[o{q}{db}], %[vf{db}], {vt(cur[q], 4)}, %[o{q}{db}]", f"vf{db}"))
+                o = F.o_idx(pair, j)
+                pv.append((f"{F.mfma} %[o{q}{o}], %[vf{2 * pair + j}], {F.pv_src(cur, q, pair)}, %[o{q}{o}]", f"vf{2 * pair + j}"))
+        # QK, PV, QK, PV ...: the steps of one score accumulator are not back to back, every P V MFMA has an MFMA and VALU
+        # instructions between the packing of its P and itself
         mf = [x for pr in zip(qk, pv) for x in pr] if qk else pv
-        if pair == 0:   # the row sums of the pair's two query blocks: P against ones (every row of the block = the sum)
-            mf += [(f"{MFMA16} %[ls{q}], %[ones], {vt(cur[q], 4)}, %[ls{q}]", None) for q in qs]
-        # the VALU stream of this group
-        if s < 2:
-            va = vg16(cur[2 + s], 2 + s)
-        elif not (last and half == 1):
-            va = vg16(nxt[s - 2], s - 2)
-        else:
-            va = []
+        if F.rowsum_mfma and pair == 0:     # P against ones: every row of the block = the sum
+            mf += [(f"{F.mfma} %[ls{q}], %[ones], {vt(cur[q], 4)}, %[ls{q}]", None) for q in qs]
+        va = F.valu(i, last)
         n = len(mf)
-        n_qk_seen = 0
         for k, (text, buf) in enumerate(mf):
             first = k == 0
             if first and i in dma:
                 st.op(f"s_add_u32 m0, %[mb], {dma[i][3]}")
-            if last and half == 1 and first:
+            if tail_half and first:
                 st.op("s_nop 4")      # (no QK^T MFMA in front of this P V MFMA: the wait states behind the VALU that packed its P)
             if buf is not None:
-                st.need(buf)
+                st.wait_lds(buf, "skip")      # (a buffer's second MFMA finds it waited for already)
             st.op(text)
             if first and i in dma:
                 vo, srd, so, _ = dma[i]
-                st.op(f"buffer_load_dwordx4 %[{vo}], %[{srd}], %[{so}] offen lds")
+                st.vmem(f"buffer_load_dwordx4 %[{vo}], %[{srd}], %[{so}] offen lds", "S3")
                 if i == 2:
                     st.op("s_add_u32 %[sok], %[sok], %[kst]")
                 if i == 4:
                     st.op("s_add_u32 %[sov], %[sov], 128")
                     st.op("s_add_u32 %[mb], %[mb], 0x4000")
                     st.op("s_and_b32 %[mb], %[mb], 0xffff")
-            for text2 in va[(len(va) * k) // n:(len(va) * (k + 1)) // n]:
+            for text2 in va[(len(va) * k) // n:(len(va) * (k + 1)) // n]:      # Bresenham over the group's MFMAs
                 st.op(text2)
-            is_qk = bool(qk) and k < 2 * len(qk) and k % 2 == 0
-            if is_qk:
-                n_qk_seen += 1
-            qk_done = bool(qk) and is_qk and n_qk_seen == len(qk)     # behind the group's last QK^T MFMA
-            pv_done = buf is not None and buf.startswith("vf") and (k == n - 1 or mf[k + 1][1] is None)
-            # fragment reloads for the tile's second half, as soon as the buffer's last MFMA has issued (SG2: pair 0, SG3: pair 1)
-            if i == 2 and qk_done and not last:
-                st.read("kf0", "k0", KOFF1)
-                st.read("kf1", "k1", KOFF1)
-            if i == 3 and qk_done and not last:
-                st.read("kf2", "k2", KOFF1)
-                st.read("kf3", "k3", KOFF1)
-            if i == 2 and pv_done:
-                st.read("vf0", "v1", VOFF)
-                st.read("vf1", "v1", VOFF + 2048)
-            if i == 3 and pv_done:
-                st.read("vf2", "v1", VOFF + 4096)
-                st.read("vf3", "v1", VOFF + 6144)
+            # fragment reloads for the iteration's second half, as soon as the buffer's last MFMA has issued (SG2: pair 0, SG3: pair 1)
+            if i in (2, 3):
+                if qk and k == 2 * len(qk) - 2 and not last:                   # behind the group's last QK^T MFMA
+                    for b in (2 * pair, 2 * pair + 1):
+                        read(st, f"kf{b}", F.kad[b], KOFF1)
+                if k == (2 * len(pv) - 1 if qk else len(pv) - 1):              # behind its last P V MFMA
+                    for b in (2 * pair, 2 * pair + 1):
+                        read(st, f"vf{b}", *F.vad[1][b])
         if i == 6 and not last:
             # slot t + 1 has landed for everybody, slot t - 1 is free; the address registers move on
-            st.drain()
-            st.op("s_waitcnt vmcnt(%d)" % {"full": 8, "nodma4": 4, "nodma0": 0}[kind])
+            drain(st)
+            st.wait_vm("S1")
             st.op("s_barrier")
-            for jj in ("k0", "k1", "k2", "k3", "v0", "v1"):
+            for jj in F.bump:
                 st.op(f"v_add_u32 %[ad{jj}], 0x4000, %[ad{jj}]")
                 st.op(f"v_and_b32 %[ad{jj}], 0xffff, %[ad{jj}]")
-            entry_reads16(st)
+            entry_reads(st, F, 0)
         if i == 7 and not last:
-            entry_reads16b(st)
+            entry_reads(st, F, 1)
     if last:
-        st.drain()
-        st.op("s_nop 7")
-        st.op("s_nop 7")
-        st.op("s_nop 7")
-    return st.out, st.queue
+        drain(st)
+        st.lines += MFMA_RESULT_TAIL
+    return st
 
 
-def stream16():
-    lines = ["s_waitcnt lgkmcnt(0)"]
-    lines += vg16(X16[0], 0) + vg16(X16[1], 1)
-    st = Stream([])
-    st.op("s_waitcnt vmcnt(8)")
+def stream(F):
+    """ENTRY, LOOP x cnt {FULL}, NODMA, NODMA, LAST -> (all lines, the lines of FULL)"""
+    st = Stream(vm=["S0"] * 4 + ["S1"] * 4 + ["S2"] * 4)
+    st.wait_lds()
+    for t in F.pre:
+        st.op(t)
+    st.wait_vm("S0")
     st.op("s_barrier")
-    entry_reads16(st)
-    entry_reads16b(st)
-    lines += st.out
-    q0 = st.queue
-    full, qa = block16("full", q0)
-    assert qa == q0, (q0, qa)
-    lines += [".Lfa4w16_loop%=:"]
-    lines += full
-    lines += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 .Lfa4w16_loop%="]
-    n4, q1 = block16("nodma4", q0)
-    n0, q2 = block16("nodma0", q1)
-    lb, q3 = block16("last", q2)
-    assert q3 == []
-    lines += n4 + n0 + lb
-    return lines, full
-
-
-def c_literal(ln):
-    """One instruction as a C string literal; the operand-type mnemonics come from common.h (MG_MFMA32_ASM, MG_CVT_PK_ASM: bf16 in the
-    product build, fp16 in the fp16 build) as adjacent literals."""
-    for mnem, macro in (("v_mfma_f32_32x32x16_bf16", "MG_MFMA32_ASM"), ("v_mfma_f32_16x16x32_bf16", "MG_MFMA16_ASM"),
-                        ("v_cvt_pk_bf16_f32", "MG_CVT_PK_ASM")):
-        if ln.startswith(mnem + " "):
-            return macro + ' "' + ln[len(mnem):]
-    return '"' + ln
+    entry_reads(st, F, 0)
+    entry_reads(st, F, 1)
+    lds, vm = st.ldsq, st.vmq
+    full = block(F, "full", lds, vm)
+    assert full.ldsq == lds and renamed(full.vmq, NEXT) == vm, (lds, full.ldsq, vm, full.vmq)      # the loop is closed
+    n1 = block(F, "nodma", lds, vm)
+    n2 = block(F, "nodma", n1.ldsq, renamed(n1.vmq, NEXT))
+    lb = block(F, "last", n2.ldsq, renamed(n2.vmq, NEXT))
+    assert lb.ldsq == [] and lb.vmq == [], (lb.ldsq, lb.vmq)
+    loop = [F.label + ":"] + full.lines + ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 " + F.label]
+    return st.lines + loop + n1.lines + n2.lines + lb.lines, full.lines
 
 
 def main():
-    lines = ["s_waitcnt lgkmcnt(0)"]
-    lines += vgroup(X[0], "%[l00]", "%[l01]")
-    st = Stream([])
-    st.op("s_waitcnt vmcnt(8)")
-    st.op("s_barrier")
-    entry_reads(st)
-    entry_reads2(st)
-    lines += st.out
-    q0 = st.queue
-    full, qa = block("full", q0)
-    assert qa == q0, (q0, qa)
-    lines += [".Lfa4w_loop%=:"]
-    lines += full
-    lines += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 .Lfa4w_loop%="]
-    n4, q1 = block("nodma4", q0)
-    n0, q2 = block("nodma0", q1)
-    lb, q3 = block("last", q2)
-    assert q3 == []
-    lines += n4 + n0 + lb
-    n_mfma = sum(1 for x in full if x.startswith(MFMA))
-    n_valu = sum(1 for x in full if x.startswith("v_") and not x.startswith(MFMA))
-    n_lds = sum(1 for x in full if x.startswith("ds_"))
     with open(sys.argv[1] if len(sys.argv) > 1 else "flash4w.inc", "w") as f:
-        f.write("// Generated by gen_fa4w.py - do not edit.  One FULL iteration: %d MFMA, %d VALU, %d ds_read_b128, %d lines.\n"
-                % (n_mfma, n_valu, n_lds, len(full)))
-        f.write("#define FA4W_ASM \\\n")
-        for x in lines:
-            f.write('  %s\\n\\t" \\\n' % c_literal(x))
-        f.write('  ""\n')
-        lines16, full16 = stream16()
-        f.write("// The 16x16x32 form.  One FULL iteration: %d MFMA, %d VALU, %d ds_read_b128, %d lines.\n"
-                % (sum(1 for x in full16 if x.startswith(MFMA16)), sum(1 for x in full16 if x.startswith("v_") and not x.startswith(MFMA16)),
-                   sum(1 for x in full16 if x.startswith("ds_")), len(full16)))
-        f.write("#define FA4W16_ASM \\\n")
-        for x in lines16:
-            f.write('  %s\\n\\t" \\\n' % c_literal(x))
-        f.write('  ""\n')
+        for F, title in ((FA32, "Generated by gen_fa4w.py - do not edit."), (FA16, "The 16x16x32 form.")):
+            lines, full = stream(F)
+            n_mfma = sum(1 for x in full if x.startswith(F.mfma))
+            n_valu = sum(1 for x in full if x.startswith("v_")) - n_mfma
+            n_lds = sum(1 for x in full if x.startswith("ds_"))
+            f.write("// %s  One FULL iteration: %d MFMA, %d VALU, %d ds_read_b128, %d lines.\n" % (title, n_mfma, n_valu, n_lds, len(full)))
+            f.write(define(F.macro, lines, eol="\\n\\t") + "\n")
 
 
 if __name__ == "__main__":

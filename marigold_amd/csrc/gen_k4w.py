@@ -15,7 +15,8 @@ The stream, per K tile t (LDS buffer b = t & 1; fragment set F[ks] = 4 pixel-sid
 
 so a piece has 66-96 MFMA gaps (2.1-3.1 k cycles) to land, the fragments of a k-step are in registers 16+ gaps before their
 first MFMA, and a gap carries at most two non-MFMA issues (MI355X_MICROARCH.md: <= 5 hide behind a 32 x 32 x 16 MFMA).
-Waits are counted (vmcnt retires in order; the LDS-DMA is only ordered against ds_read by vmcnt + barrier).
+Waits are counted by the queue model of asmstream.py from the declared entry state (vmcnt retires in order; the LDS-DMA is only
+ordered against ds_read by vmcnt + barrier).
 
 Operand names (bound in igemm2_body.h): c<ni><mi> accumulators, a<ks><mi> / b<ks><ni> fragments (pixel / weight side),
 la<ks> / lb<ks> LDS byte addresses of the fragment reads, xa<ks> / xb<ks> their buffer toggles (XOR), va<i> / vb<i> per-lane byte
@@ -24,116 +25,124 @@ buffers being filled.
 """
 import sys
 
-# Geometry (set by main): MI x NI 32 x 32 fragments per wave (2 x 2 waves): 4 x 4 = the 256 x 256 tile (prefix K4W), 3 x 5 = the
-# 192 x 320 tile (prefix K4WB: full-width tiles for the N = 320 k layers).  LDS: pixel-row buffers, then weight-row buffers;
-# a read address toggles between an operand's two buffers by XOR with a per-register constant (xa<ks> / xb<ks>), the DMA bases
-# (ma / mb) are toggled by the caller.
-MI, NI = 4, 4
+from asmstream import ALL, MFMA_RESULT_TAIL, Slots, Stream, define, renamed
 
 
-def GS():
-    return MI * NI
+class Geo:
+    """MI x NI 32 x 32 fragments per wave (2 x 2 waves): 4 x 4 = the 256 x 256 tile (prefix K4W), 3 x 5 = the 192 x 320 tile
+    (prefix K4WB: full-width tiles for the N = 320 k layers).  LDS: pixel-row buffers, then weight-row buffers; a read address
+    toggles between an operand's two buffers by XOR with a per-register constant (xa<ks> / xb<ks>), the DMA bases (ma / mb) are
+    toggled by the caller."""
+
+    def __init__(self, prefix, mi, ni):
+        self.prefix, self.MI, self.NI = prefix, mi, ni
+        self.GS = mi * ni            # MFMAs per k-step
+        self.NM = 4 * self.GS        # MFMAs per K tile
+        self.NF = mi + ni            # reads per fragment set
+        self.ND = 2 * (mi + ni)      # LDS-DMA pieces per tile and wave
+
+    def mfma(self, g):
+        ks, ni, mi = g // self.GS, (g % self.GS) // self.MI, g % self.MI
+        return f"v_mfma_f32_32x32x16_bf16 %[c{ni}{mi}], %[b{ks}{ni}], %[a{ks}{mi}], %[c{ni}{mi}]"
+
+    def reads(self, ks):
+        """the fragment reads of k-step ks, pixel side first"""
+        return ([f"ds_read_b128 %[a{ks}{i}], %[la{ks}] offset:{i * 4096}" for i in range(self.MI)] +
+                [f"ds_read_b128 %[b{ks}{i}], %[lb{ks}] offset:{i * 4096}" for i in range(self.NI)])
+
+    def toggles(self, ks):
+        return [f"v_xor_b32 %[la{ks}], %[xa{ks}], %[la{ks}]", f"v_xor_b32 %[lb{ks}], %[xb{ks}], %[lb{ks}]"]
+
+    def dma(self, i):
+        """piece i of the next-but-one tile: (M0 write, in front of an MFMA; LDS-DMA, behind it)"""
+        if i < 2 * self.MI:
+            return (f"s_add_u32 m0, %[ma], {i * 4096}", f"buffer_load_dwordx4 %[va{i}], %[sa], 0 offen lds")
+        j = i - 2 * self.MI
+        return (f"s_add_u32 m0, %[mb], {j * 4096}", f"buffer_load_dwordx4 %[vb{j}], %[sb], 0 offen lds")
+
+    def entry_lds(self):
+        return ["F0"] * self.NF + ["F1"] * self.NF
+
+    def entry_vm(self, mode):
+        return [] if mode == "last" else ["T1"] * self.ND
 
 
-def mfma(g):
-    ks, ni, mi = g // GS(), (g % GS()) // MI, g % MI
-    return f"v_mfma_f32_32x32x16_bf16 %[c{ni}{mi}], %[b{ks}{ni}], %[a{ks}{mi}], %[c{ni}{mi}]"
+# Queue tags.  LDS: F<ks> = fragment set ks of this tile, F<ks>n = of the next tile.  VMEM: T1 / T2 = the pieces of tile t + 1 /
+# t + 2.  A tile is entered with F[0] then F[1] of this tile in the LDS queue and the pieces of tile t + 1 in the VMEM queue
+# (none in front of the last tile).  In C that state is set up by igemm2_body.h: two stage_tile() calls, then
+# `wait_vmcnt<A_IT + B_IT>` (one tile's pieces stay in flight) and the barrier in front of K4W_ASM_PROLOGUE, which reads F[0]
+# and F[1] of tile 0.  What a tile issues for "the next tile" is the next stream's "this tile":
+NEXT = {"F0n": "F0", "F1n": "F1", "T2": "T1"}
 
 
-def reads(ks):
-    """the fragment reads of k-step ks, pixel side first"""
-    return ([f"ds_read_b128 %[a{ks}{i}], %[la{ks}] offset:{i * 4096}" for i in range(MI)] +
-            [f"ds_read_b128 %[b{ks}{i}], %[lb{ks}] offset:{i * 4096}" for i in range(NI)])
-
-
-def toggles(ks):
-    return [f"v_xor_b32 %[la{ks}], %[xa{ks}], %[la{ks}]", f"v_xor_b32 %[lb{ks}], %[xb{ks}], %[lb{ks}]"]
-
-
-def dma(i):
-    """piece i of the next-but-one tile: (instruction in front of the MFMA, instruction behind it) - an SALU write of M0 needs
-    one instruction before the LDS-DMA that reads it"""
-    if i < 2 * MI:
-        return (f"s_add_u32 m0, %[ma], {i * 4096}", f"buffer_load_dwordx4 %[va{i}], %[sa], 0 offen lds")
-    j = i - 2 * MI
-    return (f"s_add_u32 m0, %[mb], {j * 4096}", f"buffer_load_dwordx4 %[vb{j}], %[sb], 0 offen lds")
-
-
-def block(mode, p):
-    """mode: 'full' (tiles t+1 and t+2 exist), 'nodma' (t+1 exists), 'last'"""
-    NM, nF, ND = 4 * GS(), MI + NI, 2 * (MI + NI)
-    pre = {g: [] for g in range(NM + 1)}     # instructions in front of MFMA g (g = NM: behind the last)
-    post = {g: [] for g in range(NM)}        # instructions right behind MFMA g
-    pre[0].append(f"s_waitcnt lgkmcnt({nF})")
+def tile(G, mode, rd_per_gap, r1, r2, n0, dma=(), fill=None, drain_lds_at_r2=False):
+    """One K tile (also the skeleton of gen_cp4w.py).  mode: 'full' (tiles t + 1 and t + 2 exist), 'nodma' (t + 1 exists),
+    'last'.  dma: (gap, M0 write, LDS-DMA, tag) per piece; fill(slots, first gap behind the fragment reads) places what a
+    kernel adds between the two barriers.  -> the resolved stream; .late: tags of the F[2] / F[3] reads placed at or behind r1"""
+    sl = Slots(G.NM)
+    sl.pre(0, None, "wait_lds", "F0")
     # --- F[2], F[3] of this tile
-    cur = reads(2) + reads(3)
+    cur = [(t, "lds", f"F{ks}") for ks in (2, 3) for t in G.reads(ks)]
+    late = []
     g = 0
     while cur:
-        for _ in range(p["rd_per_gap"]):
-            if cur:
-                post[g].append(cur.pop(0))
+        for it in cur[:rd_per_gap]:
+            sl.post(g, *it)
+            if g >= r1:
+                late.append(it[2])
+        del cur[:rd_per_gap]
         g += 1
-    last_read_gap = g - 1
-    post[last_read_gap + 1] += toggles(2)
-    post[last_read_gap + 2] += toggles(3)
-    r2 = p["r2"] if NM == 64 else NM - 2 * nF - 2
-    n0 = p["n0"] if NM == 64 else NM - 2 * nF - 1
+    for ks in (2, 3):
+        for t in G.toggles(ks):
+            sl.post(g + ks - 2, t)
+    sl.pre(r1, None, "wait_lds", ALL)          # every wave has read all of this tile's buffer ...
+    if mode != "last":
+        sl.pre(r1, "s_barrier")                # ... it is free
+        for gg, m0_write, load, tag in dma:    # (an SALU write of M0 needs one instruction before the LDS-DMA that reads it)
+            sl.pre(gg, m0_write)
+            sl.post(gg, load, "vm", tag)
+        if fill:
+            fill(sl, g)
+        sl.pre(r2, None, "wait_vm", "T1")      # tile t + 1 has landed ...
+        if drain_lds_at_r2:
+            sl.pre(r2, None, "wait_lds", ALL)
+        sl.pre(r2, "s_barrier")                # ... for everyone: its first two fragment sets
+        nxt = [(t, "lds", f"F{ks}n") for ks in (0, 1) for t in G.reads(ks)]
+        assert n0 + len(nxt) <= G.NM, n0
+        for k, it in enumerate(nxt):
+            sl.post(n0 + k, *it)
+        for t in G.toggles(0) + G.toggles(1):
+            sl.tail(t)
+    st = sl.play(Stream(G.entry_lds(), G.entry_vm(mode)), G.mfma)
     if mode == "last":
-        pre[p["r1"]].append("s_waitcnt lgkmcnt(0)")
-    else:
-        pre[p["r1"]] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
-        issued = 0
-        if mode == "full":
-            for i in range(ND):
-                gg = p["d0"] + i * p["dstep"]
-                a, b = dma(i)
-                pre[gg].append(a)
-                post[gg].append(b)
-                if gg < r2:
-                    issued += 1
-        pre[r2] += [f"s_waitcnt vmcnt({issued})", "s_barrier"]
-        nxt = reads(0) + reads(1)
-        g = n0
-        while nxt:
-            post[g].append(nxt.pop(0))
-            g += 1
-        assert g <= NM, g
-        pre[NM] += toggles(0) + toggles(1)
-    lines = []
-    for g in range(NM):
-        lines += pre[g]
-        lines.append(mfma(g))
-        lines += post[g]
-    lines += pre[NM]
-    if mode == "last":
-        # the epilogue's v_accvgpr_read follow in compiler code, whose hazard recogniser does not see the MFMAs in here: an
-        # 8-pass MFMA's result may be read 11 wait states after its issue at the earliest (round 4, first run: the LAST
-        # accumulator of every wave held its value from before the final MFMA)
-        lines += ["s_nop 7", "s_nop 7", "s_nop 7"]
-    return lines
+        st.lines += MFMA_RESULT_TAIL
+    st.late = late
+    return st
 
 
-def prologue():
+def prologue(G):
     """fragment sets F[0], F[1] of tile 0 (buffer 0), then la0 / la1 -> buffer 1"""
-    return reads(0) + reads(1) + toggles(0) + toggles(1)
+    st = Stream()
+    for ks in (0, 1):
+        for t in G.reads(ks):
+            st.lds(t, f"F{ks}")
+    for t in G.toggles(0) + G.toggles(1):
+        st.op(t)
+    return st
 
 
-
-def c_literal(ln):
-    """One instruction as a C string literal; the operand-type mnemonics come from common.h (MG_MFMA32_ASM, MG_CVT_PK_ASM: bf16 in the
-    product build, fp16 in the fp16 build) as adjacent literals."""
-    for mnem, macro in (("v_mfma_f32_32x32x16_bf16", "MG_MFMA32_ASM"), ("v_cvt_pk_bf16_f32", "MG_CVT_PK_ASM")):
-        if ln.startswith(mnem + " "):
-            return macro + ' "' + ln[len(mnem):]
-    return '"' + ln
-
-
-def emit(name, lines):
-    out = [f"#define {name} \\"]
-    for ln in lines:
-        out.append(f'  {c_literal(ln)}\\n" \\')
-    out.append('  ""')
-    return "\n".join(out)
+def assert_closed(G, pro, fulls, nodma, last):
+    """The chain PROLOGUE, FULL x n, [NODMA], LAST is closed: every stream leaves in flight what the next one is entered with,
+    the last one nothing.  fulls: (stream, older LDS items, older VMEM items); `older`: what a stream issues in front of the
+    next tile's items and does not wait for (both counters retire in order: the next stream's first wait covers it).
+    st.late: reads of F[2] / F[3] that a schedule places behind r1 stay in flight to the end of their tile - rd_per_gap=1 does,
+    no wait covers them in front of their MFMAs; the default schedules have none - named so that everything else is compared
+    exactly."""
+    assert pro.ldsq == G.entry_lds(), pro.ldsq
+    for st, older_lds, older_vm in fulls + [(nodma, [], [])]:
+        assert renamed(st.ldsq, NEXT) == st.late + older_lds + G.entry_lds(), (st.ldsq, st.late)
+        assert renamed(st.vmq, NEXT) == older_vm + (G.entry_vm("full") if st is not nodma else []), st.vmq
+    assert last.ldsq == last.late and last.vmq == [], (last.ldsq, last.vmq)
 
 
 def main():
@@ -144,12 +153,16 @@ def main():
         k, v = a.split("=")
         p[k] = int(v)
     assert p["d0"] > p["r1"] and p["n0"] >= p["r2"] and p["n0"] + 16 <= 64 + 0
-    global MI, NI
     txt = ["// GENERATED by gen_k4w.py " + " ".join(f"{k}={v}" for k, v in p.items()) + " - do not edit; see the generator for the schedule."]
-    for prefix, mi, ni in (("K4W", 4, 4), ("K4WB", 3, 5)):
-        MI, NI = mi, ni
-        txt += [emit(f"{prefix}_ASM_FULL", block("full", p)), "", emit(f"{prefix}_ASM_NODMA", block("nodma", p)), "",
-                emit(f"{prefix}_ASM_LAST", block("last", p)), "", emit(f"{prefix}_ASM_PROLOGUE", prologue()), ""]
+    for G in (Geo("K4W", 4, 4), Geo("K4WB", 3, 5)):
+        r2, n0 = (p["r2"], p["n0"]) if G.NM == 64 else (G.NM - 2 * G.NF - 2, G.NM - 2 * G.NF - 1)
+        dma = [(p["d0"] + i * p["dstep"],) + G.dma(i) + ("T2",) for i in range(G.ND)]
+        full, nodma, last = (tile(G, mode, p["rd_per_gap"], p["r1"], r2, n0, dma if mode == "full" else ())
+                             for mode in ("full", "nodma", "last"))
+        pro = prologue(G)
+        assert_closed(G, pro, [(full, [], [])], nodma, last)
+        for name, st in (("FULL", full), ("NODMA", nodma), ("LAST", last), ("PROLOGUE", pro)):
+            txt += [define(f"{G.prefix}_ASM_{name}", st.lines), ""]
     print("\n".join(txt))
 
 
