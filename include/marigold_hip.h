@@ -867,7 +867,8 @@ void mg_program_destroy(mg_program* prog);
  * marigold_amd/image.py::export_model_image and run from any host language without Python.  They stand where single_infer's
  * calls stand (marigold/marigold_depth_pipeline.py:396-477): encode_rgb (:479-496), the T-step unet + scheduler.step loop
  * (:455-468), decode_depth / decode_normals (:498-516, :473-475).  All device pointers are the caller's (fp32, NCHW, contiguous);
- * the model owns its weights and workspace (one device allocation, mg_model_device_bytes).  One stream at a time per model.
+ * the model owns its weights and workspace (mg_model_device_bytes: the handle's private memory; weights that several handles
+ * share are counted by mg_model_shared_bytes, below).  One stream at a time per model.
  *  mg_model_load(path, device): device >= 0 binds the library to that GPU (mg_init) and uploads; device < 0 = host-only: the
  *  image is parsed and relocated against fake addresses so that mg_model_validate can check every op's contract without a GPU.
  *  mg_model_info: cfg16 = B, H, W, latent h, latent w, steps, prediction channels, MG_POST_*, step-noise tensors, sizeof(mg_op),
@@ -890,6 +891,38 @@ int mg_model_validate(mg_model* m);
 int mg_model_vae_encode(mg_model* m, const float* rgb, float* latent, void* stream);
 int mg_model_denoise(mg_model* m, const float* rgb_latent, float* x, const float* step_noise, void* stream);
 int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* stream);
+
+/* One image, several CONFIGURATIONS (export_model_image(configs=[...]), a version-2 file): a configuration is what a version-1
+ * image is - (members, height, width, steps, pictures per call) and its three programs.  The kernel-ready weights are stored and
+ * uploaded once, the SHARED allocation; a handle's private memory (mg_model_device_bytes) holds every configuration's constants and
+ * zeroed state and ONE scratch region sized to the largest configuration's scratch, which the configurations overlay: they never
+ * run at the same time on one handle and no program reads scratch it has not written.  A version-1 image loads as one
+ * configuration with nothing shared.
+ *  mg_model_num_configs / mg_model_config_info: the count; the 16 words of mg_model_info for configuration `index`.
+ *  mg_model_find_config: the first configuration of that processed size H x W, E members, steps and K pictures per call (K = 1: a
+ *  one-picture configuration); -1 in a field = any value.  No match: -1, and mg_last_error lists the sizes the image holds.
+ *  mg_model_select: the SELECTED configuration is what mg_model_info, mg_model_validate, mg_model_vae_encode / _denoise /
+ *  _vae_decode and every mg_model_predict* act on - with their refusals, in their words (a K > 1 configuration refuses the
+ *  one-picture calls).  Configuration 0 is selected after the load; selecting launches nothing and costs nothing.  Not while a call
+ *  on this handle is being issued from another thread.
+ *  mg_processed_size: the size the pipelines feed the VAE for a picture of Hin x Win at processing_res (util/image_util.py::
+ *  resize_max_res: the longer edge becomes processing_res, the other is truncated; the arithmetic is the reference's, in doubles);
+ *  processing_res = 0 leaves the size as it is.  With it a host picks the configuration for a picture itself:
+ *  mg_processed_size -> mg_model_find_config -> mg_model_select -> mg_model_predict_out.
+ *  mg_model_shared_bytes: the bytes of the shared weights (0 for a version-1 image), counted once however many handles read them;
+ *  mg_model_device_bytes counts the handle's PRIVATE memory only: its arena and its temporaries.
+ *  mg_model_replica: a second handle over the SAME shared weights with a private arena of its own (constants copied device to
+ *  device from `m`, zeroed state zeroed, scratch as allocated), its own programs and temporaries: what a host needs to keep a second
+ *  picture in flight.  Each handle may be driven from its own host thread on its own stream.  The replica starts on the
+ *  configuration `m` has selected.  Call it while `m` is idle.  Parent and replica are destroyed in either order (mg_model_destroy);
+ *  the shared weights are freed with the last handle.  A host-only model replicates too.  NULL on failure (mg_last_error). */
+int mg_model_num_configs(const mg_model* m);
+int mg_model_config_info(const mg_model* m, int index, int* cfg16);
+int mg_model_find_config(const mg_model* m, int H, int W, int E, int steps, int K);
+int mg_model_select(mg_model* m, int index);
+int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W);
+long long mg_model_shared_bytes(const mg_model* m);
+mg_model* mg_model_replica(const mg_model* m);
 
 /* The whole prediction of one picture as ONE call, from the uint8 bytes and a seed to the ensembled map - __call__ of the reference's
  * pipelines (marigold/marigold_depth_pipeline.py:154-338, marigold_normals_pipeline.py:139-308) up to match_input_res, for a host

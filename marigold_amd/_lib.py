@@ -212,6 +212,8 @@ EXPORTS = [
     "mg_ensemble_iid", "mg_model_predict_iid",
     "mg_depth_visualize", "mg_normals_finish", "mg_model_predict_out", "mg_model_predict_many",
     "mg_lpips_workspace_bytes", "mg_eval_iid_lpips",
+    "mg_model_num_configs", "mg_model_config_info", "mg_model_find_config", "mg_model_select", "mg_processed_size",
+    "mg_model_shared_bytes", "mg_model_replica",
 ]
 
 
@@ -337,6 +339,15 @@ def load(f16=False):
                                                                                        ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_model_predict_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 5 + \
         [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgPredictOpts), ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
+    lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]
+    lib.mg_model_config_info.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.mg_model_find_config.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5
+    lib.mg_model_select.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.mg_processed_size.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
+    lib.mg_model_shared_bytes.argtypes = [ctypes.c_void_p]
+    lib.mg_model_shared_bytes.restype = ctypes.c_longlong
+    lib.mg_model_replica.argtypes = [ctypes.c_void_p]
+    lib.mg_model_replica.restype = ctypes.c_void_p
     lib.mg_event_create.restype = ctypes.c_void_p
     lib.mg_event_record.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_event_elapsed_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]

@@ -6,10 +6,16 @@
 //   mg_model_vae_decode  = decode_depth / _normals (:498-516 + :473-475: post_quant_conv -> decoder -> channel mean / clip / shift)
 // File layout (little endian; written by image.py with struct.pack - the two sides are kept in step by tests/test_host.py):
 //   header "MGIMG1", version, ABI, counts, cfg[16] | buffer table | program table (+ named slots) | blobs (64-byte aligned)
+// Version 2 holds several CONFIGURATIONS (problem shapes) of one model: header | configurations, scratch region | configuration
+// table (cfg[16] + three programs each) | buffer table | blobs.  The packed weights are stored once (kind 3, shared); every other
+// buffer names its configuration.  A handle = the shared weights (reference-counted: mg_model_replica makes another handle over
+// them) + a private arena; mg_model_select picks the configuration the entry points act on.  A version-1 file is one configuration.
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <exception>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -27,10 +33,12 @@ struct ImgHeader {
   uint32_t version, abi, n_buffers, n_programs;
   uint32_t cfg[16];   // B, H, W, h, w, steps, prediction channels, post, step noises, sizeof(mg_op), modalities, Hout, Wout,
                       // pictures per call (0 = 1: images written before the field; B is then the members of EACH picture)
+                      // (version 2: the words of configuration 0)
 };
 struct ImgBuffer {
-  uint64_t nbytes, file_off;
-  uint32_t kind, pad;   // 0 scratch, 1 zeroed state, 2 data (weights / constants)
+  uint64_t nbytes, file_off;   // file_off of a version-2 scratch buffer: its place in the scratch region
+  uint32_t kind, cfg;          // 0 scratch, 1 zeroed state, 2 data (constants; version 1: weights too), 3 shared (the weights of a
+                               // version-2 image, stored once); cfg: the configuration a version-2 buffer of kind 0..2 belongs to
 };
 struct ImgSlot {
   char name[24];
@@ -48,7 +56,55 @@ struct ImgReloc {
   uint32_t op, slot, buf, pad;
   uint64_t off;
 };
+struct ImgV2 {   // version 2, after the header; then the configuration table, then the buffer table
+  uint32_t n_configs, pad;
+  uint64_t scratch_bytes;   // the scratch region: the largest configuration's scratch
+};
+struct ImgConfig {
+  uint32_t cfg[16];
+  ImgProgram prog[3];
+};
 #pragma pack(pop)
+
+enum { KIND_SCRATCH = 0, KIND_ZERO = 1, KIND_DATA = 2, KIND_SHARED = 3 };
+
+// What the file says, parsed and checked once on the host; a handle and its replicas read it, nobody writes it after the load.
+struct PlanBuf {
+  uint64_t nbytes, file_off;
+  uint32_t kind, cfg;
+  bool shared;    // lies in the shared weights (else in the handle's private arena)
+  uint64_t off;   // its place there
+};
+struct PlanProg {
+  std::string name;
+  std::vector<mg_op> ops;   // device pointers still null
+  std::vector<ImgReloc> rel;
+  std::vector<ImgSlot> slots;
+  const ImgSlot* slot(const char* n) const {
+    for (const ImgSlot& s : slots)
+      if (strnlen(s.name, sizeof(s.name)) == strlen(n) && memcmp(s.name, n, strlen(n)) == 0) return &s;
+    return nullptr;
+  }
+};
+struct PlanConfig {
+  uint32_t cfg[16];
+  PlanProg prog[3];
+};
+struct Plan {
+  uint32_t version = 1;
+  std::vector<PlanBuf> bufs;
+  std::vector<PlanConfig> cfgs;
+  uint64_t shared_bytes = 0, private_bytes = 0;
+};
+
+// The weights every handle over one image reads: freed with the last handle (std::shared_ptr counts, thread-safe)
+struct SharedMem {
+  char* base = nullptr;
+  bool host_only = false;
+  ~SharedMem() {
+    if (base && !host_only) (void)hipFree(base);
+  }
+};
 
 struct Slot {
   std::string name;
@@ -65,18 +121,26 @@ struct Prog {
     return nullptr;
   }
 };
+struct Config {
+  const uint32_t* cfg = nullptr;   // the plan's 16 words
+  Prog enc, den, dec;
+  int K = 1;                       // pictures per call (cfg[13], 0 = 1)
+};
 
 }  // namespace
 
 struct mg_model {
-  ImgHeader hdr;
+  std::shared_ptr<const Plan> plan;
+  std::shared_ptr<SharedMem> shared;   // the shared weights (a version-1 image: none)
   bool host_only = false;
-  char* arena = nullptr;       // one device allocation holding every buffer (host-only: a fake base address, never touched)
+  int device = -1;
+  char* arena = nullptr;       // the handle's private allocation: every configuration's constants and zeroed state, then ONE scratch
+                               // region every configuration's scratch is laid over (host-only: a fake base address, never touched)
   uint64_t arena_bytes = 0;
   std::vector<char*> bufs;
-  std::vector<uint64_t> buf_bytes;   // the buffer table's sizes: every relocation / slot is checked against them
-  Prog enc, den, dec;
-  int K = 1;                         // pictures per call (cfg[13], 0 = 1)
+  std::vector<Config> configs;
+  int sel = 0;                 // the selected configuration: what every entry point below acts on
+  const Config& cur() const { return configs[sel]; }
   void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W], one picture's: the
                                      // pictures of a call pass through it one after the other), grown on demand
   uint64_t predict_tmp_bytes = 0;
@@ -90,109 +154,254 @@ bool read_at(FILE* f, uint64_t off, void* dst, size_t n) {
   return fseek(f, (long)off, SEEK_SET) == 0 && fread(dst, 1, n, f) == n;
 }
 
-int load_program(FILE* f, const ImgProgram& ip, mg_model* m, Prog* out) {
+uint64_t r256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+// May configuration `c` point into buffer `b`?  Its own buffers and the shared weights only.
+bool owns(const Plan& p, uint32_t c, uint32_t b) { return p.version == 1 || p.bufs[b].kind == KIND_SHARED || p.bufs[b].cfg == c; }
+
+int parse_program(FILE* f, uint64_t file_bytes, const ImgProgram& ip, const Plan& p, uint32_t c, PlanProg* out) {
   out->name = std::string(ip.name, strnlen(ip.name, sizeof(ip.name)));
-  MG_REQUIRE(ip.n_ops > 0 && ip.n_slots <= 16, "mg_model_load: corrupt program table (%s)", out->name.c_str());
-  std::vector<mg_op> ops(ip.n_ops);
-  MG_REQUIRE(read_at(f, ip.ops_off, ops.data(), sizeof(mg_op) * ip.n_ops), "mg_model_load: short read (ops of %s)", out->name.c_str());
-  std::vector<ImgReloc> rel(ip.n_relocs);
-  MG_REQUIRE(ip.n_relocs == 0 || read_at(f, ip.relocs_off, rel.data(), sizeof(ImgReloc) * ip.n_relocs),
-             "mg_model_load: short read (relocations of %s)", out->name.c_str());
-  for (const ImgReloc& r : rel) {
-    MG_REQUIRE(r.op < ip.n_ops && r.buf < m->bufs.size(), "mg_model_load: relocation out of range (%s)", out->name.c_str());
-    MG_REQUIRE(r.off < m->buf_bytes[r.buf], "mg_model_load: corrupt image - a relocation of %s points %llu bytes into buffer %u of %llu bytes",
-               out->name.c_str(), (unsigned long long)r.off, r.buf, (unsigned long long)m->buf_bytes[r.buf]);
-    char* p = m->bufs[r.buf] + r.off;
-    if (r.slot < 16) {
-      ops[r.op].p[r.slot] = p;
-    } else {   // the address pair of MG_OP_IGEMM's row-statistics tickets
-      MG_REQUIRE(r.slot == 100 && ops[r.op].kind == MG_OP_IGEMM, "mg_model_load: unknown relocation slot %u", r.slot);
-      const uint64_t a = (uint64_t)(uintptr_t)p;
-      ops[r.op].i[MG_IGEMM_I_TICKETS_LO] = (int32_t)(uint32_t)(a & 0xffffffffu);
-      ops[r.op].i[MG_IGEMM_I_TICKETS_HI] = (int32_t)(uint32_t)(a >> 32);
-    }
+  const char* nm = out->name.c_str();
+  MG_REQUIRE(ip.n_ops > 0 && ip.n_slots <= 16, "mg_model_load: corrupt program table (%s)", nm);
+  MG_REQUIRE(ip.ops_off <= file_bytes && (uint64_t)ip.n_ops * sizeof(mg_op) <= file_bytes - ip.ops_off &&
+                 ip.relocs_off <= file_bytes && (uint64_t)ip.n_relocs * sizeof(ImgReloc) <= file_bytes - ip.relocs_off,
+             "mg_model_load: corrupt image - the ops or relocations of %s lie outside the %llu-byte file", nm, (unsigned long long)file_bytes);
+  out->ops.resize(ip.n_ops);
+  MG_REQUIRE(read_at(f, ip.ops_off, out->ops.data(), sizeof(mg_op) * ip.n_ops), "mg_model_load: short read (ops of %s)", nm);
+  out->rel.resize(ip.n_relocs);
+  MG_REQUIRE(ip.n_relocs == 0 || read_at(f, ip.relocs_off, out->rel.data(), sizeof(ImgReloc) * ip.n_relocs),
+             "mg_model_load: short read (relocations of %s)", nm);
+  for (const ImgReloc& r : out->rel) {
+    MG_REQUIRE(r.op < ip.n_ops && r.buf < p.bufs.size(), "mg_model_load: relocation out of range (%s)", nm);
+    MG_REQUIRE(owns(p, c, r.buf), "mg_model_load: corrupt image - a relocation of %s (configuration %u) points into buffer %u of configuration %u",
+               nm, c, r.buf, p.bufs[r.buf].cfg);
+    MG_REQUIRE(r.off < p.bufs[r.buf].nbytes, "mg_model_load: corrupt image - a relocation of %s points %llu bytes into buffer %u of %llu bytes",
+               nm, (unsigned long long)r.off, r.buf, (unsigned long long)p.bufs[r.buf].nbytes);
+    // (slot 100: the address pair of MG_OP_IGEMM's row-statistics tickets)
+    MG_REQUIRE(r.slot < 16 || (r.slot == 100 && out->ops[r.op].kind == MG_OP_IGEMM), "mg_model_load: unknown relocation slot %u", r.slot);
   }
-  out->prog = mg_program_create(ops.data(), (int)ops.size());
-  MG_REQUIRE(out->prog, "mg_model_load: mg_program_create failed (%s)", out->name.c_str());
   for (uint32_t k = 0; k < ip.n_slots; ++k) {
     const ImgSlot& s = ip.slots[k];
-    MG_REQUIRE(s.buf < m->bufs.size(), "mg_model_load: slot out of range (%s)", out->name.c_str());
-    MG_REQUIRE(s.off <= m->buf_bytes[s.buf] && s.nbytes <= m->buf_bytes[s.buf] - s.off,
-               "mg_model_load: corrupt image - slot %u of %s spans [%llu, +%llu) of a %llu-byte buffer", k, out->name.c_str(),
-               (unsigned long long)s.off, (unsigned long long)s.nbytes, (unsigned long long)m->buf_bytes[s.buf]);
-    out->slots.push_back(Slot{std::string(s.name, strnlen(s.name, sizeof(s.name))), m->bufs[s.buf] + s.off, s.nbytes});
+    MG_REQUIRE(s.buf < p.bufs.size(), "mg_model_load: slot out of range (%s)", nm);
+    MG_REQUIRE(owns(p, c, s.buf), "mg_model_load: corrupt image - slot %u of %s (configuration %u) lies in buffer %u of configuration %u", k, nm, c,
+               s.buf, p.bufs[s.buf].cfg);
+    MG_REQUIRE(s.off <= p.bufs[s.buf].nbytes && s.nbytes <= p.bufs[s.buf].nbytes - s.off,
+               "mg_model_load: corrupt image - slot %u of %s spans [%llu, +%llu) of a %llu-byte buffer", k, nm, (unsigned long long)s.off,
+               (unsigned long long)s.nbytes, (unsigned long long)p.bufs[s.buf].nbytes);
+    out->slots.push_back(s);
   }
   return 0;
 }
 
-int load_into(mg_model* m, FILE* f, int device) {
-  MG_REQUIRE(read_at(f, 0, &m->hdr, sizeof(ImgHeader)), "mg_model_load: short read (header)");
-  const ImgHeader& h = m->hdr;
-  MG_REQUIRE(memcmp(h.magic, "MGIMG1\0\0", 8) == 0 && h.version == 1, "mg_model_load: not a model image (or an unknown version)");
+// The whole file but the stored bytes of the buffers, checked: nothing below touches a device.
+int parse_image(FILE* f, Plan* p) {
+  ImgHeader h;
+  MG_REQUIRE(read_at(f, 0, &h, sizeof(ImgHeader)), "mg_model_load: short read (header)");
+  MG_REQUIRE(memcmp(h.magic, "MGIMG1\0\0", 8) == 0 && (h.version == 1 || h.version == 2), "mg_model_load: not a model image (or an unknown version)");
   MG_REQUIRE(h.abi == MG_ABI_VERSION && h.cfg[9] == sizeof(mg_op),
              "mg_model_load: the image was written for ABI %u / %u-byte ops, this library is ABI %d / %zu", h.abi, h.cfg[9], MG_ABI_VERSION, sizeof(mg_op));
-  MG_REQUIRE(h.n_programs == 3 && h.n_buffers > 0 && h.n_buffers < (1u << 24), "mg_model_load: corrupt header");
-  std::vector<ImgBuffer> bt(h.n_buffers);
-  MG_REQUIRE(read_at(f, sizeof(ImgHeader), bt.data(), sizeof(ImgBuffer) * h.n_buffers), "mg_model_load: short read (buffer table)");
+  p->version = h.version;
+  ImgV2 v2 = {1, 0, 0};
+  if (h.version == 2) {
+    MG_REQUIRE(read_at(f, sizeof(ImgHeader), &v2, sizeof(ImgV2)), "mg_model_load: short read (header)");
+    MG_REQUIRE(v2.n_configs >= 1 && v2.n_configs <= 4096 && v2.scratch_bytes < (1ull << 40), "mg_model_load: corrupt header");
+  }
+  MG_REQUIRE(h.n_programs == 3 * v2.n_configs && h.n_buffers > 0 && h.n_buffers < (1u << 24), "mg_model_load: corrupt header");
   // the file's own size bounds every stored buffer (a truncated / corrupt table must not size a staging buffer or a copy)
   MG_REQUIRE(fseek(f, 0, SEEK_END) == 0, "mg_model_load: cannot seek");
   const long fsz = ftell(f);
   MG_REQUIRE(fsz > 0, "mg_model_load: cannot size the image");
   const uint64_t file_bytes = (uint64_t)fsz;
-  std::vector<uint64_t> off(h.n_buffers);
-  uint64_t total = 0;
-  m->buf_bytes.resize(h.n_buffers);
-  for (uint32_t i = 0; i < h.n_buffers; ++i) {
-    MG_REQUIRE(bt[i].nbytes > 0 && bt[i].nbytes < (1ull << 40), "mg_model_load: corrupt image - buffer %u has %llu bytes", i, (unsigned long long)bt[i].nbytes);
-    if (bt[i].kind == 2)
-      MG_REQUIRE(bt[i].file_off <= file_bytes && bt[i].nbytes <= file_bytes - bt[i].file_off,
-                 "mg_model_load: corrupt image - buffer %u lies at [%llu, +%llu) of a %llu-byte file", i, (unsigned long long)bt[i].file_off,
-                 (unsigned long long)bt[i].nbytes, (unsigned long long)file_bytes);
-    m->buf_bytes[i] = bt[i].nbytes;
-    off[i] = total;
-    total += (bt[i].nbytes + 255) / 256 * 256;
+  // version 1: header | buffer table | three programs; version 2: header | ImgV2 | configuration table | buffer table
+  std::vector<ImgConfig> ct(v2.n_configs);
+  uint64_t buf_at = sizeof(ImgHeader);
+  if (h.version == 2) {
+    MG_REQUIRE(read_at(f, sizeof(ImgHeader) + sizeof(ImgV2), ct.data(), sizeof(ImgConfig) * v2.n_configs),
+               "mg_model_load: short read (configuration table)");
+    buf_at += sizeof(ImgV2) + sizeof(ImgConfig) * v2.n_configs;
   }
-  m->arena_bytes = total;
-  m->host_only = device < 0;
-  if (m->host_only) {
-    m->arena = (char*)(uintptr_t)0x100000000ull;   // addresses for the contract checks only: nothing is dereferenced
-  } else {
-    MG_REQUIRE(mg_init(device) == 0, "mg_model_load: %s", mg_last_error());
-    MG_CHECK_HIP(hipMalloc((void**)&m->arena, total));
+  std::vector<ImgBuffer> bt(h.n_buffers);
+  MG_REQUIRE(read_at(f, buf_at, bt.data(), sizeof(ImgBuffer) * h.n_buffers), "mg_model_load: short read (buffer table)");
+  if (h.version == 1) {
+    memcpy(ct[0].cfg, h.cfg, sizeof(h.cfg));
+    MG_REQUIRE(read_at(f, buf_at + sizeof(ImgBuffer) * h.n_buffers, ct[0].prog, sizeof(ImgProgram) * 3), "mg_model_load: short read (program table)");
   }
-  m->bufs.resize(h.n_buffers);
-  std::vector<char> stage;
+  // ---- the buffers and where a handle places them.  Version 1: everything in the private arena, in the table's order.  Version 2:
+  // the shared weights in an allocation of their own; in the arena every configuration's constants and zeroed state, then the scratch
+  // region, where a configuration's scratch buffers lie at the offsets the file gives them (configurations never run at the same time
+  // on one handle, and no program reads scratch it has not written: tests/test_gpu_scratch_independence.py)
+  p->bufs.resize(h.n_buffers);
+  std::vector<uint64_t> scratch_end(v2.n_configs, 0);
+  uint64_t shared = 0, priv = 0;
   for (uint32_t i = 0; i < h.n_buffers; ++i) {
-    m->bufs[i] = m->arena + off[i];
-    if (m->host_only) continue;
-    if (bt[i].kind == 2) {
-      stage.resize(bt[i].nbytes);
-      MG_REQUIRE(read_at(f, bt[i].file_off, stage.data(), bt[i].nbytes), "mg_model_load: short read (buffer %u)", i);
-      MG_CHECK_HIP(hipMemcpy(m->bufs[i], stage.data(), bt[i].nbytes, hipMemcpyHostToDevice));
-    } else if (bt[i].kind == 1) {
-      MG_CHECK_HIP(hipMemset(m->bufs[i], 0, bt[i].nbytes));
+    const ImgBuffer& b = bt[i];
+    MG_REQUIRE(b.nbytes > 0 && b.nbytes < (1ull << 40), "mg_model_load: corrupt image - buffer %u has %llu bytes", i, (unsigned long long)b.nbytes);
+    MG_REQUIRE(b.kind <= (h.version == 2 ? KIND_SHARED : KIND_DATA), "mg_model_load: corrupt image - buffer %u is of unknown kind %u", i, b.kind);
+    if (b.kind == KIND_DATA || b.kind == KIND_SHARED)
+      MG_REQUIRE(b.file_off <= file_bytes && b.nbytes <= file_bytes - b.file_off,
+                 "mg_model_load: corrupt image - buffer %u lies at [%llu, +%llu) of a %llu-byte file", i, (unsigned long long)b.file_off,
+                 (unsigned long long)b.nbytes, (unsigned long long)file_bytes);
+    PlanBuf& pb = p->bufs[i];
+    pb.nbytes = b.nbytes;
+    pb.file_off = b.file_off;
+    pb.kind = b.kind;
+    pb.cfg = h.version == 2 && b.kind != KIND_SHARED ? b.cfg : 0;
+    pb.shared = b.kind == KIND_SHARED;
+    MG_REQUIRE(pb.cfg < v2.n_configs, "mg_model_load: corrupt image - buffer %u belongs to configuration %u of %u", i, pb.cfg, v2.n_configs);
+    if (pb.shared) {
+      pb.off = shared;
+      shared += r256(b.nbytes);
+    } else if (h.version == 1 || b.kind != KIND_SCRATCH) {
+      pb.off = priv;
+      priv += r256(b.nbytes);
     }
   }
-  std::vector<ImgProgram> pt(h.n_programs);
-  MG_REQUIRE(read_at(f, sizeof(ImgHeader) + sizeof(ImgBuffer) * h.n_buffers, pt.data(), sizeof(ImgProgram) * h.n_programs),
-             "mg_model_load: short read (program table)");
-  Prog* dst[3] = {&m->enc, &m->den, &m->dec};
-  const char* want[3] = {"vae.encode", "denoise", "vae.decode"};
-  for (int k = 0; k < 3; ++k) {
-    if (int rc = load_program(f, pt[k], m, dst[k])) return rc;
-    MG_REQUIRE(dst[k]->name == want[k], "mg_model_load: program %d is '%s', expected '%s'", k, dst[k]->name.c_str(), want[k]);
+  if (h.version == 2) {
+    for (uint32_t i = 0; i < h.n_buffers; ++i) {
+      PlanBuf& pb = p->bufs[i];
+      if (pb.kind != KIND_SCRATCH) continue;
+      // (in the table a configuration's scratch buffers come in the order of their places: they cannot overlap each other)
+      MG_REQUIRE(pb.file_off % 256 == 0 && pb.file_off >= scratch_end[pb.cfg] && pb.file_off <= v2.scratch_bytes &&
+                     pb.nbytes <= v2.scratch_bytes - pb.file_off,
+                 "mg_model_load: corrupt image - scratch buffer %u of configuration %u lies at [%llu, +%llu) of a scratch region of %llu bytes", i,
+                 pb.cfg, (unsigned long long)pb.file_off, (unsigned long long)pb.nbytes, (unsigned long long)v2.scratch_bytes);
+      scratch_end[pb.cfg] = pb.file_off + pb.nbytes;
+      pb.off = priv + pb.file_off;
+    }
+    priv += r256(v2.scratch_bytes);
   }
-  MG_REQUIRE(m->enc.slot("rgb") && m->enc.slot("latent") && m->den.slot("rgb_latent") && m->den.slot("x") && m->dec.slot("latent") &&
-             m->dec.slot("pred"), "mg_model_load: a program lacks its input / output slots");
-  // the three programs hand K pictures of B members on to each other: [K,3,H,W] -> [K,4,h,w]; [K B,...] -> the decoder -> [K B,C,Ho,Wo]
-  m->K = h.cfg[13] ? (int)h.cfg[13] : 1;
-  const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
-  const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
-  const uint64_t K = (uint64_t)m->K;
-  MG_REQUIRE(m->K >= 1 && e_in->nbytes == K * 3 * h.cfg[1] * h.cfg[2] * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
-             xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * h.cfg[0] * h.cfg[6] * h.cfg[11] * h.cfg[12] * 4,
-             "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", m->K, h.cfg[0]);
+  p->shared_bytes = shared;
+  p->private_bytes = priv;
+  // ---- the configurations
+  p->cfgs.resize(v2.n_configs);
+  static const char* const want[3] = {"vae.encode", "denoise", "vae.decode"};
+  for (uint32_t c = 0; c < v2.n_configs; ++c) {
+    PlanConfig& pc = p->cfgs[c];
+    memcpy(pc.cfg, ct[c].cfg, sizeof(pc.cfg));
+    MG_REQUIRE(pc.cfg[9] == sizeof(mg_op), "mg_model_load: configuration %u was written for %u-byte ops, this library has %zu", c, pc.cfg[9], sizeof(mg_op));
+    for (int k = 0; k < 3; ++k) {
+      if (int rc = parse_program(f, file_bytes, ct[c].prog[k], *p, c, &pc.prog[k])) return rc;
+      MG_REQUIRE(pc.prog[k].name == want[k], "mg_model_load: program %d is '%s', expected '%s'", k, pc.prog[k].name.c_str(), want[k]);
+    }
+    const ImgSlot *e_in = pc.prog[0].slot("rgb"), *e_out = pc.prog[0].slot("latent"), *rl = pc.prog[1].slot("rgb_latent"), *xs = pc.prog[1].slot("x");
+    const ImgSlot *d_in = pc.prog[2].slot("latent"), *d_out = pc.prog[2].slot("pred");
+    MG_REQUIRE(e_in && e_out && rl && xs && d_in && d_out, "mg_model_load: a program lacks its input / output slots");
+    // the three programs hand K pictures of B members on to each other: [K,3,H,W] -> [K,4,h,w]; [K B,...] -> the decoder -> [K B,C,Ho,Wo]
+    const uint32_t* g = pc.cfg;
+    const uint64_t K = g[13] ? g[13] : 1;
+    MG_REQUIRE(K < (1u << 20) && e_in->nbytes == K * 3 * g[1] * g[2] * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
+                   xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * g[0] * g[6] * g[11] * g[12] * 4,
+               "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", (int)K, g[0]);
+  }
   return 0;
+}
+
+// The handle's buffers are placed (m->arena, m->shared): their addresses, then every configuration's programs patched to them
+int instantiate(mg_model* m) {
+  const Plan& p = *m->plan;
+  m->bufs.resize(p.bufs.size());
+  for (size_t i = 0; i < p.bufs.size(); ++i) m->bufs[i] = (p.bufs[i].shared ? m->shared->base : m->arena) + p.bufs[i].off;
+  m->configs.resize(p.cfgs.size());
+  for (size_t c = 0; c < p.cfgs.size(); ++c) {
+    Config& cf = m->configs[c];
+    cf.cfg = p.cfgs[c].cfg;
+    cf.K = cf.cfg[13] ? (int)cf.cfg[13] : 1;
+    Prog* dst[3] = {&cf.enc, &cf.den, &cf.dec};
+    for (int k = 0; k < 3; ++k) {
+      const PlanProg& pp = p.cfgs[c].prog[k];
+      std::vector<mg_op> ops = pp.ops;
+      for (const ImgReloc& r : pp.rel) {   // (checked by parse_program)
+        char* q = m->bufs[r.buf] + r.off;
+        if (r.slot < 16) {
+          ops[r.op].p[r.slot] = q;
+        } else {
+          const uint64_t a = (uint64_t)(uintptr_t)q;
+          ops[r.op].i[MG_IGEMM_I_TICKETS_LO] = (int32_t)(uint32_t)(a & 0xffffffffu);
+          ops[r.op].i[MG_IGEMM_I_TICKETS_HI] = (int32_t)(uint32_t)(a >> 32);
+        }
+      }
+      dst[k]->name = pp.name;
+      dst[k]->prog = mg_program_create(ops.data(), (int)ops.size());
+      MG_REQUIRE(dst[k]->prog, "mg_model_load: mg_program_create failed (%s)", pp.name.c_str());
+      for (const ImgSlot& s : pp.slots)
+        dst[k]->slots.push_back(Slot{std::string(s.name, strnlen(s.name, sizeof(s.name))), m->bufs[s.buf] + s.off, s.nbytes});
+    }
+  }
+  return 0;
+}
+
+// Fake addresses of a host-only handle, for the contract checks only (nothing is dereferenced): the shared weights at 4 GiB, every
+// handle's arena in a 1 TiB window of its own
+char* fake_arena() {
+  static std::atomic<uint64_t> n{0};
+  return (char*)(uintptr_t)((2 + n.fetch_add(1)) << 40);
+}
+
+// The private arena of a handle whose plan and shared weights are set: allocated, its zeroed state zeroed; its constants from the
+// file (f) or, a replica's, from `parent` device to device; scratch as allocated.
+int make_arena(mg_model* m, FILE* f, const mg_model* parent) {
+  const Plan& p = *m->plan;
+  m->arena_bytes = p.private_bytes;
+  if (m->host_only) {
+    m->arena = fake_arena();
+    return 0;
+  }
+  MG_CHECK_HIP(hipMalloc((void**)&m->arena, p.private_bytes ? p.private_bytes : 256));
+  std::vector<char> stage;
+  for (size_t i = 0; i < p.bufs.size(); ++i) {
+    const PlanBuf& b = p.bufs[i];
+    if (b.shared) continue;
+    char* dst = m->arena + b.off;
+    if (b.kind == KIND_DATA && parent) {
+      MG_CHECK_HIP(hipMemcpy(dst, parent->arena + b.off, b.nbytes, hipMemcpyDeviceToDevice));
+    } else if (b.kind == KIND_DATA) {
+      stage.resize(b.nbytes);
+      MG_REQUIRE(read_at(f, b.file_off, stage.data(), b.nbytes), "mg_model_load: short read (buffer %zu)", i);
+      MG_CHECK_HIP(hipMemcpy(dst, stage.data(), b.nbytes, hipMemcpyHostToDevice));
+    } else if (b.kind == KIND_ZERO) {
+      MG_CHECK_HIP(hipMemset(dst, 0, b.nbytes));
+    }
+  }
+  return 0;
+}
+
+int load_into(mg_model* m, FILE* f, int device) {
+  auto plan = std::make_shared<Plan>();
+  if (int rc = parse_image(f, plan.get())) return rc;
+  m->plan = plan;
+  m->host_only = device < 0;
+  m->device = device;
+  m->shared = std::make_shared<SharedMem>();
+  m->shared->host_only = m->host_only;
+  if (m->host_only) {
+    m->shared->base = (char*)(uintptr_t)0x100000000ull;
+  } else {
+    MG_REQUIRE(mg_init(device) == 0, "mg_model_load: %s", mg_last_error());
+    if (plan->shared_bytes) {
+      MG_CHECK_HIP(hipMalloc((void**)&m->shared->base, plan->shared_bytes));
+      std::vector<char> stage;
+      for (size_t i = 0; i < plan->bufs.size(); ++i) {
+        const PlanBuf& b = plan->bufs[i];
+        if (!b.shared) continue;
+        stage.resize(b.nbytes);
+        MG_REQUIRE(read_at(f, b.file_off, stage.data(), b.nbytes), "mg_model_load: short read (buffer %zu)", i);
+        MG_CHECK_HIP(hipMemcpy(m->shared->base + b.off, stage.data(), b.nbytes, hipMemcpyHostToDevice));
+      }
+    }
+  }
+  if (int rc = make_arena(m, f, nullptr)) return rc;
+  return instantiate(m);
+}
+
+int replicate_into(mg_model* r, const mg_model* m) {
+  r->plan = m->plan;
+  r->shared = m->shared;
+  r->host_only = m->host_only;
+  r->device = m->device;
+  r->sel = m->sel;
+  if (!r->host_only) MG_REQUIRE(mg_init(r->device) == 0, "mg_model_replica: %s", mg_last_error());   // (binds the calling thread to the device)
+  if (int rc = make_arena(r, nullptr, m)) return rc;
+  return instantiate(r);
 }
 
 int copy_dd(void* dst, const void* src, uint64_t n, hipStream_t s) {
@@ -230,27 +439,99 @@ mg_model* mg_model_load(const char* path, int device) {
   return m;
 }
 
+mg_model* mg_model_replica(const mg_model* m) {
+  if (!m) {
+    mg_set_error("mg_model_replica: null model");
+    return nullptr;
+  }
+  mg_model* r = new mg_model();
+  int rc;
+  try {
+    rc = replicate_into(r, m);
+  } catch (const std::exception& e) {
+    mg_set_error("mg_model_replica: %s", e.what());
+    rc = 2;
+  }
+  if (rc) {
+    mg_model_destroy(r);
+    return nullptr;
+  }
+  return r;
+}
+
 void mg_model_destroy(mg_model* m) {
   if (!m) return;
-  for (Prog* p : {&m->enc, &m->den, &m->dec})
-    if (p->prog) mg_program_destroy(p->prog);
+  for (Config& c : m->configs)
+    for (Prog* p : {&c.enc, &c.den, &c.dec})
+      if (p->prog) mg_program_destroy(p->prog);
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
   if (m->out_tmp) (void)hipFree(m->out_tmp);
-  delete m;
+  delete m;   // (the shared weights go with the last handle over them)
 }
 
 int mg_model_info(const mg_model* m, int* cfg16) {
   MG_REQUIRE(m && cfg16, "mg_model_info: null argument");
-  for (int i = 0; i < 16; ++i) cfg16[i] = (int)m->hdr.cfg[i];
+  for (int i = 0; i < 16; ++i) cfg16[i] = (int)m->cur().cfg[i];
+  return 0;
+}
+
+int mg_model_num_configs(const mg_model* m) { return m ? (int)m->configs.size() : 0; }
+
+int mg_model_config_info(const mg_model* m, int index, int* cfg16) {
+  MG_REQUIRE(m && cfg16, "mg_model_config_info: null argument");
+  MG_REQUIRE(index >= 0 && index < (int)m->configs.size(), "mg_model_config_info: configuration %d of %d", index, (int)m->configs.size());
+  for (int i = 0; i < 16; ++i) cfg16[i] = (int)m->configs[index].cfg[i];
+  return 0;
+}
+
+int mg_model_find_config(const mg_model* m, int H, int W, int E, int steps, int K) {
+  if (!m) {
+    mg_set_error("mg_model_find_config: null model");
+    return -1;
+  }
+  std::string have;
+  for (size_t c = 0; c < m->configs.size(); ++c) {
+    const uint32_t* g = m->configs[c].cfg;
+    const int k = m->configs[c].K;
+    if ((H < 0 || H == (int)g[1]) && (W < 0 || W == (int)g[2]) && (E < 0 || E == (int)g[0]) && (steps < 0 || steps == (int)g[5]) && (K < 0 || K == k))
+      return (int)c;
+    char one[96];
+    snprintf(one, sizeof(one), "%s%u x %u (E %u, %u steps, K %d)", c ? ", " : "", g[1], g[2], g[0], g[5], k);
+    if (have.size() < 600) have += one;
+  }
+  mg_set_error("mg_model_find_config: no configuration for %d x %d, E %d, %d steps, K %d (-1 = any); the image holds %s", H, W, E, steps, K, have.c_str());
+  return -1;
+}
+
+int mg_model_select(mg_model* m, int index) {
+  MG_REQUIRE(m, "mg_model_select: null model");
+  MG_REQUIRE(index >= 0 && index < (int)m->configs.size(), "mg_model_select: configuration %d of %d", index, (int)m->configs.size());
+  m->sel = index;
+  return 0;
+}
+
+int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W) {
+  MG_REQUIRE(H && W && Hin > 0 && Win > 0 && processing_res >= 0, "mg_processed_size: bad arguments (%d x %d, processing_res %d)", Hin, Win, processing_res);
+  *H = Hin;
+  *W = Win;
+  if (processing_res > 0) {   // util/image_util.py::max_res_size: Python's float arithmetic is this double arithmetic, int() truncates
+    const double fw = (double)processing_res / (double)Win, fh = (double)processing_res / (double)Hin;
+    const double factor = fw < fh ? fw : fh;
+    *W = (int)((double)Win * factor);
+    *H = (int)((double)Hin * factor);
+  }
   return 0;
 }
 
 long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes) : 0; }
 
+long long mg_model_shared_bytes(const mg_model* m) { return m ? (long long)m->plan->shared_bytes : 0; }
+
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
-  for (Prog* p : {&m->enc, &m->den, &m->dec})
+  const Config& c = m->cur();
+  for (const Prog* p : {&c.enc, &c.den, &c.dec})
     if (int rc = mg_program_validate(p->prog)) return rc;
   return 0;
 }
@@ -258,37 +539,40 @@ int mg_model_validate(mg_model* m) {
 int mg_model_vae_encode(mg_model* m, const float* rgb, float* latent, void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && latent, "mg_model_vae_encode: bad arguments (or a host-only model)");
   const hipStream_t s = (hipStream_t)stream;
-  const Slot *in = m->enc.slot("rgb"), *out = m->enc.slot("latent");
+  const Config& c = m->cur();
+  const Slot *in = c.enc.slot("rgb"), *out = c.enc.slot("latent");
   if (int rc = copy_dd(in->ptr, rgb, in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(m->enc.prog, stream)) return rc;
+  if (int rc = mg_program_run(c.enc.prog, stream)) return rc;
   return copy_dd(latent, out->ptr, out->nbytes, s);
 }
 
 int mg_model_denoise(mg_model* m, const float* rgb_latent, float* x, const float* step_noise, void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb_latent && x, "mg_model_denoise: bad arguments (or a host-only model)");
   const hipStream_t s = (hipStream_t)stream;
-  const Slot *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
+  const Config& c = m->cur();
+  const Slot *rl = c.den.slot("rgb_latent"), *xs = c.den.slot("x");
   if (int rc = copy_dd(rl->ptr, rgb_latent, rl->nbytes, s)) return rc;
   if (int rc = copy_dd(xs->ptr, x, xs->nbytes, s)) return rc;
-  const int n_noise = (int)m->hdr.cfg[8];
+  const int n_noise = (int)c.cfg[8];
   MG_REQUIRE(n_noise == 0 || step_noise, "mg_model_denoise: this scheduler draws noise in %d steps: pass [%d][B][C][h][w] floats", n_noise, n_noise);
   for (int k = 0; k < n_noise; ++k) {
     char nm[24];
     snprintf(nm, sizeof(nm), "noise%d", k);
-    const Slot* ns = m->den.slot(nm);
+    const Slot* ns = c.den.slot(nm);
     MG_REQUIRE(ns, "mg_model_denoise: the image lacks slot %s", nm);
     if (int rc = copy_dd(ns->ptr, (const char*)step_noise + (uint64_t)k * ns->nbytes, ns->nbytes, s)) return rc;
   }
-  if (int rc = mg_program_run(m->den.prog, stream)) return rc;
+  if (int rc = mg_program_run(c.den.prog, stream)) return rc;
   return copy_dd(x, xs->ptr, xs->nbytes, s);
 }
 
 int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* stream) {
   MG_REQUIRE(m && !m->host_only && latent && pred, "mg_model_vae_decode: bad arguments (or a host-only model)");
   const hipStream_t s = (hipStream_t)stream;
-  const Slot *in = m->dec.slot("latent"), *out = m->dec.slot("pred");
+  const Config& c = m->cur();
+  const Slot *in = c.dec.slot("latent"), *out = c.dec.slot("pred");
   if (int rc = copy_dd(in->ptr, latent, in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(m->dec.prog, stream)) return rc;
+  if (int rc = mg_program_run(c.dec.prog, stream)) return rc;
   return copy_dd(pred, out->ptr, out->nbytes, s);
 }
 
@@ -449,12 +733,12 @@ int grow_tmp(void** p, uint64_t* bytes, uint64_t need) {
 // decode program's output slot, *preds.  One picture per call is the n = K = 1 case.
 int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
                     const uint64_t* seeds, void* stream, const float** preds) {
-  const uint32_t* cfg = m->hdr.cfg;
-  const int K = m->K, H = (int)cfg[1], W = (int)cfg[2], n_noise = (int)cfg[8];
+  const uint32_t* cfg = m->cur().cfg;
+  const int K = m->cur().K, H = (int)cfg[1], W = (int)cfg[2], n_noise = (int)cfg[8];
   MG_REQUIRE(Hin > 0 && Win > 0, "%s: bad input size %d x %d", who, Hin, Win);
   const hipStream_t s = (hipStream_t)stream;
-  const Slot *e_in = m->enc.slot("rgb"), *e_out = m->enc.slot("latent"), *rl = m->den.slot("rgb_latent"), *xs = m->den.slot("x");
-  const Slot *d_in = m->dec.slot("latent"), *d_out = m->dec.slot("pred");
+  const Slot *e_in = m->cur().enc.slot("rgb"), *e_out = m->cur().enc.slot("latent"), *rl = m->cur().den.slot("rgb_latent"), *xs = m->cur().den.slot("x");
+  const Slot *d_in = m->cur().dec.slot("latent"), *d_out = m->cur().dec.slot("pred");
   // (mg_model_load checked that the slots chain)
   const uint64_t rgb_row = e_in->nbytes / K, x_rows = xs->nbytes / K;   // bytes per picture
   // 1. picture i -> [1,3,H,W] in [-1, 1], row i of the encoder's input slot
@@ -466,7 +750,7 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
   for (int i = 0; i < K; ++i)
     if (int rc = mg_rgb_prepare(rgb[i < n ? i : n - 1], hwc, Hin, Win, e_in->ptr + i * rgb_row, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
   // 2. encode
-  if (int rc = mg_program_run(m->enc.prog, stream)) return rc;
+  if (int rc = mg_program_run(m->cur().enc.prog, stream)) return rc;
   if (int rc = copy_dd(rl->ptr, e_out->ptr, rl->nbytes, s)) return rc;
   // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
   for (int i = 0; i < K; ++i)
@@ -474,15 +758,15 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
   for (int k = 0; k < n_noise; ++k) {
     char nm[24];
     snprintf(nm, sizeof(nm), "noise%d", k);
-    const Slot* ns = m->den.slot(nm);
+    const Slot* ns = m->cur().den.slot(nm);
     MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "%s: the image lacks slot %s", who, nm);
     for (int i = 0; i < K; ++i)
       if (int rc = mg_randn(seeds[i < n ? i : n - 1], (uint64_t)k + 1, 0, (int64_t)(x_rows / 4), ns->ptr + i * x_rows, 0, stream)) return rc;
   }
   // 4. denoise, 5. decode (an intrinsic-image model: the latent [B, 4 n, h, w] is the decoder's batch [B n, 4, h, w], the same bytes)
-  if (int rc = mg_program_run(m->den.prog, stream)) return rc;
+  if (int rc = mg_program_run(m->cur().den.prog, stream)) return rc;
   if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(m->dec.prog, stream)) return rc;
+  if (int rc = mg_program_run(m->cur().dec.prog, stream)) return rc;
   *preds = (const float*)d_out->ptr;
   return 0;
 }
@@ -531,7 +815,7 @@ template <class Ensemble, class Finish>
 int predict_resized(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
                     const uint64_t* seeds, int planes, int oh, int ow, int out_mode, uint64_t ws_bytes, float* pred_out, float** ws, void* stream,
                     Ensemble ensemble, Finish finish) {
-  const int B = (int)m->hdr.cfg[0], Ho = (int)m->hdr.cfg[11], Wo = (int)m->hdr.cfg[12];
+  const int B = (int)m->cur().cfg[0], Ho = (int)m->cur().cfg[11], Wo = (int)m->cur().cfg[12];
   const bool resize = oh != Ho || ow != Wo;
   const OutTmp t = out_tmp_layout(B, planes, Ho, Wo, oh, ow, out_mode, ws_bytes);
   if (int rc = grow_tmp(&m->out_tmp, &m->out_tmp_bytes, t.total())) return rc;
@@ -565,7 +849,7 @@ int predict_depth_or_normals(mg_model* m, const char* who, int n, const uint8_t*
                              const uint64_t* seeds, const mg_predict_opts* opts_or_null, int oh, int ow, int out_mode, bool clip,
                              const uint8_t* lut256x3, float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null,
                              uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
-  const uint32_t* cfg = m->hdr.cfg;
+  const uint32_t* cfg = m->cur().cfg;
   const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], Ho = (int)cfg[11], Wo = (int)cfg[12];
   static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
   const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
@@ -597,7 +881,7 @@ int predict_depth_or_normals(mg_model* m, const char* who, int n, const uint8_t*
 int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
                      const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
                      float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
-  const uint32_t* cfg = m->hdr.cfg;
+  const uint32_t* cfg = m->cur().cfg;
   const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "%s: an intrinsic-image model goes through mg_model_predict_iid", who);
   const bool depth = post == MG_POST_DEPTH && C == 1;
@@ -619,14 +903,14 @@ int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* 
 
 // An image of several pictures per call runs through mg_model_predict_many only
 #define MG_REQUIRE_ONE_PICTURE(m, who) \
-  MG_REQUIRE((m)->K == 1, who ": this image runs %d pictures per call: use mg_model_predict_many", (m)->K)
+  MG_REQUIRE((m)->cur().K == 1, who ": this image runs %d pictures per call: use mg_model_predict_many", (m)->cur().K)
 
 extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
                                 const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
                                 void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
   MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict");
-  const uint32_t* cfg = m->hdr.cfg;
+  const uint32_t* cfg = m->cur().cfg;
   const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
   MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
@@ -652,7 +936,7 @@ extern "C" int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* r
                                      double* info4_or_null, void* stream) {
   MG_REQUIRE(m, "mg_model_predict_many: null model");
   MG_REQUIRE(!m->host_only, "mg_model_predict_many: a host-only model cannot predict (load it with device >= 0)");
-  MG_REQUIRE(n >= 1 && n <= m->K, "mg_model_predict_many: %d pictures for an image of %d per call (1 <= n <= %d)", n, m->K, m->K);
+  MG_REQUIRE(n >= 1 && n <= m->cur().K, "mg_model_predict_many: %d pictures for an image of %d per call (1 <= n <= %d)", n, m->cur().K, m->cur().K);
   MG_REQUIRE(rgb && seeds && pred_out, "mg_model_predict_many: null argument (the rgb and seeds arrays and pred_out are required)");
   for (int i = 0; i < n; ++i) MG_REQUIRE(rgb[i], "mg_model_predict_many: null picture %d of %d", i, n);
   return predict_out_many(m, "mg_model_predict_many", n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, out_opts_or_null, pred_out,
@@ -664,7 +948,7 @@ extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, in
                                     void* stream) {
   MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict_iid: bad arguments (or a host-only model)");
   MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_iid");
-  const uint32_t* cfg = m->hdr.cfg;
+  const uint32_t* cfg = m->cur().cfg;
   const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8], n = (int)cfg[10];
   const int Ho = (int)cfg[11], Wo = (int)cfg[12];
   MG_REQUIRE(post == MG_POST_UNIT && n >= 1 && C == 3 * n,

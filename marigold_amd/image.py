@@ -1,4 +1,5 @@
-"""Model images: the pipeline's native programs for ONE problem shape, compiled ahead of time into a single file that
+"""Model images: the pipeline's native programs for one problem shape - or, with ``configs=[...]``, for several - compiled ahead of
+time into a single file that
 ``libmarigold_hip.so`` loads and runs WITHOUT Python (``mg_model_load`` / ``mg_model_vae_encode`` / ``mg_model_denoise`` /
 ``mg_model_vae_decode`` in include/marigold_hip.h) - the module-level C entry points SURVEY.md section 8(b) proposes for the
 seams ``single_infer`` calls (marigold_depth_pipeline.py:396-477: ``encode_rgb`` :491-495, the T-step ``unet`` +
@@ -14,6 +15,14 @@ Every device pointer inside an ``mg_op`` is recorded as (buffer, byte offset) - 
 weights, zeroes what must start zeroed and patches the pointers.  ``export_model_image`` works on a host without a GPU (the
 programs are built against host buffers exactly as ``mg_program_validate`` does), so the CPU test-suite round-trips an image
 through the C loader.
+
+An image of several configurations (version 2) has the same parts with one more table in front:
+
+    header | configurations, scratch region | configuration table (cfg[16] + three programs each) | buffer table | blobs
+
+The modules' packed weights (``mod.ws.cache``) are written once, as buffers every configuration refers to; the loader keeps them in
+an allocation that ``mg_model_replica`` handles share.  A call with the keywords of one configuration writes the version-1 file it
+always wrote.
 """
 import ctypes
 import struct
@@ -26,7 +35,8 @@ from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 
 MAGIC = b"MGIMG1\0\0"
 VERSION = 1
-KIND_SCRATCH, KIND_ZERO, KIND_DATA = 0, 1, 2
+VERSION_CONFIGS = 2   # several configurations in one image (export_model_image(configs=[...]))
+KIND_SCRATCH, KIND_ZERO, KIND_DATA, KIND_SHARED = 0, 1, 2, 3   # SHARED: the weight cache of a version-2 image, stored once
 SLOT_LN_COUNTERS = 100   # relocation slot of MG_OP_IGEMM's ticket address pair (ops.igemm_tickets); slots 0..15 = p[k]
 _PRED = {"depth": (L.POST_DEPTH, 1), "normals": (L.POST_NORMALS, 3), "iid": (L.POST_UNIT, 3)}
 
@@ -83,14 +93,17 @@ def _pad(f, align=64):
     return f.tell()
 
 
-def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_steps=None, images_per_program=1):
-    """Write the model image of ``pipe`` for images of ``height`` x ``width`` (the size fed to the VAE: after the pipeline's
-    ``processing_res`` resize), ``ensemble_size`` members per picture and ``denoising_steps`` scheduler steps.  Works with the
-    modules on the GPU (``pipe.to("cuda")``) or, without one, in the host-only mode.  Returns a dict describing the image.
+_CFG_KEYS = ("ensemble_size", "height", "width", "denoising_steps", "images_per_program")
+HDR, BUF, PROG, SLOT, REL = "<8sIIII16I", "<QQII", "<32sIIQQI", "<24sIIQQ", "<IIIIQ"
+V2, MAXSLOT = "<IIQ", 16   # version 2, after the header: configurations, pad, bytes of the scratch region
 
-    ``images_per_program`` = K > 1: the image runs K pictures per call (``mg_model_predict_many``) through the programs
-    ``map_images(images_per_program=K)`` runs for a full group - one encode of K pictures, one denoising program of K x
-    ``ensemble_size`` members, one decode; the header's ``cfg[13]`` is K.  K = 1 writes the one-picture image, ``cfg[13]`` = 0."""
+
+def _r256(n):
+    return (n + 255) // 256 * 256
+
+
+def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_program=1):
+    """The three programs of one configuration, built (or found) in the modules of ``pipe``, and its 16 ``cfg`` words."""
     K = int(images_per_program)
     if K < 1:
         raise ValueError(f"export_model_image: images_per_program must be >= 1 (got {images_per_program})")
@@ -119,17 +132,25 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
         den = unet.denoise_program(K * B, h, w, pipe.scheduler, T, rgb_members=B)
     n_mod = getattr(pipe, "n_targets", 1)
     dec_seq, dec_in, dec_out = vae._program("decode", K * B * n_mod, h, w, post)
-
-    bufs = _Buffers()
-    for mod in (unet, vae):
-        for v in mod.ws.cache.values():
-            for t in _tensors(v):
-                bufs.add(t, KIND_DATA)
-        for t in mod.pool.all:
-            bufs.add(t, KIND_SCRATCH)
     progs = [("vae.encode", enc_seq, {"rgb": enc_in, "latent": enc_out}),
              ("denoise", den.seq, dict({"rgb_latent": den.rgb_latent, "x": den.x}, **{f"noise{k}": nz for k, nz in enumerate(den.noises)})),
              ("vae.decode", dec_seq, {"latent": dec_in, "pred": dec_out})]
+    sz_op = ctypes.sizeof(L.MgOp)
+    cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, dec_out.shape[-2], dec_out.shape[-1],
+           K if K > 1 else 0] + [0] * 2
+    return progs, [int(c) for c in cfg]
+
+
+def _plan(pipe, progs, cache_kind=KIND_DATA):
+    """Every buffer the programs point into: the modules' weight cache (kind ``cache_kind``), the scratch of the workspace pools that
+    these programs use, and what the programs hold themselves (zeroed state, constants, input / output slots)."""
+    bufs = _Buffers()
+    for mod in (pipe.unet, pipe.vae):
+        for v in mod.ws.cache.values():
+            for t in _tensors(v):
+                bufs.add(t, cache_kind)
+        for t in mod.pool.all:
+            bufs.add(t, KIND_SCRATCH)
     for _, seq, io in progs:
         for t in seq.keep:
             # zero-initialised state the kernels rely on (V^T pad columns, tickets, flash workspace): tagged by the builder
@@ -157,79 +178,195 @@ def export_model_image(pipe, path, *, ensemble_size, height, width, denoising_st
                 used.add(hit[0])
     bufs.items = [it for k, it in enumerate(bufs.items) if it[2] != KIND_SCRATCH or k in used]
     bufs.starts = [it[0] for it in bufs.items]
+    return bufs
 
+
+def _relocate(progs, bufs, index=None):
+    """The programs' op arrays with every device pointer taken out and recorded as (op, slot, buffer, byte offset); ``index``: the
+    buffer numbers to write (the image's table), by position in ``bufs`` (None: the position itself)."""
     sz_op = ctypes.sizeof(L.MgOp)
-    with open(path, "wb") as f:
-        ptab, relocs_all, ops_all = [], [], []
-        for name, seq, io in progs:
-            relocs, raw = [], bytearray()
-            for k, op in enumerate(seq.ops):
-                c = L.MgOp()
-                ctypes.memmove(ctypes.addressof(c), ctypes.addressof(op), sz_op)
-                for s in range(16):
-                    ptr = c.p[s]
-                    if ptr:
-                        hit = bufs.find(ptr)
-                        if hit is None:
-                            raise RuntimeError(f"model image: op {k} ({seq.labels[k]}) of {name} points outside every known buffer (p[{s}])")
-                        relocs.append((k, s, hit[0], hit[1]))
-                        c.p[s] = None
-                if c.kind == L.OP_IGEMM and O.igemm_tickets(c):
-                    hit = bufs.find(O.igemm_tickets(c))
+    num = (lambda b: b) if index is None else (lambda b: index[b])
+    ptab, relocs_all, ops_all = [], [], []
+    for name, seq, io in progs:
+        relocs, raw = [], bytearray()
+        for k, op in enumerate(seq.ops):
+            c = L.MgOp()
+            ctypes.memmove(ctypes.addressof(c), ctypes.addressof(op), sz_op)
+            for s in range(16):
+                ptr = c.p[s]
+                if ptr:
+                    hit = bufs.find(ptr)
                     if hit is None:
-                        raise RuntimeError(f"model image: the row-statistics tickets of op {k} of {name} are not in a known buffer")
-                    relocs.append((k, SLOT_LN_COUNTERS, hit[0], hit[1]))
-                    O.set_igemm_tickets(c, None)
-                raw += bytes(c)
-            slots = []
-            for nm, t in io.items():
-                hit = bufs.find(t.data_ptr())
-                slots.append((nm, hit[0], hit[1], t.numel() * t.element_size()))
-            ptab.append((name, len(seq.ops), slots))
-            relocs_all.append(relocs)
-            ops_all.append(bytes(raw))
+                        raise RuntimeError(f"model image: op {k} ({seq.labels[k]}) of {name} points outside every known buffer (p[{s}])")
+                    relocs.append((k, s, num(hit[0]), hit[1]))
+                    c.p[s] = None
+            if c.kind == L.OP_IGEMM and O.igemm_tickets(c):
+                hit = bufs.find(O.igemm_tickets(c))
+                if hit is None:
+                    raise RuntimeError(f"model image: the row-statistics tickets of op {k} of {name} are not in a known buffer")
+                relocs.append((k, SLOT_LN_COUNTERS, num(hit[0]), hit[1]))
+                O.set_igemm_tickets(c, None)
+            raw += bytes(c)
+        slots = []
+        for nm, t in io.items():
+            hit = bufs.find(t.data_ptr())
+            slots.append((nm, num(hit[0]), hit[1], t.numel() * t.element_size()))
+        ptab.append((name, len(seq.ops), slots))
+        relocs_all.append(relocs)
+        ops_all.append(bytes(raw))
+    return ptab, relocs_all, ops_all
+
+
+def _write_data(f, item):
+    start, end, _k, t = item
+    off = _pad(f)
+    f.write(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes() if t.numel() * t.element_size() == end - start
+            else bytes((ctypes.c_char * (end - start)).from_address(start)))
+    return off
+
+
+def _write_blobs(f, ops_all, relocs_all):
+    ops_off, rel_off = [], []
+    for raw, relocs in zip(ops_all, relocs_all):
+        ops_off.append(_pad(f))
+        f.write(raw)
+        rel_off.append(_pad(f))
+        for (k, s, b, o) in relocs:
+            f.write(struct.pack(REL, k, s, b, 0, o))
+    return ops_off, rel_off
+
+
+def _write_programs(f, ptab, ops_off, rel_off, relocs_all):
+    for (name, n_ops, slots), oo, ro, relocs in zip(ptab, ops_off, rel_off, relocs_all):
+        assert len(slots) <= MAXSLOT, "model image: too many program slots"
+        f.write(struct.pack(PROG, name.encode(), n_ops, len(relocs), oo, ro, len(slots)))
+        f.write(b"\0" * 4)
+        for (nm, b, o, n) in slots:
+            f.write(struct.pack(SLOT, nm.encode(), b, 0, o, n))
+        f.write(b"\0" * ((MAXSLOT - len(slots)) * struct.calcsize(SLOT)))
+
+
+def _describe(path, total, bufs, ptab, cfg):
+    """What ``export_model_image`` returns for one configuration.  ``arena``: the device bytes the loader places (every buffer
+    rounded up to 256): the weight cache, the configuration's own constants and zeroed state, its scratch."""
+    items = bufs.items
+    nbytes = {k: sum(it[1] - it[0] for it in items if it[2] == k) for k in (KIND_SCRATCH, KIND_ZERO, KIND_DATA, KIND_SHARED)}
+    arena = {k: sum(_r256(it[1] - it[0]) for it in items if it[2] in ks)
+             for k, ks in (("shared", (KIND_SHARED,)), ("private", (KIND_ZERO, KIND_DATA)), ("scratch", (KIND_SCRATCH,)))}
+    return dict(path=path, file_bytes=total, buffers=len(items), scratch_bytes=nbytes[KIND_SCRATCH], zero_bytes=nbytes[KIND_ZERO],
+                data_bytes=nbytes[KIND_DATA] + nbytes[KIND_SHARED], ops={n: c for (n, c, _s) in ptab}, latent_hw=(cfg[3], cfg[4]), B=cfg[0],
+                steps=cfg[5], pred_channels=cfg[6], step_noises=cfg[8], images_per_program=cfg[13] or 1, cfg16=list(cfg), arena=arena)
+
+
+def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=None, width=None, denoising_steps=None, images_per_program=1):
+    """Write the model image of ``pipe`` for images of ``height`` x ``width`` (the size fed to the VAE: after the pipeline's
+    ``processing_res`` resize), ``ensemble_size`` members per picture and ``denoising_steps`` scheduler steps.  Works with the
+    modules on the GPU (``pipe.to("cuda")``) or, without one, in the host-only mode.  Returns a dict describing the image.
+
+    ``images_per_program`` = K > 1: the image runs K pictures per call (``mg_model_predict_many``) through the programs
+    ``map_images(images_per_program=K)`` runs for a full group - one encode of K pictures, one denoising program of K x
+    ``ensemble_size`` members, one decode; the header's ``cfg[13]`` is K.  K = 1 writes the one-picture image, ``cfg[13]`` = 0.
+
+    ``configs`` = a list of dicts of the keywords above (instead of them): ONE image for several configurations - a version-2 file
+    with a configuration table and one buffer table, the modules' packed weights stored once (kind ``KIND_SHARED``) and each
+    configuration's own constants, zeroed state and scratch tagged with its index.  ``mg_model_select`` picks the configuration a
+    loaded image runs.  The dict returned then holds ``configs`` (one dict as above per entry), ``shared_bytes`` and
+    ``scratch_bytes`` (the scratch region: the largest configuration's, not the sum)."""
+    if configs is not None:
+        if any(v is not None for v in (ensemble_size, height, width, denoising_steps)) or images_per_program != 1:
+            raise ValueError("export_model_image: pass either configs=[...] or the keywords of one configuration, not both")
+        return _export_configs(pipe, path, list(configs))
+    if ensemble_size is None or height is None or width is None:
+        raise TypeError("export_model_image: ensemble_size, height and width are required (or configs=[...])")
+    progs, cfg = _build(pipe, ensemble_size, height, width, denoising_steps, images_per_program)
+    bufs = _plan(pipe, progs)
+    with open(path, "wb") as f:
+        ptab, relocs_all, ops_all = _relocate(progs, bufs)
         # ---- layout: header, buffer table, program table, then 64-byte aligned blobs
         n_buf, n_prog = len(bufs.items), len(progs)
-        HDR, BUF, PROG, SLOT, REL = "<8sIIII16I", "<QQII", "<32sIIQQI", "<24sIIQQ", "<IIIIQ"
-        MAXSLOT = 16
         prog_sz = struct.calcsize(PROG) + 4 + MAXSLOT * struct.calcsize(SLOT)
         table_end = struct.calcsize(HDR) + n_buf * struct.calcsize(BUF) + n_prog * prog_sz
         f.write(b"\0" * table_end)
-        buf_off = []
-        for (start, end, k, t) in bufs.items:
-            if k == KIND_DATA:
-                off = _pad(f)
-                f.write(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes() if t.numel() * t.element_size() == end - start
-                        else bytes((ctypes.c_char * (end - start)).from_address(start)))
-                buf_off.append(off)
-            else:
-                buf_off.append(0)
-        ops_off, rel_off = [], []
-        for raw, relocs in zip(ops_all, relocs_all):
-            ops_off.append(_pad(f))
-            f.write(raw)
-            rel_off.append(_pad(f))
-            for (k, s, b, o) in relocs:
-                f.write(struct.pack(REL, k, s, b, 0, o))
+        buf_off = [_write_data(f, it) if it[2] == KIND_DATA else 0 for it in bufs.items]
+        ops_off, rel_off = _write_blobs(f, ops_all, relocs_all)
         total = f.tell()
         f.seek(0)
-        cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, dec_out.shape[-2], dec_out.shape[-1],
-               K if K > 1 else 0] + [0] * 2
         f.write(struct.pack(HDR, MAGIC, VERSION, L.ABI_VERSION, n_buf, n_prog, *cfg))
         for (start, end, k, _t), off in zip(bufs.items, buf_off):
             f.write(struct.pack(BUF, end - start, off, k, 0))
-        for (name, n_ops, slots), oo, ro, relocs in zip(ptab, ops_off, rel_off, relocs_all):
-            assert len(slots) <= MAXSLOT, "model image: too many program slots"
-            f.write(struct.pack(PROG, name.encode(), n_ops, len(relocs), oo, ro, len(slots)))
-            f.write(b"\0" * 4)
-            for (nm, b, o, n) in slots:
-                f.write(struct.pack(SLOT, nm.encode(), b, 0, o, n))
-            f.write(b"\0" * ((MAXSLOT - len(slots)) * struct.calcsize(SLOT)))
+        _write_programs(f, ptab, ops_off, rel_off, relocs_all)
         assert f.tell() == table_end
-    nbytes = {k: sum(it[1] - it[0] for it in bufs.items if it[2] == k) for k in (KIND_SCRATCH, KIND_ZERO, KIND_DATA)}
-    return dict(path=path, file_bytes=total, buffers=n_buf, scratch_bytes=nbytes[KIND_SCRATCH], zero_bytes=nbytes[KIND_ZERO],
-                data_bytes=nbytes[KIND_DATA], ops={n: c for (n, c, _s) in ptab}, latent_hw=(int(h), int(w)), B=B, steps=T,
-                pred_channels=cpred * n_mod, step_noises=len(den.noises), images_per_program=K)
+    # (the same plan with the weight cache told apart from the constants: what a version-2 image would share)
+    return _describe(path, total, _plan(pipe, progs, KIND_SHARED), ptab, cfg)
+
+
+def _export_configs(pipe, path, configs):
+    if not configs:
+        raise ValueError("export_model_image: configs is empty")
+    seen, built = set(), []
+    for n, c in enumerate(configs):
+        c = dict(c)
+        p = c.pop("pipe", pipe)   # (an entry may name its own pipeline object over the same modules)
+        unknown = sorted(set(c) - set(_CFG_KEYS))
+        if unknown or not all(k in c for k in _CFG_KEYS[:3]):
+            raise ValueError(f"export_model_image: configuration {n} takes the keywords {', '.join(_CFG_KEYS)} (the first three are required); "
+                             f"got {sorted(c)}")
+        if p._kind != pipe._kind:
+            raise ValueError(f"export_model_image: the configurations of one image are of one pipeline kind: configuration {n} is "
+                             f"'{p._kind}', the image '{pipe._kind}'")
+        if p.unet is not pipe.unet or p.vae is not pipe.vae:
+            raise ValueError(f"export_model_image: configuration {n} belongs to other modules: one image shares one set of weights")
+        key = (int(c["ensemble_size"]), int(c["height"]), int(c["width"]), int(c.get("denoising_steps") or p.default_denoising_steps),
+               int(c.get("images_per_program", 1)))
+        if key in seen:
+            raise ValueError(f"export_model_image: configuration {n} (ensemble_size, height, width, denoising_steps, images_per_program = {key}) "
+                             "is listed twice")
+        seen.add(key)
+        built.append(_build(p, **c))
+    # every configuration is built: the weight cache now holds what all of them need
+    plans = [_plan(pipe, progs, KIND_SHARED) for progs, _cfg in built]
+    shared = {}   # (start, end) -> number in the image's buffer table; the shared buffers come first
+    for bufs in plans:
+        for it in bufs.items:
+            if it[2] == KIND_SHARED:
+                shared.setdefault((it[0], it[1]), (len(shared), it))
+    table = [(it[1] - it[0], KIND_SHARED, 0, it) for _n, it in sorted(shared.values(), key=lambda v: v[0])]
+    per_cfg, scratch_region = [], 0
+    for ci, (bufs, (progs, cfg)) in enumerate(zip(plans, built)):
+        index, scratch = [], 0
+        for it in bufs.items:
+            if it[2] == KIND_SHARED:
+                index.append(shared[it[0], it[1]][0])
+                continue
+            index.append(len(table))
+            table.append((it[1] - it[0], it[2], ci, scratch if it[2] == KIND_SCRATCH else it))
+            if it[2] == KIND_SCRATCH:   # its place in the scratch region every configuration overlays
+                scratch += _r256(it[1] - it[0])
+        scratch_region = max(scratch_region, scratch)
+        per_cfg.append(_relocate(progs, bufs, index))
+    prog_sz = struct.calcsize(PROG) + 4 + MAXSLOT * struct.calcsize(SLOT)
+    with open(path, "wb") as f:
+        # ---- layout: header, version-2 words, configuration table (cfg[16] + three programs each), buffer table, blobs
+        table_end = struct.calcsize(HDR) + struct.calcsize(V2) + len(built) * (64 + 3 * prog_sz) + len(table) * struct.calcsize(BUF)
+        f.write(b"\0" * table_end)
+        rows = []
+        for (nbytes, kind, ci, what) in table:
+            rows.append((nbytes, what if kind == KIND_SCRATCH else _write_data(f, what) if kind in (KIND_DATA, KIND_SHARED) else 0, kind, ci))
+        offs = [_write_blobs(f, ops_all, relocs_all) for (_ptab, relocs_all, ops_all) in per_cfg]
+        total = f.tell()
+        f.seek(0)
+        f.write(struct.pack(HDR, MAGIC, VERSION_CONFIGS, L.ABI_VERSION, len(table), 3 * len(built), *built[0][1]))
+        f.write(struct.pack(V2, len(built), 0, scratch_region))
+        for (_progs, cfg), (ptab, relocs_all, _ops), (ops_off, rel_off) in zip(built, per_cfg, offs):
+            f.write(struct.pack("<16I", *cfg))
+            _write_programs(f, ptab, ops_off, rel_off, relocs_all)
+        for row in rows:
+            f.write(struct.pack(BUF, *row))
+        assert f.tell() == table_end
+    described = [_describe(path, total, bufs, ptab, cfg) for bufs, (_p, cfg), (ptab, _r, _o) in zip(plans, built, per_cfg)]
+    return dict(path=path, file_bytes=total, buffers=len(table), configs=described,
+                shared_bytes=sum(_r256(n) for (n, k, _c, _w) in table if k == KIND_SHARED), scratch_bytes=scratch_region,
+                private_bytes=sum(d["arena"]["private"] for d in described) + scratch_region)
 
 
 def export_color_table(cmap, path):
@@ -249,18 +386,61 @@ class ModelImage:
     graph-free way to run a fixed-shape deployment: ``encode`` / ``denoise`` / ``decode`` take and return torch CUDA tensors
     but only their raw pointers cross into the library."""
 
-    def __init__(self, path, device=0):
+    def __init__(self, path, device=0, *, _handle=None):
         lib = L.load()
         self._lib = lib
-        self.handle = lib.mg_model_load(path.encode(), int(device))
+        self.handle = _handle if _handle is not None else lib.mg_model_load(path.encode(), int(device))
         if not self.handle:
             L.check(1, "mg_model_load")
+        self.path, self.device = path, device
+        self.configs = []   # the 16 cfg words of every configuration the image holds (a version-1 image: one)
         cfg = (ctypes.c_int * 16)()
-        L.check(lib.mg_model_info(self.handle, cfg), "mg_model_info")
+        for i in range(lib.mg_model_num_configs(self.handle)):
+            L.check(lib.mg_model_config_info(self.handle, i, cfg), "mg_model_config_info")
+            self.configs.append(list(cfg))
+        self._selected()
+
+    def _selected(self):
+        """The attributes of the selected configuration (``mg_model_info``)."""
+        cfg = (ctypes.c_int * 16)()
+        L.check(self._lib.mg_model_info(self.handle, cfg), "mg_model_info")
         (self.B, self.H, self.W, self.h, self.w, self.steps, self.pred_channels, self.post, self.n_noise) = list(cfg)[:9]
         self.Hout, self.Wout = cfg[11], cfg[12]
         self.K = cfg[13] or 1   # pictures per call; B: the members of each
-        self.device = device
+
+    def find(self, height=-1, width=-1, ensemble_size=-1, denoising_steps=-1, images_per_program=-1):
+        """``mg_model_find_config``: the index of the first configuration that matches (-1 = any value); raises if none does."""
+        i = self._lib.mg_model_find_config(self.handle, int(height), int(width), int(ensemble_size), int(denoising_steps), int(images_per_program))
+        if i < 0:
+            L.check(1, "mg_model_find_config", self._lib)
+        return i
+
+    def select(self, index):
+        """``mg_model_select``: every call below acts on configuration ``index`` from now on.  Returns ``self``."""
+        L.check(self._lib.mg_model_select(self.handle, int(index)), "mg_model_select", self._lib)
+        self.selected = int(index)
+        self._selected()
+        return self
+
+    selected = 0
+
+    def replica(self):
+        """``mg_model_replica``: a second handle over the same device-resident weights, with its own arena, programs and
+        temporaries - to be driven from another thread on another stream."""
+        h = self._lib.mg_model_replica(self.handle)
+        if not h:
+            L.check(1, "mg_model_replica", self._lib)
+        r = ModelImage(self.path, self.device, _handle=h)
+        r.selected = self.selected
+        return r
+
+    @property
+    def shared_bytes(self):
+        return self._lib.mg_model_shared_bytes(self.handle)
+
+    @property
+    def device_bytes(self):
+        return self._lib.mg_model_device_bytes(self.handle)
 
     def validate(self):
         L.check(self._lib.mg_model_validate(self.handle), "mg_model_validate")
