@@ -1003,6 +1003,31 @@ int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* rgb, int hwc
                           float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
                           double* info4_or_null, void* stream);
 
+/* Image SEQUENCES: mg_model_predict_out with the recipe of frame-by-frame video processing - frame k starts from
+ * (1 - strength) noise + strength latent, where latent is the denoised latent of frame k - 1 on this handle.  The handle keeps ONE
+ * carried buffer, the bytes of the denoise program's x slot, allocated at the first mg_model_predict_next and counted by
+ * mg_model_device_bytes.  mg_model_predict_next is mg_model_predict_out, argument for argument, with two additions to its chain: after
+ * MG_OP_RANDN of stream 0, if a latent is carried, mg_latent_carry blends it into the x slot; after the denoise program the x slot is
+ * copied, device to device, into the carried buffer.  The noise is drawn as mg_model_predict_out draws it (the LCM step noises too).
+ * The first call after mg_model_load, mg_model_replica, mg_model_seq_reset or mg_model_select carries nothing and returns the bits of
+ * mg_model_predict_out; a replica has a state of its own, empty at first.  mg_model_predict_out itself neither reads nor changes the
+ * state.  Refused before anything is launched, with mg_model_predict_out's refusals: a strength outside [0, 1] (or NaN), a
+ * configuration of K > 1 pictures per call, an intrinsic-image model.  Synchronises where mg_model_predict_out does.  The Python
+ * pipelines give the same arrays and pictures, bit for bit, with map_video(frames, strength, generators=[NativeNoise(seed_k)],
+ * match_input_res=True) (tests/test_gpu_sequence.py; examples/host_sequence.cpp).
+ *  mg_model_seq_reset: forget the carried latent (the buffer stays allocated); the next mg_model_predict_next starts a sequence.
+ *  mg_latent_carry: the blend itself, in place on device pointers: x[i] = fl(fl(a x[i]) + fl(b prev[i])) with b = strength and
+ *  a = (float)(1.0 - (double)strength) - three fp32 roundings, no fused multiply-add: the bits of torch's (x * a) + (prev * b).
+ *  NaN and infinities propagate as IEEE 754 has them.  Four elements per lane when both pointers are 16-byte aligned, one otherwise;
+ *  nothing at or beyond x + n is written.  n == 0 is a no-op; n < 0, a null pointer with n > 0, and a strength outside [0, 1] or NaN
+ *  are refused before any GPU work.  Does not synchronise. */
+int mg_latent_carry(float* x, const float* prev, int64_t n, float strength, void* stream);
+int mg_model_seq_reset(mg_model* m);
+int mg_model_predict_next(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                          const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
+                          float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
+                          void* stream, float strength);
+
 /* The same for an intrinsic-image model (appearance, lighting): __call__ of the reference's MarigoldIIDPipeline with fill_outputs
  * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[10] = n_targets
  * >= 1, 3 n_targets prediction channels, a DDIM image: the pipeline refuses the LCM scheduler and so does this call); a depth or

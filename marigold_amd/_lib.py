@@ -214,6 +214,7 @@ EXPORTS = [
     "mg_lpips_workspace_bytes", "mg_eval_iid_lpips",
     "mg_model_num_configs", "mg_model_config_info", "mg_model_find_config", "mg_model_select", "mg_processed_size",
     "mg_model_shared_bytes", "mg_model_replica",
+    "mg_latent_carry", "mg_model_seq_reset", "mg_model_predict_next",
 ]
 
 
@@ -339,6 +340,9 @@ def load(f16=False):
                                                                                        ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_model_predict_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 5 + \
         [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgPredictOpts), ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
+    lib.mg_latent_carry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]
+    lib.mg_model_seq_reset.argtypes = [ctypes.c_void_p]
+    lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]
     lib.mg_model_config_info.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mg_model_find_config.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5

@@ -57,6 +57,12 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
     p.add_argument("--images_per_program", type=int, default=1,
                    help="Consecutive images of one processed size that share one denoising program (their members batched); "
                         "1 = one image per program.")
+    p.add_argument("--sequence", action="store_true",
+                   help="The sorted input files are consecutive frames of one sequence: every frame starts from the denoised latent of the "
+                        "frame before (map_video). With --seed s, frame k draws its noise from the engine's own generator seeded s + k, "
+                        "which a C host reproduces (mg_model_predict_next).")
+    p.add_argument("--carry_strength", type=float, default=0.1,
+                   help="--sequence: the weight of the previous frame's latent in a frame's initial latents; the noise gets 1 minus it.")
     return p
 
 
@@ -178,7 +184,19 @@ def main(kind: str, argv=None, pipeline=None) -> int:
 
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
-    if hasattr(pipeline, "map_images"):
+    if args.sequence:
+        # consecutive frames: map_video in place of map_images; frame k's noise is NativeNoise(seed + k)
+        if args.images_per_program > 1:
+            raise ValueError("--sequence runs one frame per program: --images_per_program must be 1")
+        if not hasattr(pipeline, "map_video"):
+            raise RuntimeError("--sequence needs a pipeline with map_video")
+        from .noise import NativeNoise
+        seeds = (None if args.seed is None else NativeNoise(args.seed + k) for k in range(len(files)))
+        outs = pipeline.map_video((Image.open(f) for f in files), strength=args.carry_strength, in_flight=args.maps_in_flight or None,
+                                  generators=seeds, **kw)
+        for rgb_path, out in zip(files, outs):
+            save_prediction(kind, dirs, rgb_path, out)
+    elif hasattr(pipeline, "map_images"):
         # the engine's multi-image form: up to --maps_in_flight images on the GPU at a time, outputs in input order
         if args.images_per_program > 1:
             kw["images_per_program"] = args.images_per_program

@@ -146,6 +146,11 @@ struct mg_model {
   uint64_t predict_tmp_bytes = 0;
   void* out_tmp = nullptr;           // the one-call predictions' output temporaries (see out_tmp_layout), grown on demand
   uint64_t out_tmp_bytes = 0;
+  void* seq_latent = nullptr;        // image sequences: the denoised latent of the frame before (the bytes of the x slot), allocated at the
+                                     // first mg_model_predict_next
+  uint64_t seq_bytes = 0;
+  bool seq_carried = false;          // seq_latent holds a frame of the selected configuration
+  const float* seq_call = nullptr;   // the strength, while mg_model_predict_next runs its prediction on this handle
 };
 
 namespace {
@@ -467,6 +472,7 @@ void mg_model_destroy(mg_model* m) {
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
   if (m->out_tmp) (void)hipFree(m->out_tmp);
+  if (m->seq_latent) (void)hipFree(m->seq_latent);
   delete m;   // (the shared weights go with the last handle over them)
 }
 
@@ -508,6 +514,7 @@ int mg_model_select(mg_model* m, int index) {
   MG_REQUIRE(m, "mg_model_select: null model");
   MG_REQUIRE(index >= 0 && index < (int)m->configs.size(), "mg_model_select: configuration %d of %d", index, (int)m->configs.size());
   m->sel = index;
+  m->seq_carried = false;   // a sequence does not outlive its configuration
   return 0;
 }
 
@@ -524,7 +531,7 @@ int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes + m->seq_bytes) : 0; }
 
 long long mg_model_shared_bytes(const mg_model* m) { return m ? (long long)m->plan->shared_bytes : 0; }
 
@@ -755,6 +762,9 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
   // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
   for (int i = 0; i < K; ++i)
     if (int rc = mg_randn(seeds[i < n ? i : n - 1], 0, 0, (int64_t)(x_rows / 4), xs->ptr + i * x_rows, 0, stream)) return rc;
+  // (mg_model_predict_next, K = 1) the frame before, member by member, into the initial latents
+  if (m->seq_call && m->seq_carried)
+    if (int rc = mg_latent_carry((float*)xs->ptr, (const float*)m->seq_latent, (int64_t)(xs->nbytes / 4), *m->seq_call, stream)) return rc;
   for (int k = 0; k < n_noise; ++k) {
     char nm[24];
     snprintf(nm, sizeof(nm), "noise%d", k);
@@ -765,6 +775,10 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
   }
   // 4. denoise, 5. decode (an intrinsic-image model: the latent [B, 4 n, h, w] is the decoder's batch [B n, 4, h, w], the same bytes)
   if (int rc = mg_program_run(m->cur().den.prog, stream)) return rc;
+  if (m->seq_call) {   // this frame's denoised latent, for the next one
+    if (int rc = copy_dd(m->seq_latent, xs->ptr, xs->nbytes, s)) return rc;
+    m->seq_carried = true;
+  }
   if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
   if (int rc = mg_program_run(m->cur().dec.prog, stream)) return rc;
   *preds = (const float*)d_out->ptr;
@@ -928,6 +942,33 @@ extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, in
   MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_out");
   return predict_out_many(m, "mg_model_predict_out", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, out_opts_or_null, pred_out,
                           unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
+}
+
+extern "C" int mg_model_seq_reset(mg_model* m) {
+  MG_REQUIRE(m, "mg_model_seq_reset: null model");
+  m->seq_carried = false;
+  return 0;
+}
+
+extern "C" int mg_model_predict_next(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                     const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
+                                     float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
+                                     void* stream, float strength) {
+  MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_next: null argument (the model, the picture and pred_out are required)");
+  MG_REQUIRE(!m->host_only, "mg_model_predict_next: a host-only model cannot predict (load it with device >= 0)");
+  MG_REQUIRE(m->cur().K == 1, "mg_model_predict_next: this configuration runs %d pictures per call: a sequence runs one frame per call (K = 1)", m->cur().K);
+  MG_REQUIRE(strength >= 0.f && strength <= 1.f, "mg_model_predict_next: strength %g is not in [0, 1]", (double)strength);
+  const uint32_t* cfg = m->cur().cfg;
+  MG_REQUIRE((int)cfg[7] != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict_next: an intrinsic-image model goes through mg_model_predict_iid");
+  const uint64_t need = m->cur().den.slot("x")->nbytes;
+  if (m->seq_bytes < need) m->seq_carried = false;
+  if (int rc = grow_tmp(&m->seq_latent, &m->seq_bytes, need)) return rc;
+  m->seq_call = &strength;
+  const int rc = predict_out_many(m, "mg_model_predict_next", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, out_opts_or_null, pred_out,
+                                  unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
+  m->seq_call = nullptr;
+  if (rc) m->seq_carried = false;   // a frame that failed carries nothing on
+  return rc;
 }
 
 extern "C" int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,

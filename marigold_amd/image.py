@@ -491,7 +491,18 @@ class ModelImage:
                                                O.current_stream_handle()), "mg_model_predict_iid", self._lib)
         return pred, unc, pics
 
-    def predict_out(self, u8, seed, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False, opts=None, mode=0, reciprocal=None):
+    def predict_next(self, u8, seed, strength=0.1, **kw):
+        """``mg_model_predict_next``: ``predict_out`` (its arguments, its results) for the next frame of a sequence - the frame starts
+        from ``(1 - strength) noise + strength latent``, the denoised latent of the frame this handle predicted before; the first
+        frame after the load, ``replica()``, ``select()`` or ``seq_reset()`` carries nothing and is ``predict_out`` bit for bit."""
+        return self.predict_out(u8, seed, _next=float(strength), **kw)
+
+    def seq_reset(self):
+        """``mg_model_seq_reset``: forget the carried latent; the next ``predict_next`` starts a new sequence."""
+        L.check(self._lib.mg_model_seq_reset(self.handle), "mg_model_seq_reset", self._lib)
+
+    def predict_out(self, u8, seed, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False, opts=None, mode=0, reciprocal=None,
+                    _next=None):
         """``mg_model_predict_out`` on the uint8 CUDA picture ``u8`` [Hin, Win, 3]: the pipelines' output with ``match_input_res`` ->
         (pred fp32 [C, out_h, out_w] clipped, unc fp32 [Hout, Wout] | None for a single member, u16 uint16 [out_h, out_w] | None unless
         ``u16``, picture uint8 [out_h, out_w, 3] | None unless ``picture``, info = the four numbers of ``mg_ensemble_depth``).
@@ -516,10 +527,13 @@ class ModelImage:
         pic = torch.empty(oh, ow, 3, device=dev, dtype=torch.uint8) if picture else None
         info = (ctypes.c_double * 4)()
         ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        L.check(self._lib.mg_model_predict_out(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
-                                               int(seed) & ((1 << 64) - 1), None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
-                                               pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle()),
-                "mg_model_predict_out", self._lib)
+        # (_next: the strength - the call is mg_model_predict_next, the same arguments and the strength behind them)
+        name = "mg_model_predict_out" if _next is None else "mg_model_predict_next"
+        L.check(getattr(self._lib, name)(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
+                                         int(seed) & ((1 << 64) - 1), None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
+                                         pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle(),
+                                         *(() if _next is None else (_next,))),
+                name, self._lib)
         return pred, unc, d16, pic, list(info)
 
     def predict_many(self, u8s, seeds, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False, opts=None, mode=0, reciprocal=None):

@@ -11,7 +11,9 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
   sharded over ranks and collected with ONE gather (RCCL over xGMI) before aggregation;
 * ``init_latents`` (extension) lets callers supply the initial noise for parity runs;
 * ``generator=NativeNoise(seed)`` (extension) draws the noise with the library's own generator (noise.py), as a C host does;
-* ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program.
+* ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program;
+* ``sequence=SequenceState()`` / ``map_video`` (extension) carry each frame's denoised latent into the next frame's initial noise
+  (DESIGN.md 6c).
 """
 import contextlib
 import copy
@@ -27,6 +29,7 @@ from PIL import Image
 
 from . import _lib as L
 from . import dist as mdist
+from . import ops as O
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .lanes import Turnstile as _Turnstile, run_lanes
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
@@ -56,6 +59,85 @@ class MarigoldNormalsOutput:
     uncertainty: Union[None, np.ndarray]
 
 
+class SequenceState:
+    """What a sequence of frames carries from one call to the next (``pipe(frame, sequence=state)``, ``map_video``): the denoised
+    latent of the frame before.  Frame k starts from ``(1 - strength) * noise + strength * latent`` (``mg_latent_carry``); the first
+    frame of a state starts from the noise alone, bit for bit the call without a state.
+
+    ``latent``: None, or the fp32 device tensor [E, C, h, w] of the last frame's members - the state's own memory, one of the two
+    buffers it writes in turn: valid until the frame after next is predicted (clone it to keep it).  ``frames``: how many frames
+    have been predicted.  ``reset()`` starts a new sequence.
+
+    Buffer lifetime: frame k reads buffer (k - 1) % 2 and writes buffer k % 2 on the stream it runs on, and records an event
+    behind its write; frame k + 1, on whichever stream, makes its stream wait for that event first.  Every access is therefore
+    ordered by the chain of events, and the buffers are never returned to torch's allocator while the state is in use."""
+
+    def __init__(self, strength=0.1):
+        strength = float(strength)
+        if not 0.0 <= strength <= 1.0:
+            raise ValueError(f"SequenceState: strength must be in [0, 1] (got {strength})")
+        self.strength = strength
+        self.latent = None
+        self.frames = 0
+        self._sig = None             # (pipeline kind, shape of the latent, device): what the next frame must match
+        self._ring = [None, None]
+        self._event = None           # recorded behind the last frame's copy into its buffer (kept over a reset: the buffers are reused)
+
+    def reset(self):
+        self.latent, self.frames, self._sig = None, 0, None
+
+    def _check(self, sig):
+        if self._sig is not None and self._sig != sig:
+            raise ValueError(f"sequence: the state carries a {self._sig[0]} latent of shape {tuple(self._sig[1])} on {self._sig[2]}, this "
+                             f"frame needs a {sig[0]} latent of shape {tuple(sig[1])} on {sig[2]} (reset() starts a new sequence)")
+
+
+class _FrameCarry:
+    """One frame's turn on a ``SequenceState``, around the denoising programs of its members (``single_infer``): ``blend`` before a
+    program runs, ``keep`` after it.  The first ``blend`` takes the frame's turn (``map_video`` lanes) and makes the stream wait for
+    the event of the frame before; the last ``keep`` records this frame's event and hands the turn on.  Nothing here waits on the
+    host for the GPU."""
+
+    def __init__(self, state, sig, lib, turn=None):
+        self.state, self.sig, self.lib, self.turn = state, sig, lib, turn
+        self.new = None
+
+    def _enter(self):
+        st = self.state
+        if self.turn is not None:
+            self.turn[0].wait(self.turn[1])
+        st._check(self.sig)
+        stream = torch.cuda.current_stream(self.sig[2])
+        if st._event is not None:
+            stream.wait_event(st._event)
+        slot = st.frames % 2
+        buf = st._ring[slot]
+        if buf is None or tuple(buf.shape) != tuple(self.sig[1]) or buf.device != self.sig[2]:
+            buf = st._ring[slot] = torch.empty(tuple(self.sig[1]), dtype=torch.float32, device=self.sig[2])
+        buf.record_stream(stream)   # (should the state be dropped with work of this stream still queued)
+        self.new = buf
+
+    def blend(self, x, rows):
+        if self.new is None:
+            self._enter()
+        prev = self.state.latent
+        if prev is not None:
+            prev.record_stream(torch.cuda.current_stream(self.sig[2]))
+            part = prev[rows]
+            L.check(self.lib.mg_latent_carry(x.data_ptr(), part.data_ptr(), x.numel(), self.state.strength, O.current_stream_handle()),
+                    "mg_latent_carry", self.lib)
+
+    def keep(self, x, rows, last):
+        self.new[rows].copy_(x)
+        if last:
+            st = self.state
+            st.latent, st._sig, st.frames = self.new, self.sig, st.frames + 1
+            st._event = torch.cuda.Event()
+            st._event.record(torch.cuda.current_stream(self.sig[2]))
+            if self.turn is not None:
+                self.turn[0].done(self.turn[1])
+
+
 @contextlib.contextmanager
 def _on_stream(device, stream, caller):
     """``with`` this in a lane's thread: its work goes to the lane's HIP stream, behind what the caller has queued on its own."""
@@ -72,6 +154,7 @@ class _MarigoldPipelineBase:
     _target_latent_channels = 4    # latent channels the UNet predicts (4 per modality)
     _pred_channels = 1             # channels of one decoded prediction
     _gather_turn = None            # (turnstile, map index): set only on the per-call view a lane of map_images runs on
+    _sequence_turn = None          # (turnstile, frame index): likewise, on the view a lane of map_video runs on
 
     def __init__(self, unet: UNet2DConditionModelHIP, vae: AutoencoderKLHIP,
                  scheduler: Union[DDIMScheduler, LCMScheduler], text_encoder=None, tokenizer=None,
@@ -301,6 +384,100 @@ class _MarigoldPipelineBase:
         finally:
             leave()
 
+    # ---- image sequences ---------------------------------------------------------------------
+    # Frame k of a sequence starts from 0.9 noise + 0.1 x (denoised latent of frame k - 1) - the recipe Marigold's authors give for
+    # frame-by-frame video - so consecutive maps stop flickering with the noise draw.  Only the DENOISE stage of frame k depends on
+    # frame k - 1: preprocessing and the VAE encode run ahead of it, decode / ensemble / output stage beside the next frame's
+    # denoise.
+    def _frame_carry(self, sequence, init_latents, input_image, processing_res, ensemble_size):
+        """``__call__``'s check of ``sequence=``, before anything is launched -> the frame's ``_FrameCarry`` | None."""
+        if sequence is None:
+            return None
+        if not isinstance(sequence, SequenceState):
+            raise TypeError(f"sequence must be a SequenceState (got {type(sequence).__name__})")
+        if init_latents is not None:
+            raise ValueError("sequence and init_latents cannot be combined: the sequence decides the initial latents")
+        if self._sharded():
+            raise ValueError("sequence is not available on a member-parallel pipeline")
+        h, w = self._latent_hw(self._processed_size(input_image, processing_res))
+        sig = (self._kind, (int(ensemble_size), self._target_latent_channels, h, w), self.device)
+        sequence._check(sig)
+        return _FrameCarry(sequence, sig, L.load(bool(getattr(self.unet, "f16", False))), self._sequence_turn)
+
+    def frames_in_flight_for(self, ensemble_size: int = 1) -> int:
+        """The lane count ``map_video`` uses when the caller names none: ``map_images``' - at 768 x 768, E = 1, three lanes beat one by
+        more than the spread of alternated runs at T = 1, 4 and 10 (13.6 against 17.5, 32.3 against 35.2, 68.0 against 70.8 ms per frame;
+        tools/sequence_bench.py, profiles/sequence_768.log)."""
+        return self.maps_in_flight_for(ensemble_size)
+
+    def map_video(self, frames, strength: float = 0.1, in_flight: Optional[int] = None, generators=None, **call_kwargs):
+        """``state = SequenceState(strength); (pipe(frame, sequence=state, generator=g, **call_kwargs) for frame, g in zip(frames,
+        generators))`` - consecutive frames of one sequence, each started from the frame before (``SequenceState``) - with up to
+        ``in_flight`` frames on the GPU at a time (default ``frames_in_flight_for(ensemble_size)``).  A generator with ``map_images``'
+        contract: outputs in input order, ``frames`` consumed lazily, one entry of ``generators`` per frame, a shared ``generator=``
+        refused when ``in_flight > 1``.  Every output is, bit for bit, what the serial loop returns: with several lanes only the
+        denoise stage takes turns (a ``Turnstile``, frame by frame; its GPU work is ordered by events, nothing waits on the host),
+        while a frame's preprocessing and encode run ahead of its turn and its decode, ensemble and output stage behind it.
+        Refused: ``images_per_program``, ``init_latents``, member-parallel pipelines, a frame whose processed size differs from the
+        first frame's."""
+        for name in ("images_per_program", "init_latents", "sequence"):
+            if call_kwargs.get(name) is not None:
+                raise ValueError(f"map_video: {name} cannot be combined with a sequence of frames")
+            call_kwargs.pop(name, None)
+        if self._sharded():
+            raise ValueError("map_video: a sequence is not available on a member-parallel pipeline")
+        state = SequenceState(strength)
+        n = self.frames_in_flight_for(call_kwargs.get("ensemble_size", 1)) if in_flight is None else int(in_flight)
+        if n < 1:
+            raise ValueError(f"in_flight must be >= 1 (got {in_flight})")
+        if generators is not None and hasattr(frames, "__len__") and hasattr(generators, "__len__") and len(frames) != len(generators):
+            raise ValueError(f"{len(generators)} generators for {len(frames)} frames")
+        if hasattr(frames, "__len__"):
+            n = min(n, max(1, len(frames)))
+        if self.device.type != "cuda":
+            n = 1
+        if n > 1 and call_kwargs.get("generator") is not None:
+            raise ValueError("map_video: pass `generators` (one per frame) instead of a shared `generator` when in_flight > 1")
+        return self._map_video(iter(frames), None if generators is None else iter(generators), n, state, call_kwargs)
+
+    def _map_video(self, frames, generators, n, state, call_kwargs):
+        def items():
+            """[(frame, generator)], one frame each; the two iterables advance together"""
+            size = None
+            for k, image in enumerate(frames):
+                g = None if generators is None else next(generators, StopIteration)
+                if g is StopIteration:
+                    raise ValueError("map_video: fewer generators than frames")
+                image_size = self._processed_size(image, call_kwargs.get("processing_res"))
+                if size is not None and image_size != size:
+                    raise ValueError(f"map_video: frame {k} has the processed size {image_size}, the sequence began with {size}")
+                size = image_size
+                yield [(image, g)]
+
+        take = functools.partial(next, enumerate(items()), None)
+        views, contexts, leave, turnstile = [self], [contextlib.nullcontext()], lambda: None, None   # one lane: inline, as map_images
+        if n > 1:
+            if self.empty_text_embed is None:
+                self.encode_empty_text()
+            lanes = self._lane_resources(n)
+            views = [self._view(e.unet, e.vae) for e, _ in lanes]
+            contexts, leave = self._lane_contexts([stream for _, stream in lanes])
+            turnstile = _Turnstile()   # the denoise stages, frame by frame
+
+        def run(lane, group, k):
+            pipe, kw = views[lane], dict(call_kwargs)
+            image, g = group[0]
+            if generators is not None:
+                kw["generator"] = g
+            if turnstile is not None:
+                pipe._sequence_turn = (turnstile, k)   # on this call's view of the lane
+            return [pipe(image, sequence=state, **kw)]
+
+        try:
+            yield from run_lanes(contexts, take, run, turnstile)
+        finally:
+            leave()
+
     # ---- reference methods -------------------------------------------------------------------
     def _check_inference_step(self, n_step: int) -> None:
         assert n_step >= 1
@@ -343,10 +520,11 @@ class _MarigoldPipelineBase:
     def single_infer(self, rgb_in: torch.Tensor, num_inference_steps: int,
                      generator: Union[torch.Generator, None], show_pbar: bool = False,
                      init_latents: Optional[torch.Tensor] = None,
-                     step_noises: Optional[torch.Tensor] = None, rgb_members: Optional[int] = None) -> torch.Tensor:
+                     step_noises: Optional[torch.Tensor] = None, rgb_members: Optional[int] = None, carry=None) -> torch.Tensor:
         """One batched prediction (reference :396-477).  rgb_in [B,3,h,w] in [-1,1]; identical
         (expanded) rows are encoded once.  ``rgb_members`` = m: rgb_in holds B distinct images and the batch is their
-        B x m members, image-major (one encode program of B images, one denoising program of B m members)."""
+        B x m members, image-major (one encode program of B images, one denoising program of B m members).
+        ``carry`` = (a ``_FrameCarry``, the rows of the sequence's latent these B members are, whether this is the frame's last batch)."""
         device = self.device
         B = rgb_in.shape[0] if rgb_members is None else rgb_in.shape[0] * rgb_members
         shared = rgb_members is None and (B == 1 or rgb_in.stride(0) == 0)
@@ -369,12 +547,17 @@ class _MarigoldPipelineBase:
                 nz.copy_(step_noises[k])
             else:
                 nz.copy_(self._randn(nz.shape, generator))
+        if carry is not None:
+            carry[0].blend(prog.x, carry[1])
         prog.run()
+        if carry is not None:
+            carry[0].keep(prog.x, carry[1], carry[2])
         return self._decode(prog.x)
 
     def _predict_members(self, rgb_norm, ensemble_size, denoising_steps, batch_size, generator,
-                         init_latents):
-        """All E members of one image -> [E,C,h,w] (on every rank when member-parallel)."""
+                         init_latents, carry=None):
+        """All E members of one image -> [E,C,h,w] (on every rank when member-parallel).  ``carry``: the frame's ``_FrameCarry``
+        (``sequence=``; never with ``init_latents`` or member parallelism)."""
         _bs = batch_size if batch_size > 0 else find_batch_size(
             ensemble_size=ensemble_size, input_res=max(rgb_norm.shape[1:]), dtype=self.dtype)
         E = ensemble_size
@@ -403,7 +586,8 @@ class _MarigoldPipelineBase:
             lat = None if init_latents is None else init_latents[idx]
             rgb = rgb_norm.expand(len(idx), -1, -1, -1)
             nzs = None if step_noises_all is None else [nz[idx] for nz in step_noises_all]
-            preds.append(self.single_infer(rgb, denoising_steps, generator, False, lat, step_noises=nzs))
+            rows = None if carry is None else (carry, slice(idx[0], idx[-1] + 1), i + _bs >= len(members))
+            preds.append(self.single_infer(rgb, denoising_steps, generator, False, lat, step_noises=nzs, carry=rows))
         local = torch.cat(preds, dim=0) if preds else None
         if self._sharded():
             C = self._pred_channels
@@ -584,13 +768,15 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, color_map: str = "Spectral",
                  show_progress_bar: bool = True, ensemble_kwargs: Dict = None,
-                 init_latents: Optional[torch.Tensor] = None) -> MarigoldDepthOutput:
+                 init_latents: Optional[torch.Tensor] = None,
+                 sequence: Optional[SequenceState] = None) -> MarigoldDepthOutput:
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             denoising_steps, ensemble_size, processing_res, resample_method)
+        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
-                                             generator, init_latents)
+                                             generator, init_latents, carry)
         return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
                             color_map=color_map)
 
@@ -660,13 +846,15 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None,
-                 init_latents: Optional[torch.Tensor] = None) -> MarigoldNormalsOutput:
+                 init_latents: Optional[torch.Tensor] = None,
+                 sequence: Optional[SequenceState] = None) -> MarigoldNormalsOutput:
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             denoising_steps, ensemble_size, processing_res, resample_method)
+        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
-                                             generator, init_latents)
+                                             generator, init_latents, carry)
         return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
 
     def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
@@ -827,12 +1015,14 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
                  ensemble_size: int = 1, processing_res: Optional[int] = None, match_input_res: bool = True,
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
-                 ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None) -> MarigoldIIDOutput:
+                 ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None,
+                 sequence: Optional[SequenceState] = None) -> MarigoldIIDOutput:
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             denoising_steps, ensemble_size, processing_res, resample_method)
+        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
         rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size, generator,
-                                             init_latents)
+                                             init_latents, carry)
         return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
 
     def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
