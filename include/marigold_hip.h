@@ -1135,6 +1135,55 @@ long long mg_lpips_workspace_bytes(int H, int W);
 int mg_eval_iid_lpips(const mg_lpips_net* net, const float* pred, const float* gt, const uint8_t* mask_or_null, int H, int W,
                       int up_to_scale, int gamma_mode, double* out8, void* eval_ws, void* act_ws, long long act_ws_bytes, void* stream);
 
+/* The tiny autoencoder (diffusers' AutoencoderTiny with the TAESD layout: csrc/tinyvae.hip, DESIGN.md "Tiny VAE") as plain calls - no
+ * op kind.  Every convolution is 3 x 3 / pad 1 and 64 channels wide; activations between layers are NHWC in the build's 16-bit operand
+ * type (one pixel = one 128-byte line), sums are fp32.
+ *  struct mg_tiny_vae: DEVICE pointers, in the layout the kernels read.  For either half (enc_ / dec_):
+ *    in_w   fp32 [9 * Cin][64], row (ky * 3 + kx) * Cin + ci (Cin 3 / 4); values already rounded to the operand type
+ *    in_b   fp32 [64]
+ *    w[l]   operand type [9][64 out][64 in], tap ky * 3 + kx (torch's [out][in][ky][kx] permuted to [ky][kx][out][in]), the
+ *           MG_TINY_VAE_LAYERS 64 -> 64 layers in execution order: encoder = Block, then three times (stride-2 conv, three Blocks);
+ *           decoder = three times (three Blocks, conv on the nearest x2 input), then a Block; a Block is three layers
+ *    b[l]   fp32 [64]; NULL (and ignored) for the bias-free layers: encoder 3, 13, 23, decoder 9, 19, 29
+ *    out_w  fp32 [9][64 in][4], columns >= Cout (4 / 3) zero; values already rounded to the operand type
+ *    out_b  fp32 [4]
+ *    All 16-byte aligned.  A call reads only its own half; the other may be NULL.
+ *  mg_tiny_vae_workspace_bytes(which, B, H, W): which 0 = encode (H, W: the image), 1 = decode (H, W: the latent); -1 with
+ *    mg_last_error for a refused size (B, H, W < 1, more than 2^26 full-size pixels).
+ *  mg_tiny_vae_encode: rgb fp32 [B][3][H][W] in [-1, 1] -> (x + 1) / 2 -> encoder -> latent fp32 [B][4][h][w], the SCALED latent
+ *    (scaling factor 1), h = ceil(ceil(ceil(H / 2) / 2) / 2).
+ *  mg_tiny_vae_decode: latent fp32 [B][4][h][w] -> 3 tanh(z / 3) -> decoder -> y 2 - 1 -> post (MG_POST_NONE, _DEPTH, _NORMALS, _UNIT with
+ *    the semantics of MG_OP_POST_NCHW, NaN rules included) -> out fp32 [B][3 or 1 (DEPTH)][8 h][8 w].
+ *  mg_tiny_conv3x3: the single 64 -> 64 layer.  x [B][H][W][64] -> out [B][Ho][Wo][64]: stride 1: Ho = H; stride 2: Ho = (H - 1) / 2 + 1;
+ *    up2 (stride 1 only): the layer reads the nearest x2 of x (pixel (y >> 1, x >> 1)) and Ho = 2 H.  Epilogue in this order: + bias,
+ *    + residual (operand type, at the output's pixel), ReLU (keeps NaN), one rounding to the operand type (overflow -> inf).  out may
+ *    not alias x or the residual.
+ *  ws: 16-byte aligned, owned by the call until the stream has passed it.  Every argument is checked before the first device call.  No
+ *  split-K and no atomics: the same bits on every call, and a member's result does not depend on the batch it runs in.  None
+ *  synchronises. */
+#define MG_TINY_VAE_LAYERS 33
+typedef struct mg_tiny_vae {
+  const float* enc_in_w;
+  const float* enc_in_b;
+  const void* enc_w[MG_TINY_VAE_LAYERS];
+  const float* enc_b[MG_TINY_VAE_LAYERS];
+  const float* enc_out_w;
+  const float* enc_out_b;
+  const float* dec_in_w;
+  const float* dec_in_b;
+  const void* dec_w[MG_TINY_VAE_LAYERS];
+  const float* dec_b[MG_TINY_VAE_LAYERS];
+  const float* dec_out_w;
+  const float* dec_out_b;
+} mg_tiny_vae;
+long long mg_tiny_vae_workspace_bytes(int which, int B, int H, int W);
+int mg_tiny_vae_encode(const mg_tiny_vae* net, const float* rgb, float* latent, int B, int H, int W, void* ws, long long ws_bytes,
+                       void* stream);
+int mg_tiny_vae_decode(const mg_tiny_vae* net, const float* latent, float* out, int B, int h, int w, int post, void* ws,
+                       long long ws_bytes, void* stream);
+int mg_tiny_conv3x3(const void* x, const void* w, const float* bias_or_null, const void* residual_or_null, void* out, int B, int H, int W,
+                    int stride, int up2, int relu, void* stream);
+
 /* The device I/O boundary on raw pointers (csrc/resize.hip): MG_OP_RGB_PREP and MG_OP_NORMALS_VIS as calls; neither synchronises.
  *  mg_rgb_prepare: src uint8 [Hin][Win][3] (hwc != 0) or [3][Hin][Win] -> dst [3][Hout][Wout], fp32 or (out16 != 0) the build's 16-bit
  *  operand type; mode 0 bilinear / 1 bicubic / 2 nearest-exact when the sizes differ; reciprocal: see MG_RGB_PREP_I_RECIPROCAL;

@@ -11,8 +11,8 @@ def build_synthetic_pipeline(kind="depth", unet_cfg=None, vae_cfg=None, schedule
     """A pipeline on seeded synthetic weights in the real architecture (no checkpoints exist in
     this environment - BASELINE.md §4)."""
     from . import synthetic as syn
-    from .arch import UNetConfig, VAEConfig
-    from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
+    from .arch import TinyVAEConfig, UNetConfig, VAEConfig
+    from .modules import AutoencoderKLHIP, AutoencoderTinyHIP, UNet2DConditionModelHIP
     from .schedulers import DDIMScheduler
     if kind == "iid":   # appearance model: albedo + material
         kw.setdefault("target_properties", {"target_names": ["albedo", "material"],
@@ -25,7 +25,10 @@ def build_synthetic_pipeline(kind="depth", unet_cfg=None, vae_cfg=None, schedule
     import torch
     compute_dtype = compute_dtype or torch.bfloat16   # torch.float16: the fp16-operand build of the engine
     unet = UNet2DConditionModelHIP(syn.synthetic_unet_state_dict(unet_cfg, seed), unet_cfg, compute_dtype=compute_dtype)
-    vae = AutoencoderKLHIP(syn.synthetic_vae_state_dict(vae_cfg, seed), vae_cfg, compute_dtype=compute_dtype)
+    if isinstance(vae_cfg, TinyVAEConfig):   # the tiny autoencoder in place of the SD AutoencoderKL
+        vae = AutoencoderTinyHIP(syn.synthetic_tiny_vae_state_dict(vae_cfg, seed), vae_cfg, compute_dtype=compute_dtype)
+    else:
+        vae = AutoencoderKLHIP(syn.synthetic_vae_state_dict(vae_cfg, seed), vae_cfg, compute_dtype=compute_dtype)
     emb = syn.synthetic_text_embedding(unet_cfg.cross_attention_dim)
     scheduler = scheduler or DDIMScheduler()
     cls = {"depth": MarigoldDepthPipeline, "normals": MarigoldNormalsPipeline, "iid": MarigoldIIDPipeline}[kind]

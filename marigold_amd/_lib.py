@@ -215,6 +215,7 @@ EXPORTS = [
     "mg_model_num_configs", "mg_model_config_info", "mg_model_find_config", "mg_model_select", "mg_processed_size",
     "mg_model_shared_bytes", "mg_model_replica",
     "mg_latent_carry", "mg_model_seq_reset", "mg_model_predict_next",
+    "mg_tiny_vae_workspace_bytes", "mg_tiny_vae_encode", "mg_tiny_vae_decode", "mg_tiny_conv3x3",
 ]
 
 
@@ -243,6 +244,16 @@ class MgOutputOpts(ctypes.Structure):
 class MgLpipsNet(ctypes.Structure):
     """mg_lpips_net: DEVICE addresses of the fp32 weights of the five layers, packed as the header documents."""
     _fields_ = [("conv_w", ctypes.c_void_p * 5), ("conv_b", ctypes.c_void_p * 5), ("lin_w", ctypes.c_void_p * 5)]
+
+
+TINY_VAE_LAYERS = 33   # MG_TINY_VAE_LAYERS: the 64 -> 64 layers of either half
+
+
+class MgTinyVae(ctypes.Structure):
+    """mg_tiny_vae: DEVICE addresses of the packed weights and fp32 biases of both halves, in the layout the header documents."""
+    _fields_ = [(f"{half}_{name}", ctype) for half in ("enc", "dec") for name, ctype in (
+        ("in_w", ctypes.c_void_p), ("in_b", ctypes.c_void_p), ("w", ctypes.c_void_p * TINY_VAE_LAYERS),
+        ("b", ctypes.c_void_p * TINY_VAE_LAYERS), ("out_w", ctypes.c_void_p), ("out_b", ctypes.c_void_p))]
 
 
 class MgOp(ctypes.Structure):
@@ -325,6 +336,13 @@ def load(f16=False):
     lib.mg_lpips_workspace_bytes.restype = ctypes.c_longlong
     lib.mg_eval_iid_lpips.argtypes = [ctypes.POINTER(MgLpipsNet)] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3 + \
         [ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_tiny_vae_workspace_bytes.argtypes = [ctypes.c_int] * 4
+    lib.mg_tiny_vae_workspace_bytes.restype = ctypes.c_longlong
+    lib.mg_tiny_vae_encode.argtypes = [ctypes.POINTER(MgTinyVae)] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + \
+        [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_tiny_vae_decode.argtypes = [ctypes.POINTER(MgTinyVae)] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + \
+        [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_tiny_conv3x3.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 6 + [ctypes.c_void_p]
     lib.mg_rgb_prepare.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2
     lib.mg_normals_visualize.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_randn.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]

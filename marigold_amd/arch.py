@@ -173,6 +173,69 @@ def vae_param_shapes(cfg: VAEConfig = VAEConfig()):
     return d
 
 
+@dataclass(frozen=True)
+class TinyVAEConfig:
+    """diffusers' AutoencoderTiny in the TAESD layout (DESIGN.md "Tiny VAE"): every convolution 3 x 3, every width 64, ReLU, no
+    normalisation, no attention; the latent is the scaled one (``scaling_factor`` 1)."""
+    latent_channels: int = 4
+    width: int = 64
+    num_encoder_blocks: Tuple[int, ...] = (1, 3, 3, 3)
+    num_decoder_blocks: Tuple[int, ...] = (3, 3, 3, 1)
+    latent_magnitude: float = 3.0
+    latent_shift: float = 0.5
+    scaling_factor: float = 1.0
+
+
+def _tiny_block(d, name, c):
+    for i in (0, 2, 4):
+        _conv(d, f"{name}.conv.{i}", c, c, 3)
+
+
+def tiny_vae_layers(cfg: TinyVAEConfig = TinyVAEConfig()):
+    """The two ``nn.Sequential`` lists as [(index, kind)], kind one of "conv_in", "block", "down" (stride-2 conv, no bias), "relu",
+    "up" (nearest x2), "conv" (no bias), "conv_out" - the structure ``tiny_vae_param_shapes`` names and every restatement walks."""
+    enc = [(0, "conv_in")]
+    i = 1
+    for level, n in enumerate(cfg.num_encoder_blocks):
+        if level:
+            enc.append((i, "down"))
+            i += 1
+        for _ in range(n):
+            enc.append((i, "block"))
+            i += 1
+    enc.append((i, "conv_out"))
+    dec = [(0, "conv_in"), (1, "relu")]
+    i = 2
+    last = len(cfg.num_decoder_blocks) - 1
+    for level, n in enumerate(cfg.num_decoder_blocks):
+        for _ in range(n):
+            dec.append((i, "block"))
+            i += 1
+        if level < last:
+            dec += [(i, "up"), (i + 1, "conv")]
+            i += 2
+    dec.append((i, "conv_out"))
+    return enc, dec
+
+
+def tiny_vae_param_shapes(cfg: TinyVAEConfig = TinyVAEConfig()):
+    d = OrderedDict()
+    c, L = cfg.width, cfg.latent_channels
+    enc, dec = tiny_vae_layers(cfg)
+    for half, layers, cin, cout in (("encoder", enc, 3, L), ("decoder", dec, L, 3)):
+        for i, kind in layers:
+            name = f"{half}.layers.{i}"
+            if kind == "conv_in":
+                _conv(d, name, c, cin, 3)
+            elif kind == "conv_out":
+                _conv(d, name, cout, c, 3)
+            elif kind == "block":
+                _tiny_block(d, name, c)
+            elif kind in ("down", "conv"):
+                d[f"{name}.weight"] = (c, c, 3, 3)
+    return d
+
+
 # Small configurations used by CPU tests / smoke (same topology, fewer channels).
 TINY_UNET = UNetConfig(block_out_channels=(64, 128, 128, 128), heads=(1, 2, 2, 2),
                        cross_attention_dim=64)

@@ -43,6 +43,9 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
     p.add_argument("--ensemble_size", type=int, default=1, help="Number of predictions to be ensembled.")
     p.add_argument("--half_precision", "--fp16", action="store_true",
                    help="Load the 16-bit weight variant of the checkpoint.")
+    p.add_argument("--tiny_vae", type=str, default=None, metavar="DIR",
+                   help="Folder of a diffusers AutoencoderTiny (e.g. a local copy of madebyollin/taesd): the pipeline encodes and decodes "
+                        "with it in place of the checkpoint's VAE.")
     p.add_argument("--output_processing_res", action="store_true",
                    help="Output at the processing resolution instead of resizing back to the input resolution.")
     p.add_argument("--resample_method", choices=["bilinear", "bicubic", "nearest"], default="bilinear")
@@ -127,6 +130,16 @@ def save_prediction(kind, dirs, rgb_path, out):
     return written
 
 
+def apply_tiny_vae(pipeline, folder, half_precision=False):
+    """``--tiny_vae DIR``: load the tiny autoencoder of ``folder`` with the pipeline's operand type and swap it in."""
+    import torch
+    from .checkpoint import load_tiny_vae
+    pipeline.set_vae(load_tiny_vae(folder, variant="fp16" if half_precision else None,
+                                   torch_dtype=torch.float16 if half_precision else torch.float32))
+    logging.info(f"VAE: the tiny autoencoder of `{folder}`")
+    return pipeline
+
+
 def main(kind: str, argv=None, pipeline=None) -> int:
     """``pipeline`` lets tests inject a ready pipeline object; otherwise the checkpoint is loaded."""
     import torch
@@ -157,6 +170,8 @@ def main(kind: str, argv=None, pipeline=None) -> int:
                                        torch_dtype=torch.float16 if args.half_precision else torch.float32)
         pipeline.enable_xformers_memory_efficient_attention()   # no-op: attention is always the fused kernel
         pipeline = pipeline.to("cuda")
+    if args.tiny_vae:
+        apply_tiny_vae(pipeline, args.tiny_vae, args.half_precision)
     if kind == "depth":
         logging.info(f"Loaded depth pipeline: scale_invariant={pipeline.scale_invariant}, "
                      f"shift_invariant={pipeline.shift_invariant}")

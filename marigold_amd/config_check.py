@@ -7,7 +7,7 @@ AutoencoderKL); a field it cannot honour must stop the load, never be ignored, o
 wrong numbers.  Every key of the published configs is listed here with the values the engine implements
 (SURVEY.md App. C.1 / C.5 / C.6); unknown keys are errors too.
 """
-from .arch import UNetConfig, VAEConfig
+from .arch import TinyVAEConfig, UNetConfig, VAEConfig
 
 _ANY = object()          # informational: does not change the arithmetic of the inference path
 _INFO_KEYS = ("_class_name", "_diffusers_version", "_name_or_path", "_use_default_values")
@@ -72,6 +72,18 @@ _VAE_RULES = {
 }
 
 
+# diffusers' AutoencoderTiny with the TAESD layout (madebyollin/taesd for SD 1.x / 2.x latents): one architecture, every field pinned
+_TINY_VAE_RULES = {
+    "in_channels": (3,), "out_channels": (3,), "latent_channels": (4,),
+    "encoder_block_out_channels": ([64, 64, 64, 64],), "decoder_block_out_channels": ([64, 64, 64, 64],),
+    "num_encoder_blocks": ([1, 3, 3, 3],), "num_decoder_blocks": ([3, 3, 3, 1],),
+    "act_fn": ("relu",), "upsampling_scaling_factor": (2,),
+    "latent_magnitude": (3, 3.0), "latent_shift": (0.5,), "scaling_factor": (1, 1.0),
+    "force_upcast": (False,),
+    "shift_factor": (None,),
+}
+
+
 def _check(cfg, rules, what):
     for k, v in cfg.items():
         if k in _INFO_KEYS:
@@ -105,6 +117,22 @@ def vae_config_from_json(cfg: dict) -> VAEConfig:
     return VAEConfig(block_out_channels=tuple(cfg.get("block_out_channels", (128, 256, 512, 512))),
                      layers_per_block=cfg.get("layers_per_block", 2), latent_channels=cfg.get("latent_channels", 4),
                      norm_groups=cfg.get("norm_num_groups", 32))
+
+
+def tiny_vae_config_from_json(cfg: dict) -> TinyVAEConfig:
+    if cfg.get("_class_name", "AutoencoderTiny") != "AutoencoderTiny":
+        raise UnsupportedConfigError(f"vae/config.json: _class_name = {cfg.get('_class_name')!r} is not 'AutoencoderTiny'")
+    _check({k: v for k, v in cfg.items() if not k.startswith("_")}, _TINY_VAE_RULES, "vae")
+    return TinyVAEConfig()
+
+
+TAESD_VAE_CONFIG = {
+    "_class_name": "AutoencoderTiny", "_diffusers_version": "0.25.0", "act_fn": "relu",
+    "decoder_block_out_channels": [64, 64, 64, 64], "encoder_block_out_channels": [64, 64, 64, 64], "force_upcast": False,
+    "in_channels": 3, "latent_channels": 4, "latent_magnitude": 3, "latent_shift": 0.5, "num_decoder_blocks": [3, 3, 3, 1],
+    "num_encoder_blocks": [1, 3, 3, 3], "out_channels": 3, "scaling_factor": 1.0, "shift_factor": None,
+    "upsampling_scaling_factor": 2,
+}
 
 
 # The published key sets (diffusers 0.25, stabilityai/stable-diffusion-2 as shipped inside the Marigold checkpoints):

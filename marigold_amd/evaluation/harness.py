@@ -61,6 +61,8 @@ def _model_arguments(p, kind):
                    help="Resolution the input is resized to before estimation; 0 = native.")
     p.add_argument("--ensemble_size", type=int, required=True, help="Number of predictions to be ensembled.")
     p.add_argument("--half_precision", "--fp16", action="store_true", help="Load the 16-bit weight variant.")
+    p.add_argument("--tiny_vae", type=str, default=None, metavar="DIR",
+                   help="Folder of a diffusers AutoencoderTiny: the pipeline encodes and decodes with it in place of the checkpoint's VAE.")
 
 
 def _run_arguments(p):
@@ -164,8 +166,16 @@ def _save_npy(path, arr):
 def _load_pipeline(kind, args, pipeline):
     """The injected ``pipeline``, or the checkpoint of ``args`` on the GPU."""
     import torch
-    if pipeline is not None:
-        return pipeline
+    if pipeline is None:
+        pipeline = _checkpoint_pipeline(kind, args)
+    if getattr(args, "tiny_vae", None):
+        from ..cli import apply_tiny_vae
+        apply_tiny_vae(pipeline, args.tiny_vae, args.half_precision)
+    return pipeline
+
+
+def _checkpoint_pipeline(kind, args):
+    import torch
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
     import marigold_amd as MA

@@ -272,6 +272,9 @@ def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=N
     configuration's own constants, zeroed state and scratch tagged with its index.  ``mg_model_select`` picks the configuration a
     loaded image runs.  The dict returned then holds ``configs`` (one dict as above per entry), ``shared_bytes`` and
     ``scratch_bytes`` (the scratch region: the largest configuration's, not the sum)."""
+    if not isinstance(pipe.vae, AutoencoderKLHIP):
+        raise ValueError(f"export_model_image: model images carry an AutoencoderKL as op programs; this pipeline's VAE is a "
+                         f"{type(pipe.vae).__name__} (set_vae the checkpoint's AutoencoderKL back to export)")
     if configs is not None:
         if any(v is not None for v in (ensemble_size, height, width, denoising_steps)) or images_per_program != 1:
             raise ValueError("export_model_image: pass either configs=[...] or the keywords of one configuration, not both")

@@ -10,7 +10,10 @@ import torch
 from . import _lib as L
 from . import engine as E
 from . import ops as O
-from .arch import UNetConfig, VAEConfig, unet_param_shapes, vae_param_shapes
+import ctypes
+
+from . import weights as Wm
+from .arch import TinyVAEConfig, UNetConfig, VAEConfig, tiny_vae_layers, tiny_vae_param_shapes, unet_param_shapes, vae_param_shapes
 
 
 def _check_state_dict(sd, shapes, what):
@@ -208,6 +211,18 @@ class AutoencoderKLHIP(_EngineModule):
         self.sd = state_dict
         self.config = config
 
+    @property
+    def scale_factor(self):
+        """Decoded pixels per latent pixel, per axis."""
+        return 2 ** (len(self.config.block_out_channels) - 1)
+
+    def latent_hw(self, hw):
+        """Latent size of an (H, W) image: every down-sampler is a stride-2 convolution on a (0, 1) padding - a floor."""
+        h, w = hw
+        for _ in range(len(self.config.block_out_channels) - 1):
+            h, w = (h - 2) // 2 + 1, (w - 2) // 2 + 1
+        return h, w
+
     def _program(self, kind, B, H, W, post=0):
         key = (kind, B, H, W, post)
         if key in self._programs:
@@ -259,3 +274,122 @@ class AutoencoderKLHIP(_EngineModule):
             seq.run()
             outs.append(out.clone())
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+class AutoencoderTinyHIP(_EngineModule):
+    """diffusers' AutoencoderTiny in the TAESD layout (DESIGN.md "Tiny VAE"), with the surface the pipelines use on
+    ``AutoencoderKLHIP``.  It lives in the UNet's latent space (``scaling_factor`` 1): ``encode_rgb_latent`` = encoder((x + 1) / 2),
+    ``decode`` = decoder(3 tanh(z / 3)) * 2 - 1 with the pipeline's pointwise tail fused.  No op program: the C calls
+    mg_tiny_vae_encode / mg_tiny_vae_decode (csrc/tinyvae.hip) launch the layers on torch's current stream."""
+
+    scale_factor = 8
+    decode_chunk = 0   # members per decode call; 0 = all at once
+
+    def __init__(self, state_dict, config: TinyVAEConfig = TinyVAEConfig(), compute_dtype=torch.bfloat16):
+        super().__init__(compute_dtype)
+        if config != TinyVAEConfig():
+            raise ValueError(f"AutoencoderTinyHIP implements the TAESD layout only, got {config}")
+        _check_state_dict(state_dict, tiny_vae_param_shapes(config), "tiny VAE")
+        self.sd = state_dict
+        self.config = config
+        self._net = None
+        self._buffers = {}
+
+    def latent_hw(self, hw):
+        """Latent size of an (H, W) image: three stride-2 convolutions on a (1, 1) padding - a ceiling each."""
+        h, w = hw
+        for _ in range(len(self.config.num_encoder_blocks) - 1):
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        return h, w
+
+    def _pack(self, device):
+        """The state dict in the layout mg_tiny_vae documents (include/marigold_hip.h) -> (struct, the tensors it points into)."""
+        dt, keep, net = self.compute_dtype, [], L.MgTinyVae()
+
+        def dev(t):
+            keep.append(t.to(device=device).contiguous())
+            return keep[-1].data_ptr()
+
+        def rounded(w):   # fp32 holding operand-typed values: the boundary kernels multiply in fp32
+            return Wm.to_op16(w, dt).float()
+
+        for half, layers in zip(("encoder", "decoder"), tiny_vae_layers(self.config)):
+            pre, l = half[:3], 0
+            for i, kind in layers:
+                n = f"{half}.layers.{i}"
+                if kind == "conv_in":
+                    w = rounded(self.sd[f"{n}.weight"])
+                    setattr(net, f"{pre}_in_w", dev(w.permute(2, 3, 1, 0).reshape(9 * w.shape[1], w.shape[0])))
+                    setattr(net, f"{pre}_in_b", dev(self.sd[f"{n}.bias"].float()))
+                elif kind == "conv_out":
+                    w = rounded(self.sd[f"{n}.weight"])
+                    w4 = torch.zeros(3, 3, w.shape[1], 4)
+                    w4[..., :w.shape[0]] = w.permute(2, 3, 1, 0)
+                    b4 = torch.zeros(4)
+                    b4[:w.shape[0]] = self.sd[f"{n}.bias"].float()
+                    setattr(net, f"{pre}_out_w", dev(w4.reshape(9, w.shape[1], 4)))
+                    setattr(net, f"{pre}_out_b", dev(b4))
+                elif kind in ("block", "down", "conv"):
+                    for name in ([f"{n}.conv.{j}" for j in (0, 2, 4)] if kind == "block" else [n]):
+                        w = self.sd[f"{name}.weight"]
+                        getattr(net, f"{pre}_w")[l] = dev(Wm.to_op16(w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1]), dt))
+                        getattr(net, f"{pre}_b")[l] = dev(self.sd[f"{name}.bias"].float()) if f"{name}.bias" in self.sd else None
+                        l += 1
+            assert l == L.TINY_VAE_LAYERS
+        return net, keep
+
+    def to(self, device):
+        idx = _device_index(device)
+        L.init(idx)
+        if self.f16:
+            L.init(idx, True)
+        self.device = torch.device("cuda", idx)
+        self._net, self.ws = self._pack(self.device)
+        self.pool = E.Pool(self.device)
+        self._buffers = {}
+        return self
+
+    def dry(self):
+        raise RuntimeError("AutoencoderTinyHIP has no op program to validate: its C calls check their arguments themselves")
+
+    def replica(self):
+        r = super().replica()
+        r._buffers = {}
+        return r
+
+    def _workspace(self, which, B, H, W):
+        key = (which, B, H, W)
+        if key not in self._buffers:
+            lib = L.load(self.f16)
+            n = lib.mg_tiny_vae_workspace_bytes(which, B, H, W)
+            if n < 0:
+                L.check(1, "mg_tiny_vae_workspace_bytes", lib)
+            self._buffers[key] = self.pool.get(n)
+        return self._buffers[key]
+
+    def encode_rgb_latent(self, rgb):
+        """rgb [B,3,H,W] in [-1,1] (any float dtype, on device) -> scaled latent [B,4,h,w] fp32."""
+        self._require_device()
+        B, _, H, W = rgb.shape
+        h, w = self.latent_hw((H, W))
+        x = rgb.to(self.device, torch.float32).contiguous()
+        out = torch.empty(B, self.config.latent_channels, h, w, device=self.device)
+        ws, lib = self._workspace(0, B, H, W), L.load(self.f16)
+        L.check(lib.mg_tiny_vae_encode(ctypes.byref(self._net), x.data_ptr(), out.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
+                                       O.current_stream_handle()), "mg_tiny_vae_encode", lib)
+        return out
+
+    def decode(self, latent, post=L.POST_NONE):
+        """latent [B,4,h,w] fp32 -> decoded map fp32 ([B,3,8h,8w], or [B,1,8h,8w] for POST_DEPTH)."""
+        self._require_device()
+        B, _, h, w = latent.shape
+        chunk = self.decode_chunk if 0 < self.decode_chunk < B else B
+        z = latent.to(self.device, torch.float32).contiguous()
+        out = torch.empty(B, 1 if post == L.POST_DEPTH else 3, 8 * h, 8 * w, device=self.device)
+        lib = L.load(self.f16)
+        for i in range(0, B, chunk):
+            n = min(chunk, B - i)
+            ws = self._workspace(1, n, h, w)
+            L.check(lib.mg_tiny_vae_decode(ctypes.byref(self._net), z[i:i + n].data_ptr(), out[i:i + n].data_ptr(), n, h, w, int(post),
+                                           ws.data_ptr(), ws.numel(), O.current_stream_handle()), "mg_tiny_vae_decode", lib)
+        return out

@@ -210,6 +210,18 @@ class _MarigoldPipelineBase:
         self._lanes = []   # engine replicas of map_images belong to the device they were made on
         return self
 
+    def set_vae(self, vae):
+        """Swap the pipeline's autoencoder (``AutoencoderKLHIP`` or ``AutoencoderTinyHIP``, e.g. from ``checkpoint.load_tiny_vae``)
+        for one with the UNet's operand type; it is moved to the pipeline's device.  The cached lanes of ``map_images`` hold
+        replicas of the old one and are dropped."""
+        if vae.dtype != self.unet.dtype:
+            raise ValueError(f"set_vae: the VAE computes on {vae.dtype}, the UNet on {self.unet.dtype}")
+        if self.unet.device.type == "cuda" and vae.device != self.unet.device:
+            vae.to(self.unet.device)
+        self.vae = vae
+        self._lanes = []
+        return self
+
     @classmethod
     def from_pretrained(cls, path, variant=None, torch_dtype=None, **kw):
         from .checkpoint import load_pipeline
@@ -594,7 +606,7 @@ class _MarigoldPipelineBase:
             # decoded maps are latent size x 2^(levels-1), which is smaller than the image when its size is not a
             # multiple of 8 (KITTI 1242x375 -> 768x231 -> latent 96x28 -> decoded 768x224); ranks without members
             # need the shape too, so it is computed, not taken from `local`
-            f = 2 ** (len(self.vae.config.block_out_channels) - 1)
+            f = getattr(self.vae, "scale_factor", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
             hh, ww = (f * d for d in self._latent_hw(rgb_norm.shape[-2:]))
             # maps in flight: the gather is a collective on ONE process group - every rank issues the gathers of maps 0, 1, 2 ...
             # in that order, one at a time, whichever lane (thread, stream) predicted them (map_images hands each call its turn)
@@ -686,6 +698,10 @@ class _MarigoldPipelineBase:
         return denoising_steps, ensemble_size, processing_res, get_tv_resample_method(resample_method)
 
     def _latent_hw(self, hw):
+        """The VAE's own rule (the KL encoder's down-samplers floor, the tiny autoencoder's ceil); a VAE object without
+        ``latent_hw`` is taken for an AutoencoderKL of ``config.block_out_channels`` levels."""
+        if hasattr(self.vae, "latent_hw"):
+            return self.vae.latent_hw(hw)
         h, w = hw
         for _ in range(len(self.vae.config.block_out_channels) - 1):
             h, w = (h - 2) // 2 + 1, (w - 2) // 2 + 1

@@ -11,7 +11,7 @@ import zlib
 
 import torch
 
-from .arch import UNetConfig, VAEConfig, unet_param_shapes, vae_param_shapes
+from .arch import TinyVAEConfig, UNetConfig, VAEConfig, tiny_vae_layers, tiny_vae_param_shapes, unet_param_shapes, vae_param_shapes
 
 
 def _draw(key, shape, seed):
@@ -62,6 +62,56 @@ def synthetic_unet_state_dict(cfg: UNetConfig = UNetConfig(), seed: int = 1234, 
 
 def synthetic_vae_state_dict(cfg: VAEConfig = VAEConfig(), seed: int = 1234):
     return synthetic_state_dict(vae_param_shapes(cfg), seed + 1)
+
+
+def _tiny_decoder_features(sd, cfg, z):
+    """fp64 decoder of the tiny autoencoder up to the input of its last convolution (the calibration below)."""
+    F = torch.nn.functional
+    w = {k: v.double() for k, v in sd.items() if k.startswith("decoder.")}
+    x = cfg.latent_magnitude * torch.tanh(z.double() / cfg.latent_magnitude)
+    for i, kind in tiny_vae_layers(cfg)[1]:
+        n = f"decoder.layers.{i}"
+        if kind == "conv_in":
+            x = F.conv2d(x, w[f"{n}.weight"], w[f"{n}.bias"], padding=1)
+        elif kind == "relu":
+            x = torch.relu(x)
+        elif kind == "block":
+            y = x
+            for j in (0, 2, 4):
+                y = F.conv2d(y, w[f"{n}.conv.{j}.weight"], w[f"{n}.conv.{j}.bias"], padding=1)
+                if j != 4:
+                    y = torch.relu(y)
+            x = torch.relu(y + x)
+        elif kind == "up":
+            x = F.interpolate(x, scale_factor=2, mode="nearest")
+        elif kind == "conv":
+            x = F.conv2d(x, w[f"{n}.weight"], None, padding=1)
+    return x
+
+
+def synthetic_tiny_vae_state_dict(cfg: TinyVAEConfig = TinyVAEConfig(), seed: int = 1234):
+    """Seeded weights for the tiny autoencoder that keep its activations alive and its output inside the pipelines' clip: He-normal
+    weights (std = sqrt(2 / (9 Cin)); plain N(0, 1 / fan_in) dies out under thirty ReLUs, plain He saturates every output), every
+    Block's third convolution scaled by 0.25 (the residual sum then grows slowly), biases N(0, 0.1^2), and the decoder's last
+    convolution calibrated so that on a fixed probe latent (N(0, 1), [1, 4, 8, 8], seed 99) its [0, 1]-space output has mean 0.5 and
+    standard deviation 0.2 - under 1 % of the fp64 network's [-1, 1]-space values then leave [-1, 1]."""
+    sd = {}
+    for key, shape in tiny_vae_param_shapes(cfg).items():
+        g = torch.Generator("cpu").manual_seed((zlib.crc32(key.encode()) ^ ((seed + 2) * 2654435761)) & 0x7FFFFFFF)
+        if key.endswith(".weight"):
+            t = torch.randn(tuple(shape), generator=g) * (2.0 / (9 * shape[1])) ** 0.5
+            if key.endswith(".conv.4.weight"):
+                t = t * 0.25
+        else:
+            t = 0.1 * torch.randn(tuple(shape), generator=g)
+        sd[key] = t
+    last = f"decoder.layers.{tiny_vae_layers(cfg)[1][-1][0]}"
+    probe = torch.randn(1, cfg.latent_channels, 8, 8, generator=torch.Generator("cpu").manual_seed(99))
+    raw = torch.nn.functional.conv2d(_tiny_decoder_features(sd, cfg, probe), sd[f"{last}.weight"].double(), None, padding=1)
+    scale = 0.2 / float(raw.std())
+    sd[f"{last}.weight"] = (sd[f"{last}.weight"].double() * scale).float()
+    sd[f"{last}.bias"] = torch.full_like(sd[f"{last}.bias"], 0.5 - scale * float(raw.mean()))
+    return sd
 
 
 def synthetic_text_embedding(cross_dim: int = 1024, seed: int = 7):
