@@ -6,6 +6,8 @@
 // Run:                 ./host_depth model.mgimg rgb.f32 noise.f32 depth_out.f32
 //   rgb.f32   raw fp32 [1,3,H,W] in [-1,1];  noise.f32  raw fp32 [B,4,h,w] (the initial latents);  depth_out.f32  raw fp32 [H',W']
 // (tests/test_gpu_pipeline.py::test_model_image_from_a_c_host builds and runs it and compares with the Python pipeline bit for bit.)
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -10,6 +10,8 @@
 //   out_prefix.<i>.f32 / .unc.f32 / .pgm / .ppm: the files host_picture.cpp writes, for picture i
 // The Python pipelines give the same arrays and pictures, bit for bit, with generators=[marigold_amd.NativeNoise(seed_i)]
 // (tests/test_gpu_predict_many_c_host.py builds and runs this program and compares).
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

@@ -10,6 +10,8 @@
 //                 16-bit binary PGM, pred_out.f32.pgm (65535 = far, the reference's 16-bit PNG values)
 // The Python pipelines give the same map, bit for bit, with generator=marigold_amd.NativeNoise(seed)
 // (tests/test_gpu_native_noise.py builds and runs this program and compares).
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

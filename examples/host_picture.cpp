@@ -16,6 +16,8 @@
 //   out_prefix.ppm        the picture, binary PPM
 // The Python pipelines give the same arrays and pictures, bit for bit, with generator=marigold_amd.NativeNoise(seed)
 // (tests/test_gpu_predict_out_c_host.py builds and runs this program and compares).
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

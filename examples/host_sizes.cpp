@@ -12,6 +12,8 @@
 //   out_prefix.<i>.f32 / .unc.f32 / .pgm / .ppm: the files host_picture.cpp writes, for picture i, at Hi x Wi
 // The Python pipelines give the same arrays and pictures, bit for bit, with pipe(image, processing_res=res, match_input_res=True,
 // generator=marigold_amd.NativeNoise(seed)) (tests/test_gpu_model_configs.py builds and runs this program and compares).
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

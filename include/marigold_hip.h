@@ -924,6 +924,27 @@ int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W);
 long long mg_model_shared_bytes(const mg_model* m);
 mg_model* mg_model_replica(const mg_model* m);
 
+/* Model images with the TINY autoencoder (export_model_image(tiny_vae=True), a version-3 file in the version-2 layout, for one
+ * configuration or several): cfg16[14] names the image's VAE - 0 an AutoencoderKL (every version-1 and version-2 image), 1 the tiny
+ * autoencoder - and one image has one.  Where an AutoencoderKL image runs its encode and decode programs, a tiny image calls
+ * mg_tiny_vae_encode (the K pictures of a call) and mg_tiny_vae_decode (all K B members, times the modalities, in ONE call; a member's
+ * result does not depend on the batch) on the same named slots, on the caller's stream, with the tail cfg16[7], without
+ * synchronising: in mg_model_vae_encode / mg_model_vae_decode and in every mg_model_predict*.  Nothing else differs, and a host written
+ * for AutoencoderKL images runs a tiny one unchanged, provided it sizes its buffers from cfg16 as documented: the latent size
+ * cfg16[3] x cfg16[4] is the tiny encoder's, a CEILING per stride-2 layer (30 x 44 -> 4 x 6) where the AutoencoderKL floors (3 x 5),
+ * and the decoded size cfg16[11] x cfg16[12] is 8 x that (32 x 48), which may exceed the picture.  In the file the two VAE entries of a
+ * configuration hold no ops, only their slots (rgb, latent | latent, pred) and a workspace slot (ws) of at least
+ * mg_tiny_vae_workspace_bytes - scratch of that configuration, in the region the configurations overlay; the members of struct
+ * mg_tiny_vae lie in the shared weights (mg_model_shared_bytes; replicas read the same ones), recorded as (buffer, byte offset), the six
+ * bias-free layers as absent.  mg_model_load checks all of that - every member inside its buffer with the bytes its layout implies and
+ * 16-byte aligned, NULL members exactly where the layout has them, the slot sizes chained under the ceiling rule, the workspaces - and
+ * mg_model_validate runs the two calls' own argument checks without a device.  A library built before version 3 refuses such a file
+ * as an unknown version.
+ *  mg_model_scratch_fill: a test hook - every scratch buffer of the handle (all configurations') is set to `byte` on `stream`, so that
+ *  a test can show that no result depends on what scratch held before a call (0xff: NaN in every float format).  Does not
+ *  synchronise; refuses a host-only model. */
+int mg_model_scratch_fill(mg_model* m, int byte, void* stream);
+
 /* The whole prediction of one picture as ONE call, from the uint8 bytes and a seed to the ensembled map - __call__ of the reference's
  * pipelines (marigold/marigold_depth_pipeline.py:154-338, marigold_normals_pipeline.py:139-308) up to match_input_res, for a host
  * that has neither torch nor a noise file.  All pointers are device pointers.  The chain: mg_rgb_prepare to the model's H x W (rgb

@@ -216,6 +216,7 @@ EXPORTS = [
     "mg_model_shared_bytes", "mg_model_replica",
     "mg_latent_carry", "mg_model_seq_reset", "mg_model_predict_next",
     "mg_tiny_vae_workspace_bytes", "mg_tiny_vae_encode", "mg_tiny_vae_decode", "mg_tiny_conv3x3",
+    "mg_model_scratch_fill",
 ]
 
 
@@ -360,6 +361,7 @@ def load(f16=False):
         [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgPredictOpts), ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_latent_carry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]
     lib.mg_model_seq_reset.argtypes = [ctypes.c_void_p]
+    lib.mg_model_scratch_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]
     lib.mg_model_config_info.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]

@@ -10,6 +10,10 @@
 // table (cfg[16] + three programs each) | buffer table | blobs.  The packed weights are stored once (kind 3, shared); every other
 // buffer names its configuration.  A handle = the shared weights (reference-counted: mg_model_replica makes another handle over
 // them) + a private arena; mg_model_select picks the configuration the entry points act on.  A version-1 file is one configuration.
+// Version 3 is version 2 with the TINY autoencoder (csrc/tinyvae.hip) where the AutoencoderKL programs stand, cfg[14] = 1: the two VAE
+// entries of a configuration hold no ops, only named slots (rgb, latent, ws | latent, pred, ws - all scratch of that configuration); behind
+// the buffer table lies one table more, the members of struct mg_tiny_vae as (shared buffer, byte offset).  The encode and decode
+// stages of such an image are mg_tiny_vae_encode / mg_tiny_vae_decode on those slots.
 #include <stdio.h>
 #include <string.h>
 
@@ -64,7 +68,38 @@ struct ImgConfig {
   uint32_t cfg[16];
   ImgProgram prog[3];
 };
+struct ImgTinyMember {   // version 3, after the buffer table: one per pointer of struct mg_tiny_vae, in the struct's order
+  uint32_t buf, pad;     // buf 0xffffffff: a NULL member (the bias of a bias-free layer)
+  uint64_t off;
+};
 #pragma pack(pop)
+
+enum { VAE_KL = 0, VAE_TINY = 1 };   // cfg[14]
+constexpr int TINY_MEMBERS = (int)(sizeof(mg_tiny_vae) / sizeof(void*));
+constexpr int TINY_HALF = 4 + 2 * MG_TINY_VAE_LAYERS;
+constexpr uint32_t TINY_ABSENT = 0xffffffffu;
+static_assert(TINY_MEMBERS == 2 * TINY_HALF && sizeof(mg_tiny_vae) == TINY_MEMBERS * sizeof(void*), "mg_tiny_vae: two halves of pointers");
+
+// Member k of struct mg_tiny_vae (in_w, in_b, w[33], b[33], out_w, out_b of the encoder, then of the decoder): the bytes its layout
+// implies (include/marigold_hip.h), and whether it is the bias of a bias-free layer (encoder 3, 13, 23, decoder 9, 19, 29: NULL)
+uint64_t tiny_member_bytes(int k, bool* absent) {
+  const int half = k / TINY_HALF, j = k % TINY_HALF, cin = half ? 4 : 3, plain = half ? 9 : 3;
+  *absent = false;
+  if (j == 0) return 9ull * cin * 64 * 4;
+  if (j == 1) return 64 * 4;
+  if (j < 2 + MG_TINY_VAE_LAYERS) return 9ull * 64 * 64 * 2;
+  if (j < 2 + 2 * MG_TINY_VAE_LAYERS) {
+    const int l = j - 2 - MG_TINY_VAE_LAYERS;
+    *absent = l >= plain && (l - plain) % 10 == 0;
+    return 64 * 4;
+  }
+  return j == TINY_HALF - 2 ? 9ull * 64 * 4 * 4 : 4 * 4;
+}
+
+uint32_t ceil8(uint32_t n) {   // the tiny encoder's latent size: a ceiling per stride-2 layer
+  for (int k = 0; k < 3; ++k) n = (n - 1) / 2 + 1;
+  return n;
+}
 
 enum { KIND_SCRATCH = 0, KIND_ZERO = 1, KIND_DATA = 2, KIND_SHARED = 3 };
 
@@ -92,6 +127,8 @@ struct PlanConfig {
 };
 struct Plan {
   uint32_t version = 1;
+  bool tiny = false;                   // version 3: the VAE stages are the tiny autoencoder's calls
+  ImgTinyMember tiny_net[TINY_MEMBERS] = {};   // (checked by parse_image)
   std::vector<PlanBuf> bufs;
   std::vector<PlanConfig> cfgs;
   uint64_t shared_bytes = 0, private_bytes = 0;
@@ -139,6 +176,7 @@ struct mg_model {
   uint64_t arena_bytes = 0;
   std::vector<char*> bufs;
   std::vector<Config> configs;
+  mg_tiny_vae tiny_net = {};   // a tiny image: the network in the shared weights
   int sel = 0;                 // the selected configuration: what every entry point below acts on
   const Config& cur() const { return configs[sel]; }
   void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W], one picture's: the
@@ -164,15 +202,15 @@ uint64_t r256(uint64_t b) { return (b + 255) / 256 * 256; }
 // May configuration `c` point into buffer `b`?  Its own buffers and the shared weights only.
 bool owns(const Plan& p, uint32_t c, uint32_t b) { return p.version == 1 || p.bufs[b].kind == KIND_SHARED || p.bufs[b].cfg == c; }
 
-int parse_program(FILE* f, uint64_t file_bytes, const ImgProgram& ip, const Plan& p, uint32_t c, PlanProg* out) {
+int parse_program(FILE* f, uint64_t file_bytes, const ImgProgram& ip, const Plan& p, uint32_t c, bool no_ops, PlanProg* out) {
   out->name = std::string(ip.name, strnlen(ip.name, sizeof(ip.name)));
   const char* nm = out->name.c_str();
-  MG_REQUIRE(ip.n_ops > 0 && ip.n_slots <= 16, "mg_model_load: corrupt program table (%s)", nm);
+  MG_REQUIRE((no_ops ? ip.n_ops == 0 && ip.n_relocs == 0 : ip.n_ops > 0) && ip.n_slots <= 16, "mg_model_load: corrupt program table (%s)", nm);
   MG_REQUIRE(ip.ops_off <= file_bytes && (uint64_t)ip.n_ops * sizeof(mg_op) <= file_bytes - ip.ops_off &&
                  ip.relocs_off <= file_bytes && (uint64_t)ip.n_relocs * sizeof(ImgReloc) <= file_bytes - ip.relocs_off,
              "mg_model_load: corrupt image - the ops or relocations of %s lie outside the %llu-byte file", nm, (unsigned long long)file_bytes);
   out->ops.resize(ip.n_ops);
-  MG_REQUIRE(read_at(f, ip.ops_off, out->ops.data(), sizeof(mg_op) * ip.n_ops), "mg_model_load: short read (ops of %s)", nm);
+  MG_REQUIRE(ip.n_ops == 0 || read_at(f, ip.ops_off, out->ops.data(), sizeof(mg_op) * ip.n_ops), "mg_model_load: short read (ops of %s)", nm);
   out->rel.resize(ip.n_relocs);
   MG_REQUIRE(ip.n_relocs == 0 || read_at(f, ip.relocs_off, out->rel.data(), sizeof(ImgReloc) * ip.n_relocs),
              "mg_model_load: short read (relocations of %s)", nm);
@@ -202,12 +240,14 @@ int parse_program(FILE* f, uint64_t file_bytes, const ImgProgram& ip, const Plan
 int parse_image(FILE* f, Plan* p) {
   ImgHeader h;
   MG_REQUIRE(read_at(f, 0, &h, sizeof(ImgHeader)), "mg_model_load: short read (header)");
-  MG_REQUIRE(memcmp(h.magic, "MGIMG1\0\0", 8) == 0 && (h.version == 1 || h.version == 2), "mg_model_load: not a model image (or an unknown version)");
+  MG_REQUIRE(memcmp(h.magic, "MGIMG1\0\0", 8) == 0 && h.version >= 1 && h.version <= 3, "mg_model_load: not a model image (or an unknown version)");
   MG_REQUIRE(h.abi == MG_ABI_VERSION && h.cfg[9] == sizeof(mg_op),
              "mg_model_load: the image was written for ABI %u / %u-byte ops, this library is ABI %d / %zu", h.abi, h.cfg[9], MG_ABI_VERSION, sizeof(mg_op));
   p->version = h.version;
+  p->tiny = h.version == 3;
+  const bool multi = h.version >= 2;   // the layout of several configurations
   ImgV2 v2 = {1, 0, 0};
-  if (h.version == 2) {
+  if (multi) {
     MG_REQUIRE(read_at(f, sizeof(ImgHeader), &v2, sizeof(ImgV2)), "mg_model_load: short read (header)");
     MG_REQUIRE(v2.n_configs >= 1 && v2.n_configs <= 4096 && v2.scratch_bytes < (1ull << 40), "mg_model_load: corrupt header");
   }
@@ -220,7 +260,7 @@ int parse_image(FILE* f, Plan* p) {
   // version 1: header | buffer table | three programs; version 2: header | ImgV2 | configuration table | buffer table
   std::vector<ImgConfig> ct(v2.n_configs);
   uint64_t buf_at = sizeof(ImgHeader);
-  if (h.version == 2) {
+  if (multi) {
     MG_REQUIRE(read_at(f, sizeof(ImgHeader) + sizeof(ImgV2), ct.data(), sizeof(ImgConfig) * v2.n_configs),
                "mg_model_load: short read (configuration table)");
     buf_at += sizeof(ImgV2) + sizeof(ImgConfig) * v2.n_configs;
@@ -241,7 +281,7 @@ int parse_image(FILE* f, Plan* p) {
   for (uint32_t i = 0; i < h.n_buffers; ++i) {
     const ImgBuffer& b = bt[i];
     MG_REQUIRE(b.nbytes > 0 && b.nbytes < (1ull << 40), "mg_model_load: corrupt image - buffer %u has %llu bytes", i, (unsigned long long)b.nbytes);
-    MG_REQUIRE(b.kind <= (h.version == 2 ? KIND_SHARED : KIND_DATA), "mg_model_load: corrupt image - buffer %u is of unknown kind %u", i, b.kind);
+    MG_REQUIRE(b.kind <= (multi ? KIND_SHARED : KIND_DATA), "mg_model_load: corrupt image - buffer %u is of unknown kind %u", i, b.kind);
     if (b.kind == KIND_DATA || b.kind == KIND_SHARED)
       MG_REQUIRE(b.file_off <= file_bytes && b.nbytes <= file_bytes - b.file_off,
                  "mg_model_load: corrupt image - buffer %u lies at [%llu, +%llu) of a %llu-byte file", i, (unsigned long long)b.file_off,
@@ -250,7 +290,7 @@ int parse_image(FILE* f, Plan* p) {
     pb.nbytes = b.nbytes;
     pb.file_off = b.file_off;
     pb.kind = b.kind;
-    pb.cfg = h.version == 2 && b.kind != KIND_SHARED ? b.cfg : 0;
+    pb.cfg = multi && b.kind != KIND_SHARED ? b.cfg : 0;
     pb.shared = b.kind == KIND_SHARED;
     MG_REQUIRE(pb.cfg < v2.n_configs, "mg_model_load: corrupt image - buffer %u belongs to configuration %u of %u", i, pb.cfg, v2.n_configs);
     if (pb.shared) {
@@ -261,7 +301,7 @@ int parse_image(FILE* f, Plan* p) {
       priv += r256(b.nbytes);
     }
   }
-  if (h.version == 2) {
+  if (multi) {
     for (uint32_t i = 0; i < h.n_buffers; ++i) {
       PlanBuf& pb = p->bufs[i];
       if (pb.kind != KIND_SCRATCH) continue;
@@ -277,6 +317,26 @@ int parse_image(FILE* f, Plan* p) {
   }
   p->shared_bytes = shared;
   p->private_bytes = priv;
+  // ---- version 3: the tiny network, every member inside a shared buffer with the bytes its layout implies
+  if (p->tiny) {
+    MG_REQUIRE(read_at(f, buf_at + sizeof(ImgBuffer) * h.n_buffers, p->tiny_net, sizeof(p->tiny_net)), "mg_model_load: short read (tiny VAE table)");
+    for (int k = 0; k < TINY_MEMBERS; ++k) {
+      const ImgTinyMember& t = p->tiny_net[k];
+      bool absent;
+      const uint64_t need = tiny_member_bytes(k, &absent);
+      MG_REQUIRE((t.buf == TINY_ABSENT) == absent,
+                 "mg_model_load: corrupt image - member %d of the tiny VAE is %s (the bias-free layers are encoder 3, 13, 23 and decoder 9, 19, 29)", k,
+                 absent ? "present where the layer has no bias" : "absent");
+      if (absent) continue;
+      MG_REQUIRE(t.buf < h.n_buffers && p->bufs[t.buf].kind == KIND_SHARED, "mg_model_load: corrupt image - member %d of the tiny VAE names buffer %u, not a shared one",
+                 k, t.buf);
+      MG_REQUIRE(t.off % 16 == 0, "mg_model_load: corrupt image - member %d of the tiny VAE lies at byte %llu of its buffer, not 16-byte aligned", k,
+                 (unsigned long long)t.off);
+      MG_REQUIRE(t.off <= p->bufs[t.buf].nbytes && need <= p->bufs[t.buf].nbytes - t.off,
+                 "mg_model_load: corrupt image - member %d of the tiny VAE spans [%llu, +%llu) of a %llu-byte buffer", k, (unsigned long long)t.off,
+                 (unsigned long long)need, (unsigned long long)p->bufs[t.buf].nbytes);
+    }
+  }
   // ---- the configurations
   p->cfgs.resize(v2.n_configs);
   static const char* const want[3] = {"vae.encode", "denoise", "vae.decode"};
@@ -285,7 +345,7 @@ int parse_image(FILE* f, Plan* p) {
     memcpy(pc.cfg, ct[c].cfg, sizeof(pc.cfg));
     MG_REQUIRE(pc.cfg[9] == sizeof(mg_op), "mg_model_load: configuration %u was written for %u-byte ops, this library has %zu", c, pc.cfg[9], sizeof(mg_op));
     for (int k = 0; k < 3; ++k) {
-      if (int rc = parse_program(f, file_bytes, ct[c].prog[k], *p, c, &pc.prog[k])) return rc;
+      if (int rc = parse_program(f, file_bytes, ct[c].prog[k], *p, c, p->tiny && k != 1, &pc.prog[k])) return rc;
       MG_REQUIRE(pc.prog[k].name == want[k], "mg_model_load: program %d is '%s', expected '%s'", k, pc.prog[k].name.c_str(), want[k]);
     }
     const ImgSlot *e_in = pc.prog[0].slot("rgb"), *e_out = pc.prog[0].slot("latent"), *rl = pc.prog[1].slot("rgb_latent"), *xs = pc.prog[1].slot("x");
@@ -297,6 +357,31 @@ int parse_image(FILE* f, Plan* p) {
     MG_REQUIRE(K < (1u << 20) && e_in->nbytes == K * 3 * g[1] * g[2] * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
                    xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * g[0] * g[6] * g[11] * g[12] * 4,
                "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", (int)K, g[0]);
+    MG_REQUIRE(g[14] == (p->tiny ? VAE_TINY : VAE_KL), "mg_model_load: configuration %u names VAE %u in cfg[14]: a version-%u image carries %s", c, g[14],
+               h.version, p->tiny ? "the tiny autoencoder (1)" : "an AutoencoderKL (0)");
+    if (p->tiny) {
+      // the calls' arguments: K pictures [K,3,H,W] -> [K,4,h,w] (a ceiling per stride-2 layer); K B n members [.,4,h,w] -> [.,C,8h,8w]
+      const uint64_t n = g[10], members = K * g[0] * n, cpred = g[7] == MG_POST_DEPTH ? 1 : 3;
+      MG_REQUIRE(g[1] >= 1 && g[2] >= 1 && g[1] <= (1u << 16) && g[2] <= (1u << 16) && g[0] >= 1 && n >= 1 && members < (1u << 20) &&
+                     (g[7] == MG_POST_NONE || g[7] == MG_POST_DEPTH || g[7] == MG_POST_NORMALS || g[7] == MG_POST_UNIT) &&
+                     g[3] == ceil8(g[1]) && g[4] == ceil8(g[2]) && g[11] == 8 * g[3] && g[12] == 8 * g[4] && g[6] == cpred * n &&
+                     e_out->nbytes == K * 4 * g[3] * g[4] * 4 && d_in->nbytes == members * 4 * g[3] * g[4] * 4,
+                 "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) through the tiny VAE (%u x %u -> latent %u x %u -> %u x %u)",
+                 (int)K, g[0], g[1], g[2], g[3], g[4], g[11], g[12]);
+      const ImgSlot *e_ws = pc.prog[0].slot("ws"), *d_ws = pc.prog[2].slot("ws");
+      MG_REQUIRE(e_ws && d_ws, "mg_model_load: a tiny VAE entry lacks its workspace slot");
+      const long long e_need = mg_tiny_vae_workspace_bytes(0, (int)K, (int)g[1], (int)g[2]);
+      const long long d_need = mg_tiny_vae_workspace_bytes(1, (int)members, (int)g[3], (int)g[4]);
+      MG_REQUIRE(e_need > 0 && d_need > 0, "mg_model_load: configuration %u is beyond the tiny VAE's sizes (%s)", c, mg_last_error());
+      MG_REQUIRE(e_ws->nbytes >= (uint64_t)e_need && d_ws->nbytes >= (uint64_t)d_need,
+                 "mg_model_load: corrupt image - the tiny VAE's workspaces of configuration %u hold %llu and %llu bytes, the calls need %lld and %lld", c,
+                 (unsigned long long)e_ws->nbytes, (unsigned long long)d_ws->nbytes, e_need, d_need);
+      // every slot of the two entries is scratch of this configuration, 16-byte aligned (buffers lie on 256-byte boundaries)
+      for (int k = 0; k < 3; k += 2)
+        for (const ImgSlot& sl : pc.prog[k].slots)
+          MG_REQUIRE(p->bufs[sl.buf].kind == KIND_SCRATCH && sl.off % 16 == 0, "mg_model_load: corrupt image - slot %.24s of %s is not aligned scratch",
+                     sl.name, pc.prog[k].name.c_str());
+    }
   }
   return 0;
 }
@@ -306,6 +391,10 @@ int instantiate(mg_model* m) {
   const Plan& p = *m->plan;
   m->bufs.resize(p.bufs.size());
   for (size_t i = 0; i < p.bufs.size(); ++i) m->bufs[i] = (p.bufs[i].shared ? m->shared->base : m->arena) + p.bufs[i].off;
+  if (p.tiny) {
+    const void** member = (const void**)&m->tiny_net;
+    for (int k = 0; k < TINY_MEMBERS; ++k) member[k] = p.tiny_net[k].buf == TINY_ABSENT ? nullptr : m->bufs[p.tiny_net[k].buf] + p.tiny_net[k].off;
+  }
   m->configs.resize(p.cfgs.size());
   for (size_t c = 0; c < p.cfgs.size(); ++c) {
     Config& cf = m->configs[c];
@@ -326,8 +415,10 @@ int instantiate(mg_model* m) {
         }
       }
       dst[k]->name = pp.name;
-      dst[k]->prog = mg_program_create(ops.data(), (int)ops.size());
-      MG_REQUIRE(dst[k]->prog, "mg_model_load: mg_program_create failed (%s)", pp.name.c_str());
+      if (!ops.empty()) {   // (a tiny image's VAE entries: slots only)
+        dst[k]->prog = mg_program_create(ops.data(), (int)ops.size());
+        MG_REQUIRE(dst[k]->prog, "mg_model_load: mg_program_create failed (%s)", pp.name.c_str());
+      }
       for (const ImgSlot& s : pp.slots)
         dst[k]->slots.push_back(Slot{std::string(s.name, strnlen(s.name, sizeof(s.name))), m->bufs[s.buf] + s.off, s.nbytes});
     }
@@ -412,6 +503,24 @@ int replicate_into(mg_model* r, const mg_model* m) {
 int copy_dd(void* dst, const void* src, uint64_t n, hipStream_t s) {
   MG_CHECK_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, s));
   return 0;
+}
+
+// The encode and the decode stage of the selected configuration, slot to slot on the caller's stream: the program of an AutoencoderKL
+// image; the plain calls of a tiny one (mg_model_load checked their arguments against the slots) - all K B n members in ONE decode
+int run_encode(const mg_model* m, void* stream) {
+  const Config& c = m->cur();
+  if (!m->plan->tiny) return mg_program_run(c.enc.prog, stream);
+  const Slot* ws = c.enc.slot("ws");
+  return mg_tiny_vae_encode(&m->tiny_net, (const float*)c.enc.slot("rgb")->ptr, (float*)c.enc.slot("latent")->ptr, c.K, (int)c.cfg[1], (int)c.cfg[2],
+                            ws->ptr, (long long)ws->nbytes, stream);
+}
+
+int run_decode(const mg_model* m, void* stream) {
+  const Config& c = m->cur();
+  if (!m->plan->tiny) return mg_program_run(c.dec.prog, stream);
+  const Slot* ws = c.dec.slot("ws");
+  return mg_tiny_vae_decode(&m->tiny_net, (const float*)c.dec.slot("latent")->ptr, (float*)c.dec.slot("pred")->ptr,
+                            c.K * (int)c.cfg[0] * (int)c.cfg[10], (int)c.cfg[3], (int)c.cfg[4], (int)c.cfg[7], ws->ptr, (long long)ws->nbytes, stream);
 }
 
 }  // namespace
@@ -538,8 +647,23 @@ long long mg_model_shared_bytes(const mg_model* m) { return m ? (long long)m->pl
 int mg_model_validate(mg_model* m) {
   MG_REQUIRE(m, "mg_model_validate: null model");
   const Config& c = m->cur();
+  if (m->plan->tiny) {   // the tiny calls check every argument before their first launch; dry, they launch nothing
+    g_dry_run = true;
+    int rc = run_encode(m, nullptr);
+    if (!rc) rc = run_decode(m, nullptr);
+    g_dry_run = false;
+    return rc ? rc : mg_program_validate(c.den.prog);
+  }
   for (const Prog* p : {&c.enc, &c.den, &c.dec})
     if (int rc = mg_program_validate(p->prog)) return rc;
+  return 0;
+}
+
+int mg_model_scratch_fill(mg_model* m, int byte, void* stream) {
+  MG_REQUIRE(m && !m->host_only && byte >= 0 && byte <= 255, "mg_model_scratch_fill: bad arguments (or a host-only model)");
+  const Plan& p = *m->plan;
+  for (size_t i = 0; i < p.bufs.size(); ++i)   // (the configurations' scratch buffers overlay each other: some bytes are set twice)
+    if (p.bufs[i].kind == KIND_SCRATCH) MG_CHECK_HIP(hipMemsetAsync(m->bufs[i], byte, p.bufs[i].nbytes, (hipStream_t)stream));
   return 0;
 }
 
@@ -549,7 +673,7 @@ int mg_model_vae_encode(mg_model* m, const float* rgb, float* latent, void* stre
   const Config& c = m->cur();
   const Slot *in = c.enc.slot("rgb"), *out = c.enc.slot("latent");
   if (int rc = copy_dd(in->ptr, rgb, in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(c.enc.prog, stream)) return rc;
+  if (int rc = run_encode(m, stream)) return rc;
   return copy_dd(latent, out->ptr, out->nbytes, s);
 }
 
@@ -579,7 +703,7 @@ int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* str
   const Config& c = m->cur();
   const Slot *in = c.dec.slot("latent"), *out = c.dec.slot("pred");
   if (int rc = copy_dd(in->ptr, latent, in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(c.dec.prog, stream)) return rc;
+  if (int rc = run_decode(m, stream)) return rc;
   return copy_dd(pred, out->ptr, out->nbytes, s);
 }
 
@@ -757,7 +881,7 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
   for (int i = 0; i < K; ++i)
     if (int rc = mg_rgb_prepare(rgb[i < n ? i : n - 1], hwc, Hin, Win, e_in->ptr + i * rgb_row, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
   // 2. encode
-  if (int rc = mg_program_run(m->cur().enc.prog, stream)) return rc;
+  if (int rc = run_encode(m, stream)) return rc;
   if (int rc = copy_dd(rl->ptr, e_out->ptr, rl->nbytes, s)) return rc;
   // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
   for (int i = 0; i < K; ++i)
@@ -780,7 +904,7 @@ int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* r
     m->seq_carried = true;
   }
   if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
-  if (int rc = mg_program_run(m->cur().dec.prog, stream)) return rc;
+  if (int rc = run_decode(m, stream)) return rc;
   *preds = (const float*)d_out->ptr;
   return 0;
 }

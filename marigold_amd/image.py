@@ -23,6 +23,13 @@ An image of several configurations (version 2) has the same parts with one more 
 The modules' packed weights (``mod.ws.cache``) are written once, as buffers every configuration refers to; the loader keeps them in
 an allocation that ``mg_model_replica`` handles share.  A call with the keywords of one configuration writes the version-1 file it
 always wrote.
+
+An image with the tiny autoencoder (``tiny_vae=True``, version 3) is a version-2 file, for one configuration or several, with two
+differences: the ``vae.encode`` and ``vae.decode`` entries of a configuration hold no ops, only their named slots and a workspace slot
+(scratch: the loader runs ``mg_tiny_vae_encode`` / ``mg_tiny_vae_decode`` on them), and behind the buffer table lies one table more, the
+members of ``struct mg_tiny_vae`` as (shared buffer, byte offset):
+
+    header | configurations, scratch region | configuration table | buffer table | tiny VAE members | blobs
 """
 import ctypes
 import struct
@@ -31,11 +38,15 @@ import torch
 
 from . import _lib as L
 from . import ops as O
-from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
+from .modules import AutoencoderKLHIP, AutoencoderTinyHIP, UNet2DConditionModelHIP
 
 MAGIC = b"MGIMG1\0\0"
 VERSION = 1
 VERSION_CONFIGS = 2   # several configurations in one image (export_model_image(configs=[...]))
+VERSION_TINY = 3      # the tiny autoencoder instead of the AutoencoderKL (export_model_image(tiny_vae=True)): the version-2 layout, the
+                      # two VAE entries of a configuration without ops, one table more (the members of struct mg_tiny_vae)
+VAE_KL, VAE_TINY = 0, 1   # cfg[14]
+TINY_MEMBER, TINY_ABSENT = "<IIQ", 0xFFFFFFFF   # a member of mg_tiny_vae: buffer (TINY_ABSENT: a NULL member), pad, byte offset
 KIND_SCRATCH, KIND_ZERO, KIND_DATA, KIND_SHARED = 0, 1, 2, 3   # SHARED: the weight cache of a version-2 image, stored once
 SLOT_LN_COUNTERS = 100   # relocation slot of MG_OP_IGEMM's ticket address pair (ops.igemm_tickets); slots 0..15 = p[k]
 _PRED = {"depth": (L.POST_DEPTH, 1), "normals": (L.POST_NORMALS, 3), "iid": (L.POST_UNIT, 3)}
@@ -102,6 +113,47 @@ def _r256(n):
     return (n + 255) // 256 * 256
 
 
+class _Region:
+    """``nbytes`` of scratch that exist in an image's memory plan only - the slots and workspaces of the tiny autoencoder's calls: an
+    address range no tensor has, with what ``_Buffers`` and ``_relocate`` ask of a tensor."""
+    _next = 1 << 60
+
+    def __init__(self, nbytes):
+        self.nbytes, self.ptr = int(nbytes), _Region._next
+        _Region._next += _r256(self.nbytes) + 256
+
+    def data_ptr(self):
+        return self.ptr
+
+    def numel(self):
+        return self.nbytes
+
+    def element_size(self):
+        return 1
+
+    def is_contiguous(self):
+        return True
+
+
+class _NoOps:
+    """What stands where a VAE program stands in a tiny image: no ops, the named slots only."""
+    ops, keep, labels, zero_state = (), (), (), frozenset()
+
+
+def _build_tiny_vae(pipe, K, B, n_mod, height, width, post, cpred):
+    """The two VAE entries of a tiny configuration: the slots ``mg_tiny_vae_encode`` (K pictures) and ``mg_tiny_vae_decode`` (all
+    K B n_mod members in one call) read and write, and their workspaces -> (encode entry, decode entry, (h, w))."""
+    h, w = pipe.vae.latent_hw((height, width))
+    lib = L.load()
+    need = [lib.mg_tiny_vae_workspace_bytes(0, K, height, width), lib.mg_tiny_vae_workspace_bytes(1, K * B * n_mod, h, w)]
+    if min(need) < 0:
+        L.check(1, "mg_tiny_vae_workspace_bytes", lib)
+    enc = ("vae.encode", _NoOps, {"rgb": _Region(K * 3 * height * width * 4), "latent": _Region(K * 4 * h * w * 4), "ws": _Region(need[0])})
+    dec = ("vae.decode", _NoOps, {"latent": _Region(K * B * n_mod * 4 * h * w * 4), "pred": _Region(K * B * n_mod * cpred * 64 * h * w * 4),
+                                  "ws": _Region(need[1])})
+    return enc, dec, (h, w)
+
+
 def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_program=1):
     """The three programs of one configuration, built (or found) in the modules of ``pipe``, and its 16 ``cfg`` words."""
     K = int(images_per_program)
@@ -111,10 +163,12 @@ def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_
         raise ValueError("export_model_image: intrinsic-image models are exported for one picture per call (images_per_program=1): "
                          "mg_model_predict_iid takes one picture")
     unet, vae = pipe.unet, pipe.vae
-    assert isinstance(unet, UNet2DConditionModelHIP) and isinstance(vae, AutoencoderKLHIP)
+    tiny = isinstance(vae, AutoencoderTinyHIP)   # (no op program: nothing of it to build, host-only or not)
+    assert isinstance(unet, UNet2DConditionModelHIP) and (tiny or isinstance(vae, AutoencoderKLHIP))
     if unet.ws is None:
         unet.dry()
-        vae.dry()
+        if not tiny:
+            vae.dry()
     kind = pipe._kind
     post, cpred = _PRED[kind]
     B, T = int(ensemble_size), int(denoising_steps or pipe.default_denoising_steps)
@@ -124,20 +178,27 @@ def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_
         raise ValueError("export_model_image: model images carry bf16 operands (the C host loads libmarigold_hip.so); "
                          "build the pipeline with compute_dtype=torch.bfloat16")
     unet.set_context(pipe.empty_text_embed)
-    enc_seq, enc_in, enc_out = vae._program("encode", K, height, width)
-    h, w = enc_out.shape[-2:]
+    n_mod = getattr(pipe, "n_targets", 1)
+    if tiny:
+        enc, dec, (h, w) = _build_tiny_vae(pipe, K, B, n_mod, int(height), int(width), post, cpred)
+        out_hw = (8 * h, 8 * w)
+    else:
+        enc_seq, enc_in, enc_out = vae._program("encode", K, height, width)
+        h, w = enc_out.shape[-2:]
     if K == 1:
         den = unet.denoise_program(B, h, w, pipe.scheduler, T, rgb_broadcast=True)
     else:   # the programs of a full group (pipeline._predict_group -> single_infer(..., rgb_members=B))
         den = unet.denoise_program(K * B, h, w, pipe.scheduler, T, rgb_members=B)
-    n_mod = getattr(pipe, "n_targets", 1)
-    dec_seq, dec_in, dec_out = vae._program("decode", K * B * n_mod, h, w, post)
-    progs = [("vae.encode", enc_seq, {"rgb": enc_in, "latent": enc_out}),
+    if not tiny:
+        dec_seq, dec_in, dec_out = vae._program("decode", K * B * n_mod, h, w, post)
+        enc, dec = ("vae.encode", enc_seq, {"rgb": enc_in, "latent": enc_out}), ("vae.decode", dec_seq, {"latent": dec_in, "pred": dec_out})
+        out_hw = dec_out.shape[-2:]
+    progs = [enc,
              ("denoise", den.seq, dict({"rgb_latent": den.rgb_latent, "x": den.x}, **{f"noise{k}": nz for k, nz in enumerate(den.noises)})),
-             ("vae.decode", dec_seq, {"latent": dec_in, "pred": dec_out})]
+             dec]
     sz_op = ctypes.sizeof(L.MgOp)
-    cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, dec_out.shape[-2], dec_out.shape[-1],
-           K if K > 1 else 0] + [0] * 2
+    cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, out_hw[0], out_hw[1],
+           K if K > 1 else 0, VAE_TINY if tiny else VAE_KL, 0]
     return progs, [int(c) for c in cfg]
 
 
@@ -146,12 +207,19 @@ def _plan(pipe, progs, cache_kind=KIND_DATA):
     these programs use, and what the programs hold themselves (zeroed state, constants, input / output slots)."""
     bufs = _Buffers()
     for mod in (pipe.unet, pipe.vae):
+        if isinstance(mod, AutoencoderTinyHIP):   # its weights as mg_tiny_vae lays them out, packed on the host; no pool of its own
+            for t in mod.host_pack()[1]:
+                bufs.add(t, cache_kind)
+            continue
         for v in mod.ws.cache.values():
             for t in _tensors(v):
                 bufs.add(t, cache_kind)
         for t in mod.pool.all:
             bufs.add(t, KIND_SCRATCH)
     for _, seq, io in progs:
+        for t in io.values():
+            if isinstance(t, _Region):
+                bufs.add(t, KIND_SCRATCH)
         for t in seq.keep:
             # zero-initialised state the kernels rely on (V^T pad columns, tickets, flash workspace): tagged by the builder
             # (Builder.zeros_persistent -> OpSeq.zero_state); everything else held by the program is a constant or an input /
@@ -258,7 +326,8 @@ def _describe(path, total, bufs, ptab, cfg):
                 steps=cfg[5], pred_channels=cfg[6], step_noises=cfg[8], images_per_program=cfg[13] or 1, cfg16=list(cfg), arena=arena)
 
 
-def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=None, width=None, denoising_steps=None, images_per_program=1):
+def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=None, width=None, denoising_steps=None, images_per_program=1,
+                       tiny_vae=False):
     """Write the model image of ``pipe`` for images of ``height`` x ``width`` (the size fed to the VAE: after the pipeline's
     ``processing_res`` resize), ``ensemble_size`` members per picture and ``denoising_steps`` scheduler steps.  Works with the
     modules on the GPU (``pipe.to("cuda")``) or, without one, in the host-only mode.  Returns a dict describing the image.
@@ -271,16 +340,35 @@ def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=N
     with a configuration table and one buffer table, the modules' packed weights stored once (kind ``KIND_SHARED``) and each
     configuration's own constants, zeroed state and scratch tagged with its index.  ``mg_model_select`` picks the configuration a
     loaded image runs.  The dict returned then holds ``configs`` (one dict as above per entry), ``shared_bytes`` and
-    ``scratch_bytes`` (the scratch region: the largest configuration's, not the sum)."""
-    if not isinstance(pipe.vae, AutoencoderKLHIP):
+    ``scratch_bytes`` (the scratch region: the largest configuration's, not the sum).
+
+    ``tiny_vae=True``: the pipeline's VAE is an ``AutoencoderTinyHIP`` (``pipe.set_vae(load_tiny_vae(...))``) and the image runs it:
+    ``mg_tiny_vae_encode`` / ``mg_tiny_vae_decode`` where an AutoencoderKL image runs its encode and decode programs, all members of a
+    call in one decode.  Such an image is a NEW FILE VERSION (3, for one configuration or several, in the layout of version 2 with the
+    members of ``struct mg_tiny_vae`` as one more table; ``cfg[14]`` = 1, the latent size ``cfg[3:5]`` by the tiny encoder's ceiling
+    rule): no library built before the version existed can read it, which is why it is written on request only.  Without the
+    keyword a pipeline with a tiny VAE is refused as before, and an AutoencoderKL pipeline writes the version-1 / version-2 bytes it
+    always wrote.  One image has one VAE; the dict returned for one configuration is that of a version-1 export plus ``shared_bytes``
+    (``arena``: "shared" lies in the allocation replicas share, "private" + "scratch" are ``mg_model_device_bytes``)."""
+    if tiny_vae and not isinstance(pipe.vae, AutoencoderTinyHIP):
+        raise ValueError(f"export_model_image: tiny_vae=True takes a pipeline whose VAE is an AutoencoderTinyHIP; this pipeline's is a "
+                         f"{type(pipe.vae).__name__}" + (" (an AutoencoderKLHIP is exported with tiny_vae=False, the default)"
+                                                         if isinstance(pipe.vae, AutoencoderKLHIP) else ""))
+    if not tiny_vae and not isinstance(pipe.vae, AutoencoderKLHIP):
         raise ValueError(f"export_model_image: model images carry an AutoencoderKL as op programs; this pipeline's VAE is a "
-                         f"{type(pipe.vae).__name__} (set_vae the checkpoint's AutoencoderKL back to export)")
+                         f"{type(pipe.vae).__name__} (set_vae the checkpoint's AutoencoderKL back to export" +
+                         (", or pass tiny_vae=True for a version-3 image that runs the tiny autoencoder)"
+                          if isinstance(pipe.vae, AutoencoderTinyHIP) else ")"))
     if configs is not None:
         if any(v is not None for v in (ensemble_size, height, width, denoising_steps)) or images_per_program != 1:
             raise ValueError("export_model_image: pass either configs=[...] or the keywords of one configuration, not both")
-        return _export_configs(pipe, path, list(configs))
+        return _export_configs(pipe, path, list(configs), tiny_vae)
     if ensemble_size is None or height is None or width is None:
         raise TypeError("export_model_image: ensemble_size, height and width are required (or configs=[...])")
+    if tiny_vae:   # one configuration in the layout of several: the description of that one
+        whole = _export_configs(pipe, path, [dict(ensemble_size=ensemble_size, height=height, width=width, denoising_steps=denoising_steps,
+                                                  images_per_program=images_per_program)], True)
+        return dict(whole["configs"][0], buffers=whole["buffers"], shared_bytes=whole["shared_bytes"])
     progs, cfg = _build(pipe, ensemble_size, height, width, denoising_steps, images_per_program)
     bufs = _plan(pipe, progs)
     with open(path, "wb") as f:
@@ -303,7 +391,7 @@ def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=N
     return _describe(path, total, _plan(pipe, progs, KIND_SHARED), ptab, cfg)
 
 
-def _export_configs(pipe, path, configs):
+def _export_configs(pipe, path, configs, tiny=False):
     if not configs:
         raise ValueError("export_model_image: configs is empty")
     seen, built = set(), []
@@ -347,10 +435,19 @@ def _export_configs(pipe, path, configs):
                 scratch += _r256(it[1] - it[0])
         scratch_region = max(scratch_region, scratch)
         per_cfg.append(_relocate(progs, bufs, index))
+    members = b""
+    if tiny:   # the members of struct mg_tiny_vae in the struct's order, each (shared buffer, byte offset); a NULL member: absent
+        net = pipe.vae.host_pack()[0]
+        for ptr in (ctypes.c_uint64 * (ctypes.sizeof(net) // 8)).from_buffer_copy(bytes(net)):
+            hit = plans[0].find(ptr) if ptr else None
+            assert hit is not None or not ptr, "model image: a member of the tiny VAE lies outside its packed tensors"
+            it = plans[0].items[hit[0]] if ptr else None
+            members += struct.pack(TINY_MEMBER, shared[it[0], it[1]][0], 0, hit[1]) if ptr else struct.pack(TINY_MEMBER, TINY_ABSENT, 0, 0)
     prog_sz = struct.calcsize(PROG) + 4 + MAXSLOT * struct.calcsize(SLOT)
     with open(path, "wb") as f:
         # ---- layout: header, version-2 words, configuration table (cfg[16] + three programs each), buffer table, blobs
-        table_end = struct.calcsize(HDR) + struct.calcsize(V2) + len(built) * (64 + 3 * prog_sz) + len(table) * struct.calcsize(BUF)
+        # (version 3: the table of the tiny VAE's members behind the buffer table)
+        table_end = struct.calcsize(HDR) + struct.calcsize(V2) + len(built) * (64 + 3 * prog_sz) + len(table) * struct.calcsize(BUF) + len(members)
         f.write(b"\0" * table_end)
         rows = []
         for (nbytes, kind, ci, what) in table:
@@ -358,13 +455,14 @@ def _export_configs(pipe, path, configs):
         offs = [_write_blobs(f, ops_all, relocs_all) for (_ptab, relocs_all, ops_all) in per_cfg]
         total = f.tell()
         f.seek(0)
-        f.write(struct.pack(HDR, MAGIC, VERSION_CONFIGS, L.ABI_VERSION, len(table), 3 * len(built), *built[0][1]))
+        f.write(struct.pack(HDR, MAGIC, VERSION_TINY if tiny else VERSION_CONFIGS, L.ABI_VERSION, len(table), 3 * len(built), *built[0][1]))
         f.write(struct.pack(V2, len(built), 0, scratch_region))
         for (_progs, cfg), (ptab, relocs_all, _ops), (ops_off, rel_off) in zip(built, per_cfg, offs):
             f.write(struct.pack("<16I", *cfg))
             _write_programs(f, ptab, ops_off, rel_off, relocs_all)
         for row in rows:
             f.write(struct.pack(BUF, *row))
+        f.write(members)
         assert f.tell() == table_end
     described = [_describe(path, total, bufs, ptab, cfg) for bufs, (_p, cfg), (ptab, _r, _o) in zip(plans, built, per_cfg)]
     return dict(path=path, file_bytes=total, buffers=len(table), configs=described,

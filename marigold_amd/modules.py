@@ -293,6 +293,7 @@ class AutoencoderTinyHIP(_EngineModule):
         self.sd = state_dict
         self.config = config
         self._net = None
+        self._host = None
         self._buffers = {}
 
     def latent_hw(self, hw):
@@ -348,6 +349,13 @@ class AutoencoderTinyHIP(_EngineModule):
         self.pool = E.Pool(self.device)
         self._buffers = {}
         return self
+
+    def host_pack(self):
+        """``_pack`` into host tensors -> (struct of HOST addresses, the tensors they point into), packed once and kept: what
+        ``export_model_image(tiny_vae=True)`` writes, on a host without a GPU too.  ``.to(device)`` packs for itself, as before."""
+        if self._host is None:
+            self._host = self._pack(torch.device("cpu"))
+        return self._host
 
     def dry(self):
         raise RuntimeError("AutoencoderTinyHIP has no op program to validate: its C calls check their arguments themselves")
