@@ -1257,6 +1257,48 @@ int mg_ens_align_minimize(const mg_op* reg_op, void* stream, int E, int affine, 
                           const double* C, float* st_host, const float* mm_host, double* x, double gtol, int maxiter,
                           double* fval, int* nit, int* nfev, int* status);
 
+/* TILED predictions of a large picture (marigold_amd/tiles.py, pipe.predict_tiled): the picture is cut into overlapping
+ * tiles of one size on a grid, every tile is predicted on its own, and the tiles are stitched on the device - depth tiles are first
+ * fitted, scale and shift, to a low-resolution prediction of the whole picture (the guide), then every kind is blended with feathered
+ * weights.  Plain C calls on device pointers, no op kind.  Every argument check comes before any GPU work and every message starts with
+ * the function's name; nothing synchronises.  Lengths, tile extents and starts are in pixels of the working canvas Hw x Ww.
+ *  The GRID: ny starts along y and nx along x (host arrays, 1 <= ny, nx <= MG_TILE_MAX_PER_AXIS; they travel as kernel arguments), tile
+ *  i = iy * nx + ix (row-major) has its corner at (ystarts[iy], xstarts[ix]) and the extent th x tw.  Tiles are stored one after the
+ *  other, fp32: [n][th][tw] (fit), [n][C][th][tw] (blend), 16-byte aligned.  th, tw, Hw, Ww are multiples of 8; every tile lies inside
+ *  the canvas.
+ *  mg_tile_plan: the starts along ONE axis - picture length L, tile length T, minimum overlap O, all multiples of 8.  L <= T: one
+ *    tile at 0 (of extent L).  Else n = ceil((L - O) / (T - O)) tiles of extent T, start_i = 8 floor(i (L - T) / (n - 1) / 8) for
+ *    i < n - 1 and start_{n-1} = L - T: consecutive tiles overlap by at least O, and THREE tiles may cover one coordinate (L = 120,
+ *    T = 64, O = 16: 0, 24, 56).  Returns n and writes starts[0 .. n); -1 with mg_last_error for a length below 8 or no multiple of 8,
+ *    O < 8, O > T / 2, n > MG_TILE_MAX_PER_AXIS, n > cap, a null `starts`.  Host only.
+ *  mg_tiles_workspace_bytes: what mg_tile_fit needs for n tiles of th x tw (-1 with mg_last_error for a refused shape).
+ *  mg_tile_fit (depth): per tile the (s, t) that minimise the unweighted sum over its pixels p of (s d(p) + t - G(p))^2, where G is the
+ *    guide [hg][wg] sampled bilinearly at p's canvas position - align_corners = False with edge clamp, F.interpolate(guide, (Hw, Ww),
+ *    mode="bilinear") - and only pixels where d and G are both finite count.  Sampling and the five sums N, Sd, Sg, Sdd, Sdg are fp64:
+ *    chunks of MG_TILE_FIT_CHUNK pixels, lanes -> wave shuffle -> LDS -> one partial per chunk in `ws`, then a second launch adds the
+ *    partials in a fixed order (a wave per tile) and solves s = (N Sdg - Sd Sg) / (N Sdd - Sd^2), t = (Sg - s Sd) / N.  No atomics:
+ *    two runs give the same bits.  A tile is DEGENERATE when N < 2, when N Sdd - Sd^2 <= 1e-12 N^2 (a constant tile) or when s <= 0: it
+ *    gets s = 0, t = Sg / N (t = 0 when N = 0) and flags[i] = 1, else flags[i] = 0.  coef [n][2] fp64 (s, t), flags [n] int32, ws
+ *    16-byte aligned.
+ *  mg_tile_blend: out(p) = sum_i w_i(p) v_i(p) / sum_i w_i(p) over the tiles covering p in row-major order, per channel (C = 1 depth,
+ *    3 normals), v_i = fma(s_i, d_i, t_i) with (s_i, t_i) = coef[i] rounded to fp32, or v_i = d_i when coef is NULL.  w_i = wy wx; per
+ *    axis, with u the coordinate inside the tile, T its extent and O the axis' overlap: min(lo, hi), lo = min(1, (u + 0.5) / O) where
+ *    the tile has a neighbour before it and 1 at the canvas border, hi = min(1, (T - u - 0.5) / O) likewise behind it.  Every weight is
+ *    positive (0.5 / O at a tile's edge), so any number of covering tiles may meet and the result is continuous across seams.  fp32, in
+ *    this order: num = fma(w, v, num), den = den + w, out = num / den (IEEE division).  normalize = 1 (C = 3 only): the blended vector
+ *    is divided by max(sqrt(x^2 + y^2 + z^2), 1e-6).  NaN and infinities propagate.  out [C][Hw][Ww] fp32, 16-byte aligned; four
+ *    consecutive x per lane, float4 loads and stores.  The grid must cover the canvas - first start 0, last start + extent = the
+ *    length, strictly ascending multiples of 8, consecutive tiles overlapping by at least O (oy along y, ox along x; >= 8, a multiple of 8,
+ *    at most half the extent on an axis with several tiles). */
+#define MG_TILE_MAX_PER_AXIS 32
+#define MG_TILE_FIT_CHUNK 4096
+int mg_tile_plan(int L, int T, int O, int* starts, int cap);
+long long mg_tiles_workspace_bytes(int n, int th, int tw);
+int mg_tile_fit(const float* tiles, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx, int Hw, int Ww,
+                const float* guide, int hg, int wg, double* coef, int* flags, void* ws, long long ws_bytes, void* stream);
+int mg_tile_blend(const float* tiles, int C, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx, int Hw, int Ww,
+                  int oy, int ox, const double* coef_or_null, int normalize, float* out, void* stream);
+
 /* Shader clock under matrix-core load, for bench.py's calibration block (the sysfs sensors do not answer on every box): one
  * workgroup per CU (one wave per SIMD) runs a fixed chain of v_mfma_f32_32x32x16_bf16 on random (zero_operands = 0) or zero
  * operands for ~2 ms and times it with s_memtime (shader cycles) against s_memrealtime (100 MHz).  mhz = mean over the

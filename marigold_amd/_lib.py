@@ -217,6 +217,7 @@ EXPORTS = [
     "mg_latent_carry", "mg_model_seq_reset", "mg_model_predict_next",
     "mg_tiny_vae_workspace_bytes", "mg_tiny_vae_encode", "mg_tiny_vae_decode", "mg_tiny_conv3x3",
     "mg_model_scratch_fill",
+    "mg_tile_plan", "mg_tiles_workspace_bytes", "mg_tile_fit", "mg_tile_blend",
 ]
 
 
@@ -247,6 +248,7 @@ class MgLpipsNet(ctypes.Structure):
     _fields_ = [("conv_w", ctypes.c_void_p * 5), ("conv_b", ctypes.c_void_p * 5), ("lin_w", ctypes.c_void_p * 5)]
 
 
+TILE_MAX_PER_AXIS = 32   # MG_TILE_MAX_PER_AXIS
 TINY_VAE_LAYERS = 33   # MG_TINY_VAE_LAYERS: the 64 -> 64 layers of either half
 
 
@@ -361,6 +363,14 @@ def load(f16=False):
         [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgPredictOpts), ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 6
     lib.mg_latent_carry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]
     lib.mg_model_seq_reset.argtypes = [ctypes.c_void_p]
+    lib.mg_tile_plan.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    lib.mg_tiles_workspace_bytes.argtypes = [ctypes.c_int] * 3
+    lib.mg_tiles_workspace_bytes.restype = ctypes.c_longlong
+    _grid = [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int]   # ystarts, ny, xstarts, nx, Hw, Ww
+    lib.mg_tile_fit.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _grid + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + \
+        [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_tile_blend.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + _grid + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                                                 ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_model_scratch_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]

@@ -66,7 +66,33 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                         "which a C host reproduces (mg_model_predict_next).")
     p.add_argument("--carry_strength", type=float, default=0.1,
                    help="--sequence: the weight of the previous frame's latent in a frame's initial latents; the noise gets 1 minus it.")
+    if kind != "iid":
+        p.add_argument("--tile_size", type=int, default=0,
+                       help="Predict every picture from overlapping square tiles of this size (a multiple of 8; 768 is the training size), "
+                            "stitched on the GPU against a prediction of the whole picture at --processing_res (predict_tiled): for pictures "
+                            "far larger than the processing resolution. 0 = no tiles. With --seed s the guide draws its noise from the "
+                            "engine's own generator seeded s and tile i from s + 1 + i.")
+        p.add_argument("--tile_overlap", type=int, default=0,
+                       help="--tile_size: the minimum overlap of neighbouring tiles (a multiple of 8, at most half a tile); 0 = a quarter of the tile.")
+        p.add_argument("--tiled_res", type=int, default=0,
+                       help="--tile_size: the picture is first resized so that its longer edge has this length; 0 = tiles at the input resolution.")
     return p
+
+
+def check_tile_args(args):
+    """The tile flags against the rest of the command line, before anything is loaded."""
+    if not getattr(args, "tile_size", 0):
+        if getattr(args, "tile_overlap", 0) or getattr(args, "tiled_res", 0):
+            raise ValueError("--tile_overlap and --tiled_res need --tile_size")
+        return
+    if args.sequence:
+        raise ValueError("--tile_size cannot be combined with --sequence: a sequence carries one latent per frame, tiles have many")
+    if args.images_per_program > 1:
+        raise ValueError("--tile_size runs its tiles as the images of a program: --images_per_program must be 1")
+    if args.tile_size < 16 or args.tile_size % 8 or args.tile_overlap < 0 or args.tile_overlap % 8 or 2 * args.tile_overlap > args.tile_size \
+            or args.tiled_res < 0:
+        raise ValueError(f"--tile_size {args.tile_size} / --tile_overlap {args.tile_overlap} / --tiled_res {args.tiled_res}: sizes are "
+                         "multiples of 8, the tile 16 at least, the overlap at most half a tile")
 
 
 def list_images(folder):
@@ -145,6 +171,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     import torch
     logging.basicConfig(level=logging.INFO)
     args = build_parser(kind).parse_args(argv)
+    check_tile_args(args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -210,6 +237,20 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         outs = pipeline.map_video((Image.open(f) for f in files), strength=args.carry_strength, in_flight=args.maps_in_flight or None,
                                   generators=seeds, **kw)
         for rgb_path, out in zip(files, outs):
+            save_prediction(kind, dirs, rgb_path, out)
+    elif getattr(args, "tile_size", 0):
+        # large pictures: each from overlapping tiles, stitched on the device; --processing_res is the guide's resolution
+        if not hasattr(pipeline, "predict_tiled"):
+            raise RuntimeError("--tile_size needs a pipeline with predict_tiled")
+        from .noise import NativeNoise
+        tile_kw = {k: v for k, v in kw.items() if k != "processing_res"}
+        overlap = args.tile_overlap or max(8, args.tile_size // 4 // 8 * 8)
+        for rgb_path in files:
+            out = pipeline.predict_tiled(Image.open(rgb_path), tile_size=args.tile_size, tile_overlap=overlap, tiled_res=args.tiled_res,
+                                         guide_res=args.processing_res, in_flight=args.maps_in_flight or None,
+                                         generator=None if args.seed is None else NativeNoise(args.seed), **tile_kw)
+            if getattr(out, "degenerate_tiles", None):
+                logging.warning(f"{rgb_path}: {out.degenerate_tiles} tile(s) could not be fitted to the guide and carry its mean")
             save_prediction(kind, dirs, rgb_path, out)
     elif hasattr(pipeline, "map_images"):
         # the engine's multi-image form: up to --maps_in_flight images on the GPU at a time, outputs in input order

@@ -13,7 +13,9 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
 * ``generator=NativeNoise(seed)`` (extension) draws the noise with the library's own generator (noise.py), as a C host does;
 * ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program;
 * ``sequence=SequenceState()`` / ``map_video`` (extension) carry each frame's denoised latent into the next frame's initial noise
-  (DESIGN.md 6c).
+  (DESIGN.md 6c);
+* ``predict_tiled`` (extension) cuts a large picture into overlapping tiles of the training size, predicts them through
+  ``map_images`` and stitches them on the device (tiles.py).
 """
 import contextlib
 import copy
@@ -30,6 +32,7 @@ from PIL import Image
 from . import _lib as L
 from . import dist as mdist
 from . import ops as O
+from . import tiles as tiling
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .lanes import Turnstile as _Turnstile, run_lanes
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
@@ -44,10 +47,12 @@ from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_map
 @dataclass
 class MarigoldDepthOutput:
     """depth_np [H,W] in [0,1]; depth_colored PIL RGB | None; uncertainty [H,W] | None
-    (reference :60-75)."""
+    (reference :60-75).  ``degenerate_tiles`` (extension): None, or - from ``predict_tiled`` - how many tiles could not be fitted to
+    the guide (constant, no valid pixel, a slope <= 0) and were replaced by the guide's mean over them."""
     depth_np: np.ndarray
     depth_colored: Union[None, Image.Image]
     uncertainty: Union[None, np.ndarray]
+    degenerate_tiles: Optional[int] = None
 
 
 @dataclass
@@ -490,6 +495,133 @@ class _MarigoldPipelineBase:
         finally:
             leave()
 
+    # ---- large pictures: tiles ---------------------------------------------------------------
+    # A picture far above the training size is cut into overlapping tiles of that size on a grid (tiles.plan); the tiles are
+    # same-size images, i.e. the workload of map_images(images_per_program=k) and its lanes.  Their predictions stay on the device
+    # (``_device_out``), depth tiles are fitted - scale and shift each - to one ordinary low-resolution prediction of the whole picture
+    # (tiles.fit), and the tiles are blended with feathered weights over the full-size canvas (tiles.blend).  DESIGN.md 6e.
+    _device_out = False            # True only on the view predict_tiled predicts on: _finish stops in front of its read-back tail
+
+    def _finish_device(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **_):
+        """``_finish`` without its read-back tail: the members of one image -> its clipped prediction on the device, [H,W] or
+        [3,H,W] (what ``_finish`` does up to there, then the clip its tail applies on the host)."""
+        if ensemble_size > 1:
+            final_pred, _ = self._ensemble(target_preds, ensemble_kwargs)
+        else:
+            final_pred = target_preds
+        if match_input_res:
+            final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
+        return final_pred.squeeze().float().clamp(*self._clip_range)
+
+    def _finish_or_keep(self, *args, **kw):
+        """``_finish``; on the view ``predict_tiled`` predicts on, ``_finish_device``."""
+        return self._finish_device(*args, **kw) if self._device_out else self._finish(*args, **kw)
+
+    @torch.no_grad()
+    def predict_tiled(self, image, tile_size=768, tile_overlap=192, tiled_res: int = 0, guide_res: Optional[int] = None,
+                      tiles_per_program: Optional[int] = None, in_flight: Optional[int] = None, generator=None, tile_generators=None,
+                      **call_kwargs):
+        """The prediction of a LARGE picture from overlapping tiles, stitched on the device -> the output ``__call__`` returns.
+
+        The working size is the input's - or ``max_res_size(hw, tiled_res)`` when ``tiled_res`` > 0 - with each side floored to a
+        multiple of 8; the picture is resampled to it (``resample_method``) where it differs.  ``tiles.plan(working size, tile_size,
+        tile_overlap)`` places the tiles (``tile_size`` / ``tile_overlap``: an int or (h, w), multiples of 8; the overlap is the
+        minimum, at most half a tile).  A plan of ONE tile returns exactly ``pipe(image, processing_res=tiled_res,
+        generator=generator, **call_kwargs)`` and runs no guide.  Otherwise:
+
+        * depth only - the GUIDE: the ordinary prediction ``pipe(image, processing_res=guide_res, match_input_res=False,
+          generator=generator, ...)`` (``guide_res`` None: the pipeline's default processing resolution), ensembled like any call;
+        * the TILES: crops of the working picture, taken on the device (an 8-bit picture is cropped as uint8 CUDA tensors), go through
+          ``map_images(crops, images_per_program=tiles_per_program, in_flight=in_flight, generators=..., processing_res=0,
+          match_input_res=False, ...)``; ``tiles_per_program`` defaults to min(number of tiles, 8); with ``ensemble_size`` > 1 every
+          tile is ensembled on its own; no prediction is read back;
+        * the STITCH: depth - ``tiles.fit`` against the guide, then ``tiles.blend`` with the fitted scale and shift of every tile;
+          normals - ``tiles.blend(normalize=True)``; then ``__call__``'s tail: the resize to the input size when ``match_input_res``,
+          the clip, the coloured depth / normals picture.
+
+        Noise.  Tile i (row-major) draws from ``tile_generators[i]`` when given.  Else with ``generator=NativeNoise(seed)`` the guide
+        draws from ``generator`` and tile i from ``NativeNoise((seed + 1 + i) mod 2^64)``: the result does not depend on
+        ``in_flight`` or ``tiles_per_program`` beyond the arithmetic of the batch.  A ``torch.Generator`` is consumed by the guide
+        first and then tile by tile in row-major order, with ONE program in flight (``in_flight`` is taken as 1).  ``generator=None``:
+        randomised, as in ``__call__``.
+
+        ``uncertainty`` is None in a tiled output, also for ``ensemble_size`` > 1: the tiles' uncertainties are not stitched.  A depth
+        output carries ``degenerate_tiles``, the number of tiles ``tiles.fit`` flagged.  Refused: the intrinsic-image pipeline,
+        member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program`` and ``processing_res`` (``tiled_res`` and
+        ``guide_res`` take its place)."""
+        if self._kind not in ("depth", "normals"):
+            raise ValueError("predict_tiled: the intrinsic-image pipeline is not supported (depth and normals only)")
+        if self._member_parallel or self._sharded():
+            raise ValueError("predict_tiled is not available on a member-parallel pipeline")
+        for name in ("init_latents", "sequence", "images_per_program", "processing_res"):
+            if call_kwargs.get(name) is not None:
+                raise ValueError(f"predict_tiled: {name} cannot be combined with tiles")
+            call_kwargs.pop(name, None)
+        unknown = set(call_kwargs) - set(self._call_args) - set(self._finish_args)
+        if unknown:
+            raise TypeError(f"predict_tiled() got unexpected keyword arguments {sorted(unknown)}")
+        tiled_res = int(tiled_res)
+        if tiled_res < 0:
+            raise ValueError(f"predict_tiled: tiled_res must be >= 0 (got {tiled_res})")
+        if isinstance(image, Image.Image):
+            hw = (image.height, image.width)
+        elif isinstance(image, torch.Tensor) and image.dim() == 4 and tuple(image.shape[:2]) == (1, 3):
+            hw = tuple(int(d) for d in image.shape[-2:])
+        else:
+            raise TypeError(f"predict_tiled: the image must be a PIL image or a [1, 3, H, W] tensor (got {type(image).__name__})")
+        work_hw = tuple(d // 8 * 8 for d in (max_res_size(hw, tiled_res) if tiled_res > 0 else hw))
+        plan = tiling.plan(work_hw, tile_size, tile_overlap)   # (refuses bad sizes: nothing has been launched)
+        n = len(plan.origins)
+        if tile_generators is not None:
+            tile_generators = list(tile_generators)
+            if len(tile_generators) != n:
+                raise ValueError(f"predict_tiled: {len(tile_generators)} tile_generators for {n} tiles")
+        if n == 1:
+            return self(image, processing_res=tiled_res, generator=generator, **call_kwargs)
+        if tiles_per_program is None:
+            tiles_per_program = min(n, 8)
+        if tile_generators is None and generator is not None:
+            if isinstance(generator, NativeNoise):
+                tile_generators = [NativeNoise((generator.seed + 1 + i) & ((1 << 64) - 1)) for i in range(n)]
+            else:
+                tile_generators, in_flight = [generator] * n, 1   # one stream of draws: guide, then tile by tile
+        match_input_res = call_kwargs.pop("match_input_res", True)
+        resample = get_tv_resample_method(call_kwargs.get("resample_method", "bilinear"))
+        finish = {a: call_kwargs.pop(a) for a in self._finish_args if a in call_kwargs}
+        if self.empty_text_embed is None:
+            self.encode_empty_text()
+        dev = copy.copy(self)   # shares engines, scheduler and lanes with this pipeline; its calls stop in front of the read-back
+        dev._device_out = True
+
+        # the working picture on the device, [1,3,H,W] in the input's number format
+        rgb = pil_to_tensor(image.convert("RGB")).unsqueeze(0) if isinstance(image, Image.Image) else image
+        input_size = rgb.shape
+        rgb = rgb.to(self.device)
+        if work_hw != hw:
+            rgb = resize(rgb, work_hw, interpolation=resample, antialias=True)
+        th, tw = plan.tile_hw
+        crops = [rgb[..., y0:y0 + th, x0:x0 + tw].contiguous() for y0, x0 in plan.origins]
+
+        coef = flags = None
+        if self._kind == "depth":
+            guide = dev(image, processing_res=guide_res, match_input_res=False, generator=generator, **call_kwargs)   # [hg,wg]
+        preds = list(dev.map_images(crops, in_flight=in_flight, generators=tile_generators, images_per_program=tiles_per_program,
+                                    processing_res=0, match_input_res=False, **call_kwargs))
+        preds = torch.stack(preds).reshape(n, self._pred_channels, th, tw)
+        overlap = tiling._pair(tile_overlap, "tile_overlap")
+        if self._kind == "depth":
+            coef, flags = tiling.fit(preds[:, 0], plan.origins, guide, work_hw)
+            final_pred = tiling.blend(preds, plan.origins, work_hw, overlap, coef=coef)
+        else:
+            final_pred = tiling.blend(preds, plan.origins, work_hw, overlap, normalize=True)
+        final_pred = final_pred.unsqueeze(0)
+        if match_input_res:
+            final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
+        out = self._tail(final_pred, **finish)
+        if flags is not None:
+            out.degenerate_tiles = int(flags.sum().item())
+        return out
+
     # ---- reference methods -------------------------------------------------------------------
     def _check_inference_step(self, n_step: int) -> None:
         assert n_step >= 1
@@ -681,7 +813,7 @@ class _MarigoldPipelineBase:
                                     [None] * len(images) if generators is None else list(generators))
         E = ensemble_size
         finish = {a: kw[a] for a in self._finish_args if a in kw}
-        return [self._finish(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
+        return [self._finish_or_keep(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
                              kw.get("ensemble_kwargs"), **finish) for j, (_, input_size) in enumerate(prepared)]
 
     _finish_args = ()
@@ -793,8 +925,8 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents, carry)
-        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
-                            color_map=color_map)
+        return self._finish_or_keep(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
+                                    color_map=color_map)
 
     _finish_args = ("color_map",)
 
@@ -811,23 +943,37 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
             final_pred, pred_uncert = target_preds, None
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        colored_dev = None
-        if color_map is not None and final_pred.is_cuda:
-            # colour table look-up on the device (clip(0, 1) is part of the kernel); the host gets a uint8 HWC image
-            colored_dev = colorize_depth_device(final_pred.squeeze().float(), 0.0, 1.0, cmap=color_map)
-        final_pred = final_pred.squeeze().cpu().numpy()
-        if pred_uncert is not None:
-            pred_uncert = pred_uncert.squeeze().cpu().numpy()
-        final_pred = final_pred.clip(0, 1)
-        if colored_dev is not None:
-            depth_colored_img = Image.fromarray(colored_dev.cpu().numpy())
-        elif color_map is not None:
-            colored = colorize_depth_maps(final_pred, 0, 1, cmap=color_map).squeeze()
-            colored = (colored * 255).astype(np.uint8)
-            depth_colored_img = Image.fromarray(chw2hwc(colored))
-        else:
-            depth_colored_img = None
-        return MarigoldDepthOutput(depth_np=final_pred, depth_colored=depth_colored_img, uncertainty=pred_uncert)
+        return _depth_tail(final_pred, pred_uncert, color_map)
+
+    _clip_range = (0, 1)
+
+    def _ensemble(self, target_preds, ensemble_kwargs):
+        return ensemble_depth(target_preds, scale_invariant=self.scale_invariant, shift_invariant=self.shift_invariant,
+                              **(ensemble_kwargs or {}))
+
+    def _tail(self, final_pred, color_map="Spectral") -> MarigoldDepthOutput:
+        return _depth_tail(final_pred, None, color_map)
+
+
+def _depth_tail(final_pred, pred_uncert, color_map) -> MarigoldDepthOutput:
+    """The tail of the depth pipeline's ``_finish``: the coloured picture, the arrays to the host, the clip."""
+    colored_dev = None
+    if color_map is not None and final_pred.is_cuda:
+        # colour table look-up on the device (clip(0, 1) is part of the kernel); the host gets a uint8 HWC image
+        colored_dev = colorize_depth_device(final_pred.squeeze().float(), 0.0, 1.0, cmap=color_map)
+    final_pred = final_pred.squeeze().cpu().numpy()
+    if pred_uncert is not None:
+        pred_uncert = pred_uncert.squeeze().cpu().numpy()
+    final_pred = final_pred.clip(0, 1)
+    if colored_dev is not None:
+        depth_colored_img = Image.fromarray(colored_dev.cpu().numpy())
+    elif color_map is not None:
+        colored = colorize_depth_maps(final_pred, 0, 1, cmap=color_map).squeeze()
+        colored = (colored * 255).astype(np.uint8)
+        depth_colored_img = Image.fromarray(chw2hwc(colored))
+    else:
+        depth_colored_img = None
+    return MarigoldDepthOutput(depth_np=final_pred, depth_colored=depth_colored_img, uncertainty=pred_uncert)
 
 
 class MarigoldNormalsPipeline(_MarigoldPipelineBase):
@@ -871,7 +1017,7 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents, carry)
-        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
+        return self._finish_or_keep(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
 
     def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
                 ensemble_kwargs) -> MarigoldNormalsOutput:
@@ -884,20 +1030,33 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
             final_pred, pred_uncert = target_preds, None
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        img_dev = None
-        if final_pred.is_cuda and self.device_io_stages and final_pred.squeeze().dim() == 3:
-            # the picture on the device (the clip to [-1, 1] is part of the kernel); the host gets the map and a uint8 HWC image
-            img_dev = normals_visualization_device(final_pred.squeeze().float())
-        final_pred = final_pred.squeeze().cpu().numpy()
-        if pred_uncert is not None:
-            pred_uncert = pred_uncert.squeeze().cpu().numpy()
-        final_pred = final_pred.clip(-1, 1)
-        if img_dev is not None:
-            normals_img = Image.fromarray(img_dev.cpu().numpy())
-        else:
-            normals_img = ((final_pred + 1) * 127.5).astype(np.uint8)
-            normals_img = Image.fromarray(chw2hwc(normals_img))
-        return MarigoldNormalsOutput(normals_np=final_pred, normals_img=normals_img, uncertainty=pred_uncert)
+        return _normals_tail(final_pred, pred_uncert, final_pred.is_cuda and self.device_io_stages)
+
+    _clip_range = (-1, 1)
+
+    def _ensemble(self, target_preds, ensemble_kwargs):
+        return ensemble_normals(target_preds, **(ensemble_kwargs or {}))
+
+    def _tail(self, final_pred) -> MarigoldNormalsOutput:
+        return _normals_tail(final_pred, None, final_pred.is_cuda and self.device_io_stages)
+
+
+def _normals_tail(final_pred, pred_uncert, device_picture) -> MarigoldNormalsOutput:
+    """The tail of the normals pipeline's ``_finish``: the picture, the arrays to the host, the clip."""
+    img_dev = None
+    if device_picture and final_pred.squeeze().dim() == 3:
+        # the picture on the device (the clip to [-1, 1] is part of the kernel); the host gets the map and a uint8 HWC image
+        img_dev = normals_visualization_device(final_pred.squeeze().float())
+    final_pred = final_pred.squeeze().cpu().numpy()
+    if pred_uncert is not None:
+        pred_uncert = pred_uncert.squeeze().cpu().numpy()
+    final_pred = final_pred.clip(-1, 1)
+    if img_dev is not None:
+        normals_img = Image.fromarray(img_dev.cpu().numpy())
+    else:
+        normals_img = ((final_pred + 1) * 127.5).astype(np.uint8)
+        normals_img = Image.fromarray(chw2hwc(normals_img))
+    return MarigoldNormalsOutput(normals_np=final_pred, normals_img=normals_img, uncertainty=pred_uncert)
 
 
 # ------------------------------------------------------------------------------------------ IID
