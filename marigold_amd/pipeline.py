@@ -329,52 +329,70 @@ class _MarigoldPipelineBase:
                                  "images_per_program > 1")
             if self._sharded():
                 raise ValueError("map_images: images_per_program > 1 is not available on a member-parallel pipeline")
-        n = self.maps_in_flight_for(k * call_kwargs.get("ensemble_size", 1)) if in_flight is None else int(in_flight)
-        if n < 1:
-            raise ValueError(f"in_flight must be >= 1 (got {in_flight})")
-        if generators is not None and hasattr(images, "__len__") and hasattr(generators, "__len__") and len(images) != len(generators):
-            raise ValueError(f"{len(generators)} generators for {len(images)} images")
-        if hasattr(images, "__len__"):
-            n = min(n, max(1, -(-len(images) // k)))
-        if self.device.type != "cuda":
-            n = 1
-        if n > 1 and call_kwargs.get("generator") is not None:
-            raise ValueError("map_images: pass `generators` (one per image) instead of a shared `generator` when in_flight > 1")
-        return self._map_images(iter(images), None if generators is None else iter(generators), n, call_kwargs, k)
+        n = self._lane_count("map_images", "image", images, generators, in_flight,
+                             functools.partial(self.maps_in_flight_for, k * call_kwargs.get("ensemble_size", 1)), k, call_kwargs)
+        pairs = self._paired("map_images", "image", iter(images), None if generators is None else iter(generators))
 
-    def _processed_size(self, image, processing_res):
-        """(height, width) ``_preprocess`` gives ``image``, without resampling it."""
-        if isinstance(image, Image.Image):
-            hw = (image.height, image.width)
-        elif isinstance(image, torch.Tensor):
-            hw = tuple(image.shape[-2:])
-        else:
-            raise TypeError(f"Unknown input type: {type(image) = }")
-        if processing_res is None:
-            processing_res = self.default_processing_resolution
-        return max_res_size(hw, processing_res) if processing_res > 0 else hw
-
-    def _map_images(self, images, generators, n, call_kwargs, per_program=1):
         def groups():
-            """[(image, generator)]: up to ``per_program`` consecutive images of one processed size; the two iterables advance together"""
+            """[(image, generator)]: up to k consecutive images of one processed size"""
             group, size = [], None
-            for image in images:
-                g = None if generators is None else next(generators, StopIteration)
-                if g is StopIteration:
-                    raise ValueError("map_images: fewer generators than images")
-                image_size = self._processed_size(image, call_kwargs.get("processing_res")) if per_program > 1 else None
+            for image, g in pairs:
+                image_size = self._processed_size(image, call_kwargs.get("processing_res")) if k > 1 else None
                 if group and image_size != size:   # this image opens the next group
                     yield group
                     group = []
                 group.append((image, g))
                 size = image_size
-                if len(group) == per_program:
+                if len(group) == k:
                     yield group
                     group = []
             if group:
                 yield group
 
-        take = functools.partial(next, enumerate(groups()), None)   # -> (index, group) | None; one lane at a time (run_lanes)
+        def run_one(pipe, group, index, turnstile):
+            """-> the outputs of the group's images, in order"""
+            kw = dict(call_kwargs)
+            if len(group) > 1:
+                return pipe._call_group([im for im, _ in group], None if generators is None else [g for _, g in group], kw)
+            image, g = group[0]
+            if generators is not None:
+                kw["generator"] = g
+            if turnstile is not None:
+                pipe._gather_turn = (turnstile, index)   # on this call's view of the lane
+            return [pipe(image, **kw)]
+
+        return self._drive_lanes(groups(), n, self._sharded(), run_one)   # (a turnstile: the gathers, map by map)
+
+    def _lane_count(self, caller, noun, items, generators, in_flight, default, per_lane, call_kwargs):
+        """The checks ``map_images`` and ``map_video`` make of their arguments at the call -> the number of lanes.  ``default()``: the
+        count when the caller names none; ``per_lane``: how many items a lane takes at a time."""
+        n = default() if in_flight is None else int(in_flight)
+        if n < 1:
+            raise ValueError(f"in_flight must be >= 1 (got {in_flight})")
+        if generators is not None and hasattr(items, "__len__") and hasattr(generators, "__len__") and len(items) != len(generators):
+            raise ValueError(f"{len(generators)} generators for {len(items)} {noun}s")
+        if hasattr(items, "__len__"):
+            n = min(n, max(1, -(-len(items) // per_lane)))
+        if self.device.type != "cuda":
+            n = 1
+        if n > 1 and call_kwargs.get("generator") is not None:
+            raise ValueError(f"{caller}: pass `generators` (one per {noun}) instead of a shared `generator` when in_flight > 1")
+        return n
+
+    @staticmethod
+    def _paired(caller, noun, items, generators):
+        """(item, its generator | None) for every item; the two iterators advance together."""
+        for item in items:
+            g = None if generators is None else next(generators, StopIteration)
+            if g is StopIteration:
+                raise ValueError(f"{caller}: fewer generators than {noun}s")
+            yield item, g
+
+    def _drive_lanes(self, groups, n, ordered, run_one):
+        """A generator over the outputs of ``run_one(view, group, k, turnstile)`` for group k = 0, 1 ... of the iterator ``groups``, on
+        ``n`` lanes (``run_lanes``).  ``view``: the pipeline the lane runs on; ``turnstile``: with several lanes and ``ordered``, the
+        ``Turnstile`` a stage of the calls passes in the order of k, else None."""
+        take = functools.partial(next, enumerate(groups), None)   # -> (index, group) | None; one lane at a time (run_lanes)
         views, contexts, leave, turnstile = [self], [contextlib.nullcontext()], lambda: None, None   # one lane: inline, on this very object
         if n > 1:
             if self.empty_text_embed is None:
@@ -382,24 +400,27 @@ class _MarigoldPipelineBase:
             lanes = self._lane_resources(n)
             views = [self._view(e.unet, e.vae) for e, _ in lanes]   # lane 0 too: no lane works on the caller's object
             contexts, leave = self._lane_contexts([stream for _, stream in lanes])
-            turnstile = _Turnstile() if self._sharded() else None
-
-        def run(lane, group, k):
-            """-> the outputs of the group's images, in order"""
-            pipe, kw = views[lane], dict(call_kwargs)
-            if len(group) > 1:
-                return pipe._call_group([im for im, _ in group], None if generators is None else [g for _, g in group], kw)
-            image, g = group[0]
-            if generators is not None:
-                kw["generator"] = g
-            if turnstile is not None:
-                pipe._gather_turn = (turnstile, k)   # on this call's view of the lane
-            return [pipe(image, **kw)]
-
+            turnstile = _Turnstile() if ordered else None
         try:
-            yield from run_lanes(contexts, take, run, turnstile)
+            yield from run_lanes(contexts, take, lambda lane, group, k: run_one(views[lane], group, k, turnstile), turnstile)
         finally:
             leave()
+
+    @staticmethod
+    def _input_hw(image):
+        """(height, width) of a PIL image or an image tensor."""
+        if isinstance(image, Image.Image):
+            return image.height, image.width
+        if isinstance(image, torch.Tensor):
+            return tuple(image.shape[-2:])
+        raise TypeError(f"Unknown input type: {type(image) = }")
+
+    def _processed_size(self, image, processing_res):
+        """(height, width) ``_preprocess`` gives ``image``, without resampling it."""
+        hw = self._input_hw(image)
+        if processing_res is None:
+            processing_res = self.default_processing_resolution
+        return max_res_size(hw, processing_res) if processing_res > 0 else hw
 
     # ---- image sequences ---------------------------------------------------------------------
     # Frame k of a sequence starts from 0.9 noise + 0.1 x (denoised latent of frame k - 1) - the recipe Marigold's authors give for
@@ -444,56 +465,30 @@ class _MarigoldPipelineBase:
         if self._sharded():
             raise ValueError("map_video: a sequence is not available on a member-parallel pipeline")
         state = SequenceState(strength)
-        n = self.frames_in_flight_for(call_kwargs.get("ensemble_size", 1)) if in_flight is None else int(in_flight)
-        if n < 1:
-            raise ValueError(f"in_flight must be >= 1 (got {in_flight})")
-        if generators is not None and hasattr(frames, "__len__") and hasattr(generators, "__len__") and len(frames) != len(generators):
-            raise ValueError(f"{len(generators)} generators for {len(frames)} frames")
-        if hasattr(frames, "__len__"):
-            n = min(n, max(1, len(frames)))
-        if self.device.type != "cuda":
-            n = 1
-        if n > 1 and call_kwargs.get("generator") is not None:
-            raise ValueError("map_video: pass `generators` (one per frame) instead of a shared `generator` when in_flight > 1")
-        return self._map_video(iter(frames), None if generators is None else iter(generators), n, state, call_kwargs)
+        n = self._lane_count("map_video", "frame", frames, generators, in_flight,
+                             functools.partial(self.frames_in_flight_for, call_kwargs.get("ensemble_size", 1)), 1, call_kwargs)
+        pairs = self._paired("map_video", "frame", iter(frames), None if generators is None else iter(generators))
 
-    def _map_video(self, frames, generators, n, state, call_kwargs):
         def items():
-            """[(frame, generator)], one frame each; the two iterables advance together"""
+            """[(frame, generator)], one frame each, all of the first frame's processed size"""
             size = None
-            for k, image in enumerate(frames):
-                g = None if generators is None else next(generators, StopIteration)
-                if g is StopIteration:
-                    raise ValueError("map_video: fewer generators than frames")
+            for k, (image, g) in enumerate(pairs):
                 image_size = self._processed_size(image, call_kwargs.get("processing_res"))
                 if size is not None and image_size != size:
                     raise ValueError(f"map_video: frame {k} has the processed size {image_size}, the sequence began with {size}")
                 size = image_size
                 yield [(image, g)]
 
-        take = functools.partial(next, enumerate(items()), None)
-        views, contexts, leave, turnstile = [self], [contextlib.nullcontext()], lambda: None, None   # one lane: inline, as map_images
-        if n > 1:
-            if self.empty_text_embed is None:
-                self.encode_empty_text()
-            lanes = self._lane_resources(n)
-            views = [self._view(e.unet, e.vae) for e, _ in lanes]
-            contexts, leave = self._lane_contexts([stream for _, stream in lanes])
-            turnstile = _Turnstile()   # the denoise stages, frame by frame
-
-        def run(lane, group, k):
-            pipe, kw = views[lane], dict(call_kwargs)
+        def run_one(pipe, group, index, turnstile):
+            kw = dict(call_kwargs)
             image, g = group[0]
             if generators is not None:
                 kw["generator"] = g
             if turnstile is not None:
-                pipe._sequence_turn = (turnstile, k)   # on this call's view of the lane
+                pipe._sequence_turn = (turnstile, index)   # on this call's view of the lane
             return [pipe(image, sequence=state, **kw)]
 
-        try:
-            yield from run_lanes(contexts, take, run, turnstile)
-        finally:
-            leave()
+        return self._drive_lanes(items(), n, True, run_one)   # (a turnstile: the denoise stages, frame by frame)
 
     # ---- large pictures: tiles ---------------------------------------------------------------
     # A picture far above the training size is cut into overlapping tiles of that size on a grid (tiles.plan); the tiles are
@@ -502,20 +497,23 @@ class _MarigoldPipelineBase:
     # (tiles.fit), and the tiles are blended with feathered weights over the full-size canvas (tiles.blend).  DESIGN.md 6e.
     _device_out = False            # True only on the view predict_tiled predicts on: _finish stops in front of its read-back tail
 
-    def _finish_device(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **_):
-        """``_finish`` without its read-back tail: the members of one image -> its clipped prediction on the device, [H,W] or
-        [3,H,W] (what ``_finish`` does up to there, then the clip its tail applies on the host)."""
+    _clip_range = (0, 1)           # of a finished prediction
+
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **finish):
+        """``__call__``'s tail: the members of one image -> its output (``_tail``: the kind's pictures, read-backs and clip).  On the
+        view ``predict_tiled`` predicts on it stops in front of ``_tail``: -> the clipped prediction on the device, [H,W] or [3,H,W]
+        (the clip is the one ``_tail`` applies on the host)."""
+        if target_preds is None:  # member-parallel non-root rank with a rooted gather
+            return self._empty_output()
         if ensemble_size > 1:
-            final_pred, _ = self._ensemble(target_preds, ensemble_kwargs)
+            final_pred, pred_uncert = self._ensemble(target_preds, ensemble_kwargs)
         else:
-            final_pred = target_preds
+            final_pred, pred_uncert = target_preds, None
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        return final_pred.squeeze().float().clamp(*self._clip_range)
-
-    def _finish_or_keep(self, *args, **kw):
-        """``_finish``; on the view ``predict_tiled`` predicts on, ``_finish_device``."""
-        return self._finish_device(*args, **kw) if self._device_out else self._finish(*args, **kw)
+        if self._device_out:
+            return final_pred.squeeze().float().clamp(*self._clip_range)
+        return self._tail(final_pred, pred_uncert, **finish)
 
     @torch.no_grad()
     def predict_tiled(self, image, tile_size=768, tile_overlap=192, tiled_res: int = 0, guide_res: Optional[int] = None,
@@ -563,12 +561,10 @@ class _MarigoldPipelineBase:
         tiled_res = int(tiled_res)
         if tiled_res < 0:
             raise ValueError(f"predict_tiled: tiled_res must be >= 0 (got {tiled_res})")
-        if isinstance(image, Image.Image):
-            hw = (image.height, image.width)
-        elif isinstance(image, torch.Tensor) and image.dim() == 4 and tuple(image.shape[:2]) == (1, 3):
-            hw = tuple(int(d) for d in image.shape[-2:])
-        else:
+        if not isinstance(image, Image.Image) and \
+                not (isinstance(image, torch.Tensor) and image.dim() == 4 and tuple(image.shape[:2]) == (1, 3)):
             raise TypeError(f"predict_tiled: the image must be a PIL image or a [1, 3, H, W] tensor (got {type(image).__name__})")
+        hw = self._input_hw(image)
         work_hw = tuple(d // 8 * 8 for d in (max_res_size(hw, tiled_res) if tiled_res > 0 else hw))
         plan = tiling.plan(work_hw, tile_size, tile_overlap)   # (refuses bad sizes: nothing has been launched)
         n = len(plan.origins)
@@ -617,7 +613,7 @@ class _MarigoldPipelineBase:
         final_pred = final_pred.unsqueeze(0)
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        out = self._tail(final_pred, **finish)
+        out = self._tail(final_pred, None, **finish)
         if flags is not None:
             out.degenerate_tiles = int(flags.sum().item())
         return out
@@ -698,6 +694,11 @@ class _MarigoldPipelineBase:
             carry[0].keep(prog.x, carry[1], carry[2])
         return self._decode(prog.x)
 
+    def _step_noise_count(self, denoising_steps):
+        """How many per-step noises the scheduler, set to ``denoising_steps`` steps here, has a program draw."""
+        self.scheduler.set_timesteps(denoising_steps)
+        return sum(bool(self.scheduler.needs_noise(i)) for i in range(denoising_steps))
+
     def _predict_members(self, rgb_norm, ensemble_size, denoising_steps, batch_size, generator,
                          init_latents, carry=None):
         """All E members of one image -> [E,C,h,w] (on every rank when member-parallel).  ``carry``: the frame's ``_FrameCarry``
@@ -718,8 +719,7 @@ class _MarigoldPipelineBase:
             # the LCM scheduler consumes the generator once per non-final step (:466-468): those draws are made for
             # all E members on every rank too, in the order a single process holding the E members in one batch makes
             # them (initial latents, then one [E,...] draw per step), and sliced by member
-            self.scheduler.set_timesteps(denoising_steps)
-            n_noise = sum(bool(self.scheduler.needs_noise(i)) for i in range(denoising_steps))
+            n_noise = self._step_noise_count(denoising_steps)
             if n_noise:
                 step_noises_all = [self._randn(init_latents.shape, generator) for _ in range(n_noise)]
             members = mdist.shard_members(E, mdist.world_size(self._member_group),
@@ -761,8 +761,7 @@ class _MarigoldPipelineBase:
         res = max(rgb_norms[0].shape[1:])
         hh, ww = self._latent_hw(rgb_norms[0].shape[-2:])
         C = self._target_latent_channels
-        self.scheduler.set_timesteps(denoising_steps)
-        n_noise = sum(bool(self.scheduler.needs_noise(i)) for i in range(denoising_steps))
+        n_noise = self._step_noise_count(denoising_steps)
         lone_bs = batch_size if batch_size > 0 else find_batch_size(ensemble_size=E, input_res=res, dtype=self.dtype)
         lats, noises = [], [[] for _ in range(n_noise)]
         for g in generators:
@@ -813,10 +812,23 @@ class _MarigoldPipelineBase:
                                     [None] * len(images) if generators is None else list(generators))
         E = ensemble_size
         finish = {a: kw[a] for a in self._finish_args if a in kw}
-        return [self._finish_or_keep(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
+        return [self._finish(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
                              kw.get("ensemble_kwargs"), **finish) for j, (_, input_size) in enumerate(prepared)]
 
-    _finish_args = ()
+    _finish_args = ()   # the keywords of ``__call__`` that go to the kind's ``_tail``
+
+    @torch.no_grad()
+    def _call(self, input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
+              generator, ensemble_kwargs, init_latents, sequence, **finish):
+        """What every kind's ``__call__`` runs; ``finish``: its keywords of ``_finish_args``."""
+        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
+            denoising_steps, ensemble_size, processing_res, resample_method)
+        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
+        rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
+
+        target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
+                                             generator, init_latents, carry)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **finish)
 
     def _call_settings(self, denoising_steps, ensemble_size, processing_res, resample_method):
         """``__call__``'s defaults and argument checks -> (denoising_steps, ensemble_size, processing_res, resample mode)."""
@@ -840,7 +852,7 @@ class _MarigoldPipelineBase:
         return h, w
 
     # The uint8 ends of a CUDA pipeline run on the device (csrc/resize.hip): MG_OP_RGB_PREP in ``_preprocess``, MG_OP_NORMALS_VIS in the
-    # normals pipeline's ``_finish``.  False: the host code of both (what host pipelines and float inputs run anyway) - the same bits.
+    # normals pipeline's ``_tail``.  False: the host code of both (what host pipelines and float inputs run anyway) - the same bits.
     device_io_stages = True
 
     def _preprocess_device(self, input_image, processing_res, resample_method):
@@ -910,7 +922,6 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
         reference :498-516 + :473-475)."""
         return self.vae.decode(depth_latent, post=L.POST_DEPTH)
 
-    @torch.no_grad()
     def __call__(self, input_image: Union[Image.Image, torch.Tensor], denoising_steps: Optional[int] = None,
                  ensemble_size: int = 1, processing_res: Optional[int] = None, match_input_res: bool = True,
                  resample_method: str = "bilinear", batch_size: int = 0,
@@ -918,41 +929,20 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
                  show_progress_bar: bool = True, ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
                  sequence: Optional[SequenceState] = None) -> MarigoldDepthOutput:
-        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
-            denoising_steps, ensemble_size, processing_res, resample_method)
-        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
-        rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
-
-        target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
-                                             generator, init_latents, carry)
-        return self._finish_or_keep(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
-                                    color_map=color_map)
+        return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
+                          generator, ensemble_kwargs, init_latents, sequence, color_map=color_map)
 
     _finish_args = ("color_map",)
 
-    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs,
-                color_map="Spectral") -> MarigoldDepthOutput:
-        """``__call__``'s tail: the members of one image -> its output."""
-        if target_preds is None:  # member-parallel non-root rank with a rooted gather
-            return MarigoldDepthOutput(depth_np=None, depth_colored=None, uncertainty=None)
-        if ensemble_size > 1:
-            final_pred, pred_uncert = ensemble_depth(target_preds, scale_invariant=self.scale_invariant,
-                                                     shift_invariant=self.shift_invariant,
-                                                     **(ensemble_kwargs or {}))
-        else:
-            final_pred, pred_uncert = target_preds, None
-        if match_input_res:
-            final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        return _depth_tail(final_pred, pred_uncert, color_map)
-
-    _clip_range = (0, 1)
+    def _empty_output(self) -> MarigoldDepthOutput:
+        return MarigoldDepthOutput(depth_np=None, depth_colored=None, uncertainty=None)
 
     def _ensemble(self, target_preds, ensemble_kwargs):
         return ensemble_depth(target_preds, scale_invariant=self.scale_invariant, shift_invariant=self.shift_invariant,
                               **(ensemble_kwargs or {}))
 
-    def _tail(self, final_pred, color_map="Spectral") -> MarigoldDepthOutput:
-        return _depth_tail(final_pred, None, color_map)
+    def _tail(self, final_pred, pred_uncert, color_map="Spectral") -> MarigoldDepthOutput:
+        return _depth_tail(final_pred, pred_uncert, color_map)
 
 
 def _depth_tail(final_pred, pred_uncert, color_map) -> MarigoldDepthOutput:
@@ -1002,7 +992,6 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
         :437-440)."""
         return self.vae.decode(normals_latent, post=L.POST_NORMALS)
 
-    @torch.no_grad()
     def __call__(self, input_image: Union[Image.Image, torch.Tensor], denoising_steps: Optional[int] = None,
                  ensemble_size: int = 1, processing_res: Optional[int] = None, match_input_res: bool = True,
                  resample_method: str = "bilinear", batch_size: int = 0,
@@ -1010,35 +999,19 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
                  ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
                  sequence: Optional[SequenceState] = None) -> MarigoldNormalsOutput:
-        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
-            denoising_steps, ensemble_size, processing_res, resample_method)
-        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
-        rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
-
-        target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
-                                             generator, init_latents, carry)
-        return self._finish_or_keep(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
-
-    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
-                ensemble_kwargs) -> MarigoldNormalsOutput:
-        """``__call__``'s tail: the members of one image -> its output."""
-        if target_preds is None:
-            return MarigoldNormalsOutput(normals_np=None, normals_img=None, uncertainty=None)
-        if ensemble_size > 1:
-            final_pred, pred_uncert = ensemble_normals(target_preds, **(ensemble_kwargs or {}))
-        else:
-            final_pred, pred_uncert = target_preds, None
-        if match_input_res:
-            final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        return _normals_tail(final_pred, pred_uncert, final_pred.is_cuda and self.device_io_stages)
+        return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
+                          generator, ensemble_kwargs, init_latents, sequence)
 
     _clip_range = (-1, 1)
+
+    def _empty_output(self) -> MarigoldNormalsOutput:
+        return MarigoldNormalsOutput(normals_np=None, normals_img=None, uncertainty=None)
 
     def _ensemble(self, target_preds, ensemble_kwargs):
         return ensemble_normals(target_preds, **(ensemble_kwargs or {}))
 
-    def _tail(self, final_pred) -> MarigoldNormalsOutput:
-        return _normals_tail(final_pred, None, final_pred.is_cuda and self.device_io_stages)
+    def _tail(self, final_pred, pred_uncert) -> MarigoldNormalsOutput:
+        return _normals_tail(final_pred, pred_uncert, final_pred.is_cuda and self.device_io_stages)
 
 
 def _normals_tail(final_pred, pred_uncert, device_picture) -> MarigoldNormalsOutput:
@@ -1185,34 +1158,24 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
                               uncertainty=None if pred_uncert is None else pred_uncert[:, 3 * i:3 * i + 3],
                               target_properties=self.target_properties)
 
-    @torch.no_grad()
     def __call__(self, input_image: Union[Image.Image, torch.Tensor], denoising_steps: Optional[int] = None,
                  ensemble_size: int = 1, processing_res: Optional[int] = None, match_input_res: bool = True,
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None,
                  sequence: Optional[SequenceState] = None) -> MarigoldIIDOutput:
-        denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
-            denoising_steps, ensemble_size, processing_res, resample_method)
-        carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
-        rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
-        target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size, generator,
-                                             init_latents, carry)
-        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs)
+        return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
+                          generator, ensemble_kwargs, init_latents, sequence)
 
-    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample,
-                ensemble_kwargs) -> MarigoldIIDOutput:
-        """``__call__``'s tail: the members of one image -> its output."""
-        output = MarigoldIIDOutput(target_names=self.target_names)
-        if target_preds is None:   # member-parallel non-root rank with a rooted gather
-            return output
-        assert target_preds.dim() == 4 and target_preds.shape[1] == 3 * self.n_targets
-        if ensemble_size > 1:
-            final_pred, pred_uncert = ensemble_iid(target_preds, **(ensemble_kwargs or {}))
-        else:
-            final_pred, pred_uncert = target_preds, None
-        if match_input_res:
-            final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
+    def _empty_output(self) -> MarigoldIIDOutput:
+        return MarigoldIIDOutput(target_names=self.target_names)
+
+    def _ensemble(self, target_preds, ensemble_kwargs):
+        return ensemble_iid(target_preds, **(ensemble_kwargs or {}))
+
+    def _tail(self, final_pred, pred_uncert) -> MarigoldIIDOutput:
+        assert final_pred.dim() == 4 and final_pred.shape[1] == 3 * self.n_targets
+        output = self._empty_output()
         self.fill_outputs(output, final_pred, pred_uncert)
         assert output.is_complete
         return output

@@ -162,7 +162,7 @@ def test_host_normals_prediction_keeps_the_numpy_picture():
     g = torch.Generator().manual_seed(3)
     pred = torch.randn(1, 3, 9, 14, generator=g)
     pred[0, :, 2, 3] = torch.tensor([-1.5, 1.5, 1.0])
-    out = MarigoldNormalsPipeline._finish(SimpleNamespace(), pred, (1, 3, 9, 14), 1, False, None, None)
+    out = MarigoldNormalsPipeline._tail(SimpleNamespace(), pred, None)
     clipped = pred[0].numpy().clip(-1, 1)
     assert np.array_equal(out.normals_np, clipped) and out.uncertainty is None
     assert np.array_equal(np.asarray(out.normals_img), np.moveaxis(((clipped + 1) * 127.5).astype(np.uint8), 0, -1))

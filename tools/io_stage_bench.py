@@ -6,7 +6,7 @@ seeded data.
   ``pil_to_tensor``, the device resample where the size changes, torch's normalisation, the range assert).  Host clock around work
   that ends where ``single_infer`` starts computing: the normalised image on the device (the host branch's upload included) and the
   stream drained.  The time inside ``_preprocess`` alone is reported too - what a lane thread spends before it hands over.
-* normals output: ``MarigoldNormalsPipeline._finish`` of a CUDA prediction through MG_OP_NORMALS_VIS and through the numpy lines; host
+* normals output: ``MarigoldNormalsPipeline._tail`` (``_finish``'s end) of a CUDA prediction through MG_OP_NORMALS_VIS and through the numpy lines; host
   clock around work that ends in the read-backs.
 * the launches alone by device events.
 
@@ -116,8 +116,8 @@ def main():
     for h, w in ((768, 768), (375, 1242)):
         pred = torch.nn.functional.normalize(torch.randn(1, 3, h, w, generator=g), dim=1).to(dev)
 
-        def finish(on, pred=pred, h=h, w=w):
-            return MarigoldNormalsPipeline._finish(SimpleNamespace(device_io_stages=on), pred, (1, 3, h, w), 1, False, None, None)
+        def finish(on, pred=pred):
+            return MarigoldNormalsPipeline._tail(SimpleNamespace(device_io_stages=on), pred, None)
         t = _alternate(args.rounds, [("numpy", lambda: finish(False)), ("device", lambda: finish(True))])
         a, b = finish(False), finish(True)
         same = np.array_equal(a.normals_np, b.normals_np) and np.array_equal(np.asarray(a.normals_img), np.asarray(b.normals_img))
