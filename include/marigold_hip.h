@@ -1298,6 +1298,75 @@ int mg_tile_fit(const float* tiles, int th, int tw, const int* ystarts, int ny, 
                 const float* guide, int hg, int wg, double* coef, int* flags, void* ws, long long ws_bytes, void* stream);
 int mg_tile_blend(const float* tiles, int C, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx, int Hw, int Ww,
                   int oy, int ox, const double* coef_or_null, int normalize, float* out, void* stream);
+/*  mg_tile_crop: the GATHER of the tiles out of the picture - `count` tiles of the grid, from tile `first` on in row-major order, copied
+ *    into dst as `count` contiguous uint8 pictures of th x tw in the layout of src: src [Hw][Ww][3] and dst [count][th][tw][3] with
+ *    hwc != 0, else src [3][Hw][Ww] and dst [count][3][th][tw].  One launch, no synchronisation; nothing outside dst[0, count 3 th tw)
+ *    is written.  Starts and extents are multiples of 8, so every tile row begins on a multiple of 24 bytes (hwc) or 8 bytes (chw) of
+ *    either buffer: a lane moves 8 bytes, as one 8-byte load and store where src and dst are both 8-byte aligned, byte by byte
+ *    otherwise (the pointers themselves need no alignment).  Refused: a null pointer, th, tw, Hw, Ww or a start that is no multiple
+ *    of 8, a tile outside the canvas, a canvas above 2^28 pixels, ny or nx outside 1 .. MG_TILE_MAX_PER_AXIS, first < 0, count < 1 or
+ *    first + count > ny nx.  The grid need not cover the canvas. */
+int mg_tile_crop(const uint8_t* src, int hwc, int Hw, int Ww, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx,
+                 int first, int count, uint8_t* dst, void* stream);
+
+/* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
+ * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
+ * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with
+ * mg_model_find_config:
+ *  tiled.tile_config   the tiles' configuration: its size cfg[1] x cfg[2] is the tile size th x tw (multiples of 8, decoded at that
+ *                      size, at most the picture's), K = cfg[13] >= 1 tiles per call, B = cfg[0] members each
+ *  tiled.guide_config  depth only (ignored for normals): a configuration of ONE picture per call, of the same kind and with the same
+ *                      B, whose size is the processed size of the guide (mg_processed_size(Hin, Win, guide_res))
+ *  tiled.overlap_y/_x  the minimum overlap of neighbouring tiles
+ *  tiled.tail_config   -1, or the configuration that runs the SHORT LAST GROUP: of the tile configuration's kind, size and B, with
+ *                      exactly r = n mod K pictures per call (ignored when r = 0).  map_images runs a group of r < K tiles as a
+ *                      program of r pictures, so with it the call is predict_tiled bit for bit; with -1 the last group follows
+ *                      mg_model_predict_many's rule for n < K on tile_config - the same up to the arithmetic of the larger batch
+ * The call selects the configurations itself and leaves the handle on the one that was selected before it (the sequence state of
+ * mg_model_predict_next is neither read nor changed).  The chain, every step the code the other calls run:
+ *  1. the plan: mg_tile_plan(Hin, th, overlap_y) and mg_tile_plan(Win, tw, overlap_x); n = ny nx tiles
+ *  2. depth: the guide = the chain of mg_model_predict on guide_config with `seed`, clipped to [0, 1]; its info4 goes to `info4`
+ *  3. the tiles in groups of K in row-major order: mg_tile_crop gathers a group, which runs the chain of mg_model_predict_many on
+ *     tile_config - tile i with the seed (seed + 1 + i) mod 2^64 - to the decoded size, clipped; a short last group follows that
+ *     call's rule for n < K, or runs whole on tail_config.  The maps go to one buffer [n][C][th][tw], with B > 1 and unc_out given the uncertainties to [n][th][tw]
+ *  4. depth: mg_tile_fit against the guide, mg_tile_blend with its coefficients; normals: mg_tile_blend(normalize = 1).  The
+ *     uncertainty: normals - mg_tile_blend of the tiles' uncertainties; depth - mg_tile_blend with the coefficients (s_i, 0), the
+ *     scales of the fit: a tile's uncertainty is in units of its own normalised depth.  A degenerate tile (s_i = 0) contributes 0
+ *     with its weight.
+ *  5. with out_opts.out_h x out_w set and different from Hin x Win the stitched prediction - not the uncertainty - is resampled to
+ *     them; then the output stage of mg_model_predict_out.
+ *  rgb, mode, reciprocal, opts, out_opts   as in mg_model_predict_out; mode and reciprocal act in mg_rgb_prepare of the guide; the
+ *              tiles are not resampled and always take reciprocal = 1, as the crops predict_tiled cuts on the device do;
+ *              out_opts NULL or 0 x 0: Hin x Win
+ *  pred_out    fp32 [channels][out_h][out_w], clipped; 16-byte aligned
+ *  unc_out     fp32 [Hin][Win] | NULL, written when B > 1; 16-byte aligned
+ *  u16_out, picture_out   as in mg_model_predict_out, at out_h x out_w
+ *  info4       HOST double [4] | NULL: the guide's, as in mg_model_predict (zeros for normals)
+ *  degenerate  DEVICE int32 [n] | NULL, depth only: mg_tile_fit's flag of every tile; their sum is the `degenerate_tiles` of
+ *              pipe.predict_tiled.  Left to the device so that the call need not wait for it.
+ * The working size is Hin x Win (multiples of 8): a host that wants another (predict_tiled's tiled_res) resamples the picture itself.
+ * The temporaries - crops, tile maps, tile uncertainties, fit workspace, coefficients, canvas - are the model's: grown on demand,
+ * counted by mg_model_device_bytes, freed by mg_model_destroy; mg_model_scratch_fill fills them too.  Synchronises where
+ * mg_ensemble_depth does (depth, B > 1: once for the guide and once per tile) and nowhere else.  Refused before anything is launched,
+ * the message starting with "mg_model_predict_tiled:": a null model, picture, tiled or pred_out; a host-only model; an
+ * intrinsic-image model; Hin or Win that is no multiple of 8; configuration indices out of range; a tile configuration whose size is
+ * no multiple of 8, is not decoded at its own size or exceeds the picture; a plan of ONE tile (that picture goes through
+ * mg_model_predict_out); a guide configuration with K > 1, another B or another kind than the tile configuration; a tail configuration of
+ * another kind, size or B than the tile configuration or with another K than n mod K; outputs that are
+ * not 16-byte aligned; every refusal of mg_tile_plan and every output-option refusal of mg_model_predict_out, in their own words.
+ * pipe.predict_tiled(tile_size=(th, tw), tile_overlap=..., guide_res=..., tiles_per_program=K, in_flight=1,
+ * generator=NativeNoise(seed), match_input_res=True, ensemble_kwargs=dict(output_uncertainty=True)) gives the same arrays and
+ * pictures, bit for bit (tests/test_gpu_predict_tiled_c_host.py; examples/host_tiled.cpp).  Tiled intrinsic images, member-parallel
+ * pipelines and sequences of tiled pictures are not covered. */
+typedef struct mg_tiled_opts {
+  int guide_config, tile_config;   /* indices of mg_model_find_config */
+  int overlap_y, overlap_x;        /* minimum overlap of neighbouring tiles, multiples of 8 */
+  int tail_config;                 /* -1 | the configuration of n mod K pictures per call for the short last group */
+} mg_tiled_opts;
+int mg_model_predict_tiled(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                           const mg_tiled_opts* tiled, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
+                           float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
+                           double* info4_or_null, int* degenerate_or_null, void* stream);
 
 /* Shader clock under matrix-core load, for bench.py's calibration block (the sysfs sensors do not answer on every box): one
  * workgroup per CU (one wave per SIMD) runs a fixed chain of v_mfma_f32_32x32x16_bf16 on random (zero_operands = 0) or zero

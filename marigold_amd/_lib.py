@@ -218,6 +218,7 @@ EXPORTS = [
     "mg_tiny_vae_workspace_bytes", "mg_tiny_vae_encode", "mg_tiny_vae_decode", "mg_tiny_conv3x3",
     "mg_model_scratch_fill",
     "mg_tile_plan", "mg_tiles_workspace_bytes", "mg_tile_fit", "mg_tile_blend",
+    "mg_tile_crop", "mg_model_predict_tiled",
 ]
 
 
@@ -241,6 +242,16 @@ class MgOutputOpts(ctypes.Structure):
     """mg_output_opts; the defaults are MG_OUTPUT_OPTS_DEFAULT (the model's output size, no colour table).  ``lut256x3``: the DEVICE
     address of the colour map's 256 x 3 uint8 table."""
     _fields_ = [("out_h", ctypes.c_int), ("out_w", ctypes.c_int), ("out_mode", ctypes.c_int), ("lut256x3", ctypes.c_void_p)]
+
+
+class MgTiledOpts(ctypes.Structure):
+    """mg_tiled_opts: the configurations of the model image (``mg_model_find_config``) - the guide's, the tiles' and, or -1, the short
+    last group's - and the minimum overlap along y and x."""
+    _fields_ = [("guide_config", ctypes.c_int), ("tile_config", ctypes.c_int), ("overlap_y", ctypes.c_int), ("overlap_x", ctypes.c_int),
+                ("tail_config", ctypes.c_int)]
+
+    def __init__(self, guide_config=0, tile_config=0, overlap_y=0, overlap_x=0, tail_config=-1):
+        super().__init__(guide_config, tile_config, overlap_y, overlap_x, tail_config)
 
 
 class MgLpipsNet(ctypes.Structure):
@@ -371,6 +382,10 @@ def load(f16=False):
         [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p]
     lib.mg_tile_blend.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + _grid + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                                                  ctypes.c_void_p, ctypes.c_void_p]
+    lib.mg_tile_crop.argtypes = [ctypes.c_void_p] + _grid[4:] + [ctypes.c_int] * 3 + _grid[:4] + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mg_model_predict_tiled.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgTiledOpts),
+                                                                                         ctypes.POINTER(MgPredictOpts),
+                                                                                         ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 7
     lib.mg_model_scratch_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]

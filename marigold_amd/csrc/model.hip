@@ -189,6 +189,8 @@ struct mg_model {
   uint64_t seq_bytes = 0;
   bool seq_carried = false;          // seq_latent holds a frame of the selected configuration
   const float* seq_call = nullptr;   // the strength, while mg_model_predict_next runs its prediction on this handle
+  void* tiled_tmp = nullptr;         // mg_model_predict_tiled's temporaries (see TiledTmp), grown on demand
+  uint64_t tiled_tmp_bytes = 0;
 };
 
 namespace {
@@ -582,6 +584,7 @@ void mg_model_destroy(mg_model* m) {
   if (m->predict_tmp) (void)hipFree(m->predict_tmp);
   if (m->out_tmp) (void)hipFree(m->out_tmp);
   if (m->seq_latent) (void)hipFree(m->seq_latent);
+  if (m->tiled_tmp) (void)hipFree(m->tiled_tmp);
   delete m;   // (the shared weights go with the last handle over them)
 }
 
@@ -640,7 +643,7 @@ int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes + m->seq_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes + m->seq_bytes + m->tiled_tmp_bytes) : 0; }
 
 long long mg_model_shared_bytes(const mg_model* m) { return m ? (long long)m->plan->shared_bytes : 0; }
 
@@ -664,6 +667,8 @@ int mg_model_scratch_fill(mg_model* m, int byte, void* stream) {
   const Plan& p = *m->plan;
   for (size_t i = 0; i < p.bufs.size(); ++i)   // (the configurations' scratch buffers overlay each other: some bytes are set twice)
     if (p.bufs[i].kind == KIND_SCRATCH) MG_CHECK_HIP(hipMemsetAsync(m->bufs[i], byte, p.bufs[i].nbytes, (hipStream_t)stream));
+  // (the temporaries of a tiled prediction are scratch of the same kind: everything in them is written before it is read)
+  if (m->tiled_tmp) MG_CHECK_HIP(hipMemsetAsync(m->tiled_tmp, byte, m->tiled_tmp_bytes, (hipStream_t)stream));
   return 0;
 }
 
@@ -1014,6 +1019,21 @@ int predict_depth_or_normals(mg_model* m, const char* who, int n, const uint8_t*
       });
 }
 
+// The output-option refusals of mg_model_predict_out, in `who`'s name, for a model of the kind (post, C) whose stitched or ensembled
+// map is Ho x Wo -> the size to store
+int check_output_opts(const char* who, int post, int C, const mg_output_opts& q, int Ho, int Wo, const uint16_t* u16_out_or_null,
+                      const uint8_t* picture_out_or_null, int* oh, int* ow) {
+  const bool depth = post == MG_POST_DEPTH && C == 1;
+  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
+  if (int rc = output_size(who, q.out_h, q.out_w, q.out_mode, 1ll << 30, Ho, Wo, oh, ow)) return rc;
+  if (depth) {
+    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "%s: the picture of a depth model needs out_opts.lut256x3 (the colour table)", who);
+  } else {
+    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "%s: u16_out and lut256x3 belong to a depth model, this one predicts normals", who);
+  }
+  return 0;
+}
+
 // mg_model_predict_out and mg_model_predict_many after their own argument checks: the refusals they share (in `who`'s name), then the
 // prediction.  One picture is n = 1.
 int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
@@ -1022,17 +1042,10 @@ int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* 
   const uint32_t* cfg = m->cur().cfg;
   const int C = (int)cfg[6], post = (int)cfg[7];
   MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "%s: an intrinsic-image model goes through mg_model_predict_iid", who);
-  const bool depth = post == MG_POST_DEPTH && C == 1;
-  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
   static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
   const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
   int oh, ow;
-  if (int rc = output_size(who, q.out_h, q.out_w, q.out_mode, 1ll << 30, (int)cfg[11], (int)cfg[12], &oh, &ow)) return rc;
-  if (depth) {
-    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "%s: the picture of a depth model needs out_opts.lut256x3 (the colour table)", who);
-  } else {
-    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "%s: u16_out and lut256x3 belong to a depth model, this one predicts normals", who);
-  }
+  if (int rc = check_output_opts(who, post, C, q, (int)cfg[11], (int)cfg[12], u16_out_or_null, picture_out_or_null, &oh, &ow)) return rc;
   return predict_depth_or_normals(m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, oh, ow, q.out_mode, true, q.lut256x3,
                                   pred_out, unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
 }
@@ -1106,6 +1119,179 @@ extern "C" int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* r
   for (int i = 0; i < n; ++i) MG_REQUIRE(rgb[i], "mg_model_predict_many: null picture %d of %d", i, n);
   return predict_out_many(m, "mg_model_predict_many", n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, out_opts_or_null, pred_out,
                           unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
+}
+
+// ---- the tiled prediction of a large picture as one call (pipe.predict_tiled): plan -> guide -> tiles, a group of K per
+// call of the tile configuration's programs -> fit and blend -> resize -> output stage.  Every stage is the code the calls above and
+// csrc/tiles.hip already run; this function only strings them together.
+namespace {
+
+// mg_model_predict_tiled's temporaries, carved out of the model's tiled_tmp in this order, each part rounded up to 256 bytes
+struct TiledTmp {
+  uint64_t crops = 0, maps = 0, unc = 0, fit_ws = 0, coef = 0, coef_unc = 0, flags = 0, guide = 0, canvas = 0, rtmp = 0;
+  uint64_t total() const { return crops + maps + unc + fit_ws + coef + coef_unc + flags + guide + canvas + rtmp; }
+};
+
+// the handle goes back to the configuration it was on, on every way out
+struct Reselect {
+  mg_model* m;
+  int sel;
+  ~Reselect() { m->sel = sel; }
+};
+
+}  // namespace
+
+extern "C" int mg_model_predict_tiled(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
+                                      const mg_tiled_opts* tiled, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
+                                      float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
+                                      double* info4_or_null, int* degenerate_or_null, void* stream) {
+  const char* who = "mg_model_predict_tiled";
+  MG_REQUIRE(m && rgb && tiled && pred_out, "%s: null argument (the model, the picture, tiled and pred_out are required)", who);
+  const int n_cfg = (int)m->configs.size();
+  MG_REQUIRE(tiled->tile_config >= 0 && tiled->tile_config < n_cfg, "%s: tile configuration %d of %d", who, tiled->tile_config, n_cfg);
+  const Config& tc = m->configs[tiled->tile_config];
+  const int B = (int)tc.cfg[0], th = (int)tc.cfg[1], tw = (int)tc.cfg[2], C = (int)tc.cfg[6], post = (int)tc.cfg[7], K = tc.K;
+  MG_REQUIRE(post != MG_POST_UNIT && tc.cfg[10] == 1, "%s: an intrinsic-image model is not supported (depth and normals only)", who);
+  const bool depth = post == MG_POST_DEPTH && C == 1;
+  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
+  MG_REQUIRE(Hin >= 8 && Win >= 8 && Hin % 8 == 0 && Win % 8 == 0, "%s: the picture size %d x %d must be multiples of 8 (the call works at the picture's size)",
+             who, Hin, Win);
+  MG_REQUIRE((long long)Hin * Win <= (1ll << 28) && Hin <= 65535, "%s: a picture of %d x %d is not supported", who, Hin, Win);
+  MG_REQUIRE(th % 8 == 0 && tw % 8 == 0 && (int)tc.cfg[11] == th && (int)tc.cfg[12] == tw && (long long)th * tw <= (1ll << 26),
+             "%s: the tile configuration's size %d x %d (decoded %d x %d) must be multiples of 8, decoded at that size", who, th, tw, (int)tc.cfg[11],
+             (int)tc.cfg[12]);
+  MG_REQUIRE(th <= Hin && tw <= Win, "%s: the tile configuration's size %d x %d exceeds the picture %d x %d", who, th, tw, Hin, Win);
+  // 1. the plan
+  int ys[MG_TILE_MAX_PER_AXIS], xs[MG_TILE_MAX_PER_AXIS];
+  const int ny = mg_tile_plan(Hin, th, tiled->overlap_y, ys, MG_TILE_MAX_PER_AXIS);
+  const int nx = ny < 1 ? -1 : mg_tile_plan(Win, tw, tiled->overlap_x, xs, MG_TILE_MAX_PER_AXIS);
+  if (nx < 1) {
+    const std::string why = mg_last_error();
+    mg_set_error("%s: %s", who, why.c_str());
+    return 2;
+  }
+  const int n = ny * nx;
+  MG_REQUIRE(n > 1, "%s: the plan is ONE tile (the picture is the tile): use mg_model_predict_out", who);
+  int hg = 0, wg = 0;
+  if (depth) {
+    MG_REQUIRE(tiled->guide_config >= 0 && tiled->guide_config < n_cfg, "%s: guide configuration %d of %d", who, tiled->guide_config, n_cfg);
+    const Config& gc = m->configs[tiled->guide_config];
+    MG_REQUIRE(gc.K == 1, "%s: the guide configuration runs %d pictures per call, the guide is ONE picture (K = 1)", who, gc.K);
+    MG_REQUIRE((int)gc.cfg[0] == B, "%s: the guide configuration has %d members, the tile configuration %d", who, (int)gc.cfg[0], B);
+    MG_REQUIRE((int)gc.cfg[7] == post && (int)gc.cfg[6] == C && gc.cfg[10] == 1, "%s: the guide configuration is of another kind than the tile configuration", who);
+    hg = (int)gc.cfg[11];
+    wg = (int)gc.cfg[12];
+    MG_REQUIRE(hg >= 1 && wg >= 1 && (long long)hg * wg <= (1ll << 26), "%s: bad guide size %d x %d", who, hg, wg);
+  }
+  // the short last group: r tiles, whole on a configuration of r pictures per call, or padded on the tile configuration
+  const int r = n % K;
+  const bool tail = r != 0 && tiled->tail_config != -1;
+  if (tail) {
+    MG_REQUIRE(tiled->tail_config >= 0 && tiled->tail_config < n_cfg, "%s: tail configuration %d of %d", who, tiled->tail_config, n_cfg);
+    const Config& lc = m->configs[tiled->tail_config];
+    MG_REQUIRE(lc.K == r, "%s: the tail configuration runs %d pictures per call, the short last group has %d tiles (%d tiles, %d per call)", who, lc.K,
+               r, n, K);
+    MG_REQUIRE((int)lc.cfg[0] == B && (int)lc.cfg[7] == post && (int)lc.cfg[6] == C && lc.cfg[10] == 1 && (int)lc.cfg[1] == th && (int)lc.cfg[2] == tw &&
+                   (int)lc.cfg[11] == th && (int)lc.cfg[12] == tw,
+               "%s: the tail configuration is of another kind, size (%d x %d) or member count (%d) than the tile configuration (%d x %d, %d)", who,
+               (int)lc.cfg[1], (int)lc.cfg[2], (int)lc.cfg[0], th, tw, B);
+  }
+  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
+  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
+  int oh, ow;
+  if (int rc = check_output_opts(who, post, C, q, Hin, Win, u16_out_or_null, picture_out_or_null, &oh, &ow)) return rc;
+  MG_REQUIRE((uintptr_t)pred_out % 16 == 0 && (uintptr_t)unc_out_or_null % 16 == 0, "%s: pred_out and unc_out must be 16-byte aligned", who);
+  MG_REQUIRE((uintptr_t)degenerate_or_null % 4 == 0, "%s: degenerate must be aligned to its elements", who);
+  if (opts_or_null && !depth)
+    MG_REQUIRE(opts_or_null->normals_reduction == 0 || opts_or_null->normals_reduction == 1, "%s: Unrecognized reduction method: %d.", who,
+               opts_or_null->normals_reduction);
+  MG_REQUIRE(!m->host_only, "%s: a host-only model cannot predict (load it with device >= 0)", who);
+
+  // the temporaries
+  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
+  const bool with_unc = B > 1 && unc_out_or_null, resize = oh != Hin || ow != Win;
+  const uint64_t tile_px = (uint64_t)th * tw;
+  TiledTmp t;
+  t.crops = r256((uint64_t)K * 3 * tile_px);
+  t.maps = r256((uint64_t)n * C * tile_px * 4);
+  if (with_unc) t.unc = r256((uint64_t)n * tile_px * 4);
+  if (depth) {
+    t.fit_ws = r256((uint64_t)mg_tiles_workspace_bytes(n, th, tw));
+    t.coef = r256((uint64_t)n * 16);
+    if (with_unc) t.coef_unc = r256((uint64_t)n * 16);
+    if (!degenerate_or_null) t.flags = r256((uint64_t)n * 4);
+    t.guide = r256((uint64_t)hg * wg * 4);
+  }
+  if (resize) {
+    t.canvas = r256((uint64_t)C * Hin * Win * 4);
+    if (q.out_mode != 2 && oh != Hin && ow != Win) t.rtmp = r256((uint64_t)C * Hin * ow * 4);
+  }
+  if (int rc = grow_tmp(&m->tiled_tmp, &m->tiled_tmp_bytes, t.total())) return rc;
+  char* at = (char*)m->tiled_tmp;
+  auto carve = [&](uint64_t bytes) {
+    char* p = bytes ? at : nullptr;
+    at += bytes;
+    return p;
+  };
+  uint8_t* const crops = (uint8_t*)carve(t.crops);
+  float* const maps = (float*)carve(t.maps);
+  float* const uncs = (float*)carve(t.unc);
+  void* const fit_ws = carve(t.fit_ws);
+  double* const coef = (double*)carve(t.coef);
+  double* const coef_unc = (double*)carve(t.coef_unc);
+  int* const own_flags = (int*)carve(t.flags);
+  int* const flags = degenerate_or_null ? degenerate_or_null : own_flags;
+  float* const guide = (float*)carve(t.guide);
+  float* const canvas = resize ? (float*)carve(t.canvas) : pred_out;
+  float* const rtmp = (float*)carve(t.rtmp);
+  const hipStream_t s = (hipStream_t)stream;
+
+  Reselect back = {m, m->sel};
+  if (info4_or_null)
+    for (int i = 0; i < 4; ++i) info4_or_null[i] = 0.0;
+  // 2. the guide: one ordinary prediction of the whole picture at the guide configuration's size, clipped
+  if (depth) {
+    m->sel = tiled->guide_config;
+    if (int rc = predict_depth_or_normals(m, who, 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, hg, wg, 0, true, nullptr, guide,
+                                          nullptr, nullptr, nullptr, info4_or_null, stream))
+      return rc;
+  }
+  // 3. the tiles, a group of K per call
+  std::vector<const uint8_t*> pics((size_t)K);
+  std::vector<uint64_t> seeds((size_t)K);
+  for (int first = 0; first < n; first += K) {
+    const int cnt = n - first < K ? n - first : K;
+    m->sel = cnt < K && tail ? tiled->tail_config : tiled->tile_config;
+    if (int rc = mg_tile_crop(rgb, hwc, Hin, Win, th, tw, ys, ny, xs, nx, first, cnt, crops, stream)) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      pics[i] = crops + (uint64_t)i * 3 * tile_px;
+      seeds[i] = seed + 1 + (uint64_t)(first + i);   // (mod 2^64)
+    }
+    if (int rc = predict_depth_or_normals(m, who, cnt, pics.data(), hwc, th, tw, 0, 1, seeds.data(), opts_or_null, th, tw, 0, true, nullptr,
+                                          maps + (uint64_t)first * C * tile_px, with_unc ? uncs + (uint64_t)first * tile_px : nullptr, nullptr, nullptr,
+                                          nullptr, stream))
+      return rc;
+  }
+  // 4. the stitch
+  const int oy = tiled->overlap_y, ox = tiled->overlap_x;
+  if (depth) {
+    if (int rc = mg_tile_fit(maps, th, tw, ys, ny, xs, nx, Hin, Win, guide, hg, wg, coef, flags, fit_ws, (long long)t.fit_ws, stream)) return rc;
+    if (int rc = mg_tile_blend(maps, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, coef, 0, canvas, stream)) return rc;
+    if (with_unc) {   // (s_i, 0): the scales of the fit without its shifts
+      MG_CHECK_HIP(hipMemsetAsync(coef_unc, 0, (size_t)n * 16, s));
+      MG_CHECK_HIP(hipMemcpy2DAsync(coef_unc, 16, coef, 16, 8, (size_t)n, hipMemcpyDeviceToDevice, s));
+      if (int rc = mg_tile_blend(uncs, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, coef_unc, 0, unc_out_or_null, stream)) return rc;
+    }
+  } else {
+    if (int rc = mg_tile_blend(maps, 3, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, nullptr, 1, canvas, stream)) return rc;
+    if (with_unc)
+      if (int rc = mg_tile_blend(uncs, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, nullptr, 0, unc_out_or_null, stream)) return rc;
+  }
+  // 5. match_input_res, then the output stage of mg_model_predict_out on what was stored
+  if (resize)
+    if (int rc = mg_resize(canvas, pred_out, rtmp, C, Hin, Win, oh, ow, q.out_mode, 0, stream)) return rc;
+  if (depth) return mg_depth_visualize(pred_out, q.lut256x3, (int64_t)oh * ow, pred_out, u16_out_or_null, picture_out_or_null, stream);
+  return mg_normals_finish(pred_out, oh, ow, pred_out, picture_out_or_null, stream);
 }
 
 extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,

@@ -194,6 +194,40 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict
   for (int c = 0; c < C; ++c) *(float4*)(out + ((long long)c * Hw + y) * Ww + x) = make_float4(r[c][0], r[c][1], r[c][2], r[c][3]);
 }
 
+// The gather of uint8 tiles out of a picture.  Both layouts are rows of bytes: hwc - a tile is th rows of 3 tw bytes, row r at
+// ((y0 + r) Ww + x0) 3 of the picture; chw - 3 th rows of tw bytes, row c th + r at (c Hw + y0 + r) Ww + x0.  In `dst` the rows of a
+// tile follow each other without a gap.  Starts and extents are multiples of 8, so every row starts and ends on a multiple of 8 bytes
+// from either base: a lane moves one 8-byte word.  VEC: both bases are 8-byte aligned and the word is one load and one store; else
+// eight byte loads and stores.  grid (ceil(words per tile / 256), count).
+constexpr int CROP_THREADS = 256;
+template <bool VEC>
+__global__ __launch_bounds__(CROP_THREADS) void tile_crop_kernel(const uint8_t* __restrict__ src, int hwc, int Hw, int Ww, int th, int tw,
+                                                                 tile_grid g, int first, uint8_t* __restrict__ dst) {
+  const int row_words = (hwc ? 3 * tw : tw) / 8, rows = hwc ? th : 3 * th;
+  const int w = blockIdx.x * CROP_THREADS + threadIdx.x;   // (3 th tw / 8 <= 3 * 2^23: word indices fit an int)
+  if (w >= rows * row_words) return;
+  const int tile = first + blockIdx.y, q = w / row_words, j = w % row_words;
+  const int y0 = g.ys[tile / g.nx], x0 = g.xs[tile % g.nx];
+  long long from;
+  if (hwc) {
+    from = ((long long)(y0 + q) * Ww + x0) * 3;
+  } else {
+    const int c = q / th, r = q % th;
+    from = ((long long)c * Hw + y0 + r) * Ww + x0;
+  }
+  const uint8_t* s = src + from + (long long)j * 8;
+  uint8_t* d = dst + (long long)blockIdx.y * 3 * th * tw + (long long)w * 8;
+  if constexpr (VEC) {
+    *(uint2*)d = *(const uint2*)s;
+  } else {
+    uint8_t b[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) b[k] = s[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = b[k];
+  }
+}
+
 // the checks fit and blend share: the extents, the canvas and the starts of one axis (name: "y" / "x")
 int check_axis(const char* fn, const char* name, const int* starts, int count, int T, int L) {
   MG_REQUIRE(starts, "%s: null pointer (%sstarts)", fn, name);
@@ -310,6 +344,28 @@ extern "C" int mg_tile_blend(const float* tiles, int C, int th, int tw, const in
     MG_LAUNCH(tile_blend_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, tiles, th, tw, g, Hw, Ww, (float)oy, (float)ox, coef_or_null, normalize, out);
   else
     MG_LAUNCH(tile_blend_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, tiles, th, tw, g, Hw, Ww, (float)oy, (float)ox, coef_or_null, normalize, out);
+  if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int mg_tile_crop(const uint8_t* src, int hwc, int Hw, int Ww, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx,
+                            int first, int count, uint8_t* dst, void* stream) {
+  const char* fn = "mg_tile_crop";
+  MG_REQUIRE(src && dst, "%s: null pointer", fn);
+  if (int rc = check_axis(fn, "y", ystarts, ny, th, Hw)) return rc;
+  if (int rc = check_axis(fn, "x", xstarts, nx, tw, Ww)) return rc;
+  if (int rc = check_tile_shape(fn, (long long)ny * nx, th, tw)) return rc;
+  for (int i = 0; i < ny; ++i) MG_REQUIRE(ystarts[i] % 8 == 0, "%s: start %d along y is no multiple of 8", fn, ystarts[i]);
+  for (int i = 0; i < nx; ++i) MG_REQUIRE(xstarts[i] % 8 == 0, "%s: start %d along x is no multiple of 8", fn, xstarts[i]);
+  MG_REQUIRE((long long)Hw * Ww <= (1ll << 28), "%s: a canvas of %d x %d is not supported", fn, Hw, Ww);
+  MG_REQUIRE(first >= 0 && count >= 1 && (long long)first + count <= (long long)ny * nx, "%s: tiles [%d, %d + %d) of a grid of %d x %d", fn, first,
+             first, count, ny, nx);
+  const tile_grid g = make_grid(ystarts, ny, xstarts, nx);
+  const dim3 grid((3 * th * tw / 8 + CROP_THREADS - 1) / CROP_THREADS, count);   // (th tw <= 2^26; count <= 1024)
+  if ((uintptr_t)src % 8 == 0 && (uintptr_t)dst % 8 == 0)
+    MG_LAUNCH(tile_crop_kernel<true>, grid, dim3(CROP_THREADS), 0, (hipStream_t)stream, src, hwc, Hw, Ww, th, tw, g, first, dst);
+  else
+    MG_LAUNCH(tile_crop_kernel<false>, grid, dim3(CROP_THREADS), 0, (hipStream_t)stream, src, hwc, Hw, Ww, th, tw, g, first, dst);
   if (!g_dry_run) MG_CHECK_HIP(hipGetLastError());
   return 0;
 }

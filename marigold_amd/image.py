@@ -674,6 +674,54 @@ class ModelImage:
                 "mg_model_predict_many", self._lib)
         return pred, unc, d16, pic, [list(info[4 * i:4 * i + 4]) for i in range(n)]
 
+    def predict_tiled(self, u8, seed, guide_config, tile_config, overlap, *, out_size=None, out_mode=0, lut=None, u16=False, picture=False,
+                      opts=None, mode=0, reciprocal=None, uncertainty=True, flags=True, tail_config=None):
+        """``mg_model_predict_tiled`` on the LARGE uint8 CUDA picture ``u8`` [Hin, Win, 3] (both multiples of 8): ``pipe.predict_tiled``
+        with ``match_input_res`` -> (pred fp32 [C, out_h, out_w] clipped, unc fp32 [Hin, Win] | None for a single member or unless
+        ``uncertainty``, u16 uint16 [out_h, out_w] | None unless ``u16``, picture uint8 [out_h, out_w, 3] | None unless ``picture``,
+        info = the guide's four numbers of ``mg_ensemble_depth``, flags int32 CUDA [n tiles] | None for normals or unless ``flags``:
+        ``mg_tile_fit``'s flag per tile - ``int(flags.sum())`` is ``degenerate_tiles``).  ``guide_config`` / ``tile_config``: indices of
+        ``find`` (the guide's is ignored for normals); ``tail_config``: None, or the configuration of n mod K tiles per call that runs the
+        short last group as ``map_images`` does (without it the group is padded: the same up to the arithmetic of the batch); ``overlap``: an int or (y, x); ``out_size``: None = the picture's size;
+        ``mode`` / ``reciprocal``: the resampling of the GUIDE's input as in ``predict_out`` (by default the reciprocal normalisation
+        when the guide is resampled).  The handle stays on the configuration it was on."""
+        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_tiled: a uint8 CUDA [H, W, 3] picture"
+        u8 = u8.contiguous()
+        Hin, Win = u8.shape[:2]
+        tile_config, guide_config = int(tile_config), int(guide_config)
+        if not 0 <= tile_config < len(self.configs):
+            raise ValueError(f"predict_tiled: tile configuration {tile_config} of {len(self.configs)}")
+        tc = self.configs[tile_config]
+        B, C, depth = tc[0], tc[6], tc[6] == 1
+        if reciprocal is None:
+            gc = self.configs[guide_config] if depth and 0 <= guide_config < len(self.configs) else None
+            reciprocal = gc is not None and (Hin, Win) != (gc[1], gc[2])
+        oy, ox = (int(overlap[0]), int(overlap[1])) if isinstance(overlap, (tuple, list)) else (int(overlap), int(overlap))
+        oh, ow = (Hin, Win) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        if lut is not None:
+            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_tiled: the colour table is uint8 CUDA [256, 3]"
+            lut = lut.contiguous()
+        tiled = L.MgTiledOpts(guide_config, tile_config, oy, ox, -1 if tail_config is None else int(tail_config))
+        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
+                                  None if lut is None else lut.data_ptr())
+        dev = u8.device
+        n_max = L.TILE_MAX_PER_AXIS ** 2
+        pred = torch.empty(C, max(oh, 0), max(ow, 0), device=dev, dtype=torch.float32)
+        unc = torch.empty(Hin, Win, device=dev, dtype=torch.float32) if B > 1 and uncertainty else None
+        d16 = torch.empty(max(oh, 0), max(ow, 0), device=dev, dtype=torch.uint16) if u16 else None
+        pic = torch.empty(max(oh, 0), max(ow, 0), 3, device=dev, dtype=torch.uint8) if picture else None
+        flg = torch.zeros(n_max, device=dev, dtype=torch.int32) if depth and flags else None
+        info = (ctypes.c_double * 4)()
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        L.check(self._lib.mg_model_predict_tiled(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
+                                                 int(seed) & ((1 << 64) - 1), ctypes.byref(tiled), None if opts is None else ctypes.byref(opts),
+                                                 ctypes.byref(out_opts), pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, ptr(flg),
+                                                 O.current_stream_handle()), "mg_model_predict_tiled", self._lib)
+        if flg is not None:   # the plan the call made: its number of tiles
+            from . import tiles as tiling
+            flg = flg[:len(tiling.plan((Hin, Win), (tc[1], tc[2]), (oy, ox)).origins)]
+        return pred, unc, d16, pic, list(info), flg
+
     def close(self):
         if self.handle:
             self._lib.mg_model_destroy(self.handle)

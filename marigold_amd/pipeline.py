@@ -496,13 +496,15 @@ class _MarigoldPipelineBase:
     # (``_device_out``), depth tiles are fitted - scale and shift each - to one ordinary low-resolution prediction of the whole picture
     # (tiles.fit), and the tiles are blended with feathered weights over the full-size canvas (tiles.blend).  DESIGN.md 6e.
     _device_out = False            # True only on the view predict_tiled predicts on: _finish stops in front of its read-back tail
+    _device_out_uncertainty = False   # on that view: _finish hands back the pair (prediction, uncertainty | None), both on the device
 
     _clip_range = (0, 1)           # of a finished prediction
 
     def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **finish):
         """``__call__``'s tail: the members of one image -> its output (``_tail``: the kind's pictures, read-backs and clip).  On the
         view ``predict_tiled`` predicts on it stops in front of ``_tail``: -> the clipped prediction on the device, [H,W] or [3,H,W]
-        (the clip is the one ``_tail`` applies on the host)."""
+        (the clip is the one ``_tail`` applies on the host) - or, where the view asks for it (``_device_out_uncertainty``), the pair of
+        that prediction and the ensemble's uncertainty, [H,W] fp32 on the device, None without one."""
         if target_preds is None:  # member-parallel non-root rank with a rooted gather
             return self._empty_output()
         if ensemble_size > 1:
@@ -512,7 +514,10 @@ class _MarigoldPipelineBase:
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
         if self._device_out:
-            return final_pred.squeeze().float().clamp(*self._clip_range)
+            final_pred = final_pred.squeeze().float().clamp(*self._clip_range)
+            if self._device_out_uncertainty:
+                return final_pred, None if pred_uncert is None else pred_uncert.squeeze().float()
+            return final_pred
         return self._tail(final_pred, pred_uncert, **finish)
 
     @torch.no_grad()
@@ -543,8 +548,16 @@ class _MarigoldPipelineBase:
         first and then tile by tile in row-major order, with ONE program in flight (``in_flight`` is taken as 1).  ``generator=None``:
         randomised, as in ``__call__``.
 
-        ``uncertainty`` is None in a tiled output, also for ``ensemble_size`` > 1: the tiles' uncertainties are not stitched.  A depth
-        output carries ``degenerate_tiles``, the number of tiles ``tiles.fit`` flagged.  Refused: the intrinsic-image pipeline,
+        Uncertainty.  With ``ensemble_size`` > 1 and ``ensemble_kwargs=dict(output_uncertainty=True)`` - the switch ``__call__``
+        honours - ``uncertainty`` is an [Hw, Ww] fp32 array at the WORKING size (like ``__call__``'s it is never resampled to the input
+        size); in every other case it is None.  Every tile's uncertainty u_i comes from the tile's own ensemble and stays on the device
+        beside its prediction.  Normals: ``tiles.blend(u, ...)``, the feathered mean of the tiles' uncertainties.  Depth: u_i is in units
+        of the tile's normalised depth and the stitched depth is s_i d_i + t_i, so the tile contributes s_i u_i:
+        ``tiles.blend(u, ..., coef=[(s_i, 0)])`` with the s_i of the depth's fit.  A degenerate tile has s_i = 0 and therefore
+        contributes 0 with its weight - where only such a tile covers a pixel the uncertainty there is 0, which says nothing about the
+        prediction; ``degenerate_tiles`` reports how many there are.  The guide's uncertainty is not used.
+
+        A depth output carries ``degenerate_tiles``, the number of tiles ``tiles.fit`` flagged.  Refused: the intrinsic-image pipeline,
         member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program`` and ``processing_res`` (``tiled_res`` and
         ``guide_res`` take its place)."""
         if self._kind not in ("depth", "normals"):
@@ -588,6 +601,7 @@ class _MarigoldPipelineBase:
             self.encode_empty_text()
         dev = copy.copy(self)   # shares engines, scheduler and lanes with this pipeline; its calls stop in front of the read-back
         dev._device_out = True
+        with_unc = call_kwargs.get("ensemble_size", 1) > 1 and bool((call_kwargs.get("ensemble_kwargs") or {}).get("output_uncertainty"))
 
         # the working picture on the device, [1,3,H,W] in the input's number format
         rgb = pil_to_tensor(image.convert("RGB")).unsqueeze(0) if isinstance(image, Image.Image) else image
@@ -601,19 +615,27 @@ class _MarigoldPipelineBase:
         coef = flags = None
         if self._kind == "depth":
             guide = dev(image, processing_res=guide_res, match_input_res=False, generator=generator, **call_kwargs)   # [hg,wg]
+        dev._device_out_uncertainty = with_unc   # (the guide above handed back its prediction alone; the tiles hand back pairs)
         preds = list(dev.map_images(crops, in_flight=in_flight, generators=tile_generators, images_per_program=tiles_per_program,
                                     processing_res=0, match_input_res=False, **call_kwargs))
+        uncert = None
+        if with_unc:
+            preds, uncert = [p for p, _ in preds], torch.stack([u for _, u in preds]).reshape(n, th, tw)
         preds = torch.stack(preds).reshape(n, self._pred_channels, th, tw)
         overlap = tiling._pair(tile_overlap, "tile_overlap")
         if self._kind == "depth":
             coef, flags = tiling.fit(preds[:, 0], plan.origins, guide, work_hw)
             final_pred = tiling.blend(preds, plan.origins, work_hw, overlap, coef=coef)
+            if with_unc:   # s_i u_i: the scale of the fit without its shift
+                uncert = tiling.blend(uncert, plan.origins, work_hw, overlap, coef=torch.stack([coef[:, 0], torch.zeros_like(coef[:, 0])], dim=1))
         else:
             final_pred = tiling.blend(preds, plan.origins, work_hw, overlap, normalize=True)
+            if with_unc:
+                uncert = tiling.blend(uncert, plan.origins, work_hw, overlap)
         final_pred = final_pred.unsqueeze(0)
         if match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
-        out = self._tail(final_pred, None, **finish)
+        out = self._tail(final_pred, uncert, **finish)
         if flags is not None:
             out.degenerate_tiles = int(flags.sum().item())
         return out

@@ -1,8 +1,9 @@
-"""Tiled predictions of a large picture: the plan of overlapping tiles, the scale-and-shift fit of depth tiles to a
-low-resolution guide and the feathered blend over the full-size canvas - ``mg_tile_plan`` / ``mg_tile_fit`` / ``mg_tile_blend``
-(csrc/tiles.hip; the contract is in include/marigold_hip.h).  ``fit`` and ``blend`` take CUDA tensors and run on the current stream;
-nothing here synchronises or reads a tile back.  ``MarigoldDepthPipeline.predict_tiled`` / ``MarigoldNormalsPipeline.predict_tiled``
-are built on these three."""
+"""Tiled predictions of a large picture: the plan of overlapping tiles, the gather of the tiles out of the uint8
+picture, the scale-and-shift fit of depth tiles to a low-resolution guide and the feathered blend over the full-size canvas -
+``mg_tile_plan`` / ``mg_tile_crop`` / ``mg_tile_fit`` / ``mg_tile_blend`` (csrc/tiles.hip; the contract is in include/marigold_hip.h).
+``crop``, ``fit`` and ``blend`` take CUDA tensors and run on the current stream; nothing here synchronises or reads a tile back.
+``MarigoldDepthPipeline.predict_tiled`` / ``MarigoldNormalsPipeline.predict_tiled`` are built on ``plan``, ``fit`` and ``blend``;
+``mg_model_predict_tiled`` on all four."""
 import ctypes
 from collections import namedtuple
 
@@ -57,6 +58,40 @@ def _lib_and_tiles(tiles, what, dims, lib):
     if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.dtype == torch.float32 and tiles.dim() == dims):
         raise ValueError(f"{what}: the tiles must be a {dims}-dimensional fp32 CUDA tensor")
     return lib if lib is not None else L.init(tiles.device.index or 0), tiles.contiguous()
+
+
+def crop(picture_u8, plan, first=0, count=None, out=None, lib=None):
+    """``count`` tiles of ``plan`` (a ``TilePlan``; default: all from ``first`` on), starting at tile ``first`` in row-major order,
+    gathered out of the uint8 CUDA picture in ONE launch (``mg_tile_crop``) -> uint8 CUDA [count, th, tw, 3] for a picture [H, W, 3],
+    [count, 3, th, tw] for a picture [3, H, W] or [1, 3, H, W]: what ``picture[..., y0:y0 + th, x0:x0 + tw]`` gives tile by tile.  The
+    picture may start at any byte.  ``out``: a contiguous uint8 CUDA tensor of count * 3 * th * tw elements to write into (any
+    alignment); the result is a view of it.  Runs on the current stream, does not synchronise."""
+    p = picture_u8
+    if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8):
+        raise ValueError("tiles.crop: the picture must be a uint8 CUDA tensor")
+    if p.dim() == 4 and p.shape[0] == 1:
+        p = p[0]
+    if p.dim() != 3 or 3 not in (p.shape[0], p.shape[-1]):
+        raise ValueError(f"tiles.crop: the picture must be [H, W, 3], [3, H, W] or [1, 3, H, W], got {tuple(picture_u8.shape)}")
+    hwc = p.shape[-1] == 3
+    p = p.contiguous()
+    Hw, Ww = (p.shape[0], p.shape[1]) if hwc else (p.shape[1], p.shape[2])
+    th, tw = plan.tile_hw
+    n = len(plan.origins)
+    first = int(first)
+    count = n - first if count is None else int(count)
+    ys, ny, xs, nx = _grid(plan.origins, n, "tiles.crop")
+    shape = (max(count, 0), th, tw, 3) if hwc else (max(count, 0), 3, th, tw)
+    lib = lib if lib is not None else L.init(p.device.index or 0)
+    with torch.cuda.device(p.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=p.device)
+        elif not (isinstance(out, torch.Tensor) and out.device == p.device and out.dtype == torch.uint8 and out.is_contiguous()
+                  and out.numel() == max(count, 0) * 3 * th * tw):
+            raise ValueError(f"tiles.crop: out must be a contiguous uint8 tensor of {max(count, 0) * 3 * th * tw} elements on the picture's device")
+        L.check(lib.mg_tile_crop(p.data_ptr(), int(hwc), Hw, Ww, th, tw, ys, ny, xs, nx, first, count, out.data_ptr(),
+                                 O.current_stream_handle()), "mg_tile_crop", lib)
+    return out.view(shape)
 
 
 def fit(tiles, origins, guide, canvas_hw, lib=None):
