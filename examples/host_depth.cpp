@@ -6,7 +6,7 @@
 // Run:                 ./host_depth model.mgimg rgb.f32 noise.f32 depth_out.f32
 //   rgb.f32   raw fp32 [1,3,H,W] in [-1,1];  noise.f32  raw fp32 [B,4,h,w] (the initial latents);  depth_out.f32  raw fp32 [H',W']
 // (tests/test_gpu_pipeline.py::test_model_image_from_a_c_host builds and runs it and compares with the Python pipeline bit for bit.)
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -50,10 +50,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mg_model_load: %s\n", mg_last_error());
     return 1;
   }
-  int cfg[16];
+  int cfg[MG_CFG_WORDS];
   CHECK(mg_model_info(m, cfg));
-  const int B = cfg[0], H = cfg[1], W = cfg[2], h = cfg[3], w = cfg[4], steps = cfg[5], C = cfg[6], Ho = cfg[11], Wo = cfg[12];
-  if (C != 1 || cfg[8] != 0) {
+  const int B = cfg[MG_CFG_MEMBERS], H = cfg[MG_CFG_HEIGHT], W = cfg[MG_CFG_WIDTH], h = cfg[MG_CFG_LATENT_H], w = cfg[MG_CFG_LATENT_W];
+  const int steps = cfg[MG_CFG_STEPS], C = cfg[MG_CFG_CHANNELS], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W];
+  if (C != 1 || cfg[MG_CFG_STEP_NOISES] != 0) {
     fprintf(stderr, "this example runs depth images with a noise-free (DDIM) scheduler\n");
     return 2;
   }

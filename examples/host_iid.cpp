@@ -14,7 +14,7 @@
 //   out_prefix.<t>.ppm    the picture of target t, binary PPM
 // The Python pipeline gives the same arrays, uncertainties and pictures, bit for bit, with generator=marigold_amd.NativeNoise(seed)
 // (tests/test_gpu_iid_c_host.py builds and runs this program and compares).
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,9 +81,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mg_model_load: %s\n", mg_last_error());
     return 1;
   }
-  int cfg[16];
+  int cfg[MG_CFG_WORDS];
   CHECK(mg_model_info(m, cfg));
-  const int B = cfg[0], H = cfg[1], W = cfg[2], steps = cfg[5], C = cfg[6], n = cfg[10], Ho = cfg[11], Wo = cfg[12];
+  const int B = cfg[MG_CFG_MEMBERS], H = cfg[MG_CFG_HEIGHT], W = cfg[MG_CFG_WIDTH], steps = cfg[MG_CFG_STEPS];
+  const int C = cfg[MG_CFG_CHANNELS], n = cfg[MG_CFG_MODALITIES], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W];
   const int oh = opts.out_h ? opts.out_h : Ho, ow = opts.out_w ? opts.out_w : Wo;
   printf("model image: %d member(s) of %dx%d, %d steps, %d target(s), %.1f MB on the device\n", B, H, W, steps, n,
          mg_model_device_bytes(m) / 1e6);

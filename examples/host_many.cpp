@@ -10,7 +10,7 @@
 //   out_prefix.<i>.f32 / .unc.f32 / .pgm / .ppm: the files host_picture.cpp writes, for picture i
 // The Python pipelines give the same arrays and pictures, bit for bit, with generators=[marigold_amd.NativeNoise(seed_i)]
 // (tests/test_gpu_predict_many_c_host.py builds and runs this program and compares).
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,9 +77,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mg_model_load: %s\n", mg_last_error());
     return 1;
   }
-  int cfg[16];
+  int cfg[MG_CFG_WORDS];
   CHECK(mg_model_info(m, cfg));
-  const int B = cfg[0], H = cfg[1], W = cfg[2], steps = cfg[5], C = cfg[6], post = cfg[7], Ho = cfg[11], Wo = cfg[12], K = cfg[13] ? cfg[13] : 1;
+  const int B = cfg[MG_CFG_MEMBERS], H = cfg[MG_CFG_HEIGHT], W = cfg[MG_CFG_WIDTH], steps = cfg[MG_CFG_STEPS], C = cfg[MG_CFG_CHANNELS];
+  const int post = cfg[MG_CFG_POST], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W], K = MG_CFG_PICTURES_OF(cfg);
   const bool depth = post == MG_POST_DEPTH;
   const int oh = out.out_h ? out.out_h : Ho, ow = out.out_w ? out.out_w : Wo;
   printf("model image: %d picture(s) per call, %d member(s) each, %dx%d, %d steps, %.1f MB on the device\n", K, B, H, W, steps,

@@ -10,7 +10,7 @@
 //                 16-bit binary PGM, pred_out.f32.pgm (65535 = far, the reference's 16-bit PNG values)
 // The Python pipelines give the same map, bit for bit, with generator=marigold_amd.NativeNoise(seed)
 // (tests/test_gpu_native_noise.py builds and runs this program and compares).
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,9 +54,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mg_model_load: %s\n", mg_last_error());
     return 1;
   }
-  int cfg[16];
+  int cfg[MG_CFG_WORDS];
   CHECK(mg_model_info(m, cfg));
-  const int B = cfg[0], H = cfg[1], W = cfg[2], steps = cfg[5], C = cfg[6], Ho = cfg[11], Wo = cfg[12];
+  const int B = cfg[MG_CFG_MEMBERS], H = cfg[MG_CFG_HEIGHT], W = cfg[MG_CFG_WIDTH], steps = cfg[MG_CFG_STEPS];
+  const int C = cfg[MG_CFG_CHANNELS], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W];
   printf("model image: %d member(s) of %dx%d, %d steps, %d prediction channel(s), %.1f MB on the device\n", B, H, W, steps, C,
          mg_model_device_bytes(m) / 1e6);
   std::vector<uint8_t> bytes((size_t)Hin * Win * 3);

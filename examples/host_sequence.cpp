@@ -11,7 +11,7 @@
 //   out_prefix.<k>.f32 / .unc.f32 / .pgm / .ppm: the files host_picture.cpp writes, for frame k, at Hin x Win (bilinear)
 // The Python pipelines give the same arrays and pictures, bit for bit, with generators=[marigold_amd.NativeNoise(seed_k)]
 // (tests/test_gpu_sequence.py builds and runs this program and compares).
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,9 +67,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "mg_model_load: %s\n", mg_last_error());
     return 1;
   }
-  int cfg[16];
+  int cfg[MG_CFG_WORDS];
   CHECK(mg_model_info(m, cfg));
-  const int B = cfg[0], H = cfg[1], W = cfg[2], steps = cfg[5], C = cfg[6], post = cfg[7], Ho = cfg[11], Wo = cfg[12];
+  const int B = cfg[MG_CFG_MEMBERS], H = cfg[MG_CFG_HEIGHT], W = cfg[MG_CFG_WIDTH], steps = cfg[MG_CFG_STEPS];
+  const int C = cfg[MG_CFG_CHANNELS], post = cfg[MG_CFG_POST], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W];
   const bool depth = post == MG_POST_DEPTH;
   printf("model image: %d member(s), %dx%d, %d steps; %d frame(s), strength %g\n", B, H, W, steps, n, (double)strength);
   mg_output_opts out = MG_OUTPUT_OPTS_DEFAULT;   // match_input_res: every output at the frame's size

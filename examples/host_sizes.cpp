@@ -12,7 +12,7 @@
 //   out_prefix.<i>.f32 / .unc.f32 / .pgm / .ppm: the files host_picture.cpp writes, for picture i, at Hi x Wi
 // The Python pipelines give the same arrays and pictures, bit for bit, with pipe(image, processing_res=res, match_input_res=True,
 // generator=marigold_amd.NativeNoise(seed)) (tests/test_gpu_model_configs.py builds and runs this program and compares).
-// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, cfg16[14] = 1) runs through this
+// A model image with the tiny autoencoder (export_model_image(..., tiny_vae=True), a version-3 file, MG_CFG_VAE = MG_VAE_TINY) runs through this
 // program unchanged: every size it uses comes from cfg16, where the latent and decoded sizes follow that VAE's ceiling rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,7 +88,7 @@ int main(int argc, char** argv) {
     const int Hin = atoi(a[1]), Win = atoi(a[2]), res = atoi(a[3]);
     const uint64_t seed = strtoull(a[4], nullptr, 0);
     // the configuration for this picture
-    int H, W, cfg[16];
+    int H, W, cfg[MG_CFG_WORDS];
     CHECK(mg_processed_size(Hin, Win, res, &H, &W));
     const int index = mg_model_find_config(m, H, W, members, -1, 1);
     if (index < 0) {
@@ -97,8 +97,8 @@ int main(int argc, char** argv) {
     }
     CHECK(mg_model_select(m, index));
     CHECK(mg_model_info(m, cfg));
-    const int B = cfg[0], C = cfg[6], Ho = cfg[11], Wo = cfg[12];
-    const bool depth = cfg[7] == MG_POST_DEPTH, picture = depth ? d_lut != nullptr : true;
+    const int B = cfg[MG_CFG_MEMBERS], C = cfg[MG_CFG_CHANNELS], Ho = cfg[MG_CFG_OUT_H], Wo = cfg[MG_CFG_OUT_W];
+    const bool depth = cfg[MG_CFG_POST] == MG_POST_DEPTH, picture = depth ? d_lut != nullptr : true;
     // the picture in, the outputs at its own size
     const size_t in_bytes = (size_t)Hin * Win * 3, n_out = (size_t)Hin * Win, n_unc = (size_t)Ho * Wo;
     std::vector<uint8_t> bytes(in_bytes), pic(3 * n_out);
@@ -151,7 +151,7 @@ int main(int argc, char** argv) {
     double sum = 0;
     for (float v : pred) sum += v;
     printf("picture %d: %d x %d -> configuration %d (%d x %d, %d member(s), %d steps): %s map %dx%dx%d written, mean %.6f%s%s\n", i, Hin, Win,
-           index, H, W, B, cfg[5], depth ? "depth" : "normals", C, Hin, Win, sum / pred.size(), B > 1 ? "; uncertainty" : "",
+           index, H, W, B, cfg[MG_CFG_STEPS], depth ? "depth" : "normals", C, Hin, Win, sum / pred.size(), B > 1 ? "; uncertainty" : "",
            picture ? "; picture" : "");
     HIPCHECK(hipFree(d_rgb));
     HIPCHECK(hipFree(d_pred));

@@ -82,11 +82,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   // the tile configuration: of the tile size, the most tiles per call
-  int cfg[16], K = 0;
+  int cfg[MG_CFG_WORDS], K = 0;
   for (int c = 0; c < mg_model_num_configs(m); ++c) {
     CHECK(mg_model_config_info(m, c, cfg));
-    const int k = cfg[13] ? cfg[13] : 1;
-    if (cfg[1] == th && cfg[2] == tw && k > K) {
+    const int k = MG_CFG_PICTURES_OF(cfg);
+    if (cfg[MG_CFG_HEIGHT] == th && cfg[MG_CFG_WIDTH] == tw && k > K) {
       tiled.tile_config = c;
       K = k;
     }
@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   CHECK(mg_model_config_info(m, tiled.tile_config, cfg));
-  const int B = cfg[0], steps = cfg[5], C = cfg[6], post = cfg[7];
+  const int B = cfg[MG_CFG_MEMBERS], steps = cfg[MG_CFG_STEPS], C = cfg[MG_CFG_CHANNELS], post = cfg[MG_CFG_POST];
   const bool depth = post == MG_POST_DEPTH;
   int Hg = 0, Wg = 0;
   if (depth) {
@@ -144,9 +144,9 @@ int main(int argc, char** argv) {
   if (n % K) {
     tiled.tail_config = mg_model_find_config(m, th, tw, B, steps, n % K);
     if (tiled.tail_config >= 0) {
-      int tail[16];
+      int tail[MG_CFG_WORDS];
       CHECK(mg_model_config_info(m, tiled.tail_config, tail));
-      if (tail[6] != C || tail[7] != post) tiled.tail_config = -1;
+      if (tail[MG_CFG_CHANNELS] != C || tail[MG_CFG_POST] != post) tiled.tail_config = -1;
     }
   }
   const bool picture = depth ? d_lut != nullptr : true;

@@ -871,10 +871,10 @@ void mg_program_destroy(mg_program* prog);
  * share are counted by mg_model_shared_bytes, below).  One stream at a time per model.
  *  mg_model_load(path, device): device >= 0 binds the library to that GPU (mg_init) and uploads; device < 0 = host-only: the
  *  image is parsed and relocated against fake addresses so that mg_model_validate can check every op's contract without a GPU.
- *  mg_model_info: cfg16 = B, H, W, latent h, latent w, steps, prediction channels, MG_POST_*, step-noise tensors, sizeof(mg_op),
- *  modalities, decoded H, decoded W, K.  cfg16[13] = K, the pictures per call the image was exported for
- *  (export_model_image(images_per_program=K)): 0 in an image of one picture per call - every image written before the field
- *  existed, and every K = 1 export since - else the written value, K > 1; B = cfg16[0] is then the members of EACH picture.
+ *  mg_model_info: cfg16 = the MG_CFG_WORDS configuration words, named by enum mg_cfg below.  cfg16[13] = K, the pictures per call the
+ *  image was exported for (export_model_image(images_per_program=K)), is MG_CFG_PICTURES: 0 in an image of one picture per call -
+ *  every image written before the field existed, and every K = 1 export since - else the written value, K > 1 (read it with
+ *  MG_CFG_PICTURES_OF); B = cfg16[MG_CFG_MEMBERS] is then the members of EACH picture.
  *  mg_model_vae_encode: rgb [1,3,H,W] in [-1,1] -> latent [1,4,h,w] (x 0.18215, posterior mean).
  *  mg_model_denoise: rgb_latent [1,4,h,w], x [B,C,h,w] in / out (the initial noise -> the denoised latent), step_noise
  *  [n][B,C,h,w] for the LCM scheduler's n noisy steps (NULL for DDIM).
@@ -883,6 +883,27 @@ void mg_program_destroy(mg_program* prog);
  *  [K,4,h,w]; x, latent and pred have K B rows, image-major (row i B + j = member j of picture i), step_noise [n][K B,C,h,w].
  *  mg_model_load checks that the slots of the three programs chain for K pictures of B members before anything can run. */
 typedef struct mg_model mg_model;
+/* The configuration words of mg_model_info / mg_model_config_info (and of the image file): position = word. */
+enum mg_cfg {
+  MG_CFG_MEMBERS = 0,       /* B: the ensemble members of each picture */
+  MG_CFG_HEIGHT = 1,        /* H x W: the size fed to the VAE */
+  MG_CFG_WIDTH = 2,
+  MG_CFG_LATENT_H = 3,      /* h x w */
+  MG_CFG_LATENT_W = 4,
+  MG_CFG_STEPS = 5,         /* scheduler steps */
+  MG_CFG_CHANNELS = 6,      /* prediction channels */
+  MG_CFG_POST = 7,          /* MG_POST_*: the decoder's pointwise tail */
+  MG_CFG_STEP_NOISES = 8,   /* step-noise tensors (the LCM scheduler's) */
+  MG_CFG_OP_BYTES = 9,      /* sizeof(mg_op) */
+  MG_CFG_MODALITIES = 10,   /* 1; an intrinsic-image model: its targets */
+  MG_CFG_OUT_H = 11,        /* the decoded size */
+  MG_CFG_OUT_W = 12,
+  MG_CFG_PICTURES = 13,     /* K, written 0 for 1: read it with MG_CFG_PICTURES_OF */
+  MG_CFG_VAE = 14,          /* MG_VAE_* */
+  MG_CFG_WORDS = 16         /* (word 15 is reserved, written 0) */
+};
+enum { MG_VAE_KL = 0, MG_VAE_TINY = 1 };
+#define MG_CFG_PICTURES_OF(cfg) ((cfg)[MG_CFG_PICTURES] ? (cfg)[MG_CFG_PICTURES] : 1)
 mg_model* mg_model_load(const char* path, int device);
 void mg_model_destroy(mg_model* m);
 int mg_model_info(const mg_model* m, int* cfg16);
@@ -925,14 +946,14 @@ long long mg_model_shared_bytes(const mg_model* m);
 mg_model* mg_model_replica(const mg_model* m);
 
 /* Model images with the TINY autoencoder (export_model_image(tiny_vae=True), a version-3 file in the version-2 layout, for one
- * configuration or several): cfg16[14] names the image's VAE - 0 an AutoencoderKL (every version-1 and version-2 image), 1 the tiny
+ * configuration or several): cfg[MG_CFG_VAE] names the image's VAE - MG_VAE_KL an AutoencoderKL (every version-1 and version-2 image), MG_VAE_TINY the tiny
  * autoencoder - and one image has one.  Where an AutoencoderKL image runs its encode and decode programs, a tiny image calls
  * mg_tiny_vae_encode (the K pictures of a call) and mg_tiny_vae_decode (all K B members, times the modalities, in ONE call; a member's
- * result does not depend on the batch) on the same named slots, on the caller's stream, with the tail cfg16[7], without
+ * result does not depend on the batch) on the same named slots, on the caller's stream, with the tail cfg[MG_CFG_POST], without
  * synchronising: in mg_model_vae_encode / mg_model_vae_decode and in every mg_model_predict*.  Nothing else differs, and a host written
  * for AutoencoderKL images runs a tiny one unchanged, provided it sizes its buffers from cfg16 as documented: the latent size
- * cfg16[3] x cfg16[4] is the tiny encoder's, a CEILING per stride-2 layer (30 x 44 -> 4 x 6) where the AutoencoderKL floors (3 x 5),
- * and the decoded size cfg16[11] x cfg16[12] is 8 x that (32 x 48), which may exceed the picture.  In the file the two VAE entries of a
+ * cfg[MG_CFG_LATENT_H] x cfg[MG_CFG_LATENT_W] is the tiny encoder's, a CEILING per stride-2 layer (30 x 44 -> 4 x 6) where the AutoencoderKL floors (3 x 5),
+ * and the decoded size cfg[MG_CFG_OUT_H] x cfg[MG_CFG_OUT_W] is 8 x that (32 x 48), which may exceed the picture.  In the file the two VAE entries of a
  * configuration hold no ops, only their slots (rgb, latent | latent, pred) and a workspace slot (ws) of at least
  * mg_tiny_vae_workspace_bytes - scratch of that configuration, in the region the configurations overlay; the members of struct
  * mg_tiny_vae lie in the shared weights (mg_model_shared_bytes; replicas read the same ones), recorded as (buffer, byte offset), the six
@@ -949,9 +970,9 @@ int mg_model_scratch_fill(mg_model* m, int byte, void* stream);
  * pipelines (marigold/marigold_depth_pipeline.py:154-338, marigold_normals_pipeline.py:139-308) up to match_input_res, for a host
  * that has neither torch nor a noise file.  All pointers are device pointers.  The chain: mg_rgb_prepare to the model's H x W (rgb
  * uint8 [Hin][Win][3] with hwc != 0, else [3][Hin][Win]; mode and reciprocal as in mg_rgb_prepare) -> encode -> MG_OP_RANDN of
- * stream 0 as the initial latents [B,C,h,w] -> denoise (an LCM image: step noise k = stream k + 1, cfg[8] of them) -> decode ->
+ * stream 0 as the initial latents [B,C,h,w] -> denoise (an LCM image: step noise k = stream k + 1, cfg[MG_CFG_STEP_NOISES] of them) -> decode ->
  * ensemble: depth by mg_ensemble_depth, normals by MG_OP_ENS_NORMALS, a single member (B == 1) is copied.  pred_out fp32 [channels]
- * [cfg[11]][cfg[12]] (the decoded size); unc_out fp32 [cfg[11]][cfg[12]] | NULL, written when B > 1 (the pipelines return none for
+ * [cfg[MG_CFG_OUT_H]][cfg[MG_CFG_OUT_W]] (the decoded size); unc_out fp32 [cfg[MG_CFG_OUT_H]][cfg[MG_CFG_OUT_W]] | NULL, written when B > 1 (the pipelines return none for
  * one member); info4 | NULL as in mg_ensemble_depth (zeros where no alignment ran).  opts NULL = the reference's defaults
  * (ensemble.py:39-49, :199-203), which MG_PREDICT_OPTS_DEFAULT spells out.  An intrinsic-image model is refused (its entry point is
  * mg_model_predict_iid, below).  The resampling
@@ -972,13 +993,13 @@ int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win,
 /* mg_model_predict carried on through match_input_res to what the pipelines return (marigold/marigold_depth_pipeline.py:306-329,
  * marigold_normals_pipeline.py:282-301) and what script/depth/run.py writes: the map at the size asked for, clipped, the 16-bit depth
  * and the picture.  Arguments up to opts are mg_model_predict's; the chain up to the ensemble is the same, call for call.  Then:
- * with out_opts.out_h x out_w set and different from the decoded size cfg[11] x cfg[12] the ensembled prediction - not the
+ * with out_opts.out_h x out_w set and different from the decoded size cfg[MG_CFG_OUT_H] x cfg[MG_CFG_OUT_W] the ensembled prediction - not the
  * uncertainty - is resampled to them (MG_OP_RESIZE in mode out_opts.out_mode); then one launch of the output stage on what was
  * stored to pred_out, clipping it in place: depth - MG_OP_COLORIZE with P_CLIPPED = P_DEPTH (clip to [0, 1], the 16-bit values, the
  * colour picture from out_opts.lut256x3, a DEVICE pointer to the colour map's 256 x 3 uint8 table); normals - mg_normals_finish (clip
  * to [-1, 1], the picture).
  *  pred_out    fp32 [channels][out_h][out_w] (the decoded size when out_h = out_w = 0), clipped
- *  unc_out     fp32 [cfg[11]][cfg[12]] | NULL, written when B > 1
+ *  unc_out     fp32 [cfg[MG_CFG_OUT_H]][cfg[MG_CFG_OUT_W]] | NULL, written when B > 1
  *  u16_out     uint16 [out_h][out_w] | NULL = uint16(pred_out * 65535), a depth model only
  *  picture_out uint8 [out_h][out_w][3] | NULL; a depth model needs out_opts.lut256x3 for it
  *  info4       as in mg_model_predict
@@ -1000,13 +1021,13 @@ int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int 
                          float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
                          void* stream);
 
-/* mg_model_predict_out for n pictures in ONE call, on an image exported for K >= n pictures per call (cfg16[13]): the pictures share
+/* mg_model_predict_out for n pictures in ONE call, on an image exported for K >= n pictures per call (cfg[MG_CFG_PICTURES]): the pictures share
  * one encode, one denoise and one decode program - the programs map_images(images_per_program=K) runs - and every stage before and
  * after them runs per picture, the very code of mg_model_predict_out (one picture is its n = K = 1 case).
  *  rgb         a HOST array of n DEVICE pointers, every picture uint8 Hin x Win in the layout `hwc` names
  *  seeds       a HOST array of n seeds: picture i draws what its lone call draws from seeds[i] (MG_OP_RANDN stream 0 = its B initial
  *              latents, stream k + 1 = its LCM step noise k), into rows [i B, (i + 1) B) of the denoise program
- *  pred_out    fp32 [n][channels][out_h][out_w], clipped     unc_out  fp32 [n][cfg[11]][cfg[12]] | NULL, written when B > 1
+ *  pred_out    fp32 [n][channels][out_h][out_w], clipped     unc_out  fp32 [n][cfg[MG_CFG_OUT_H]][cfg[MG_CFG_OUT_W]] | NULL, written when B > 1
  *  u16_out     uint16 [n][out_h][out_w] | NULL               picture_out uint8 [n][out_h][out_w][3] | NULL
  *  info4       double [n][4] | NULL, per picture as in mg_model_predict
  * opts and out_opts apply to every picture, with the defaults of mg_model_predict_out.  A call with n < K feeds picture n - 1 and its
@@ -1050,17 +1071,17 @@ int mg_model_predict_next(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int
                           void* stream, float strength);
 
 /* The same for an intrinsic-image model (appearance, lighting): __call__ of the reference's MarigoldIIDPipeline with fill_outputs
- * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[10] = n_targets
+ * (marigold/marigold_iid_pipeline.py:239-411) as ONE call.  It takes an intrinsic-image model only (MG_POST_UNIT, cfg[MG_CFG_MODALITIES] = n_targets
  * >= 1, 3 n_targets prediction channels, a DDIM image: the pipeline refuses the LCM scheduler and so does this call); a depth or
  * normals model is refused.  The chain up to the decoder is that of mg_model_predict, argument for argument; the denoised latent
  * [B, 4 n_targets, h, w] is the decoder's batch [B n_targets, 4, h, w] as it lies.  Then: B > 1 - one MG_OP_ENS_IID over the members,
  * straight out of the decoder's output (opts.reduction; unc_out, when given, receives the uncertainty); B == 1 - a copy, unc_out is
- * not written (the pipeline returns none).  With opts.out_h, out_w set and different from the decoded size cfg[11] x cfg[12] the
+ * not written (the pipeline returns none).  With opts.out_h, out_w set and different from the decoded size cfg[MG_CFG_OUT_H] x cfg[MG_CFG_OUT_W] the
  * ensembled prediction is resampled to them (the pipeline's match_input_res: MG_OP_RESIZE in mode opts.out_mode; the uncertainty
  * is not resampled, reference :378-385).  With pictures_out the targets' pictures are made of what was stored to pred_out
  * (MG_OP_IID_VIS; bit t of linear_bits / up_to_scale_bits describes target t).
  *  pred_out fp32 [3 n_targets][out_h][out_w] (the decoded size when out_h = out_w = 0)
- *  unc_out  fp32 [3 n_targets][cfg[11]][cfg[12]] | NULL
+ *  unc_out  fp32 [3 n_targets][cfg[MG_CFG_OUT_H]][cfg[MG_CFG_OUT_W]] | NULL
  *  pictures_out uint8 [n_targets][out_h][out_w][3] | NULL
  * opts NULL = MG_IID_OPTS_DEFAULT: the median, every target in sRGB space, no resampling.  The temporaries (input resampling,
  * the prediction before its resampling with that pass's intermediate, the picture stage's workspace) are the model's: allocated at the
@@ -1313,8 +1334,8 @@ int mg_tile_crop(const uint8_t* src, int hwc, int Hw, int Ww, int th, int tw, co
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with
  * mg_model_find_config:
- *  tiled.tile_config   the tiles' configuration: its size cfg[1] x cfg[2] is the tile size th x tw (multiples of 8, decoded at that
- *                      size, at most the picture's), K = cfg[13] >= 1 tiles per call, B = cfg[0] members each
+ *  tiled.tile_config   the tiles' configuration: its size cfg[MG_CFG_HEIGHT] x cfg[MG_CFG_WIDTH] is the tile size th x tw (multiples of 8, decoded at that
+ *                      size, at most the picture's), K = cfg[MG_CFG_PICTURES] >= 1 tiles per call, B = cfg[MG_CFG_MEMBERS] members each
  *  tiled.guide_config  depth only (ignored for normals): a configuration of ONE picture per call, of the same kind and with the same
  *                      B, whose size is the processed size of the guide (mg_processed_size(Hin, Win, guide_res))
  *  tiled.overlap_y/_x  the minimum overlap of neighbouring tiles

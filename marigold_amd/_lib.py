@@ -261,6 +261,12 @@ class MgLpipsNet(ctypes.Structure):
 
 TILE_MAX_PER_AXIS = 32   # MG_TILE_MAX_PER_AXIS
 TINY_VAE_LAYERS = 33   # MG_TINY_VAE_LAYERS: the 64 -> 64 layers of either half
+# enum mg_cfg: the configuration words of a model image (mg_model_info), position = word; "pictures" is written 0 for 1.  An image
+# holds CFG_WORDS of them: what lies behind the named ones is reserved, written 0
+CFG = ("members", "height", "width", "latent_h", "latent_w", "steps", "channels", "post", "step_noises", "op_bytes", "modalities",
+       "out_h", "out_w", "pictures", "vae")
+CFG_WORDS = 16
+VAE_KL, VAE_TINY = 0, 1   # MG_VAE_*: the word "vae"
 
 
 class MgTinyVae(ctypes.Structure):

@@ -1,16 +1,17 @@
-// Module-level entry points: a MODEL IMAGE (marigold_amd/image.py::export_model_image - the pipeline's three native programs
-// for one problem shape, their kernel-ready weights and a memory plan) loaded and run from C, no Python at run time.
+// The model image: its file format, loader, handle and stage entry points (csrc/predict.hip holds the one-call predictions over a
+// loaded image; csrc/model.h what the two files share).  A MODEL IMAGE (marigold_amd/image.py::export_model_image - the pipeline's three native programs
+// for one problem shape, their kernel-ready weights and a memory plan) is loaded and run from C, no Python at run time.
 // These are the seams the reference's single_infer calls (marigold/marigold_depth_pipeline.py:396-477):
 //   mg_model_vae_encode  = encode_rgb            (:479-496: vae.encoder -> quant_conv -> mean -> x 0.18215)
 //   mg_model_denoise     = the T-step loop       (:455-468: unet(cat(rgb_latent, x), t, ctx) + scheduler.step, all steps)
 //   mg_model_vae_decode  = decode_depth / _normals (:498-516 + :473-475: post_quant_conv -> decoder -> channel mean / clip / shift)
 // File layout (little endian; written by image.py with struct.pack - the two sides are kept in step by tests/test_host.py):
-//   header "MGIMG1", version, ABI, counts, cfg[16] | buffer table | program table (+ named slots) | blobs (64-byte aligned)
+//   header "MGIMG1", version, ABI, counts, the 16 configuration words (enum mg_cfg) | buffer table | program table (+ named slots) | blobs (64-byte aligned)
 // Version 2 holds several CONFIGURATIONS (problem shapes) of one model: header | configurations, scratch region | configuration
-// table (cfg[16] + three programs each) | buffer table | blobs.  The packed weights are stored once (kind 3, shared); every other
+// table (16 words + three programs each) | buffer table | blobs.  The packed weights are stored once (kind 3, shared); every other
 // buffer names its configuration.  A handle = the shared weights (reference-counted: mg_model_replica makes another handle over
 // them) + a private arena; mg_model_select picks the configuration the entry points act on.  A version-1 file is one configuration.
-// Version 3 is version 2 with the TINY autoencoder (csrc/tinyvae.hip) where the AutoencoderKL programs stand, cfg[14] = 1: the two VAE
+// Version 3 is version 2 with the TINY autoencoder (csrc/tinyvae.hip) where the AutoencoderKL programs stand, MG_CFG_VAE = MG_VAE_TINY: the two VAE
 // entries of a configuration hold no ops, only named slots (rgb, latent, ws | latent, pred, ws - all scratch of that configuration); behind
 // the buffer table lies one table more, the members of struct mg_tiny_vae as (shared buffer, byte offset).  The encode and decode
 // stages of such an image are mg_tiny_vae_encode / mg_tiny_vae_decode on those slots.
@@ -23,11 +24,9 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "model.h"
 
-extern "C" int mg_ens_align_minimize(const mg_op* reg_op, void* stream, int E, int affine, int reduction, double lam, const double* mean,
-                                     const double* C, float* st_host, const float* mm_host, double* x, double gtol, int maxiter,
-                                     double* fval, int* nit, int* nfev, int* status);
+using namespace mg_image;
 
 namespace {
 
@@ -35,9 +34,7 @@ namespace {
 struct ImgHeader {
   char magic[8];
   uint32_t version, abi, n_buffers, n_programs;
-  uint32_t cfg[16];   // B, H, W, h, w, steps, prediction channels, post, step noises, sizeof(mg_op), modalities, Hout, Wout,
-                      // pictures per call (0 = 1: images written before the field; B is then the members of EACH picture)
-                      // (version 2: the words of configuration 0)
+  uint32_t cfg[MG_CFG_WORDS];   // enum mg_cfg (version 2: the words of configuration 0)
 };
 struct ImgBuffer {
   uint64_t nbytes, file_off;   // file_off of a version-2 scratch buffer: its place in the scratch region
@@ -65,7 +62,7 @@ struct ImgV2 {   // version 2, after the header; then the configuration table, t
   uint64_t scratch_bytes;   // the scratch region: the largest configuration's scratch
 };
 struct ImgConfig {
-  uint32_t cfg[16];
+  uint32_t cfg[MG_CFG_WORDS];
   ImgProgram prog[3];
 };
 struct ImgTinyMember {   // version 3, after the buffer table: one per pointer of struct mg_tiny_vae, in the struct's order
@@ -74,7 +71,6 @@ struct ImgTinyMember {   // version 3, after the buffer table: one per pointer o
 };
 #pragma pack(pop)
 
-enum { VAE_KL = 0, VAE_TINY = 1 };   // cfg[14]
 constexpr int TINY_MEMBERS = (int)(sizeof(mg_tiny_vae) / sizeof(void*));
 constexpr int TINY_HALF = 4 + 2 * MG_TINY_VAE_LAYERS;
 constexpr uint32_t TINY_ABSENT = 0xffffffffu;
@@ -122,10 +118,14 @@ struct PlanProg {
   }
 };
 struct PlanConfig {
-  uint32_t cfg[16];
+  uint32_t words[MG_CFG_WORDS];   // as the file has them
+  Cfg cfg;
   PlanProg prog[3];
 };
-struct Plan {
+
+}  // namespace
+
+struct mg_image::Plan {
   uint32_t version = 1;
   bool tiny = false;                   // version 3: the VAE stages are the tiny autoencoder's calls
   ImgTinyMember tiny_net[TINY_MEMBERS] = {};   // (checked by parse_image)
@@ -135,7 +135,7 @@ struct Plan {
 };
 
 // The weights every handle over one image reads: freed with the last handle (std::shared_ptr counts, thread-safe)
-struct SharedMem {
+struct mg_image::SharedMem {
   char* base = nullptr;
   bool host_only = false;
   ~SharedMem() {
@@ -143,63 +143,11 @@ struct SharedMem {
   }
 };
 
-struct Slot {
-  std::string name;
-  char* ptr;
-  uint64_t nbytes;
-};
-struct Prog {
-  std::string name;
-  mg_program* prog = nullptr;
-  std::vector<Slot> slots;
-  const Slot* slot(const char* n) const {
-    for (const Slot& s : slots)
-      if (s.name == n) return &s;
-    return nullptr;
-  }
-};
-struct Config {
-  const uint32_t* cfg = nullptr;   // the plan's 16 words
-  Prog enc, den, dec;
-  int K = 1;                       // pictures per call (cfg[13], 0 = 1)
-};
-
-}  // namespace
-
-struct mg_model {
-  std::shared_ptr<const Plan> plan;
-  std::shared_ptr<SharedMem> shared;   // the shared weights (a version-1 image: none)
-  bool host_only = false;
-  int device = -1;
-  char* arena = nullptr;       // the handle's private allocation: every configuration's constants and zeroed state, then ONE scratch
-                               // region every configuration's scratch is laid over (host-only: a fake base address, never touched)
-  uint64_t arena_bytes = 0;
-  std::vector<char*> bufs;
-  std::vector<Config> configs;
-  mg_tiny_vae tiny_net = {};   // a tiny image: the network in the shared weights
-  int sel = 0;                 // the selected configuration: what every entry point below acts on
-  const Config& cur() const { return configs[sel]; }
-  void* predict_tmp = nullptr;       // the one-call predictions' input resampling temporary (fp32 [3][Hin][W], one picture's: the
-                                     // pictures of a call pass through it one after the other), grown on demand
-  uint64_t predict_tmp_bytes = 0;
-  void* out_tmp = nullptr;           // the one-call predictions' output temporaries (see out_tmp_layout), grown on demand
-  uint64_t out_tmp_bytes = 0;
-  void* seq_latent = nullptr;        // image sequences: the denoised latent of the frame before (the bytes of the x slot), allocated at the
-                                     // first mg_model_predict_next
-  uint64_t seq_bytes = 0;
-  bool seq_carried = false;          // seq_latent holds a frame of the selected configuration
-  const float* seq_call = nullptr;   // the strength, while mg_model_predict_next runs its prediction on this handle
-  void* tiled_tmp = nullptr;         // mg_model_predict_tiled's temporaries (see TiledTmp), grown on demand
-  uint64_t tiled_tmp_bytes = 0;
-};
-
 namespace {
 
 bool read_at(FILE* f, uint64_t off, void* dst, size_t n) {
   return fseek(f, (long)off, SEEK_SET) == 0 && fread(dst, 1, n, f) == n;
 }
-
-uint64_t r256(uint64_t b) { return (b + 255) / 256 * 256; }
 
 // May configuration `c` point into buffer `b`?  Its own buffers and the shared weights only.
 bool owns(const Plan& p, uint32_t c, uint32_t b) { return p.version == 1 || p.bufs[b].kind == KIND_SHARED || p.bufs[b].cfg == c; }
@@ -243,8 +191,9 @@ int parse_image(FILE* f, Plan* p) {
   ImgHeader h;
   MG_REQUIRE(read_at(f, 0, &h, sizeof(ImgHeader)), "mg_model_load: short read (header)");
   MG_REQUIRE(memcmp(h.magic, "MGIMG1\0\0", 8) == 0 && h.version >= 1 && h.version <= 3, "mg_model_load: not a model image (or an unknown version)");
-  MG_REQUIRE(h.abi == MG_ABI_VERSION && h.cfg[9] == sizeof(mg_op),
-             "mg_model_load: the image was written for ABI %u / %u-byte ops, this library is ABI %d / %zu", h.abi, h.cfg[9], MG_ABI_VERSION, sizeof(mg_op));
+  MG_REQUIRE(h.abi == MG_ABI_VERSION && h.cfg[MG_CFG_OP_BYTES] == sizeof(mg_op),
+             "mg_model_load: the image was written for ABI %u / %u-byte ops, this library is ABI %d / %zu", h.abi, h.cfg[MG_CFG_OP_BYTES], MG_ABI_VERSION,
+             sizeof(mg_op));
   p->version = h.version;
   p->tiny = h.version == 3;
   const bool multi = h.version >= 2;   // the layout of several configurations
@@ -344,8 +293,17 @@ int parse_image(FILE* f, Plan* p) {
   static const char* const want[3] = {"vae.encode", "denoise", "vae.decode"};
   for (uint32_t c = 0; c < v2.n_configs; ++c) {
     PlanConfig& pc = p->cfgs[c];
-    memcpy(pc.cfg, ct[c].cfg, sizeof(pc.cfg));
-    MG_REQUIRE(pc.cfg[9] == sizeof(mg_op), "mg_model_load: configuration %u was written for %u-byte ops, this library has %zu", c, pc.cfg[9], sizeof(mg_op));
+    memcpy(pc.words, ct[c].cfg, sizeof(pc.words));
+    // THE place the words are read by position.  The checks below are made on them as the file has them (unsigned: a corrupt word must
+    // not wrap into a plausible size); everything after the load reads pc.cfg
+    const uint32_t* g = pc.words;
+    const uint32_t B = g[MG_CFG_MEMBERS], H = g[MG_CFG_HEIGHT], W = g[MG_CFG_WIDTH], lh = g[MG_CFG_LATENT_H], lw = g[MG_CFG_LATENT_W];
+    const uint32_t C = g[MG_CFG_CHANNELS], post = g[MG_CFG_POST], Ho = g[MG_CFG_OUT_H], Wo = g[MG_CFG_OUT_W], vae = g[MG_CFG_VAE];
+    const uint64_t K = MG_CFG_PICTURES_OF(g), n = g[MG_CFG_MODALITIES];
+    pc.cfg = Cfg{(int)B, (int)H,  (int)W,  (int)lh, (int)lw, (int)g[MG_CFG_STEPS], (int)C, (int)post, (int)g[MG_CFG_STEP_NOISES],
+                 (int)n, (int)Ho, (int)Wo, (int)K,  (int)vae};
+    MG_REQUIRE(g[MG_CFG_OP_BYTES] == sizeof(mg_op), "mg_model_load: configuration %u was written for %u-byte ops, this library has %zu", c,
+               g[MG_CFG_OP_BYTES], sizeof(mg_op));
     for (int k = 0; k < 3; ++k) {
       if (int rc = parse_program(f, file_bytes, ct[c].prog[k], *p, c, p->tiny && k != 1, &pc.prog[k])) return rc;
       MG_REQUIRE(pc.prog[k].name == want[k], "mg_model_load: program %d is '%s', expected '%s'", k, pc.prog[k].name.c_str(), want[k]);
@@ -354,26 +312,24 @@ int parse_image(FILE* f, Plan* p) {
     const ImgSlot *d_in = pc.prog[2].slot("latent"), *d_out = pc.prog[2].slot("pred");
     MG_REQUIRE(e_in && e_out && rl && xs && d_in && d_out, "mg_model_load: a program lacks its input / output slots");
     // the three programs hand K pictures of B members on to each other: [K,3,H,W] -> [K,4,h,w]; [K B,...] -> the decoder -> [K B,C,Ho,Wo]
-    const uint32_t* g = pc.cfg;
-    const uint64_t K = g[13] ? g[13] : 1;
-    MG_REQUIRE(K < (1u << 20) && e_in->nbytes == K * 3 * g[1] * g[2] * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
-                   xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * g[0] * g[6] * g[11] * g[12] * 4,
-               "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", (int)K, g[0]);
-    MG_REQUIRE(g[14] == (p->tiny ? VAE_TINY : VAE_KL), "mg_model_load: configuration %u names VAE %u in cfg[14]: a version-%u image carries %s", c, g[14],
-               h.version, p->tiny ? "the tiny autoencoder (1)" : "an AutoencoderKL (0)");
+    MG_REQUIRE(K < (1u << 20) && e_in->nbytes == K * 3 * H * W * 4 && e_out->nbytes == rl->nbytes && xs->nbytes == d_in->nbytes &&
+                   xs->nbytes % (4 * K) == 0 && d_out->nbytes == K * B * C * Ho * Wo * 4,
+               "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) per call", (int)K, B);
+    MG_REQUIRE(vae == (uint32_t)(p->tiny ? MG_VAE_TINY : MG_VAE_KL), "mg_model_load: configuration %u names VAE %u in cfg[14]: a version-%u image carries %s",
+               c, vae, h.version, p->tiny ? "the tiny autoencoder (1)" : "an AutoencoderKL (0)");
     if (p->tiny) {
       // the calls' arguments: K pictures [K,3,H,W] -> [K,4,h,w] (a ceiling per stride-2 layer); K B n members [.,4,h,w] -> [.,C,8h,8w]
-      const uint64_t n = g[10], members = K * g[0] * n, cpred = g[7] == MG_POST_DEPTH ? 1 : 3;
-      MG_REQUIRE(g[1] >= 1 && g[2] >= 1 && g[1] <= (1u << 16) && g[2] <= (1u << 16) && g[0] >= 1 && n >= 1 && members < (1u << 20) &&
-                     (g[7] == MG_POST_NONE || g[7] == MG_POST_DEPTH || g[7] == MG_POST_NORMALS || g[7] == MG_POST_UNIT) &&
-                     g[3] == ceil8(g[1]) && g[4] == ceil8(g[2]) && g[11] == 8 * g[3] && g[12] == 8 * g[4] && g[6] == cpred * n &&
-                     e_out->nbytes == K * 4 * g[3] * g[4] * 4 && d_in->nbytes == members * 4 * g[3] * g[4] * 4,
+      const uint64_t members = K * B * n, cpred = post == MG_POST_DEPTH ? 1 : 3;
+      MG_REQUIRE(H >= 1 && W >= 1 && H <= (1u << 16) && W <= (1u << 16) && B >= 1 && n >= 1 && members < (1u << 20) &&
+                     (post == MG_POST_NONE || post == MG_POST_DEPTH || post == MG_POST_NORMALS || post == MG_POST_UNIT) && lh == ceil8(H) &&
+                     lw == ceil8(W) && Ho == 8 * lh && Wo == 8 * lw && C == cpred * n && e_out->nbytes == K * 4 * lh * lw * 4 &&
+                     d_in->nbytes == members * 4 * lh * lw * 4,
                  "mg_model_load: the image's slots do not chain for %d picture(s) of %u member(s) through the tiny VAE (%u x %u -> latent %u x %u -> %u x %u)",
-                 (int)K, g[0], g[1], g[2], g[3], g[4], g[11], g[12]);
+                 (int)K, B, H, W, lh, lw, Ho, Wo);
       const ImgSlot *e_ws = pc.prog[0].slot("ws"), *d_ws = pc.prog[2].slot("ws");
       MG_REQUIRE(e_ws && d_ws, "mg_model_load: a tiny VAE entry lacks its workspace slot");
-      const long long e_need = mg_tiny_vae_workspace_bytes(0, (int)K, (int)g[1], (int)g[2]);
-      const long long d_need = mg_tiny_vae_workspace_bytes(1, (int)members, (int)g[3], (int)g[4]);
+      const long long e_need = mg_tiny_vae_workspace_bytes(0, (int)K, (int)H, (int)W);
+      const long long d_need = mg_tiny_vae_workspace_bytes(1, (int)members, (int)lh, (int)lw);
       MG_REQUIRE(e_need > 0 && d_need > 0, "mg_model_load: configuration %u is beyond the tiny VAE's sizes (%s)", c, mg_last_error());
       MG_REQUIRE(e_ws->nbytes >= (uint64_t)e_need && d_ws->nbytes >= (uint64_t)d_need,
                  "mg_model_load: corrupt image - the tiny VAE's workspaces of configuration %u hold %llu and %llu bytes, the calls need %lld and %lld", c,
@@ -401,7 +357,7 @@ int instantiate(mg_model* m) {
   for (size_t c = 0; c < p.cfgs.size(); ++c) {
     Config& cf = m->configs[c];
     cf.cfg = p.cfgs[c].cfg;
-    cf.K = cf.cfg[13] ? (int)cf.cfg[13] : 1;
+    cf.words = p.cfgs[c].words;
     Prog* dst[3] = {&cf.enc, &cf.den, &cf.dec};
     for (int k = 0; k < 3; ++k) {
       const PlanProg& pp = p.cfgs[c].prog[k];
@@ -502,30 +458,32 @@ int replicate_into(mg_model* r, const mg_model* m) {
   return instantiate(r);
 }
 
-int copy_dd(void* dst, const void* src, uint64_t n, hipStream_t s) {
+}  // namespace
+
+int mg_image::copy_dd(void* dst, const void* src, uint64_t n, hipStream_t s) {
   MG_CHECK_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
 // The encode and the decode stage of the selected configuration, slot to slot on the caller's stream: the program of an AutoencoderKL
 // image; the plain calls of a tiny one (mg_model_load checked their arguments against the slots) - all K B n members in ONE decode
-int run_encode(const mg_model* m, void* stream) {
+int mg_image::run_encode(const mg_model* m, void* stream) {
   const Config& c = m->cur();
   if (!m->plan->tiny) return mg_program_run(c.enc.prog, stream);
+  const Cfg& g = c.cfg;
   const Slot* ws = c.enc.slot("ws");
-  return mg_tiny_vae_encode(&m->tiny_net, (const float*)c.enc.slot("rgb")->ptr, (float*)c.enc.slot("latent")->ptr, c.K, (int)c.cfg[1], (int)c.cfg[2],
-                            ws->ptr, (long long)ws->nbytes, stream);
+  return mg_tiny_vae_encode(&m->tiny_net, (const float*)c.enc.slot("rgb")->ptr, (float*)c.enc.slot("latent")->ptr, g.K, g.H, g.W, ws->ptr,
+                            (long long)ws->nbytes, stream);
 }
 
-int run_decode(const mg_model* m, void* stream) {
+int mg_image::run_decode(const mg_model* m, void* stream) {
   const Config& c = m->cur();
   if (!m->plan->tiny) return mg_program_run(c.dec.prog, stream);
+  const Cfg& g = c.cfg;
   const Slot* ws = c.dec.slot("ws");
-  return mg_tiny_vae_decode(&m->tiny_net, (const float*)c.dec.slot("latent")->ptr, (float*)c.dec.slot("pred")->ptr,
-                            c.K * (int)c.cfg[0] * (int)c.cfg[10], (int)c.cfg[3], (int)c.cfg[4], (int)c.cfg[7], ws->ptr, (long long)ws->nbytes, stream);
+  return mg_tiny_vae_decode(&m->tiny_net, (const float*)c.dec.slot("latent")->ptr, (float*)c.dec.slot("pred")->ptr, g.K * g.B * g.n_mod, g.h, g.w,
+                            g.post, ws->ptr, (long long)ws->nbytes, stream);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -581,16 +539,12 @@ void mg_model_destroy(mg_model* m) {
     for (Prog* p : {&c.enc, &c.den, &c.dec})
       if (p->prog) mg_program_destroy(p->prog);
   if (m->arena && !m->host_only) (void)hipFree(m->arena);
-  if (m->predict_tmp) (void)hipFree(m->predict_tmp);
-  if (m->out_tmp) (void)hipFree(m->out_tmp);
-  if (m->seq_latent) (void)hipFree(m->seq_latent);
-  if (m->tiled_tmp) (void)hipFree(m->tiled_tmp);
-  delete m;   // (the shared weights go with the last handle over them)
+  delete m;   // (its temporaries free themselves; the shared weights go with the last handle over them)
 }
 
 int mg_model_info(const mg_model* m, int* cfg16) {
   MG_REQUIRE(m && cfg16, "mg_model_info: null argument");
-  for (int i = 0; i < 16; ++i) cfg16[i] = (int)m->cur().cfg[i];
+  for (int i = 0; i < MG_CFG_WORDS; ++i) cfg16[i] = (int)m->cur().words[i];
   return 0;
 }
 
@@ -599,7 +553,7 @@ int mg_model_num_configs(const mg_model* m) { return m ? (int)m->configs.size() 
 int mg_model_config_info(const mg_model* m, int index, int* cfg16) {
   MG_REQUIRE(m && cfg16, "mg_model_config_info: null argument");
   MG_REQUIRE(index >= 0 && index < (int)m->configs.size(), "mg_model_config_info: configuration %d of %d", index, (int)m->configs.size());
-  for (int i = 0; i < 16; ++i) cfg16[i] = (int)m->configs[index].cfg[i];
+  for (int i = 0; i < MG_CFG_WORDS; ++i) cfg16[i] = (int)m->configs[index].words[i];
   return 0;
 }
 
@@ -610,12 +564,10 @@ int mg_model_find_config(const mg_model* m, int H, int W, int E, int steps, int 
   }
   std::string have;
   for (size_t c = 0; c < m->configs.size(); ++c) {
-    const uint32_t* g = m->configs[c].cfg;
-    const int k = m->configs[c].K;
-    if ((H < 0 || H == (int)g[1]) && (W < 0 || W == (int)g[2]) && (E < 0 || E == (int)g[0]) && (steps < 0 || steps == (int)g[5]) && (K < 0 || K == k))
-      return (int)c;
+    const Cfg& g = m->configs[c].cfg;
+    if ((H < 0 || H == g.H) && (W < 0 || W == g.W) && (E < 0 || E == g.B) && (steps < 0 || steps == g.steps) && (K < 0 || K == g.K)) return (int)c;
     char one[96];
-    snprintf(one, sizeof(one), "%s%u x %u (E %u, %u steps, K %d)", c ? ", " : "", g[1], g[2], g[0], g[5], k);
+    snprintf(one, sizeof(one), "%s%u x %u (E %u, %u steps, K %d)", c ? ", " : "", (unsigned)g.H, (unsigned)g.W, (unsigned)g.B, (unsigned)g.steps, g.K);
     if (have.size() < 600) have += one;
   }
   mg_set_error("mg_model_find_config: no configuration for %d x %d, E %d, %d steps, K %d (-1 = any); the image holds %s", H, W, E, steps, K, have.c_str());
@@ -643,7 +595,11 @@ int mg_processed_size(int Hin, int Win, int processing_res, int* H, int* W) {
   return 0;
 }
 
-long long mg_model_device_bytes(const mg_model* m) { return m ? (long long)(m->arena_bytes + m->predict_tmp_bytes + m->out_tmp_bytes + m->seq_bytes + m->tiled_tmp_bytes) : 0; }
+long long mg_model_device_bytes(const mg_model* m) {
+  uint64_t bytes = m ? m->arena_bytes : 0;
+  for (int k = 0; m && k < TMP_COUNT; ++k) bytes += m->tmp[k].bytes;
+  return (long long)bytes;
+}
 
 long long mg_model_shared_bytes(const mg_model* m) { return m ? (long long)m->plan->shared_bytes : 0; }
 
@@ -668,7 +624,8 @@ int mg_model_scratch_fill(mg_model* m, int byte, void* stream) {
   for (size_t i = 0; i < p.bufs.size(); ++i)   // (the configurations' scratch buffers overlay each other: some bytes are set twice)
     if (p.bufs[i].kind == KIND_SCRATCH) MG_CHECK_HIP(hipMemsetAsync(m->bufs[i], byte, p.bufs[i].nbytes, (hipStream_t)stream));
   // (the temporaries of a tiled prediction are scratch of the same kind: everything in them is written before it is read)
-  if (m->tiled_tmp) MG_CHECK_HIP(hipMemsetAsync(m->tiled_tmp, byte, m->tiled_tmp_bytes, (hipStream_t)stream));
+  const Tmp& tiled = m->tmp[TMP_TILED];
+  if (tiled.p) MG_CHECK_HIP(hipMemsetAsync(tiled.p, byte, tiled.bytes, (hipStream_t)stream));
   return 0;
 }
 
@@ -689,7 +646,7 @@ int mg_model_denoise(mg_model* m, const float* rgb_latent, float* x, const float
   const Slot *rl = c.den.slot("rgb_latent"), *xs = c.den.slot("x");
   if (int rc = copy_dd(rl->ptr, rgb_latent, rl->nbytes, s)) return rc;
   if (int rc = copy_dd(xs->ptr, x, xs->nbytes, s)) return rc;
-  const int n_noise = (int)c.cfg[8];
+  const int n_noise = c.cfg.n_noise;
   MG_REQUIRE(n_noise == 0 || step_noise, "mg_model_denoise: this scheduler draws noise in %d steps: pass [%d][B][C][h][w] floats", n_noise, n_noise);
   for (int k = 0; k < n_noise; ++k) {
     char nm[24];
@@ -714,613 +671,3 @@ int mg_model_vae_decode(mg_model* m, const float* latent, float* pred, void* str
 
 }  // extern "C"
 
-// ---- ensemble_depth as one call (marigold/util/ensemble.py:39-196; the Python form: marigold_amd/ensemble.py::ensemble_depth) ----
-namespace {
-struct DevBuf {   // frees on every exit path
-  void* p = nullptr;
-  bool host = false;
-  ~DevBuf() {
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-  }
-};
-mg_op make_median_op(const float* d, const float* st, float* med, float* mad, float* mm, void* scratch, int E, long long HW, int reduction,
-                     int has_shift) {
-  mg_op op;
-  memset(&op, 0, sizeof(op));
-  op.kind = MG_OP_ENS_DEPTH_MEDIAN;
-  op.i[MG_ENS_DEPTH_MEDIAN_I_E] = E;
-  op.i[MG_ENS_DEPTH_MEDIAN_I_REDUCTION] = reduction;
-  op.i[MG_ENS_DEPTH_MEDIAN_I_HAS_SHIFT] = has_shift;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_D] = (void*)d;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_ST] = (void*)st;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_MED] = med;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_MAD] = mad;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_MINMAX] = mm;
-  op.p[MG_ENS_DEPTH_MEDIAN_P_SCRATCH] = scratch;
-  op.l[MG_ENS_DEPTH_MEDIAN_L_HW] = HW;
-  return op;
-}
-}  // namespace
-
-extern "C" int mg_ensemble_depth(const float* preds, int E, int H, int W, int scale_invariant, int shift_invariant, int reduction,
-                                 double regularizer_strength, int max_iter, double tol, int max_res, float* depth_out, float* unc_out,
-                                 double* info4, void* stream) {
-  MG_REQUIRE(preds && depth_out && E >= 1 && H > 0 && W > 0, "ensemble_depth: bad arguments");
-  MG_REQUIRE(reduction == 0 || reduction == 1, "Unrecognized reduction method: %d.", reduction);                    // ensemble.py:86-87
-  MG_REQUIRE(scale_invariant || !shift_invariant, "Pure shift-invariant ensembling is not supported.");           // :88-89
-  MG_REQUIRE(scale_invariant, "Unrecognized alignment.");                                                          // :189-190
-  const hipStream_t s = (hipStream_t)stream;
-  const long long HW = (long long)H * W;
-  const int affine = scale_invariant && shift_invariant;
-  DevBuf scratch, st_dev, mm_dev;
-  MG_CHECK_HIP(hipMalloc(&scratch.p, 12288));
-  MG_CHECK_HIP(hipMalloc(&st_dev.p, sizeof(float) * 2 * E));
-  MG_CHECK_HIP(hipMalloc(&mm_dev.p, sizeof(float) * (2 + 2 * E)));
-  double fval = 0.0;
-  int nit = 0, nfev = 0, status = 0;
-  {
-    // --- the alignment (compute_param, :154-173) on the members, down-sampled with nearest-exact beyond max_res (:158-161)
-    const float* d_align = preds;
-    int Ha = H, Wa = W;
-    DevBuf small;
-    if (max_res > 0 && (H > W ? H : W) > max_res) {
-      const double f = (double)max_res / W < (double)max_res / H ? (double)max_res / W : (double)max_res / H;
-      Ha = (int)(H * f);
-      Wa = (int)(W * f);
-      MG_CHECK_HIP(hipMalloc(&small.p, sizeof(float) * (size_t)E * Ha * Wa));
-      if (int rc = mg_resize(preds, small.p, nullptr, E, H, W, Ha, Wa, /* nearest-exact */ 2, /* fp32 */ 0, stream)) return rc;
-      d_align = (const float*)small.p;
-    }
-    const long long HWa = (long long)Ha * Wa;
-    DevBuf sscratch, stats;
-    MG_CHECK_HIP(hipMalloc(&sscratch.p, sizeof(double) * 128 * (size_t)E * (E + 3)));
-    MG_CHECK_HIP(hipMalloc(&stats.p, sizeof(double) * (3 * (size_t)E + (size_t)E * E)));
-    mg_op so;
-    memset(&so, 0, sizeof(so));
-    so.kind = MG_OP_ENS_DEPTH_STATS;
-    so.i[MG_ENS_DEPTH_STATS_I_E] = E;
-    so.p[MG_ENS_DEPTH_STATS_P_D] = (void*)d_align;
-    so.p[MG_ENS_DEPTH_STATS_P_SCRATCH] = sscratch.p;
-    so.p[MG_ENS_DEPTH_STATS_P_OUT] = stats.p;
-    so.l[MG_ENS_DEPTH_STATS_L_HW] = HWa;
-    if (int rc = mg_launch(&so, stream)) return rc;
-    std::vector<double> hs(3 * (size_t)E + (size_t)E * E);
-    MG_CHECK_HIP(hipMemcpyAsync(hs.data(), stats.p, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, s));
-    MG_CHECK_HIP(hipStreamSynchronize(s));
-    const double *dmin = hs.data(), *dmax = dmin + E, *mean = dmax + E, *C = mean + E;
-    // init_param (:163-168): fp32 arithmetic, as the reference's torch ops
-    const int n = affine ? 2 * E : E;
-    std::vector<double> x(n), x0;
-    for (int i = 0; i < E; ++i) {
-      const float lo = (float)dmin[i], hi = (float)dmax[i];
-      if (affine) {
-        const float rng = hi - lo;
-        const float sc = 1.0f / (rng < 1e-6f ? 1e-6f : rng);   // clamp(min=1e-6): a NaN range stays NaN, as in ensemble.py::init_param
-        x[i] = (double)sc;
-        x[E + i] = (double)(-sc * lo);
-      } else {
-        x[i] = (double)(1.0f / (hi < 1e-6f ? 1e-6f : hi));
-      }
-    }
-    x0 = x;
-    // the regulariser's device pass reads its 2E parameters from, and writes its 2 + 2E results to, host-mapped memory
-    DevBuf st_host, mm_host;
-    st_host.host = mm_host.host = true;
-    MG_CHECK_HIP(hipHostMalloc(&st_host.p, sizeof(float) * 2 * E, hipHostMallocMapped));
-    MG_CHECK_HIP(hipHostMalloc(&mm_host.p, sizeof(float) * (2 + 2 * E), hipHostMallocMapped));
-    void *st_d = nullptr, *mm_d = nullptr;
-    MG_CHECK_HIP(hipHostGetDevicePointer(&st_d, st_host.p, 0));
-    MG_CHECK_HIP(hipHostGetDevicePointer(&mm_d, mm_host.p, 0));
-    const mg_op reg = make_median_op(d_align, (const float*)st_d, nullptr, nullptr, (float*)mm_d, scratch.p, E, HWa, reduction, affine);
-    if (int rc = mg_ens_align_minimize(&reg, stream, E, affine, reduction, regularizer_strength, mean, C, (float*)st_host.p,
-                                       (const float*)mm_host.p, x.data(), tol, max_iter, &fval, &nit, &nfev, &status))
-      return rc;
-    bool finite = status != 3;
-    for (double v : x) finite = finite && v == v && v - v == 0.0;
-    if (!finite) x = x0;   // the optimiser ended on non-finite parameters: fall back to the starting point (as the Python form)
-    std::vector<float> st(2 * (size_t)E, 0.f);
-    for (int i = 0; i < E; ++i) {
-      st[i] = (float)x[i];
-      st[E + i] = affine ? (float)x[E + i] : 0.f;
-    }
-    MG_CHECK_HIP(hipMemcpyAsync(st_dev.p, st.data(), sizeof(float) * st.size(), hipMemcpyHostToDevice, s));
-    MG_CHECK_HIP(hipStreamSynchronize(s));   // (st is a stack-lifetime host buffer)
-  }
-  // --- align -> lower-middle median (+ MAD) / mean (+ std) -> min / max normalisation (:175-194), all on the device
-  const mg_op fin = make_median_op(preds, (const float*)st_dev.p, depth_out, unc_out, (float*)mm_dev.p, scratch.p, E, HW, reduction, affine);
-  if (int rc = mg_launch(&fin, stream)) return rc;
-  mg_op no;
-  memset(&no, 0, sizeof(no));
-  no.kind = MG_OP_ENS_DEPTH_NORM;
-  no.i[MG_ENS_DEPTH_NORM_I_SHIFT_INVARIANT] = affine;
-  no.p[MG_ENS_DEPTH_NORM_P_MED] = depth_out;
-  no.p[MG_ENS_DEPTH_NORM_P_MAD] = unc_out;
-  no.p[MG_ENS_DEPTH_NORM_P_MINMAX] = mm_dev.p;
-  no.l[MG_ENS_DEPTH_NORM_L_HW] = HW;
-  if (int rc = mg_launch(&no, stream)) return rc;
-  MG_CHECK_HIP(hipStreamSynchronize(s));   // the temporaries above are freed on return
-  if (info4) { info4[0] = fval; info4[1] = nfev; info4[2] = nit; info4[3] = status; }
-  return 0;
-}
-
-// ---- the whole prediction as one call: bytes + seed -> ensembled map (__call__ of the reference's pipelines up to match_input_res:
-// marigold/marigold_depth_pipeline.py:229-312, marigold_normals_pipeline.py:215-290; with fill_outputs for the intrinsic-image
-// pipeline, marigold_iid_pipeline.py:239-411).  The stages hand their results on inside the model's own program slots; the members
-// are ensembled straight out of the decode program's output slot.
-namespace {
-
-// A temporary of the model: at least `need` bytes behind *p, allocated at the first call that needs it, replaced when a later call
-// needs more (mg_model_device_bytes counts *bytes, mg_model_destroy frees).
-int grow_tmp(void** p, uint64_t* bytes, uint64_t need) {
-  if (*bytes >= need) return 0;
-  if (*p) MG_CHECK_HIP(hipFree(*p));   // (hipFree waits for the work that still uses it)
-  *p = nullptr;
-  *bytes = 0;
-  MG_CHECK_HIP(hipMalloc(p, need));
-  *bytes = need;
-  return 0;
-}
-
-// Stages 1 to 5 of a one-call prediction, the same for every kind of model, for the n <= K pictures of one call: each picture into its
-// row of the encoder's input, ONE encode, each picture's noise into its B rows (MG_OP_RANDN of its own seed: stream 0 = the initial
-// latents, stream k + 1 = the LCM scheduler's step noise k - what its lone call draws), ONE denoise, ONE decode.  A call with n < K
-// feeds picture n - 1 and its seed to the spare rows too, so that nothing in the programs reads what an earlier call left; the
-// spare results are never read.  `who` names the entry point in the messages.  On return the K B members lie image-major in the
-// decode program's output slot, *preds.  One picture per call is the n = K = 1 case.
-int predict_members(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
-                    const uint64_t* seeds, void* stream, const float** preds) {
-  const uint32_t* cfg = m->cur().cfg;
-  const int K = m->cur().K, H = (int)cfg[1], W = (int)cfg[2], n_noise = (int)cfg[8];
-  MG_REQUIRE(Hin > 0 && Win > 0, "%s: bad input size %d x %d", who, Hin, Win);
-  const hipStream_t s = (hipStream_t)stream;
-  const Slot *e_in = m->cur().enc.slot("rgb"), *e_out = m->cur().enc.slot("latent"), *rl = m->cur().den.slot("rgb_latent"), *xs = m->cur().den.slot("x");
-  const Slot *d_in = m->cur().dec.slot("latent"), *d_out = m->cur().dec.slot("pred");
-  // (mg_model_load checked that the slots chain)
-  const uint64_t rgb_row = e_in->nbytes / K, x_rows = xs->nbytes / K;   // bytes per picture
-  // 1. picture i -> [1,3,H,W] in [-1, 1], row i of the encoder's input slot
-  float* tmp = nullptr;
-  if (mode != 2 && Hin != H && Win != W) {
-    if (int rc = grow_tmp(&m->predict_tmp, &m->predict_tmp_bytes, (uint64_t)3 * Hin * W * 4)) return rc;
-    tmp = (float*)m->predict_tmp;
-  }
-  for (int i = 0; i < K; ++i)
-    if (int rc = mg_rgb_prepare(rgb[i < n ? i : n - 1], hwc, Hin, Win, e_in->ptr + i * rgb_row, 0, H, W, mode, reciprocal, tmp, stream)) return rc;
-  // 2. encode
-  if (int rc = run_encode(m, stream)) return rc;
-  if (int rc = copy_dd(rl->ptr, e_out->ptr, rl->nbytes, s)) return rc;
-  // 3. the initial latents: stream 0; the LCM scheduler's step noises: stream k + 1
-  for (int i = 0; i < K; ++i)
-    if (int rc = mg_randn(seeds[i < n ? i : n - 1], 0, 0, (int64_t)(x_rows / 4), xs->ptr + i * x_rows, 0, stream)) return rc;
-  // (mg_model_predict_next, K = 1) the frame before, member by member, into the initial latents
-  if (m->seq_call && m->seq_carried)
-    if (int rc = mg_latent_carry((float*)xs->ptr, (const float*)m->seq_latent, (int64_t)(xs->nbytes / 4), *m->seq_call, stream)) return rc;
-  for (int k = 0; k < n_noise; ++k) {
-    char nm[24];
-    snprintf(nm, sizeof(nm), "noise%d", k);
-    const Slot* ns = m->cur().den.slot(nm);
-    MG_REQUIRE(ns && ns->nbytes == xs->nbytes, "%s: the image lacks slot %s", who, nm);
-    for (int i = 0; i < K; ++i)
-      if (int rc = mg_randn(seeds[i < n ? i : n - 1], (uint64_t)k + 1, 0, (int64_t)(x_rows / 4), ns->ptr + i * x_rows, 0, stream)) return rc;
-  }
-  // 4. denoise, 5. decode (an intrinsic-image model: the latent [B, 4 n, h, w] is the decoder's batch [B n, 4, h, w], the same bytes)
-  if (int rc = mg_program_run(m->cur().den.prog, stream)) return rc;
-  if (m->seq_call) {   // this frame's denoised latent, for the next one
-    if (int rc = copy_dd(m->seq_latent, xs->ptr, xs->nbytes, s)) return rc;
-    m->seq_carried = true;
-  }
-  if (int rc = copy_dd(d_in->ptr, xs->ptr, d_in->nbytes, s)) return rc;
-  if (int rc = run_decode(m, stream)) return rc;
-  *preds = (const float*)d_out->ptr;
-  return 0;
-}
-
-}  // namespace
-
-namespace {
-
-// out_h / out_w / out_mode of an entry point's options (0 x 0: the decoded size; max_pixels 0: no bound) -> the size to store
-int output_size(const char* who, int out_h, int out_w, int out_mode, long long max_pixels, int Ho, int Wo, int* oh, int* ow) {
-  MG_REQUIRE((out_h == 0 && out_w == 0) || (out_h > 0 && out_w > 0 && (!max_pixels || (long long)out_h * out_w <= max_pixels)),
-             "%s: bad output size %d x %d", who, out_h, out_w);
-  MG_REQUIRE(out_mode >= 0 && out_mode <= 2, "%s: out_mode must be 0 (bilinear), 1 (bicubic) or 2 (nearest-exact)", who);
-  *oh = out_h ? out_h : Ho;
-  *ow = out_w ? out_w : Wo;
-  return 0;
-}
-
-// The output temporaries of a one-call prediction, carved out of the model's out_tmp in this order (each part rounded up to 256
-// bytes): the ensembled map at the decoded size (several members AND a resize: the resize reads it), the resize's fp32 intermediate
-// [planes][Ho][out_w] (modes 0 / 1 when both sizes change), the picture stage's workspace (intrinsic images: [n][MG_IID_VIS_PARTS]
-// for a target that is linear and up to scale; depth and normals: none).
-struct OutTmp {
-  uint64_t ens = 0, rtmp = 0, ws = 0;
-  uint64_t total() const { return ens + rtmp + ws; }
-};
-OutTmp out_tmp_layout(int B, int planes, int Ho, int Wo, int oh, int ow, int out_mode, uint64_t ws_bytes) {
-  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
-  OutTmp t;
-  const bool resize = oh != Ho || ow != Wo;
-  if (resize && B > 1) t.ens = r256((uint64_t)planes * Ho * Wo * 4);
-  if (resize && out_mode != 2 && oh != Ho && ow != Wo) t.rtmp = r256((uint64_t)planes * Ho * ow * 4);
-  t.ws = r256(ws_bytes);
-  return t;
-}
-
-// Stages 1 to 7 of a one-call prediction of n pictures: the members (predict_members), then for picture i, one after the other,
-// 6. ensemble(i, members, dst) -> int: its B members in the decoder's output slot -> the ensembled map (one member: the pipelines
-//    return it as it is, without an uncertainty, and `ensemble` is not called),
-// 7. match_input_res (marigold_depth_pipeline.py:306-312, marigold_normals_pipeline.py:282-288, marigold_iid_pipeline.py:378-385):
-//    the prediction only, [planes][Ho][Wo] -> row i of pred_out [n][planes][oh][ow],
-// 8. finish(i, row i of pred_out) -> int: the entry point's output stage on what was stored.
-// The temporaries serve the pictures in turn (the stream orders them).  *ws (may be null): the picture workspace of ws_bytes, valid
-// until the model's next prediction.
-template <class Ensemble, class Finish>
-int predict_resized(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
-                    const uint64_t* seeds, int planes, int oh, int ow, int out_mode, uint64_t ws_bytes, float* pred_out, float** ws, void* stream,
-                    Ensemble ensemble, Finish finish) {
-  const int B = (int)m->cur().cfg[0], Ho = (int)m->cur().cfg[11], Wo = (int)m->cur().cfg[12];
-  const bool resize = oh != Ho || ow != Wo;
-  const OutTmp t = out_tmp_layout(B, planes, Ho, Wo, oh, ow, out_mode, ws_bytes);
-  if (int rc = grow_tmp(&m->out_tmp, &m->out_tmp_bytes, t.total())) return rc;
-  float* const ens = (float*)m->out_tmp;
-  float* const rtmp = t.rtmp ? (float*)((char*)m->out_tmp + t.ens) : nullptr;
-  if (ws) *ws = t.ws ? (float*)((char*)m->out_tmp + t.ens + t.rtmp) : nullptr;
-  const float* all = nullptr;
-  if (int rc = predict_members(m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, stream, &all)) return rc;
-  for (int i = 0; i < n; ++i) {
-    const float* preds = all + (uint64_t)i * B * planes * Ho * Wo;
-    float* const out = pred_out + (uint64_t)i * planes * oh * ow;
-    const float* final_pred = preds;   // at the decoded size
-    if (B > 1) {
-      float* const dst = resize ? ens : out;
-      if (int rc = ensemble(i, preds, dst)) return rc;
-      final_pred = dst;
-    }
-    if (resize) {
-      if (int rc = mg_resize(final_pred, out, rtmp, planes, Ho, Wo, oh, ow, out_mode, 0, stream)) return rc;
-    } else if (B == 1) {
-      if (int rc = copy_dd(out, preds, (uint64_t)planes * Ho * Wo * 4, (hipStream_t)stream)) return rc;
-    }
-    if (int rc = finish(i, out)) return rc;
-  }
-  return 0;
-}
-
-// Stages 1 to 8 of a depth / normals prediction of n pictures; unc_out [n][Ho][Wo], info4 [n][4], the pictures of the output stage
-// (u16_out [n][oh][ow], picture_out [n][oh][ow][3]; `clip`: the output stage runs - mg_model_predict stores the map as it is)
-int predict_depth_or_normals(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
-                             const uint64_t* seeds, const mg_predict_opts* opts_or_null, int oh, int ow, int out_mode, bool clip,
-                             const uint8_t* lut256x3, float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null,
-                             uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
-  const uint32_t* cfg = m->cur().cfg;
-  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], Ho = (int)cfg[11], Wo = (int)cfg[12];
-  static const mg_predict_opts defaults = MG_PREDICT_OPTS_DEFAULT;
-  const mg_predict_opts& o = opts_or_null ? *opts_or_null : defaults;
-  if (info4_or_null)
-    for (int i = 0; i < 4 * n; ++i) info4_or_null[i] = 0.0;
-  const uint64_t HWo = (uint64_t)Ho * Wo, hw = (uint64_t)oh * ow;
-  return predict_resized(
-      m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, C, oh, ow, out_mode, 0, pred_out, nullptr, stream,
-      [&](int i, const float* preds, float* dst) {
-        float* const unc = unc_out_or_null ? unc_out_or_null + i * HWo : nullptr;
-        if (post == MG_POST_DEPTH)
-          return mg_ensemble_depth(preds, B, Ho, Wo, o.scale_invariant, o.shift_invariant, o.reduction, o.regularizer_strength, o.max_iter, o.tol,
-                                   o.max_res, dst, unc, info4_or_null ? info4_or_null + 4 * i : nullptr, stream);
-        MG_REQUIRE(o.normals_reduction == 0 || o.normals_reduction == 1, "Unrecognized reduction method: %d.", o.normals_reduction);
-        return mg_ensemble_normals(preds, dst, unc, B, (int64_t)HWo, o.normals_reduction, stream);
-      },
-      // 8. the output stage on what was stored, in place: the clip (:314-316 / :294), the 16-bit depth (script/depth/run.py), the picture
-      [&](int i, float* out) {
-        if (!clip) return 0;
-        uint8_t* const pic = picture_out_or_null ? picture_out_or_null + i * hw * 3 : nullptr;
-        if (post == MG_POST_DEPTH)
-          return mg_depth_visualize(out, lut256x3, (int64_t)hw, out, u16_out_or_null ? u16_out_or_null + i * hw : nullptr, pic, stream);
-        return mg_normals_finish(out, oh, ow, out, pic, stream);
-      });
-}
-
-// The output-option refusals of mg_model_predict_out, in `who`'s name, for a model of the kind (post, C) whose stitched or ensembled
-// map is Ho x Wo -> the size to store
-int check_output_opts(const char* who, int post, int C, const mg_output_opts& q, int Ho, int Wo, const uint16_t* u16_out_or_null,
-                      const uint8_t* picture_out_or_null, int* oh, int* ow) {
-  const bool depth = post == MG_POST_DEPTH && C == 1;
-  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
-  if (int rc = output_size(who, q.out_h, q.out_w, q.out_mode, 1ll << 30, Ho, Wo, oh, ow)) return rc;
-  if (depth) {
-    MG_REQUIRE(!picture_out_or_null || q.lut256x3, "%s: the picture of a depth model needs out_opts.lut256x3 (the colour table)", who);
-  } else {
-    MG_REQUIRE(!u16_out_or_null && !q.lut256x3, "%s: u16_out and lut256x3 belong to a depth model, this one predicts normals", who);
-  }
-  return 0;
-}
-
-// mg_model_predict_out and mg_model_predict_many after their own argument checks: the refusals they share (in `who`'s name), then the
-// prediction.  One picture is n = 1.
-int predict_out_many(mg_model* m, const char* who, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
-                     const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
-                     float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null, void* stream) {
-  const uint32_t* cfg = m->cur().cfg;
-  const int C = (int)cfg[6], post = (int)cfg[7];
-  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "%s: an intrinsic-image model goes through mg_model_predict_iid", who);
-  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
-  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
-  int oh, ow;
-  if (int rc = check_output_opts(who, post, C, q, (int)cfg[11], (int)cfg[12], u16_out_or_null, picture_out_or_null, &oh, &ow)) return rc;
-  return predict_depth_or_normals(m, who, n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, oh, ow, q.out_mode, true, q.lut256x3,
-                                  pred_out, unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
-}
-
-}  // namespace
-
-// An image of several pictures per call runs through mg_model_predict_many only
-#define MG_REQUIRE_ONE_PICTURE(m, who) \
-  MG_REQUIRE((m)->cur().K == 1, who ": this image runs %d pictures per call: use mg_model_predict_many", (m)->cur().K)
-
-extern "C" int mg_model_predict(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                const mg_predict_opts* opts_or_null, float* pred_out, float* unc_out_or_null, double* info4_or_null,
-                                void* stream) {
-  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict: bad arguments (or a host-only model)");
-  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict");
-  const uint32_t* cfg = m->cur().cfg;
-  const int C = (int)cfg[6], post = (int)cfg[7];
-  MG_REQUIRE(post != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict: intrinsic-image models are not supported yet");
-  MG_REQUIRE((post == MG_POST_DEPTH && C == 1) || (post == MG_POST_NORMALS && C == 3), "mg_model_predict: a depth or a normals image is required");
-  // the map at the decoded size: no resize, no temporaries
-  return predict_depth_or_normals(m, "mg_model_predict", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, (int)cfg[11], (int)cfg[12], 0,
-                                  false, nullptr, pred_out, unc_out_or_null, nullptr, nullptr, info4_or_null, stream);
-}
-
-extern "C" int mg_model_predict_out(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                    const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
-                                    float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
-                                    void* stream) {
-  MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_out: null argument (the model, the picture and pred_out are required)");
-  MG_REQUIRE(!m->host_only, "mg_model_predict_out: a host-only model cannot predict (load it with device >= 0)");
-  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_out");
-  return predict_out_many(m, "mg_model_predict_out", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, out_opts_or_null, pred_out,
-                          unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
-}
-
-extern "C" int mg_model_seq_reset(mg_model* m) {
-  MG_REQUIRE(m, "mg_model_seq_reset: null model");
-  m->seq_carried = false;
-  return 0;
-}
-
-extern "C" int mg_model_predict_next(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                     const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null, float* pred_out,
-                                     float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null, double* info4_or_null,
-                                     void* stream, float strength) {
-  MG_REQUIRE(m && rgb && pred_out, "mg_model_predict_next: null argument (the model, the picture and pred_out are required)");
-  MG_REQUIRE(!m->host_only, "mg_model_predict_next: a host-only model cannot predict (load it with device >= 0)");
-  MG_REQUIRE(m->cur().K == 1, "mg_model_predict_next: this configuration runs %d pictures per call: a sequence runs one frame per call (K = 1)", m->cur().K);
-  MG_REQUIRE(strength >= 0.f && strength <= 1.f, "mg_model_predict_next: strength %g is not in [0, 1]", (double)strength);
-  const uint32_t* cfg = m->cur().cfg;
-  MG_REQUIRE((int)cfg[7] != MG_POST_UNIT && cfg[10] == 1, "mg_model_predict_next: an intrinsic-image model goes through mg_model_predict_iid");
-  const uint64_t need = m->cur().den.slot("x")->nbytes;
-  if (m->seq_bytes < need) m->seq_carried = false;
-  if (int rc = grow_tmp(&m->seq_latent, &m->seq_bytes, need)) return rc;
-  m->seq_call = &strength;
-  const int rc = predict_out_many(m, "mg_model_predict_next", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, out_opts_or_null, pred_out,
-                                  unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
-  m->seq_call = nullptr;
-  if (rc) m->seq_carried = false;   // a frame that failed carries nothing on
-  return rc;
-}
-
-extern "C" int mg_model_predict_many(mg_model* m, int n, const uint8_t* const* rgb, int hwc, int Hin, int Win, int mode, int reciprocal,
-                                     const uint64_t* seeds, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
-                                     float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
-                                     double* info4_or_null, void* stream) {
-  MG_REQUIRE(m, "mg_model_predict_many: null model");
-  MG_REQUIRE(!m->host_only, "mg_model_predict_many: a host-only model cannot predict (load it with device >= 0)");
-  MG_REQUIRE(n >= 1 && n <= m->cur().K, "mg_model_predict_many: %d pictures for an image of %d per call (1 <= n <= %d)", n, m->cur().K, m->cur().K);
-  MG_REQUIRE(rgb && seeds && pred_out, "mg_model_predict_many: null argument (the rgb and seeds arrays and pred_out are required)");
-  for (int i = 0; i < n; ++i) MG_REQUIRE(rgb[i], "mg_model_predict_many: null picture %d of %d", i, n);
-  return predict_out_many(m, "mg_model_predict_many", n, rgb, hwc, Hin, Win, mode, reciprocal, seeds, opts_or_null, out_opts_or_null, pred_out,
-                          unc_out_or_null, u16_out_or_null, picture_out_or_null, info4_or_null, stream);
-}
-
-// ---- the tiled prediction of a large picture as one call (pipe.predict_tiled): plan -> guide -> tiles, a group of K per
-// call of the tile configuration's programs -> fit and blend -> resize -> output stage.  Every stage is the code the calls above and
-// csrc/tiles.hip already run; this function only strings them together.
-namespace {
-
-// mg_model_predict_tiled's temporaries, carved out of the model's tiled_tmp in this order, each part rounded up to 256 bytes
-struct TiledTmp {
-  uint64_t crops = 0, maps = 0, unc = 0, fit_ws = 0, coef = 0, coef_unc = 0, flags = 0, guide = 0, canvas = 0, rtmp = 0;
-  uint64_t total() const { return crops + maps + unc + fit_ws + coef + coef_unc + flags + guide + canvas + rtmp; }
-};
-
-// the handle goes back to the configuration it was on, on every way out
-struct Reselect {
-  mg_model* m;
-  int sel;
-  ~Reselect() { m->sel = sel; }
-};
-
-}  // namespace
-
-extern "C" int mg_model_predict_tiled(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                      const mg_tiled_opts* tiled, const mg_predict_opts* opts_or_null, const mg_output_opts* out_opts_or_null,
-                                      float* pred_out, float* unc_out_or_null, uint16_t* u16_out_or_null, uint8_t* picture_out_or_null,
-                                      double* info4_or_null, int* degenerate_or_null, void* stream) {
-  const char* who = "mg_model_predict_tiled";
-  MG_REQUIRE(m && rgb && tiled && pred_out, "%s: null argument (the model, the picture, tiled and pred_out are required)", who);
-  const int n_cfg = (int)m->configs.size();
-  MG_REQUIRE(tiled->tile_config >= 0 && tiled->tile_config < n_cfg, "%s: tile configuration %d of %d", who, tiled->tile_config, n_cfg);
-  const Config& tc = m->configs[tiled->tile_config];
-  const int B = (int)tc.cfg[0], th = (int)tc.cfg[1], tw = (int)tc.cfg[2], C = (int)tc.cfg[6], post = (int)tc.cfg[7], K = tc.K;
-  MG_REQUIRE(post != MG_POST_UNIT && tc.cfg[10] == 1, "%s: an intrinsic-image model is not supported (depth and normals only)", who);
-  const bool depth = post == MG_POST_DEPTH && C == 1;
-  MG_REQUIRE(depth || (post == MG_POST_NORMALS && C == 3), "%s: a depth or a normals image is required", who);
-  MG_REQUIRE(Hin >= 8 && Win >= 8 && Hin % 8 == 0 && Win % 8 == 0, "%s: the picture size %d x %d must be multiples of 8 (the call works at the picture's size)",
-             who, Hin, Win);
-  MG_REQUIRE((long long)Hin * Win <= (1ll << 28) && Hin <= 65535, "%s: a picture of %d x %d is not supported", who, Hin, Win);
-  MG_REQUIRE(th % 8 == 0 && tw % 8 == 0 && (int)tc.cfg[11] == th && (int)tc.cfg[12] == tw && (long long)th * tw <= (1ll << 26),
-             "%s: the tile configuration's size %d x %d (decoded %d x %d) must be multiples of 8, decoded at that size", who, th, tw, (int)tc.cfg[11],
-             (int)tc.cfg[12]);
-  MG_REQUIRE(th <= Hin && tw <= Win, "%s: the tile configuration's size %d x %d exceeds the picture %d x %d", who, th, tw, Hin, Win);
-  // 1. the plan
-  int ys[MG_TILE_MAX_PER_AXIS], xs[MG_TILE_MAX_PER_AXIS];
-  const int ny = mg_tile_plan(Hin, th, tiled->overlap_y, ys, MG_TILE_MAX_PER_AXIS);
-  const int nx = ny < 1 ? -1 : mg_tile_plan(Win, tw, tiled->overlap_x, xs, MG_TILE_MAX_PER_AXIS);
-  if (nx < 1) {
-    const std::string why = mg_last_error();
-    mg_set_error("%s: %s", who, why.c_str());
-    return 2;
-  }
-  const int n = ny * nx;
-  MG_REQUIRE(n > 1, "%s: the plan is ONE tile (the picture is the tile): use mg_model_predict_out", who);
-  int hg = 0, wg = 0;
-  if (depth) {
-    MG_REQUIRE(tiled->guide_config >= 0 && tiled->guide_config < n_cfg, "%s: guide configuration %d of %d", who, tiled->guide_config, n_cfg);
-    const Config& gc = m->configs[tiled->guide_config];
-    MG_REQUIRE(gc.K == 1, "%s: the guide configuration runs %d pictures per call, the guide is ONE picture (K = 1)", who, gc.K);
-    MG_REQUIRE((int)gc.cfg[0] == B, "%s: the guide configuration has %d members, the tile configuration %d", who, (int)gc.cfg[0], B);
-    MG_REQUIRE((int)gc.cfg[7] == post && (int)gc.cfg[6] == C && gc.cfg[10] == 1, "%s: the guide configuration is of another kind than the tile configuration", who);
-    hg = (int)gc.cfg[11];
-    wg = (int)gc.cfg[12];
-    MG_REQUIRE(hg >= 1 && wg >= 1 && (long long)hg * wg <= (1ll << 26), "%s: bad guide size %d x %d", who, hg, wg);
-  }
-  // the short last group: r tiles, whole on a configuration of r pictures per call, or padded on the tile configuration
-  const int r = n % K;
-  const bool tail = r != 0 && tiled->tail_config != -1;
-  if (tail) {
-    MG_REQUIRE(tiled->tail_config >= 0 && tiled->tail_config < n_cfg, "%s: tail configuration %d of %d", who, tiled->tail_config, n_cfg);
-    const Config& lc = m->configs[tiled->tail_config];
-    MG_REQUIRE(lc.K == r, "%s: the tail configuration runs %d pictures per call, the short last group has %d tiles (%d tiles, %d per call)", who, lc.K,
-               r, n, K);
-    MG_REQUIRE((int)lc.cfg[0] == B && (int)lc.cfg[7] == post && (int)lc.cfg[6] == C && lc.cfg[10] == 1 && (int)lc.cfg[1] == th && (int)lc.cfg[2] == tw &&
-                   (int)lc.cfg[11] == th && (int)lc.cfg[12] == tw,
-               "%s: the tail configuration is of another kind, size (%d x %d) or member count (%d) than the tile configuration (%d x %d, %d)", who,
-               (int)lc.cfg[1], (int)lc.cfg[2], (int)lc.cfg[0], th, tw, B);
-  }
-  static const mg_output_opts out_defaults = MG_OUTPUT_OPTS_DEFAULT;
-  const mg_output_opts& q = out_opts_or_null ? *out_opts_or_null : out_defaults;
-  int oh, ow;
-  if (int rc = check_output_opts(who, post, C, q, Hin, Win, u16_out_or_null, picture_out_or_null, &oh, &ow)) return rc;
-  MG_REQUIRE((uintptr_t)pred_out % 16 == 0 && (uintptr_t)unc_out_or_null % 16 == 0, "%s: pred_out and unc_out must be 16-byte aligned", who);
-  MG_REQUIRE((uintptr_t)degenerate_or_null % 4 == 0, "%s: degenerate must be aligned to its elements", who);
-  if (opts_or_null && !depth)
-    MG_REQUIRE(opts_or_null->normals_reduction == 0 || opts_or_null->normals_reduction == 1, "%s: Unrecognized reduction method: %d.", who,
-               opts_or_null->normals_reduction);
-  MG_REQUIRE(!m->host_only, "%s: a host-only model cannot predict (load it with device >= 0)", who);
-
-  // the temporaries
-  auto r256 = [](uint64_t b) { return (b + 255) / 256 * 256; };
-  const bool with_unc = B > 1 && unc_out_or_null, resize = oh != Hin || ow != Win;
-  const uint64_t tile_px = (uint64_t)th * tw;
-  TiledTmp t;
-  t.crops = r256((uint64_t)K * 3 * tile_px);
-  t.maps = r256((uint64_t)n * C * tile_px * 4);
-  if (with_unc) t.unc = r256((uint64_t)n * tile_px * 4);
-  if (depth) {
-    t.fit_ws = r256((uint64_t)mg_tiles_workspace_bytes(n, th, tw));
-    t.coef = r256((uint64_t)n * 16);
-    if (with_unc) t.coef_unc = r256((uint64_t)n * 16);
-    if (!degenerate_or_null) t.flags = r256((uint64_t)n * 4);
-    t.guide = r256((uint64_t)hg * wg * 4);
-  }
-  if (resize) {
-    t.canvas = r256((uint64_t)C * Hin * Win * 4);
-    if (q.out_mode != 2 && oh != Hin && ow != Win) t.rtmp = r256((uint64_t)C * Hin * ow * 4);
-  }
-  if (int rc = grow_tmp(&m->tiled_tmp, &m->tiled_tmp_bytes, t.total())) return rc;
-  char* at = (char*)m->tiled_tmp;
-  auto carve = [&](uint64_t bytes) {
-    char* p = bytes ? at : nullptr;
-    at += bytes;
-    return p;
-  };
-  uint8_t* const crops = (uint8_t*)carve(t.crops);
-  float* const maps = (float*)carve(t.maps);
-  float* const uncs = (float*)carve(t.unc);
-  void* const fit_ws = carve(t.fit_ws);
-  double* const coef = (double*)carve(t.coef);
-  double* const coef_unc = (double*)carve(t.coef_unc);
-  int* const own_flags = (int*)carve(t.flags);
-  int* const flags = degenerate_or_null ? degenerate_or_null : own_flags;
-  float* const guide = (float*)carve(t.guide);
-  float* const canvas = resize ? (float*)carve(t.canvas) : pred_out;
-  float* const rtmp = (float*)carve(t.rtmp);
-  const hipStream_t s = (hipStream_t)stream;
-
-  Reselect back = {m, m->sel};
-  if (info4_or_null)
-    for (int i = 0; i < 4; ++i) info4_or_null[i] = 0.0;
-  // 2. the guide: one ordinary prediction of the whole picture at the guide configuration's size, clipped
-  if (depth) {
-    m->sel = tiled->guide_config;
-    if (int rc = predict_depth_or_normals(m, who, 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, opts_or_null, hg, wg, 0, true, nullptr, guide,
-                                          nullptr, nullptr, nullptr, info4_or_null, stream))
-      return rc;
-  }
-  // 3. the tiles, a group of K per call
-  std::vector<const uint8_t*> pics((size_t)K);
-  std::vector<uint64_t> seeds((size_t)K);
-  for (int first = 0; first < n; first += K) {
-    const int cnt = n - first < K ? n - first : K;
-    m->sel = cnt < K && tail ? tiled->tail_config : tiled->tile_config;
-    if (int rc = mg_tile_crop(rgb, hwc, Hin, Win, th, tw, ys, ny, xs, nx, first, cnt, crops, stream)) return rc;
-    for (int i = 0; i < cnt; ++i) {
-      pics[i] = crops + (uint64_t)i * 3 * tile_px;
-      seeds[i] = seed + 1 + (uint64_t)(first + i);   // (mod 2^64)
-    }
-    if (int rc = predict_depth_or_normals(m, who, cnt, pics.data(), hwc, th, tw, 0, 1, seeds.data(), opts_or_null, th, tw, 0, true, nullptr,
-                                          maps + (uint64_t)first * C * tile_px, with_unc ? uncs + (uint64_t)first * tile_px : nullptr, nullptr, nullptr,
-                                          nullptr, stream))
-      return rc;
-  }
-  // 4. the stitch
-  const int oy = tiled->overlap_y, ox = tiled->overlap_x;
-  if (depth) {
-    if (int rc = mg_tile_fit(maps, th, tw, ys, ny, xs, nx, Hin, Win, guide, hg, wg, coef, flags, fit_ws, (long long)t.fit_ws, stream)) return rc;
-    if (int rc = mg_tile_blend(maps, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, coef, 0, canvas, stream)) return rc;
-    if (with_unc) {   // (s_i, 0): the scales of the fit without its shifts
-      MG_CHECK_HIP(hipMemsetAsync(coef_unc, 0, (size_t)n * 16, s));
-      MG_CHECK_HIP(hipMemcpy2DAsync(coef_unc, 16, coef, 16, 8, (size_t)n, hipMemcpyDeviceToDevice, s));
-      if (int rc = mg_tile_blend(uncs, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, coef_unc, 0, unc_out_or_null, stream)) return rc;
-    }
-  } else {
-    if (int rc = mg_tile_blend(maps, 3, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, nullptr, 1, canvas, stream)) return rc;
-    if (with_unc)
-      if (int rc = mg_tile_blend(uncs, 1, th, tw, ys, ny, xs, nx, Hin, Win, oy, ox, nullptr, 0, unc_out_or_null, stream)) return rc;
-  }
-  // 5. match_input_res, then the output stage of mg_model_predict_out on what was stored
-  if (resize)
-    if (int rc = mg_resize(canvas, pred_out, rtmp, C, Hin, Win, oh, ow, q.out_mode, 0, stream)) return rc;
-  if (depth) return mg_depth_visualize(pred_out, q.lut256x3, (int64_t)oh * ow, pred_out, u16_out_or_null, picture_out_or_null, stream);
-  return mg_normals_finish(pred_out, oh, ow, pred_out, picture_out_or_null, stream);
-}
-
-extern "C" int mg_model_predict_iid(mg_model* m, const uint8_t* rgb, int hwc, int Hin, int Win, int mode, int reciprocal, uint64_t seed,
-                                    const mg_iid_opts* opts_or_null, float* pred_out, float* unc_out_or_null, uint8_t* pictures_out_or_null,
-                                    void* stream) {
-  MG_REQUIRE(m && !m->host_only && rgb && pred_out, "mg_model_predict_iid: bad arguments (or a host-only model)");
-  MG_REQUIRE_ONE_PICTURE(m, "mg_model_predict_iid");
-  const uint32_t* cfg = m->cur().cfg;
-  const int B = (int)cfg[0], C = (int)cfg[6], post = (int)cfg[7], n_noise = (int)cfg[8], n = (int)cfg[10];
-  const int Ho = (int)cfg[11], Wo = (int)cfg[12];
-  MG_REQUIRE(post == MG_POST_UNIT && n >= 1 && C == 3 * n,
-             "mg_model_predict_iid: an intrinsic-image model is required (a depth or a normals image goes through mg_model_predict)");
-  // MarigoldIIDPipeline._check_inference_step (marigold_iid_pipeline.py:443-447) raises on the LCM scheduler: so does its C form
-  MG_REQUIRE(n_noise == 0, "mg_model_predict_iid: This pipeline implementation does not support the LCMScheduler (the image draws noise in %d steps)", n_noise);
-  static const mg_iid_opts defaults = MG_IID_OPTS_DEFAULT;
-  const mg_iid_opts& o = opts_or_null ? *opts_or_null : defaults;
-  MG_REQUIRE(o.reduction == 0 || o.reduction == 1, "mg_model_predict_iid: Unrecognized reduction method: %d.", o.reduction);
-  int oh, ow;
-  if (int rc = output_size("mg_model_predict_iid", o.out_h, o.out_w, o.out_mode, 0, Ho, Wo, &oh, &ow)) return rc;
-  MG_REQUIRE(n <= 16 && !((unsigned)(o.linear_bits | o.up_to_scale_bits) >> n), "mg_model_predict_iid: a flag names a target beyond the %d of the model (at most 16)", n);
-  const uint64_t ws_bytes = pictures_out_or_null && (o.linear_bits & o.up_to_scale_bits) ? (uint64_t)n * MG_IID_VIS_PARTS * 4 : 0;
-  float* ws = nullptr;
-  // 6. the ensemble is ensemble_iid (:369-375)
-  return predict_resized(
-      m, "mg_model_predict_iid", 1, &rgb, hwc, Hin, Win, mode, reciprocal, &seed, C, oh, ow, o.out_mode, ws_bytes, pred_out, &ws, stream,
-      [&](int, const float* preds, float* dst) { return mg_ensemble_iid(preds, B, (int64_t)C * Ho * Wo, o.reduction, dst, unc_out_or_null, stream); },
-      // 8. the pictures of what was stored (fill_outputs -> MarigoldIIDOutput.fill_entry, :117-136, :393-411)
-      [&](int, float* out) {
-        if (!pictures_out_or_null) return 0;
-        return mg_iid_visualize(out, pictures_out_or_null, ws, n, oh, ow, o.linear_bits, o.up_to_scale_bits, stream);
-      });
-}

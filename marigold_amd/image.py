@@ -18,7 +18,7 @@ through the C loader.
 
 An image of several configurations (version 2) has the same parts with one more table in front:
 
-    header | configurations, scratch region | configuration table (cfg[16] + three programs each) | buffer table | blobs
+    header | configurations, scratch region | configuration table (16 words + three programs each) | buffer table | blobs
 
 The modules' packed weights (``mod.ws.cache``) are written once, as buffers every configuration refers to; the loader keeps them in
 an allocation that ``mg_model_replica`` handles share.  A call with the keywords of one configuration writes the version-1 file it
@@ -45,7 +45,6 @@ VERSION = 1
 VERSION_CONFIGS = 2   # several configurations in one image (export_model_image(configs=[...]))
 VERSION_TINY = 3      # the tiny autoencoder instead of the AutoencoderKL (export_model_image(tiny_vae=True)): the version-2 layout, the
                       # two VAE entries of a configuration without ops, one table more (the members of struct mg_tiny_vae)
-VAE_KL, VAE_TINY = 0, 1   # cfg[14]
 TINY_MEMBER, TINY_ABSENT = "<IIQ", 0xFFFFFFFF   # a member of mg_tiny_vae: buffer (TINY_ABSENT: a NULL member), pad, byte offset
 KIND_SCRATCH, KIND_ZERO, KIND_DATA, KIND_SHARED = 0, 1, 2, 3   # SHARED: the weight cache of a version-2 image, stored once
 SLOT_LN_COUNTERS = 100   # relocation slot of MG_OP_IGEMM's ticket address pair (ops.igemm_tickets); slots 0..15 = p[k]
@@ -155,7 +154,7 @@ def _build_tiny_vae(pipe, K, B, n_mod, height, width, post, cpred):
 
 
 def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_program=1):
-    """The three programs of one configuration, built (or found) in the modules of ``pipe``, and its 16 ``cfg`` words."""
+    """The three programs of one configuration, built (or found) in the modules of ``pipe``, and its 16 words (``_lib.CFG``)."""
     K = int(images_per_program)
     if K < 1:
         raise ValueError(f"export_model_image: images_per_program must be >= 1 (got {images_per_program})")
@@ -196,10 +195,11 @@ def _build(pipe, ensemble_size, height, width, denoising_steps=None, images_per_
     progs = [enc,
              ("denoise", den.seq, dict({"rgb_latent": den.rgb_latent, "x": den.x}, **{f"noise{k}": nz for k, nz in enumerate(den.noises)})),
              dec]
-    sz_op = ctypes.sizeof(L.MgOp)
-    cfg = [B, height, width, h, w, T, cpred * n_mod, post, len(den.noises), sz_op, n_mod, out_hw[0], out_hw[1],
-           K if K > 1 else 0, VAE_TINY if tiny else VAE_KL, 0]
-    return progs, [int(c) for c in cfg]
+    words = dict(members=B, height=height, width=width, latent_h=h, latent_w=w, steps=T, channels=cpred * n_mod, post=post,
+                 step_noises=len(den.noises), op_bytes=ctypes.sizeof(L.MgOp), modalities=n_mod, out_h=out_hw[0], out_w=out_hw[1],
+                 pictures=K if K > 1 else 0, vae=L.VAE_TINY if tiny else L.VAE_KL)
+    assert set(words) == set(L.CFG), "model image: every configuration word is named once"
+    return progs, [int(words[name]) for name in L.CFG] + [0] * (L.CFG_WORDS - len(L.CFG))
 
 
 def _plan(pipe, progs, cache_kind=KIND_DATA):
@@ -317,13 +317,14 @@ def _write_programs(f, ptab, ops_off, rel_off, relocs_all):
 def _describe(path, total, bufs, ptab, cfg):
     """What ``export_model_image`` returns for one configuration.  ``arena``: the device bytes the loader places (every buffer
     rounded up to 256): the weight cache, the configuration's own constants and zeroed state, its scratch."""
-    items = bufs.items
+    items, c = bufs.items, dict(zip(L.CFG, cfg))
     nbytes = {k: sum(it[1] - it[0] for it in items if it[2] == k) for k in (KIND_SCRATCH, KIND_ZERO, KIND_DATA, KIND_SHARED)}
     arena = {k: sum(_r256(it[1] - it[0]) for it in items if it[2] in ks)
              for k, ks in (("shared", (KIND_SHARED,)), ("private", (KIND_ZERO, KIND_DATA)), ("scratch", (KIND_SCRATCH,)))}
     return dict(path=path, file_bytes=total, buffers=len(items), scratch_bytes=nbytes[KIND_SCRATCH], zero_bytes=nbytes[KIND_ZERO],
-                data_bytes=nbytes[KIND_DATA] + nbytes[KIND_SHARED], ops={n: c for (n, c, _s) in ptab}, latent_hw=(cfg[3], cfg[4]), B=cfg[0],
-                steps=cfg[5], pred_channels=cfg[6], step_noises=cfg[8], images_per_program=cfg[13] or 1, cfg16=list(cfg), arena=arena)
+                data_bytes=nbytes[KIND_DATA] + nbytes[KIND_SHARED], ops={n: k for (n, k, _s) in ptab}, latent_hw=(c["latent_h"], c["latent_w"]),
+                B=c["members"], steps=c["steps"], pred_channels=c["channels"], step_noises=c["step_noises"],
+                images_per_program=c["pictures"] or 1, cfg16=list(cfg), arena=arena)
 
 
 def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=None, width=None, denoising_steps=None, images_per_program=1,
@@ -334,7 +335,7 @@ def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=N
 
     ``images_per_program`` = K > 1: the image runs K pictures per call (``mg_model_predict_many``) through the programs
     ``map_images(images_per_program=K)`` runs for a full group - one encode of K pictures, one denoising program of K x
-    ``ensemble_size`` members, one decode; the header's ``cfg[13]`` is K.  K = 1 writes the one-picture image, ``cfg[13]`` = 0.
+    ``ensemble_size`` members, one decode; the header's word ``pictures`` (``_lib.CFG``) is K.  K = 1 writes the one-picture image, ``pictures`` = 0.
 
     ``configs`` = a list of dicts of the keywords above (instead of them): ONE image for several configurations - a version-2 file
     with a configuration table and one buffer table, the modules' packed weights stored once (kind ``KIND_SHARED``) and each
@@ -345,7 +346,7 @@ def export_model_image(pipe, path, *, configs=None, ensemble_size=None, height=N
     ``tiny_vae=True``: the pipeline's VAE is an ``AutoencoderTinyHIP`` (``pipe.set_vae(load_tiny_vae(...))``) and the image runs it:
     ``mg_tiny_vae_encode`` / ``mg_tiny_vae_decode`` where an AutoencoderKL image runs its encode and decode programs, all members of a
     call in one decode.  Such an image is a NEW FILE VERSION (3, for one configuration or several, in the layout of version 2 with the
-    members of ``struct mg_tiny_vae`` as one more table; ``cfg[14]`` = 1, the latent size ``cfg[3:5]`` by the tiny encoder's ceiling
+    members of ``struct mg_tiny_vae`` as one more table; the word ``vae`` = ``VAE_TINY``, the latent size by the tiny encoder's ceiling
     rule): no library built before the version existed can read it, which is why it is written on request only.  Without the
     keyword a pipeline with a tiny VAE is refused as before, and an AutoencoderKL pipeline writes the version-1 / version-2 bytes it
     always wrote.  One image has one VAE; the dict returned for one configuration is that of a version-1 export plus ``shared_bytes``
@@ -445,7 +446,7 @@ def _export_configs(pipe, path, configs, tiny=False):
             members += struct.pack(TINY_MEMBER, shared[it[0], it[1]][0], 0, hit[1]) if ptr else struct.pack(TINY_MEMBER, TINY_ABSENT, 0, 0)
     prog_sz = struct.calcsize(PROG) + 4 + MAXSLOT * struct.calcsize(SLOT)
     with open(path, "wb") as f:
-        # ---- layout: header, version-2 words, configuration table (cfg[16] + three programs each), buffer table, blobs
+        # ---- layout: header, version-2 words, configuration table (16 words + three programs each), buffer table, blobs
         # (version 3: the table of the tiny VAE's members behind the buffer table)
         table_end = struct.calcsize(HDR) + struct.calcsize(V2) + len(built) * (64 + 3 * prog_sz) + len(table) * struct.calcsize(BUF) + len(members)
         f.write(b"\0" * table_end)
@@ -482,6 +483,14 @@ def export_color_table(cmap, path):
     return table
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _u64(seed):
+    return int(seed) & ((1 << 64) - 1)
+
+
 class ModelImage:
     """ctypes handle on a loaded model image - what a non-Python host does, spelled in Python for the tests and as a second,
     graph-free way to run a fixed-shape deployment: ``encode`` / ``denoise`` / ``decode`` take and return torch CUDA tensors
@@ -495,19 +504,24 @@ class ModelImage:
             L.check(1, "mg_model_load")
         self.path, self.device = path, device
         self.configs = []   # the 16 cfg words of every configuration the image holds (a version-1 image: one)
-        cfg = (ctypes.c_int * 16)()
+        cfg = (ctypes.c_int * L.CFG_WORDS)()
         for i in range(lib.mg_model_num_configs(self.handle)):
             L.check(lib.mg_model_config_info(self.handle, i, cfg), "mg_model_config_info")
             self.configs.append(list(cfg))
         self._selected()
 
+    def config(self, index):
+        """Configuration ``index`` by name: {name of ``_lib.CFG``: word}, as the image has them (``pictures``: 0 = one per call)."""
+        return dict(zip(L.CFG, self.configs[int(index)]))
+
     def _selected(self):
         """The attributes of the selected configuration (``mg_model_info``)."""
-        cfg = (ctypes.c_int * 16)()
+        cfg = (ctypes.c_int * L.CFG_WORDS)()
         L.check(self._lib.mg_model_info(self.handle, cfg), "mg_model_info")
-        (self.B, self.H, self.W, self.h, self.w, self.steps, self.pred_channels, self.post, self.n_noise) = list(cfg)[:9]
-        self.Hout, self.Wout = cfg[11], cfg[12]
-        self.K = cfg[13] or 1   # pictures per call; B: the members of each
+        c = dict(zip(L.CFG, cfg))
+        self.B, self.H, self.W, self.h, self.w, self.steps = (c[k] for k in ("members", "height", "width", "latent_h", "latent_w", "steps"))
+        self.pred_channels, self.post, self.n_noise, self.Hout, self.Wout = (c[k] for k in ("channels", "post", "step_noises", "out_h", "out_w"))
+        self.K = c["pictures"] or 1   # pictures per call; B: the members of each
 
     def find(self, height=-1, width=-1, ensemble_size=-1, denoising_steps=-1, images_per_program=-1):
         """``mg_model_find_config``: the index of the first configuration that matches (-1 = any value); raises if none does."""
@@ -571,24 +585,50 @@ class ModelImage:
                                               O.current_stream_handle()), "mg_model_vae_decode")
         return out
 
+    # ---- what the one-call predictions share: their checks of the pictures, their output options, their output tensors
+    @staticmethod
+    def _pictures(who, u8s, reciprocal, size):
+        """The uint8 CUDA pictures of a call, one [Hin, Win, 3] or a list of one size, checked in ``who``'s name -> (contiguous, Hin, Win,
+        reciprocal: by default the reciprocal normalisation when the input is resampled - its size is not ``size``; None: never)."""
+        many = isinstance(u8s, list)
+        for u8 in u8s if many else [u8s]:
+            assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, \
+                f"{who}: uint8 CUDA [H, W, 3] pictures" if many else f"{who}: a uint8 CUDA [H, W, 3] picture"
+            assert not many or u8.shape == u8s[0].shape, f"{who}: the pictures of one call have one size"
+        Hin, Win = (u8s[0] if many else u8s).shape[:2]
+        if reciprocal is None:
+            reciprocal = size is not None and (Hin, Win) != tuple(size)
+        return ([u8.contiguous() for u8 in u8s] if many else u8s.contiguous()), Hin, Win, int(bool(reciprocal))
+
+    @staticmethod
+    def _out_opts(who, out_size, out_mode, lut):
+        """``_lib.MgOutputOpts`` of (out_size | None, out_mode, lut | None) -> (the struct, the table it points to: keep it until the call)."""
+        if lut is not None:
+            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, f"{who}: the colour table is uint8 CUDA [256, 3]"
+            lut = lut.contiguous()
+        oh, ow = (0, 0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        return L.MgOutputOpts(oh, ow, int(O.RESIZE_MODES.get(out_mode, out_mode)), _ptr(lut)), lut
+
+    @staticmethod
+    def _outputs(dev, lead, C, out_hw, unc_shape, u16=False, picture=False):
+        """The tensors a call writes, each behind the leading shape ``lead`` -> (pred fp32 [C, oh, ow], unc fp32 ``unc_shape`` | None for
+        None, u16 uint16 [oh, ow] | None, picture uint8 [oh, ow, 3] | None)."""
+        new = lambda dtype, *shape: torch.empty(*lead, *shape, device=dev, dtype=dtype)   # noqa: E731
+        return (new(torch.float32, C, *out_hw), None if unc_shape is None else new(torch.float32, *unc_shape),
+                new(torch.uint16, *out_hw) if u16 else None, new(torch.uint8, *out_hw, 3) if picture else None)
+
     def predict_iid(self, u8, seed, *, opts=None, pictures=False, mode=0, reciprocal=None):
         """``mg_model_predict_iid`` on the uint8 CUDA picture ``u8`` [Hin, Win, 3]: -> (pred fp32 [3 n, out_h, out_w], unc fp32
         [3 n, Hout, Wout] | None for a single member, pictures uint8 [n, out_h, out_w, 3] | None unless ``pictures``).  ``opts``: an
         ``_lib.MgIidOpts`` (None = the defaults); ``mode`` / ``reciprocal``: the input resampling as in ``mg_rgb_prepare`` (by default
         the reciprocal normalisation when the picture is resampled, as the pipelines' input stage)."""
-        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_iid: a uint8 CUDA [H, W, 3] picture"
-        u8 = u8.contiguous()
-        Hin, Win = u8.shape[:2]
-        if reciprocal is None:
-            reciprocal = (Hin, Win) != (self.H, self.W)
+        u8, Hin, Win, reciprocal = self._pictures("predict_iid", u8, reciprocal, (self.H, self.W))
         oh, ow = ((opts.out_h or self.Hout), (opts.out_w or self.Wout)) if opts is not None else (self.Hout, self.Wout)
-        n = self.pred_channels // 3
-        pred = torch.empty(self.pred_channels, oh, ow, device=u8.device, dtype=torch.float32)
-        unc = torch.empty(self.pred_channels, self.Hout, self.Wout, device=u8.device, dtype=torch.float32) if self.B > 1 else None
-        pics = torch.empty(n, oh, ow, 3, device=u8.device, dtype=torch.uint8) if pictures else None
-        L.check(self._lib.mg_model_predict_iid(self.handle, u8.data_ptr(), 1, Hin, Win, int(mode), int(bool(reciprocal)), int(seed) & ((1 << 64) - 1),
-                                               None if opts is None else ctypes.byref(opts), pred.data_ptr(),
-                                               None if unc is None else unc.data_ptr(), None if pics is None else pics.data_ptr(),
+        C = self.pred_channels
+        pred, unc, _, _ = self._outputs(u8.device, (), C, (oh, ow), (C, self.Hout, self.Wout) if self.B > 1 else None)
+        pics = torch.empty(C // 3, oh, ow, 3, device=u8.device, dtype=torch.uint8) if pictures else None
+        L.check(self._lib.mg_model_predict_iid(self.handle, u8.data_ptr(), 1, Hin, Win, int(mode), reciprocal, _u64(seed),
+                                               None if opts is None else ctypes.byref(opts), pred.data_ptr(), _ptr(unc), _ptr(pics),
                                                O.current_stream_handle()), "mg_model_predict_iid", self._lib)
         return pred, unc, pics
 
@@ -610,30 +650,16 @@ class ModelImage:
         ``out_size``: (out_h, out_w), None = the model's output size; ``out_mode``: a key of ``ops.RESIZE_MODES`` or its number;
         ``lut``: the colour table, uint8 CUDA [256, 3] (a depth model's picture needs it); ``opts``: an ``_lib.MgPredictOpts``;
         ``mode`` / ``reciprocal``: the input resampling as in ``predict_iid``."""
-        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_out: a uint8 CUDA [H, W, 3] picture"
-        u8 = u8.contiguous()
-        Hin, Win = u8.shape[:2]
-        if reciprocal is None:
-            reciprocal = (Hin, Win) != (self.H, self.W)
-        oh, ow = (self.Hout, self.Wout) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        if lut is not None:
-            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_out: the colour table is uint8 CUDA [256, 3]"
-            lut = lut.contiguous()
-        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
-                                  None if lut is None else lut.data_ptr())
-        dev = u8.device
-        pred = torch.empty(self.pred_channels, oh, ow, device=dev, dtype=torch.float32)
-        unc = torch.empty(self.Hout, self.Wout, device=dev, dtype=torch.float32) if self.B > 1 else None
-        d16 = torch.empty(oh, ow, device=dev, dtype=torch.uint16) if u16 else None
-        pic = torch.empty(oh, ow, 3, device=dev, dtype=torch.uint8) if picture else None
+        u8, Hin, Win, reciprocal = self._pictures("predict_out", u8, reciprocal, (self.H, self.W))
+        out_opts, lut = self._out_opts("predict_out", out_size, out_mode, lut)
+        out_hw = (self.Hout, self.Wout) if out_size is None else (out_opts.out_h, out_opts.out_w)
+        pred, unc, d16, pic = self._outputs(u8.device, (), self.pred_channels, out_hw, (self.Hout, self.Wout) if self.B > 1 else None, u16, picture)
         info = (ctypes.c_double * 4)()
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         # (_next: the strength - the call is mg_model_predict_next, the same arguments and the strength behind them)
         name = "mg_model_predict_out" if _next is None else "mg_model_predict_next"
-        L.check(getattr(self._lib, name)(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
-                                         int(seed) & ((1 << 64) - 1), None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
-                                         pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle(),
-                                         *(() if _next is None else (_next,))),
+        L.check(getattr(self._lib, name)(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), reciprocal, _u64(seed),
+                                         None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts), pred.data_ptr(), _ptr(unc),
+                                         _ptr(d16), _ptr(pic), info, O.current_stream_handle(), *(() if _next is None else (_next,))),
                 name, self._lib)
         return pred, unc, d16, pic, list(info)
 
@@ -646,31 +672,16 @@ class ModelImage:
         u8s, seeds = list(u8s), list(seeds)
         n = len(u8s)
         assert n >= 1 and len(seeds) == n, "predict_many: one seed per picture"
-        for u8 in u8s:
-            assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_many: uint8 CUDA [H, W, 3] pictures"
-            assert u8.shape == u8s[0].shape, "predict_many: the pictures of one call have one size"
-        u8s = [u8.contiguous() for u8 in u8s]
-        Hin, Win = u8s[0].shape[:2]
-        if reciprocal is None:
-            reciprocal = (Hin, Win) != (self.H, self.W)
-        oh, ow = (self.Hout, self.Wout) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        if lut is not None:
-            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_many: the colour table is uint8 CUDA [256, 3]"
-            lut = lut.contiguous()
-        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
-                                  None if lut is None else lut.data_ptr())
-        dev = u8s[0].device
-        pred = torch.empty(n, self.pred_channels, oh, ow, device=dev, dtype=torch.float32)
-        unc = torch.empty(n, self.Hout, self.Wout, device=dev, dtype=torch.float32) if self.B > 1 else None
-        d16 = torch.empty(n, oh, ow, device=dev, dtype=torch.uint16) if u16 else None
-        pic = torch.empty(n, oh, ow, 3, device=dev, dtype=torch.uint8) if picture else None
+        u8s, Hin, Win, reciprocal = self._pictures("predict_many", u8s, reciprocal, (self.H, self.W))
+        out_opts, lut = self._out_opts("predict_many", out_size, out_mode, lut)
+        out_hw = (self.Hout, self.Wout) if out_size is None else (out_opts.out_h, out_opts.out_w)
+        pred, unc, d16, pic = self._outputs(u8s[0].device, (n,), self.pred_channels, out_hw, (self.Hout, self.Wout) if self.B > 1 else None,
+                                            u16, picture)
         info = (ctypes.c_double * (4 * n))()
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         L.check(self._lib.mg_model_predict_many(self.handle, n, (ctypes.c_void_p * n)(*[u8.data_ptr() for u8 in u8s]), 1, Hin, Win,
-                                                int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
-                                                (ctypes.c_uint64 * n)(*[int(s) & ((1 << 64) - 1) for s in seeds]),
+                                                int(O.RESIZE_MODES.get(mode, mode)), reciprocal, (ctypes.c_uint64 * n)(*[_u64(s) for s in seeds]),
                                                 None if opts is None else ctypes.byref(opts), ctypes.byref(out_opts),
-                                                pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, O.current_stream_handle()),
+                                                pred.data_ptr(), _ptr(unc), _ptr(d16), _ptr(pic), info, O.current_stream_handle()),
                 "mg_model_predict_many", self._lib)
         return pred, unc, d16, pic, [list(info[4 * i:4 * i + 4]) for i in range(n)]
 
@@ -685,41 +696,28 @@ class ModelImage:
         short last group as ``map_images`` does (without it the group is padded: the same up to the arithmetic of the batch); ``overlap``: an int or (y, x); ``out_size``: None = the picture's size;
         ``mode`` / ``reciprocal``: the resampling of the GUIDE's input as in ``predict_out`` (by default the reciprocal normalisation
         when the guide is resampled).  The handle stays on the configuration it was on."""
-        assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[-1] == 3, "predict_tiled: a uint8 CUDA [H, W, 3] picture"
-        u8 = u8.contiguous()
-        Hin, Win = u8.shape[:2]
         tile_config, guide_config = int(tile_config), int(guide_config)
         if not 0 <= tile_config < len(self.configs):
             raise ValueError(f"predict_tiled: tile configuration {tile_config} of {len(self.configs)}")
-        tc = self.configs[tile_config]
-        B, C, depth = tc[0], tc[6], tc[6] == 1
-        if reciprocal is None:
-            gc = self.configs[guide_config] if depth and 0 <= guide_config < len(self.configs) else None
-            reciprocal = gc is not None and (Hin, Win) != (gc[1], gc[2])
+        tc = self.config(tile_config)
+        B, C, depth = tc["members"], tc["channels"], tc["channels"] == 1
+        gc = self.config(guide_config) if depth and 0 <= guide_config < len(self.configs) else None
+        u8, Hin, Win, reciprocal = self._pictures("predict_tiled", u8, reciprocal, None if gc is None else (gc["height"], gc["width"]))
         oy, ox = (int(overlap[0]), int(overlap[1])) if isinstance(overlap, (tuple, list)) else (int(overlap), int(overlap))
-        oh, ow = (Hin, Win) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        if lut is not None:
-            assert lut.is_cuda and lut.dtype == torch.uint8 and lut.numel() == 768, "predict_tiled: the colour table is uint8 CUDA [256, 3]"
-            lut = lut.contiguous()
+        out_opts, lut = self._out_opts("predict_tiled", out_size, out_mode, lut)
         tiled = L.MgTiledOpts(guide_config, tile_config, oy, ox, -1 if tail_config is None else int(tail_config))
-        out_opts = L.MgOutputOpts(0 if out_size is None else oh, 0 if out_size is None else ow, int(O.RESIZE_MODES.get(out_mode, out_mode)),
-                                  None if lut is None else lut.data_ptr())
-        dev = u8.device
-        n_max = L.TILE_MAX_PER_AXIS ** 2
-        pred = torch.empty(C, max(oh, 0), max(ow, 0), device=dev, dtype=torch.float32)
-        unc = torch.empty(Hin, Win, device=dev, dtype=torch.float32) if B > 1 and uncertainty else None
-        d16 = torch.empty(max(oh, 0), max(ow, 0), device=dev, dtype=torch.uint16) if u16 else None
-        pic = torch.empty(max(oh, 0), max(ow, 0), 3, device=dev, dtype=torch.uint8) if picture else None
-        flg = torch.zeros(n_max, device=dev, dtype=torch.int32) if depth and flags else None
+        # (a size the call refuses is refused by the call: the tensors it would have written are empty)
+        out_hw = (Hin, Win) if out_size is None else (max(out_opts.out_h, 0), max(out_opts.out_w, 0))
+        pred, unc, d16, pic = self._outputs(u8.device, (), C, out_hw, (Hin, Win) if B > 1 and uncertainty else None, u16, picture)
+        flg = torch.zeros(L.TILE_MAX_PER_AXIS ** 2, device=u8.device, dtype=torch.int32) if depth and flags else None
         info = (ctypes.c_double * 4)()
-        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        L.check(self._lib.mg_model_predict_tiled(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), int(bool(reciprocal)),
-                                                 int(seed) & ((1 << 64) - 1), ctypes.byref(tiled), None if opts is None else ctypes.byref(opts),
-                                                 ctypes.byref(out_opts), pred.data_ptr(), ptr(unc), ptr(d16), ptr(pic), info, ptr(flg),
+        L.check(self._lib.mg_model_predict_tiled(self.handle, u8.data_ptr(), 1, Hin, Win, int(O.RESIZE_MODES.get(mode, mode)), reciprocal,
+                                                 _u64(seed), ctypes.byref(tiled), None if opts is None else ctypes.byref(opts),
+                                                 ctypes.byref(out_opts), pred.data_ptr(), _ptr(unc), _ptr(d16), _ptr(pic), info, _ptr(flg),
                                                  O.current_stream_handle()), "mg_model_predict_tiled", self._lib)
         if flg is not None:   # the plan the call made: its number of tiles
             from . import tiles as tiling
-            flg = flg[:len(tiling.plan((Hin, Win), (tc[1], tc[2]), (oy, ox)).origins)]
+            flg = flg[:len(tiling.plan((Hin, Win), (tc["height"], tc["width"]), (oy, ox)).origins)]
         return pred, unc, d16, pic, list(info), flg
 
     def close(self):

@@ -9,13 +9,14 @@ import ctypes
 import dataclasses
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,14 +71,7 @@ def _arrays(out, field="array"):
 @pytest.fixture(scope="module")
 def host_iid(tmp_path_factory):
     """examples/host_iid.cpp, built as the ``host_map`` fixture of tests/test_gpu_native_noise.py builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_iid") / "host_iid")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_iid.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_iid", tmp_path_factory.mktemp("host_iid"))
 
 
 def _export(pipe, path, E, hw):

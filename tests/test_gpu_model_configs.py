@@ -8,7 +8,6 @@ A, B, C, A, D on one handle: the second A catches a zeroed-state buffer another 
 reaches into private data.  Replicas run from two host threads on two streams, switching configuration between pictures."""
 import functools
 import os
-import shutil
 import subprocess
 import threading
 
@@ -16,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -250,14 +251,7 @@ def test_replicas_on_two_streams_from_two_threads(lib, depth):
 @pytest.fixture(scope="module")
 def host_sizes(tmp_path_factory):
     """examples/host_sizes.cpp, built as the ``host_picture`` fixture of tests/test_gpu_predict_out_c_host.py builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_sizes") / "host_sizes")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_sizes.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_sizes", tmp_path_factory.mktemp("host_sizes"))
 
 
 def _pnm(path, magic, h, w, maxval, dtype, channels):

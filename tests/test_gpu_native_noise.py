@@ -16,7 +16,6 @@ Bounds, and where they come from.
 import ctypes
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -24,6 +23,7 @@ import pytest
 import torch
 from PIL import Image
 
+from tests import c_hosts
 from tests import philox_reference as P
 
 pytestmark = pytest.mark.gpu
@@ -251,14 +251,7 @@ def test_lcm_step_noise_is_the_next_stream(libs):
 @pytest.fixture(scope="module")
 def host_map(tmp_path_factory):
     """examples/host_map.cpp, built as tests/test_gpu_pipeline.py::test_model_image_from_a_c_host builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_map") / "host_map")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_map.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_map", tmp_path_factory.mktemp("host_map"))
 
 
 def _run_host(exe, tmp_path, pipe, pil, model_hw, E, seed, **export_kw):

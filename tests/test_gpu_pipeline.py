@@ -825,23 +825,17 @@ def test_model_image_runs_the_pipeline_from_c(tiny, tmp_path):
 def test_model_image_from_a_c_host(tiny, tmp_path):
     """examples/host_depth.cpp - a host program without Python (hipcc + libmarigold_hip.so only) - loads a model image and writes
     the ensembled depth map of E = 2 members: identical to the Python pipeline's map for the same latents."""
-    import shutil
     import subprocess
     from marigold_amd import image, schedulers as S
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    from tests import c_hosts
+    if not c_hosts.have_hipcc():
         pytest.skip("hipcc not available on this box")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     img, lat0, rgb = _inputs()
     pipe = _engine_pipe(tiny, "depth", S.DDIMScheduler())
     pipe.default_denoising_steps = 2
     path = str(tmp_path / "tiny.mgimg")
     image.export_model_image(pipe, path, ensemble_size=2, height=64, width=128)
-    exe = str(tmp_path / "host_depth")
-    r = subprocess.run([hipcc, "-O2", os.path.join(root, "examples", "host_depth.cpp"), "-I" + os.path.join(root, "include"),
-                        "-L" + os.path.join(root, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(root, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = c_hosts.build_example("host_depth", tmp_path)
     rgb.numpy().astype(np.float32).tofile(str(tmp_path / "rgb.f32"))
     lat0[:2].numpy().astype(np.float32).tofile(str(tmp_path / "noise.f32"))
     r = subprocess.run([exe, path, str(tmp_path / "rgb.f32"), str(tmp_path / "noise.f32"), str(tmp_path / "depth.f32")],

@@ -9,13 +9,14 @@ ones the untouched pipeline maps to 64 x 128 by itself: 64 x 128 at ``processing
 import ctypes
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,14 +102,7 @@ def models(lib, tmp_path_factory):
 @pytest.fixture(scope="module")
 def host_many(tmp_path_factory):
     """examples/host_many.cpp, built as the ``host_picture`` fixture of tests/test_gpu_predict_out_c_host.py builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_many") / "host_many")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_many.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_many", tmp_path_factory.mktemp("host_many"))
 
 
 def _check(kind, E, got, ref, size):

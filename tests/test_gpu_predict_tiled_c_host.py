@@ -22,13 +22,14 @@ asks for 96 x 192.  That case is the normals model's: the depth guide of Python 
 import ctypes
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -268,14 +269,7 @@ def test_refusals_leave_the_outputs_untouched(lib, models):
 @pytest.fixture(scope="module")
 def host_tiled(tmp_path_factory):
     """examples/host_tiled.cpp, built as the ``host_picture`` fixture of tests/test_gpu_predict_out_c_host.py builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_tiled") / "host_tiled")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_tiled.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_tiled", tmp_path_factory.mktemp("host_tiled"))
 
 
 def _pnm(path, magic, h, w, maxval, dtype, channels):

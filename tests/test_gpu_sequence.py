@@ -13,13 +13,14 @@ The models are the tiny synthetic ones of tests/test_gpu_predict_out_c_host.py: 
 import dataclasses
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -400,14 +401,7 @@ def _pnm(path, magic, h, w, maxval, dtype, channels):
 @pytest.fixture(scope="module")
 def host_sequence(tmp_path_factory):
     """examples/host_sequence.cpp, built as the ``host_picture`` fixture of tests/test_gpu_predict_out_c_host.py builds its example."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_sequence") / "host_sequence")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_sequence.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
+    return c_hosts.build_example("host_sequence", tmp_path_factory.mktemp("host_sequence"))
 
 
 @pytest.mark.parametrize("kind,E", [("depth", 1), ("normals", 2)], ids=["depth-E1", "normals-E2"])

@@ -14,13 +14,14 @@ import ctypes
 import dataclasses
 import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 from PIL import Image
+
+from tests import c_hosts
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -364,13 +365,7 @@ def test_c_host_picture_runs_a_tiny_image_unchanged(lib, models, tmp_path_factor
     """examples/host_picture.cpp, built as tests/test_gpu_predict_out_c_host.py builds it, in a fresh process on the 30 x 44 tiny depth image
     with three members: the files it writes against the pipeline's output."""
     from marigold_amd import image
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to build the C host"
-    exe = str(tmp_path_factory.mktemp("host_picture_tiny") / "host_picture")
-    r = subprocess.run([hipcc, "-O2", os.path.join(ROOT, "examples", "host_picture.cpp"), "-I" + os.path.join(ROOT, "include"),
-                        "-L" + os.path.join(ROOT, "marigold_amd"), "-lmarigold_hip", "-Wl,-rpath," + os.path.join(ROOT, "marigold_amd"), "-o", exe],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = c_hosts.build_example("host_picture", tmp_path_factory.mktemp("host_picture_tiny"))
     raw, prefix, lut_path = str(tmp_path / "image.u8"), str(tmp_path / "out"), str(tmp_path / "spectral.lut")
     np.asarray(_pil(*ODD)).tofile(raw)
     image.export_color_table("Spectral", lut_path)

@@ -67,6 +67,21 @@ def test_every_kinds_field_names_and_number_match_the_header():
     assert L.FIELDS[L.OP_ENS_IID][1] == dict(i=("e", "reduction"), p=("preds", "pred", "unc"), l=("n",))
 
 
+def test_configuration_word_names_match_the_header_and_the_wire_format():
+    """enum mg_cfg of include/marigold_hip.h equals _lib.CFG (position = word), and MG_VAE_* equal _lib.VAE_*: the one comparison of
+    the two tables of a model image's configuration words."""
+    from marigold_amd import _lib as L
+    hdr = open(os.path.join(ROOT, "include", "marigold_hip.h")).read()
+    parsed = {name: int(n) for name, n in re.findall(r"^\s*MG_CFG_(\w+) = (\d+)", hdr, flags=re.M)}
+    assert parsed.pop("WORDS") == L.CFG_WORDS == 16
+    assert parsed == {name.upper(): k for k, name in enumerate(L.CFG)} and len(set(L.CFG)) == len(L.CFG) < L.CFG_WORDS
+    assert {name: int(n) for name, n in re.findall(r"\bMG_VAE_(\w+) = (\d+)", hdr)} == dict(KL=L.VAE_KL, TINY=L.VAE_TINY) == dict(KL=0, TINY=1)
+    assert re.search(r"#define MG_CFG_PICTURES_OF\(cfg\) \(\(cfg\)\[MG_CFG_PICTURES\] \? \(cfg\)\[MG_CFG_PICTURES\] : 1\)", hdr)
+    # the wire format, written out on purpose: images in the field carry these positions
+    assert dict(zip(L.CFG, range(16))) == dict(members=0, height=1, width=2, latent_h=3, latent_w=4, steps=5, channels=6, post=7, step_noises=8,
+                                               op_bytes=9, modalities=10, out_h=11, out_w=12, pictures=13, vae=14)
+
+
 def test_op_field_names_match_the_header_and_the_wire_format():
     """For the four kinds with many launch forms every builder argument lands in the raw slot the header documents (the numbers below
     are the wire format, written out on purpose) and reads back by name; the views restate the launcher's defaulting rules

@@ -5,15 +5,15 @@ program compiles against the header."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from marigold_amd import _lib as L, ops, opstats
 
+from tests import c_hosts
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def _header():
@@ -93,16 +93,11 @@ def test_calls_check_their_arguments_without_a_device():
 def test_options_struct_size_and_the_example_compile(tmp_path):
     """``sizeof(mg_iid_opts)`` as a C++ compiler sees it equals the ctypes mirror's; examples/host_iid.cpp (which static_asserts the same
     size) compiles with hipcc against the header."""
-    assert os.path.exists(HIPCC), "hipcc is needed to compile against the header"
     src = tmp_path / "size.cpp"
     src.write_text('#include <stdio.h>\n#include "marigold_hip.h"\nint main() { printf("%zu %zu", sizeof(mg_iid_opts), sizeof(mg_op)); return 0; }\n')
-    exe = str(tmp_path / "size")
-    r = subprocess.run([HIPCC, "-x", "c++", str(src), "-I" + os.path.join(ROOT, "include"), "-o", exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = c_hosts.compile_only(src, tmp_path / "size")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()
     assert [int(v) for v in out] == [ctypes.sizeof(L.MgIidOpts), ctypes.sizeof(L.MgOp)] == [24, 360]
     example = os.path.join(ROOT, "examples", "host_iid.cpp")
     assert "static_assert(sizeof(mg_iid_opts)" in open(example).read()
-    r = subprocess.run([HIPCC, "-O2", "--offload-arch=gfx950", "-c", example, "-I" + os.path.join(ROOT, "include"), "-o", str(tmp_path / "host_iid.o")],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    c_hosts.compile_only(example, tmp_path / "host_iid.o")

@@ -97,6 +97,34 @@ def test_layout_of_a_multi_configuration_image(lib, exported):
     assert all(r[1] % 256 == 0 and r[1] + r[0] <= scratch_region for r in rows if r[2] == 0)
 
 
+def test_configurations_read_by_name(exported):
+    """``ModelImage.config(i)`` is ``ModelImage.configs[i]`` under the names of ``_lib.CFG``; the word ``pictures`` is written 0 for one
+    picture per call and K otherwise."""
+    from marigold_amd import image, _lib as L
+    multi, singles = exported
+    for path in [multi["path"]] + [one["path"] for one in singles]:
+        m = image.ModelImage(path, device=-1)
+        try:
+            for i, words in enumerate(m.configs):
+                named = m.config(i)
+                assert list(named) == list(L.CFG) and len(words) == L.CFG_WORDS == 16 and words[len(L.CFG):] == [0]
+                for n in L.CFG:
+                    assert named[n] == words[L.CFG.index(n)], (path, i, n)
+        finally:
+            m.close()
+    m = image.ModelImage(multi["path"], device=-1)
+    try:
+        for i, c in enumerate(CONFIGS):
+            K, named = c["images_per_program"], m.config(i)
+            assert named["pictures"] == (0 if K == 1 else K) and m.select(i).K == K
+            assert (named["members"], named["height"], named["width"], named["steps"]) == (c["ensemble_size"], c["height"], c["width"], 2)
+            assert (named["latent_h"], named["latent_w"], named["out_h"], named["out_w"]) == (c["height"] // 8, c["width"] // 8, c["height"], c["width"])
+            assert (named["channels"], named["post"], named["step_noises"], named["modalities"], named["vae"]) == (1, L.POST_DEPTH, 0, 1, L.VAE_KL)
+            assert named["op_bytes"] == ctypes.sizeof(L.MgOp) == 360
+    finally:
+        m.close()
+
+
 def test_version_1_is_unchanged(lib, exported):
     from marigold_amd import image
     _multi, singles = exported

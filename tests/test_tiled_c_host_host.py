@@ -8,15 +8,15 @@ tests/test_gpu_predict_tiled_c_host.py run them on the device."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from marigold_amd import _lib as L
 
+from tests import c_hosts
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 LIBS = pytest.mark.parametrize("f16", [False, True], ids=["bf16-lib", "f16-lib"])
 A = 0x10000   # a fake, 16-byte aligned device address: no call here gets as far as touching it
 # (E, H, W, T, K): 0 the guide of a 128 x 256 picture at guide_res 128, 1 tiles K = 2, 2 tiles with E = 3, 3 a guide with E = 3 and
@@ -87,20 +87,15 @@ def test_prototypes_bindings_and_exports():
 
 
 def test_options_struct_size_and_the_example_compile(tmp_path):
-    assert os.path.exists(HIPCC), "hipcc is needed to compile against the header"
     src = tmp_path / "size.cpp"
     src.write_text('#include <stdio.h>\n#include "marigold_hip.h"\nint main() { printf("%zu %zu %d", sizeof(mg_tiled_opts), sizeof(mg_op), '
                    'MG_ABI_VERSION); return 0; }\n')
-    exe = str(tmp_path / "size")
-    r = subprocess.run([HIPCC, "-x", "c++", str(src), "-I" + os.path.join(ROOT, "include"), "-o", exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    exe = c_hosts.compile_only(src, tmp_path / "size")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.split()
     assert [int(v) for v in out] == [ctypes.sizeof(L.MgTiledOpts), ctypes.sizeof(L.MgOp), L.ABI_VERSION] == [20, 360, 4]
     example = os.path.join(ROOT, "examples", "host_tiled.cpp")
     assert "static_assert(sizeof(mg_tiled_opts)" in open(example).read()
-    r = subprocess.run([HIPCC, "-O2", "--offload-arch=gfx950", "-c", example, "-I" + os.path.join(ROOT, "include"), "-o", str(tmp_path / "host_tiled.o")],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
+    c_hosts.compile_only(example, tmp_path / "host_tiled.o")
 
 
 # ---- mg_tile_crop's refusals -------------------------------------------------------------------------------------------------------

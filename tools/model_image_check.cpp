@@ -18,13 +18,13 @@
 // The steps on a loaded image; -> the step that failed, or null.  The handles it makes are the caller's to destroy.
 static const char* steps(mg_model* m, mg_model** r, mg_model** rr, int* n_out, long long* shared, long long* priv) {
   const int n = *n_out = mg_model_num_configs(m);
-  int cfg[16], sel[16];
+  int cfg[MG_CFG_WORDS], sel[MG_CFG_WORDS];
   if (n < 1) return "mg_model_num_configs";
   for (int i = 0; i < n; ++i) {
     if (mg_model_config_info(m, i, cfg)) return "mg_model_config_info";
     if (mg_model_select(m, i) || mg_model_info(m, sel) || memcmp(cfg, sel, sizeof(cfg))) return "mg_model_select / mg_model_info";
     if (mg_model_validate(m)) return "mg_model_validate";
-    const int found = mg_model_find_config(m, cfg[1], cfg[2], cfg[0], cfg[5], cfg[13] ? cfg[13] : 1);
+    const int found = mg_model_find_config(m, cfg[MG_CFG_HEIGHT], cfg[MG_CFG_WIDTH], cfg[MG_CFG_MEMBERS], cfg[MG_CFG_STEPS], MG_CFG_PICTURES_OF(cfg));
     if (found < 0 || found > i) return "mg_model_find_config";
   }
   if (mg_model_config_info(m, n, cfg) == 0 || mg_model_select(m, n) == 0 || mg_model_select(m, -1) == 0) return "an index out of range was taken";
