@@ -127,6 +127,67 @@ __device__ __forceinline__ void half_swap(float g0, float g1, float& first, floa
   second = __uint_as_float(r[1]);
 }
 
+// ---- the steps the GEMM, convolution and attention epilogues share: 8 consecutive channels of one row per lane ----
+// eight fp32 -> the 16 bytes of one store (cvt_pk_bf16_f32's rounding and fp16 saturation), and back
+__device__ __forceinline__ uint4 mg_pack8(const float (&v)[8]) {
+  uint4 pk;
+  pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
+  pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
+  return pk;
+}
+__device__ __forceinline__ void mg_unpack8(const uint4 w, float (&v)[8]) {
+  v[0] = bflo(w.x); v[1] = bfhi(w.x); v[2] = bflo(w.y); v[3] = bfhi(w.y);
+  v[4] = bflo(w.z); v[5] = bfhi(w.z); v[6] = bflo(w.w); v[7] = bfhi(w.w);
+}
+// two vectors of four fp32 (float4 from memory, f32x4 from an LDS read) as one array
+template <class V4>
+__device__ __forceinline__ void mg_join8(const V4 lo, const V4 hi, float (&v)[8]) {
+  v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+  v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+}
+__device__ __forceinline__ void mg_load8(const float* p, float (&v)[8]) {   // p: 16-byte aligned
+  const float4 lo = *(const float4*)p, hi = *(const float4*)(p + 4);
+  mg_join8(lo, hi, v);
+}
+// v += eight values: two fp32 vectors (bias, time-embedding row, split-K partials) or eight packed operands (the residual).  Each
+// word is unpacked next to its add, as the epilogues were written by hand: hipcc's schedule follows the source order.
+template <class V4>
+__device__ __forceinline__ void mg_add8(float (&v)[8], const V4 lo, const V4 hi) {
+  v[0] += lo.x; v[1] += lo.y; v[2] += lo.z; v[3] += lo.w;
+  v[4] += hi.x; v[5] += hi.y; v[6] += hi.z; v[7] += hi.w;
+}
+__device__ __forceinline__ void mg_add8(float (&v)[8], const float* p) {   // p: 16-byte aligned
+  const float4 lo = *(const float4*)p, hi = *(const float4*)(p + 4);
+  mg_add8(v, lo, hi);
+}
+__device__ __forceinline__ void mg_add8(float (&v)[8], const uint4 w) {
+  v[0] += bflo(w.x); v[1] += bfhi(w.x); v[2] += bflo(w.y); v[3] += bfhi(w.y);
+  v[4] += bflo(w.z); v[5] += bfhi(w.z); v[6] += bflo(w.w); v[7] += bfhi(w.w);
+}
+// (sum, sum of squares) of a row in fp64 -> (mean, rstd): fp64 for the cancellation E[x^2] - mean^2 only, 1/sqrt in fp32
+// (v_rsq_f32, ~1 ulp).  The row-resident kernels and the tile GEMM's cross-attention epilogue call this; the slot reducer of
+// igemm2_body.h (ln_out_finish) spells the same three lines out, because the call changed that kernel family's register
+// allocation (docs/history/epilogue_steps.md) - the tables must agree bit for bit whichever kernel wrote them, so the two copies
+// change together.  (GroupNorm's finalize in norm.hip is other arithmetic - fp64 1 / sqrt - and not one of these.)
+__device__ __forceinline__ float2 mg_row_mean_rstd(double s, double q, double inv_n, float eps) {
+  const double mean = s * inv_n;
+  const float var = fmaxf((float)__builtin_fma(q, inv_n, -mean * mean), 0.f);
+  return make_float2((float)mean, __builtin_amdgcn_rsqf(var + eps));
+}
+// The softmax of the collapsed cross-attention (2 keys per head): eight scaled scores = 4 (key 0, key 1) pairs of the score
+// columns c0 .. c0 + 7 -> four words of packed probabilities; pairs at or beyond sm_cols (padding heads) give zero.
+__device__ __forceinline__ uint4 mg_pair_softmax4(const float (&s)[8], int c0, int sm_cols) {
+  uint32_t w4[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float mx = fmaxf(s[2 * k], s[2 * k + 1]);
+    const float e0 = __expf(s[2 * k] - mx), e1 = __expf(s[2 * k + 1] - mx);
+    const float inv = 1.0f / (e0 + e1);
+    w4[k] = (c0 + 2 * k < sm_cols) ? pack2bf(e0 * inv, e1 * inv) : 0u;
+  }
+  return make_uint4(w4[0], w4[1], w4[2], w4[3]);
+}
+
 __device__ __forceinline__ float silu_fast_f(float x) {  // x * sigmoid(x): one v_exp, one v_rcp
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
@@ -196,6 +257,19 @@ __device__ __forceinline__ void mg_handoff_release() {   // lane 0, behind the w
 }
 __device__ __forceinline__ void mg_handoff_acquire() {   // the last arriver's lane 0, in front of the barrier that releases its readers
   if constexpr (MG_HANDOFF_FENCES) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+// The ticket itself, drawn by ONE lane of the workgroup behind that barrier: true for the last of `total` arrivers, which has
+// then also put the counter back to zero for the next launch (stream-ordered).  The caller keeps what surrounds it: the vmcnt
+// drain and barrier in front, the LDS broadcast of the answer and the barrier behind.
+__device__ __forceinline__ bool mg_draw_last_ticket(unsigned* counter, unsigned total) {
+  mg_handoff_release();
+  const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool last = ticket == total - 1;
+  if (last) {
+    mg_handoff_acquire();
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return last;
 }
 
 #define MG_ZERO_BYTES (128 * 1024)

@@ -181,32 +181,25 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_patch_kernel(const ConvPAr
   auto fix_load = [&](int c) {
     if constexpr (SSL) { fix_c = c; return; }
     const float* scp = a.ss + (long long)img * 2 * a.Cin + c * 64 + fix_j8;
-    const float4 s0 = *(const float4*)scp, s1 = *(const float4*)(scp + 4);
-    const float4 h0 = *(const float4*)(scp + a.Cin), h1 = *(const float4*)(scp + a.Cin + 4);
-    fsc[0] = s0.x; fsc[1] = s0.y; fsc[2] = s0.z; fsc[3] = s0.w; fsc[4] = s1.x; fsc[5] = s1.y; fsc[6] = s1.z; fsc[7] = s1.w;
-    fsh[0] = h0.x; fsh[1] = h0.y; fsh[2] = h0.z; fsh[3] = h0.w; fsh[4] = h1.x; fsh[5] = h1.y; fsh[6] = h1.z; fsh[7] = h1.w;
+    mg_load8(scp, fsc);
+    mg_load8(scp + a.Cin, fsh);
   };
   auto fix_vec = [&](int it, int pb) {
     if (!((fix_mask >> it) & 1u)) return;
     uint4* p = (uint4*)(patch0 + pb * PATCH + (it * NT + tid) * 16);
-    const uint4 u = *p;
-    float v[8] = {bflo(u.x), bfhi(u.x), bflo(u.y), bfhi(u.y), bflo(u.z), bfhi(u.z), bflo(u.w), bfhi(u.w)};
+    float v[8];
+    mg_unpack8(*p, v);
     if constexpr (SSL) {
       const float* scp = ssl + fix_c * 64 + fix_j8;
-      const float4 s0 = *(const float4*)scp, s1 = *(const float4*)(scp + 4);
-      const float4 h0 = *(const float4*)(scp + a.Cin), h1 = *(const float4*)(scp + a.Cin + 4);
-      fsc[0] = s0.x; fsc[1] = s0.y; fsc[2] = s0.z; fsc[3] = s0.w; fsc[4] = s1.x; fsc[5] = s1.y; fsc[6] = s1.z; fsc[7] = s1.w;
-      fsh[0] = h0.x; fsh[1] = h0.y; fsh[2] = h0.z; fsh[3] = h0.w; fsh[4] = h1.x; fsh[5] = h1.y; fsh[6] = h1.z; fsh[7] = h1.w;
+      mg_load8(scp, fsc);
+      mg_load8(scp + a.Cin, fsh);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       v[j] = __builtin_fmaf(v[j], fsc[j], fsh[j]);
       if (a.silu) v[j] = silu_fast_f(v[j]);
     }
-    uint4 o;
-    o.x = cvt_pk_bf16_f32(v[0], v[1]); o.y = cvt_pk_bf16_f32(v[2], v[3]);
-    o.z = cvt_pk_bf16_f32(v[4], v[5]); o.w = cvt_pk_bf16_f32(v[6], v[7]);
-    *p = o;
+    *p = mg_pack8(v);
   };
 
   const int T = a.T, chunks = a.chunks;
@@ -339,28 +332,14 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv_patch_kernel(const ConvPAr
         for (int j = 0; j < 4; ++j) half_swap(acc[ni][mi][8 * gp + j], acc[ni][mi][8 * gp + 4 + j], v[j], v[4 + j]);
         const int n = nb + 16 * gp + 8 * half;
         if (pix_ok && n < a.N) {
-          if (a.bias) {
-            const float4 b0 = *(const float4*)(a.bias + n), b1 = *(const float4*)(a.bias + n + 4);
-            v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-            v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-          }
-          if (a.rowvec) {
-            const float* rv = a.rowvec + (long long)img * a.rv_stride + n;
-            const float4 r0 = *(const float4*)rv, r1 = *(const float4*)(rv + 4);
-            v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
-            v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
-          }
-          if (a.res) {
-            const uint4 r4 = *(const uint4*)(a.res + orow * a.ldr + n);
-            v[0] += bflo(r4.x); v[1] += bfhi(r4.x); v[2] += bflo(r4.y); v[3] += bfhi(r4.y);
-            v[4] += bflo(r4.z); v[5] += bfhi(r4.z); v[6] += bflo(r4.w); v[7] += bfhi(r4.w);
-          }
-          uint4 pk;
-          pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-          pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
+          if (a.bias) mg_add8(v, a.bias + n);
+          if (a.rowvec) mg_add8(v, a.rowvec + (long long)img * a.rv_stride + n);
+          if (a.res) mg_add8(v, *(const uint4*)(a.res + orow * a.ldr + n));
+          const uint4 pk = mg_pack8(v);
           *(uint4*)(a.out + orow * a.ldo + n) = pk;
           if constexpr (GNS) {   // of the values as stored (bf16): what a statistics pass over the tensor would see
-            const float w[8] = {bflo(pk.x), bfhi(pk.x), bflo(pk.y), bfhi(pk.y), bflo(pk.z), bfhi(pk.z), bflo(pk.w), bfhi(pk.w)};
+            float w[8];
+            mg_unpack8(pk, w);
             gsum[ni][gp][0] += (w[0] + w[1]) + (w[2] + w[3]);
             gsq[ni][gp][0] += (w[0] * w[0] + w[1] * w[1]) + (w[2] * w[2] + w[3] * w[3]);
             gsum[ni][gp][1] += (w[4] + w[5]) + (w[6] + w[7]);

@@ -367,17 +367,7 @@ __device__ __forceinline__ void f4_segment(const FaArgs& a, char* smem, const in
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int* flag = (int*)(smem + F4_PRE);
-    if (tid == 0) {
-      unsigned* ctr = (unsigned*)a.ws + rem;
-      mg_handoff_release();
-      const unsigned ticket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool lastp = ticket == (unsigned)(npieces - 1);
-      if (lastp) {
-        mg_handoff_acquire();
-        __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream-ordered)
-      }
-      *flag = lastp ? 1 : 0;
-    }
+    if (tid == 0) *flag = mg_draw_last_ticket((unsigned*)a.ws + rem, (unsigned)npieces) ? 1 : 0;
     __syncthreads();
     finish = *flag != 0;
     __syncthreads();
@@ -449,10 +439,7 @@ __device__ __forceinline__ void f4_segment(const FaArgs& a, char* smem, const in
         float v[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) half_swap(o[q][dt][8 * gp + j] * inv[q], o[q][dt][8 * gp + 4 + j] * inv[q], v[j], v[4 + j]);
-        uint4 pk;
-        pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-        pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-        *(uint4*)(orow + dt * 32 + 16 * gp + 8 * half) = pk;
+        *(uint4*)(orow + dt * 32 + 16 * gp + 8 * half) = mg_pack8(v);
       }
   }
   if (dbgw && lane == 0) dbgw[7] = __builtin_amdgcn_s_memrealtime();

@@ -52,32 +52,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const Igemm2Args a) 
     for (int j = 0; j < 8; ++j) v[j] = 0.f;
     for (int sidx = 0; sidx < a.splits; ++sidx) {
       const float* p = a.ws + ((long long)sidx * a.M + m) * a.N + n;
-      const float4 x0 = *(const float4*)p, x1 = *(const float4*)(p + 4);
-      v[0] += x0.x; v[1] += x0.y; v[2] += x0.z; v[3] += x0.w;
-      v[4] += x1.x; v[5] += x1.y; v[6] += x1.z; v[7] += x1.w;
+      mg_add8(v, p);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] *= a.scale;
-    if (a.bias) {
-      const float4 b0 = *(const float4*)(a.bias + n), b1 = *(const float4*)(a.bias + n + 4);
-      v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-      v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-    }
+    if (a.bias) mg_add8(v, a.bias + n);
     if (a.rowvec) {
       const float* rv = a.rowvec + (long long)(m / a.rows_per_img) * a.rv_stride + n;
-      const float4 r0 = *(const float4*)rv, r1 = *(const float4*)(rv + 4);
-      v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
-      v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
+      mg_add8(v, rv);
     }
-    if (a.res) {
-      const uint4 r4 = *(const uint4*)(a.res + (long long)m * a.ldr + n);
-      v[0] += bflo(r4.x); v[1] += bfhi(r4.x); v[2] += bflo(r4.y); v[3] += bfhi(r4.y);
-      v[4] += bflo(r4.z); v[5] += bfhi(r4.z); v[6] += bflo(r4.w); v[7] += bfhi(r4.w);
-    }
-    uint4 pk;
-    pk.x = cvt_pk_bf16(v[0], v[1]); pk.y = cvt_pk_bf16(v[2], v[3]);
-    pk.z = cvt_pk_bf16(v[4], v[5]); pk.w = cvt_pk_bf16(v[6], v[7]);
-    *(uint4*)((bf16_t*)a.out + (long long)m * a.ldo + n) = pk;
+    if (a.res) mg_add8(v, *(const uint4*)(a.res + (long long)m * a.ldr + n));
+    *(uint4*)((bf16_t*)a.out + (long long)m * a.ldo + n) = mg_pack8(v);
   }
 }
 

@@ -61,8 +61,6 @@ struct Igemm2Args {
   double inv_c2;
 };
 
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) { return cvt_pk_bf16_f32(lo, hi); }   // (common.h: RNE; the fp16 build saturates)
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -847,16 +845,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's slot stores have been written through
     __syncthreads();                                     // (also: every wave is past the K loop - the ring is free)
     int* const flag = (int*)smem;
-    if (tid == 0) {
-      mg_handoff_release();
-      const unsigned ticket = __hip_atomic_fetch_add(&a.ln_ctr[tile_m], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(a.tiles_n - 1);
-      if (last) {
-        mg_handoff_acquire();
-        __hip_atomic_store(&a.ln_ctr[tile_m], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      *flag = last ? 1 : 0;
-    }
+    if (tid == 0) *flag = mg_draw_last_ticket(&a.ln_ctr[tile_m], (unsigned)a.tiles_n) ? 1 : 0;
     __syncthreads();
     if (*flag == 0) return;
     const int slots = a.N >> 5;
@@ -914,24 +903,14 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
           const int c = ni * 32 + gp * 16;
-          const float4 g0 = *(const float4*)(pg + c), g1 = *(const float4*)(pg + c + 4);
-          const float4 c0 = *(const float4*)(pc + c), c1 = *(const float4*)(pc + c + 4);
-          const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-          const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-          float v[8];
+          float gg[8], cc[8], v[8];
+          mg_load8(pg + c, gg);
+          mg_load8(pc + c, cc);
 #pragma unroll
           for (int j = 0; j < 4; ++j) half_swap(acc[ni][0][8 * gp + j], acc[ni][0][8 * gp + 4 + j], v[j], v[4 + j]);
-          uint32_t w4[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float s0 = __builtin_fmaf(v[2 * k], l_sc, __builtin_fmaf(l_mr, gg[2 * k], cc[2 * k])) * a.sm_scale;
-            const float s1 = __builtin_fmaf(v[2 * k + 1], l_sc, __builtin_fmaf(l_mr, gg[2 * k + 1], cc[2 * k + 1])) * a.sm_scale;
-            const float mx = fmaxf(s0, s1);
-            const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);
-            const float inv = 1.0f / (e0 + e1);
-            w4[k] = (c + 8 * half + 2 * k < a.sm_cols) ? pack2bf(e0 * inv, e1 * inv) : 0u;
-          }
-          pf[ni * 2 + gp] = __builtin_bit_cast(bf16x8, make_uint4(w4[0], w4[1], w4[2], w4[3]));
+          for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(v[j], l_sc, __builtin_fmaf(l_mr, gg[j], cc[j])) * a.sm_scale;
+          pf[ni * 2 + gp] = __builtin_bit_cast(bf16x8, mg_pair_softmax4(v, c + 8 * half, a.sm_cols));
         }
       const bf16_t* const wrow = a.w2 + (long long)l31 * 64 + 8 * half;           // + cb * 2048 + kb * 16
       bf16_t* const po = (bf16_t*)a.out + (long long)mc * a.ldo + 8 * half;      // + cb * 32 + gp * 16
@@ -982,9 +961,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
             v[4] += bc.x + bflo(r4.z); v[5] += bc.y + bfhi(r4.z); v[6] += bc.z + bflo(r4.w); v[7] += bc.w + bfhi(r4.w);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { ps += v[j]; pq = __builtin_fmaf(v[j], v[j], pq); }
-            uint4 pk;
-            pk.x = cvt_pk_bf16(v[0], v[1]); pk.y = cvt_pk_bf16(v[2], v[3]);
-            pk.z = cvt_pk_bf16(v[4], v[5]); pk.w = cvt_pk_bf16(v[6], v[7]);
+            const uint4 pk = mg_pack8(v);
             if (row_ok) *(uint4*)(po + cb * 32 + gp * 16) = pk;
           }
           sd += (double)ps;
@@ -994,11 +971,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
       if (a.ln_out) {   // here: [M] (mean, rstd) rows of the output, written directly
         sd += __shfl_xor(sd, 32);
         qd += __shfl_xor(qd, 32);
-        if (half == 0 && row_ok) {
-          const double mean = sd * a.inv_c2;
-          const float var = fmaxf((float)__builtin_fma(qd, a.inv_c2, -mean * mean), 0.f);
-          a.ln_out[m] = make_float2((float)mean, __builtin_amdgcn_rsqf(var + a.ln_eps));
-        }
+        if (half == 0 && row_ok) a.ln_out[m] = mg_row_mean_rstd(sd, qd, a.inv_c2, a.ln_eps);
       }
       return;
     }
@@ -1057,10 +1030,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
               const float o1 = o4[1] * gelu_poly_f(o4[3]);  // channel 16i + 8 + 4h + j
               half_swap(o0, o1, r[j], r[4 + j]);
             }
-            uint4 pk;
-            pk.x = cvt_pk_bf16(r[0], r[1]); pk.y = cvt_pk_bf16(r[2], r[3]);
-            pk.z = cvt_pk_bf16(r[4], r[5]); pk.w = cvt_pk_bf16(r[6], r[7]);
-            *(uint4*)(po[mi] + ni * 16) = pk;
+            *(uint4*)(po[mi] + ni * 16) = mg_pack8(r);
           }
         }
       };
@@ -1118,14 +1088,11 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
             constexpr int dummy = 0; (void)dummy;
             const int c = ni * 32 + gp * 16;              // compile-time after unrolling: an immediate offset
             if (colw + c >= a.n_end) break;               // wave-uniform
-            const float4 b0 = *(const float4*)(pb + c), b1 = *(const float4*)(pb + c + 4);
-            float cb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            float gg[8];
+            float cb[8], gg[8];
+            mg_load8(pb + c, cb);
             if constexpr (kLN) {
-              const float4 g0 = *(const float4*)(pg + c), g1 = *(const float4*)(pg + c + 4);
-              const float4 c0 = *(const float4*)(pc + c), c1 = *(const float4*)(pc + c + 4);
-              gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-              cb[0] += c0.x; cb[1] += c0.y; cb[2] += c0.z; cb[3] += c0.w; cb[4] += c1.x; cb[5] += c1.y; cb[6] += c1.z; cb[7] += c1.w;
+              mg_load8(pg + c, gg);
+              mg_add8(cb, pc + c);
             }
             uint4 rr[MI];
             float4 rv0[MI], rv1[MI];
@@ -1145,23 +1112,13 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
 #pragma unroll
               for (int j = 0; j < 8; ++j)
                 v[j] = __builtin_fmaf(v[j], l_sc[mi], kLN ? __builtin_fmaf(l_mr[mi], gg[j], cb[j]) : cb[j]);
-              if constexpr (kRV) {
-                v[0] += rv0[mi].x; v[1] += rv0[mi].y; v[2] += rv0[mi].z; v[3] += rv0[mi].w;
-                v[4] += rv1[mi].x; v[5] += rv1[mi].y; v[6] += rv1[mi].z; v[7] += rv1[mi].w;
-              }
-              if constexpr (kRES) {
-                const uint4 r4 = rr[mi];
-                v[0] += bflo(r4.x); v[1] += bfhi(r4.x); v[2] += bflo(r4.y); v[3] += bfhi(r4.y);
-                v[4] += bflo(r4.z); v[5] += bfhi(r4.z); v[6] += bflo(r4.w); v[7] += bfhi(r4.w);
-              }
+              if constexpr (kRV) mg_add8(v, rv0[mi], rv1[mi]);
+              if constexpr (kRES) mg_add8(v, rr[mi]);
               if constexpr (kLNO) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { ps[mi] += v[j]; pq[mi] = __builtin_fmaf(v[j], v[j], pq[mi]); }
               }
-              uint4 pk;
-              pk.x = cvt_pk_bf16(v[0], v[1]); pk.y = cvt_pk_bf16(v[2], v[3]);
-              pk.z = cvt_pk_bf16(v[4], v[5]); pk.w = cvt_pk_bf16(v[6], v[7]);
-              *(uint4*)(po[mi] + c) = pk;
+              *(uint4*)(po[mi] + c) = mg_pack8(v);
             }
           }
           if constexpr (kLNO) {   // both halves of the lane pair hold 16 of the row's 32 columns (N % 32 == 0: whole blocks)
@@ -1246,10 +1203,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
           }
           if (m < a.M && nok) {
             const int oc = (nb >> 1) + 8 * half;  // 16 output channels per 32 weight rows
-            uint4 pk;
-            pk.x = cvt_pk_bf16(r[0], r[1]); pk.y = cvt_pk_bf16(r[2], r[3]);
-            pk.z = cvt_pk_bf16(r[4], r[5]); pk.w = cvt_pk_bf16(r[6], r[7]);
-            *(uint4*)((bf16_t*)a.out + (long long)z * a.sO + (long long)m * a.ldo + oc) = pk;
+            *(uint4*)((bf16_t*)a.out + (long long)z * a.sO + (long long)m * a.ldo + oc) = mg_pack8(r);
           }
         }
       }
@@ -1322,14 +1276,17 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
           rv0[mi] = *(const float4*)rv;
           rv1[mi] = *(const float4*)(rv + 4);
         }
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        const float cb[8] = {c0.x + b0.x, c0.y + b0.y, c0.z + b0.z, c0.w + b0.w, c1.x + b1.x, c1.y + b1.y, c1.z + b1.z, c1.w + b1.w};
+        float gg[8], cb[8];
+        mg_join8(g0, g1, gg);
+        mg_join8(c0, c1, cb);
+        mg_add8(cb, b0, b1);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
           float v[8];
 #pragma unroll
           for (int j = 0; j < 4; ++j) half_swap(acc[ni][mi][8 * gp + j], acc[ni][mi][8 * gp + 4 + j], v[j], v[4 + j]);
-          const float rvv[8] = {rv0[mi].x, rv0[mi].y, rv0[mi].z, rv0[mi].w, rv1[mi].x, rv1[mi].y, rv1[mi].z, rv1[mi].w};
+          float rvv[8];
+          mg_join8(rv0[mi], rv1[mi], rvv);
           // scale, folded LayerNorm (rstd acc - mean rstd g + c), bias, time-embedding row: two fused multiply-adds + an add
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(v[j], l_sc[mi], __builtin_fmaf(l_mr[mi], gg[j], cb[j])) + rvv[j];
@@ -1355,16 +1312,12 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
             }
             if (ok) *(uint4*)((bf16_t*)a.out + (long long)z * a.sO + e_row[mi] * a.ldo + n) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
           } else {
-            const uint4 r4 = rr[mi];
-            v[0] += bflo(r4.x); v[1] += bfhi(r4.x); v[2] += bflo(r4.y); v[3] += bfhi(r4.y);
-            v[4] += bflo(r4.z); v[5] += bfhi(r4.z); v[6] += bflo(r4.w); v[7] += bfhi(r4.w);
+            mg_add8(v, rr[mi]);
             if (a.ln_out && ok) {
 #pragma unroll
               for (int j = 0; j < 8; ++j) { ps[mi] += v[j]; pq[mi] = __builtin_fmaf(v[j], v[j], pq[mi]); }
             }
-            uint4 pk;
-            pk.x = cvt_pk_bf16(v[0], v[1]); pk.y = cvt_pk_bf16(v[2], v[3]);
-            pk.z = cvt_pk_bf16(v[4], v[5]); pk.w = cvt_pk_bf16(v[6], v[7]);
+            const uint4 pk = mg_pack8(v);
             if (ok) *(uint4*)((bf16_t*)a.out + (long long)z * a.sO + e_row[mi] * a.ldo + n) = pk;
           }
         }
@@ -1415,10 +1368,7 @@ __device__ __forceinline__ void igemm2_body(const Igemm2Args& a) {
             const int tok = m - img * a.rows_per_img;
             if (tok + 8 <= a.rows_per_img && (a.rows_per_img & 7) == 0) {
               bf16_t* o = (bf16_t*)a.out + (long long)z * a.sO + ((long long)img * a.ctr + n) * a.ldt + tok;
-              uint4 pk;
-              pk.x = cvt_pk_bf16(v[0], v[1]); pk.y = cvt_pk_bf16(v[2], v[3]);
-              pk.z = cvt_pk_bf16(v[4], v[5]); pk.w = cvt_pk_bf16(v[6], v[7]);
-              *(uint4*)o = pk;
+              *(uint4*)o = mg_pack8(v);
             } else {
 #pragma unroll
               for (int j = 0; j < 8; ++j) {

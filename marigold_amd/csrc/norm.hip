@@ -188,16 +188,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
   // The reduction order is fixed by the thread index, not by which block happens to be last: bit-reproducible.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) {
-    mg_handoff_release();
-    const unsigned ticket = __hip_atomic_fetch_add(&counters[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == (unsigned)(slots - 1);
-    lds[0] = last ? 1.f : 0.f;
-    if (last) {
-      mg_handoff_acquire();
-      __hip_atomic_store(&counters[b], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) lds[0] = mg_draw_last_ticket(&counters[b], (unsigned)slots) ? 1.f : 0.f;
   __syncthreads();
   if (lds[0] == 0.f) return;
   gn_finalize_image<true>(partials, gamma, beta, ss, b, Ctot, groups, slots, HW, eps, threadIdx.x, 256);

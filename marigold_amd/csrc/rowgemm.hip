@@ -112,6 +112,94 @@ __device__ __forceinline__ void rg_wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// ---- the collapsed 2-token cross-attention on 32 rows held in registers: the ONE copy that rowgemm_xattn_kernel and the XA
+// prologue of rowgemm_kernel both run, so the two launches agree bit for bit by construction
+// (tests: test_rowgemm_cross_attention_as_geglu_prologue).  Two weight images in LDS at address lds0 (sb: the same place as a
+// pointer, + lane * 16): [scores stage: 2 K/16 fragments + fp32 c[64], g[64]] and, (2 K/16 + 1) KB behind it, [K/64 x 8 VO^T
+// fragments + fp32 bias[K]].  The callers differ in where the images sit and which other weights are under way, in what they wait
+// for between the two halves, in the surplus wave's part and in what becomes of the row sums.
+// First half: scores [32 rows][64] = LN(x) Wqk^T (folded LayerNorm, one ordinary stage) -> softmax over column pairs; the packed
+// probabilities are K steps 0..3 of the second product.
+template <int K>
+__device__ __forceinline__ void rg_xattn_probs(const bf16x8 (&xf)[K / 16], const char* sb, uint32_t lds0, float l_sc, float l_mr,
+                                               float sm_scale, int sm_cols, int half, bf16x8 (&pf)[4]) {
+  constexpr int KS = K / 16;
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + s * 1024));
+    const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + (KS + s) * 1024));
+    acc0 = mg_mfma32(w0, xf[s], acc0);
+    acc1 = mg_mfma32(w1, xf[s], acc1);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int c = t * 32 + q * 16 + 8 * half;   // this lane's 8 score columns: 4 (key 0, key 1) pairs
+      const uint32_t cbp = lds0 + (uint32_t)(2 * KS * 1024 + c * 4);
+      f32x4 c0 = rg_lds16<0>(cbp), c1 = rg_lds16<16>(cbp), g0 = rg_lds16<256>(cbp), g1 = rg_lds16<272>(cbp);
+      rg_lgk0(c0, c1, g0, g1);
+      float cc[8], gg[8], sv[8];
+      mg_join8(c0, c1, cc);
+      mg_join8(g0, g1, gg);
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        sv[i] = __builtin_fmaf(t == 0 ? acc0[8 * q + i] : acc1[8 * q + i], l_sc, __builtin_fmaf(l_mr, gg[i], cc[i])) * sm_scale;
+      pf[t * 2 + q] = __builtin_bit_cast(bf16x8, mg_pair_softmax4(sv, c, sm_cols));
+    }
+}
+// Second half: out = P VO^T + bias + x (K/64 sub-stages of 8 fragments), stored to po (the lane's row, + 8 half) and left in xf:
+// the rows' registers are the residual and, for the XA prologue, K steps 4 jj + 2 t + q of the projection that follows (the
+// write-back is dead in the stand-alone kernel).  sd, qd: (sum, sum of squares) of this lane's half of its row.
+template <int K>
+__device__ __forceinline__ void rg_xattn_out(bf16x8 (&xf)[K / 16], const bf16x8 (&pf)[4], const char* sb, uint32_t lds0, bf16_t* po,
+                                             int half, double& sd, double& qd) {
+  constexpr int NSUB = K / 64, S0 = (2 * (K / 16) + 1) * 1024;
+#pragma unroll
+  for (int jj = 0; jj < NSUB; ++jj) {
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 0) * 4 + s) * 1024));
+      const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 1) * 4 + s) * 1024));
+      acc0 = mg_mfma32(w0, pf[s], acc0);
+      acc1 = mg_mfma32(w1, pf[s], acc1);
+    }
+    float ps = 0.f, pq = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int c = jj * 64 + t * 32 + q * 16;
+        const uint32_t bp = lds0 + (uint32_t)(S0 + NSUB * 8 * 1024 + (c + 8 * half) * 4);
+        f32x4 b0 = rg_lds16<0>(bp), b1 = rg_lds16<16>(bp);
+        rg_lgk0(b0, b1);
+        float bb[8], rr[8], v[8];
+        mg_join8(b0, b1, bb);
+        mg_unpack8(__builtin_bit_cast(uint4, xf[jj * 4 + t * 2 + q]), rr);   // the row's own channels c + 8 half .. + 8
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          v[i] = (t == 0 ? acc0[8 * q + i] : acc1[8 * q + i]) + bb[i] + rr[i];
+          ps += v[i];
+          pq = __builtin_fmaf(v[i], v[i], pq);
+        }
+        const uint4 pk = mg_pack8(v);
+        *(uint4*)(po + c) = pk;
+        xf[jj * 4 + t * 2 + q] = __builtin_bit_cast(bf16x8, pk);
+      }
+    asm volatile("" : "+v"(ps), "+v"(pq));   // taken here (hipcc otherwise sinks the sums into the caller's `if (ln_out)` block and keeps all 320 values alive)
+    sd += (double)ps;
+    qd += (double)pq;
+    __builtin_amdgcn_sched_barrier(0);   // (unrolled for the register-resident residual: keep the sub-stages' fragment reads apart)
+  }
+}
+
 template <int K, int NW, int EPI, bool LN, bool GN, bool RES, bool LNO, bool XA = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4)))
 void rowgemm_kernel(const RgArgs a) {
@@ -167,15 +255,13 @@ void rowgemm_kernel(const RgArgs a) {
       const float* ps = a.gn_ss + (long long)(row0 / a.T) * 2 * K + 8 * half;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-        const float4 s0 = *(const float4*)(ps + 16 * s), s1 = *(const float4*)(ps + 16 * s + 4);
-        const float4 h0 = *(const float4*)(ps + K + 16 * s), h1 = *(const float4*)(ps + K + 16 * s + 4);
-        const uint4 v = __builtin_bit_cast(uint4, xf[s]);
-        uint4 o;
-        o.x = cvt_pk_bf16_f32(__builtin_fmaf(bflo(v.x), s0.x, h0.x), __builtin_fmaf(bfhi(v.x), s0.y, h0.y));
-        o.y = cvt_pk_bf16_f32(__builtin_fmaf(bflo(v.y), s0.z, h0.z), __builtin_fmaf(bfhi(v.y), s0.w, h0.w));
-        o.z = cvt_pk_bf16_f32(__builtin_fmaf(bflo(v.z), s1.x, h1.x), __builtin_fmaf(bfhi(v.z), s1.y, h1.y));
-        o.w = cvt_pk_bf16_f32(__builtin_fmaf(bflo(v.w), s1.z, h1.z), __builtin_fmaf(bfhi(v.w), s1.w, h1.w));
-        xf[s] = __builtin_bit_cast(bf16x8, o);
+        float sc[8], sh[8], v[8];
+        mg_load8(ps + 16 * s, sc);
+        mg_load8(ps + K + 16 * s, sh);
+        mg_unpack8(__builtin_bit_cast(uint4, xf[s]), v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = __builtin_fmaf(v[i], sc[i], sh[i]);
+        xf[s] = __builtin_bit_cast(bf16x8, mg_pack8(v));
       }
     }
   }
@@ -186,9 +272,9 @@ void rowgemm_kernel(const RgArgs a) {
     l_mr = -st.y * st.x;
   }
   if constexpr (XA) {
-    // ---- the collapsed cross-attention on the rows in registers (rowgemm_xattn_kernel's arithmetic, operation for operation:
-    // the results are bit-identical to the separate launch).  Its two weight images sit behind ring slot 0, which already
-    // receives the first GEGLU stage; slots 1 and 2 are primed once every wave has left the images.
+    // ---- the collapsed cross-attention on the rows in registers (rg_xattn_probs / rg_xattn_out, the code of the separate
+    // launch).  Its two weight images sit behind ring slot 0, which already receives the first GEGLU stage; slots 1 and 2 are
+    // primed once every wave has left the images.
     constexpr int NSUB = K / 64, P0 = 2 * KS + 1, P1 = NSUB * 8 + 2, S0 = P0 * 1024, XOFF = STAGE;
     auto issue_img = [&](auto pieces_tag, int src_off, int dst_off) {
       constexpr int P = decltype(pieces_tag)::value;
@@ -206,94 +292,15 @@ void rowgemm_kernel(const RgArgs a) {
       const char* const sb = smem + XOFF + lane * 16;
       const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_AS char*)smem + (uint32_t)XOFF;
       bf16x8 pf[4];
-      {
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + s * 1024));
-          const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + (KS + s) * 1024));
-          acc0 = mg_mfma32(w0, xf[s], acc0);
-          acc1 = mg_mfma32(w1, xf[s], acc1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int c = t * 32 + q * 16 + 8 * half;   // this lane's 8 score columns: 4 (key 0, key 1) pairs
-            const uint32_t cbp = lds0 + (uint32_t)(2 * KS * 1024 + c * 4);
-            f32x4 c0 = rg_lds16<0>(cbp), c1 = rg_lds16<16>(cbp), g0 = rg_lds16<256>(cbp), g1 = rg_lds16<272>(cbp);
-            rg_lgk0(c0, c1, g0, g1);
-            const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-            uint32_t w4[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float a0 = t == 0 ? acc0[8 * q + 2 * k] : acc1[8 * q + 2 * k], a1 = t == 0 ? acc0[8 * q + 2 * k + 1] : acc1[8 * q + 2 * k + 1];
-              const float s0 = __builtin_fmaf(a0, l_sc, __builtin_fmaf(l_mr, gg[2 * k], cc[2 * k])) * a.sm_scale;
-              const float s1 = __builtin_fmaf(a1, l_sc, __builtin_fmaf(l_mr, gg[2 * k + 1], cc[2 * k + 1])) * a.sm_scale;
-              const float mx = fmaxf(s0, s1);
-              const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);
-              const float inv = 1.0f / (e0 + e1);
-              w4[k] = (c + 2 * k < a.sm_cols) ? pack2bf(e0 * inv, e1 * inv) : 0u;
-            }
-            pf[t * 2 + q] = __builtin_bit_cast(bf16x8, make_uint4(w4[0], w4[1], w4[2], w4[3]));
-          }
-      }
-      bf16_t* const px2 = a.xout + (long long)m * a.ldx + 8 * half;
+      rg_xattn_probs<K>(xf, sb, lds0, l_sc, l_mr, a.sm_scale, a.sm_cols, half, pf);
       double sd2 = 0.0, qd2 = 0.0;
-#pragma unroll
-      for (int jj = 0; jj < NSUB; ++jj) {
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 0) * 4 + s) * 1024));
-          const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 1) * 4 + s) * 1024));
-          acc0 = mg_mfma32(w0, pf[s], acc0);
-          acc1 = mg_mfma32(w1, pf[s], acc1);
-        }
-        float ps = 0.f, pq = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int c = jj * 64 + t * 32 + q * 16;
-            const uint32_t bp = lds0 + (uint32_t)(S0 + NSUB * 8 * 1024 + (c + 8 * half) * 4);
-            f32x4 b0 = rg_lds16<0>(bp), b1 = rg_lds16<16>(bp);
-            rg_lgk0(b0, b1);
-            const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            const uint4 r4 = __builtin_bit_cast(uint4, xf[jj * 4 + t * 2 + q]);   // the row's own channels c + 8 half .. + 8
-            const float rr[8] = {bflo(r4.x), bfhi(r4.x), bflo(r4.y), bfhi(r4.y), bflo(r4.z), bfhi(r4.z), bflo(r4.w), bfhi(r4.w)};
-            float v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              v[i] = (t == 0 ? acc0[8 * q + i] : acc1[8 * q + i]) + bb[i] + rr[i];
-              ps += v[i];
-              pq = __builtin_fmaf(v[i], v[i], pq);
-            }
-            uint4 pk;
-            pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-            pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-            *(uint4*)(px2 + c) = pk;
-            xf[jj * 4 + t * 2 + q] = __builtin_bit_cast(bf16x8, pk);   // ... and K steps 4 jj + 2 t + q of the GEGLU projection
-          }
-        asm volatile("" : "+v"(ps), "+v"(pq));
-        sd2 += (double)ps;
-        qd2 += (double)pq;
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      rg_xattn_out<K>(xf, pf, sb, lds0, a.xout + (long long)m * a.ldx + 8 * half, half, sd2, qd2);
       // (mean, rstd) of the new rows exactly as the separate launch stores and the GEGLU form reloads them
       sd2 += __shfl_xor(sd2, 32);
       qd2 += __shfl_xor(qd2, 32);
-      const double mean = sd2 * a.inv_k;
-      const float var = fmaxf((float)__builtin_fma(qd2, a.inv_k, -mean * mean), 0.f);
-      const float mean_f = (float)mean, rstd = __builtin_amdgcn_rsqf(var + a.ln_eps);
-      l_sc = rstd;
-      l_mr = -rstd * mean_f;
+      const float2 st2 = mg_row_mean_rstd(sd2, qd2, a.inv_k, a.ln_eps);
+      l_sc = st2.y;
+      l_mr = -st2.y * st2.x;
     }
     __builtin_amdgcn_s_barrier();   // every wave has left the images: ring slots 1 and 2 are free
     if (h0 + 1 < hend) issue(h0 + 1, 1);
@@ -409,8 +416,9 @@ void rowgemm_kernel(const RgArgs a) {
           f32x4 c0 = rg_lds16<0>(cbp), c1 = rg_lds16<16>(cbp), g0 = c0, g1 = c0;
           if constexpr (LN) { g0 = rg_lds16<256>(cbp); g1 = rg_lds16<272>(cbp); }
           rg_lgk0(c0, c1, g0, g1);
-          const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-          const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+          float cc[8], gg[8];
+          mg_join8(c0, c1, cc);
+          mg_join8(g0, g1, gg);
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const float av = t == 0 ? acc0[8 * q + i] : acc1[8 * q + i];
@@ -419,8 +427,7 @@ void rowgemm_kernel(const RgArgs a) {
             else o[i] = v * o[i];
           }
         }
-        pk[q].x = cvt_pk_bf16_f32(o[0], o[1]); pk[q].y = cvt_pk_bf16_f32(o[2], o[3]);
-        pk[q].z = cvt_pk_bf16_f32(o[4], o[5]); pk[q].w = cvt_pk_bf16_f32(o[6], o[7]);
+        pk[q] = mg_pack8(o);
       }
       *(uint4*)(po + j * 32) = pk[0];
       *(uint4*)(po + j * 32 + 16) = pk[1];
@@ -449,10 +456,7 @@ void rowgemm_kernel(const RgArgs a) {
             }
             v[i] = __builtin_fmaf(av, sc, LN ? __builtin_fmaf(mr, gg, cc) : cc);
           }
-          uint4 pk;
-          pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-          pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-          *(uint4*)(pv + (long long)(t * 32) * a.ldt + 16 * q) = pk;
+          *(uint4*)(pv + (long long)(t * 32) * a.ldt + 16 * q) = mg_pack8(v);
         }
       }
     } else {
@@ -466,12 +470,12 @@ void rowgemm_kernel(const RgArgs a) {
           f32x4 c0 = rg_lds16<0>(cbp), c1 = rg_lds16<16>(cbp), g0 = c0, g1 = c0;
           if constexpr (LN) { g0 = rg_lds16<256>(cbp); g1 = rg_lds16<272>(cbp); }
           rg_lgk0(c0, c1, g0, g1);
-          const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-          const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+          float cc[8], gg[8], rr[8], v[8];
+          mg_join8(c0, c1, cc);
+          mg_join8(g0, g1, gg);
           uint4 r4 = make_uint4(0, 0, 0, 0);
           if constexpr (RES) r4 = rres[t * 2 + q];
-          const float rr[8] = {bflo(r4.x), bfhi(r4.x), bflo(r4.y), bfhi(r4.y), bflo(r4.z), bfhi(r4.z), bflo(r4.w), bfhi(r4.w)};
-          float v[8];
+          mg_unpack8(r4, rr);
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const float av = t == 0 ? acc0[8 * q + i] : acc1[8 * q + i];
@@ -479,10 +483,7 @@ void rowgemm_kernel(const RgArgs a) {
             if constexpr (RES) v[i] += rr[i];
             if constexpr (LNO) { ps += v[i]; pq = __builtin_fmaf(v[i], v[i], pq); }
           }
-          uint4 pk;
-          pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-          pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-          *(uint4*)(po + c) = pk;
+          *(uint4*)(po + c) = mg_pack8(v);
         }
       if constexpr (LNO) { sd += (double)ps; qd += (double)pq; }
       // the next stage's residual rows: behind this stage's stores, ahead of the next weight prefetch in the vmcnt queue
@@ -505,11 +506,7 @@ void rowgemm_kernel(const RgArgs a) {
   if constexpr (LNO) {   // (mean, rstd) of the new rows: the wave holds them whole (fp64 only for E[x^2] - mean^2)
     sd += __shfl_xor(sd, 32);
     qd += __shfl_xor(qd, 32);
-    if (half == 0 && active) {
-      const double mean = sd * a.inv_n;
-      const float var = fmaxf((float)__builtin_fma(qd, a.inv_n, -mean * mean), 0.f);
-      a.ln_out[m] = make_float2((float)mean, __builtin_amdgcn_rsqf(var + a.ln_eps));
-    }
+    if (half == 0 && active) a.ln_out[m] = mg_row_mean_rstd(sd, qd, a.inv_n, a.ln_eps);
   }
 }
 
@@ -564,96 +561,16 @@ void rowgemm_xattn_kernel(const RgXArgs a) {
   const char* const sb = smem + lane * 16;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_AS char*)smem;
   bf16x8 pf[4];
-  {
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + s * 1024));
-      const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + (KS + s) * 1024));
-      acc0 = mg_mfma32(w0, xf[s], acc0);
-      acc1 = mg_mfma32(w1, xf[s], acc1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int c = t * 32 + q * 16 + 8 * half;   // this lane's 8 score columns: 4 (key 0, key 1) pairs
-        const uint32_t cbp = lds0 + (uint32_t)(2 * KS * 1024 + c * 4);
-        f32x4 c0 = rg_lds16<0>(cbp), c1 = rg_lds16<16>(cbp), g0 = rg_lds16<256>(cbp), g1 = rg_lds16<272>(cbp);
-        rg_lgk0(c0, c1, g0, g1);
-        const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        uint32_t w4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float a0 = t == 0 ? acc0[8 * q + 2 * k] : acc1[8 * q + 2 * k], a1 = t == 0 ? acc0[8 * q + 2 * k + 1] : acc1[8 * q + 2 * k + 1];
-          const float s0 = __builtin_fmaf(a0, l_sc, __builtin_fmaf(l_mr, gg[2 * k], cc[2 * k])) * a.sm_scale;
-          const float s1 = __builtin_fmaf(a1, l_sc, __builtin_fmaf(l_mr, gg[2 * k + 1], cc[2 * k + 1])) * a.sm_scale;
-          const float mx = fmaxf(s0, s1);
-          const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);
-          const float inv = 1.0f / (e0 + e1);
-          w4[k] = (c + 2 * k < a.sm_cols) ? pack2bf(e0 * inv, e1 * inv) : 0u;
-        }
-        pf[t * 2 + q] = __builtin_bit_cast(bf16x8, make_uint4(w4[0], w4[1], w4[2], w4[3]));
-      }
-  }
+  rg_xattn_probs<K>(xf, sb, lds0, l_sc, l_mr, a.sm_scale, a.sm_cols, half, pf);
   rg_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   if (!active) return;
-  bf16_t* const po = a.out + (long long)m * a.ldo + 8 * half;
   double sd = 0.0, qd = 0.0;
-#pragma unroll
-  for (int jj = 0; jj < NSUB; ++jj) {
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const bf16x8 w0 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 0) * 4 + s) * 1024));
-      const bf16x8 w1 = __builtin_bit_cast(bf16x8, *(const uint4*)(sb + S0 + ((jj * 2 + 1) * 4 + s) * 1024));
-      acc0 = mg_mfma32(w0, pf[s], acc0);
-      acc1 = mg_mfma32(w1, pf[s], acc1);
-    }
-    float ps = 0.f, pq = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int c = jj * 64 + t * 32 + q * 16;
-        const uint32_t bp = lds0 + (uint32_t)(S0 + NSUB * 8 * 1024 + (c + 8 * half) * 4);
-        f32x4 b0 = rg_lds16<0>(bp), b1 = rg_lds16<16>(bp);
-        rg_lgk0(b0, b1);
-        const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-        const uint4 r4 = __builtin_bit_cast(uint4, xf[jj * 4 + t * 2 + q]);   // the row's own channels c + 8 half .. + 8
-        const float rr[8] = {bflo(r4.x), bfhi(r4.x), bflo(r4.y), bfhi(r4.y), bflo(r4.z), bfhi(r4.z), bflo(r4.w), bfhi(r4.w)};
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          v[i] = (t == 0 ? acc0[8 * q + i] : acc1[8 * q + i]) + bb[i] + rr[i];
-          ps += v[i];
-          pq = __builtin_fmaf(v[i], v[i], pq);
-        }
-        uint4 pk;
-        pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-        pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-        *(uint4*)(po + c) = pk;
-      }
-    asm volatile("" : "+v"(ps), "+v"(pq));   // taken here (hipcc otherwise sinks the sums into the `if (ln_out)` block and keeps all 320 values alive)
-    sd += (double)ps;
-    qd += (double)pq;
-    __builtin_amdgcn_sched_barrier(0);   // (unrolled for the register-resident residual: keep the sub-stages' fragment reads apart)
-  }
+  rg_xattn_out<K>(xf, pf, sb, lds0, a.out + (long long)m * a.ldo + 8 * half, half, sd, qd);
   if (a.ln_out) {
     sd += __shfl_xor(sd, 32);
     qd += __shfl_xor(qd, 32);
-    if (half == 0) {
-      const double mean = sd * a.inv_n;
-      const float var = fmaxf((float)__builtin_fma(qd, a.inv_n, -mean * mean), 0.f);
-      a.ln_out[m] = make_float2((float)mean, __builtin_amdgcn_rsqf(var + a.ln_eps));
-    }
+    if (half == 0) a.ln_out[m] = mg_row_mean_rstd(sd, qd, a.inv_n, a.ln_eps);
   }
 }
 
@@ -726,26 +643,16 @@ __global__ __launch_bounds__(256) void rowgemm_xattn_ksplit_kernel(const RgXkArg
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int c = t * 32 + q * 16 + 8 * half;
-        const float4 c0 = *(const float4*)(cbp + c), c1 = *(const float4*)(cbp + c + 4);
-        const float4 g0 = *(const float4*)(cbp + 64 + c), g1 = *(const float4*)(cbp + 64 + c + 4);
-        const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        float sv[8];
+        float cc[8], gg[8], sv[8];
+        mg_load8(cbp + c, cc);
+        mg_load8(cbp + 64 + c, gg);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const int r = t * 16 + q * 8 + i;
           const float av = (part[0][r][lane] + part[1][r][lane]) + (part[2][r][lane] + part[3][r][lane]);
           sv[i] = __builtin_fmaf(av, l_sc, __builtin_fmaf(l_mr, gg[i], cc[i])) * a.sm_scale;
         }
-        uint32_t w4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float mx = fmaxf(sv[2 * k], sv[2 * k + 1]);
-          const float e0 = __expf(sv[2 * k] - mx), e1 = __expf(sv[2 * k + 1] - mx);
-          const float inv = 1.0f / (e0 + e1);
-          w4[k] = (c + 2 * k < a.sm_cols) ? pack2bf(e0 * inv, e1 * inv) : 0u;
-        }
-        pf[t * 2 + q] = __builtin_bit_cast(bf16x8, make_uint4(w4[0], w4[1], w4[2], w4[3]));
+        pf[t * 2 + q] = __builtin_bit_cast(bf16x8, mg_pair_softmax4(sv, c, a.sm_cols));
       }
   }
   // ---- this wave's output channels [KQ wave, KQ (wave + 1)): P VO^T + bias + x ----
@@ -766,21 +673,16 @@ __global__ __launch_bounds__(256) void rowgemm_xattn_ksplit_kernel(const RgXkArg
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const float4 b0 = *(const float4*)(pb + tt * 32 + q * 16), b1 = *(const float4*)(pb + tt * 32 + q * 16 + 4);
-      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-      const uint4 r4 = __builtin_bit_cast(uint4, xf[tt * 2 + q]);
-      const float rr[8] = {bflo(r4.x), bfhi(r4.x), bflo(r4.y), bfhi(r4.y), bflo(r4.z), bfhi(r4.z), bflo(r4.w), bfhi(r4.w)};
-      float v[8];
+      float bb[8], rr[8], v[8];
+      mg_load8(pb + tt * 32 + q * 16, bb);
+      mg_unpack8(__builtin_bit_cast(uint4, xf[tt * 2 + q]), rr);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         v[i] = acc[8 * q + i] + bb[i] + rr[i];
         ps += v[i];
         pq = __builtin_fmaf(v[i], v[i], pq);
       }
-      uint4 pk;
-      pk.x = cvt_pk_bf16_f32(v[0], v[1]); pk.y = cvt_pk_bf16_f32(v[2], v[3]);
-      pk.z = cvt_pk_bf16_f32(v[4], v[5]); pk.w = cvt_pk_bf16_f32(v[6], v[7]);
-      *(uint4*)(po + tt * 32 + q * 16) = pk;
+      *(uint4*)(po + tt * 32 + q * 16) = mg_pack8(v);
     }
     if ((tt & 1) == 1 || tt == NT2 - 1) {   // fp32 partials of <= 64 values, then fp64 (as the tile GEMM's statistics)
       asm volatile("" : "+v"(ps), "+v"(pq));
@@ -796,9 +698,7 @@ __global__ __launch_bounds__(256) void rowgemm_xattn_ksplit_kernel(const RgXkArg
     if (wave == 0 && half == 0) {
       const double s4 = (rstat[0][l31][0] + rstat[1][l31][0]) + (rstat[2][l31][0] + rstat[3][l31][0]);
       const double q4 = (rstat[0][l31][1] + rstat[1][l31][1]) + (rstat[2][l31][1] + rstat[3][l31][1]);
-      const double mean = s4 * a.inv_n;
-      const float var = fmaxf((float)__builtin_fma(q4, a.inv_n, -mean * mean), 0.f);
-      a.ln_out[m] = make_float2((float)mean, __builtin_amdgcn_rsqf(var + a.ln_eps));
+      a.ln_out[m] = mg_row_mean_rstd(s4, q4, a.inv_n, a.ln_eps);
     }
   }
 }

@@ -158,16 +158,8 @@ __global__ __launch_bounds__(256) void tiny_conv_kernel(const TinyConvArgs a) {
           for (int j = 0; j < 4; ++j) half_swap(acc[ni][mi][8 * gp + j], acc[ni][mi][8 * gp + 4 + j], v[j], v[4 + j]);
           const int n = (wn * NI + ni) * 32 + 16 * gp + 8 * half;
           if (pix_ok) {
-            if (a.bias) {
-              const float4 b0 = *(const float4*)(a.bias + n), b1 = *(const float4*)(a.bias + n + 4);
-              v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w;
-              v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-            }
-            if (a.res) {
-              const uint4 r4 = *(const uint4*)(a.res + orow + n);
-              v[0] += bflo(r4.x); v[1] += bfhi(r4.x); v[2] += bflo(r4.y); v[3] += bfhi(r4.y);
-              v[4] += bflo(r4.z); v[5] += bfhi(r4.z); v[6] += bflo(r4.w); v[7] += bfhi(r4.w);
-            }
+            if (a.bias) mg_add8(v, a.bias + n);
+            if (a.res) mg_add8(v, *(const uint4*)(a.res + orow + n));
             if (a.relu) {
 #pragma unroll
               for (int j = 0; j < 8; ++j) v[j] = tv_relu(v[j]);
@@ -257,8 +249,8 @@ __global__ __launch_bounds__(256) void tiny_last_kernel(const bf16_t* __restrict
     const uint4* src = (const uint4*)(x + ((b * H + iy) * W + ix) * 64);
 #pragma unroll
     for (int c8 = 0; c8 < 8; ++c8) {
-      const uint4 u = src[c8];
-      const float v[8] = {bflo(u.x), bfhi(u.x), bflo(u.y), bfhi(u.y), bflo(u.z), bfhi(u.z), bflo(u.w), bfhi(u.w)};
+      float v[8];
+      mg_unpack8(src[c8], v);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll
