@@ -37,7 +37,8 @@ enum mg_op_kind {
    *  Statistics hand-off (P_LN_OUT, F_LN_EPS, I_TICKETS_LO / _HI): ln_out f32 [M][N/32 + 1][2] holds the LayerNorm statistics
    *  of the tensor this launch produces (bf16 epilogue, N % 32 == 0): every tile writes (sum, sum of squares) of its rows over each
    *  32-column slot into [M][N/32][2], and the last column tile of a row block to finish reduces them to (mean, rstd) rows [M][2]
-   *  stored BEHIND the slots (at ln_out + M * (N/32) * 8 bytes) - that address is the ln_in of the consuming layers.  Launches
+   *  stored BEHIND the slots (at ln_out + M * (N/32) * 8 bytes) - that address is the ln_in of the consuming layers.  ln_out is
+   *  taken from the fp32 values before they are rounded (and, in the fp16 build, saturated) to the 16-bit row that is stored.  Launches
    *  that write statistics share one ticket array: they must be stream-ordered with respect to each other.
    *  Folded LayerNorm (P_LN_IN, P_LN_G, P_LN_C; diffusers BasicTransformerBlock: norm1 -> attn1.to_q/k/v, norm2 -> attn2.to_q,
    *  norm3 -> ff.net.0.proj): A holds the raw rows x, Wt = W * gamma, and out = rstd[m] * (acc - mean[m] * ln_g[n]) + ln_c[n] with

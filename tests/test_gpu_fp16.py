@@ -19,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_kernel_suite_on_fp16_operands():
     """tests/test_gpu_kernels.py with MARIGOLD_TEST_OPERANDS=fp16: operands rounded to fp16, launches through the fp16 library,
-    fp32 torch references of the rounded values, the same tolerances.  (Cases built on bf16's exponent range are marked
-    ``bf16_only`` there and skip.)"""
+    fp32 torch references of the rounded values, the same tolerances.  (Every input there is O(1); the fused-norm cases of the
+    four-wave convolution tiles, a bf16-only kernel form, skip themselves.  The edge of the fp16 range - saturating stores, the
+    attention kernels' fp16 window - is tests/test_gpu_operand_range.py's, on both builds.)"""
     env = dict(os.environ, MARIGOLD_TEST_OPERANDS="fp16")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_kernels.py"), "-m", "gpu", "-q", "-x",
                         "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
@@ -32,7 +33,7 @@ def test_kernel_suite_on_fp16_operands():
 
 def test_norm_conditioning_on_fp16_operands():
     """tests/test_gpu_norm_conditioning.py the same way: the whole ladder (|mean| / sigma up to 64) is representable in fp16, whose
-    11-bit mantissas fill the fp32 partial sums that bf16's 8 bits leave nearly exact - nothing there is ``bf16_only``."""
+    11-bit mantissas fill the fp32 partial sums that bf16's 8 bits leave nearly exact - nothing there needs bf16's exponent range."""
     env = dict(os.environ, MARIGOLD_TEST_OPERANDS="fp16")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_norm_conditioning.py"), "-m", "gpu", "-q",
                         "-x", "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
