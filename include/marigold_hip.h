@@ -1331,6 +1331,33 @@ int mg_tile_blend(const float* tiles, int C, int th, int tw, const int* ystarts,
 int mg_tile_crop(const uint8_t* src, int hwc, int Hw, int Ww, int th, int tw, const int* ystarts, int ny, const int* xstarts, int nx,
                  int first, int count, uint8_t* dst, void* stream);
 
+/* EDGE-GUIDED UPSAMPLING of a prediction to the picture's size (marigold_amd/guided.py, pipe(..., guided_upsample=True)):
+ * joint bilateral upsampling - the low-resolution prediction is enlarged while the full-size picture decides which low-resolution
+ * neighbours a pixel may borrow from.  A plain C call on device pointers, no op kind; one launch, no atomics (two runs give the same
+ * bits), fp32 - the same bits from the bf16- and the fp16-operand build; it does not synchronise.
+ *  pred      fp32 [C][h][w], 1 <= C <= 16 (1 depth, 3 normals, 3 per target for intrinsic images); 4-byte aligned
+ *  guide_lo  uint8 planes [3][h][w]: the picture resampled to the prediction's size (mg_resize, u8, bilinear)
+ *  guide_hi  uint8, the picture itself at H x W: [H][W][3] with hwc != 0, else [3][H][W]
+ *  radius    R, 1 .. 4 (2 is the usual choice);  sigma  > 0, on the 0 .. 1 colour scale (0.1 is the usual choice)
+ *  out       fp32 [C][H][W]; 4-byte aligned.  Any H, W, h, w >= 1, smaller or larger, up to 2^30 pixels either side.
+ * For output pixel (Y, X), all in fp32:
+ *    sy = (h / H) (Y + 0.5) - 0.5 with the scale float(h) / float(H) computed first, fy = floor(sy); sx, fx likewise
+ *    taps i = fy - R + 1 .. fy + R and j = fx - R + 1 .. fx + R: (2R)^2 of them
+ *    spatial weight  max(0, 1 - |sy - i| / R) max(0, 1 - |sx - j| / R)
+ *    the tap's index is clamped into [0, h) x [0, w) AFTERWARDS (edge replication); the tap keeps its weight
+ *    range weight    expf(-d2 / (2 sigma^2)) + 1e-4,  d2 = sum over the 3 colours of (guide_hi[Y, X, c] / 255 - guide_lo[c, i, j] / 255)^2
+ *    out[c] = sum weight pred[c, i, j] / sum weight, evaluated as sum (weight / sum weight) pred[c, i, j] with IEEE divisions, the taps
+ *    in row-major order: a pixel with ONE tap of non-zero weight returns that tap's value bit for bit (equal sizes and R = 1: out = pred)
+ * The weights are computed once per pixel and serve every channel.  The floor 1e-4 keeps the denominator positive and lets the result
+ * fall back to the spatial (tent) filter where no tap resembles the pixel; with R = 1 and a constant picture the result is bilinear
+ * enlargement.  Non-finite values of pred propagate as this arithmetic gives (a tap of weight 0 with an infinite value gives NaN);
+ * there is no special case.  Refused before anything is launched, the message starting with "mg_guided_upsample:": a null pointer, C
+ * outside 1 .. 16, a size below 1 or above 2^30 pixels, a radius outside 1 .. 4, a sigma that is not > 0 or not finite (or whose
+ * 2 sigma^2 leaves the fp32 range), pred or out not 4-byte aligned.  Guided output is no out_mode of the one-call predictions: a host
+ * composes it (examples/host_guided.cpp). */
+int mg_guided_upsample(const float* pred, int C, int h, int w, const uint8_t* guide_lo, const uint8_t* guide_hi, int hwc, int H, int W,
+                       int radius, float sigma, float* out, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

@@ -3,6 +3,7 @@ reference's pipeline API (exports mirror /root/reference/marigold/__init__.py:31
 from .pipeline import (IIDEntry, MarigoldDepthOutput, MarigoldDepthPipeline,  # noqa: F401
                        MarigoldIIDOutput, MarigoldIIDPipeline, MarigoldNormalsOutput, MarigoldNormalsPipeline, SequenceState)
 from .noise import NativeNoise, native_randn  # noqa: F401
+from .guided import guided_upsample  # noqa: F401
 
 MarigoldPipeline = MarigoldDepthPipeline  # for backward compatibility
 

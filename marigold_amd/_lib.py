@@ -219,6 +219,7 @@ EXPORTS = [
     "mg_model_scratch_fill",
     "mg_tile_plan", "mg_tiles_workspace_bytes", "mg_tile_fit", "mg_tile_blend",
     "mg_tile_crop", "mg_model_predict_tiled",
+    "mg_guided_upsample",
 ]
 
 
@@ -392,6 +393,8 @@ def load(f16=False):
     lib.mg_model_predict_tiled.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64, ctypes.POINTER(MgTiledOpts),
                                                                                          ctypes.POINTER(MgPredictOpts),
                                                                                          ctypes.POINTER(MgOutputOpts)] + [ctypes.c_void_p] * 7
+    lib.mg_guided_upsample.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + \
+        [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
     lib.mg_model_scratch_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]

@@ -66,6 +66,12 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                         "which a C host reproduces (mg_model_predict_next).")
     p.add_argument("--carry_strength", type=float, default=0.1,
                    help="--sequence: the weight of the previous frame's latent in a frame's initial latents; the noise gets 1 minus it.")
+    p.add_argument("--guided_upsample", action="store_true",
+                   help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
+                        "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
+    p.add_argument("--guided_sigma", type=float, default=0.1,
+                   help="--guided_upsample: the colour distance, on the 0 .. 1 scale, at which a neighbour stops counting.")
+    p.add_argument("--guided_radius", type=int, default=2, help="--guided_upsample: the reach in low-resolution pixels, 1 to 4.")
     if kind != "iid":
         p.add_argument("--tile_size", type=int, default=0,
                        help="Predict every picture from overlapping square tiles of this size (a multiple of 8; 768 is the training size), "
@@ -93,6 +99,20 @@ def check_tile_args(args):
             or args.tiled_res < 0:
         raise ValueError(f"--tile_size {args.tile_size} / --tile_overlap {args.tile_overlap} / --tiled_res {args.tiled_res}: sizes are "
                          "multiples of 8, the tile 16 at least, the overlap at most half a tile")
+
+
+def guided_upsample_arg(args):
+    """The guided flags against the rest of the command line, before anything is loaded -> the pipelines' ``guided_upsample`` keyword,
+    or None without ``--guided_upsample`` (the keyword is then not passed at all)."""
+    if not args.guided_upsample:
+        return None
+    if args.output_processing_res:
+        raise ValueError("--guided_upsample enlarges to the input size: it cannot be combined with --output_processing_res")
+    if getattr(args, "tile_size", 0):
+        raise ValueError("--guided_upsample cannot be combined with --tile_size")
+    from .guided import settings
+    radius, sigma = settings(dict(radius=args.guided_radius, sigma=args.guided_sigma))
+    return dict(radius=radius, sigma=sigma)
 
 
 def list_images(folder):
@@ -172,6 +192,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     logging.basicConfig(level=logging.INFO)
     args = build_parser(kind).parse_args(argv)
     check_tile_args(args)
+    guided = guided_upsample_arg(args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -216,6 +237,8 @@ def main(kind: str, argv=None, pipeline=None) -> int:
               batch_size=args.batch_size, show_progress_bar=True, resample_method=args.resample_method)
     if kind == "depth":
         kw["color_map"] = args.color_map
+    if guided is not None:
+        kw["guided_upsample"] = guided
 
     def generator_of(_path):   # a fresh generator per image, like the reference's loop (script/depth/run.py:240-244)
         if args.seed is None:

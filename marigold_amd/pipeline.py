@@ -34,6 +34,7 @@ from . import dist as mdist
 from . import ops as O
 from . import tiles as tiling
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
+from .guided import guided_upsample, settings as guided_settings
 from .lanes import Turnstile as _Turnstile, run_lanes
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .noise import NativeNoise
@@ -500,18 +501,26 @@ class _MarigoldPipelineBase:
 
     _clip_range = (0, 1)           # of a finished prediction
 
-    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **finish):
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=None, **finish):
         """``__call__``'s tail: the members of one image -> its output (``_tail``: the kind's pictures, read-backs and clip).  On the
         view ``predict_tiled`` predicts on it stops in front of ``_tail``: -> the clipped prediction on the device, [H,W] or [3,H,W]
         (the clip is the one ``_tail`` applies on the host) - or, where the view asks for it (``_device_out_uncertainty``), the pair of
-        that prediction and the ensemble's uncertainty, [H,W] fp32 on the device, None without one."""
+        that prediction and the ensemble's uncertainty, [H,W] fp32 on the device, None without one.  ``guided``: None, or what
+        ``_guided_plan`` and ``_preprocess`` left for the edge-guided enlargement that then takes the resize's place -
+        (radius, sigma, the input picture's bytes on the device, whether they are HWC)."""
         if target_preds is None:  # member-parallel non-root rank with a rooted gather
             return self._empty_output()
         if ensemble_size > 1:
             final_pred, pred_uncert = self._ensemble(target_preds, ensemble_kwargs)
         else:
             final_pred, pred_uncert = target_preds, None
-        if match_input_res:
+        if guided is not None:
+            radius, sigma, picture, hwc = guided
+            lead = final_pred.shape[:-2]
+            final_pred = guided_upsample(final_pred.float().reshape((-1,) + tuple(final_pred.shape[-2:])), picture, radius, sigma, hwc,
+                                         lib=L.load(bool(getattr(self.unet, "f16", False))))
+            final_pred = final_pred.reshape(tuple(lead) + tuple(final_pred.shape[-2:]))
+        elif match_input_res:
             final_pred = resize(final_pred, input_size[-2:], interpolation=resample, antialias=True)
         if self._device_out:
             final_pred = final_pred.squeeze().float().clamp(*self._clip_range)
@@ -558,13 +567,13 @@ class _MarigoldPipelineBase:
         prediction; ``degenerate_tiles`` reports how many there are.  The guide's uncertainty is not used.
 
         A depth output carries ``degenerate_tiles``, the number of tiles ``tiles.fit`` flagged.  Refused: the intrinsic-image pipeline,
-        member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program`` and ``processing_res`` (``tiled_res`` and
-        ``guide_res`` take its place)."""
+        member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program``, ``guided_upsample`` and ``processing_res``
+        (``tiled_res`` and ``guide_res`` take its place)."""
         if self._kind not in ("depth", "normals"):
             raise ValueError("predict_tiled: the intrinsic-image pipeline is not supported (depth and normals only)")
         if self._member_parallel or self._sharded():
             raise ValueError("predict_tiled is not available on a member-parallel pipeline")
-        for name in ("init_latents", "sequence", "images_per_program", "processing_res"):
+        for name in ("init_latents", "sequence", "images_per_program", "processing_res", "guided_upsample"):
             if call_kwargs.get(name) is not None:
                 raise ValueError(f"predict_tiled: {name} cannot be combined with tiles")
             call_kwargs.pop(name, None)
@@ -813,7 +822,7 @@ class _MarigoldPipelineBase:
         return torch.cat(preds, dim=0) if len(preds) > 1 else preds[0]
 
     _call_args = ("denoising_steps", "ensemble_size", "processing_res", "match_input_res", "resample_method", "batch_size",
-                  "show_progress_bar", "ensemble_kwargs")
+                  "show_progress_bar", "ensemble_kwargs", "guided_upsample")
 
     @torch.no_grad()
     def _call_group(self, images, generators, call_kwargs):
@@ -826,31 +835,59 @@ class _MarigoldPipelineBase:
             raise TypeError(f"{type(self).__name__}() got unexpected keyword arguments {sorted(unknown)}")
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             kw.get("denoising_steps"), kw.get("ensemble_size", 1), kw.get("processing_res"), kw.get("resample_method", "bilinear"))
-        prepared = [self._preprocess(im, processing_res, resample) for im in images]
-        sizes = {tuple(r.shape[-2:]) for r, _ in prepared}
+        plans = [self._guided_plan(kw.get("guided_upsample"), kw.get("match_input_res", True), im) for im in images]
+        prepared = [self._guided_prepared(im, processing_res, resample, plan) for im, plan in zip(images, plans)]
+        sizes = {tuple(r.shape[-2:]) for r, _, _ in prepared}
         if len(sizes) != 1:
             raise ValueError(f"images of one program must have one processed size, got {sorted(sizes)}")
-        preds = self._predict_group([r for r, _ in prepared], ensemble_size, denoising_steps, kw.get("batch_size", 0),
+        preds = self._predict_group([r for r, _, _ in prepared], ensemble_size, denoising_steps, kw.get("batch_size", 0),
                                     [None] * len(images) if generators is None else list(generators))
         E = ensemble_size
         finish = {a: kw[a] for a in self._finish_args if a in kw}
         return [self._finish(preds[j * E:(j + 1) * E], input_size, ensemble_size, kw.get("match_input_res", True), resample,
-                             kw.get("ensemble_kwargs"), **finish) for j, (_, input_size) in enumerate(prepared)]
+                             kw.get("ensemble_kwargs"), guided=guided, **finish) for j, (_, input_size, guided) in enumerate(prepared)]
 
     _finish_args = ()   # the keywords of ``__call__`` that go to the kind's ``_tail``
 
     @torch.no_grad()
     def _call(self, input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-              generator, ensemble_kwargs, init_latents, sequence, **finish):
+              generator, ensemble_kwargs, init_latents, sequence, guided_upsample=None, **finish):
         """What every kind's ``__call__`` runs; ``finish``: its keywords of ``_finish_args``."""
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             denoising_steps, ensemble_size, processing_res, resample_method)
+        plan = self._guided_plan(guided_upsample, match_input_res, input_image)
         carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
-        rgb_norm, input_size = self._preprocess(input_image, processing_res, resample)
+        rgb_norm, input_size, guided = self._guided_prepared(input_image, processing_res, resample, plan)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents, carry)
-        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, **finish)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=guided, **finish)
+
+    def _guided_plan(self, guided_upsample, match_input_res, input_image):
+        """``__call__``'s check of ``guided_upsample=``, before anything is launched -> None (the keyword is off) | (radius, sigma)."""
+        plan = guided_settings(guided_upsample)
+        if plan is None:
+            return None
+        if not match_input_res:
+            raise ValueError("guided_upsample enlarges the prediction to the input size: it cannot be combined with match_input_res=False")
+        if getattr(self.device, "type", None) != "cuda" or not getattr(self, "device_io_stages", False):
+            raise ValueError("guided_upsample runs on the device: it needs a CUDA pipeline with device_io_stages")
+        if self._member_parallel or self._sharded():
+            raise ValueError("guided_upsample is not available on a member-parallel pipeline")
+        if not isinstance(input_image, Image.Image) and not (
+                isinstance(input_image, torch.Tensor) and input_image.dtype == torch.uint8 and input_image.dim() == 4
+                and tuple(input_image.shape[:2]) == (1, 3)):
+            raise ValueError("guided_upsample is guided by the input picture's bytes: the input must be a PIL image or a uint8 "
+                             "[1, 3, H, W] tensor")
+        return plan
+
+    def _guided_prepared(self, input_image, processing_res, resample, plan):
+        """``_preprocess`` -> (rgb_norm, input_size, ``_finish``'s ``guided``): with a plan the picture's bytes, uploaded once for the
+        input stage, are kept for the finish stage."""
+        if plan is None:
+            return self._preprocess(input_image, processing_res, resample) + (None,)
+        rgb_norm, input_size, picture, hwc = self._preprocess_device(input_image, processing_res, resample, keep_picture=True)
+        return rgb_norm, input_size, plan + (picture, hwc)
 
     def _call_settings(self, denoising_steps, ensemble_size, processing_res, resample_method):
         """``__call__``'s defaults and argument checks -> (denoising_steps, ensemble_size, processing_res, resample mode)."""
@@ -877,11 +914,13 @@ class _MarigoldPipelineBase:
     # normals pipeline's ``_tail``.  False: the host code of both (what host pipelines and float inputs run anyway) - the same bits.
     device_io_stages = True
 
-    def _preprocess_device(self, input_image, processing_res, resample_method):
+    def _preprocess_device(self, input_image, processing_res, resample_method, keep_picture=False):
         """``_preprocess`` of a PIL image or a uint8 [1,3,H,W] tensor on the device -> (rgb_norm on the device, input_size), or None
         where the host code must run to give the same bits.  The picture goes up once as uint8 - PIL's HWC bytes as they are, no
         host transpose - and one MG_OP_RGB_PREP makes what the VAE encoder reads.  The range assert of the host code is vacuous
-        here: the bytes 0 ... 255 map into [-1, 1] exactly (0 -> -1, 255 -> 1, monotonic in between), so it is not repeated."""
+        here: the bytes 0 ... 255 map into [-1, 1] exactly (0 -> -1, 255 -> 1, monotonic in between), so it is not repeated.
+        ``keep_picture``: -> (rgb_norm, input_size, the uploaded bytes, whether they are HWC) - the one upload serves the finish stage
+        too (``guided_upsample=``)."""
         if isinstance(input_image, Image.Image):
             u8 = torch.from_numpy(np.array(input_image.convert("RGB")))   # [H,W,3]; (np.array: torch wants a writable buffer)
             hwc, hw = True, tuple(u8.shape[:2])
@@ -896,9 +935,10 @@ class _MarigoldPipelineBase:
         resample = processing_res > 0 and max(hw) != processing_res   # (else resize_max_res's factor is exactly 1: the same size)
         on_device = u8.is_cuda or resample
         size = max_res_size(hw, processing_res) if resample else hw
-        if u8.is_cuda and u8.device != self.device:
+        if keep_picture or (u8.is_cuda and u8.device != self.device):
             u8 = u8.to(self.device)
-        return prepare_rgb_device(u8, size, resample_method, self.io_dtype, hwc, device=self.device, reciprocal=on_device), input_size
+        rgb_norm = prepare_rgb_device(u8, size, resample_method, self.io_dtype, hwc, device=self.device, reciprocal=on_device)
+        return (rgb_norm, input_size, u8, hwc) if keep_picture else (rgb_norm, input_size)
 
     def _preprocess(self, input_image, processing_res, resample_method):
         if getattr(self, "device_io_stages", False) and getattr(self.device, "type", None) == "cuda":
@@ -950,9 +990,9 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, color_map: str = "Spectral",
                  show_progress_bar: bool = True, ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None) -> MarigoldDepthOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldDepthOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence, color_map=color_map)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample, color_map=color_map)
 
     _finish_args = ("color_map",)
 
@@ -1020,9 +1060,9 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None) -> MarigoldNormalsOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldNormalsOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample)
 
     _clip_range = (-1, 1)
 
@@ -1185,9 +1225,9 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None) -> MarigoldIIDOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldIIDOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample)
 
     def _empty_output(self) -> MarigoldIIDOutput:
         return MarigoldIIDOutput(target_names=self.target_names)
