@@ -1358,6 +1358,43 @@ int mg_tile_crop(const uint8_t* src, int hwc, int Hw, int Ww, int th, int tw, co
 int mg_guided_upsample(const float* pred, int C, int h, int w, const uint8_t* guide_lo, const uint8_t* guide_hi, int hwc, int H, int W,
                        int radius, float sigma, float* out, void* stream);
 
+/* DEPTH ALIGNMENT (marigold_amd/align.py, pipe(..., align=state), map_video(align=True)): the scale and shift that carry
+ * one affine-invariant depth map into the range of another - a reference with trusted values at some pixels, or the frame before -
+ * fitted robustly on the device, and their application.  Plain C calls on device pointers, no op kind.  Every argument check comes
+ * before any GPU work and every message starts with the function's name; nothing synchronises.
+ *  mg_depth_align_workspace_bytes: what mg_depth_align_fit needs for n pixels, 1 <= n <= 2^30 (-1 with mg_last_error otherwise).
+ *  mg_depth_align_fit: d, ref fp32 [n]; mask uint8 [n] or NULL.  A pixel COUNTS when its mask byte is non-zero (or there is no mask) and
+ *    d and ref are both finite.  All arithmetic is fp64.  One SOLVE, with weights w over the pixels that count: the sums N = sum w,
+ *    Sd = sum w d, Sg = sum w ref, Sdd = sum w d^2, Sdg = sum w d ref - the terms are w d, (w d) d and (w d) ref, each product rounded -
+ *    then, with fit_shift != 0, s = (N Sdg - Sd Sg) / (N Sdd - Sd^2), t = (Sg - s Sd) / N; with fit_shift = 0, s = Sdg / Sdd, t = 0.
+ *    iters = 0: one solve with w = 1 - plain least squares; start_mode and the start values are ignored.  iters = k >= 1: k solves with
+ *    the Cauchy weights w = 1 / (1 + r^2), r = ((s d + t) - ref) / delta, each from the coefficients of the solve before it; the first
+ *    from (s_start, t_start) under MG_ALIGN_START_GIVEN, from an extra unweighted solve done first under MG_ALIGN_START_LS.  delta is
+ *    in the units of ref: a residual of delta halves a pixel's weight.  The coefficients never leave the device between solves: the
+ *    solve launch writes them to `coef`, where the next partial-sum launch reads them.  Sums as in mg_tile_fit: fixed chunks of
+ *    pixels, lanes -> wave shuffle -> LDS -> one partial per chunk in `ws`, then a second launch (one wave) adds the partials in a fixed
+ *    order and solves.  No atomics: two runs give the same bits, and so do the bf16- and the fp16-operand build.  The fit is
+ *    DEGENERATE when fewer than 2 pixels count, when N Sdd - Sd^2 <= 1e-12 N^2 (with shift) or Sdd <= 1e-12 N (without), or when a
+ *    solve yields s <= 0 or a coefficient that is not finite: then coef = (1, 0) and flag = 1, and the remaining solves change
+ *    nothing; else flag = 0.  coef DEVICE fp64 [2] (s, t), flag DEVICE int32 [1], ws 16-byte aligned.  Refused: n < 1 or > 2^30, a
+ *    null d, ref, coef, flag or ws, pointers not aligned to their elements, ws_bytes too small or ws not 16-byte aligned, iters outside
+ *    0 .. MG_ALIGN_MAX_ITERS, and with iters >= 1 an unknown start_mode, a delta that is not finite or <= 0, start values that are not
+ *    finite under MG_ALIGN_START_GIVEN.
+ *  mg_depth_align_apply: out[i] = (float)((double)x[i] * coef[0] + (use_shift ? coef[1] : 0)) - the product and the sum each rounded
+ *    in fp64, then one rounding to fp32.  With clip_lo <= clip_hi the result v is clamped as v < lo ? lo : (v > hi ? hi : v), so a NaN
+ *    stays a NaN; clip_lo > clip_hi (or a NaN bound) means no clamp.  out may be x.  Four elements per lane where x and out are both
+ *    16-byte aligned, element by element otherwise and for the n % 4 tail.  use_shift = 0 is how an uncertainty map follows its
+ *    depth map.  Refused: n < 1 or > 2^30, a null x, coef or out, pointers not aligned to their elements.
+ * Alignment is no stage of the one-call predictions: a host composes it (examples/host_align.cpp). */
+#define MG_ALIGN_MAX_ITERS 32
+enum { MG_ALIGN_START_GIVEN = 0, MG_ALIGN_START_LS = 1 };
+long long mg_depth_align_workspace_bytes(long long n);
+int mg_depth_align_fit(const float* d, const float* ref, const unsigned char* mask_or_null, long long n,
+                       int fit_shift, int iters, int start_mode, double s_start, double t_start, double delta,
+                       double* coef, int* flag, void* ws, long long ws_bytes, void* stream);
+int mg_depth_align_apply(const float* x, long long n, const double* coef, int use_shift,
+                         float clip_lo, float clip_hi, float* out, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

@@ -4,6 +4,7 @@ from .pipeline import (IIDEntry, MarigoldDepthOutput, MarigoldDepthPipeline,  # 
                        MarigoldIIDOutput, MarigoldIIDPipeline, MarigoldNormalsOutput, MarigoldNormalsPipeline, SequenceState)
 from .noise import NativeNoise, native_randn  # noqa: F401
 from .guided import guided_upsample  # noqa: F401
+from .align import DepthAlignState, align_depth  # noqa: F401
 
 MarigoldPipeline = MarigoldDepthPipeline  # for backward compatibility
 

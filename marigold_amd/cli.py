@@ -66,6 +66,16 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                         "which a C host reproduces (mg_model_predict_next).")
     p.add_argument("--carry_strength", type=float, default=0.1,
                    help="--sequence: the weight of the previous frame's latent in a frame's initial latents; the noise gets 1 minus it.")
+    if kind == "depth":   # (the other kinds have no affine ambiguity: there the flags are unknown arguments)
+        p.add_argument("--sequence_align", action="store_true",
+                       help="--sequence: fit every frame's depth map, scale and shift, robustly to the aligned map of the frame before "
+                            "(or to the first frame's) on the GPU, so that the range stops changing from frame to frame "
+                            "(map_video(align=...)).")
+        p.add_argument("--align_delta", type=float, default=0.05,
+                       help="--sequence_align: the residual, in depth units, at which a pixel's weight in the fit has fallen to a half.")
+        p.add_argument("--align_iters", type=int, default=4, help="--sequence_align: reweighted solves per frame, 0 (plain least squares) to 32.")
+        p.add_argument("--align_reference", choices=["previous", "first"], default="previous",
+                       help="--sequence_align: what a frame is fitted to.")
     p.add_argument("--guided_upsample", action="store_true",
                    help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
                         "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
@@ -113,6 +123,21 @@ def guided_upsample_arg(args):
     from .guided import settings
     radius, sigma = settings(dict(radius=args.guided_radius, sigma=args.guided_sigma))
     return dict(radius=radius, sigma=sigma)
+
+
+def sequence_align_arg(parser, args):
+    """The alignment flags against the rest of the command line, before anything is loaded -> ``map_video``'s ``align`` keyword, or None
+    without ``--sequence_align`` (the keyword is then not passed at all).  What does not fit is an argparse error."""
+    if not getattr(args, "sequence_align", False):
+        return None
+    if not args.sequence:
+        parser.error("--sequence_align aligns consecutive frames: it needs --sequence")
+    from .align import DepthAlignState
+    try:
+        DepthAlignState(iters=args.align_iters, delta=args.align_delta, reference=args.align_reference)
+    except ValueError as e:
+        parser.error(str(e))
+    return dict(iters=args.align_iters, delta=args.align_delta, reference=args.align_reference)
 
 
 def list_images(folder):
@@ -190,9 +215,11 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     """``pipeline`` lets tests inject a ready pipeline object; otherwise the checkpoint is loaded."""
     import torch
     logging.basicConfig(level=logging.INFO)
-    args = build_parser(kind).parse_args(argv)
+    parser = build_parser(kind)
+    args = parser.parse_args(argv)
     check_tile_args(args)
     guided = guided_upsample_arg(args)
+    align = sequence_align_arg(parser, args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -257,8 +284,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
             raise RuntimeError("--sequence needs a pipeline with map_video")
         from .noise import NativeNoise
         seeds = (None if args.seed is None else NativeNoise(args.seed + k) for k in range(len(files)))
+        video_kw = dict(kw) if align is None else dict(kw, align=align)
         outs = pipeline.map_video((Image.open(f) for f in files), strength=args.carry_strength, in_flight=args.maps_in_flight or None,
-                                  generators=seeds, **kw)
+                                  generators=seeds, **video_kw)
         for rgb_path, out in zip(files, outs):
             save_prediction(kind, dirs, rgb_path, out)
     elif getattr(args, "tile_size", 0):

@@ -33,6 +33,15 @@ class Turnstile:
             self._cv.notify_all()
 
 
+class Turnstiles(tuple):
+    """One ``Turnstile`` per ordered stage of a call (``map_video(align=...)``: the denoise stage, then the align stage).  They fail
+    together: a lane waiting at any stage must not wait for a call that will never reach it."""
+
+    def abort(self, error):
+        for t in self:
+            t.abort(error)
+
+
 def run_lanes(lanes, take, run, turnstile=None):
     """A generator over the outputs of ``run(lane_index, group, k)`` for every ``(k, group)`` that ``take()`` hands out (None: the
     input is exhausted; k counts from 0), in the order of k, as they complete.

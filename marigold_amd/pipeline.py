@@ -14,6 +14,8 @@ ensembling).  Differences that are deliberate and documented in DESIGN.md:
 * ``map_images(images_per_program=k)`` (extension) runs the members of up to k same-size images in one program;
 * ``sequence=SequenceState()`` / ``map_video`` (extension) carry each frame's denoised latent into the next frame's initial noise
   (DESIGN.md 6c);
+* ``align=DepthAlignState()`` / ``map_video(align=True)`` (extension, depth) fit every frame's map, scale and shift, robustly to the
+  frame before on the device, so that the range stops changing from frame to frame (align.py, DESIGN.md 6g);
 * ``predict_tiled`` (extension) cuts a large picture into overlapping tiles of the training size, predicts them through
   ``map_images`` and stitches them on the device (tiles.py).
 """
@@ -33,9 +35,10 @@ from . import _lib as L
 from . import dist as mdist
 from . import ops as O
 from . import tiles as tiling
+from .align import DepthAlignState, settings as align_settings
 from .ensemble import ensemble_depth, ensemble_iid, ensemble_normals
 from .guided import guided_upsample, settings as guided_settings
-from .lanes import Turnstile as _Turnstile, run_lanes
+from .lanes import Turnstile as _Turnstile, Turnstiles as _Turnstiles, run_lanes
 from .modules import AutoencoderKLHIP, UNet2DConditionModelHIP
 from .noise import NativeNoise
 from .schedulers import DDIMScheduler, LCMScheduler
@@ -49,11 +52,15 @@ from .util.image_util import (chw2hwc, colorize_depth_device, colorize_depth_map
 class MarigoldDepthOutput:
     """depth_np [H,W] in [0,1]; depth_colored PIL RGB | None; uncertainty [H,W] | None
     (reference :60-75).  ``degenerate_tiles`` (extension): None, or - from ``predict_tiled`` - how many tiles could not be fitted to
-    the guide (constant, no valid pixel, a slope <= 0) and were replaced by the guide's mean over them."""
+    the guide (constant, no valid pixel, a slope <= 0) and were replaced by the guide's mean over them.  ``align_coef`` / ``align_flag``
+    (extension): None, or - from a call with ``align=`` - the DEVICE tensors of the frame's fit, fp64 [2] (s, t) and int32 [1]
+    (1: degenerate, the frame passed unchanged); reading them is the caller's choice."""
     depth_np: np.ndarray
     depth_colored: Union[None, Image.Image]
     uncertainty: Union[None, np.ndarray]
     degenerate_tiles: Optional[int] = None
+    align_coef: Optional[torch.Tensor] = None
+    align_flag: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -161,6 +168,7 @@ class _MarigoldPipelineBase:
     _pred_channels = 1             # channels of one decoded prediction
     _gather_turn = None            # (turnstile, map index): set only on the per-call view a lane of map_images runs on
     _sequence_turn = None          # (turnstile, frame index): likewise, on the view a lane of map_video runs on
+    _align_turn = None             # (turnstile, frame index): likewise, for the align stage of map_video(align=...)
 
     def __init__(self, unet: UNet2DConditionModelHIP, vae: AutoencoderKLHIP,
                  scheduler: Union[DDIMScheduler, LCMScheduler], text_encoder=None, tokenizer=None,
@@ -322,6 +330,8 @@ class _MarigoldPipelineBase:
         k = int(images_per_program)
         if k < 1:
             raise ValueError(f"images_per_program must be >= 1 (got {images_per_program})")
+        if call_kwargs.get("align") is not None:
+            raise ValueError("map_images: align orders consecutive frames; use map_video(align=...) or call the pipeline frame by frame")
         if k > 1:
             if call_kwargs.get("init_latents") is not None:
                 raise ValueError("map_images: init_latents cannot be combined with images_per_program > 1")
@@ -392,7 +402,8 @@ class _MarigoldPipelineBase:
     def _drive_lanes(self, groups, n, ordered, run_one):
         """A generator over the outputs of ``run_one(view, group, k, turnstile)`` for group k = 0, 1 ... of the iterator ``groups``, on
         ``n`` lanes (``run_lanes``).  ``view``: the pipeline the lane runs on; ``turnstile``: with several lanes and ``ordered``, the
-        ``Turnstile`` a stage of the calls passes in the order of k, else None."""
+        ``Turnstile`` a stage of the calls passes in the order of k, else None; ``ordered`` = 2, 3 ...: that many stages, a
+        ``Turnstiles`` with one turnstile each, which fail together."""
         take = functools.partial(next, enumerate(groups), None)   # -> (index, group) | None; one lane at a time (run_lanes)
         views, contexts, leave, turnstile = [self], [contextlib.nullcontext()], lambda: None, None   # one lane: inline, on this very object
         if n > 1:
@@ -401,7 +412,7 @@ class _MarigoldPipelineBase:
             lanes = self._lane_resources(n)
             views = [self._view(e.unet, e.vae) for e, _ in lanes]   # lane 0 too: no lane works on the caller's object
             contexts, leave = self._lane_contexts([stream for _, stream in lanes])
-            turnstile = _Turnstile() if ordered else None
+            turnstile = None if not ordered else _Turnstile() if ordered is True else _Turnstiles(_Turnstile() for _ in range(ordered))
         try:
             yield from run_lanes(contexts, take, lambda lane, group, k: run_one(views[lane], group, k, turnstile), turnstile)
         finally:
@@ -449,7 +460,7 @@ class _MarigoldPipelineBase:
         tools/sequence_bench.py, profiles/sequence_768.log)."""
         return self.maps_in_flight_for(ensemble_size)
 
-    def map_video(self, frames, strength: float = 0.1, in_flight: Optional[int] = None, generators=None, **call_kwargs):
+    def map_video(self, frames, strength: float = 0.1, in_flight: Optional[int] = None, generators=None, align=None, **call_kwargs):
         """``state = SequenceState(strength); (pipe(frame, sequence=state, generator=g, **call_kwargs) for frame, g in zip(frames,
         generators))`` - consecutive frames of one sequence, each started from the frame before (``SequenceState``) - with up to
         ``in_flight`` frames on the GPU at a time (default ``frames_in_flight_for(ensemble_size)``).  A generator with ``map_images``'
@@ -458,7 +469,17 @@ class _MarigoldPipelineBase:
         denoise stage takes turns (a ``Turnstile``, frame by frame; its GPU work is ordered by events, nothing waits on the host),
         while a frame's preprocessing and encode run ahead of its turn and its decode, ensemble and output stage behind it.
         Refused: ``images_per_program``, ``init_latents``, member-parallel pipelines, a frame whose processed size differs from the
-        first frame's."""
+        first frame's.
+
+        ``align`` (depth only): ``True`` or a dict with ``iters``, ``delta``, ``reference`` and / or ``fit_shift`` - one
+        ``DepthAlignState`` for this call, ``pipe(frame, sequence=state, align=align_state, ...)`` per frame: every frame's map is fitted,
+        scale and shift, to the aligned map of the frame before (or the first frame's).  With several lanes the align stage takes turns
+        in frame order too, on a turnstile of its own; the outputs stay the serial loop's bit for bit."""
+        if isinstance(align, DepthAlignState):
+            raise ValueError("map_video: align is True or a dict of settings; the call keeps a DepthAlignState of its own")
+        align_state = align_settings(align)
+        if align_state is not None:
+            self._align_plan(align_state, None, None)   # (the kind and the device: refused before anything is drawn or launched)
         for name in ("images_per_program", "init_latents", "sequence"):
             if call_kwargs.get(name) is not None:
                 raise ValueError(f"map_video: {name} cannot be combined with a sequence of frames")
@@ -485,11 +506,15 @@ class _MarigoldPipelineBase:
             image, g = group[0]
             if generators is not None:
                 kw["generator"] = g
-            if turnstile is not None:
-                pipe._sequence_turn = (turnstile, index)   # on this call's view of the lane
+            if align_state is not None:
+                kw["align"] = align_state
+            if turnstile is not None:   # on this call's view of the lane
+                pipe._sequence_turn = (turnstile if align_state is None else turnstile[0], index)
+                pipe._align_turn = None if align_state is None else (turnstile[1], index)
             return [pipe(image, sequence=state, **kw)]
 
-        return self._drive_lanes(items(), n, True, run_one)   # (a turnstile: the denoise stages, frame by frame)
+        # (a turnstile: the denoise stages, frame by frame; with align a second one: the align stages)
+        return self._drive_lanes(items(), n, True if align_state is None else 2, run_one)
 
     # ---- large pictures: tiles ---------------------------------------------------------------
     # A picture far above the training size is cut into overlapping tiles of that size on a grid (tiles.plan); the tiles are
@@ -501,19 +526,26 @@ class _MarigoldPipelineBase:
 
     _clip_range = (0, 1)           # of a finished prediction
 
-    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=None, **finish):
+    def _finish(self, target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=None, align=None,
+                **finish):
         """``__call__``'s tail: the members of one image -> its output (``_tail``: the kind's pictures, read-backs and clip).  On the
         view ``predict_tiled`` predicts on it stops in front of ``_tail``: -> the clipped prediction on the device, [H,W] or [3,H,W]
         (the clip is the one ``_tail`` applies on the host) - or, where the view asks for it (``_device_out_uncertainty``), the pair of
         that prediction and the ensemble's uncertainty, [H,W] fp32 on the device, None without one.  ``guided``: None, or what
         ``_guided_plan`` and ``_preprocess`` left for the edge-guided enlargement that then takes the resize's place -
-        (radius, sigma, the input picture's bytes on the device, whether they are HWC)."""
+        (radius, sigma, the input picture's bytes on the device, whether they are HWC).  ``align``: None, or the frame's
+        ``DepthAlignState`` (``_align_plan``): after the ensemble and before the enlargement the prediction is fitted to the state's
+        reference and replaced by ``s * pred + t``, unclipped, the uncertainty by ``s`` times itself; the output carries the fit."""
         if target_preds is None:  # member-parallel non-root rank with a rooted gather
             return self._empty_output()
         if ensemble_size > 1:
             final_pred, pred_uncert = self._ensemble(target_preds, ensemble_kwargs)
         else:
             final_pred, pred_uncert = target_preds, None
+        fitted = None
+        if align is not None:
+            final_pred, pred_uncert, *fitted = align._step(final_pred, pred_uncert, L.load(bool(getattr(self.unet, "f16", False))),
+                                                           self._align_turn)
         if guided is not None:
             radius, sigma, picture, hwc = guided
             lead = final_pred.shape[:-2]
@@ -527,7 +559,10 @@ class _MarigoldPipelineBase:
             if self._device_out_uncertainty:
                 return final_pred, None if pred_uncert is None else pred_uncert.squeeze().float()
             return final_pred
-        return self._tail(final_pred, pred_uncert, **finish)
+        out = self._tail(final_pred, pred_uncert, **finish)
+        if fitted is not None:
+            out.align_coef, out.align_flag = fitted
+        return out
 
     @torch.no_grad()
     def predict_tiled(self, image, tile_size=768, tile_overlap=192, tiled_res: int = 0, guide_res: Optional[int] = None,
@@ -567,13 +602,13 @@ class _MarigoldPipelineBase:
         prediction; ``degenerate_tiles`` reports how many there are.  The guide's uncertainty is not used.
 
         A depth output carries ``degenerate_tiles``, the number of tiles ``tiles.fit`` flagged.  Refused: the intrinsic-image pipeline,
-        member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program``, ``guided_upsample`` and ``processing_res``
-        (``tiled_res`` and ``guide_res`` take its place)."""
+        member-parallel pipelines, ``init_latents``, ``sequence``, ``images_per_program``, ``guided_upsample``, ``align`` and
+        ``processing_res`` (``tiled_res`` and ``guide_res`` take its place)."""
         if self._kind not in ("depth", "normals"):
             raise ValueError("predict_tiled: the intrinsic-image pipeline is not supported (depth and normals only)")
         if self._member_parallel or self._sharded():
             raise ValueError("predict_tiled is not available on a member-parallel pipeline")
-        for name in ("init_latents", "sequence", "images_per_program", "processing_res", "guided_upsample"):
+        for name in ("init_latents", "sequence", "images_per_program", "processing_res", "guided_upsample", "align"):
             if call_kwargs.get(name) is not None:
                 raise ValueError(f"predict_tiled: {name} cannot be combined with tiles")
             call_kwargs.pop(name, None)
@@ -851,17 +886,44 @@ class _MarigoldPipelineBase:
 
     @torch.no_grad()
     def _call(self, input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-              generator, ensemble_kwargs, init_latents, sequence, guided_upsample=None, **finish):
+              generator, ensemble_kwargs, init_latents, sequence, guided_upsample=None, align=None, **finish):
         """What every kind's ``__call__`` runs; ``finish``: its keywords of ``_finish_args``."""
         denoising_steps, ensemble_size, processing_res, resample = self._call_settings(
             denoising_steps, ensemble_size, processing_res, resample_method)
         plan = self._guided_plan(guided_upsample, match_input_res, input_image)
         carry = self._frame_carry(sequence, init_latents, input_image, processing_res, ensemble_size)
+        align = self._align_plan(align, input_image, processing_res)
         rgb_norm, input_size, guided = self._guided_prepared(input_image, processing_res, resample, plan)
 
         target_preds = self._predict_members(rgb_norm, ensemble_size, denoising_steps, batch_size,
                                              generator, init_latents, carry)
-        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=guided, **finish)
+        return self._finish(target_preds, input_size, ensemble_size, match_input_res, resample, ensemble_kwargs, guided=guided, align=align,
+                            **finish)
+
+    def _align_plan(self, align, input_image, processing_res):
+        """``__call__``'s check of ``align=``, before anything is launched -> the frame's ``DepthAlignState`` | None.  ``input_image``
+        None (``map_video``, before its first frame): the kind and the device alone."""
+        if align is None:
+            return None
+        if not isinstance(align, DepthAlignState):
+            raise TypeError(f"align must be a DepthAlignState (got {type(align).__name__})")
+        if self._kind != "depth":
+            raise ValueError(f"align fits the scale and shift of an affine-invariant depth map: the {self._kind} pipeline has no such ambiguity")
+        if self._member_parallel or self._sharded():
+            raise ValueError("align is not available on a member-parallel pipeline")
+        if getattr(self.device, "type", None) != "cuda":
+            raise ValueError("align runs on the device: it needs a CUDA pipeline")
+        if self._device_out:
+            raise ValueError("align cannot be combined with tiles")
+        if input_image is not None:
+            align._check((tuple(int(v) for v in self._decoded_size(self._processed_size(input_image, processing_res))), self.device))
+        return align
+
+    def _decoded_size(self, hw):
+        """(height, width) of a prediction decoded from the latent of a picture processed at ``hw``: the latent's size times the VAE's
+        factor, which is below ``hw`` where that is no multiple of the factor."""
+        f = getattr(self.vae, "scale_factor", None) or 2 ** (len(self.vae.config.block_out_channels) - 1)
+        return tuple(f * d for d in self._latent_hw(hw))
 
     def _guided_plan(self, guided_upsample, match_input_res, input_image):
         """``__call__``'s check of ``guided_upsample=``, before anything is launched -> None (the keyword is off) | (radius, sigma)."""
@@ -990,9 +1052,10 @@ class MarigoldDepthPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, color_map: str = "Spectral",
                  show_progress_bar: bool = True, ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldDepthOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None,
+                 align: Optional[DepthAlignState] = None) -> MarigoldDepthOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample, color_map=color_map)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample, align, color_map=color_map)
 
     _finish_args = ("color_map",)
 
@@ -1060,9 +1123,9 @@ class MarigoldNormalsPipeline(_MarigoldPipelineBase):
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None,
                  init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldNormalsOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None, align=None) -> MarigoldNormalsOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample, align)
 
     _clip_range = (-1, 1)
 
@@ -1225,9 +1288,9 @@ class MarigoldIIDPipeline(_MarigoldPipelineBase):
                  resample_method: str = "bilinear", batch_size: int = 0,
                  generator: Union[torch.Generator, None] = None, show_progress_bar: bool = True,
                  ensemble_kwargs: Dict = None, init_latents: Optional[torch.Tensor] = None,
-                 sequence: Optional[SequenceState] = None, guided_upsample=None) -> MarigoldIIDOutput:
+                 sequence: Optional[SequenceState] = None, guided_upsample=None, align=None) -> MarigoldIIDOutput:
         return self._call(input_image, denoising_steps, ensemble_size, processing_res, match_input_res, resample_method, batch_size,
-                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample)
+                          generator, ensemble_kwargs, init_latents, sequence, guided_upsample, align)
 
     def _empty_output(self) -> MarigoldIIDOutput:
         return MarigoldIIDOutput(target_names=self.target_names)
