@@ -1395,6 +1395,57 @@ int mg_depth_align_fit(const float* d, const float* ref, const unsigned char* ma
 int mg_depth_align_apply(const float* x, long long n, const double* coef, int use_shift,
                          float clip_lo, float clip_hi, float* out, void* stream);
 
+/* DEPTH TO 3D (marigold_amd/points.py): camera-space points and surface normals from a depth map on the device - the
+ * dense normals map, and the kept pixels compacted into a point cloud in row-major order without the host learning their number.
+ * Plain C calls on device pointers, no op kind.  Every argument check comes before any GPU work and every message starts with the
+ * function's name; nothing synchronises.  No atomics: two runs give the same bits, and so do the bf16- and the fp16-operand build.
+ * All arithmetic is fp64, every product, sum and quotient rounded on its own in the order written here; results are rounded once to
+ * fp32.
+ *  CAMERA.  fx, fy, cx, cy in pixels of the map's own grid.  Pixel (row y, column x) sits at image coordinates (x, y), integer
+ *    coordinates at pixel centres.  The camera frame is x right, y down, z forward.
+ *  DEPTH.  z = (double)d without coef; with coef, a DEVICE fp64 [2] (what mg_depth_align_fit leaves, or two uploaded numbers),
+ *    z = (double)d * coef[0] + coef[1], the product and the sum each rounded.
+ *  USABLE pixel: its mask byte is non-zero (or there is no mask), d and z are finite, and z_min < z <= z_max (z_min >= 0; z_max may be
+ *    +inf).
+ *  JOINED: two usable 4-neighbours p, q are joined when edge_rel == 0 or |z_p - z_q| <= edge_rel * min(z_p, z_q) - the flying-pixel
+ *    rule.
+ *  KEPT pixel: usable and joined to every usable in-bounds 4-neighbour.  Neighbours that are not usable do not count against it.
+ *  POINT: X = ((x - cx) * z) / fx, Y = ((y - cy) * z) / fy, Z = z; each rounded to fp32 for the record, the fp64 values serve the normal.
+ *  NORMAL of a kept pixel p: the horizontal tangent Tu is P_east - P_west when both neighbours are joined to p, the one-sided
+ *    difference P_east - P_p or P_p - P_west with one of them, and with none there is no normal; the vertical tangent Tv likewise,
+ *    south minus north.  N = Tv x Tu, each component a b - c d with both products rounded:
+ *    (Tv.y Tu.z - Tv.z Tu.y, Tv.z Tu.x - Tv.x Tu.z, Tv.x Tu.y - Tv.y Tu.x).  A dot product is (a.x b.x + a.y b.y) + a.z b.z.  If
+ *    N . P > 0, N is negated: the normal looks at the camera.  Then N is divided, component by component, by sqrt(N . N); there is no
+ *    normal when N . N is zero or not finite.  normals_frame MG_NORMALS_FRAME_CAMERA gives N in the camera frame (a wall facing the
+ *    camera: (0, 0, -1)); MG_NORMALS_FRAME_MARIGOLD gives (Nx, -Ny, -Nz): x right, y up, z toward the viewer (that wall: (0, 0, 1)) -
+ *    how this model family's normal maps are published and what mg_eval_normals takes.
+ *  mg_depth_normals: d fp32 [h][w], mask uint8 [h][w] or NULL, coef or NULL -> out fp32 [3][h][w] and valid uint8 [h][w].  A pixel
+ *    that is not kept or has no normal gets zeros and a zero byte.  One launch.
+ *  mg_depth_points_workspace_bytes: what mg_depth_points needs for n = h w pixels, 1 <= n <= 2^30 (-1 with mg_last_error otherwise).
+ *  mg_depth_points: colors uint8 [h][w][3] with hwc != 0, planes [3][h][w] with hwc = 0, or NULL.  Outputs: xyz fp32 [capacity][3];
+ *    rgb uint8 [capacity][3], given exactly when colors is; nrm fp32 [capacity][3] or NULL; index int32 [capacity] or NULL, the source
+ *    pixel's row-major index; count DEVICE int64 [2]: the kept pixels, and the records written = min(kept, capacity).  The records are
+ *    in row-major pixel order; nothing at or past record `written` is touched; a kept pixel without a normal is still a record, with
+ *    the normal (0, 0, 0).  Three launches, none of which waits on another workgroup: the kept pixels of every chunk of 2048 are
+ *    counted; one workgroup adds the counts in chunk order into the chunks' offsets and `count`; the scatter decides again what is
+ *    kept and ranks a pixel within its chunk with 64-lane ballots and population counts.  ws, 16-byte aligned, holds the chunks' counts
+ *    and offsets and nothing else; it is the call's until the stream has passed it.
+ * Refused by both calls: a null d, out, valid, xyz, count or ws; colors without rgb or rgb without colors; h or w below 1 or more than
+ * 2^30 pixels; fx or fy not finite or <= 0; cx or cy not finite; z_min negative or not finite; z_max NaN or <= z_min; edge_rel
+ * negative or not finite; an unknown normals_frame; capacity < 1; fp32, int32, int64 or fp64 pointers not aligned to their elements;
+ * ws_bytes too small or ws not 16-byte aligned.
+ * Points are no stage of the one-call predictions: a host composes them (examples/host_points.cpp). */
+enum { MG_NORMALS_FRAME_CAMERA = 0, MG_NORMALS_FRAME_MARIGOLD = 1 };
+int mg_depth_normals(const float* d, const unsigned char* mask_or_null, const double* coef_or_null, int h, int w,
+                     double fx, double fy, double cx, double cy, double z_min, double z_max, double edge_rel, int normals_frame,
+                     float* out, unsigned char* valid, void* stream);
+long long mg_depth_points_workspace_bytes(long long n);
+int mg_depth_points(const float* d, const unsigned char* colors_or_null, int hwc, const unsigned char* mask_or_null,
+                    const double* coef_or_null, int h, int w, double fx, double fy, double cx, double cy,
+                    double z_min, double z_max, double edge_rel, int normals_frame, long long capacity,
+                    float* xyz, unsigned char* rgb_or_null, float* nrm_or_null, int* index_or_null, long long* count,
+                    void* ws, long long ws_bytes, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

@@ -5,6 +5,8 @@ from .pipeline import (IIDEntry, MarigoldDepthOutput, MarigoldDepthPipeline,  # 
 from .noise import NativeNoise, native_randn  # noqa: F401
 from .guided import guided_upsample  # noqa: F401
 from .align import DepthAlignState, align_depth  # noqa: F401
+from .points import (Intrinsics, PointCloud, depth_to_normals, depth_to_points, intrinsics_from_fov,  # noqa: F401
+                     read_ply, scale_intrinsics, write_ply)
 
 MarigoldPipeline = MarigoldDepthPipeline  # for backward compatibility
 

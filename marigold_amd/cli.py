@@ -5,6 +5,7 @@ the same minus ``--color_map``):
   depth   : <out>/depth_npy/<name>_depth.npy      float32 [H,W] in [0,1]
             <out>/depth_bw/<name>_depth.png        16-bit PNG, value * 65535
             <out>/depth_colored/<name>_depth_colored.png
+            <out>/depth_points/<name>_points.ply   with --save_points (an extension): the map as a coloured point cloud, binary PLY
   normals : <out>/normals_npy/<name>_normals.npy  float32 [3,H,W] in [-1,1]
             <out>/normals_vis/<name>_normals.png   (n + 1) * 127.5
   iid     : <out>/iid_{appearance|lighting}_npy/<name>_<target>.npy  float32 [H,W,3] in [0,1]
@@ -17,6 +18,7 @@ fp16-operand build of the engine (fp32 accumulation), like the reference; withou
 """
 import argparse
 import logging
+import math
 import os
 from glob import glob
 
@@ -76,6 +78,24 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
         p.add_argument("--align_iters", type=int, default=4, help="--sequence_align: reweighted solves per frame, 0 (plain least squares) to 32.")
         p.add_argument("--align_reference", choices=["previous", "first"], default="previous",
                        help="--sequence_align: what a frame is fitted to.")
+    if kind == "depth":   # (depth to 3D, marigold_amd/points.py; the other kinds predict no depth: there the flags are unknown arguments)
+        p.add_argument("--save_points", action="store_true",
+                       help="Also write <output_dir>/depth_points/<name>_points.ply: the depth map as a point cloud in the camera's frame "
+                            "(x right, y down, z forward) with the picture's colours, a binary PLY that 3D viewers open. Needs --fov_deg or "
+                            "--focal_px.")
+        p.add_argument("--fov_deg", type=float, default=None,
+                       help="--save_points: the horizontal field of view of the input picture in degrees (square pixels, the principal "
+                            "point at the centre).")
+        p.add_argument("--focal_px", type=float, default=None,
+                       help="--save_points: the focal length in pixels of the input picture, in place of --fov_deg.")
+        p.add_argument("--points_near", type=float, default=1.0,
+                       help="--save_points: the distance given to depth 0. The model's depth is affine-invariant, so near and far are the "
+                            "user's choice; the defaults 1 and 10 are arbitrary.")
+        p.add_argument("--points_far", type=float, default=10.0, help="--save_points: the distance given to depth 1 (z = near + d * (far - near)).")
+        p.add_argument("--points_edge_rel", type=float, default=0.05,
+                       help="--save_points: drop a pixel when a neighbour's distance differs by more than this fraction of the nearer one "
+                            "(the flying pixels of a depth edge); 0 keeps them.")
+        p.add_argument("--points_normals", action="store_true", help="--save_points: add the surface normal of every point to the records.")
     p.add_argument("--guided_upsample", action="store_true",
                    help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
                         "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
@@ -138,6 +158,54 @@ def sequence_align_arg(parser, args):
     except ValueError as e:
         parser.error(str(e))
     return dict(iters=args.align_iters, delta=args.align_delta, reference=args.align_reference)
+
+
+def save_points_arg(parser, args):
+    """The point-cloud flags against the rest of the command line, before anything is loaded -> None without ``--save_points``, else the
+    settings ``save_points`` takes.  What does not fit is an argparse error; the combination with ``--tile_size`` is refused like the
+    other combinations with it."""
+    if not getattr(args, "save_points", False):
+        return None
+    if getattr(args, "tile_size", 0):
+        raise ValueError("--save_points cannot be combined with --tile_size")
+    if (args.fov_deg is None) == (args.focal_px is None):
+        parser.error("--save_points needs the camera: exactly one of --fov_deg and --focal_px")
+    if args.fov_deg is not None and not 0.0 < args.fov_deg < 180.0:
+        parser.error(f"--fov_deg must lie inside (0, 180) (got {args.fov_deg})")
+    if args.focal_px is not None and not (math.isfinite(args.focal_px) and args.focal_px > 0.0):
+        parser.error(f"--focal_px must be finite and > 0 (got {args.focal_px})")
+    if not (math.isfinite(args.points_near) and math.isfinite(args.points_far) and 0.0 <= args.points_near < args.points_far):
+        parser.error(f"--points_near / --points_far must be finite with 0 <= near < far (got {args.points_near}, {args.points_far})")
+    if not (math.isfinite(args.points_edge_rel) and args.points_edge_rel >= 0.0):
+        parser.error(f"--points_edge_rel must be finite and >= 0 (got {args.points_edge_rel})")
+    return dict(fov_deg=args.fov_deg, focal_px=args.focal_px, near=args.points_near, far=args.points_far, edge_rel=args.points_edge_rel,
+                normals=args.points_normals)
+
+
+def save_points(folder, rgb_path, out, cfg, device):
+    """``--save_points``: one picture's depth map as ``<folder>/<name>_points.ply`` -> the path.  The camera is given for the input
+    picture and rescaled to the map's size where that differs (--output_processing_res); the colours are the picture's own, resampled to
+    the map's size; z = near + depth * (far - near) goes in as ``coef``.  One read-back: the cloud's."""
+    import torch
+    from . import points as P
+    from .util.image_util import InterpolationMode, resize
+    depth = torch.from_numpy(np.ascontiguousarray(out.depth_np, dtype=np.float32)).to(device)
+    h, w = depth.shape
+    picture = torch.from_numpy(np.array(Image.open(rgb_path).convert("RGB"))).to(device)
+    H, W = picture.shape[:2]
+    if cfg["focal_px"] is not None:
+        K = P.Intrinsics(cfg["focal_px"], cfg["focal_px"], (W - 1) / 2.0, (H - 1) / 2.0)
+    else:
+        K = P.intrinsics_from_fov(H, W, cfg["fov_deg"])
+    planes = picture.permute(2, 0, 1)[None]
+    if (H, W) != (h, w):
+        K = P.scale_intrinsics(K, (H, W), (h, w))
+        planes = resize(planes, (h, w), InterpolationMode.BILINEAR, antialias=True)
+    cloud = P.depth_to_points(depth, K, colors=planes[0].contiguous(), coef=(cfg["far"] - cfg["near"], cfg["near"]), edge_rel=cfg["edge_rel"],
+                              normals=cfg["normals"], frame="camera")
+    path = os.path.join(folder, os.path.splitext(os.path.basename(rgb_path))[0] + "_points.ply")
+    _save(path, cloud.write_ply)
+    return path
 
 
 def list_images(folder):
@@ -220,6 +288,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     check_tile_args(args)
     guided = guided_upsample_arg(args)
     align = sequence_align_arg(parser, args)
+    points = save_points_arg(parser, args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -235,6 +304,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         logging.error(f"No image found in '{args.input_rgb_dir}'")
         return 1
     logging.info(f"Found {len(files)} images")
+    if points is not None:
+        points_dir = os.path.join(args.output_dir, "depth_points")
+        os.makedirs(points_dir, exist_ok=True)
     if pipeline is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
@@ -274,6 +346,11 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         g.manual_seed(args.seed)
         return g
 
+    def save(rgb_path, out):
+        save_prediction(kind, dirs, rgb_path, out)
+        if points is not None:
+            save_points(points_dir, rgb_path, out, points, device)
+
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
     if args.sequence:
@@ -288,7 +365,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         outs = pipeline.map_video((Image.open(f) for f in files), strength=args.carry_strength, in_flight=args.maps_in_flight or None,
                                   generators=seeds, **video_kw)
         for rgb_path, out in zip(files, outs):
-            save_prediction(kind, dirs, rgb_path, out)
+            save(rgb_path, out)
     elif getattr(args, "tile_size", 0):
         # large pictures: each from overlapping tiles, stitched on the device; --processing_res is the guide's resolution
         if not hasattr(pipeline, "predict_tiled"):
@@ -302,7 +379,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
                                          generator=None if args.seed is None else NativeNoise(args.seed), **tile_kw)
             if getattr(out, "degenerate_tiles", None):
                 logging.warning(f"{rgb_path}: {out.degenerate_tiles} tile(s) could not be fitted to the guide and carry its mean")
-            save_prediction(kind, dirs, rgb_path, out)
+            save(rgb_path, out)
     elif hasattr(pipeline, "map_images"):
         # the engine's multi-image form: up to --maps_in_flight images on the GPU at a time, outputs in input order
         if args.images_per_program > 1:
@@ -310,9 +387,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         outs = pipeline.map_images((Image.open(f) for f in files), in_flight=args.maps_in_flight or None,
                                    generators=(generator_of(f) for f in files), **kw)
         for rgb_path, out in zip(files, outs):
-            save_prediction(kind, dirs, rgb_path, out)
+            save(rgb_path, out)
     else:   # an object with the reference pipeline's call surface only
         for rgb_path in files:
             out = pipeline(Image.open(rgb_path), generator=generator_of(rgb_path), **kw)
-            save_prediction(kind, dirs, rgb_path, out)
+            save(rgb_path, out)
     return 0
