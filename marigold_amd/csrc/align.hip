@@ -1,13 +1,14 @@
 // Depth alignment: the robust scale and shift that carry one depth map into the range of another - a reference with
 // trusted values, or the frame before - and their application.  The contract of every entry point is in include/marigold_hip.h.
 // A fit is 1 + iters (+ 1 under MG_ALIGN_START_LS) pairs of launches: the partial sums of fixed chunks of pixels, then one wave that
-// adds the partials in a fixed order and solves.  The coefficients stay on the device: the solve writes them to `coef`, the next
-// partial launch reads its weights' coefficients from there.  Bound by memory where it is bound by anything: 8 n bytes per solve,
+// adds the partials and solves; the order of every sum is reduce.h's.  The coefficients stay on the device: the solve writes them to
+// `coef`, the next partial launch reads its weights' coefficients from there.  Bound by memory where it is bound by anything: 8 n bytes per solve,
 // tens of microseconds at 768 x 768 - the launches themselves cost as much.  fp64 throughout, as in the tile fit (tiles.hip), the price
 // of a result that can be checked to 1e-9.  Built with -ffp-contract=off: every product and sum below is rounded on its own.
 #include <cmath>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -18,11 +19,6 @@ constexpr int ALIGN_SUMS = 6;                                // count, N, Sd, Sg
 constexpr long long ALIGN_MAX_N = 1ll << 30;
 
 enum { WEIGHTS_ONE = 0, WEIGHTS_FROM_ARGS = 1, WEIGHTS_FROM_COEF = 2 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // grid (chunks): block c sums pixels [c ALIGN_CHUNK, (c + 1) ALIGN_CHUNK) -> part[c * 6 + {count, N, Sd, Sg, Sdd, Sdg}].  Element loads
 // (consecutive lanes, consecutive pixels): no alignment beyond the element's is asked of d and ref, and the lane that takes a pixel - hence
@@ -65,32 +61,15 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_partial_kernel(const floa
       acc[5] += wd * g;
     }
   }
-  __shared__ double lds[ALIGN_THREADS / 64][ALIGN_SUMS];
-  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-#pragma unroll
-  for (int k = 0; k < ALIGN_SUMS; ++k) {
-    const double v = wave_sum_d(acc[k]);
-    if (lane == 0) lds[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ALIGN_SUMS) {
-    double v = lds[0][threadIdx.x];
-    for (int w = 1; w < ALIGN_THREADS / 64; ++w) v += lds[w][threadIdx.x];
-    part[(long long)blockIdx.x * ALIGN_SUMS + threadIdx.x] = v;
-  }
+  block_sum_store<ALIGN_SUMS, ALIGN_THREADS>(acc, part + (long long)blockIdx.x * ALIGN_SUMS);
 }
 
-// one wave: lane l adds the partials of chunks l, l + 64, ... in that order, the lanes' sums meet in the shuffle tree - a fixed order,
-// the same bits on every run - then lane 0 solves.  `first`: the fit's first solve, which sets the flag; a later one leaves a fit that
-// is already degenerate alone.
+// one wave: the partials of the chunks, lane-strided (reduce.h), then lane 0 solves.  `first`: the fit's first solve, which sets the
+// flag; a later one leaves a fit that is already degenerate alone.
 __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restrict__ part, long long chunks, int fit_shift, int first,
                                                          double* __restrict__ coef, int* __restrict__ flag) {
-  double a[ALIGN_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (long long c = threadIdx.x; c < chunks; c += 64)
-#pragma unroll
-    for (int k = 0; k < ALIGN_SUMS; ++k) a[k] += part[c * ALIGN_SUMS + k];
-#pragma unroll
-  for (int k = 0; k < ALIGN_SUMS; ++k) a[k] = wave_sum_d(a[k]);
+  double a[ALIGN_SUMS];
+  lane_rows_sum<ALIGN_SUMS>(part, chunks, a);
   if (threadIdx.x != 0) return;
   if (!first && flag[0] != 0) return;
   const double count = a[0], N = a[1], Sd = a[2], Sg = a[3], Sdd = a[4], Sdg = a[5];
@@ -98,10 +77,10 @@ __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restric
   int bad = 1;
   if (count >= 2.0) {
     if (fit_shift) {
-      const double det = N * Sdd - Sd * Sd;
-      if (det > 1e-12 * N * N) {
-        s = (N * Sdg - Sd * Sg) / det;
-        t = (Sg - s * Sd) / N;
+      const scale_shift f = scale_shift_solve(N, Sd, Sg, Sdd, Sdg);
+      if (f.det > 1e-12 * N * N) {
+        s = f.s;
+        t = f.t;
         bad = 0;
       }
     } else if (Sdd > 1e-12 * N) {

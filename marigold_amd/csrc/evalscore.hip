@@ -5,8 +5,8 @@
 //
 // Element arithmetic is fp32 with IEEE division, sqrt and the library's accurate logf / log10f / acosf (this file is built with
 // -ffp-contract=off and no fast-math, so an expression rounds like the numpy / torch element ops it restates); every sum is fp64.
-// Reductions: thread -> wave (xor butterfly) -> block (LDS, fixed order) -> one row of a per-block partial table; a one-block
-// launch then adds the rows in block order.  No floating-point atomics: two launches on the same input give the same bits.
+// Reductions: thread -> wave -> block -> one row of a per-block partial table; a one-block launch then adds the rows.  The order of
+// every step is reduce.h's.  No floating-point atomics: two launches on the same input give the same bits.
 // The median of the angles is exact: they are non-negative, so their bit patterns order as unsigned integers, and three histogram
 // passes over 11 / 11 / 10 bits (integer atomics in LDS, merged into a global histogram) select the two middle order statistics.
 // The same selection finds the brightness quantile of the intrinsic-image scores (compute_iid_metric, src/util/metric.py:263-338;
@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "iid_images.h"   // EV_BLOCKS, EV_THREADS, IidMap, iid_gamma, IidImages and the head of the IID workspace layout
+#include "reduce.h"
 
 namespace {
 
@@ -46,32 +47,10 @@ struct SelState {
 };
 static_assert(sizeof(SelState) <= 64, "SelState");
 
-// v[k] summed over the block -> dst[k] (the block's row of a partial table); every thread of the block calls it
-template <int N>
-__device__ __forceinline__ void block_sum_store(const double (&v)[N], double* __restrict__ dst) {
-  __shared__ double red[EV_THREADS / 64][N];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double x = v[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);   // (a + b on both sides of a pair: the same bits in every lane)
-    if (lane == 0) red[wave][k] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    const int k = threadIdx.x;
-    dst[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
-}
-
 // rows [0, nblk) of a partial table added in row order -> out[N]; one block
 __global__ __launch_bounds__(64) void sum_rows_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk, int N) {
   const int k = threadIdx.x;
-  if (k >= N) return;
-  double s = 0.0;
-  for (int b = 0; b < nblk; ++b) s += part[(size_t)b * N + k];
-  out[k] = s;
+  if (k < N) out[k] = column_sum(part + k, nblk, N);
 }
 
 // ---- depth ----------------------------------------------------------------------------------------------------------
@@ -107,18 +86,15 @@ __global__ __launch_bounds__(EV_THREADS) void depth_ls_kernel(const float* __res
     acc[3] += x * x;
     acc[4] += x * yd;
   }
-  block_sum_store<LS_N>(acc, part + (size_t)blockIdx.x * LS_N);
+  block_sum_store<LS_N, EV_THREADS>(acc, part + (size_t)blockIdx.x * LS_N);
 }
 
 // scale, shift of the 2 x 2 normal equations (evaluation/alignment.py), cast to fp32 like the fit of fp32 arrays
 __device__ __forceinline__ void ls_solve(const double* __restrict__ sums, float& s, float& t) {
   if (!sums) { s = 1.f; t = 0.f; return; }
-  const double n = sums[0], sx = sums[1], sy = sums[2], sxx = sums[3], sxy = sums[4];
-  const double det = n * sxx - sx * sx;
-  const double scale = (n * sxy - sx * sy) / det;
-  const double shift = (sy - scale * sx) / n;
-  s = (float)scale;
-  t = (float)shift;
+  const scale_shift f = scale_shift_solve(sums[0], sums[1], sums[2], sums[3], sums[4]);   // unguarded, like the host's
+  s = (float)f.s;
+  t = (float)f.t;
 }
 
 // sums: 0 |a-g|/g  1 (a-g)^2/g  2 (a-g)^2  3 (ln a - ln g)^2  4 ln a - ln g  5 |log10 a - log10 g|  6..8 max(a/g, g/a) < 1.25^k
@@ -163,18 +139,13 @@ __global__ __launch_bounds__(EV_THREADS) void depth_metrics_kernel(const float* 
     acc[9] += (double)(id * id);
     acc[10] += 1.0;
   }
-  block_sum_store<DM_N>(acc, part + (size_t)blockIdx.x * DM_N);
+  block_sum_store<DM_N, EV_THREADS>(acc, part + (size_t)blockIdx.x * DM_N);
 }
 
 __global__ __launch_bounds__(64) void depth_metrics_final_kernel(const double* __restrict__ part, const double* __restrict__ sums,
                                                                  double* __restrict__ out, int nblk) {
   __shared__ double S[DM_N];
-  if (threadIdx.x < DM_N) {
-    double v = 0.0;
-    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * DM_N + threadIdx.x];
-    S[threadIdx.x] = v;
-  }
-  __syncthreads();
+  rows_sum<DM_N>(part, nblk, DM_N, 1, S);
   if (threadIdx.x != 0) return;
   const double n = S[10];
   float s, t;
@@ -251,7 +222,7 @@ __global__ __launch_bounds__(EV_THREADS) void normals_stats_kernel(const float* 
   __syncthreads();
   for (int b = threadIdx.x; b < 2048; b += EV_THREADS)
     if (hist[b]) atomicAdd(&ghist[b], hist[b]);
-  block_sum_store<NM_N>(acc, part + (size_t)blockIdx.x * NM_N);
+  block_sum_store<NM_N, EV_THREADS>(acc, part + (size_t)blockIdx.x * NM_N);
 }
 
 // the bin that holds rank st->rem[r] of a histogram, for both ranks (lane 0 of waves 0 and 1); the bin joins the prefix
@@ -274,12 +245,7 @@ __device__ __forceinline__ void select_bin(SelState* __restrict__ st, const unsi
 __global__ __launch_bounds__(128) void normals_reduce_kernel(const double* __restrict__ part, double* __restrict__ out,
                                                              SelState* __restrict__ st, const unsigned* __restrict__ hist0, int nblk) {
   __shared__ double S[NM_N];
-  if (threadIdx.x < NM_N) {
-    double v = 0.0;
-    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * NM_N + threadIdx.x];
-    S[threadIdx.x] = v;
-  }
-  __syncthreads();
+  rows_sum<NM_N>(part, nblk, NM_N, 1, S);
   if (threadIdx.x == 0) {
     const double n = S[7];
     out[0] = S[0] / n;
@@ -414,7 +380,7 @@ __global__ __launch_bounds__(EV_THREADS) void iid_prep_kernel(IidImages im, IidB
   __syncthreads();
   for (int b = threadIdx.x; b < 2048; b += EV_THREADS)
     if (hist[b]) atomicAdd(&ghist[b], hist[b]);
-  block_sum_store<II_N>(acc, part + (size_t)blockIdx.x * II_N);
+  block_sum_store<II_N, EV_THREADS>(acc, part + (size_t)blockIdx.x * II_N);
 }
 
 // one block: the alignment scale; the ranks of the two order statistics around 0.9 (n - 1); the first selection step.
@@ -423,12 +389,7 @@ __global__ __launch_bounds__(128) void iid_prep_reduce_kernel(const double* __re
                                                               SelState* __restrict__ st, IidMap* __restrict__ map,
                                                               const unsigned* __restrict__ hist0, int nblk) {
   __shared__ double S[II_N];
-  if (threadIdx.x < II_N) {
-    double v = 0.0;
-    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * II_N + threadIdx.x];
-    S[threadIdx.x] = v;
-  }
-  __syncthreads();
+  rows_sum<II_N>(part, nblk, II_N, 1, S);
   if (threadIdx.x == 0) {
     const double s = S[0] / S[1];
     out[2] = s;
@@ -488,18 +449,13 @@ __global__ __launch_bounds__(EV_THREADS) void iid_psnr_kernel(IidImages im, doub
     acc[0] += d * d;
     acc[1] += 1.0;
   }
-  block_sum_store<2>(acc, part + (size_t)blockIdx.x * 2);
+  block_sum_store<2, EV_THREADS>(acc, part + (size_t)blockIdx.x * 2);
 }
 
 __global__ __launch_bounds__(64) void iid_psnr_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk,
                                                             int mapped, int want_psnr) {
   __shared__ double S[2];
-  if (threadIdx.x < 2) {
-    double v = 0.0;
-    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * 2 + threadIdx.x];
-    S[threadIdx.x] = v;
-  }
-  __syncthreads();
+  rows_sum<2>(part, nblk, 2, 1, S);
   if (threadIdx.x != 0) return;
   const double n = S[1];
   if (want_psnr) out[0] = 10.0 * log10(1.0 / (S[0] / n));   // identical images: 1 / 0 = +inf, like the host; n = 0: NaN
@@ -586,18 +542,13 @@ __global__ __launch_bounds__(EV_THREADS) void iid_ssim_kernel(IidImages im, Ssim
     }
     __syncthreads();   // the next tile overwrites the patches and the intermediate
   }
-  block_sum_store<2>(acc, part + (size_t)blockIdx.x * 2);
+  block_sum_store<2, EV_THREADS>(acc, part + (size_t)blockIdx.x * 2);
 }
 
 __global__ __launch_bounds__(64) void iid_ssim_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk,
                                                             double count) {
   __shared__ double S[2];
-  if (threadIdx.x < 2) {
-    double v = 0.0;
-    for (int b = 0; b < nblk; ++b) v += part[(size_t)b * 2 + threadIdx.x];
-    S[threadIdx.x] = v;
-  }
-  __syncthreads();
+  rows_sum<2>(part, nblk, 2, 1, S);
   if (threadIdx.x == 0) out[1] = S[1] > 0.0 ? S[0] / count : (double)__builtin_nanf("");
 }
 

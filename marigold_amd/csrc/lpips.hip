@@ -15,12 +15,13 @@
 //                      convolution's staging cannot give (its windows overlap, and the last rows / columns of some sizes lie in no window);
 //                      an integer atomic.
 //  lpips_dist_kernel   per position, one wave: both channel norms, then the weighted squared difference of the unit vectors, in fp32;
-//                      the spatial sum in fp64, thread -> wave -> block -> a partial table that lpips_final_kernel adds in row order.
+//                      the spatial sum in fp64, wave -> block -> a partial table that lpips_final_kernel adds; the order is reduce.h's.
 #include <math.h>
 #include <string.h>
 
 #include "common.h"
 #include "iid_images.h"
+#include "reduce.h"
 
 namespace {
 
@@ -198,8 +199,7 @@ __global__ __launch_bounds__(EV_THREADS) void lpips_range_kernel(IidImages im, u
     bad += !(p >= 0.f && p <= 1.f);
     bad += !(g >= 0.f && g <= 1.f);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  bad = wave_sum_xor(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, (unsigned long long)bad);
 }
 
@@ -207,9 +207,8 @@ __global__ __launch_bounds__(EV_THREADS) void lpips_range_kernel(IidImages im, u
 // of sum_c lin_c * (fp_c / |fp| - fg_c / |fg|)^2.  A wave owns a position at a time (positions wave, wave + waves, ...: one order).
 __global__ __launch_bounds__(LP_THREADS) void lpips_dist_kernel(const float* __restrict__ f, const float* __restrict__ lin,
                                                                 double* __restrict__ part, int P, int C) {
-  __shared__ double red[LP_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   for (long long p = (long long)blockIdx.x * (LP_THREADS / 64) + wave; p < P; p += (long long)gridDim.x * (LP_THREADS / 64)) {
     const float* __restrict__ fp = f + (size_t)p * C;
     const float* __restrict__ fg = f + ((size_t)P + p) * C;
@@ -219,24 +218,17 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_dist_kernel(const float* __r
       sp += a * a;
       sg += b * b;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {   // (a + b on both sides of a pair: the same bits in every lane)
-      sp += __shfl_xor(sp, o);
-      sg += __shfl_xor(sg, o);
-    }
+    sp = wave_sum_xor(sp);
+    sg = wave_sum_xor(sg);
     const float np = lpips_norm(sp), ng = lpips_norm(sg);
     float d = 0.f;
     for (int c = lane; c < C; c += 64) {
       const float t = fp[c] / np - fg[c] / ng;
       d += lin[c] * (t * t);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
-    acc += (double)d;
+    acc[0] += (double)wave_sum_xor(d);
   }
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  waves_sum_store<1, LP_THREADS>(acc, part + blockIdx.x);   // (acc is wave-uniform already: the waves' half of the block sum alone)
 }
 
 struct LpipsTail {
@@ -248,14 +240,9 @@ struct LpipsTail {
 __global__ __launch_bounds__(64) void lpips_final_kernel(const double* __restrict__ part, const unsigned long long* __restrict__ count,
                                                          double* __restrict__ out, LpipsTail t) {
   __shared__ double T[LP_TAPS];
-  if (threadIdx.x < LP_TAPS) {
-    const int k = threadIdx.x;
-    double s = 0.0;
-    for (int b = 0; b < t.nblk[k]; ++b) s += part[(size_t)k * EV_BLOCKS + b];
-    T[k] = s / (double)t.P[k];
-  }
-  __syncthreads();
+  rows_sum<LP_TAPS>(part, threadIdx.x < LP_TAPS ? t.nblk[threadIdx.x] : 0, 1, EV_BLOCKS, T);   // [tap][EV_BLOCKS]: a tap is a column
   if (threadIdx.x != 0) return;
+  for (int k = 0; k < LP_TAPS; ++k) T[k] = T[k] / (double)t.P[k];
   out[0] = (((T[0] + T[1]) + T[2]) + T[3]) + T[4];
   out[1] = (double)*count;
   for (int k = 0; k < LP_TAPS; ++k) out[2 + k] = T[k];

@@ -4,8 +4,9 @@
 // lane.  The fit reads every tile once too, but its first launch is slower than that read: the fp64 sampling of the guide (small,
 // cache-resident) is the likely bound - measured at 1.5 TB/s of tile bytes (docs/history/tiled.md).  That launch is a
 // twenty-thousandth of a tiled prediction, and fp64 is the price of a result that can be checked to 1e-9.
-// The file is built with -ffp-contract=off and the blend spells its roundings out.
+// The file is built with -ffp-contract=off and the blend spells its roundings out; the order of the fit's sums is reduce.h's.
 #include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -28,11 +29,6 @@ __device__ __forceinline__ void bilinear_src(int dst, double scale, int in, int&
   i1 = i0 < in - 1 ? i0 + 1 : i0;
   l1 = src - (double)i0;
   l1 = l1 < 0.0 ? 0.0 : (l1 > 1.0 ? 1.0 : l1);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 // grid (chunks, n): block (c, i) sums chunk c of tile i -> part[(i * chunks + c) * 5 + {N, Sd, Sg, Sdd, Sdg}]
@@ -81,44 +77,24 @@ __global__ __launch_bounds__(FIT_THREADS) void tile_fit_partial_kernel(const flo
       }
     }
   }
-  __shared__ double lds[FIT_THREADS / 64][5];
-  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const double s = wave_sum_d(acc[k]);
-    if (lane == 0) lds[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    double s = lds[0][threadIdx.x];
-    for (int w = 1; w < FIT_THREADS / 64; ++w) s += lds[w][threadIdx.x];
-    part[((long long)tile * chunks + chunk) * 5 + threadIdx.x] = s;
-  }
+  block_sum_store<5, FIT_THREADS>(acc, part + ((long long)tile * chunks + chunk) * 5);
 }
 
-// one wave per tile: lane l adds the partials of chunks l, l + 64, ... in that order, the lanes' sums meet in the shuffle tree - a fixed
-// order, the same bits on every run - then lane 0 solves
+// one wave per tile: the partials of its chunks, lane-strided (reduce.h), then lane 0 solves
 __global__ __launch_bounds__(64) void tile_fit_solve_kernel(const double* __restrict__ part, int chunks, double* __restrict__ coef,
                                                             int* __restrict__ flags) {
   const int tile = blockIdx.x;
-  double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int c = threadIdx.x; c < chunks; c += 64)
-#pragma unroll
-    for (int k = 0; k < 5; ++k) a[k] += part[((long long)tile * chunks + c) * 5 + k];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) a[k] = wave_sum_d(a[k]);
+  double a[5];
+  lane_rows_sum<5>(part + (long long)tile * chunks * 5, chunks, a);
   if (threadIdx.x != 0) return;
   const double N = a[0], Sd = a[1], Sg = a[2], Sdd = a[3], Sdg = a[4];
   double s = 0.0, t = N > 0.0 ? Sg / N : 0.0;
   int flag = 1;
-  const double det = N * Sdd - Sd * Sd;
-  if (N >= 2.0 && det > 1e-12 * N * N) {
-    const double slope = (N * Sdg - Sd * Sg) / det;
-    if (slope > 0.0) {
-      s = slope;
-      t = (Sg - slope * Sd) / N;
-      flag = 0;
-    }
+  const scale_shift f = scale_shift_solve(N, Sd, Sg, Sdd, Sdg);
+  if (N >= 2.0 && f.det > 1e-12 * N * N && f.s > 0.0) {
+    s = f.s;
+    t = f.t;
+    flag = 0;
   }
   coef[2 * tile] = s;
   coef[2 * tile + 1] = t;
