@@ -1446,6 +1446,46 @@ int mg_depth_points(const float* d, const unsigned char* colors_or_null, int hwc
                     float* xyz, unsigned char* rgb_or_null, float* nrm_or_null, int* index_or_null, long long* count,
                     void* ws, long long ws_bytes, void* stream);
 
+/* DEPTH TO MESH (marigold_amd/mesh.py): the depth map as a triangle mesh on the device - vertices, and triangles that
+ * stop at depth edges, both compacted without the host learning a count.  CAMERA, DEPTH, USABLE, POINT and the arithmetic are those of
+ * DEPTH TO 3D above, unchanged; JOINED(p, q), edge_rel == 0 or |z_p - z_q| <= edge_rel * min(z_p, z_q), is asked here of any two usable
+ * pixels, diagonal neighbours included.  A plain C call on device pointers, no op kind; every check before any GPU work; nothing
+ * synchronises; no atomics: every output byte is a function of the inputs alone, and the same in both operand builds.
+ *  CELL (x, y), 0 <= x < w - 1, 0 <= y < h - 1, has the corners A = (x, y), B = (x + 1, y), C = (x, y + 1), D = (x + 1, y + 1).
+ *  CANDIDATE triangles of a cell.  Four usable corners: the cell is split along A-D when |z_A - z_D| <= |z_B - z_C| (fp64, each
+ *    difference rounded on its own), else along B-C.  Split A-D: T0 = (A, C, D), T1 = (A, D, B).  Split B-C: T0 = (A, C, B),
+ *    T1 = (B, C, D).  Exactly three usable corners: one candidate, in slot T0 - D missing: (A, C, B); A missing: (B, C, D); B missing:
+ *    (A, C, D); C missing: (A, D, B).  Fewer than three: none.  In every order above (P1 - P0) x (P2 - P0) points toward the camera,
+ *    the orientation of N = Tv x Tu.
+ *  FACE: a candidate all three of whose edges are joined.  With four usable corners the split is chosen first; then each of its two
+ *    triangles stands or falls on its own.  Faces are ordered by cell in row-major order, inside a cell T0 before T1.
+ *  VERTEX: a usable pixel that is a corner of at least one face.  Vertices are in row-major pixel order; the three int32 entries of a
+ *    face are its corners' ranks in that order.
+ *  Vertex record: xyz fp32, the POINT, one rounding; rgb, given exactly when colors is: the picture's bytes; index or NULL: the
+ *    row-major pixel index; nrm or NULL: the NORMAL rule above - central, one-sided or no tangent per axis, turned toward the camera,
+ *    either frame - where a 4-neighbour counts for a tangent when it is usable and joined to this pixel.  The demotion of a KEPT pixel
+ *    (a usable neighbour that is not joined) does not apply to a vertex.  A vertex without a normal gets zeros.
+ *  count DEVICE int64 [4]: V, V_written = min(V, capacity_v), F, F_written = min(F, capacity_f) when V <= capacity_v, else 0 - a mesh
+ *    whose vertices were cut has no faces that could be trusted.  Nothing at or past the written records is touched.  A map with
+ *    h == 1 or w == 1 has no cells: the call succeeds with four zeros.
+ *  mg_depth_mesh_workspace_bytes: what mg_depth_mesh needs for n = h w pixels, 1 <= n <= 2^30 (-1 with mg_last_error otherwise): the
+ *    face and vertex counts and offsets of the chunks of 2048 pixels, an int32 [n] map of the vertices' ranks and a byte per cell.
+ *  mg_depth_mesh: the arguments of mg_depth_points with capacity_v, capacity_f, faces int32 [capacity_f][3] and count [4].  Five
+ *    launches, none of which waits on another workgroup: every cell's code (its split or three-corner form, which of T0 / T1 are
+ *    faces) and the chunks' face counts; the chunks' vertex counts from the codes of the up to four cells around a pixel; one workgroup
+ *    adds both tables in chunk order into offsets and writes count; the vertex scatter, which also writes the rank map; the face
+ *    scatter, which reads it.  Ranks inside a chunk come from 64-lane ballots and population counts.
+ * Refused, the message starting with "mg_depth_mesh:": everything mg_depth_points refuses about d, colors and rgb, the map, the camera,
+ * the range, edge_rel and the frame; a null xyz, faces, count or ws; capacity_v or capacity_f below 1; xyz, nrm, index, faces, count or
+ * coef not aligned to their elements; ws not 16-byte aligned or ws_bytes too small.  examples/host_mesh.cpp composes a prediction, the
+ * colours and this call into a PLY. */
+long long mg_depth_mesh_workspace_bytes(long long n);
+int mg_depth_mesh(const float* d, const unsigned char* colors_or_null, int hwc, const unsigned char* mask_or_null,
+                  const double* coef_or_null, int h, int w, double fx, double fy, double cx, double cy,
+                  double z_min, double z_max, double edge_rel, int normals_frame, long long capacity_v, long long capacity_f,
+                  float* xyz, unsigned char* rgb_or_null, float* nrm_or_null, int* index_or_null, int* faces, long long* count,
+                  void* ws, long long ws_bytes, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

@@ -222,6 +222,7 @@ EXPORTS = [
     "mg_guided_upsample",
     "mg_depth_align_workspace_bytes", "mg_depth_align_fit", "mg_depth_align_apply",
     "mg_depth_normals", "mg_depth_points_workspace_bytes", "mg_depth_points",
+    "mg_depth_mesh_workspace_bytes", "mg_depth_mesh",
 ]
 
 
@@ -411,6 +412,10 @@ def load(f16=False):
     lib.mg_depth_points_workspace_bytes.restype = ctypes.c_longlong
     lib.mg_depth_points.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 2 + \
         [ctypes.c_double] * 7 + [ctypes.c_int, ctypes.c_longlong] + [ctypes.c_void_p] * 6 + [ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_depth_mesh_workspace_bytes.argtypes = [ctypes.c_longlong]
+    lib.mg_depth_mesh_workspace_bytes.restype = ctypes.c_longlong
+    lib.mg_depth_mesh.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 2 + \
+        [ctypes.c_double] * 7 + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_void_p] * 7 + [ctypes.c_longlong, ctypes.c_void_p]
     lib.mg_model_scratch_fill.argtypes =[ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]

@@ -6,6 +6,7 @@ the same minus ``--color_map``):
             <out>/depth_bw/<name>_depth.png        16-bit PNG, value * 65535
             <out>/depth_colored/<name>_depth_colored.png
             <out>/depth_points/<name>_points.ply   with --save_points (an extension): the map as a coloured point cloud, binary PLY
+            <out>/depth_mesh/<name>_mesh.ply       with --save_mesh (an extension): the map as a coloured triangle mesh, binary PLY
   normals : <out>/normals_npy/<name>_normals.npy  float32 [3,H,W] in [-1,1]
             <out>/normals_vis/<name>_normals.png   (n + 1) * 127.5
   iid     : <out>/iid_{appearance|lighting}_npy/<name>_<target>.npy  float32 [H,W,3] in [0,1]
@@ -96,6 +97,12 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                        help="--save_points: drop a pixel when a neighbour's distance differs by more than this fraction of the nearer one "
                             "(the flying pixels of a depth edge); 0 keeps them.")
         p.add_argument("--points_normals", action="store_true", help="--save_points: add the surface normal of every point to the records.")
+        p.add_argument("--save_mesh", action="store_true",
+                       help="Also write <output_dir>/depth_mesh/<name>_mesh.ply: the depth map as a triangle mesh in the camera's frame with "
+                            "the picture's colours at its vertices, a binary PLY that 3D viewers open (marigold_amd/mesh.py). The camera, the "
+                            "range, the edge rule and the normals are --save_points': --fov_deg or --focal_px, --points_near, --points_far, "
+                            "--points_edge_rel (here: no triangle spans two distances that differ by more), --points_normals. May be given "
+                            "with or without --save_points.")
     p.add_argument("--guided_upsample", action="store_true",
                    help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
                         "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
@@ -160,16 +167,16 @@ def sequence_align_arg(parser, args):
     return dict(iters=args.align_iters, delta=args.align_delta, reference=args.align_reference)
 
 
-def save_points_arg(parser, args):
-    """The point-cloud flags against the rest of the command line, before anything is loaded -> None without ``--save_points``, else the
-    settings ``save_points`` takes.  What does not fit is an argparse error; the combination with ``--tile_size`` is refused like the
-    other combinations with it."""
-    if not getattr(args, "save_points", False):
+def save_points_arg(parser, args, flag="--save_points"):
+    """The point-cloud flags against the rest of the command line, before anything is loaded -> None without ``flag`` (``--save_points``,
+    or ``--save_mesh``, which takes the same settings), else the settings ``save_points`` / ``save_mesh`` take.  What does not fit is an
+    argparse error; the combination with ``--tile_size`` is refused like the other combinations with it."""
+    if not getattr(args, flag[2:], False):
         return None
     if getattr(args, "tile_size", 0):
-        raise ValueError("--save_points cannot be combined with --tile_size")
+        raise ValueError(f"{flag} cannot be combined with --tile_size")
     if (args.fov_deg is None) == (args.focal_px is None):
-        parser.error("--save_points needs the camera: exactly one of --fov_deg and --focal_px")
+        parser.error(f"{flag} needs the camera: exactly one of --fov_deg and --focal_px")
     if args.fov_deg is not None and not 0.0 < args.fov_deg < 180.0:
         parser.error(f"--fov_deg must lie inside (0, 180) (got {args.fov_deg})")
     if args.focal_px is not None and not (math.isfinite(args.focal_px) and args.focal_px > 0.0):
@@ -182,10 +189,10 @@ def save_points_arg(parser, args):
                 normals=args.points_normals)
 
 
-def save_points(folder, rgb_path, out, cfg, device):
-    """``--save_points``: one picture's depth map as ``<folder>/<name>_points.ply`` -> the path.  The camera is given for the input
-    picture and rescaled to the map's size where that differs (--output_processing_res); the colours are the picture's own, resampled to
-    the map's size; z = near + depth * (far - near) goes in as ``coef``.  One read-back: the cloud's."""
+def _map_camera_colours(rgb_path, out, cfg, device):
+    """What ``save_points`` and ``save_mesh`` hand to the device call -> (depth on the device, K, the picture's planes at the map's size).
+    The camera is given for the input picture and rescaled to the map's size where that differs (--output_processing_res); the colours
+    are the picture's own, resampled to the map's size."""
     import torch
     from . import points as P
     from .util.image_util import InterpolationMode, resize
@@ -201,10 +208,30 @@ def save_points(folder, rgb_path, out, cfg, device):
     if (H, W) != (h, w):
         K = P.scale_intrinsics(K, (H, W), (h, w))
         planes = resize(planes, (h, w), InterpolationMode.BILINEAR, antialias=True)
-    cloud = P.depth_to_points(depth, K, colors=planes[0].contiguous(), coef=(cfg["far"] - cfg["near"], cfg["near"]), edge_rel=cfg["edge_rel"],
+    return depth, K, planes[0].contiguous()
+
+
+def save_points(folder, rgb_path, out, cfg, device):
+    """``--save_points``: one picture's depth map as ``<folder>/<name>_points.ply`` -> the path.  z = near + depth * (far - near) goes in
+    as ``coef``.  One read-back: the cloud's."""
+    from . import points as P
+    depth, K, planes = _map_camera_colours(rgb_path, out, cfg, device)
+    cloud = P.depth_to_points(depth, K, colors=planes, coef=(cfg["far"] - cfg["near"], cfg["near"]), edge_rel=cfg["edge_rel"],
                               normals=cfg["normals"], frame="camera")
     path = os.path.join(folder, os.path.splitext(os.path.basename(rgb_path))[0] + "_points.ply")
     _save(path, cloud.write_ply)
+    return path
+
+
+def save_mesh(folder, rgb_path, out, cfg, device):
+    """``--save_mesh``: one picture's depth map as ``<folder>/<name>_mesh.ply`` -> the path; the camera, the colours and ``coef`` as in
+    ``save_points``.  One read-back: the mesh's."""
+    from . import mesh as M
+    depth, K, planes = _map_camera_colours(rgb_path, out, cfg, device)
+    mesh = M.depth_to_mesh(depth, K, colors=planes, coef=(cfg["far"] - cfg["near"], cfg["near"]), edge_rel=cfg["edge_rel"],
+                           normals=cfg["normals"], frame="camera")
+    path = os.path.join(folder, os.path.splitext(os.path.basename(rgb_path))[0] + "_mesh.ply")
+    _save(path, mesh.write_ply)
     return path
 
 
@@ -289,6 +316,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     guided = guided_upsample_arg(args)
     align = sequence_align_arg(parser, args)
     points = save_points_arg(parser, args)
+    mesh = save_points_arg(parser, args, "--save_mesh")
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -307,6 +335,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     if points is not None:
         points_dir = os.path.join(args.output_dir, "depth_points")
         os.makedirs(points_dir, exist_ok=True)
+    if mesh is not None:
+        mesh_dir = os.path.join(args.output_dir, "depth_mesh")
+        os.makedirs(mesh_dir, exist_ok=True)
     if pipeline is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
@@ -350,6 +381,8 @@ def main(kind: str, argv=None, pipeline=None) -> int:
         save_prediction(kind, dirs, rgb_path, out)
         if points is not None:
             save_points(points_dir, rgb_path, out, points, device)
+        if mesh is not None:
+            save_mesh(mesh_dir, rgb_path, out, mesh, device)
 
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")

@@ -48,8 +48,8 @@ def _ply_dtype(normals, colours):
     return np.dtype(fields)   # (packed: 12, 15, 24 or 27 bytes per record)
 
 
-def write_ply(path, xyz, normals=None, rgb=None):
-    """Binary little-endian PLY: ``x y z`` float, then ``nx ny nz`` float when given, then ``red green blue`` uchar when given."""
+def _ply_vertices(xyz, normals, rgb):
+    """-> (the header up to the vertex properties, as lines; the packed vertex records) - what ``write_ply`` and ``write_mesh_ply`` share"""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
     dt = _ply_dtype(normals is not None, rgb is not None)
     rec = np.empty(len(xyz), dt)
@@ -62,6 +62,12 @@ def write_ply(path, xyz, normals=None, rgb=None):
         rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}"]
     head += [f"property {'uchar' if dt[name] == np.uint8 else 'float'} {name}" for name in dt.names]
+    return head, rec
+
+
+def write_ply(path, xyz, normals=None, rgb=None):
+    """Binary little-endian PLY: ``x y z`` float, then ``nx ny nz`` float when given, then ``red green blue`` uchar when given."""
+    head, rec = _ply_vertices(xyz, normals, rgb)
     head.append("end_header")
     with open(path, "wb") as f:
         f.write(("\n".join(head) + "\n").encode("ascii"))
