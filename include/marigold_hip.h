@@ -1486,6 +1486,65 @@ int mg_depth_mesh(const float* d, const unsigned char* colors_or_null, int hwc, 
                   float* xyz, unsigned char* rgb_or_null, float* nrm_or_null, int* index_or_null, int* faces, long long* count,
                   void* ws, long long ws_bytes, void* stream);
 
+/* DEPTH TO VIEW (marigold_amd/view.py): the picture seen from a moved camera - the FACES of DEPTH TO MESH above, transformed
+ * into a second pinhole camera, drawn into a 64-bit depth-and-id buffer with integer atomic minima and resolved to a picture, a depth
+ * map and a validity map, with optional filling of the disocclusion holes.  CAMERA, DEPTH, USABLE, POINT, JOINED, CELL, CANDIDATE and
+ * FACE are those above, unchanged.  A plain C call on device pointers, no op kind; every check before any GPU work; nothing
+ * synchronises.  Integer minima and integer sums commute, and there are no float atomics, no tickets and no workgroup that waits on
+ * another: every output byte is a function of the inputs alone, and the same in both operand builds.  All floating arithmetic is fp64,
+ * every product, sum and quotient rounded on its own in the order written here; all coverage arithmetic is int64.
+ *  TARGET CAMERA.  fx2, fy2, cx2, cy2 and a size h2 x w2, under the CAMERA conventions.  pose is a HOST pointer to 12 doubles, the
+ *    rows of [R | t] (R00 R01 R02 t0, R10 ...), read before the call returns, or NULL for the identity.  R need not be orthonormal,
+ *    only finite; a mirror is a legal input.
+ *  TRANSFORM of a corner with the fp64 POINT (X, Y, Z) - not the record rounded to fp32: X' = ((R00 X + R01 Y) + R02 Z) + t0, Y' and
+ *    Z' likewise with rows 1 and 2; u = (fx2 X') / Z' + cx2, v = (fy2 Y') / Z' + cy2, q = 1 / Z'.
+ *  DROPPED faces.  A face is dropped, and counted once, under the first reason that applies:
+ *    1. near: some corner's Z' is not finite or is < z_near (z_near > 0).  There is no clipping.
+ *    2. off: some corner's |u| or |v| is not <= 2^20 (a NaN is off).
+ *    3. back: with the snapped corners xi = llrint(256 u), yi = llrint(256 v) (round half to even), the doubled signed area
+ *       A = (x2 - x0) (y1 - y0) - (x1 - x0) (y2 - y0) <= 0.  The identity view gives A > 0 for every face.
+ *    4. span: the box of pixel centres ceil(min xi / 256) .. floor(max xi / 256), and the same in y, before clamping to the target,
+ *       is wider or taller than MG_VIEW_MAX_SPAN pixels.  The cap is a condition, not a tuning: it bounds one lane's loop at 4096
+ *       pixel tests and keeps every edge value below 2^30, so that its conversion to fp64 is exact.  A surface magnified that far
+ *       gives holes and a non-zero count.
+ *    A face that is not dropped is drawn, whether or not it covers a pixel centre of the target.
+ *  COVERAGE.  With E(a, b, c) = (c.x - a.x) (b.y - a.y) - (b.x - a.x) (c.y - a.y), so that A = E(P0, P1, P2), the pixel centre
+ *    p = (256 px, 256 py) has the edge values e0 = E(p, P1, P2), e1 = E(P0, p, P2), e2 = E(P0, P1, p); e0 + e1 + e2 == A.  It is
+ *    covered when all three are >= 0: the rule is inclusive on every edge.  A pixel on a shared edge or on a vertex is offered by
+ *    every face that touches it and the depth buffer decides: there are no cracks, and the last row and column of an identity view
+ *    are covered.
+ *  DEPTH and KEY of an offer: s = (e0 q0 + e1 q1) + e2 q2, Zv = (float)((double)A / s); the offer is skipped unless Zv is finite and
+ *    > 0.  key = (bits of Zv) << 32 | face_id, face_id = 2 * (row-major index of the cell's corner A) + slot (T0: 0, T1: 1; below
+ *    2^31).  The smallest key wins: the nearest surface, and the lowest face id on equal fp32 depth.
+ *  COLOUR of the winner, per channel, c0 c1 c2 the picture's bytes at its corners: c = (((e0 q0) c0 + (e1 q1) c1) + (e2 q2) c2) / s,
+ *    byte = min((int)(c + 0.5), 255).  At a vertex this is the vertex's byte.
+ *  FILL.  fill_radius r, 0 .. MG_VIEW_MAX_FILL, 0: none.  A pixel that no face covers looks along its row for the nearest covered
+ *    pixel within r on the left and within r on the right - covered by a face, never by a fill - and takes the depth and the colour
+ *    of the one with the larger depth (the background); with only one, that one; on equal depth the left.
+ *  Outputs: rgb uint8 in the layout of colors ([h2][w2][3] with hwc != 0, planes [3][h2][w2] with hwc = 0); depth fp32 [h2][w2];
+ *    valid uint8 [h2][w2]: 1 where a face covers the pixel, 2 where filled, 0 elsewhere, where depth and rgb are zeros; face int32
+ *    [h2][w2] or NULL: the winning face id, -1 where no face covers the pixel, filled or not; count DEVICE int64 [8]: faces, drawn,
+ *    near, off, back, span, pixels covered, pixels filled.  A map with h == 1 or w == 1 has no cells: zeros everywhere.
+ *  mg_depth_view_workspace_bytes: what mg_depth_view needs for n2 = h2 w2 target pixels, 1 <= n2 <= 2^30 (-1 with mg_last_error
+ *    otherwise): 8 bytes per target pixel, rounded up to 16 bytes; the counts are summed in count itself.
+ *  mg_depth_view: three launches - the key buffer to "no offer" and count to zeros; the splat, one lane per cell, a 64-bit atomic
+ *    minimum per offer, the face counts summed per workgroup and added with integer atomics; the resolve, one lane per target pixel,
+ *    which computes the winning face again from its id and fills from the key buffer, so that filled pixels never feed other fills.
+ * Refused, the message starting with "mg_depth_view:": a null d, colors, rgb, depth, valid, count or ws; everything mg_depth_points
+ * refuses about the map, the camera, the range and edge_rel; a target below 1 x 1 or above 2^30 pixels; fx2 or fy2 not finite or <= 0;
+ * cx2 or cy2 not finite; a pose entry that is not finite; z_near not finite or <= 0; fill_radius outside 0 .. MG_VIEW_MAX_FILL; d,
+ * depth, face, count or coef not aligned to their elements; ws not 16-byte aligned or ws_bytes too small.  examples/host_view.cpp
+ * composes a prediction, the colours and two of these calls into a stereo pair. */
+#define MG_VIEW_MAX_SPAN 64
+#define MG_VIEW_MAX_FILL 64
+long long mg_depth_view_workspace_bytes(long long n2);
+int mg_depth_view(const float* d, const unsigned char* colors, int hwc, const unsigned char* mask_or_null,
+                  const double* coef_or_null, int h, int w, double fx, double fy, double cx, double cy,
+                  double z_min, double z_max, double edge_rel, const double* pose_or_null,
+                  double fx2, double fy2, double cx2, double cy2, int h2, int w2, double z_near, int fill_radius,
+                  unsigned char* rgb, float* depth, unsigned char* valid, int* face_or_null, long long* count,
+                  void* ws, long long ws_bytes, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

@@ -7,6 +7,7 @@ the same minus ``--color_map``):
             <out>/depth_colored/<name>_depth_colored.png
             <out>/depth_points/<name>_points.ply   with --save_points (an extension): the map as a coloured point cloud, binary PLY
             <out>/depth_mesh/<name>_mesh.ply       with --save_mesh (an extension): the map as a coloured triangle mesh, binary PLY
+            <out>/depth_stereo/<name>_stereo.png   with --save_stereo (an extension): the picture from two eyes, left beside right
   normals : <out>/normals_npy/<name>_normals.npy  float32 [3,H,W] in [-1,1]
             <out>/normals_vis/<name>_normals.png   (n + 1) * 127.5
   iid     : <out>/iid_{appearance|lighting}_npy/<name>_<target>.npy  float32 [H,W,3] in [0,1]
@@ -103,6 +104,17 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                             "range, the edge rule and the normals are --save_points': --fov_deg or --focal_px, --points_near, --points_far, "
                             "--points_edge_rel (here: no triangle spans two distances that differ by more), --points_normals. May be given "
                             "with or without --save_points.")
+        p.add_argument("--save_stereo", action="store_true",
+                       help="Also write <output_dir>/depth_stereo/<name>_stereo.png: the picture seen by a left and a right eye, left "
+                            "beside right at the map's size, rendered on the device from the triangles of --save_mesh "
+                            "(marigold_amd/view.py). The camera, the range and the edge rule are --save_points': --fov_deg or --focal_px, "
+                            "--points_near, --points_far, --points_edge_rel.")
+        p.add_argument("--stereo_baseline", type=float, default=0.065,
+                       help="--save_stereo: the distance between the two eyes, in the units of --points_near / --points_far. The default "
+                            "rests on nothing measured: the distances themselves are the caller's choice.")
+        p.add_argument("--stereo_fill", type=int, default=8,
+                       help="--save_stereo: fill a pixel no triangle covers from the farther of the nearest covered pixels of its row, "
+                            "within this many pixels (0 to 64; 0: leave the holes black). The default rests on nothing measured.")
     p.add_argument("--guided_upsample", action="store_true",
                    help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
                         "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
@@ -235,6 +247,32 @@ def save_mesh(folder, rgb_path, out, cfg, device):
     return path
 
 
+def save_stereo_arg(parser, args):
+    """``--save_stereo`` against the rest of the command line -> None without it, else the settings ``save_stereo`` takes: those of
+    ``--save_points`` with the baseline and the fill radius."""
+    cfg = save_points_arg(parser, args, "--save_stereo")
+    if cfg is None:
+        return None
+    if not math.isfinite(args.stereo_baseline):
+        parser.error(f"--stereo_baseline must be finite (got {args.stereo_baseline})")
+    if not 0 <= args.stereo_fill <= 64:
+        parser.error(f"--stereo_fill must lie in 0 .. 64 (got {args.stereo_fill})")
+    return dict(cfg, baseline=args.stereo_baseline, fill=args.stereo_fill)
+
+
+def save_stereo(folder, rgb_path, out, cfg, device):
+    """``--save_stereo``: one picture's stereo pair as ``<folder>/<name>_stereo.png``, left beside right -> the path; the camera, the
+    colours and ``coef`` as in ``save_points``.  One read-back per eye: its picture."""
+    from . import view as V
+    depth, K, planes = _map_camera_colours(rgb_path, out, cfg, device)
+    pair = V.stereo_pair(depth, K, planes, cfg["baseline"], coef=(cfg["far"] - cfg["near"], cfg["near"]), edge_rel=cfg["edge_rel"],
+                         fill_radius=cfg["fill"])
+    both = np.concatenate([eye.to_host().rgb for eye in pair], axis=1)
+    path = os.path.join(folder, os.path.splitext(os.path.basename(rgb_path))[0] + "_stereo.png")
+    _save(path, lambda tmp: Image.fromarray(both).save(tmp, format="PNG"))
+    return path
+
+
 def list_images(folder):
     files = sorted(f for f in glob(os.path.join(folder, "*")) if os.path.splitext(f)[1].lower() in EXTENSION_LIST)
     return files
@@ -317,6 +355,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     align = sequence_align_arg(parser, args)
     points = save_points_arg(parser, args)
     mesh = save_points_arg(parser, args, "--save_mesh")
+    stereo = save_stereo_arg(parser, args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -338,6 +377,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     if mesh is not None:
         mesh_dir = os.path.join(args.output_dir, "depth_mesh")
         os.makedirs(mesh_dir, exist_ok=True)
+    if stereo is not None:
+        stereo_dir = os.path.join(args.output_dir, "depth_stereo")
+        os.makedirs(stereo_dir, exist_ok=True)
     if pipeline is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
@@ -383,6 +425,8 @@ def main(kind: str, argv=None, pipeline=None) -> int:
             save_points(points_dir, rgb_path, out, points, device)
         if mesh is not None:
             save_mesh(mesh_dir, rgb_path, out, mesh, device)
+        if stereo is not None:
+            save_stereo(stereo_dir, rgb_path, out, stereo, device)
 
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")

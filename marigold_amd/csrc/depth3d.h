@@ -1,6 +1,6 @@
-// The rules of depth to 3D (include/marigold_hip.h states them), one copy for points.hip and mesh.hip: which pixels
-// are usable, which are joined, a pixel's point, its tangents and its normal, the coefficients, and what every entry point refuses about
-// the map, the camera and the rules.  fp64 throughout; both files are built with -ffp-contract=off, so every product, sum and quotient
+// The rules of depth to 3D (include/marigold_hip.h states them), one copy for points.hip, mesh.hip and view.hip: which pixels
+// are usable, which are joined, a pixel's point, its tangents and its normal, the coefficients, a cell's split and faces, and what every entry point refuses about
+// the map, the camera and the rules.  fp64 throughout; all three files are built with -ffp-contract=off, so every product, sum and quotient
 // below is rounded on its own, in the order the header writes them.
 #pragma once
 #include <cmath>
@@ -111,6 +111,57 @@ __device__ __forceinline__ void load_coef(const PointsArgs& a, double& s, double
     s = a.coef[0];
     t = a.coef[1];
   }
+}
+
+// ---- the cell rules of the meshes (6i) and the views (6j) ----
+
+// A cell's code: bits 0 and 1 - T0, T1 are faces; bits 2.. - the form, which names the candidates' corners.
+enum { FORM_SPLIT_AD = 0, FORM_SPLIT_BC = 1, FORM_NO_D = 2, FORM_NO_A = 3, FORM_NO_B = 4, FORM_NO_C = 5 };
+enum { CORNER_A = 0, CORNER_B = 1, CORNER_C = 2, CORNER_D = 3 };
+
+// the corners of candidate `slot` of a cell of `form`, two bits each, P0 lowest: (A, C, D), (A, D, B), (A, C, B), (B, C, D)
+constexpr unsigned TRI_ACD = CORNER_A | CORNER_C << 2 | CORNER_D << 4, TRI_ADB = CORNER_A | CORNER_D << 2 | CORNER_B << 4;
+constexpr unsigned TRI_ACB = CORNER_A | CORNER_C << 2 | CORNER_B << 4, TRI_BCD = CORNER_B | CORNER_C << 2 | CORNER_D << 4;
+
+__device__ __forceinline__ unsigned triangle_of(int form, int slot) {
+  switch (form) {
+    case FORM_SPLIT_AD: return slot == 0 ? TRI_ACD : TRI_ADB;
+    case FORM_SPLIT_BC: return slot == 0 ? TRI_ACB : TRI_BCD;
+    case FORM_NO_D: return TRI_ACB;
+    case FORM_NO_A: return TRI_BCD;
+    case FORM_NO_B: return TRI_ACD;
+    default: return TRI_ADB;   // FORM_NO_C
+  }
+}
+
+// the code of the cell anchored at pixel i (0 for a pixel of the last row or column: no cell)
+__device__ __forceinline__ unsigned cell_code(const PointsArgs& a, double s, double t, long long i) {
+  const int y = (int)(i / a.w), x = (int)(i - (long long)y * a.w);
+  if (x >= a.w - 1 || y >= a.h - 1) return 0;
+  double z[4];
+  bool ok[4];
+  ok[CORNER_A] = depth_at(a, s, t, y, x, z[CORNER_A]);
+  ok[CORNER_B] = depth_at(a, s, t, y, x + 1, z[CORNER_B]);
+  ok[CORNER_C] = depth_at(a, s, t, y + 1, x, z[CORNER_C]);
+  ok[CORNER_D] = depth_at(a, s, t, y + 1, x + 1, z[CORNER_D]);
+  const int usable = (int)ok[0] + (int)ok[1] + (int)ok[2] + (int)ok[3];
+  if (usable < 3) return 0;
+  int form, slots = 1;
+  if (usable == 4) {
+    form = fabs(z[CORNER_A] - z[CORNER_D]) <= fabs(z[CORNER_B] - z[CORNER_C]) ? FORM_SPLIT_AD : FORM_SPLIT_BC;
+    slots = 2;
+  } else {
+    form = !ok[CORNER_D] ? FORM_NO_D : !ok[CORNER_A] ? FORM_NO_A : !ok[CORNER_B] ? FORM_NO_B : FORM_NO_C;
+  }
+  unsigned code = (unsigned)form << 2;
+#pragma unroll
+  for (int slot = 0; slot < 2; ++slot) {
+    if (slot >= slots) continue;
+    const unsigned tri = triangle_of(form, slot);
+    const double z0 = z[tri & 3u], z1 = z[(tri >> 2) & 3u], z2 = z[(tri >> 4) & 3u];   // (usable corners only: the form saw to that)
+    if (joined_to(a, z0, z1) && joined_to(a, z1, z2) && joined_to(a, z2, z0)) code |= 1u << slot;
+  }
+  return code;
 }
 
 // what every call refuses about the map, the camera and the rules -> 0 | 2 with the message set

@@ -1,6 +1,7 @@
 // Depth to mesh: a depth map as vertices and triangles that stop at depth edges - mg_depth_mesh, both streams compacted
 // consistently without the host learning a count.  The definitions (cell, candidate, face, vertex, count) and the contract are in
-// include/marigold_hip.h; the rules shared with the point clouds (usable, joined, point, normal) are depth3d.h's.
+// include/marigold_hip.h; the rules shared with the point clouds (usable, joined, point, normal) and the cell rules
+// (a cell's code, its form, the corners of its candidates) are depth3d.h's.
 // Five launches, none of which waits on another workgroup; only stream order separates them:
 //   1. every anchor pixel decides its cell's code - the form (split, or which corner is missing) and which of T0 / T1 are faces - into
 //      a byte map, and the faces of every chunk of anchors are counted;
@@ -11,7 +12,7 @@
 //      record, and its rank into an int32 map;
 //   5. the face scatter ranks the faces likewise and reads the three indices from that map.
 // No atomics, no tickets: where a record goes is a function of the inputs alone.  fp64 throughout, built with -ffp-contract=off.
-#include "depth3d.h"   // the rules, shared with points.hip
+#include "depth3d.h"   // the rules, shared with points.hip and view.hip
 
 namespace {
 
@@ -20,25 +21,6 @@ constexpr int MESH_CHUNK = 2048;                               // pixels (anchor
 constexpr int MESH_PER_THREAD = MESH_CHUNK / MESH_THREADS;
 constexpr int MESH_WAVES = MESH_THREADS / 64;
 constexpr int MESH_SCAN_LANES = 256;                           // lanes of the one workgroup that turns counts into offsets
-
-// A cell's code: bits 0 and 1 - T0, T1 are faces; bits 2.. - the form, which names the candidates' corners.
-enum { FORM_SPLIT_AD = 0, FORM_SPLIT_BC = 1, FORM_NO_D = 2, FORM_NO_A = 3, FORM_NO_B = 4, FORM_NO_C = 5 };
-enum { CORNER_A = 0, CORNER_B = 1, CORNER_C = 2, CORNER_D = 3 };
-
-// the corners of candidate `slot` of a cell of `form`, two bits each, P0 lowest: (A, C, D), (A, D, B), (A, C, B), (B, C, D)
-constexpr unsigned TRI_ACD = CORNER_A | CORNER_C << 2 | CORNER_D << 4, TRI_ADB = CORNER_A | CORNER_D << 2 | CORNER_B << 4;
-constexpr unsigned TRI_ACB = CORNER_A | CORNER_C << 2 | CORNER_B << 4, TRI_BCD = CORNER_B | CORNER_C << 2 | CORNER_D << 4;
-
-__device__ __forceinline__ unsigned triangle_of(int form, int slot) {
-  switch (form) {
-    case FORM_SPLIT_AD: return slot == 0 ? TRI_ACD : TRI_ADB;
-    case FORM_SPLIT_BC: return slot == 0 ? TRI_ACB : TRI_BCD;
-    case FORM_NO_D: return TRI_ACB;
-    case FORM_NO_A: return TRI_BCD;
-    case FORM_NO_B: return TRI_ACD;
-    default: return TRI_ADB;   // FORM_NO_C
-  }
-}
 
 // bit c: corner c of the cell belongs to one of its faces
 __device__ __forceinline__ unsigned corners_in_faces(unsigned code) {
@@ -51,36 +33,6 @@ __device__ __forceinline__ unsigned corners_in_faces(unsigned code) {
     used |= 1u << (tri & 3u) | 1u << ((tri >> 2) & 3u) | 1u << ((tri >> 4) & 3u);
   }
   return used;
-}
-
-// the code of the cell anchored at pixel i (0 for a pixel of the last row or column: no cell)
-__device__ __forceinline__ unsigned cell_code(const PointsArgs& a, double s, double t, long long i) {
-  const int y = (int)(i / a.w), x = (int)(i - (long long)y * a.w);
-  if (x >= a.w - 1 || y >= a.h - 1) return 0;
-  double z[4];
-  bool ok[4];
-  ok[CORNER_A] = depth_at(a, s, t, y, x, z[CORNER_A]);
-  ok[CORNER_B] = depth_at(a, s, t, y, x + 1, z[CORNER_B]);
-  ok[CORNER_C] = depth_at(a, s, t, y + 1, x, z[CORNER_C]);
-  ok[CORNER_D] = depth_at(a, s, t, y + 1, x + 1, z[CORNER_D]);
-  const int usable = (int)ok[0] + (int)ok[1] + (int)ok[2] + (int)ok[3];
-  if (usable < 3) return 0;
-  int form, slots = 1;
-  if (usable == 4) {
-    form = fabs(z[CORNER_A] - z[CORNER_D]) <= fabs(z[CORNER_B] - z[CORNER_C]) ? FORM_SPLIT_AD : FORM_SPLIT_BC;
-    slots = 2;
-  } else {
-    form = !ok[CORNER_D] ? FORM_NO_D : !ok[CORNER_A] ? FORM_NO_A : !ok[CORNER_B] ? FORM_NO_B : FORM_NO_C;
-  }
-  unsigned code = (unsigned)form << 2;
-#pragma unroll
-  for (int slot = 0; slot < 2; ++slot) {
-    if (slot >= slots) continue;
-    const unsigned tri = triangle_of(form, slot);
-    const double z0 = z[tri & 3u], z1 = z[(tri >> 2) & 3u], z2 = z[(tri >> 4) & 3u];   // (usable corners only: the form saw to that)
-    if (joined_to(a, z0, z1) && joined_to(a, z1, z2) && joined_to(a, z2, z0)) code |= 1u << slot;
-  }
-  return code;
 }
 
 // whether pixel (x, y) is a corner of a face: it is D of the cell up and to the left, C of the one above, B of the one to the left and A
