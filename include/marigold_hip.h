@@ -1545,6 +1545,55 @@ int mg_depth_view(const float* d, const unsigned char* colors, int hwc, const un
                   unsigned char* rgb, float* depth, unsigned char* valid, int* face_or_null, long long* count,
                   void* ws, long long ws_bytes, void* stream);
 
+/* DEPTH TO FOCUS (marigold_amd/focus.py): the picture refocused from its depth map - a synthetic shallow depth of field.
+ * Every pixel is blurred by the circle of confusion its distance from a focus distance implies; near, blurred surfaces spread over what
+ * is behind them, and a sharp foreground is not polluted by its blurred background.  DEPTH (z, coef) and USABLE (mask, z_min, z_max) are
+ * those of DEPTH TO 3D above, unchanged; there is no camera.  A plain C call on device pointers, no op kind; every check before any GPU
+ * work; nothing synchronises.  Everything after the blur radius is integer arithmetic, and integer sums commute: every output byte is a
+ * function of the inputs alone, and the same in both operand builds.  There are no float atomics, no tickets and no workgroup that
+ * waits on another.
+ *  FOCUS DISTANCE zf.  With focus_x >= 0 and focus_y >= 0 it is the fp64 z of pixel (row focus_y, column focus_x), read on the device:
+ *    a host can focus on a pixel of a prediction it has never seen.  With focus_x == focus_y == -1 it is the host double z_focus.
+ *  BLUR RADIUS of a usable pixel, fp64, every operation rounded on its own: b = gain * fabs(1.0 / z - 1.0 / zf) in
+ *    MG_FOCUS_SPACE_LENS - the thin lens: gain = 0.5 * fx * aperture, the aperture in the units of z - and b = gain * fabs(z - zf) in
+ *    MG_FOCUS_SPACE_LINEAR.  r16 = !(b < max_radius) ? 16 * max_radius : (int)llrint(16.0 * b) (round half to even): the radius in
+ *    sixteenths of a pixel, capped; a NaN is capped.  gain is finite and >= 0, max_radius 0 .. MG_FOCUS_MAX_RADIUS.  z_min >= 0, as
+ *    USABLE requires, so a usable z is > 0 and 1.0 / z is finite or +inf.
+ *  BAD FOCUS: the focus pixel is not usable, or zf is not finite, or zf <= 0 in MG_FOCUS_SPACE_LENS.  Then count[4] = 1, every r16 is 0
+ *    and rgb is the source, byte for byte.  Otherwise count[4] = 0.
+ *  ORDER.  q is in front of or level with p when (float)z_q <= (float)z_p, each z rounded once to fp32.
+ *  CONTRIBUTION.  For a usable target p and every usable q inside the picture at the offset (dx, dy), |dx|, |dy| <= max_radius:
+ *    e = r16_q when q is in front of or level with p, else e = min(r16_q, r16_p); q contributes when
+ *    256 * (dx * dx + dy * dy) <= e * e, in integers.  p always contributes to itself.
+ *  WEIGHT.  W[e] = floor(2^24 / N[e]), N[e] the number of integer offsets of the whole plane with 256 * (dx^2 + dy^2) <= e^2: N[0] = 1,
+ *    N[16] = 5, N[512] = 3209, so W >= 5228.  N is not clipped at the picture's border.
+ *  RESULT.  D = sum of W and C_k = sum of W * c_k over the contributions, c_k the source byte of channel k, in unsigned 64-bit integers
+ *    (at most 4225 * 2^24 * 255 < 2^45); the output byte is (C_k + D / 2) / D, integer divisions.  A target that is not usable keeps its
+ *    source bytes.
+ *  Inputs: d fp32 [h][w]; colors uint8 [h][w][3] with hwc != 0, planes [3][h][w] with hwc = 0; mask uint8 [h][w] or NULL; coef or NULL.
+ *  Outputs: rgb uint8 in the layout of colors; valid uint8 [h][w]: 1 usable, 0 not; radius uint16 [h][w] or NULL: r16, 0xFFFF where
+ *    the pixel is not usable; count DEVICE int64 [5]: usable pixels, sharp pixels (r16 == 0), capped pixels (r16 == 16 * max_radius,
+ *    counted when max_radius > 0), contributions summed over all targets, the bad-focus flag.
+ *  mg_depth_focus_workspace_bytes: what mg_depth_focus needs for n = h w pixels, 1 <= n <= 2^30 (-1 with mg_last_error otherwise):
+ *    (float)z and r16 of every pixel, 6 bytes, each of the two arrays rounded up to 16 bytes.
+ *  mg_depth_focus: three launches - count to zeros; the prepare, one lane per pixel, which writes (float)z and r16 to the workspace,
+ *    valid and radius, and adds the three pixel counts with integer atomics, one per workgroup; the gather, a workgroup per tile of
+ *    32 x 8 targets, which takes the largest r16 within max_radius of its tile - no tap beyond that radius can contribute - stages
+ *    the tile and a halo of that radius in LDS and sums every target's window from there.  The weights are a compile-time table.
+ * Refused, the message starting with "mg_depth_focus:": a null d, colors, rgb, valid, count or ws; everything mg_depth_points refuses
+ * about the map and the range; a space other than the two; gain not finite or < 0; max_radius outside 0 .. MG_FOCUS_MAX_RADIUS; a
+ * focus pair that is neither a pixel nor (-1, -1), or a pixel outside the picture; d, radius, count or coef not aligned to their
+ * elements; ws not 16-byte aligned or ws_bytes too small.  examples/host_focus.cpp composes a prediction, the colours and this call
+ * into a picture. */
+#define MG_FOCUS_MAX_RADIUS 32
+enum { MG_FOCUS_SPACE_LENS = 0, MG_FOCUS_SPACE_LINEAR = 1 };
+long long mg_depth_focus_workspace_bytes(long long n);
+int mg_depth_focus(const float* d, const unsigned char* colors, int hwc, const unsigned char* mask_or_null,
+                   const double* coef_or_null, int h, int w, double z_min, double z_max,
+                   int space, double gain, int max_radius, int focus_x, int focus_y, double z_focus,
+                   unsigned char* rgb, unsigned char* valid, unsigned short* radius_or_null, long long* count,
+                   void* ws, long long ws_bytes, void* stream);
+
 /* The TILED prediction of a large picture as ONE call (pipe.predict_tiled for a host without Python): from the uint8 bytes of the
  * picture and a seed to the stitched, clipped map at the size asked for, the stitched uncertainty, the 16-bit depth and the picture.
  * It runs on a model image of several configurations (export_model_image(configs=[...])), which the host finds with

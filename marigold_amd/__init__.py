@@ -9,6 +9,7 @@ from .points import (Intrinsics, PointCloud, depth_to_normals, depth_to_points, 
                      read_ply, scale_intrinsics, write_ply)
 from .mesh import HostMesh, Mesh, depth_to_mesh, read_mesh_ply, write_mesh_ply  # noqa: F401
 from .view import HostView, View, render_view, stereo_pair  # noqa: F401
+from .focus import HostRefocus, Refocus, refocus  # noqa: F401
 
 MarigoldPipeline = MarigoldDepthPipeline  # for backward compatibility
 

@@ -224,6 +224,7 @@ EXPORTS = [
     "mg_depth_normals", "mg_depth_points_workspace_bytes", "mg_depth_points",
     "mg_depth_mesh_workspace_bytes", "mg_depth_mesh",
     "mg_depth_view_workspace_bytes", "mg_depth_view",
+    "mg_depth_focus_workspace_bytes", "mg_depth_focus",
 ]
 
 
@@ -269,6 +270,8 @@ ALIGN_MAX_ITERS = 32   # MG_ALIGN_MAX_ITERS
 ALIGN_START_GIVEN, ALIGN_START_LS = 0, 1   # MG_ALIGN_START_*
 NORMALS_FRAME = {"camera": 0, "marigold": 1}   # MG_NORMALS_FRAME_*
 VIEW_MAX_SPAN, VIEW_MAX_FILL = 64, 64   # MG_VIEW_MAX_SPAN, MG_VIEW_MAX_FILL
+FOCUS_MAX_RADIUS = 32   # MG_FOCUS_MAX_RADIUS
+FOCUS_SPACE = {"lens": 0, "linear": 1}   # MG_FOCUS_SPACE_*
 TINY_VAE_LAYERS = 33   # MG_TINY_VAE_LAYERS: the 64 -> 64 layers of either half
 # enum mg_cfg: the configuration words of a model image (mg_model_info), position = word; "pictures" is written 0 for 1.  An image
 # holds CFG_WORDS of them: what lies behind the named ones is reserved, written 0
@@ -423,6 +426,11 @@ def load(f16=False):
     lib.mg_depth_view.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 2 + \
         [ctypes.c_double] * 7 + [ctypes.c_void_p] + [ctypes.c_double] * 4 + [ctypes.c_int] * 2 + [ctypes.c_double, ctypes.c_int] + \
         [ctypes.c_void_p] * 6 + [ctypes.c_longlong, ctypes.c_void_p]
+    lib.mg_depth_focus_workspace_bytes.argtypes = [ctypes.c_longlong]
+    lib.mg_depth_focus_workspace_bytes.restype = ctypes.c_longlong
+    lib.mg_depth_focus.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 2 + \
+        [ctypes.c_double] * 2 + [ctypes.c_int, ctypes.c_double] + [ctypes.c_int] * 3 + [ctypes.c_double] + [ctypes.c_void_p] * 5 + \
+        [ctypes.c_longlong, ctypes.c_void_p]
     lib.mg_model_scratch_fill.argtypes =[ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mg_model_predict_next.argtypes = lib.mg_model_predict_out.argtypes + [ctypes.c_float]
     lib.mg_model_num_configs.argtypes = [ctypes.c_void_p]

@@ -8,6 +8,7 @@ the same minus ``--color_map``):
             <out>/depth_points/<name>_points.ply   with --save_points (an extension): the map as a coloured point cloud, binary PLY
             <out>/depth_mesh/<name>_mesh.ply       with --save_mesh (an extension): the map as a coloured triangle mesh, binary PLY
             <out>/depth_stereo/<name>_stereo.png   with --save_stereo (an extension): the picture from two eyes, left beside right
+            <out>/depth_refocus/<name>_refocus.png with --save_refocus (an extension): the picture with a shallow depth of field
   normals : <out>/normals_npy/<name>_normals.npy  float32 [3,H,W] in [-1,1]
             <out>/normals_vis/<name>_normals.png   (n + 1) * 127.5
   iid     : <out>/iid_{appearance|lighting}_npy/<name>_<target>.npy  float32 [H,W,3] in [0,1]
@@ -115,6 +116,23 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
         p.add_argument("--stereo_fill", type=int, default=8,
                        help="--save_stereo: fill a pixel no triangle covers from the farther of the nearest covered pixels of its row, "
                             "within this many pixels (0 to 64; 0: leave the holes black). The default rests on nothing measured.")
+        p.add_argument("--save_refocus", action="store_true",
+                       help="Also write <output_dir>/depth_refocus/<name>_refocus.png: the picture at the map's size with a shallow depth "
+                            "of field, every pixel blurred on the device by the circle of confusion of a thin lens focused at one distance "
+                            "(marigold_amd/focus.py). The camera and the range are --save_points': --fov_deg or --focal_px, --points_near, "
+                            "--points_far.")
+        p.add_argument("--refocus_at", type=str, default="0.5,0.5",
+                       help="--save_refocus: focus on the distance of this pixel, given as Y,X in fractions of the height and the width "
+                            "(0,0: the top left corner; the default is the centre).")
+        p.add_argument("--refocus_distance", type=float, default=None,
+                       help="--save_refocus: focus at this distance, in the units of --points_near / --points_far, in place of --refocus_at.")
+        p.add_argument("--refocus_aperture", type=float, default=0.1,
+                       help="--save_refocus: the diameter of the lens, in the units of --points_near / --points_far; the blur radius in "
+                            "pixels is half the focal length in pixels times this times |1 / z - 1 / focus|. No measurement stands behind "
+                            "the default: the distances themselves are the caller's choice.")
+        p.add_argument("--refocus_max_radius", type=int, default=16,
+                       help="--save_refocus: the largest blur radius in pixels (0 to 32); larger ones are capped. No measurement stands "
+                            "behind the default.")
     p.add_argument("--guided_upsample", action="store_true",
                    help="Enlarge the prediction to the input size with edge-guided (joint bilateral) upsampling in place of the plain "
                         "resampling: the input picture decides which low-resolution neighbours a pixel borrows from, so edges stay sharp.")
@@ -273,6 +291,46 @@ def save_stereo(folder, rgb_path, out, cfg, device):
     return path
 
 
+def save_refocus_arg(parser, args):
+    """``--save_refocus`` against the rest of the command line -> None without it, else the settings ``save_refocus`` takes: those of
+    ``--save_points`` with the focus - ``at``, fractions (y, x), or ``distance`` - the aperture and the largest radius."""
+    cfg = save_points_arg(parser, args, "--save_refocus")
+    if cfg is None:
+        return None
+    try:
+        fy, fx = (float(v) for v in args.refocus_at.split(","))
+    except ValueError:
+        fy = fx = math.nan
+    if not (0.0 <= fy <= 1.0 and 0.0 <= fx <= 1.0):
+        parser.error(f"--refocus_at must be Y,X, two fractions inside [0, 1] (got {args.refocus_at})")
+    if args.refocus_distance is not None and not (math.isfinite(args.refocus_distance) and args.refocus_distance > 0.0):
+        parser.error(f"--refocus_distance must be finite and > 0 (got {args.refocus_distance})")
+    if not (math.isfinite(args.refocus_aperture) and args.refocus_aperture >= 0.0):
+        parser.error(f"--refocus_aperture must be finite and >= 0 (got {args.refocus_aperture})")
+    if not 0 <= args.refocus_max_radius <= 32:
+        parser.error(f"--refocus_max_radius must lie in 0 .. 32 (got {args.refocus_max_radius})")
+    return dict(cfg, at=(fy, fx), distance=args.refocus_distance, aperture=args.refocus_aperture, max_radius=args.refocus_max_radius)
+
+
+def save_refocus(folder, rgb_path, out, cfg, device):
+    """``--save_refocus``: one picture refocused as ``<folder>/<name>_refocus.png`` at the map's size -> the path; the camera, the
+    colours and ``coef`` as in ``save_points``.  The focus pixel is the fraction of the map's size, rounded down and kept inside the
+    map; its distance is read on the device.  One read-back: the picture."""
+    from . import focus as F
+    depth, K, planes = _map_camera_colours(rgb_path, out, cfg, device)
+    h, w = depth.shape
+    if cfg["distance"] is not None:
+        where = dict(focus=cfg["distance"])
+    else:
+        where = dict(focus_at=(min(int(cfg["at"][0] * h), h - 1), min(int(cfg["at"][1] * w), w - 1)))
+    shot = F.refocus(depth, planes, K=K, aperture=cfg["aperture"], max_radius=cfg["max_radius"], coef=(cfg["far"] - cfg["near"], cfg["near"]),
+                     **where)
+    picture = shot.to_host().rgb
+    path = os.path.join(folder, os.path.splitext(os.path.basename(rgb_path))[0] + "_refocus.png")
+    _save(path, lambda tmp: Image.fromarray(picture).save(tmp, format="PNG"))
+    return path
+
+
 def list_images(folder):
     files = sorted(f for f in glob(os.path.join(folder, "*")) if os.path.splitext(f)[1].lower() in EXTENSION_LIST)
     return files
@@ -356,6 +414,7 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     points = save_points_arg(parser, args)
     mesh = save_points_arg(parser, args, "--save_mesh")
     stereo = save_stereo_arg(parser, args)
+    refocus = save_refocus_arg(parser, args)
     if args.ensemble_size > 15:
         logging.warning("Running with large ensemble size will be slow.")
     match_input_res = not args.output_processing_res
@@ -380,6 +439,9 @@ def main(kind: str, argv=None, pipeline=None) -> int:
     if stereo is not None:
         stereo_dir = os.path.join(args.output_dir, "depth_stereo")
         os.makedirs(stereo_dir, exist_ok=True)
+    if refocus is not None:
+        refocus_dir = os.path.join(args.output_dir, "depth_refocus")
+        os.makedirs(refocus_dir, exist_ok=True)
     if pipeline is None:
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: the Marigold HIP engine has no CPU fallback")
@@ -427,6 +489,8 @@ def main(kind: str, argv=None, pipeline=None) -> int:
             save_mesh(mesh_dir, rgb_path, out, mesh, device)
         if stereo is not None:
             save_stereo(stereo_dir, rgb_path, out, stereo, device)
+        if refocus is not None:
+            save_refocus(refocus_dir, rgb_path, out, refocus, device)
 
     if args.images_per_program < 1:
         raise ValueError(f"--images_per_program must be >= 1 (got {args.images_per_program})")
