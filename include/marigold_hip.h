@@ -15,6 +15,10 @@
  * *program* (mg_program_*) that the library replays with no host logic in between (and
  * optionally as a captured hipGraph).  The Python host mirrors the reference's
  * unet/vae/scheduler interface by building such programs (marigold_amd/engine.py, modules.py).
+ *
+ * The stream contract - a call enqueues all of its device work on the stream it is given, owns its workspace until that stream has
+ * passed it, and does not synchronise except where its comment says so - is tested for every stand-alone call that takes a stream
+ * (tests/test_gpu_stream_fidelity.py; tests/test_stream_fidelity_host.py holds that file's table to the prototypes below).
  */
 #ifndef MARIGOLD_HIP_H
 #define MARIGOLD_HIP_H

@@ -73,10 +73,10 @@ def _dev(a):
     return None if a is None else torch.from_numpy(a).cuda()
 
 
-def _fit(lib, d, ref, mask, fit_shift, iters, start, coef, flag, ws, delta=DELTA):
+def _fit(lib, d, ref, mask, fit_shift, iters, start, coef, flag, ws, delta=DELTA, stream=None):
     mode, s0, t0 = (L.ALIGN_START_LS, 1.0, 0.0) if start == "ls" else (L.ALIGN_START_GIVEN,) + tuple(start)
     rc = lib.mg_depth_align_fit(d.data_ptr(), ref.data_ptr(), None if mask is None else mask.data_ptr(), d.numel(), fit_shift, iters, mode, s0, t0,
-                                delta, coef.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), None)
+                                delta, coef.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), stream)
     assert rc == 0, lib.mg_last_error().decode()
 
 

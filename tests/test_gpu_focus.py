@@ -33,7 +33,7 @@ def _lib(f16):
     return L.init(0, f16)
 
 
-def _focus(lib, c, off=0, garbage=None, coef_dev=None, radius=None):
+def _focus(lib, c, off=0, garbage=None, coef_dev=None, radius=None, stream=None):
     """one raw mg_depth_focus of case ``c`` -> dict of the outputs as numpy (``radius`` None where it was not asked for)"""
     h, w = c.shape
     n = h * w
@@ -51,7 +51,7 @@ def _focus(lib, c, off=0, garbage=None, coef_dev=None, radius=None):
     fy, fx = c.focus_at if c.focus_at is not None else (-1, -1)
     rc = lib.mg_depth_focus(dd.ptr(), cc.ptr(), int(c.hwc), _ptr(mm), _ptr(coef_dev), h, w, c.z_range[0], c.z_range[1], c.space, c.gain, c.max_radius,
                             fx, fy, 0.0 if c.focus is None else c.focus, rgb.ptr(), valid.ptr(), rad.ptr() if want_radius else None, count.ptr(),
-                            ws.ptr(), need, None)
+                            ws.ptr(), need, stream)
     assert rc == 0, lib.mg_last_error().decode()
     torch.cuda.synchronize()
     ws.read()

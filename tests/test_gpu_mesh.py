@@ -114,7 +114,7 @@ def _lib(f16):
     return L.init(0, f16)
 
 
-def _mesh(lib, d, colors, mask, K, opt, cap_v, cap_f, off=0, coef_dev=None):
+def _mesh(lib, d, colors, mask, K, opt, cap_v, cap_f, off=0, coef_dev=None, stream=None):
     """one raw mg_depth_mesh -> dict of the outputs as numpy (whole buffers of the capacities, canaries past what was written)"""
     coef, edge, frame, hwc = opt
     h, w = d.shape
@@ -130,7 +130,7 @@ def _mesh(lib, d, colors, mask, K, opt, cap_v, cap_f, off=0, coef_dev=None):
     xyz, rgb, nrm = _Padded(np.float32, 3 * cap_v, off), _Padded(np.uint8, 3 * cap_v, off), _Padded(np.float32, 3 * cap_v, off)
     index, faces, count = _Padded(np.int32, cap_v, off), _Padded(np.int32, 3 * cap_f, off), _Padded(np.int64, 4, off)
     rc = lib.mg_depth_mesh(dd.ptr(), _ptr(cc), int(hwc), _ptr(mm), _ptr(coef_dev), h, w, *K, Z_RANGE[0], Z_RANGE[1], edge, L.NORMALS_FRAME[frame],
-                           cap_v, cap_f, xyz.ptr(), rgb.ptr(), nrm.ptr(), index.ptr(), faces.ptr(), count.ptr(), ws.ptr(), need, None)
+                           cap_v, cap_f, xyz.ptr(), rgb.ptr(), nrm.ptr(), index.ptr(), faces.ptr(), count.ptr(), ws.ptr(), need, stream)
     assert rc == 0, lib.mg_last_error().decode()
     torch.cuda.synchronize()
     ws.read()

@@ -157,7 +157,7 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _points(lib, d, colors, mask, K, opt, capacity, off=0, coef_dev=None):
+def _points(lib, d, colors, mask, K, opt, capacity, off=0, coef_dev=None, stream=None):
     """one raw mg_depth_points -> dict of the outputs as numpy (whole buffers of ``capacity`` records, canaries past ``written``)"""
     coef, edge, frame, hwc = opt
     h, w = d.shape
@@ -173,7 +173,7 @@ def _points(lib, d, colors, mask, K, opt, capacity, off=0, coef_dev=None):
     xyz, rgb, nrm = _Padded(np.float32, 3 * capacity, off), _Padded(np.uint8, 3 * capacity, off), _Padded(np.float32, 3 * capacity, off)
     index, count = _Padded(np.int32, capacity, off), _Padded(np.int64, 2, off)
     rc = lib.mg_depth_points(dd.ptr(), _ptr(cc), int(hwc), _ptr(mm), _ptr(coef_dev), h, w, *K, Z_RANGE[0], Z_RANGE[1], edge, L.NORMALS_FRAME[frame],
-                             capacity, xyz.ptr(), rgb.ptr(), nrm.ptr(), index.ptr(), count.ptr(), ws.ptr(), need, None)
+                             capacity, xyz.ptr(), rgb.ptr(), nrm.ptr(), index.ptr(), count.ptr(), ws.ptr(), need, stream)
     assert rc == 0, lib.mg_last_error().decode()
     torch.cuda.synchronize()
     ws.read()
@@ -182,14 +182,14 @@ def _points(lib, d, colors, mask, K, opt, capacity, off=0, coef_dev=None):
                 count=count.read())
 
 
-def _normals(lib, d, mask, K, opt, off=0):
+def _normals(lib, d, mask, K, opt, off=0, stream=None):
     coef, edge, frame, _ = opt
     h, w = d.shape
     dd, mm = _Padded(np.float32, h * w, off, d), _dev(mask)
     cf = None if coef is None else _Padded(np.float64, 2, off, coef)
     out, valid = _Padded(np.float32, 3 * h * w, off), _Padded(np.uint8, h * w, off)
     rc = lib.mg_depth_normals(dd.ptr(), _ptr(mm), None if cf is None else cf.ptr(), h, w, *K, Z_RANGE[0], Z_RANGE[1], edge, L.NORMALS_FRAME[frame],
-                              out.ptr(), valid.ptr(), None)
+                              out.ptr(), valid.ptr(), stream)
     assert rc == 0, lib.mg_last_error().decode()
     torch.cuda.synchronize()
     return out.read().reshape(3, h, w), valid.read().reshape(h, w)

@@ -34,7 +34,7 @@ def _lib(f16):
     return L.init(0, f16)
 
 
-def _view(lib, c, off=0, garbage=None, coef_dev=None, face=None):
+def _view(lib, c, off=0, garbage=None, coef_dev=None, face=None, stream=None):
     """one raw mg_depth_view of case ``c`` -> dict of the outputs as numpy (``face`` None where it was not asked for)"""
     coef, edge, hwc = c.opt
     (h, w), (h2, w2) = c.shape, c.size
@@ -53,7 +53,7 @@ def _view(lib, c, off=0, garbage=None, coef_dev=None, face=None):
     pose = None if c.pose is None else np.ascontiguousarray(c.pose, np.float64)
     rc = lib.mg_depth_view(dd.ptr(), cc.ptr(), int(hwc), _ptr(mm), _ptr(coef_dev), h, w, *c.K, Z_RANGE[0], Z_RANGE[1], edge,
                            None if pose is None else pose.ctypes.data, *c.K_out, h2, w2, Z_NEAR, c.fill, rgb.ptr(), depth.ptr(), valid.ptr(),
-                           fmap.ptr() if want_face else None, count.ptr(), ws.ptr(), need, None)
+                           fmap.ptr() if want_face else None, count.ptr(), ws.ptr(), need, stream)
     assert rc == 0, lib.mg_last_error().decode()
     torch.cuda.synchronize()
     ws.read()
